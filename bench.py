@@ -5,7 +5,7 @@ renderer = one integrate pass of `steps`=8 delta-tracking events per pixel + _re
 inputs resident in HBM.  For N > 1 the image plane is sharded into interleaved row blocks (total work fixed =
 strong scaling) and every frame is gathered over RCCL (all_gather, overlapped with the next frame's kernel).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 Prints ONE JSON line on rank 0 (contract in the task description) with `roofline` and `cpu_baseline` objects.
@@ -32,6 +32,7 @@ FAST_MATH_BOUNDS = {"max_abs_d_missing": 1e-6, "min_equal_counts_crossing": 0.97
                     "p999_abs_d_crossing": 1.2e-3, "max_abs_d_crossing": 2e-3}
 # VPT_OPTION_SPLIT_STREAMS as the library sets it by itself (vpt_core.hip default_split): what a run without --split-streams uses
 DEFAULT_SPLIT = {"mcm": 2, "mip": 3, "eam": 3, "iso": 2, "depth": 3, "mcs": 2, "lao": 2}
+DUMP_CAP_BYTES = 60 << 20  # --dump-outputs: at most this many bytes of arrays in all (below 64 MB with the .npy headers)
 
 
 def parse():
@@ -44,8 +45,9 @@ def parse():
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--renderer", default="mcm", choices=["mcm", "mcs", "eam", "mip", "iso", "depth", "lao"])
     ap.add_argument("--extinction", type=float, default=None)
-    ap.add_argument("--repeats", type=int, default=5,
-                    help="the K-step timed block (barrier + synchronize on both sides) is run this many times; the MEDIAN block is reported")
+    ap.add_argument("--repeats", type=int, default=1,
+                    help="the K-step timed block (barrier + synchronize on both sides) is run this many times; the MEDIAN block is reported "
+                         "(default 1: exactly --steps steps are timed); an untimed block of --steps steps, run the same way, goes first")
     ap.add_argument("--warmup-seconds", type=float, default=0.3, help="warm up for at least this long (and at least --warmup steps)")
     ap.add_argument("--other-configs", type=int, default=1,
                     help="N = 1: after the timed region also measure BASELINE.json's other single-GPU configurations (C2 EAM 256^3, C3 MCS 512^3, "
@@ -120,7 +122,36 @@ def parse():
                     help="1 = N ranks on ONE GPU (every rank on device 0) with the collectives over gloo instead of RCCL, which refuses two ranks on one "
                          "device: runs the whole N > 1 control flow of this file (shards of every rank, buckets, frame checks, the forms beside the line) "
                          "where only one GPU exists.  The line says `rehearsal`; its figures are NOT measurements of anything")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the line's path computed in its last step, as the caller receives it (the "
+                         "RGBA16F frame; N > 1: the gathered frame), to DIR/frame.npy in float32 (over %d MB: a fixed seeded sample of "
+                         "its pixels, DIR/frame.npy + DIR/frame_pixels.npy).  The timed steps then start from a restarted accumulation "
+                         "(reset, per-frame draws from the first), so that the same arguments give the same outputs whatever the "
+                         "time-based warm-up ran" % (DUMP_CAP_BYTES >> 20))
     return ap.parse_args()
+
+
+def dump_outputs(outputs, directory, seed=0):
+    """writes each array of `outputs` as <directory>/<name>.npy in float32.  Above DUMP_CAP_BYTES in all, each array keeps its share of
+    the cap as a fixed seeded sample of its pixels (rows of the array flattened to [pixels][channels], sorted pixel order), their flat
+    indices in <name>_pixels.npy (float64: exact)"""
+    os.makedirs(directory, exist_ok=True)
+    import numpy as np
+    arrays = {k: np.asarray(v, dtype=np.float32) for k, v in outputs.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    written = []
+    for name, a in sorted(arrays.items()):
+        if total > DUMP_CAP_BYTES:
+            flat = a.reshape(-1, a.shape[-1]) if a.ndim > 1 else a.reshape(-1, 1)
+            share = DUMP_CAP_BYTES * a.nbytes // total
+            n = min(flat.shape[0], share // (flat.shape[1] * 4 + 8))
+            pick = np.sort(np.random.default_rng(seed).choice(flat.shape[0], n, replace=False))
+            np.save(os.path.join(directory, name + "_pixels.npy"), pick.astype(np.float64))
+            a = flat[pick]
+            written.append(name + "_pixels")
+        np.save(os.path.join(directory, name + ".npy"), a)
+        written.append(name)
+    return written
 
 
 def cpu_baseline(vol, args, matrix, tf):
@@ -418,6 +449,8 @@ def native_preflight(dist, torch, device, rank, world, local_rank, timeout=180):
 
 def main():
     args = parse()
+    if args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)              # a directory that cannot be made fails before the run, not after it
     if args.profile_kernel < 0:
         args.profile_kernel = max(8, args.steps // 2) | 1        # odd: the sampled launches do not sit at the same place of every timed block
         if args.steps % args.profile_kernel == 0:
@@ -835,8 +868,19 @@ def main():
             return bool(ok), {"what": "oracle band rows %d..%d after %d passes; fast-math variant against the contract oracle, per pixel, max over the "
                                       "RGB channels of |radiance difference|" % (y0, y1, frames_done[0]), "measured": stats, "bounds": B}
 
+        def last_outputs():
+            """what a caller of the timed path receives from its last step: the frame (N = 1: the renderer's texture; N > 1: the
+            gathered frame, rank 0), as float32"""
+            if use_native[0]:
+                frame = native.frame() if native.receives() else None
+            elif use_dist:
+                frame = pipe["gather"].last_frame().cpu().numpy()
+            else:
+                frame = r.getTexture()
+            return {} if frame is None else {"frame": frame.astype(np.float32)}
+
         def measure():
-            """W warm-up steps (and >= --warmup-seconds), then --repeats blocks of EXACTLY K timed steps between barriers; the median
+            """W warm-up steps (and >= --warmup-seconds), one untimed block of K steps, then --repeats blocks of EXACTLY K timed steps between barriers; the median
             block, max over ranks; the frame checked (N = 1: oracle band; N > 1: the gathered frame)"""
             res = {"native": use_native[0], "gather_choice": None, "bucket_kernel": bucket_on[0] and not use_native[0]}
             launches0 = r.bucket_launches() if args.renderer == "mcm" else 0
@@ -879,11 +923,23 @@ def main():
                 more -= more % max(1, pipe["gather"].F)
                 if more > 0:
                     run_steps(more); drain(); torch.cuda.synchronize()
-            # R timed blocks of EXACTLY K steps, each bracketed by barrier + synchronize; the MEDIAN block is the one reported
+            if args.dump_outputs:
+                # --dump-outputs: the timed steps start from a restarted accumulation with the per-frame draws from the first, so
+                # that their last step computes the same whatever number of steps the time-based warm-up ran (the frame checks
+                # replay the passes from here)
+                r.rng = GoldenRatioRng()
+                r.reset()
+                frames_done[0] = 0
+                drain()
+                torch.cuda.synchronize()
+            # R timed blocks of EXACTLY K steps, each bracketed by barrier + synchronize; the MEDIAN block is the one reported.  They follow
+            # one untimed block run the same way: the first block after the warm-up ran ~2 % slower than the ones after it on an MI355X
+            # (MCM line, K = 20: 1.645-1.660 ms against 1.61-1.62 ms), which a median of five hid and one timed block would not
             blocks = []
+            nblocks = max(1, args.repeats) + 1
             r.clear_sample_count()
             r.set_profiling(args.profile_kernel)
-            for rep in range(max(1, args.repeats)):
+            for rep in range(nblocks):
                 if use_dist:
                     dist.barrier()
                 torch.cuda.synchronize()
@@ -895,6 +951,9 @@ def main():
                     dist.barrier()
                 torch.cuda.synchronize()
                 blocks.append(time.perf_counter() - t0)
+            if args.dump_outputs and rank == 0:
+                res["outputs"] = last_outputs()
+            blocks = blocks[1:]                                   # (the untimed block)
             tb = torch.tensor(blocks, dtype=torch.float64, device=device)
             if use_dist:
                 dist.all_reduce(tb, op=dist.ReduceOp.MAX)          # per block: the slowest rank
@@ -902,11 +961,11 @@ def main():
             dt = sorted(blocks)[len(blocks) // 2]
             res["dt"] = dt
             res["blocks_ms"] = [b * 1e3 for b in blocks]
-            res["kernel_ms"], res["launches"] = r.profile()           # HIP events over ALL timed blocks, on the kernel's stream
+            res["kernel_ms"], res["launches"] = r.profile()           # HIP events over ALL blocks, on the kernel's stream
             res["side_kernel_ms"], res["side_launches"] = r.profile_side()   # ... and around the sampled passes' launch on the first side stream
             res["tile_classes"] = r.tile_classes()[:2] if (args.renderer == "mcm" and args.tile_classes) else None
             r.set_profiling(False)
-            res["samples_local"] = r.sample_count() / max(1, args.repeats)   # per block (every block runs the same K passes)
+            res["samples_local"] = r.sample_count() / nblocks     # per block (every block runs the same K passes)
             tt = torch.tensor([dt, float(res["samples_local"])], dtype=torch.float64, device=device)
             if use_dist:
                 tsum = tt.clone(); dist.all_reduce(tsum, op=dist.ReduceOp.SUM)
@@ -1189,6 +1248,9 @@ def main():
                 stream_gbs = None
         state["stream_gbs"] = stream_gbs
         line0 = make_line(res) if rank == 0 else None
+        if args.dump_outputs and rank == 0:
+            names = dump_outputs(res.get("outputs") or {}, args.dump_outputs)
+            print("bench.py: --dump-outputs: %s written to %s" % (", ".join(n + ".npy" for n in names) or "nothing", args.dump_outputs), file=sys.stderr)
         matrix = r._matrix()
         other = None
         if rank == 0 and world == 1 and args.other_configs and args.renderer == "mcm":

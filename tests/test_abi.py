@@ -29,10 +29,10 @@ def test_library_exports_every_declared_symbol():
     assert sorted(N.SYMBOLS) == sorted(names)
 
 
-def test_header_is_plain_c():
+def test_header_is_plain_c(tmp_path):
     """the boundary is a C ABI: compiles as C11 with gcc, no C++/torch types"""
     src = '#include "vpt.h"\nint main(void){ vpt_uniforms u; (void)u; return sizeof(vpt_uniforms) == 128 ? 0 : 1; }\n'
-    exe = "/tmp/vpt_abi_check"
+    exe = str(tmp_path / "vpt_abi_check")
     subprocess.run(["gcc", "-std=c11", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-x", "c", "-", "-o", exe],
                    input=src.encode(), check=True)
     assert subprocess.call([exe]) == 0
