@@ -169,8 +169,8 @@ VPT_API int vpt_renderer_render(vpt_renderer *r, const vpt_uniforms *u);
 /* Frame sequences: `count` consecutive render() passes enqueued by ONE call.  `base` holds the uniforms the frames
  * share; frame_vars holds count x 8 floats {rand_seed, offset, mix, 0, light.x, light.y, light.z, 0} — the uniforms
  * that change per frame.  mode VPT_PLAY_EAGER: count launches with the per-frame uniforms in their arguments.
- * VPT_PLAY_GRAPH: the launch sequence is captured once into a hipGraph and replayed (uniforms from a device table read
- * through a device-side frame counter) — where that is the faster form: a captured sequence is whole-image kernels on one stream, so a
+ * VPT_PLAY_GRAPH: the launch sequence is captured once into a hipGraph and replayed (launch i takes its uniforms from entry i
+ * of a device table that each call refills before the replay) — where that is the faster form: a captured sequence is whole-image kernels on one stream, so a
  * renderer whose passes run as tile lists and / or on several streams (the defaults) plays the sequence eagerly instead; set
  * VPT_OPTION_SPLIT_STREAMS 1 and VPT_OPTION_TILE_CLASSES 0 to get the graph.  VPT_PLAY_FUSED (MIP, EAM, MCS, MCM, ISO, Depth; MCM below 8 passes: played eagerly, the faster form there): ONE launch runs all `count` passes
  * of a pixel back to back with the photon state (MCM) or the accumulator (MIP, EAM, MCS, ISO, Depth) in registers — no

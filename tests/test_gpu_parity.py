@@ -706,7 +706,7 @@ def test_play_frame_sequences_equal_render_calls(gpu_ctx, oracle, kind):
         for b in MCM_BUFFERS:
             assert_same_bits(fusedr.read(b), ref.read(b), "mcm fused passes state %d" % b)
         assert fusedr.sample_count() == want_ns
-        fusedr.play(2, use_graph=True); ref.render(); ref.render()          # the graph path's device frame counter stayed in step
+        fusedr.play(2, use_graph=True); ref.render(); ref.render()          # a graph-mode call after fused passes plays the frames it is given
         assert_same_bits(fusedr.read(buf), ref.read(buf), "graph replay after fused passes")
         fusedr.destroy()
     else:
@@ -717,6 +717,70 @@ def test_play_frame_sequences_equal_render_calls(gpu_ctx, oracle, kind):
         fusedr.destroy()
     for r in (ref, eager, graph):
         r.destroy()
+    sc.gvol.destroy()
+
+
+@pytest.mark.parametrize("kind", ["mip", "eam", "mcs", "iso", "depth"])
+def test_fused_play_on_split_streams_equals_render_calls(gpu_ctx, oracle, kind):
+    """VPT_PLAY_FUSED with the default stream counts, where every stream of a split pass reads the frame table.  At 1920x1080 (8160 tiles;
+    1764 HIT tiles under the default camera) split_for (vpt_internal.h) gives min(split, max(1, tiles / per)) streams: MIP, EAM, Depth
+    (split 3, per 192) 3 for the whole image and 3 for the HIT list; ISO, MCS (split 2, per 384) 2 and 2.
+    play(4, fused); play(1, fused); render(); play(4, fused) == 10 x render()"""
+    sc = Scene(gpu_ctx, oracle, 32, 1920, 1080, tf=colour_tf(64, 1))
+
+    def make():
+        r = sc.renderer(kind)
+        if kind == 'mcs':
+            r.extinction = 9
+        r.reset()
+        return r
+
+    ref = make()
+    for _ in range(10):
+        ref.render()
+    fusedr = make()
+    fusedr.play(4, fused=True); fusedr.play(1, fused=True); fusedr.render(); fusedr.play(4, fused=True)
+    assert_same_bits(fusedr.getTexture(), ref.getTexture(), "%s fused passes on split streams" % kind)
+    assert_same_bits(fusedr.read(N.BUFFER_ACCUM), ref.read(N.BUFFER_ACCUM), "%s fused passes on split streams, accumulator" % kind)
+    assert fusedr.sample_count() == ref.sample_count()
+    ref.destroy(); fusedr.destroy()
+    sc.gvol.destroy()
+
+
+def test_long_fused_play_equals_render_calls(gpu_ctx, oracle):
+    """More frames than the frame table's ring holds (2048), by play(n, fused) calls with no readback in between: the ring wraps and its
+    half-ring guard runs while the passes of earlier calls may still read it on the side streams.  MCS at 768x512 under a close camera
+    (1536 tiles, 1093 HIT tiles): split_for gives min(2, 1536 / 384) = 2 streams for the whole image and min(2, 1093 / 384) = 2 for the
+    HIT list.  Both upload forms run (up to 32 entries in kernel arguments, more through the staging ring).  == as many render() calls,
+    and so is the same sequence replayed as hipGraphs on one stream (the graph's own table, refilled by every call)"""
+    sc = Scene(gpu_ctx, oracle, 32, 768, 512, tf=colour_tf(64, 1), camera=orbit_camera(768 / 512, 2.2, 0.4, 1.2))
+    counts = [1, 7, 33, 500] * 4                             # 2164 frames
+
+    def make(one_stream=False):
+        r = sc.renderer('mcs')
+        r.extinction = 9
+        if one_stream:
+            r.set_option(N.OPTION_SPLIT_STREAMS, 1); r.set_option(N.OPTION_TILE_CLASSES, 0)
+        r.reset()
+        return r
+
+    ref = make()
+    for _ in range(sum(counts)):
+        ref.render()
+    fusedr = make()
+    for n in counts:
+        fusedr.play(n, fused=True)
+    assert_same_bits(fusedr.getTexture(), ref.getTexture(), "mcs, %d fused passes" % sum(counts))
+    assert_same_bits(fusedr.read(N.BUFFER_ACCUM), ref.read(N.BUFFER_ACCUM), "mcs, %d fused passes, accumulator" % sum(counts))
+    assert fusedr.sample_count() == ref.sample_count()
+    graph = make(one_stream=True)
+    graph.render()                                           # warm: lazy allocations happen outside the capture
+    for n in counts[1:]:
+        graph.play(n, use_graph=True)
+    assert_same_bits(graph.getTexture(), ref.getTexture(), "mcs, %d frames by graph replays" % sum(counts))
+    assert_same_bits(graph.read(N.BUFFER_ACCUM), ref.read(N.BUFFER_ACCUM), "mcs, %d frames by graph replays, accumulator" % sum(counts))
+    assert graph.sample_count() == ref.sample_count()
+    ref.destroy(); fusedr.destroy(); graph.destroy()
     sc.gvol.destroy()
 
 

@@ -439,7 +439,7 @@ extern "C" int vpt_renderer_create(vpt_context *c, int kind, int width, int heig
     r->samples = nullptr; r->samples_host = 0; r->profiling = false; r->events_used = 0; r->profile_every = 1; r->profile_seq = 0;
     r->side_events_used = 0; r->timed_now = false;
     r->ndc_x = r->ndc_y = nullptr;
-    r->frame_table = nullptr; r->frame_staging = nullptr; r->frame_counter = nullptr; r->frames_played = 0;
+    r->frame_table = nullptr; r->frame_staging = nullptr; r->frames_played = 0;
     r->warmed = false; r->play_graph = nullptr;
     r->fast_math = 0; r->boundary_atlas = 1; r->column_records = 2;
     r->frame_ring = nullptr; r->ring_frames = 0; r->split = default_split(kind); r->split_auto = true; r->target_is_callers = false; r->no_split = false; r->bucket_call = false; r->last_ranges = 1; r->stop_events = nullptr; r->stop_used = false; r->ev_fork = nullptr; for (int i = 0; i < VPT_MAX_SPLIT - 1; i++) { r->side[i] = nullptr; r->ev_join[i] = nullptr; } r->side_busy = false; r->main_dirty = true; r->mcm_persistent = 0; r->work_counter = nullptr; r->mcs_persistent = false;   // measured slower than k_mcs at every extinction tried
@@ -481,7 +481,6 @@ extern "C" int vpt_renderer_destroy(vpt_renderer *r) {
     if (r->frame_ring) hipFree(r->frame_ring);
     if (r->frame_table) hipFree(r->frame_table);
     if (r->frame_staging) hipHostFree(r->frame_staging);
-    if (r->frame_counter) hipFree(r->frame_counter);
     for (int i = 0; i < VPT_MAX_SPLIT - 1; i++) if (r->side[i]) { hipStreamDestroy(r->side[i]); hipEventDestroy(r->ev_join[i]); }
     if (r->ev_fork) hipEventDestroy(r->ev_fork);
     if (r->play_graph) play_graph_free(r->play_graph);

@@ -120,8 +120,8 @@ struct vpt_renderer {
     uint2 *render_target;          // caller-owned redirect of the render buffer (or null)
     uint2 *frame_ring; int ring_frames;   // VPT_PLAY_FRAMES: VPT_FRAME_SLOTS frames of W x local_h RGBA16F (allocated on first use); frames of the last call
     float *ndc_x, *ndc_y;          // pixel-centre NDC tables (W and H entries)
-    FrameVar *frame_table; FrameVar *frame_staging; uint32_t *frame_counter;   // device ring of per-frame uniforms + pinned staging
-    uint64_t frames_played;        // host copy of the monotonic device frame counter
+    FrameVar *frame_table; FrameVar *frame_staging;   // device ring of per-frame uniforms (+ the table of a captured sequence) + pinned staging
+    uint64_t frames_played;        // frames uploaded so far (monotonic): the ring's and the staging ring's cursor
     bool warmed;                   // at least one eager fused render() has run (lazy allocations done)
     struct PlayGraph *play_graph;  // cached hipGraph of a frame sequence
     uint32_t *work_counter;        // tile counter of the persistent MCS kernel
@@ -207,7 +207,6 @@ bool invert_matrix(const float *m, double out[4][4]);               // column-ma
 int classes_build(vpt_renderer *r, const float *mvp_inverse);       // tile lists of `mvp_inverse` on the device (classify_tiles)
 void play_graph_free(PlayGraph *g);                                 // vpt_render.hip
 void tonemappers_unbind(vpt_context *c, vpt_renderer *r);           // vpt_post.hip
-void advance_frames(vpt_renderer *r, uint32_t n);                   // vpt_render.hip: the device frame counter of the graph path += n
 
 // the renderer families behind the entry points of vpt_render.hip
 int march_reset(vpt_renderer *r, const PassArgs &a);                // vpt_march.hip: MIP, EAM, MCS
@@ -238,7 +237,7 @@ struct BucketCall {              // scope of a vpt_renderer_play_into* call (vpt
 };
 // frame sequences (vpt_render.hip)
 int play_args(vpt_renderer *r, const vpt_uniforms *base, int count, PassArgs *a);
-int play_upload_table(vpt_renderer *r, const float *vars, int count, PassArgs *a);
+int play_upload_table(vpt_renderer *r, const float *vars, int count, bool graph, PassArgs *a);
 int check_step(const vpt_uniforms *u);
 static inline PassArgs frame_args(const PassArgs &a, const FrameVar &v) {      // eager frames carry their uniforms in the kernel arguments
     PassArgs f = a;

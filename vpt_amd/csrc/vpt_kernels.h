@@ -156,33 +156,24 @@ struct PassArgs {
     float4 *st0, *st1, *st2, *st3;   // MCM photon state, tile order
     uint2 *render;               // RGBA16F, row-major local rows
     unsigned long long *samples; // volume-sample counter
-    // frame sequences (vpt_renderer_play / hipGraph replay): the per-frame uniforms come from a device table indexed
-    // by a device-side frame counter, so one captured launch sequence serves every replay
-    const struct FrameVar *frame_table;     // ring of frame_mask + 1 entries
-    const uint32_t *frame_counter;          // frames played so far (monotonic); entry = counter & frame_mask
+    // frame sequences (vpt_renderer_play, vpt_gather_play): pass f of a launch takes its per-frame uniforms from entry
+    // (frame_base + f) & frame_mask of a device table, both given by value; null = the uniforms above are the frame's
+    const struct FrameVar *frame_table;     // frame_mask + 1 entries
     // tone mapping fused into the fused passes' frame store (VPT_TONEMAPPER_OPTION_FUSE): the armed tone mapper's byte table
     // (vpt_tonemap.h: 65 536 entries indexed by the half bits of a channel + the constant alpha) with the TmFuse block behind it — the RGBA8
     // output (row-major local rows, like `render`), the mapper's form and Artistic's uniforms; null = no tone mapper armed
     const uint8_t *tm_table;
     uint32_t frame_mask;
-    uint32_t frame_base;                    // fused sequences (multi_passes > 1): index of the sequence's first frame, BY VALUE — a pass split over
-                                            // streams must not read the device counter, which the context's stream advances behind its own range only
+    uint32_t frame_base;
 };
 #define VPT_BUCKET_FRAMES 16     // frames one launch of the bucket kernels holds (vpt_kernels_mcm.h; VPT_OPTION_BUCKET_KERNEL)
 struct FrameVar { float seed, offset, mix, pad0; float lx, ly, lz, pad1; };   // the uniforms that change per frame
-VPT_DEV void apply_frame_table(PassArgs &a) {
-    if (a.frame_table) {
-        FrameVar v = a.frame_table[*a.frame_counter & a.frame_mask];
-        a.seed = v.seed; a.offset = v.offset; a.mix = v.mix;
-        a.light = f3{ v.lx, v.ly, v.lz };
-    }
-}
-// VPT_PLAY_FUSED for the accumulating renderers: pass f of a fused launch takes its per-frame uniforms from the f-th
-// entry of the frame table after the device frame counter, exactly as launch f of the unfused sequence would
+// pass f of a launch (0 for a single pass; f < multi_passes in the fused loops) takes the uniforms of table entry frame_base + f,
+// exactly as launch f of the unfused sequence would
 VPT_DEV uint32_t multi_pass_count(const PassArgs &a) { return a.multi_passes > 1u ? a.multi_passes : 1u; }
-VPT_DEV void multi_pass_select(PassArgs &a, uint32_t base, uint32_t f) {
-    if (a.multi_passes > 1u) {
-        FrameVar v = a.frame_table[(base + f) & a.frame_mask];
+VPT_DEV void frame_select(PassArgs &a, uint32_t f) {
+    if (a.frame_table) {
+        FrameVar v = a.frame_table[(a.frame_base + f) & a.frame_mask];
         a.seed = v.seed; a.offset = v.offset; a.mix = v.mix;
         a.light = f3{ v.lx, v.ly, v.lz };
     }

@@ -75,7 +75,7 @@ VPT_DEV uint2 iso_shade(const PassArgs &a, const LdsTables &t, uint2 closest, ui
 #endif
 template <int MODE, int V>
 __global__ void __launch_bounds__(VPT_BLOCK) __attribute__((amdgpu_waves_per_eu(VPT_ISO_WAVES, 8))) k_iso(PassArgs a) {
-    if (a.multi_passes > 1u) multi_pass_select(a, a.frame_base, 0); else apply_frame_table(a);
+    frame_select(a, 0);
     extern __shared__ float4 lds_raw[];
     LdsTables t = stage_lds<(V & VPT_V_WIDE) != 0>(lds_raw, a);
     Pix p = map_pixel(a.pm);
@@ -90,10 +90,9 @@ __global__ void __launch_bounds__(VPT_BLOCK) __attribute__((amdgpu_waves_per_eu(
             // VPT_PLAY_FUSED: the remaining passes of the sequence; every pass but the last one only leaves its 7 shading
             // samples in the counter (its render buffer is overwritten by the next pass anyway)
             if (a.multi_passes > 1u) {
-                uint32_t base = a.frame_base;
                 for (uint32_t f = 1; f < a.multi_passes; f++) {
                     if (half_hi(m.y) > 0.0f) ns += 7;
-                    multi_pass_select(a, base, f);
+                    frame_select(a, f);
                     m = iso_closer(m, iso_pixel<V>(a, t, p, ns));
                 }
             }
@@ -152,7 +151,7 @@ VPT_DEV float depth_pixel(const PassArgs &a, const LdsTables &t, const Pix &p, u
 }
 template <int MODE, int V>
 __global__ void __launch_bounds__(VPT_BLOCK) VPT_WAVES_ATTR(VPT_DEPTH_WAVES) k_depth(PassArgs a) {
-    apply_frame_table(a);
+    frame_select(a, 0);
     extern __shared__ float4 lds_raw[];
     LdsTables t = stage_lds<(V & VPT_V_WIDE) != 0>(lds_raw, a);
     Pix p = map_pixel(a.pm);
@@ -163,9 +162,8 @@ __global__ void __launch_bounds__(VPT_BLOCK) VPT_WAVES_ATTR(VPT_DEPTH_WAVES) k_d
             frame[p.k] = depth_pixel<V>(a, t, p, ns);
         } else {
             float m = acc[p.k];
-            uint32_t base = a.frame_base;
             for (uint32_t f = 0, np = multi_pass_count(a); f < np; f++) {
-                multi_pass_select(a, base, f);
+                frame_select(a, f);
                 m = mixf(m, depth_pixel<V>(a, t, p, ns), a.mix);     // DepthRenderer.glsl:114-118
             }
             acc[p.k] = m;

@@ -49,7 +49,7 @@ VPT_DEV uint32_t mip_pixel(const PassArgs &a, const LdsTables &t, const Pix &p, 
 // (MIPRenderer.glsl:105-109, max on unorm8), renderFrame (:141-144) in one pass.
 template <int MODE, int V>
 __global__ void __launch_bounds__(VPT_BLOCK) VPT_WAVES_ATTR(VPT_MIP_WAVES) k_mip(PassArgs a) {
-    apply_frame_table(a);
+    frame_select(a, 0);
     extern __shared__ float4 lds_raw[];
     LdsTables t = stage_lds<(V & VPT_V_WIDE) != 0>(lds_raw, a);
     Pix p = map_pixel(a.pm);
@@ -59,9 +59,9 @@ __global__ void __launch_bounds__(VPT_BLOCK) VPT_WAVES_ATTR(VPT_MIP_WAVES) k_mip
         if (MODE == 0) {
             frame[p.k] = (uint8_t)mip_pixel<V>(a, t, p, ns);
         } else {
-            uint32_t m = acc[p.k], base = a.frame_base;
+            uint32_t m = acc[p.k];
             for (uint32_t f = 0, np = multi_pass_count(a); f < np; f++) {
-                multi_pass_select(a, base, f);
+                frame_select(a, f);
                 m = max(m, mip_pixel<V>(a, t, p, ns));
             }
             acc[p.k] = (uint8_t)m;
@@ -148,7 +148,7 @@ VPT_DEV uint32_t eam_mix(uint32_t acc, uint32_t frame, float m) {
 }
 template <int MODE, int V>
 __global__ void __launch_bounds__(VPT_BLOCK) VPT_WAVES_ATTR(VPT_EAM_WAVES) k_eam(PassArgs a) {
-    apply_frame_table(a);
+    frame_select(a, 0);
     extern __shared__ float4 lds_raw[];
     LdsTables t = stage_lds<(V & VPT_V_WIDE) != 0>(lds_raw, a);
     Pix p = map_pixel(a.pm);
@@ -158,9 +158,9 @@ __global__ void __launch_bounds__(VPT_BLOCK) VPT_WAVES_ATTR(VPT_EAM_WAVES) k_eam
         if (MODE == 0) {
             frame[p.k] = eam_pixel<V>(a, t, p, ns);
         } else {
-            uint32_t m = acc[p.k], base = a.frame_base;
+            uint32_t m = acc[p.k];
             for (uint32_t f = 0, np = multi_pass_count(a); f < np; f++) {
-                multi_pass_select(a, base, f);
+                frame_select(a, f);
                 m = eam_mix(m, eam_pixel<V>(a, t, p, ns), a.mix);
             }
             acc[p.k] = m;
@@ -253,7 +253,7 @@ VPT_DEV float4 mcs_mix(float4 acc, float4 frame, float inv) {   // MCSRenderer.g
 }
 template <int MODE, int V>
 __global__ void __launch_bounds__(VPT_BLOCK) VPT_WAVES_ATTR(VPT_MCS_WAVES) k_mcs(PassArgs a) {
-    apply_frame_table(a);
+    frame_select(a, 0);
     extern __shared__ float4 lds_raw[];
     LdsTables t = stage_lds<(V & VPT_V_WIDE) != 0>(lds_raw, a);
     Pix p = map_pixel(a.pm);
@@ -264,9 +264,8 @@ __global__ void __launch_bounds__(VPT_BLOCK) VPT_WAVES_ATTR(VPT_MCS_WAVES) k_mcs
             frame[p.k] = mcs_pixel<V>(a, t, p, ns);
         } else {
             float4 m = acc[p.k];
-            uint32_t base = a.frame_base;
             for (uint32_t f = 0, np = multi_pass_count(a); f < np; f++) {
-                multi_pass_select(a, base, f);
+                frame_select(a, f);
                 m = mcs_mix(m, mcs_pixel<V>(a, t, p, ns), a.mix);
             }
             acc[p.k] = m;

@@ -521,7 +521,7 @@ __global__ void __launch_bounds__(VPT_BLOCK) __attribute__((amdgpu_waves_per_eu(
 #ifdef VPT_EVENT_TIMING
     EventClock evc; ev_start(evc);
 #endif
-    apply_frame_table(a);
+    frame_select(a, 0);
     // the photon state (4 x dwordx4 per lane, one contiguous 1 KiB segment per wave and array) does not depend on the LDS
     // image: its loads are issued first, so they fly while the workgroup stages the tables and hashes its seed
     Pix p = map_pixel(a.pm);
@@ -545,7 +545,7 @@ __global__ void __launch_bounds__(VPT_BLOCK) __attribute__((amdgpu_waves_per_eu(
 // short enough to be resident at once at that occupancy (shards)
 template <bool FUSE_RENDER, int V>
 __global__ void __launch_bounds__(VPT_BLOCK) __attribute__((amdgpu_waves_per_eu(5, 8))) k_mcm_integrate_early(PassArgs a) {
-    apply_frame_table(a);
+    frame_select(a, 0);
     Pix p = map_pixel(a.pm);
     PhotonState st;
     if (p.tile) st = photon_load(a, p.k);
@@ -660,7 +660,7 @@ VPT_DEV void mcm_events_miss_fast(const PassArgs &a, const float4 *tf, const Fas
 template <bool FUSE_RENDER, int V, bool CHECK, bool LATE>
 __global__ void __launch_bounds__(VPT_BLOCK)
 __attribute__((amdgpu_waves_per_eu(((V & (VPT_V_NEAREST | VPT_V_RG | VPT_V_F32)) && !(V & VPT_V_FAST)) ? 7 : 8, 8))) k_mcm_miss(PassArgs a) {
-    apply_frame_table(a);
+    frame_select(a, 0);
     Pix p = map_pixel(a.pm);
     float4 s1 = make_float4(0.0f, 0.0f, 1.0f, 0.0f), s3 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     f3 s0 = { 0.0f, 0.0f, 0.0f };
@@ -720,9 +720,8 @@ VPT_DEV void mcm_multi_body(PassArgs &a, uint32_t npasses, uint2 *ring, uint32_t
     if (!p.valid) return;
     float px = ndc_col(a.pm, p.i), py = ndc_row(a.pm, p.j);
     Photon ph = photon_unpack(photon_load(a, p.k));
-    uint32_t base = a.frame_base;
     for (uint32_t f = 0; f < npasses; f++) {
-        a.seed = a.frame_table[(base + f) & a.frame_mask].seed;
+        a.seed = a.frame_table[(a.frame_base + f) & a.frame_mask].seed;
         EV_LOCAL
         if (V & VPT_V_FAST) mcm_events_fast<V & ~VPT_V_FAST>(a, t, ph, px, py EV_ARG);
         else mcm_events<V>(a, t, ph, px, py EV_ARG);

@@ -592,7 +592,6 @@ static int gather_enqueue_frame(vpt_gather *g, PassArgs &a, hipEvent_t t0 = null
     if (t0) HIP_TRY(hipEventRecord(t0, cs));
     if (fused_passes) {
         VPT_TRY(mcm_multi(r, a, fused_passes, nullptr));
-        advance_frames(r, fused_passes);
     } else {
         VPT_TRY(launch_fused(r, a));
     }
@@ -643,7 +642,7 @@ extern "C" int vpt_gather_play(vpt_gather *g, const vpt_uniforms *base, const fl
     if (mode == VPT_PLAY_FUSED) {
         // `count` passes in one launch, then ONE gather of the resulting frame
         if (r->kind != VPT_RENDERER_MCM) return fail(VPT_ERR_UNSUPPORTED, "fused passes are implemented for the MCM renderer only");
-        VPT_TRY(play_upload_table(r, frame_vars, count, &a));
+        VPT_TRY(play_upload_table(r, frame_vars, count, false, &a));
         hipEvent_t t0 = nullptr, t1 = nullptr;
         profile_events(r, &t0, &t1);
         if (t0) r->event_launches[r->events_used - 1] = (uint32_t)count;

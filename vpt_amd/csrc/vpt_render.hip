@@ -3,12 +3,6 @@
 // launched by the family units (vpt_mcm.hip, vpt_march.hip, vpt_extra.hip).
 #include "vpt_internal.h"
 
-__global__ void k_advance_frame(uint32_t *counter) { *counter = *counter + 1u; }
-__global__ void k_advance_frames(uint32_t *counter, uint32_t n) { *counter = *counter + n; }
-void advance_frames(vpt_renderer *r, uint32_t n) {
-    hipLaunchKernelGGL(k_advance_frames, dim3(1), dim3(1), 0, r->ctx->stream, r->frame_counter, n);
-}
-
 // The accumulating ray marchers (MIP, EAM, ISO; MCS and Depth under a condition).  A pixel whose ray misses the cube contributes a
 // constant frame value — MIP 0 (MIPRenderer.glsl:57-59), EAM (0,0,0,1) (EAMRenderer.glsl:58-60), ISO "no hit" (ISORenderer.glsl:58-61),
 // Depth -1, MCS the environment along the ray (MCSRenderer.glsl:113-116) — and its accumulator sits at a fixed point of the
@@ -172,8 +166,7 @@ extern "C" int vpt_renderer_render(vpt_renderer *r, const vpt_uniforms *u) {
 // ---------------------------------------------------------------------------------------------
 struct PlayGraph {
     hipGraph_t graph; hipGraphExec_t exec;
-    int count; bool with_gather; PassArgs key;
-    bool ran;
+    int count; PassArgs key;
 };
 void play_graph_free(PlayGraph *g) {
     if (!g) return;
@@ -181,9 +174,9 @@ void play_graph_free(PlayGraph *g) {
     if (g->graph) hipGraphDestroy(g->graph);
     delete g;
 }
-// Appends the per-frame uniforms of the next `count` frames to the device ring (through a pinned staging ring, so the
-// copy is asynchronous and the host never waits) and returns the PassArgs shared by the frames.  The device frame
-// counter is monotonic: a captured graph needs no per-replay patching.
+// The per-frame uniforms of a sequence reach its kernels through a device table: pass f of a launch reads entry frame_base + f, both given
+// by value.  Sequences played eagerly or by fused launches append their entries to a ring of VPT_FRAME_RING; a captured sequence reads the
+// VPT_FRAME_RING / 4 entries behind the ring, launch i entry i, so one capture serves every replay.
 #define VPT_FRAME_RING 2048
 int play_args(vpt_renderer *r, const vpt_uniforms *base, int count, PassArgs *a) {
     if (count < 1 || count > VPT_FRAME_RING / 4) return fail(VPT_ERR_INVALID, "frame count %d out of range [1, %d]", count, VPT_FRAME_RING / 4);
@@ -196,147 +189,158 @@ __global__ void k_store_frame_vars(FrameVar *table, FrameVarBlock blk, uint32_t 
     const uint32_t t = threadIdx.x;
     if (t < count) table[(pos + t) & mask] = blk.v[t];
 }
-int play_upload_table(vpt_renderer *r, const float *vars, int count, PassArgs *a) {
+// Uploads the `count` entries of a sequence on the context's stream (asynchronously: the host never waits) — to the ring at its cursor, or
+// for a captured sequence (graph) to the first `count` entries of its table — and points `a` at them.
+int play_upload_table(vpt_renderer *r, const float *vars, int count, bool graph, PassArgs *a) {
     vpt_context *c = r->ctx;
     static_assert(sizeof(FrameVar) == 8 * sizeof(float), "FrameVar is 8 floats");
     if (!r->frame_table) {
-        HIP_TRY(hipMalloc(&r->frame_table, (size_t)VPT_FRAME_RING * sizeof(FrameVar)));
+        HIP_TRY(hipMalloc(&r->frame_table, (size_t)(VPT_FRAME_RING + VPT_FRAME_RING / 4) * sizeof(FrameVar)));
         HIP_TRY(hipHostMalloc((void **)&r->frame_staging, (size_t)VPT_FRAME_RING * sizeof(FrameVar), hipHostMallocDefault));
-        HIP_TRY(hipMalloc(&r->frame_counter, sizeof(uint32_t)));
-        HIP_TRY(hipMemsetAsync(r->frame_counter, 0, sizeof(uint32_t), c->stream));
         r->frames_played = 0;
     }
-    // a staging slot is reused VPT_FRAME_RING frames later: never let more than half a ring be in flight
-    if ((r->frames_played % (VPT_FRAME_RING / 2)) + (uint64_t)count > VPT_FRAME_RING / 2) HIP_TRY(hipStreamSynchronize(c->stream));
+    // a staging slot (and a ring entry) is reused VPT_FRAME_RING frames later: never let more than half a ring be in flight on any stream
+    if ((r->frames_played % (VPT_FRAME_RING / 2)) + (uint64_t)count > VPT_FRAME_RING / 2) {
+        VPT_TRY(join_side(r));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
     const FrameVar *src = (const FrameVar *)vars;
-    int pos = (int)(r->frames_played % VPT_FRAME_RING);
+    const uint32_t cursor = (uint32_t)(r->frames_played % VPT_FRAME_RING);
+    FrameVar *table = graph ? r->frame_table + VPT_FRAME_RING : r->frame_table;
+    const uint32_t pos = graph ? 0u : cursor, mask = graph ? VPT_FRAME_RING / 4 - 1 : VPT_FRAME_RING - 1;
     if (count <= VPT_TABLE_BY_ARGS) {
         // short sequences: the entries travel in the arguments of a one-wave kernel (a copy engine's H2D transfer in the middle of the stream
         // costs the sequence 10-20 us of idle chip; measured per play() call of 4 / 16 frames)
         FrameVarBlock blk;
         memcpy(blk.v, src, (size_t)count * sizeof(FrameVar));
-        hipLaunchKernelGGL(k_store_frame_vars, dim3(1), dim3(64), 0, c->stream, r->frame_table, blk, (uint32_t)pos, (uint32_t)count, (uint32_t)(VPT_FRAME_RING - 1));
+        hipLaunchKernelGGL(k_store_frame_vars, dim3(1), dim3(64), 0, c->stream, table, blk, pos, (uint32_t)count, mask);
     } else {
-        int first = count < VPT_FRAME_RING - pos ? count : VPT_FRAME_RING - pos;
-        memcpy(r->frame_staging + pos, src, (size_t)first * sizeof(FrameVar));
-        HIP_TRY(hipMemcpyAsync(r->frame_table + pos, r->frame_staging + pos, (size_t)first * sizeof(FrameVar), hipMemcpyHostToDevice, c->stream));
-        if (first < count) {
-            memcpy(r->frame_staging, src + first, (size_t)(count - first) * sizeof(FrameVar));
-            HIP_TRY(hipMemcpyAsync(r->frame_table, r->frame_staging, (size_t)(count - first) * sizeof(FrameVar), hipMemcpyHostToDevice, c->stream));
+        // through the pinned staging ring at the cursor, in pieces that wrap neither the staging ring nor the table
+        for (int done = 0; done < count;) {
+            const uint32_t s = (cursor + (uint32_t)done) % VPT_FRAME_RING, d = (pos + (uint32_t)done) & mask;
+            const int n = std::min(count - done, (int)std::min(VPT_FRAME_RING - s, mask + 1 - d));
+            memcpy(r->frame_staging + s, src + done, (size_t)n * sizeof(FrameVar));
+            HIP_TRY(hipMemcpyAsync(table + d, r->frame_staging + s, (size_t)n * sizeof(FrameVar), hipMemcpyHostToDevice, c->stream));
+            done += n;
         }
     }
     r->main_dirty = true;                             // the side streams of a split pass read the table too: they fork behind this upload
-    a->frame_base = (uint32_t)r->frames_played;       // == the device counter when the sequence starts (both advance by `count` per sequence)
     r->frames_played += (uint64_t)count;
-    a->frame_table = r->frame_table;
-    a->frame_counter = r->frame_counter;
-    a->frame_mask = VPT_FRAME_RING - 1;
+    a->frame_table = table;
+    a->frame_base = pos;
+    a->frame_mask = mask;
     return VPT_OK;
 }
 static bool play_key_equal(const PassArgs &x, const PassArgs &y) { return memcmp(&x, &y, sizeof(PassArgs)) == 0; }
 
-extern "C" int vpt_renderer_play(vpt_renderer *r, const vpt_uniforms *base, const float *frame_vars, int count, int use_graph) {
-    if (!r || !base || !frame_vars) return fail(VPT_ERR_INVALID, "null argument");
-    if (r->kind == VPT_RENDERER_DOS) return fail(VPT_ERR_UNSUPPORTED, "frame sequences are not defined for the DOS renderer: drive it slice by slice");
-    vpt_context *c = r->ctx;
-    HIP_TRY(hipSetDevice(c->device));
-    PassArgs a;
-    VPT_TRY(play_args(r, base, count, &a));
+// The form a sequence is played in: `mode` as asked, or VPT_PLAY_EAGER where that is the faster form of the same sequence.
+static int play_form(const vpt_renderer *r, int mode, int count) {
+    const bool split = r->split > 1 && !r->target_is_callers;
     // A captured sequence lives on the capturing stream alone and freezes its grids: whole-image kernels on one stream.  Where the eager
     // passes run as tile lists and / or on several streams (the defaults), they are the faster form — 1080p, us per frame, eager | graph:
     // MCM 94 | 123, EAM 52 | 87, MIP 48 | 77, MCS 15 | 38, ISO 45 | 72, Depth 52 | 75 — and VPT_PLAY_GRAPH asks for the faster form of the
     // same sequence, not for a hipGraph at any price: the graph is kept for renderers set to one stream without tile classes, where the
-    // launches are the same and one replay saves the host count - 1 enqueues.
-    if (use_graph == VPT_PLAY_GRAPH && (r->cls.enabled || (r->split > 1 && !r->target_is_callers))) use_graph = VPT_PLAY_EAGER;
+    // launches are the same and one replay saves the host count - 1 enqueues.  (Before the first render() the lazy allocations are not
+    // done: the capture waits for a warmed renderer.)
+    if (mode == VPT_PLAY_GRAPH && (r->cls.enabled || split || !r->warmed)) return VPT_PLAY_EAGER;
     // MCM's passes-in-registers kernel is a whole-image launch on one stream: it beats the tile-class passes on two streams from 8 passes per
     // launch on (1080p, us per pass, bit-exact | fast-math: loop 93.0 | 78.7; 2 per launch 109.1 | 100.7, 4: 97.1 | 84.6, 8: 92.5 | 75.1, 16: 90.9 | 70.2)
-    if (use_graph == VPT_PLAY_FUSED && r->kind == VPT_RENDERER_MCM && count < 8 && r->cls.enabled && r->split > 1 && !r->target_is_callers) use_graph = VPT_PLAY_EAGER;
-    // (eager sequences and the marchers' fused passes are launched exactly as render() launches them: the streams of a split pass are not
-    // joined between two calls any more than between two render() calls; a captured graph and MCM's whole-image sequence kernels join)
-    if (use_graph == VPT_PLAY_GRAPH || ((use_graph == VPT_PLAY_FUSED || use_graph == VPT_PLAY_FRAMES) && r->kind == VPT_RENDERER_MCM)) VPT_TRY(join_side(r));
-    if (use_graph == VPT_PLAY_GRAPH && r->warmed) {
-        VPT_TRY(play_upload_table(r, frame_vars, count, &a));
-        // a captured sequence runs whole-image kernels (a graph freezes its grids; tile lists change with every reset)
-        if (r->kind == VPT_RENDERER_MCM) { VPT_TRY(mcm_before_pass(r, a, nullptr)); VPT_TRY(mcm_materialize(r)); }
-        const float first_mix = ((const FrameVar *)frame_vars)[0].mix;
-        a.frame_base = 0;                                   // (replays index the table by the device counter; the graph's key must not move)
-        PlayGraph *g = r->play_graph;
-        if (!g || g->with_gather || g->count != count || !play_key_equal(g->key, a)) {
-            if (g) { HIP_TRY(hipStreamSynchronize(c->stream)); play_graph_free(g); r->play_graph = nullptr; }
-            g = new PlayGraph(); memset(g, 0, sizeof(*g));
-            g->count = count; g->with_gather = false; g->key = a;
-            HIP_TRY(hipStreamBeginCapture(c->stream, hipStreamCaptureModeRelaxed));
-            int rc = VPT_OK;
-            r->no_split = true;                       // a captured sequence lives on the capturing stream alone
-            for (int i = 0; i < count && rc == VPT_OK; i++) {
-                PassArgs f = a;
-                if (i == 0) f.mix = first_mix;                // (per-frame uniforms come from the table; marcher_track wants the first pass's mix)
-                rc = launch_fused(r, f);
-                hipLaunchKernelGGL(k_advance_frame, dim3(1), dim3(1), 0, c->stream, r->frame_counter);
-            }
-            r->no_split = false;
-            hipError_t e = hipStreamEndCapture(c->stream, &g->graph);
-            if (rc == VPT_OK && e != hipSuccess) rc = fail(VPT_ERR_HIP, "hipStreamEndCapture: %s", hipGetErrorString(e));
-            if (rc == VPT_OK) { e = hipGraphInstantiate(&g->exec, g->graph, nullptr, nullptr, 0); if (e != hipSuccess) rc = fail(VPT_ERR_HIP, "hipGraphInstantiate: %s", hipGetErrorString(e)); }
-            if (rc != VPT_OK) { play_graph_free(g); return rc; }
-            r->play_graph = g;
-        }
-        else {
-            // a cached graph is replayed without passing through launch_fused: the marchers' pass tracking is told by hand
-            for (int i = 0; i < count; i++) VPT_TRY(marcher_track(r, a, true, ((const FrameVar *)frame_vars)[i].mix));
-            r->cls.list_now = false;
-        }
-        {
-            Timed t(r, true, (uint32_t)count);       // a replay is timed as a whole: events inside a graph cannot be read back
-            HIP_TRY(hipGraphLaunch(g->exec, c->stream));
-        }
-        g->ran = true; r->tm_valid = false;
-    } else if (use_graph == VPT_PLAY_FRAMES && r->kind != VPT_RENDERER_MCM) {
-        return fail(VPT_ERR_UNSUPPORTED, "VPT_PLAY_FRAMES is implemented for the MCM renderer");
-    } else if (use_graph == VPT_PLAY_FUSED && r->kind != VPT_RENDERER_MCM) {
-        // the accumulating renderers: the pass loop lives in their fused kernels (PassArgs.multi_passes)
-        if (r->kind == VPT_RENDERER_LAO) return fail(VPT_ERR_UNSUPPORTED, "fused passes are pointless for the LAO renderer: its frames do not accumulate");
-        VPT_TRY(play_upload_table(r, frame_vars, count, &a));
-        a.multi_passes = (uint32_t)count;
-        a.mix = ((const FrameVar *)frame_vars)[0].mix;      // (the kernels take every pass's uniforms from the table; marcher_track wants the first pass's)
-        {
-            Timed t(r, true, (uint32_t)count);
-            VPT_TRY(launch_fused(r, a));
-        }
-        advance_frames(r, (uint32_t)count);
-        HIP_TRY(hipGetLastError());
-        r->warmed = true;
-    } else if (use_graph == VPT_PLAY_FUSED || use_graph == VPT_PLAY_FRAMES) {
-        uint2 *ring = nullptr;
-        if (use_graph == VPT_PLAY_FRAMES) {
-            if (count > VPT_FRAME_SLOTS) return fail(VPT_ERR_INVALID, "VPT_PLAY_FRAMES: %d frames, the ring holds %d", count, VPT_FRAME_SLOTS);
-            if (!r->frame_ring) {
-                const size_t bytes = (size_t)VPT_FRAME_SLOTS * r->W * r->local_h * 8;
-                HIP_TRY(hipMalloc(&r->frame_ring, bytes));
-                HIP_TRY(hipMemsetAsync(r->frame_ring, 0, bytes, c->stream));   // a shard's padding rows are never written: zero, as in the render buffer
-            }
-            ring = r->frame_ring; r->ring_frames = count;
-        }
-        VPT_TRY(play_upload_table(r, frame_vars, count, &a));
-        bool by_class = false;                           // VPT_PLAY_FRAMES where the tile classes are in force: the bucket kernels, one launch per class
-        if (ring && count <= VPT_BUCKET_FRAMES) VPT_TRY(mcm_bucket_ready(r, a, &by_class));
-        {
-            Timed t(r, true, (uint32_t)count);
-            if (by_class) VPT_TRY(mcm_bucket(r, a, (const FrameVar *)frame_vars, count, ring, (uint32_t)((size_t)r->W * r->local_h), true, nullptr));
-            else VPT_TRY(mcm_multi(r, a, (uint32_t)count, ring));
-        }
-        advance_frames(r, (uint32_t)count);   // keeps the graph path's counter in step
-        HIP_TRY(hipGetLastError());
-        r->warmed = true;
-    } else {
-        const FrameVar *v = (const FrameVar *)frame_vars;
-        for (int i = 0; i < count; i++) {
-            Timed t(r, true);
-            VPT_TRY(launch_fused(r, frame_args(a, v[i])));
-        }
-        HIP_TRY(hipGetLastError());
-        r->warmed = true;
+    if (mode == VPT_PLAY_FUSED && r->kind == VPT_RENDERER_MCM && count < 8 && r->cls.enabled && split) return VPT_PLAY_EAGER;
+    return mode == VPT_PLAY_GRAPH || mode == VPT_PLAY_FUSED || mode == VPT_PLAY_FRAMES ? mode : VPT_PLAY_EAGER;
+}
+// (eager sequences and the marchers' fused passes are launched exactly as render() launches them: the streams of a split pass are not
+// joined between two calls any more than between two render() calls; a captured graph and MCM's whole-image sequence kernels join)
+static int play_eager(vpt_renderer *r, const PassArgs &a, const FrameVar *v, int count) {
+    for (int i = 0; i < count; i++) {
+        Timed t(r, true);
+        VPT_TRY(launch_fused(r, frame_args(a, v[i])));
     }
+    return VPT_OK;
+}
+static int play_graph(vpt_renderer *r, PassArgs &a, const float *frame_vars, int count) {
+    vpt_context *c = r->ctx;
+    const FrameVar *v = (const FrameVar *)frame_vars;
+    VPT_TRY(join_side(r));
+    VPT_TRY(play_upload_table(r, frame_vars, count, true, &a));
+    // a captured sequence runs whole-image kernels (a graph freezes its grids; tile lists change with every reset)
+    if (r->kind == VPT_RENDERER_MCM) { VPT_TRY(mcm_before_pass(r, a, nullptr)); VPT_TRY(mcm_materialize(r)); }
+    PlayGraph *g = r->play_graph;
+    if (!g || g->count != count || !play_key_equal(g->key, a)) {
+        if (g) { HIP_TRY(hipStreamSynchronize(c->stream)); play_graph_free(g); r->play_graph = nullptr; }
+        g = new PlayGraph(); memset(g, 0, sizeof(*g));
+        g->count = count; g->key = a;
+        HIP_TRY(hipStreamBeginCapture(c->stream, hipStreamCaptureModeRelaxed));
+        int rc = VPT_OK;
+        r->no_split = true;                       // a captured sequence lives on the capturing stream alone
+        for (int i = 0; i < count && rc == VPT_OK; i++) {
+            PassArgs f = a;
+            f.frame_base = (uint32_t)i;
+            if (i == 0) f.mix = v[0].mix;                 // (per-frame uniforms come from the table; marcher_track wants the first pass's mix)
+            rc = launch_fused(r, f);
+        }
+        r->no_split = false;
+        hipError_t e = hipStreamEndCapture(c->stream, &g->graph);
+        if (rc == VPT_OK && e != hipSuccess) rc = fail(VPT_ERR_HIP, "hipStreamEndCapture: %s", hipGetErrorString(e));
+        if (rc == VPT_OK) { e = hipGraphInstantiate(&g->exec, g->graph, nullptr, nullptr, 0); if (e != hipSuccess) rc = fail(VPT_ERR_HIP, "hipGraphInstantiate: %s", hipGetErrorString(e)); }
+        if (rc != VPT_OK) { play_graph_free(g); return rc; }
+        r->play_graph = g;
+    } else {
+        // a cached graph is replayed without passing through launch_fused: the marchers' pass tracking is told by hand
+        for (int i = 0; i < count; i++) VPT_TRY(marcher_track(r, a, true, v[i].mix));
+        r->cls.list_now = false;
+    }
+    {
+        Timed t(r, true, (uint32_t)count);       // a replay is timed as a whole: events inside a graph cannot be read back
+        HIP_TRY(hipGraphLaunch(g->exec, c->stream));
+    }
+    r->tm_valid = false;
+    return VPT_OK;
+}
+// the accumulating renderers: the pass loop lives in their fused kernels (PassArgs.multi_passes)
+static int play_fused_marchers(vpt_renderer *r, PassArgs &a, const float *frame_vars, int count) {
+    if (r->kind == VPT_RENDERER_LAO) return fail(VPT_ERR_UNSUPPORTED, "fused passes are pointless for the LAO renderer: its frames do not accumulate");
+    VPT_TRY(play_upload_table(r, frame_vars, count, false, &a));
+    a.multi_passes = (uint32_t)count;
+    a.mix = ((const FrameVar *)frame_vars)[0].mix;      // (the kernels take every pass's uniforms from the table; marcher_track wants the first pass's)
+    Timed t(r, true, (uint32_t)count);
+    return launch_fused(r, a);
+}
+// MCM's fused passes: the passes-in-registers kernel, or with VPT_PLAY_FRAMES every frame written to the frame ring
+static int play_mcm_multi(vpt_renderer *r, PassArgs &a, const float *frame_vars, int count, bool frames) {
+    vpt_context *c = r->ctx;
+    VPT_TRY(join_side(r));
+    uint2 *ring = nullptr;
+    if (frames) {
+        if (count > VPT_FRAME_SLOTS) return fail(VPT_ERR_INVALID, "VPT_PLAY_FRAMES: %d frames, the ring holds %d", count, VPT_FRAME_SLOTS);
+        if (!r->frame_ring) {
+            const size_t bytes = (size_t)VPT_FRAME_SLOTS * r->W * r->local_h * 8;
+            HIP_TRY(hipMalloc(&r->frame_ring, bytes));
+            HIP_TRY(hipMemsetAsync(r->frame_ring, 0, bytes, c->stream));   // a shard's padding rows are never written: zero, as in the render buffer
+        }
+        ring = r->frame_ring; r->ring_frames = count;
+    }
+    VPT_TRY(play_upload_table(r, frame_vars, count, false, &a));
+    bool by_class = false;                           // VPT_PLAY_FRAMES where the tile classes are in force: the bucket kernels, one launch per class
+    if (ring && count <= VPT_BUCKET_FRAMES) VPT_TRY(mcm_bucket_ready(r, a, &by_class));
+    Timed t(r, true, (uint32_t)count);
+    if (by_class) return mcm_bucket(r, a, (const FrameVar *)frame_vars, count, ring, (uint32_t)((size_t)r->W * r->local_h), true, nullptr);
+    return mcm_multi(r, a, (uint32_t)count, ring);
+}
+
+extern "C" int vpt_renderer_play(vpt_renderer *r, const vpt_uniforms *base, const float *frame_vars, int count, int use_graph) {
+    if (!r || !base || !frame_vars) return fail(VPT_ERR_INVALID, "null argument");
+    if (r->kind == VPT_RENDERER_DOS) return fail(VPT_ERR_UNSUPPORTED, "frame sequences are not defined for the DOS renderer: drive it slice by slice");
+    HIP_TRY(hipSetDevice(r->ctx->device));
+    PassArgs a;
+    VPT_TRY(play_args(r, base, count, &a));
+    const int mode = play_form(r, use_graph, count);
+    if (mode == VPT_PLAY_FRAMES && r->kind != VPT_RENDERER_MCM) return fail(VPT_ERR_UNSUPPORTED, "VPT_PLAY_FRAMES is implemented for the MCM renderer");
+    if (mode == VPT_PLAY_GRAPH) VPT_TRY(play_graph(r, a, frame_vars, count));
+    else if (mode == VPT_PLAY_EAGER) VPT_TRY(play_eager(r, a, (const FrameVar *)frame_vars, count));
+    else if (r->kind == VPT_RENDERER_MCM) VPT_TRY(play_mcm_multi(r, a, frame_vars, count, mode == VPT_PLAY_FRAMES));
+    else VPT_TRY(play_fused_marchers(r, a, frame_vars, count));
+    HIP_TRY(hipGetLastError());
+    r->warmed = true;
     if (r->kind == VPT_RENDERER_MCM) r->samples_host += r->valid_pixels * (uint64_t)base->steps * (uint64_t)count;
     return VPT_OK;
 }
