@@ -418,13 +418,15 @@ def _frame_ring(r):
 
 
 @pytest.mark.parametrize("fast", [0, 1])
-@pytest.mark.parametrize("shard,form", [(None, 0), ((1, 3, 8), 0), (None, 1)])
-def test_bucket_kernel_equals_frame_by_frame(gpu_ctx, oracle, fast, shard, form):
+@pytest.mark.parametrize("shard,form,split", [pytest.param(None, 0, None, id="None-0"), pytest.param((1, 3, 8), 0, None, id="shard1-0"),
+                                               pytest.param(None, 1, None, id="None-1"), pytest.param(None, 0, 3, id="None-0-split3")])
+def test_bucket_kernel_equals_frame_by_frame(gpu_ctx, oracle, fast, shard, form, split):
     """VPT_OPTION_BUCKET_KERNEL: vpt_renderer_play_into runs its frames by one launch per tile class (k_mcm_bucket_hit | k_mcm_bucket_miss,
     seeds by value, state in registers).  Every frame of every bucket, all four state buffers and the sample count identical to the
     frame-by-frame form; buckets of 1, 7 and 16 frames and one of 21 (two launches), render() calls in between, a camera that moves
     without a reset (the classes are void: frame by frame from there on) and a second reset.  The renderer's own frame ring stands in
-    for the caller's bucket memory."""
+    for the caller's bucket memory.  split = 3: the frame-by-frame passes deal the tiles to three streams (HIT | MISS/2 | MISS/2), the
+    bucket kernels to two."""
     env = env_map(16, 8)
 
     def run(bucket):
@@ -432,6 +434,8 @@ def test_bucket_kernel_equals_frame_by_frame(gpu_ctx, oracle, fast, shard, form)
         r = mcm_with_form(sc, form, shard=shard) if shard else mcm_with_form(sc, form)
         r.set_option(N.OPTION_FAST_MATH, fast)
         r.set_option(N.OPTION_BUCKET_KERNEL, bucket)
+        if split:
+            r.set_option(N.OPTION_SPLIT_STREAMS, split)
         r.extinction = 4; r.steps = 4; r.anisotropy = 0.2
         r.reset()
         r.render()

@@ -179,7 +179,7 @@ int volume_records(vpt_volume *v) {
                        v->linear, v->records, v->nx, v->ny, v->nz, v->rec_wide ? v->rtabc : v->rtab32, v->rec_wide ? 1 : 0);
     HIP_TRY(hipGetLastError());
     v->rec_valid = true;
-    for (vpt_renderer *r : c->renderers) if (r->vol == v) r->main_dirty = true;    // side streams must see the build
+    for (vpt_renderer *r : c->renderers) if (r->vol == v) r->streams.mark_dirty();    // side streams must see the build
     return VPT_OK;
 }
 static int volume_upload(vpt_volume *v, int x, int y, int z, int w, int h, int d, const void *data, size_t nbytes, bool on_device) {
@@ -442,9 +442,9 @@ extern "C" int vpt_renderer_create(vpt_context *c, int kind, int width, int heig
     r->frame_table = nullptr; r->frame_staging = nullptr; r->frames_played = 0;
     r->warmed = false; r->play_graph = nullptr;
     r->fast_math = 0; r->boundary_atlas = 1; r->column_records = 2;
-    r->frame_ring = nullptr; r->ring_frames = 0; r->split = default_split(kind); r->split_auto = true; r->target_is_callers = false; r->no_split = false; r->bucket_call = false; r->last_ranges = 1; r->stop_events = nullptr; r->stop_used = false; r->ev_fork = nullptr; for (int i = 0; i < VPT_MAX_SPLIT - 1; i++) { r->side[i] = nullptr; r->ev_join[i] = nullptr; } r->side_busy = false; r->main_dirty = true; r->mcm_persistent = 0; r->work_counter = nullptr; r->mcs_persistent = false;   // measured slower than k_mcs at every extinction tried
+    r->frame_ring = nullptr; r->ring_frames = 0; r->split = default_split(kind); r->split_auto = true; r->target_is_callers = false; r->no_split = false; r->bucket_call = false; r->stop_events = nullptr; r->stop_used = false; r->mcm_persistent = 0; r->work_counter = nullptr; r->mcs_persistent = false;   // measured slower than k_mcs at every extinction tried
     r->render_target = nullptr;
-    memset(&r->cls, 0, sizeof(r->cls)); r->cls.enabled = true; r->last_layout = 0; { const char *e = getenv("VPT_HIT_KERNEL_FORM"); r->hit_form = (e && (e[0] == '1' || e[0] == '2') && !e[1]) ? e[0] - '0' : 0; } r->bucket_kernel = false; r->bucket_launches = 0;
+    memset(&r->cls, 0, sizeof(r->cls)); r->cls.enabled = true; { const char *e = getenv("VPT_HIT_KERNEL_FORM"); r->hit_form = (e && (e[0] == '1' || e[0] == '2') && !e[1]) ? e[0] - '0' : 0; } r->bucket_kernel = false; r->bucket_launches = 0;
     r->tm_owner = nullptr; r->tm_valid = false; r->tm_table = nullptr; r->tm_out = nullptr; r->tm_mode = 0;
     r->lao = LaoParams{ 1, 0.69f, 1, 0.05f, 1, 0.54f, 10, 0.19f, 1.0f, { 2.0f, 12.0f, 3.0f } };
     int rc = renderer_alloc_buffers(r);
@@ -481,8 +481,7 @@ extern "C" int vpt_renderer_destroy(vpt_renderer *r) {
     if (r->frame_ring) hipFree(r->frame_ring);
     if (r->frame_table) hipFree(r->frame_table);
     if (r->frame_staging) hipHostFree(r->frame_staging);
-    for (int i = 0; i < VPT_MAX_SPLIT - 1; i++) if (r->side[i]) { hipStreamDestroy(r->side[i]); hipEventDestroy(r->ev_join[i]); }
-    if (r->ev_fork) hipEventDestroy(r->ev_fork);
+    destroy_split_streams(r);
     if (r->play_graph) play_graph_free(r->play_graph);
     for (auto &ev : r->events) { hipEventDestroy(ev.first); hipEventDestroy(ev.second); }
     for (auto &ev : r->side_events) { hipEventDestroy(ev.first); hipEventDestroy(ev.second); }
@@ -744,9 +743,11 @@ static bool streams_overlap(hipStream_t a, hipStream_t b) {
     (void)hipGetLastError();
     return seen;
 }
-// a new non-blocking stream that overlaps every stream of `others` (null entries skipped)
-hipError_t create_overlapping_stream(hipStream_t *out, const hipStream_t *others, int n_others) {
+// a new non-blocking stream that overlaps r's context stream and every side stream r has
+hipError_t create_overlapping_stream(hipStream_t *out, const vpt_renderer *r) {
     static const bool probe = []() { const char *e = getenv("VPT_STREAM_PROBE"); return !(e && e[0] == '0'); }();
+    hipStream_t others[VPT_MAX_SPLIT] = { r->ctx->stream };
+    for (int k = 0; k < VPT_MAX_SPLIT - 1; k++) others[1 + k] = r->streams.side[k];
     hipStream_t tried[8]; int nt = 0; hipStream_t chosen = nullptr;
     while (nt < 8 && !chosen) {
         hipStream_t c;
@@ -754,7 +755,7 @@ hipError_t create_overlapping_stream(hipStream_t *out, const hipStream_t *others
         if (e != hipSuccess) { if (nt == 0) return e; (void)hipGetLastError(); break; }
         tried[nt++] = c;
         bool ok = true;
-        for (int i = 0; i < n_others && ok && probe; i++) if (others[i]) ok = streams_overlap(others[i], c);
+        for (int i = 0; i < VPT_MAX_SPLIT && ok && probe; i++) if (others[i]) ok = streams_overlap(others[i], c);
         if (ok) chosen = c;
     }
     if (!chosen) chosen = tried[0];
@@ -767,27 +768,44 @@ hipError_t create_overlapping_stream(hipStream_t *out, const hipStream_t *others
 // the side streams of VPT_OPTION_SPLIT_STREAMS = r->split, created (and picked: create_overlapping_stream) when the option is set or, for
 // the library's default, by the first pass that wants them
 int ensure_split_streams(vpt_renderer *r) {
-    if (r->split < 2 || (r->side[r->split - 2] && r->ev_fork)) return VPT_OK;
+    StreamSet &s = r->streams;
+    if (r->split < 2 || (s.side[r->split - 2] && s.ev_fork)) return VPT_OK;
     HIP_TRY(hipSetDevice(r->ctx->device));
-    if (!r->ev_fork) HIP_TRY(hipEventCreateWithFlags(&r->ev_fork, hipEventDisableTiming));
-    for (int i = 0; i + 1 < r->split; i++) if (!r->side[i]) {
-        hipStream_t others[VPT_MAX_SPLIT] = { r->ctx->stream };      // the context's stream and the side streams there are
-        for (int k = 0; k < VPT_MAX_SPLIT - 1; k++) others[1 + k] = r->side[k];
+    if (!s.ev_fork) HIP_TRY(hipEventCreateWithFlags(&s.ev_fork, hipEventDisableTiming));
+    for (int i = 0; i + 1 < r->split; i++) if (!s.side[i]) {
         HIP_TRY(hipStreamSynchronize(r->ctx->stream));
-        HIP_TRY(create_overlapping_stream(&r->side[i], others, VPT_MAX_SPLIT));
-        HIP_TRY(hipEventCreateWithFlags(&r->ev_join[i], hipEventDisableTiming));
+        HIP_TRY(create_overlapping_stream(&s.side[i], r));
+        HIP_TRY(hipEventCreateWithFlags(&s.ev_join[i], hipEventDisableTiming));
     }
-    r->main_dirty = true;
+    s.mark_dirty();
     return VPT_OK;
+}
+void destroy_split_streams(vpt_renderer *r) {
+    StreamSet &s = r->streams;
+    for (int i = 0; i < VPT_MAX_SPLIT - 1; i++) if (s.side[i]) { hipStreamDestroy(s.side[i]); hipEventDestroy(s.ev_join[i]); }
+    if (s.ev_fork) hipEventDestroy(s.ev_fork);
 }
 // the side stream's work happens-before everything enqueued on the context's stream from here on
 int join_side(vpt_renderer *r) {
-    if (!r || !r->side_busy) return VPT_OK;
-    for (int i = 0; i < VPT_MAX_SPLIT - 1; i++) if (r->side[i]) {
-        HIP_TRY(hipEventRecord(r->ev_join[i], r->side[i]));
-        HIP_TRY(hipStreamWaitEvent(r->ctx->stream, r->ev_join[i], 0));
+    if (!r || !r->streams.busy()) return VPT_OK;
+    StreamSet &s = r->streams;
+    for (int i = 0; i < VPT_MAX_SPLIT - 1; i++) if (s.side[i]) {
+        HIP_TRY(hipEventRecord(s.ev_join[i], s.side[i]));
+        HIP_TRY(hipStreamWaitEvent(r->ctx->stream, s.ev_join[i], 0));
     }
-    r->side_busy = false; r->main_dirty = true;
+    s.last = Deal{}; s.dirty = true;
+    return VPT_OK;
+}
+// the ordering rule of split passes (vpt_internal.h StreamSet), before the launches of deal d
+int streams_deal(vpt_renderer *r, Deal d) {
+    StreamSet &s = r->streams;
+    if (s.busy() && d != s.last) VPT_TRY(join_side(r));
+    if (d.ranges >= 2 && s.dirty) {
+        HIP_TRY(hipEventRecord(s.ev_fork, r->ctx->stream));
+        for (int i = 0; i + 1 < d.ranges; i++) HIP_TRY(hipStreamWaitEvent(s.side[i], s.ev_fork, 0));
+        s.dirty = false;
+    }
+    s.last = d;
     return VPT_OK;
 }
 // classifies the tiles for `mvp_inverse` (see classify_tiles) and puts the lists on the device: HIT tiles first, then MISS tiles.
@@ -835,7 +853,7 @@ int classes_build(vpt_renderer *r, const float *mvp_inverse) {
     HIP_TRY(hipMemcpyAsync(c.list, list, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, r->ctx->stream));
     HIP_TRY(hipEventRecord(c.staged[s], r->ctx->stream));
     c.stage_next = s ^ 1;
-    r->main_dirty = true;
+    r->streams.mark_dirty();
     c.n_hit = nh; c.n_miss = nm;
     memmove(c.mvp, mvp_inverse, sizeof(c.mvp));
     memcpy(c.built_mvp, mvp_inverse, sizeof(c.built_mvp)); memcpy(c.built_geom, geom, sizeof(geom)); c.built = true;

@@ -102,6 +102,29 @@ struct TileClasses {
     // pass has written since the reset: only there do the skipped tiles hold their final texels (marcher_track)
     const void *complete[VPT_COMPLETE_DESTS]; int n_complete;
 };
+// Split passes (VPT_OPTION_SPLIT_STREAMS = K): a sampling pass is dealt to up to K streams as tile-row ranges or parts of a tile list;
+// range i runs on range_stream(r, i), the context's stream for i = 0 and a private side stream otherwise.  A pixel's pass depends on
+// its own previous pass only, so the ranges never wait for each other: the launch gap, ramp and tail of one overlap the body of the
+// others.  A Deal is how one launch maps the tiles to streams.  streams_deal(r, d), called before the launches, is the whole rule:
+// the side streams are joined when they still hold a different deal's work (a tile's next pass must follow its last on one stream),
+// and a deal of two or more ranges forks the side streams it uses behind the context's stream if that stream has enqueued anything
+// since they last waited for it (dirty).  Every other entry point joins the side streams into the context's stream first (join_side).
+enum { DEAL_ROWS = 0, DEAL_LISTS = 1 };
+struct Deal {
+    int layout = DEAL_ROWS;        // DEAL_ROWS: tile-row ranges; DEAL_LISTS: parts of the tile lists
+    int ranges = 1;                // streams launched on
+    bool operator==(const Deal &o) const { return layout == o.layout && ranges == o.ranges; }
+    bool operator!=(const Deal &o) const { return !(*this == o); }
+};
+struct StreamSet {
+    hipStream_t side[VPT_MAX_SPLIT - 1] = {};
+    hipEvent_t ev_fork = nullptr, ev_join[VPT_MAX_SPLIT - 1] = {};
+    bool dirty = true;             // the context's stream has enqueued work the side streams have not waited for
+    Deal last;                     // the deal of the last launch since the last join (a join resets it)
+    bool busy() const { return last.ranges >= 2; }   // the side streams may hold work the context's stream has not joined
+    void mark_dirty() { dirty = true; }
+};
+
 struct vpt_renderer {
     vpt_context *ctx;
     int kind;
@@ -130,22 +153,18 @@ struct vpt_renderer {
     float2 *dos_samples; int dos_nsamples;   // DOS: uOcclusionSamples (vpt_renderer_set_occlusion_samples)
     int dos_rect[4]; bool dos_rect_valid;   // DOS: tile rectangle [x0, y0, x1, y1) of the previous integrate call (see dos_tile_rect)
     int dos_cur;                   // DOS: which of the occlusion buffers st[2|3] holds the latest slice (colour: st[0], in place)
-    // VPT_OPTION_SPLIT_STREAMS = K: the MCM pass is launched as K tile-row ranges, all but the first on private side streams.  A
-    // pixel's pass depends on its own previous pass only, so the ranges never wait for each other: the launch gap, ramp and tail
-    // of one overlap the body of the others.  Every other entry point joins the side streams into the context's stream first.
+    // VPT_OPTION_SPLIT_STREAMS = K: a sampling pass may be dealt to up to K streams (split_allowed, StreamSet)
     bool target_is_callers;        // render_target was set by vpt_renderer_set_render_target (not by the gather pipeline)
     bool no_split;                 // set while a frame sequence is being captured into a hipGraph (one stream only)
     bool bucket_call;              // inside vpt_renderer_play_into*: the passes into the caller's bucket may use every stream, the call joins them before it returns
-    int last_ranges;               // how many tile-row ranges (streams) the last sampling launch used
     hipEvent_t *stop_events;       // gather pipeline: event i is attached to range i's launch (hipExtLaunchKernel stop event: the
     bool stop_used;                // dispatch packet's own completion signal, no barrier packet behind the kernel)
     int split; bool split_auto;     // split_auto: the stream count is the library's default and follows the launch size (split_for)
-    hipStream_t side[VPT_MAX_SPLIT - 1]; hipEvent_t ev_fork, ev_join[VPT_MAX_SPLIT - 1]; bool side_busy, main_dirty;
+    StreamSet streams;
     int boundary_atlas;            // VPT_OPTION_BOUNDARY_ATLAS (default 1): MCM takes out-of-cube samples from the volume's boundary atlas
     int fast_math;                 // VPT_OPTION_FAST_MATH: MCM events with hardware rcp / rsq / log / sin / cos (k_mcm_integrate<.., V | VPT_V_FAST>)
     int mcm_persistent;            // 0: k_mcm_integrate; 1: k_mcm_persist; 2: k_mcm_persist with next-segment prefetch // (persistent waves, state prefetch) for the MCM integrate pass
     struct TileClasses cls;        // MCM: HIT / MISS tile lists of the last reset's matrix (see classify_tiles)
-    int last_layout;               // how the last sampling launch mapped tiles to streams: 0 = tile-row ranges, 1 = tile lists
     // tone mapping fused into the fused passes' frame store: the armed tone mapper (null: none), whether its output holds the tone-mapped
     // image of what the render buffer holds now, and the store's arguments (PassArgs.tm_*)
     struct vpt_tonemapper *tm_owner; bool tm_valid; const uint8_t *tm_table; uint32_t *tm_out; int tm_mode;
@@ -199,10 +218,12 @@ static inline size_t frame_elem(int kind) {
 // shared host functions (vpt_core.hip unless noted)
 // ---------------------------------------------------------------------------------------------
 int ensure_split_streams(vpt_renderer *r);          // creates the side streams r->split asks for, if they do not exist yet
+void destroy_split_streams(vpt_renderer *r);
 int join_side(vpt_renderer *r);                     // the side streams' work happens-before everything enqueued on the context's stream from here on
+int streams_deal(vpt_renderer *r, Deal d);          // before the launches of a deal: join and fork as the deal needs (StreamSet)
 int make_args(vpt_renderer *r, const vpt_uniforms *u, bool need_volume, PassArgs *a);
 int volume_records(vpt_volume *v);                  // builds the column records of a finalized one-channel byte volume if they are not current
-hipError_t create_overlapping_stream(hipStream_t *out, const hipStream_t *others, int n_others);
+hipError_t create_overlapping_stream(hipStream_t *out, const vpt_renderer *r);   // overlaps r's context stream and side streams
 bool invert_matrix(const float *m, double out[4][4]);               // column-major float matrix -> its inverse (double); false: singular
 int classes_build(vpt_renderer *r, const float *mvp_inverse);       // tile lists of `mvp_inverse` on the device (classify_tiles)
 void play_graph_free(PlayGraph *g);                                 // vpt_render.hip
@@ -259,6 +280,11 @@ static inline dim3 tile_grid(const vpt_renderer *r) { return dim3((unsigned)(r->
 static inline bool wave_blocks(const vpt_renderer *r) {
     return r->kind != VPT_RENDERER_MCM && r->kind != VPT_RENDERER_DOS && lds_bytes(r) * 28 <= 150 * 1024;
 }
+// may this pass be dealt to several streams?  (A frame rendered into caller memory — vpt_renderer_set_render_target — is consumed by work
+// the caller enqueues on the context's stream right behind it: such passes stay on that stream unless the caller has taken the join upon
+// itself (vpt_renderer_play_into*: one join per bucket of frames, at the end of the call).  The gather pipeline waits for every range itself.)
+static inline bool split_allowed(const vpt_renderer *r) { return r->split >= 2 && !r->no_split && (!r->target_is_callers || r->bucket_call); }
+static inline hipStream_t range_stream(const vpt_renderer *r, int i) { return i == 0 ? r->ctx->stream : r->streams.side[i - 1]; }
 // one sampling launch; in the gather pipeline the range's "rendered" event rides on the dispatch itself
 template <typename K>
 static void launch_range(K kernel, vpt_renderer *r, dim3 grid, dim3 block, size_t lds, hipStream_t stream, const PassArgs &a, int range) {
@@ -291,54 +317,30 @@ static int launch_sampling(K kernel, vpt_renderer *r, const PassArgs &a, unsigne
     const bool wave = wave_blocks(r);
     const unsigned xmul = wave ? 4u : 1u;
     const dim3 block(wave ? 64u : (unsigned)VPT_BLOCK);
-    const bool split = r->split >= 2 && !r->no_split && (!r->target_is_callers || r->bucket_call);
+    const bool split = split_allowed(r);
     if (split) VPT_TRY(ensure_split_streams(r));
-    // (a frame rendered into caller memory — vpt_renderer_set_render_target — is consumed by work the caller enqueues on the
-    // context's stream right behind it: such passes stay on that stream unless the caller has taken the join upon itself
-    // (vpt_renderer_play_into*: one join per bucket of frames, at the end of the call).  The gather pipeline waits for every range itself.)
     if (r->cls.list_now) {
         // the HIT tiles only (marcher_track): K equal parts of the list on the K streams
         const int k = split ? std::min(split_for(r, r->cls.n_hit), r->cls.n_hit) : 1;
-        if (r->side_busy && (r->last_layout != 1 || r->last_ranges != k)) VPT_TRY(join_side(r));      // the tile -> stream map changes
-        r->last_layout = 1;
-        if (k >= 2 && r->main_dirty) {
-            HIP_TRY(hipEventRecord(r->ev_fork, r->ctx->stream));
-            for (int i = 0; i + 1 < r->split; i++) HIP_TRY(hipStreamWaitEvent(r->side[i], r->ev_fork, 0));
-            r->main_dirty = false;
-        }
+        VPT_TRY(streams_deal(r, Deal{ DEAL_LISTS, k }));
         for (int i = 0; i < k; i++) {
             const int h0 = (int)((long long)r->cls.n_hit * i / k), h1 = (int)((long long)r->cls.n_hit * (i + 1) / k);
             PassArgs part = a;
             part.pm.tile_list = r->cls.list + h0; part.pm.list_n = h1 - h0;
             const unsigned blocks = wave ? (unsigned)((h1 - h0 + 7) / 8) * 32u : (unsigned)(h1 - h0);
-            launch_range(kernel, r, dim3(blocks), block, lds, i == 0 ? r->ctx->stream : r->side[i - 1], part, i);
+            launch_range(kernel, r, dim3(blocks), block, lds, range_stream(r, i), part, i);
         }
-        if (k >= 2) r->side_busy = true;
-        r->last_ranges = k;
         return VPT_OK;
     }
-    const int kw = split ? split_for(r, r->tiles_x * r->tiles_y) : 1;
-    if (r->side_busy && (r->last_layout != 0 || r->last_ranges != kw)) VPT_TRY(join_side(r));     // the previous pass dealt the tiles to the streams in another way
-    r->last_layout = 0;
-    if (split && kw >= 2 && r->tiles_y >= kw) {
-        dim3 g = tile_grid(r);
-        const unsigned k = (unsigned)kw;
-        if (r->main_dirty) {      // whatever the context's stream did to the renderer's buffers since the last join comes first
-            HIP_TRY(hipEventRecord(r->ev_fork, r->ctx->stream));
-            for (unsigned i = 0; i + 1 < k; i++) HIP_TRY(hipStreamWaitEvent(r->side[i], r->ev_fork, 0));
-            r->main_dirty = false;
-        }
-        for (unsigned i = 0; i < k; i++) {            // tile rows [g.y * i / k, g.y * (i + 1) / k)
-            const unsigned y0 = g.y * i / k, y1 = g.y * (i + 1u) / k;
-            PassArgs part = a;
-            part.pm.ty0 = (int)y0;
-            launch_range(kernel, r, dim3(g.x * xmul, y1 - y0), block, lds, i == 0 ? r->ctx->stream : r->side[i - 1], part, (int)i);
-        }
-        r->side_busy = true; r->last_ranges = (int)k;
-    } else {
-        dim3 g = tile_grid(r);
-        launch_range(kernel, r, dim3(g.x * xmul, g.y), block, lds, r->ctx->stream, a, 0);
-        r->last_ranges = 1;
+    const dim3 g = tile_grid(r);
+    int k = split ? split_for(r, r->tiles_x * r->tiles_y) : 1;
+    if (r->tiles_y < k) k = 1;
+    VPT_TRY(streams_deal(r, Deal{ DEAL_ROWS, k }));
+    for (int i = 0; i < k; i++) {                     // tile rows [g.y * i / k, g.y * (i + 1) / k)
+        const unsigned y0 = g.y * i / k, y1 = g.y * (i + 1) / k;
+        PassArgs part = a;
+        part.pm.ty0 = (int)y0;
+        launch_range(kernel, r, dim3(g.x * xmul, y1 - y0), block, lds, range_stream(r, i), part, i);
     }
     return VPT_OK;
 }

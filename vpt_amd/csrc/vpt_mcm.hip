@@ -58,6 +58,18 @@ static int mcm_classify(vpt_renderer *r, const vpt_uniforms *u) {
     return classes_build(r, u->mvp_inverse);
 }
 
+// profiling (inside a Timed pair only): starts on `s` the pair vpt_renderer_profile_side reads, around the first launch a pass puts
+// on a side stream; returns the event to record on `s` behind that launch, or null
+static hipEvent_t side_events_begin(vpt_renderer *r, hipStream_t s) {
+    if (!r->timed_now) return nullptr;
+    if (r->side_events_used == r->side_events.size()) {
+        hipEvent_t a0, a1;
+        if (hipEventCreate(&a0) == hipSuccess && hipEventCreate(&a1) == hipSuccess) r->side_events.push_back({ a0, a1 });
+    }
+    if (r->side_events_used == r->side_events.size()) return nullptr;
+    hipEventRecord(r->side_events[r->side_events_used].first, s);
+    return r->side_events[r->side_events_used++].second;
+}
 // one MCM pass (integrate, or render() = integrate + renderFrame) as list launches: the HIT tiles through k_mcm_integrate on the
 // context's stream, the MISS tiles through k_mcm_miss — with VPT_OPTION_SPLIT_STREAMS = K as K - 1 equal parts on the side streams,
 // so that the latency-bound HIT tiles and the arithmetic-bound MISS tiles share the chip for the whole frame
@@ -83,10 +95,7 @@ static int launch_mcm_classes(vpt_renderer *r, const PassArgs &a) {
     const size_t lds_hit = lds_bytes(r), lds_miss = (size_t)r->tf_w * 2 * sizeof(float4);
     if (lds_hit > 160 * 1024) return fail(VPT_ERR_UNSUPPORTED, "transfer function + volume tables need %zu B of LDS (> 160 KiB)", lds_hit);
     if (lds_hit > 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void *)kh, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_hit));
-    int k = 1;
-    if (r->split >= 2 && !r->no_split && (!r->target_is_callers || r->bucket_call)) k = r->split;
-    if (r->side_busy && r->last_layout != 1) VPT_TRY(join_side(r));      // the tile -> stream map changes: order the streams once
-    r->last_layout = 1;
+    const int k = split_allowed(r) ? r->split : 1;
     struct Part { PassKernel kernel; const uint32_t *list; int n; size_t lds; };
     Part parts[VPT_MAX_SPLIT]; int np = 0;
     // (measured, 1080p headline frame, us per frame: HIT | MISS on two streams 81.0; HIT | MISS/2 | MISS/2 82.3-83.0; HIT/2 | HIT/2 | MISS
@@ -106,59 +115,34 @@ static int launch_mcm_classes(vpt_renderer *r, const PassArgs &a) {
         const int m0 = (int)((long long)r->cls.n_miss * i / miss_parts), m1 = (int)((long long)r->cls.n_miss * (i + 1) / miss_parts);
         if (m1 > m0) parts[np++] = Part{ km, r->cls.list + r->cls.n_hit + m0, m1 - m0, lds_miss };
     }
+    VPT_TRY(streams_deal(r, Deal{ DEAL_LISTS, k == 1 ? 1 : std::max(np, 1) }));
+    auto part_args = [&](int i) {
+        PassArgs part = a;
+        part.pm.tile_list = parts[i].list; part.pm.list_n = parts[i].n; part.miss_load_pos = r->cls.stale ? 0u : 1u; part.violations = r->cls.violations;
+        part.miss_verify = check ? 1u : 0u;
+        VPT_TIMING_ARG(part, i < hit_parts);
+        return part;
+    };
     if (k == 1) {
         // one stream: the launches follow each other; the dispatch's completion event (gather pipeline) rides on the last
         for (int i = 0; i < np; i++) {
-            PassArgs part = a;
-            part.pm.tile_list = parts[i].list; part.pm.list_n = parts[i].n; part.miss_load_pos = r->cls.stale ? 0u : 1u; part.violations = r->cls.violations;
-            part.miss_verify = check ? 1u : 0u;
-            VPT_TIMING_ARG(part, i < hit_parts);
+            const PassArgs part = part_args(i);
             // profiling: the caller's pair (Timed) brackets both launches; the MISS-tile kernel gets the pair vpt_renderer_profile_side reads
-            hipEvent_t e1 = nullptr;
-            if (i >= hit_parts && i == np - 1 && r->timed_now) {
-                if (r->side_events_used == r->side_events.size()) {
-                    hipEvent_t a0, a1;
-                    if (hipEventCreate(&a0) == hipSuccess && hipEventCreate(&a1) == hipSuccess) r->side_events.push_back({ a0, a1 });
-                }
-                if (r->side_events_used < r->side_events.size()) {
-                    hipEventRecord(r->side_events[r->side_events_used].first, r->ctx->stream);
-                    e1 = r->side_events[r->side_events_used++].second;
-                }
-            }
+            const hipEvent_t e1 = i >= hit_parts && i == np - 1 ? side_events_begin(r, r->ctx->stream) : nullptr;
             if (i + 1 == np) launch_range(parts[i].kernel, r, dim3((unsigned)parts[i].n), dim3(VPT_BLOCK), parts[i].lds, r->ctx->stream, part, 0);
             else hipLaunchKernelGGL(parts[i].kernel, dim3((unsigned)parts[i].n), dim3(VPT_BLOCK), parts[i].lds, r->ctx->stream, part);
             if (e1) hipEventRecord(e1, r->ctx->stream);
         }
-        r->last_ranges = 1;
     } else {
-        if (r->main_dirty) {
-            HIP_TRY(hipEventRecord(r->ev_fork, r->ctx->stream));
-            for (int i = 0; i + 1 < k; i++) HIP_TRY(hipStreamWaitEvent(r->side[i], r->ev_fork, 0));
-            r->main_dirty = false;
-        }
         // (the MISS-tile kernel is the longer of the two and goes first: its stream is the one a short sequence of frames waits for at the
         // end — blocks of 5 frames 87.5 -> 85.3 us per frame, of 20 frames 81.9 -> 81.1, long sequences the same)
         for (int i = np - 1; i >= 0; i--) {
-            PassArgs part = a;
-            part.pm.tile_list = parts[i].list; part.pm.list_n = parts[i].n; part.miss_load_pos = r->cls.stale ? 0u : 1u; part.violations = r->cls.violations;
-            part.miss_verify = check ? 1u : 0u;
-            VPT_TIMING_ARG(part, i < hit_parts);
+            const PassArgs part = part_args(i);
             // profiling: the context's stream is bracketed by the caller (Timed); the first side launch gets a pair of its own
-            hipEvent_t e1 = nullptr;
-            if (i == 1 && r->timed_now) {
-                if (r->side_events_used == r->side_events.size()) {
-                    hipEvent_t a0, a1;
-                    if (hipEventCreate(&a0) == hipSuccess && hipEventCreate(&a1) == hipSuccess) r->side_events.push_back({ a0, a1 });
-                }
-                if (r->side_events_used < r->side_events.size()) {
-                    hipEventRecord(r->side_events[r->side_events_used].first, r->side[0]);
-                    e1 = r->side_events[r->side_events_used++].second;
-                }
-            }
-            launch_range(parts[i].kernel, r, dim3((unsigned)parts[i].n), dim3(VPT_BLOCK), parts[i].lds, i == 0 ? r->ctx->stream : r->side[i - 1], part, i);
-            if (e1) hipEventRecord(e1, r->side[0]);
+            const hipEvent_t e1 = i == 1 ? side_events_begin(r, range_stream(r, 1)) : nullptr;
+            launch_range(parts[i].kernel, r, dim3((unsigned)parts[i].n), dim3(VPT_BLOCK), parts[i].lds, range_stream(r, i), part, i);
+            if (e1) hipEventRecord(e1, range_stream(r, 1));
         }
-        r->side_busy = true; r->last_ranges = std::max(np, 1);
     }
     r->cls.stale = r->cls.n_miss > 0; r->cls.stale_fast = fast;
     return VPT_OK;
@@ -171,7 +155,7 @@ typedef void (*BucketKernel)(PassArgs, FrameSeeds, uint32_t, void *, uint32_t);
 int mcm_bucket_ready(vpt_renderer *r, const PassArgs &a, bool *ready) {
     bool same = false;
     VPT_TRY(mcm_before_pass(r, a, &same));
-    const bool two_streams = r->split >= 2 && !r->no_split && (!r->target_is_callers || r->bucket_call);
+    const bool two_streams = split_allowed(r);
     if (two_streams) VPT_TRY(ensure_split_streams(r));
     *ready = same && r->cls.enabled && mcm_classes_runnable(r, a) && mcm_plain_volume(r) && two_streams && !r->cls.verify;
     return VPT_OK;
@@ -201,13 +185,7 @@ int mcm_bucket(vpt_renderer *r, const PassArgs &a, const FrameVar *v, int count,
     const size_t lds_hit = lds_bytes(r), lds_miss = (size_t)r->tf_w * 2 * sizeof(float4);
     if (lds_hit > 160 * 1024) return fail(VPT_ERR_UNSUPPORTED, "transfer function + volume tables need %zu B of LDS (> 160 KiB)", lds_hit);
     if (lds_hit > 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void *)kh, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_hit));
-    if (r->side_busy && r->last_layout != 1) VPT_TRY(join_side(r));
-    r->last_layout = 1;
-    if (r->main_dirty) {
-        HIP_TRY(hipEventRecord(r->ev_fork, r->ctx->stream));
-        for (int i = 0; i + 1 < r->split; i++) HIP_TRY(hipStreamWaitEvent(r->side[i], r->ev_fork, 0));
-        r->main_dirty = false;
-    }
+    VPT_TRY(streams_deal(r, Deal{ DEAL_LISTS, 2 }));
     FrameSeeds fs;
     for (int f = 0; f < VPT_BUCKET_FRAMES; f++) fs.seed[f] = f < count ? v[f].seed : 0.0f;
     PassArgs part = a;
@@ -219,9 +197,8 @@ int mcm_bucket(vpt_renderer *r, const PassArgs &a, const FrameVar *v, int count,
     }
     if (r->cls.n_miss > 0) {
         part.pm.tile_list = r->cls.list + r->cls.n_hit; part.pm.list_n = r->cls.n_miss;
-        hipLaunchKernelGGL(km, dim3((unsigned)r->cls.n_miss), dim3(VPT_BLOCK), lds_miss, r->side[0], part, fs, (uint32_t)count, ring, slot_pixels);
+        hipLaunchKernelGGL(km, dim3((unsigned)r->cls.n_miss), dim3(VPT_BLOCK), lds_miss, range_stream(r, 1), part, fs, (uint32_t)count, ring, slot_pixels);
     }
-    r->side_busy = true; r->last_ranges = 2;
     r->cls.stale = r->cls.n_miss > 0; r->cls.stale_fast = fast;
     r->tm_valid = false;
     r->bucket_launches++;
@@ -270,7 +247,7 @@ static int launch_mcm_pass(vpt_renderer *r, const PassArgs &a) {
     // share 17.7 against 19.4) and lose when they have to follow each other on ONE stream (102; the share: 30.5 against 20.7): a pass
     // that must stay on the context's stream — no VPT_OPTION_SPLIT_STREAMS, a caller-owned render target without
     // vpt_renderer_play_into*, a sequence being captured — runs the general kernel.
-    const bool two_streams = r->split >= 2 && !r->no_split && (!r->target_is_callers || r->bucket_call);
+    const bool two_streams = split_allowed(r);
     if (two_streams) VPT_TRY(ensure_split_streams(r));
     if (same && r->cls.enabled && mcm_classes_runnable(r, a) && (two_streams || r->cls.one_stream)) return launch_mcm_classes<FUSE>(r, a);
     VPT_TRY(mcm_materialize(r));
@@ -292,13 +269,13 @@ int mcm_render_frame(vpt_renderer *r, const PassArgs &a) {
     // _renderFrame behind an integrate pass of the tile classes that is still on its two streams (render() hook by hook, AbstractRenderer.js:60-70):
     // the HIT tiles' texels by the context's stream, the MISS tiles' by the side stream — each behind its own class kernel, no join, so the
     // next pass's kernels overlap this one's as they do behind the fused call (1080p: 124 -> 104 us per frame hook by hook; fused 92)
-    if (r->side_busy && r->last_layout == 1 && r->last_ranges == 2 && r->cls.valid && r->cls.n_hit > 0 && r->cls.n_miss > 0 &&
+    if (r->streams.busy() && r->streams.last == Deal{ DEAL_LISTS, 2 } && r->cls.valid && r->cls.n_hit > 0 && r->cls.n_miss > 0 &&
         !r->target_is_callers && !r->stop_events) {          // (the lists are those of the launch still in flight: a reset joins before it rebuilds them)
         PassArgs part = a;
         part.pm.tile_list = r->cls.list; part.pm.list_n = r->cls.n_hit;
         hipLaunchKernelGGL(k_mcm_render, dim3((unsigned)r->cls.n_hit), dim3(VPT_BLOCK), 0, r->ctx->stream, part);
         part.pm.tile_list = r->cls.list + r->cls.n_hit; part.pm.list_n = r->cls.n_miss;
-        hipLaunchKernelGGL(k_mcm_render, dim3((unsigned)r->cls.n_miss), dim3(VPT_BLOCK), 0, r->side[0], part);
+        hipLaunchKernelGGL(k_mcm_render, dim3((unsigned)r->cls.n_miss), dim3(VPT_BLOCK), 0, range_stream(r, 1), part);
         return VPT_OK;
     }
     VPT_TRY(join_side(r));

@@ -23,7 +23,7 @@ int mcm_multi(vpt_renderer *r, const PassArgs &a, uint32_t npasses, uint2 *ring)
     r->tm_valid = false;
     VPT_TRY(mcm_before_pass(r, a, nullptr));
     VPT_TRY(mcm_materialize(r));                      // a whole-image kernel: every tile's full photon state
-    if (r->side_busy) VPT_TRY(join_side(r));
+    VPT_TRY(streams_deal(r, Deal{ DEAL_ROWS, 1 }));   // one stream: the side streams are joined first
     if (a.vol.records) {                              // column records: LINEAR one-channel byte volumes
         const int v = class_variant(r, a);
         VARIANT_CASES(ring ? launch_frames(k_mcm_frames<V>, r, a, npasses, ring) : launch_multi(k_mcm_multi<V>, r, a, npasses))

@@ -101,7 +101,7 @@ static void launch_tonemap(vpt_tonemapper *t, const uint2 *src, size_t n, const 
             }
             r->tm_owner = t; r->tm_table = t->table; r->tm_out = t->out; r->tm_mode = f.mode;
             r->tm_valid = true;
-            r->main_dirty = true;       // side streams of split passes must see the table this stream has just (re)built
+            r->streams.mark_dirty();    // side streams of split passes must see the table this stream has just (re)built
         }
     } arm{ t, fr, p };
     if (!current) {
@@ -471,10 +471,8 @@ extern "C" int vpt_gather_create(vpt_renderer *r, const void *id128, int rank, i
     hipError_t e;
     {   // the communication stream must overlap the streams the passes run on
         { int jr = ensure_split_streams(r); if (jr == VPT_OK) jr = join_side(r); if (jr != VPT_OK) { delete g; return jr; } }
-        hipStream_t others[VPT_MAX_SPLIT] = { r->ctx->stream };
-        for (int k = 0; k < VPT_MAX_SPLIT - 1; k++) others[1 + k] = r->side[k];
         hipStreamSynchronize(r->ctx->stream);
-        e = create_overlapping_stream(&g->comm_stream, others, VPT_MAX_SPLIT);
+        e = create_overlapping_stream(&g->comm_stream, r);
     }
     for (int b = 0; b < 2 && e == hipSuccess; b++) {
         for (int i = 0; i < VPT_MAX_SPLIT && e == hipSuccess; i++) e = hipEventCreateWithFlags(&g->rendered[b][i], hipEventDisableTiming);
@@ -580,9 +578,8 @@ static int gather_enqueue_frame(vpt_gather *g, PassArgs &a, hipEvent_t t0 = null
     const int b = st.buffer;
     if (st.wait_gathered) {                                                  // on every stream that may carry a range of this frame
         HIP_TRY(hipStreamWaitEvent(cs, g->gathered[st.parity], 0));
-        for (int i = 0; i < VPT_MAX_SPLIT - 1; i++) if (r->side[i]) HIP_TRY(hipStreamWaitEvent(r->side[i], g->gathered[st.parity], 0));
+        for (int i = 0; i < VPT_MAX_SPLIT - 1; i++) if (r->streams.side[i]) HIP_TRY(hipStreamWaitEvent(r->streams.side[i], g->gathered[st.parity], 0));
     }
-    r->last_ranges = 1;
     // the "rendered" events ride on the dispatches themselves (hipExtLaunchKernel stop events): a hipEventRecord behind the kernel
     // is a barrier packet of its own on the compute queue, 3-4.5 us per frame at every frame size (tools/r02_exp24.sh)
     r->stop_events = fused_passes ? nullptr : g->rendered[st.rendered_event]; r->stop_used = false;
@@ -596,12 +593,12 @@ static int gather_enqueue_frame(vpt_gather *g, PassArgs &a, hipEvent_t t0 = null
         VPT_TRY(launch_fused(r, a));
     }
     if (t1) HIP_TRY(hipEventRecord(t1, cs));
-    // A split pass (VPT_OPTION_SPLIT_STREAMS): the communication stream waits for every range; the ranges' streams are NOT joined,
-    // so range i of the next frame starts behind range i of this one, whatever the other ranges and the gather are doing.
+    // A split pass (VPT_OPTION_SPLIT_STREAMS): the communication stream waits for every range of the pass's deal; the ranges' streams are
+    // NOT joined, so range i of the next frame (same deal) starts behind range i of this one, whatever the other ranges and the gather are doing.
     const bool rode = r->stop_used;                                          // the events were attached to the launches themselves
     r->stop_events = nullptr; r->stop_used = false;
-    for (int i = 0; i < r->last_ranges; i++) {
-        hipStream_t s = i == 0 ? cs : r->side[i - 1];
+    for (int i = 0; i < r->streams.last.ranges; i++) {
+        hipStream_t s = range_stream(r, i);
         if (!rode) HIP_TRY(hipEventRecord(g->rendered[st.rendered_event][i], s));
         HIP_TRY(hipStreamWaitEvent(g->comm_stream, g->rendered[st.rendered_event][i], 0));
     }

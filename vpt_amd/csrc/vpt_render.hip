@@ -224,7 +224,7 @@ int play_upload_table(vpt_renderer *r, const float *vars, int count, bool graph,
             done += n;
         }
     }
-    r->main_dirty = true;                             // the side streams of a split pass read the table too: they fork behind this upload
+    r->streams.mark_dirty();                          // the side streams of a split pass read the table too: they fork behind this upload
     r->frames_played += (uint64_t)count;
     a->frame_table = table;
     a->frame_base = pos;
