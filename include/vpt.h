@@ -56,6 +56,24 @@ extern "C" {
 #define VPT_FORMAT_RG32F 3       /* format RG, internalFormat RG32F (or RG16F widened on upload), type FLOAT / HALF_FLOAT: two interleaved float
                                   * channels (Volume.js:58-60 allocates whatever internalFormat the manifest names); blocks are uploaded as
                                   * interleaved float32 pairs */
+#define VPT_FORMAT_R8_SNORM 4    /* format RED, internalFormat R8_SNORM, type BYTE: two's-complement bytes, texture(uVolume, p).r = max(c / 127, -1).
+                                  * Stored as they are in one-byte bricks like R8 (same bricked_bytes); -128 is clamped to -127 once at
+                                  * finalize; every tap is decoded to fl32(c / 127) and filtered in the R32F order: bit-identical to the R32F
+                                  * volume of the decoded texels.  Blocks are uploaded as bytes.  Not taken by column records, the persistent
+                                  * forms (VPT_OPTION_*_PERSISTENT) or the MCM tile classes: MCM runs its general pass on these volumes */
+#define VPT_FORMAT_RG8_SNORM 5   /* format RG, internalFormat RG8_SNORM, type BYTE: two interleaved SNORM channels (as R8_SNORM; the RGB8_SNORM /
+                                  * RGBA8_SNORM manifests' first two channels) */
+/* Packed formats: blocks are uploaded as the packed words of their GL type (2 or 4 bytes per texel); the library decodes them on the device
+ * (GL ES 3.0 rules) into (r, g) float pairs, and from then on the volume is an RG32F volume.  UNORM channels are fl32(c / (2^b - 1)). */
+#define VPT_FORMAT_RGB565 6      /* format RGB, internalFormat RGB565, type UNSIGNED_SHORT_5_6_5: r = bits 15-11 / 31, g = bits 10-5 / 63 */
+#define VPT_FORMAT_RGBA4 7       /* format RGBA, internalFormat RGBA4, type UNSIGNED_SHORT_4_4_4_4: r = bits 15-12 / 15, g = bits 11-8 / 15 */
+#define VPT_FORMAT_RGB5_A1 8     /* format RGBA, internalFormat RGB5_A1, type UNSIGNED_SHORT_5_5_5_1: r = bits 15-11 / 31, g = bits 10-6 / 31 */
+#define VPT_FORMAT_RGB10_A2 9    /* format RGBA, internalFormat RGB10_A2, type UNSIGNED_INT_2_10_10_10_REV: r = bits 9-0 / 1023, g = bits 19-10 / 1023 */
+#define VPT_FORMAT_R11F_G11F_B10F 10  /* format RGB, internalFormat R11F_G11F_B10F, type UNSIGNED_INT_10F_11F_11F_REV: r = bits 10-0, g = bits 21-11
+                                  * as unsigned 11-bit floats (5-bit exponent, 6-bit mantissa: exponent 0 denormal, 31 Inf / NaN).  A non-finite
+                                  * texel switches the boundary atlas off, as for any float volume */
+#define VPT_FORMAT_RGB9_E5 11    /* format RGB, internalFormat RGB9_E5, type UNSIGNED_INT_5_9_9_9_REV: r = bits 8-0, g = bits 17-9, shared
+                                  * exponent e = bits 31-27: m * 2^(e - 24) */
 
 /* Buffers readable through vpt_renderer_read (SingleBuffer.js / DoubleBuffer.js attachments) */
 #define VPT_BUFFER_RENDER 0      /* RGBA16F, 8 B/pixel  (AbstractRenderer.js:142-155, getTexture() :114-116) */

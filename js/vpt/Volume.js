@@ -3,7 +3,23 @@
 const { EventTarget, CustomEvent } = require('./EventTarget.js');
 const { native } = require('./native.js');
 
-const { RAWReader, GL_RED, GL_RG, GL_RGB, GL_RGBA, GL_UNSIGNED_BYTE, GL_FLOAT, GL_HALF_FLOAT } = require('./readers/readers.js');
+const R = require('./readers/readers.js');
+const { RAWReader, GL_RED, GL_RG, GL_RGB, GL_RGBA, GL_UNSIGNED_BYTE, GL_FLOAT, GL_HALF_FLOAT, GL_BYTE } = R;
+
+// [type, format, internalFormat, native format name, channels in the file, element kind] of the formats keyed on all three: SNORM bytes
+// (RGB8_SNORM / RGBA8_SNORM keep their first two channels, as RGB8 / RGBA8 do) and the packed types (one word per texel, decoded on the device)
+const SIZED = [
+    [GL_BYTE, GL_RED, R.GL_R8_SNORM, 'VPT_FORMAT_R8_SNORM', 1, 'i8'],
+    [GL_BYTE, GL_RG, R.GL_RG8_SNORM, 'VPT_FORMAT_RG8_SNORM', 2, 'i8'],
+    [GL_BYTE, GL_RGB, R.GL_RGB8_SNORM, 'VPT_FORMAT_RG8_SNORM', 3, 'i8'],
+    [GL_BYTE, GL_RGBA, R.GL_RGBA8_SNORM, 'VPT_FORMAT_RG8_SNORM', 4, 'i8'],
+    [R.GL_UNSIGNED_SHORT_5_6_5, GL_RGB, R.GL_RGB565, 'VPT_FORMAT_RGB565', 1, 'packed'],
+    [R.GL_UNSIGNED_SHORT_4_4_4_4, GL_RGBA, R.GL_RGBA4, 'VPT_FORMAT_RGBA4', 1, 'packed'],
+    [R.GL_UNSIGNED_SHORT_5_5_5_1, GL_RGBA, R.GL_RGB5_A1, 'VPT_FORMAT_RGB5_A1', 1, 'packed'],
+    [R.GL_UNSIGNED_INT_2_10_10_10_REV, GL_RGBA, R.GL_RGB10_A2, 'VPT_FORMAT_RGB10_A2', 1, 'packed'],
+    [R.GL_UNSIGNED_INT_10F_11F_11F_REV, GL_RGB, R.GL_R11F_G11F_B10F, 'VPT_FORMAT_R11F_G11F_B10F', 1, 'packed'],
+    [R.GL_UNSIGNED_INT_5_9_9_9_REV, GL_RGB, R.GL_RGB9_E5, 'VPT_FORMAT_RGB9_E5', 1, 'packed'],
+];
 
 // IEEE half -> float (exact)
 function halfToFloat(h) {
@@ -13,9 +29,10 @@ function halfToFloat(h) {
     return s * (1 + m / 1024) * Math.pow(2, e - 15);
 }
 
-// (native format, channels in the file, element kind) for a manifest's (format, type): what a WebGL2 sampler3D can filter —
-// UNSIGNED_BYTE with 1-4 channels (the shaders read .rg: further channels are dropped on upload), FLOAT / HALF_FLOAT with one
-// channel (R32F / R16F).  Anything else raises the reference's error (Volume.js:103).
+// (native format, channels in the file, element kind) for a manifest's (type, format, internalFormat): what a WebGL2 sampler3D can
+// filter — UNSIGNED_BYTE and FLOAT / HALF_FLOAT with 1-4 channels (the shaders read .rg: further channels are dropped on upload), BYTE
+// with an SNORM internal format, the packed types with the internal format each names (vpt_amd/volume.py device_format).  Anything
+// else raises the reference's error (Volume.js:103).
 function deviceFormat(N, modality) {
     const t = modality.type, f = modality.format;
     if (t === GL_UNSIGNED_BYTE && (f === GL_RED || f === GL_RG || f === GL_RGB || f === GL_RGBA)) {
@@ -26,13 +43,16 @@ function deviceFormat(N, modality) {
         const n = f === GL_RED ? 1 : (f === GL_RG ? 2 : (f === GL_RGB ? 3 : 4));
         return { fmt: n === 1 ? N.VPT_FORMAT_R32F : N.VPT_FORMAT_RG32F, channels: n, kind: t === GL_FLOAT ? 'f32' : 'f16' };
     }
+    const sized = SIZED.find(e => e[0] === t && e[1] === f && e[2] === modality.internalFormat);
+    if (sized) { return { fmt: N[sized[3]], channels: sized[4], kind: sized[5] }; }
     throw new Error('Unknown volume datatype: ' + t);
 }
 
-// a block as the bytes vpt_volume_upload_block takes: u8 with at most two channels, or float32
+// a block as the bytes vpt_volume_upload_block takes: (u)int8 with at most two channels, float32, or packed words
 function blockBytes(data, df) {
     const u8 = data instanceof Uint8Array ? data : new Uint8Array(data.buffer || data, data.byteOffset || 0, data.byteLength);
-    if (df.kind === 'u8') {
+    if (df.kind === 'packed') { return u8; }                 // the words as they are
+    if (df.kind === 'u8' || df.kind === 'i8') {
         if (df.channels <= 2) { return u8; }
         const n = u8.length / df.channels, out = new Uint8Array(2 * n);
         for (let i = 0; i < n; i++) { out[2 * i] = u8[df.channels * i]; out[2 * i + 1] = u8[df.channels * i + 1]; }

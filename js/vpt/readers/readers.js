@@ -7,6 +7,12 @@ const GL_RED = 6403, GL_R8 = 33321, GL_UNSIGNED_BYTE = 5121;
 const GL_RG = 33319, GL_RG8 = 33323;                  // two-channel volumes of BVP manifests
 const GL_RGB = 6407, GL_RGB8 = 32849, GL_RGBA = 6408, GL_RGBA8 = 32856;   // byte manifests with more channels (the shaders read .rg)
 const GL_FLOAT = 5126, GL_HALF_FLOAT = 5131, GL_R32F = 33326, GL_R16F = 33325;   // float volumes (Volume.js:84-105)
+const GL_BYTE = 5120;                                  // signed-normalised volumes (Volume.js:84-105: Int8Array)
+const GL_R8_SNORM = 0x8F94, GL_RG8_SNORM = 0x8F95, GL_RGB8_SNORM = 0x8F96, GL_RGBA8_SNORM = 0x8F97;
+// packed texel types (Uint16Array / Uint32Array) and the one sized internal format each can be filtered as
+const GL_UNSIGNED_SHORT_5_6_5 = 0x8363, GL_RGB565 = 0x8D62, GL_UNSIGNED_SHORT_4_4_4_4 = 0x8033, GL_RGBA4 = 0x8056;
+const GL_UNSIGNED_SHORT_5_5_5_1 = 0x8034, GL_RGB5_A1 = 0x8057, GL_UNSIGNED_INT_2_10_10_10_REV = 0x8368, GL_RGB10_A2 = 0x8059;
+const GL_UNSIGNED_INT_10F_11F_11F_REV = 0x8C3B, GL_R11F_G11F_B10F = 0x8C3A, GL_UNSIGNED_INT_5_9_9_9_REV = 0x8C3E, GL_RGB9_E5 = 0x8C3D;
 
 class AbstractReader {                                          // AbstractReader.js:1-15
     constructor(loader) { this._loader = loader; }
@@ -127,4 +133,7 @@ function ReaderFactory(which) {                                 // ReaderFactory
 }
 
 module.exports = { AbstractReader, RAWReader, ZIPReader, BVPReader, ReaderFactory, GL_RED, GL_R8, GL_RG, GL_RG8, GL_UNSIGNED_BYTE,
-    GL_RGB, GL_RGB8, GL_RGBA, GL_RGBA8, GL_FLOAT, GL_HALF_FLOAT, GL_R32F, GL_R16F };
+    GL_RGB, GL_RGB8, GL_RGBA, GL_RGBA8, GL_FLOAT, GL_HALF_FLOAT, GL_R32F, GL_R16F,
+    GL_BYTE, GL_R8_SNORM, GL_RG8_SNORM, GL_RGB8_SNORM, GL_RGBA8_SNORM, GL_UNSIGNED_SHORT_5_6_5, GL_RGB565, GL_UNSIGNED_SHORT_4_4_4_4, GL_RGBA4,
+    GL_UNSIGNED_SHORT_5_5_5_1, GL_RGB5_A1, GL_UNSIGNED_INT_2_10_10_10_REV, GL_RGB10_A2, GL_UNSIGNED_INT_10F_11F_11F_REV, GL_R11F_G11F_B10F,
+    GL_UNSIGNED_INT_5_9_9_9_REV, GL_RGB9_E5 };

@@ -77,15 +77,19 @@ extern "C" int vpt_context_synchronize(vpt_context *c) {
 // ---------------------------------------------------------------------------------------------
 extern "C" int vpt_volume_create(vpt_context *c, int w, int h, int d, int format, vpt_volume **out) {
     if (!c || !out) return fail(VPT_ERR_INVALID, "null argument");
-    if (format != VPT_FORMAT_R8 && format != VPT_FORMAT_RG8 && format != VPT_FORMAT_R32F && format != VPT_FORMAT_RG32F) return fail(VPT_ERR_UNSUPPORTED, "Unknown volume datatype: %d", format);  // Volume.js:103
+    if (format < VPT_FORMAT_R8 || format > VPT_FORMAT_RGB9_E5) return fail(VPT_ERR_UNSUPPORTED, "Unknown volume datatype: %d", format);  // Volume.js:103
     if (w < 1 || h < 1 || d < 1 || w > 4096 || h > 4096 || d > 4096)
         return fail(VPT_ERR_INVALID, "volume dimensions %dx%dx%d out of range [1,4096]", w, h, d);
     HIP_TRY(hipSetDevice(c->device));
     vpt_volume *v = new vpt_volume();
     memset(v, 0, sizeof(*v));
     v->ctx = c; v->nx = w; v->ny = h; v->nz = d;
-    v->channels = (format == VPT_FORMAT_RG8 || format == VPT_FORMAT_RG32F) ? 2 : 1;
-    v->f32 = format == VPT_FORMAT_R32F || format == VPT_FORMAT_RG32F;
+    // packed formats (VPT_FORMAT_RGB565 ..): the words are decoded on upload (k_decode_packed) into an RG32F volume
+    v->packed = format >= VPT_FORMAT_RGB565 ? format : 0;
+    v->packed_bytes = (format == VPT_FORMAT_RGB565 || format == VPT_FORMAT_RGBA4 || format == VPT_FORMAT_RGB5_A1) ? 2 : 4;
+    v->snorm = format == VPT_FORMAT_R8_SNORM || format == VPT_FORMAT_RG8_SNORM;
+    v->channels = (format == VPT_FORMAT_RG8 || format == VPT_FORMAT_RG32F || format == VPT_FORMAT_RG8_SNORM || v->packed) ? 2 : 1;
+    v->f32 = format == VPT_FORMAT_R32F || format == VPT_FORMAT_RG32F || v->packed;
     v->vox_bytes = v->channels * (v->f32 ? 4 : 1);
     // RG8: 256-byte slots (R brick at +0, G brick at +128); R32F: 512-byte slots; RG32F: 1024-byte slots (G brick at +512)
     const int slot_shift = (v->f32 ? 9 : 7) + (v->channels == 2 ? 1 : 0);
@@ -141,7 +145,7 @@ extern "C" int vpt_volume_create(vpt_context *c, int w, int h, int d, int format
         HIP_TRY(hipMemcpy(v->tab32, t32.data(), t32.size() * 4, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(v->tabc, tc.data(), tc.size() * 4, hipMemcpyHostToDevice));
     }
-    if (v->channels == 1 && !v->f32) {
+    if (v->channels == 1 && !v->f32 && !v->snorm) {
         // column records: 2-D Z-order over (x, y) with as many bits per axis as the axis needs, nz records of 4 bytes per column
         int cb[2] = { 0, 0 };
         while ((1 << cb[0]) < w) cb[0]++;
@@ -168,7 +172,7 @@ extern "C" int vpt_volume_create(vpt_context *c, int w, int h, int d, int format
 // The column records (vpt_device.h record_addr) of a one-channel byte volume, (re)built from the linear storage when blocks have been
 // uploaded since the last build.  Allocated on first use: only the MCM renderer samples them (4 bytes per voxel).
 int volume_records(vpt_volume *v) {
-    if (!v || v->channels != 1 || v->f32) return fail(VPT_ERR_INVALID, "column records exist for one-channel byte volumes");
+    if (!v || v->channels != 1 || v->f32 || v->snorm) return fail(VPT_ERR_INVALID, "column records exist for one-channel UNSIGNED_BYTE volumes");
     VPT_TRY(vpt_volume_finalize(v));
     if (v->rec_valid) return VPT_OK;
     vpt_context *c = v->ctx;
@@ -186,13 +190,14 @@ static int volume_upload(vpt_volume *v, int x, int y, int z, int w, int h, int d
     if (!v || !data) return fail(VPT_ERR_INVALID, "null argument");
     if (w < 1 || h < 1 || d < 1 || x < 0 || y < 0 || z < 0 || x + w > v->nx || y + h > v->ny || z + d > v->nz)
         return fail(VPT_ERR_INVALID, "block (%d,%d,%d)+(%d,%d,%d) outside volume %dx%dx%d", x, y, z, w, h, d, v->nx, v->ny, v->nz);
-    size_t need = (size_t)w * h * d * v->vox_bytes;
+    const size_t texels = (size_t)w * h * d;
+    size_t need = texels * (v->packed ? v->packed_bytes : v->vox_bytes);        // packed formats: the caller's words
     if (nbytes < need) return fail(VPT_ERR_INVALID, "block data too short: %zu < %zu", nbytes, need);
     vpt_context *c = v->ctx;
     HIP_TRY(hipSetDevice(c->device));
     for (vpt_renderer *r : c->renderers) if (r->vol == v) VPT_TRY(join_side(r));
     bool full_xy = (x == 0 && y == 0 && w == v->nx && h == v->ny);
-    if (full_xy) {   // contiguous run of z-slices (RAWReader.js:47-63 produces exactly these)
+    if (full_xy && !v->packed) {   // contiguous run of z-slices (RAWReader.js:47-63 produces exactly these)
         uint8_t *dst = v->linear + (size_t)z * v->nx * v->ny * v->vox_bytes;
         HIP_TRY(hipMemcpyAsync(dst, data, need, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
     } else {
@@ -206,8 +211,11 @@ static int volume_upload(vpt_volume *v, int x, int y, int z, int w, int h, int d
             HIP_TRY(hipMemcpyAsync(v->staging, data, need, hipMemcpyHostToDevice, c->stream));
             src = v->staging;
         }
-        int grid = (int)((need / v->vox_bytes + 255) / 256); if (grid > 4096) grid = 4096;
-        hipLaunchKernelGGL(k_blit_block, dim3(grid), dim3(256), 0, c->stream, v->linear, v->nx, v->ny, src, x, y, z, w, h, d, v->vox_bytes);
+        int grid = (int)((texels + 255) / 256); if (grid > 4096) grid = 4096;
+        if (v->packed)   // the (r, g) floats of each word at the block's place in the RG32F storage
+            hipLaunchKernelGGL(k_decode_packed, dim3(grid), dim3(256), 0, c->stream, (float2 *)v->linear, v->nx, v->ny, src, v->packed, x, y, z, w, h, d);
+        else
+            hipLaunchKernelGGL(k_blit_block, dim3(grid), dim3(256), 0, c->stream, v->linear, v->nx, v->ny, src, x, y, z, w, h, d, v->vox_bytes);
         HIP_TRY(hipGetLastError());
     }
     if (!on_device) HIP_TRY(hipStreamSynchronize(c->stream));   // host buffer may be released by the caller
@@ -228,6 +236,11 @@ extern "C" int vpt_volume_finalize(vpt_volume *v) {
     int nbx = (v->nx + 3) / 4, nby = (v->ny + 3) / 4, nbz = (v->nz + 3) / 4;
     if (nby > 65535 || nbz > 65535) return fail(VPT_ERR_UNSUPPORTED, "too many bricks");
     const int strips = (nbx + VPT_BRICKIFY_RUN - 1) / VPT_BRICKIFY_RUN;
+    if (v->snorm) {   // R8_SNORM / RG8_SNORM: -128 reads as -1 = -127 / 127 (GL ES 3.0 2.1.6.1); clamped once, before bricks and atlas
+        const size_t n = (size_t)v->nx * v->ny * v->nz * v->channels;
+        int grid = (int)((n / 4 + 255) / 256); if (grid > 4096) grid = 4096; if (grid < 1) grid = 1;
+        hipLaunchKernelGGL(k_snorm_clamp, dim3(grid), dim3(256), 0, c->stream, v->linear, n);
+    }
     // one-channel volumes with dword-aligned rows go through the LDS-staged kernel (dword loads and stores)
     int fast = (v->channels == 1 && v->nx % 4 == 0) ? strips : 0;
     if (v->f32) {
@@ -1133,7 +1146,16 @@ static int probe_sample(vpt_renderer *r, const float *xyz, float *rgba, size_t n
             case 40: if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<40>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); else hipLaunchKernelGGL(k_probe_sample<40>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); break;
             case 41: if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<41>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); else hipLaunchKernelGGL(k_probe_sample<41>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); break;
             case 42: if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<42>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); else hipLaunchKernelGGL(k_probe_sample<42>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); break;
-            default: if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<43>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); else hipLaunchKernelGGL(k_probe_sample<43>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); break;
+            case 43: if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<43>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); else hipLaunchKernelGGL(k_probe_sample<43>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); break;
+            case 128: if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<128>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); else hipLaunchKernelGGL(k_probe_sample<128>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); break;
+            case 129: if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<129>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); else hipLaunchKernelGGL(k_probe_sample<129>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); break;
+            case 130: if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<130>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); else hipLaunchKernelGGL(k_probe_sample<130>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); break;
+            case 131: if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<131>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); else hipLaunchKernelGGL(k_probe_sample<131>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); break;
+            case 136: if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<136>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); else hipLaunchKernelGGL(k_probe_sample<136>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); break;
+            case 137: if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<137>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); else hipLaunchKernelGGL(k_probe_sample<137>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); break;
+            case 138: if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<138>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); else hipLaunchKernelGGL(k_probe_sample<138>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); break;
+            case 139: if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<139>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); else hipLaunchKernelGGL(k_probe_sample<139>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); break;
+            default: hipFree(din); hipFree(dout); return fail(VPT_ERR_INVALID, "no probe kernel for variant %d", variant_of(r));
         }
         e = hipGetLastError();
     }

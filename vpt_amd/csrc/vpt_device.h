@@ -350,6 +350,7 @@ VPT_DEV const uint8_t *cell_addr(const DevVolume &v, const LdsTables &t, uint32_
 #define VPT_V_F32     32  // FLOAT texels (R32F; R16F widened on upload): 5^3 floats in a 512-byte slot, no normalisation
 #define VPT_V_RG      8   // two-channel (RG8) volume: texture(uVolume, p).rg has both channels, the transfer function is looked up in 2-D
 #define VPT_V_REC     64  // in-cube samples from the column records instead of the bricks (one-channel byte volumes, LINEAR filter; MCM)
+#define VPT_V_SNORM   128 // BYTE texels (R8_SNORM / RG8_SNORM): bricks as R8 / RG8, each tap decoded to fl32(c / 127) and filtered as R32F
 // the eight taps around a cell of one channel's brick and their trilinear blend: taps +0,+1 (y,z) ; +5,+6 (y+1,z) ;
 // +25,+26 (y,z+1) ; +30,+31 (y+1,z+1) = two 8-byte windows of one line.
 // tools/gather_rates.hip (MI355X, L1-resident gathers): a dword-aligned 8/12/16-byte wave load costs ~27-33 cycles
@@ -364,21 +365,34 @@ template <int B> VPT_DEV float cvt_ubyte(uint32_t w) {
     else asm("v_cvt_f32_ubyte3 %0, %1" : "=v"(r) : "v"(w));
     return r;
 }
-// the blend of the eight taps held in the two 8-byte windows (l0 | h0 = window +0, l1 | h1 = window +25)
+// SNORM tap: the signed byte B of w as the float an R32F volume of the decoded texels holds, fl32(c / 127) (c >= -127: the storage is
+// clamped at finalize).  fl32(c * (1/127)) is not that float for 22 of the byte values; fma(c, hi, c * lo) with hi + lo = 1/127 split
+// into two floats is, for every c in [-128, 255] (exhaustive check: tests/test_volume_formats.py).  The compiler sign-extends and converts
+// the byte in ONE instruction (v_cvt_f32_i32 with an SDWA sext byte select, the signed twin of v_cvt_f32_ubyteN) and pairs the taps'
+// mul / fma into v_pk_mul_f32 / v_pk_fma_f32: k_mip's body 1 263 instructions against 1 166 for R8 and 1 052 for R32F.
+#define VPT_SNORM_HI 0x1.020408p-7f      // fl32(1/127)
+#define VPT_SNORM_LO 0x1.020408p-35f     // fl32(1/127 - VPT_SNORM_HI)
+VPT_DEV float snorm_decode(float c) { return fmaf(c, VPT_SNORM_HI, c * VPT_SNORM_LO); }
+template <int B> VPT_DEV float snorm_byte(uint32_t w) { return snorm_decode((float)(int32_t)(int8_t)(uint8_t)(w >> (8 * B))); }
+// byte -> the tap's float: UNSIGNED_BYTE volumes keep the integer value (normalised once after the blend), SNORM volumes decode it
+template <bool SNORM, int B> VPT_DEV float byte_tap(uint32_t w) { if (SNORM) return snorm_byte<B>(w); return cvt_ubyte<B>(w); }
+// the blend of the eight taps held in the two 8-byte windows (l0 | h0 = window +0, l1 | h1 = window +25).  SNORM: decoded taps, the
+// R32F path's lerps and no normalisation — bit-identical to the R32F volume of the decoded texels (GL: convert, then filter)
+template <bool SNORM = false>
 VPT_DEV float trilinear_blend(uint32_t l0, uint32_t h0, uint32_t l1, uint32_t h1, float fx, float fy, float fz) {
     // byte -> float straight out of the loaded dwords (v_cvt_f32_ubyteN: the byte select is free).  Written as opaque
     // instructions: left to itself the compiler turns (float)b - (float)a into (float)(b - a) and spends 18 integer-class
     // instructions (shifts, SDWA subtracts, two conversions per pair) where 8 conversions + 4 fp32 subtracts do —
     // integer-class VALU instructions cost ~4.3 cycles per wave on this chip against ~2.6 for fp32 add/mul/fma
     // (tools/valu_rates.hip).  Same values, same results.
-    float c000 = cvt_ubyte<0>(l0), c100 = cvt_ubyte<1>(l0);
-    float c010 = cvt_ubyte<1>(h0), c110 = cvt_ubyte<2>(h0);
-    float c001 = cvt_ubyte<0>(l1), c101 = cvt_ubyte<1>(l1);
-    float c011 = cvt_ubyte<1>(h1), c111 = cvt_ubyte<2>(h1);
+    float c000 = byte_tap<SNORM, 0>(l0), c100 = byte_tap<SNORM, 1>(l0);
+    float c010 = byte_tap<SNORM, 1>(h0), c110 = byte_tap<SNORM, 2>(h0);
+    float c001 = byte_tap<SNORM, 0>(l1), c101 = byte_tap<SNORM, 1>(l1);
+    float c011 = byte_tap<SNORM, 1>(h1), c111 = byte_tap<SNORM, 2>(h1);
     float c00 = lerpf(c000, c100, fx), c10 = lerpf(c010, c110, fx);
     float c01 = lerpf(c001, c101, fx), c11 = lerpf(c011, c111, fx);
     float c0 = lerpf(c00, c10, fy), c1 = lerpf(c01, c11, fy);
-    return lerpf(c0, c1, fz) * VPT_INV255;
+    return SNORM ? lerpf(c0, c1, fz) : lerpf(c0, c1, fz) * VPT_INV255;
 }
 // the two 12-byte windows of the ALIGNED form, by GLOBAL loads: `a` = the (byte-aligned) address of the cell's first tap.  The dword-aligned
 // address is formed by pointer arithmetic — round 3 went through uintptr_t, which loses the address space: the compiler emitted flat_load,
@@ -392,6 +406,7 @@ VPT_DEV TapWindow load_window(const uint8_t *a, uint32_t phase) {
 // the same with the address still in its two parts — the uniform base of the brick array and the 32-bit offset of the cell (volumes up to
 // 4 GiB of bricks) —: the dword alignment is taken off the OFFSET, and the load keeps global_load's SGPR-base + VGPR-offset form (no 64-bit
 // address arithmetic per window).  The brick array is 256-byte aligned, so the byte phase of the address is the offset's.
+template <bool SNORM = false>
 VPT_DEV float aligned_taps(const uint8_t *base, uint32_t off, float fx, float fy, float fz) {
     const uint32_t o1 = off + 25u, s0 = off & 3u, s1 = o1 & 3u;
     TapWindow q0, q1;
@@ -399,7 +414,7 @@ VPT_DEV float aligned_taps(const uint8_t *base, uint32_t off, float fx, float fy
     __builtin_memcpy(&q1, __builtin_assume_aligned(base + (o1 - s1), 4), 12);
     const uint32_t l0 = __builtin_amdgcn_alignbyte(q0.b, q0.a, s0), h0 = __builtin_amdgcn_alignbyte(q0.c, q0.b, s0);
     const uint32_t l1 = __builtin_amdgcn_alignbyte(q1.b, q1.a, s1), h1 = __builtin_amdgcn_alignbyte(q1.c, q1.b, s1);
-    return trilinear_blend(l0, h0, l1, h1, fx, fy, fz);
+    return trilinear_blend<SNORM>(l0, h0, l1, h1, fx, fy, fz);
 }
 template <int V>
 VPT_DEV float trilinear_taps(const uint8_t *a, float fx, float fy, float fz) {
@@ -415,7 +430,7 @@ VPT_DEV float trilinear_taps(const uint8_t *a, float fx, float fy, float fz) {
         __builtin_memcpy(&w1, a + 25, 8);
         l0 = (uint32_t)w0; h0 = (uint32_t)(w0 >> 32); l1 = (uint32_t)w1; h1 = (uint32_t)(w1 >> 32);
     }
-    return trilinear_blend(l0, h0, l1, h1, fx, fy, fz);
+    return trilinear_blend<(V & VPT_V_SNORM) != 0>(l0, h0, l1, h1, fx, fy, fz);
 }
 // ---- column records (round 4) -------------------------------------------------------------------------------------------
 // The photons of the MCM renderer sample at independent random positions: after its first event no two lanes of a wave share a
@@ -517,16 +532,18 @@ VPT_DEV uint32_t boundary_cell_lane(const DevVolume &v, f3 p, float &out_fa, flo
     out_fa = fa; out_fb = fb;
     return f * v.atlas_face + ((b << v.atlas_shift) + a);
 }
+template <bool SNORM = false>
 VPT_DEV float boundary_blend(uint32_t w, float fa, float fb) {
-    float c00 = cvt_ubyte<0>(w), c10 = cvt_ubyte<1>(w), c01 = cvt_ubyte<2>(w), c11 = cvt_ubyte<3>(w);
-    return lerpf(lerpf(c00, c10, fa), lerpf(c01, c11, fa), fb) * VPT_INV255;
+    float c00 = byte_tap<SNORM, 0>(w), c10 = byte_tap<SNORM, 1>(w), c01 = byte_tap<SNORM, 2>(w), c11 = byte_tap<SNORM, 3>(w);
+    const float r = lerpf(lerpf(c00, c10, fa), lerpf(c01, c11, fa), fb);
+    return SNORM ? r : r * VPT_INV255;
 }
-// texture(uVolume, clamp(p)).rg through the boundary atlas for ANY volume format (V: VPT_V_NEAREST | VPT_V_RG | VPT_V_F32): channel c's faces lie
+// texture(uVolume, clamp(p)).rg through the boundary atlas for ANY volume format (V: VPT_V_NEAREST | VPT_V_RG | VPT_V_F32 | VPT_V_SNORM): channel c's faces lie
 // 6 * atlas_face cells behind channel c - 1's; float volumes keep four floats per cell.  Same texels, same order of operations as
 // sample_volume_rg<V> at the clamped position (float texels: finite ones, see vpt_volume_finalize).  Precondition as boundary_cell's.
 template <int V>
 VPT_DEV f2 sample_boundary_rg(const DevVolume &v, f3 p) {
-    constexpr bool NEAREST = (V & VPT_V_NEAREST) != 0, RG = (V & VPT_V_RG) != 0, F32 = (V & VPT_V_F32) != 0;
+    constexpr bool NEAREST = (V & VPT_V_NEAREST) != 0, RG = (V & VPT_V_RG) != 0, F32 = (V & VPT_V_F32) != 0, SNORM = (V & VPT_V_SNORM) != 0;
     float fa, fb;
     const uint32_t idx = boundary_cell_lane<NEAREST>(v, p, fa, fb);
     float val[2] = { 0.0f, 0.0f };
@@ -538,7 +555,8 @@ VPT_DEV f2 sample_boundary_rg(const DevVolume &v, f3 p) {
             val[c] = NEAREST ? t.x : lerpf(lerpf(t.x, t.y, fa), lerpf(t.z, t.w, fa), fb);
         } else {
             const uint32_t w = v.atlas[cell];
-            val[c] = NEAREST ? cvt_ubyte<0>(w) * VPT_INV255 : boundary_blend(w, fa, fb);
+            if (SNORM) val[c] = NEAREST ? snorm_byte<0>(w) : boundary_blend<true>(w, fa, fb);
+            else val[c] = NEAREST ? cvt_ubyte<0>(w) * VPT_INV255 : boundary_blend(w, fa, fb);
         }
     }
     return f2{ val[0], val[1] };
@@ -554,6 +572,7 @@ template <int V>
 VPT_DEV f2 sample_volume_rg(const DevVolume &v, const LdsTables &t, f3 p) {
     constexpr bool WIDE = (V & VPT_V_WIDE) != 0;
     constexpr bool RG = (V & VPT_V_RG) != 0;
+    constexpr bool SNORM = (V & VPT_V_SNORM) != 0;
     if (V & VPT_V_F32) {
         // FLOAT texels (Volume.js:84-105 `FLOAT` / `HALF_FLOAT`; LINEAR filtering of float textures: OES_texture_float_linear,
         // RenderingContext.js:78): the brick holds 5^3 floats, a row's two taps are one dword-aligned 8-byte load; same
@@ -585,6 +604,7 @@ VPT_DEV f2 sample_volume_rg(const DevVolume &v, const LdsTables &t, f3 p) {
     if (V & VPT_V_NEAREST) {
         uint32_t x = nearest_cell(p.x, v.fnx, v.hx), y = nearest_cell(p.y, v.fny, v.hy), z = nearest_cell(p.z, v.fnz, v.hz);
         const uint8_t *a = cell_addr<WIDE>(v, t, x, y, z);
+        if (SNORM) return f2{ snorm_decode((float)(int8_t)a[0]), RG ? snorm_decode((float)(int8_t)a[128]) : 0.0f };
         return f2{ (float)a[0] * VPT_INV255, RG ? (float)a[128] * VPT_INV255 : 0.0f };
     }
     uint32_t x, y, z; float fx, fy, fz;
@@ -597,7 +617,7 @@ VPT_DEV f2 sample_volume_rg(const DevVolume &v, const LdsTables &t, f3 p) {
     }
     if ((V & VPT_V_ALIGNED) && !WIDE) {
         const uint32_t off = t.tx[x] + t.ty[y] + t.tz[z];
-        return f2{ aligned_taps(v.bricks, off, fx, fy, fz), RG ? aligned_taps(v.bricks, off + 128u, fx, fy, fz) : 0.0f };
+        return f2{ aligned_taps<SNORM>(v.bricks, off, fx, fy, fz), RG ? aligned_taps<SNORM>(v.bricks, off + 128u, fx, fy, fz) : 0.0f };
     }
     const uint8_t *a = cell_addr<WIDE>(v, t, x, y, z);
     return f2{ trilinear_taps<V>(a, fx, fy, fz), RG ? trilinear_taps<V>(a + 128, fx, fy, fz) : 0.0f };

@@ -135,7 +135,16 @@ static int launch_dos(vpt_renderer *r, PassArgs &a, const int rect[4]) {
         case 40: return launch_dos_slice(k_dos_slice<40 | VPT_DOS_TAPS>, r, a, rect);
         case 41: return launch_dos_slice(k_dos_slice<41 | VPT_DOS_TAPS>, r, a, rect);
         case 42: return launch_dos_slice(k_dos_slice<42 | VPT_DOS_TAPS>, r, a, rect);
-        default: return launch_dos_slice(k_dos_slice<43 | VPT_DOS_TAPS>, r, a, rect);
+        case 43: return launch_dos_slice(k_dos_slice<43 | VPT_DOS_TAPS>, r, a, rect);
+        case 128: return launch_dos_slice(k_dos_slice<128 | VPT_DOS_TAPS>, r, a, rect);
+        case 129: return launch_dos_slice(k_dos_slice<129 | VPT_DOS_TAPS>, r, a, rect);
+        case 130: return launch_dos_slice(k_dos_slice<130 | VPT_DOS_TAPS>, r, a, rect);
+        case 131: return launch_dos_slice(k_dos_slice<131 | VPT_DOS_TAPS>, r, a, rect);
+        case 136: return launch_dos_slice(k_dos_slice<136 | VPT_DOS_TAPS>, r, a, rect);
+        case 137: return launch_dos_slice(k_dos_slice<137 | VPT_DOS_TAPS>, r, a, rect);
+        case 138: return launch_dos_slice(k_dos_slice<138 | VPT_DOS_TAPS>, r, a, rect);
+        case 139: return launch_dos_slice(k_dos_slice<139 | VPT_DOS_TAPS>, r, a, rect);
+        default: return fail(VPT_ERR_INVALID, "no DOS kernel for variant %d", variant_of(r));
     }
 }
 // _integrateFrame of the DOS renderer (DOSRenderer.js:199-259): `count` full-screen passes, pass s with

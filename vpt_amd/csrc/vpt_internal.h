@@ -51,6 +51,9 @@ struct vpt_volume {
     int nx, ny, nz;
     int channels;          // 1 = R8 / R32F, 2 = RG8 (interleaved)
     bool f32;              // FLOAT texels (VPT_FORMAT_R32F): 4 bytes per voxel, 512-byte brick slots
+    bool snorm;            // BYTE texels (VPT_FORMAT_R8_SNORM / RG8_SNORM): stored like R8 / RG8, sampled through VPT_V_SNORM
+    int packed;            // packed source format (VPT_FORMAT_RGB565 ..; 0: none): uploads are decoded into RG32F storage (f32, 2 channels)
+    int packed_bytes;      // bytes per packed source texel: 2 or 4
     int vox_bytes;         // bytes per voxel of the linear storage: channels * (f32 ? 4 : 1)
     int filter;
     uint8_t *linear;       // nx*ny*nz*channels, the "texture storage" blocks are uploaded into
@@ -352,13 +355,15 @@ static int launch_sampling(K kernel, vpt_renderer *r, const PassArgs &a, unsigne
 #define VPT_RECORDS_AUTO_BYTES (512ull << 20)
 static inline bool renderer_uses_records(const vpt_renderer *r) {
     const vpt_volume *v = r->vol;
-    if (!(r->kind == VPT_RENDERER_MCM && v && v->channels == 1 && !v->f32 && v->filter == VPT_FILTER_LINEAR && v->rtab32 != nullptr)) return false;
+    if (!(r->kind == VPT_RENDERER_MCM && v && v->channels == 1 && !v->f32 && !v->snorm && v->filter == VPT_FILTER_LINEAR && v->rtab32 != nullptr)) return false;
     return r->column_records == 1 || (r->column_records == 2 && v->brick_bytes > VPT_RECORDS_AUTO_BYTES);
 }
 static inline int variant_of(const vpt_renderer *r) {
     return ((r->vol->wide || (renderer_uses_records(r) && r->vol->rec_wide)) ? VPT_V_WIDE : 0) | (r->vol->filter == VPT_FILTER_NEAREST ? VPT_V_NEAREST : 0) | (r->vol->channels == 2 ? VPT_V_RG : 0) |
-           (r->vol->f32 ? VPT_V_F32 : 0);
+           (r->vol->f32 ? VPT_V_F32 : 0) | (r->vol->snorm ? VPT_V_SNORM : 0);
 }
+// an UNSIGNED_BYTE one-channel volume: what the column records and the persistent forms take
+static inline bool unsigned_r8(const vpt_volume *v) { return v->channels == 1 && !v->f32 && !v->snorm; }
 #define LAUNCH_S(KT, r, a) do { \
     unsigned g_ = (unsigned)(r)->ntiles; \
     switch (variant_of(r)) { \
@@ -377,7 +382,16 @@ static inline int variant_of(const vpt_renderer *r) {
         case 40: VPT_TRY(launch_sampling(KT(40), (r), (a), g_)); break; \
         case 41: VPT_TRY(launch_sampling(KT(41), (r), (a), g_)); break; \
         case 42: VPT_TRY(launch_sampling(KT(42), (r), (a), g_)); break; \
-        default: VPT_TRY(launch_sampling(KT(43), (r), (a), g_)); break; \
+        case 43: VPT_TRY(launch_sampling(KT(43), (r), (a), g_)); break; \
+        case 128: VPT_TRY(launch_sampling(KT(128), (r), (a), g_)); break; \
+        case 129: VPT_TRY(launch_sampling(KT(129), (r), (a), g_)); break; \
+        case 130: VPT_TRY(launch_sampling(KT(130), (r), (a), g_)); break; \
+        case 131: VPT_TRY(launch_sampling(KT(131), (r), (a), g_)); break; \
+        case 136: VPT_TRY(launch_sampling(KT(136), (r), (a), g_)); break; \
+        case 137: VPT_TRY(launch_sampling(KT(137), (r), (a), g_)); break; \
+        case 138: VPT_TRY(launch_sampling(KT(138), (r), (a), g_)); break; \
+        case 139: VPT_TRY(launch_sampling(KT(139), (r), (a), g_)); break; \
+        default: return fail(VPT_ERR_INVALID, "no sampling kernel for variant %d", variant_of(r)); \
     } } while (0)
 
 struct Timed {   // HIP events around the dominant kernel (or around one graph replay of `launches` of them)

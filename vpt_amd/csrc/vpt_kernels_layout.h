@@ -32,6 +32,53 @@ __global__ void k_blit_block(uint8_t *vol, int nx, int ny, const uint8_t *blk, i
         for (int c = 0; c < ch; c++) vol[dst + c] = blk[t * ch + c];
     }
 }
+// ---- packed texel types (GL ES 3.0 section 3.8.3): the (r, g) floats of one word -----------------------------------------------
+// UNORM c of b bits: fl32(c / (2^b - 1)) (the library is built with correctly rounded fp32 division)
+VPT_DEV float unorm_channel(uint32_t c, float max) { return (float)c / max; }
+// unsigned 11- or 10-bit float (5-bit exponent, M-bit mantissa): e = 0 denormal m 2^-14 / 2^M, e = 31 Inf (m = 0) or NaN
+VPT_DEV float unsigned_small_float(uint32_t bits, int M) {
+    const uint32_t e = bits >> M, m = bits & ((1u << M) - 1u);
+    if (e == 0u) return (float)m * __uint_as_float((uint32_t)(127 - 14 - M) << 23);      // exact: m < 2^M, a power-of-two scale
+    if (e == 31u) return m == 0u ? __uint_as_float(0x7f800000u) : __uint_as_float(0x7fc00000u);
+    return __uint_as_float(((e - 15u + 127u) << 23) | (m << (23 - M)));                 // the same value as an fp32 bit pattern
+}
+VPT_DEV float2 decode_packed(uint32_t w, int format) {
+    switch (format) {
+        case VPT_FORMAT_RGB565: return make_float2(unorm_channel((w >> 11) & 31u, 31.0f), unorm_channel((w >> 5) & 63u, 63.0f));
+        case VPT_FORMAT_RGBA4: return make_float2(unorm_channel((w >> 12) & 15u, 15.0f), unorm_channel((w >> 8) & 15u, 15.0f));
+        case VPT_FORMAT_RGB5_A1: return make_float2(unorm_channel((w >> 11) & 31u, 31.0f), unorm_channel((w >> 6) & 31u, 31.0f));
+        case VPT_FORMAT_RGB10_A2: return make_float2(unorm_channel(w & 1023u, 1023.0f), unorm_channel((w >> 10) & 1023u, 1023.0f));
+        case VPT_FORMAT_R11F_G11F_B10F: return make_float2(unsigned_small_float(w & 2047u, 6), unsigned_small_float((w >> 11) & 2047u, 6));
+        default: {                                                                            // RGB9_E5: m 2^(e - 24), exact
+            const float scale = __uint_as_float(((w >> 27) + 103u) << 23);
+            return make_float2((float)(w & 511u) * scale, (float)((w >> 9) & 511u) * scale);
+        }
+    }
+}
+// texSubImage3D of a packed block (bw x bh x bd words of 2 or 4 bytes) -> the (r, g) floats at (x0, y0, z0) of the RG32F linear volume
+__global__ void k_decode_packed(float2 *vol, int nx, int ny, const uint8_t *blk, int format, int x0, int y0, int z0, int bw, int bh, int bd) {
+    const size_t n = (size_t)bw * bh * bd;
+    const bool half = format == VPT_FORMAT_RGB565 || format == VPT_FORMAT_RGBA4 || format == VPT_FORMAT_RGB5_A1;
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (size_t)gridDim.x * blockDim.x) {
+        int x = (int)(t % bw); size_t r = t / bw; int y = (int)(r % bh); int z = (int)(r / bh);
+        uint32_t w;
+        if (half) { uint16_t h; __builtin_memcpy(&h, blk + 2 * t, 2); w = h; }
+        else __builtin_memcpy(&w, blk + 4 * t, 4);
+        vol[((size_t)(z0 + z) * ny + (y0 + y)) * nx + (x0 + x)] = decode_packed(w, format);
+    }
+}
+// SNORM volumes: byte 0x80 (-128) -> 0x81 (-127) over the linear storage (n bytes), four bytes per thread and step
+__global__ void k_snorm_clamp(uint8_t *lin, size_t n) {
+    const size_t n4 = n / 4;
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < n4; t += (size_t)gridDim.x * blockDim.x) {
+        const uint32_t w = ((const uint32_t *)lin)[t];
+        uint32_t o = w;
+        for (int k = 0; k < 4; k++) if (((w >> (8 * k)) & 0xffu) == 0x80u) o |= 1u << (8 * k);
+        if (o != w) ((uint32_t *)lin)[t] = o;
+    }
+    for (size_t t = 4 * n4 + (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (size_t)gridDim.x * blockDim.x)
+        if (lin[t] == 0x80u) lin[t] = 0x81u;
+}
 // linear volume -> apron bricks in Morton order; one 128-thread workgroup per brick
 // (3-D grid: a 1-D grid of 2048^3's 2^27 bricks x 128 threads exceeds HIP's 2^32 work-items per dimension)
 // `ch` = 1 (R8: 128-byte slots) or 2 (RG8: 256-byte slots, the R brick at +0 and the G brick at +128)

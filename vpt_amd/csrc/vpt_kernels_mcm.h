@@ -187,7 +187,7 @@ VPT_DEV float4 mcm_sample_finish(const PassArgs &a, const LdsTables &t, const Sa
 }
 template <int V>
 VPT_DEV float4 mcm_sample(const PassArgs &a, const LdsTables &t, f3 p, bool oob) {
-    if (!(V & (VPT_V_NEAREST | VPT_V_RG | VPT_V_F32))) return mcm_sample_finish<V>(a, t, mcm_sample_issue<V>(a, t, p, oob));
+    if (!(V & (VPT_V_NEAREST | VPT_V_RG | VPT_V_F32 | VPT_V_SNORM))) return mcm_sample_finish<V>(a, t, mcm_sample_issue<V>(a, t, p, oob));
     float4 vs = sample_volume_color<V>(a, t, p);
     asm volatile("" : "+v"(vs.w));
     return vs;
@@ -626,7 +626,7 @@ VPT_DEV void mcm_events_miss(const PassArgs &a, const float4 *tf, Photon &ph, fl
     for (uint32_t s = 0u; s < a.steps; s++) {
         float dist = random_exponential(state, a.inv_extinction);
         ph.position = madd3(ph.position, dist, ph.direction);
-        constexpr bool OTHER = (V & (VPT_V_NEAREST | VPT_V_RG | VPT_V_F32)) != 0;      // another volume format: the one-phase sample
+        constexpr bool OTHER = (V & (VPT_V_NEAREST | VPT_V_RG | VPT_V_F32 | VPT_V_SNORM)) != 0;      // another volume format: the one-phase sample
         MissLoad l = { 0u, 0.0f, 0.0f };
         if (OTHER) miss_sample_any<V>(a, tf, ph.position);
         else l = miss_sample_issue<CHECK>(a, ph.position, a.violations);
@@ -645,7 +645,7 @@ VPT_DEV void mcm_events_miss_fast(const PassArgs &a, const float4 *tf, const Fas
     for (uint32_t s = 0u; s < a.steps; s++) {
         float dist = fmaf(hw_log2(pcg_float(state)), ld, ld32);
         ph.position = madd3(ph.position, dist, ph.direction);
-        constexpr bool OTHER = (V & (VPT_V_NEAREST | VPT_V_RG | VPT_V_F32)) != 0;
+        constexpr bool OTHER = (V & (VPT_V_NEAREST | VPT_V_RG | VPT_V_F32 | VPT_V_SNORM)) != 0;
         MissLoad l = { 0u, 0.0f, 0.0f };
         if (OTHER) miss_sample_any<V>(a, tf, ph.position);
         else l = miss_sample_issue<CHECK>(a, ph.position, a.violations);
@@ -659,7 +659,7 @@ VPT_DEV void mcm_events_miss_fast(const PassArgs &a, const float4 *tf, const Fas
 // (8 waves per SIMD = 64 VGPRs; the contract arithmetic of the other volume formats needs two more: 7 waves there instead of a spill)
 template <bool FUSE_RENDER, int V, bool CHECK, bool LATE>
 __global__ void __launch_bounds__(VPT_BLOCK)
-__attribute__((amdgpu_waves_per_eu(((V & (VPT_V_NEAREST | VPT_V_RG | VPT_V_F32)) && !(V & VPT_V_FAST)) ? 7 : 8, 8))) k_mcm_miss(PassArgs a) {
+__attribute__((amdgpu_waves_per_eu(((V & (VPT_V_NEAREST | VPT_V_RG | VPT_V_F32 | VPT_V_SNORM)) && !(V & VPT_V_FAST)) ? 7 : 8, 8))) k_mcm_miss(PassArgs a) {
     frame_select(a, 0);
     Pix p = map_pixel(a.pm);
     float4 s1 = make_float4(0.0f, 0.0f, 1.0f, 0.0f), s3 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);

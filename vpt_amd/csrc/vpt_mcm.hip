@@ -25,11 +25,12 @@ static bool mcm_classes_usable(const vpt_renderer *r, const PassArgs &a) {
     return r->cls.enabled && r->cls.valid && a.blur == 0.0f && memcmp(r->cls.mvp, a.mvp_inv.m, sizeof(r->cls.mvp)) == 0;
 }
 // the kernel side of it: the volume's boundary atlas (what k_mcm_miss samples; every format since round 4), no persistent-wave option
+// (SNORM volumes: the general pass — no MISS-tile kernel form of their own)
 static bool mcm_classes_runnable(const vpt_renderer *r, const PassArgs &a) {
-    return a.vol.atlas != nullptr && !r->mcm_persistent;
+    return a.vol.atlas != nullptr && !r->mcm_persistent && !r->vol->snorm;
 }
 // ... and of the bucket kernels (and of the HIT-tile kernel's early form): LINEAR one-channel byte volumes
-static bool mcm_plain_volume(const vpt_renderer *r) { return (variant_of(r) & ~VPT_V_WIDE) == 0; }
+static bool mcm_plain_volume(const vpt_renderer *r) { return (variant_of(r) & ~VPT_V_WIDE) == 0 && unsigned_r8(r->vol); }
 template <bool FUSE> static PassKernel format_miss_kernel(int v, bool fast) {
     if (fast) FORMAT_CASES((PassKernel)k_mcm_miss<FUSE, F | VPT_V_FAST, false, true>)
     FORMAT_CASES((PassKernel)k_mcm_miss<FUSE, F, false, true>)
@@ -92,6 +93,7 @@ static int launch_mcm_classes(vpt_renderer *r, const PassArgs &a) {
                          : (PassKernel)k_mcm_miss<FUSE, 0, true, true>;
     else km = fast ? (late ? (PassKernel)k_mcm_miss<FUSE, VPT_V_FAST, false, true> : (PassKernel)k_mcm_miss<FUSE, VPT_V_FAST, false, false>)
                    : (PassKernel)k_mcm_miss<FUSE, 0, false, true>;
+    if (!kh || !km) return fail(VPT_ERR_INVALID, "no MCM tile-class kernels for variant %d", variant_of(r));
     const size_t lds_hit = lds_bytes(r), lds_miss = (size_t)r->tf_w * 2 * sizeof(float4);
     if (lds_hit > 160 * 1024) return fail(VPT_ERR_UNSUPPORTED, "transfer function + volume tables need %zu B of LDS (> 160 KiB)", lds_hit);
     if (lds_hit > 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void *)kh, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_hit));
@@ -182,6 +184,7 @@ int mcm_bucket(vpt_renderer *r, const PassArgs &a, const FrameVar *v, int count,
     BucketKernel kh, km;
     if (display_table) bucket_kernels<true>(class_variant(r, a), early, &kh, &km);
     else bucket_kernels<false>(class_variant(r, a), early, &kh, &km);
+    if (!kh || !km) return fail(VPT_ERR_INVALID, "no MCM tile-class kernels for variant %d", variant_of(r));
     const size_t lds_hit = lds_bytes(r), lds_miss = (size_t)r->tf_w * 2 * sizeof(float4);
     if (lds_hit > 160 * 1024) return fail(VPT_ERR_UNSUPPORTED, "transfer function + volume tables need %zu B of LDS (> 160 KiB)", lds_hit);
     if (lds_hit > 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void *)kh, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_hit));
@@ -251,7 +254,7 @@ static int launch_mcm_pass(vpt_renderer *r, const PassArgs &a) {
     if (two_streams) VPT_TRY(ensure_split_streams(r));
     if (same && r->cls.enabled && mcm_classes_runnable(r, a) && (two_streams || r->cls.one_stream)) return launch_mcm_classes<FUSE>(r, a);
     VPT_TRY(mcm_materialize(r));
-    if (r->mcm_persistent && r->vol->channels == 1 && !r->vol->f32) { LAUNCH_MCM_PERSIST(FUSE, r, a); return VPT_OK; }
+    if (r->mcm_persistent && unsigned_r8(r->vol)) { LAUNCH_MCM_PERSIST(FUSE, r, a); return VPT_OK; }
     return mcm_general_pass(r, a, FUSE);
 }
 

@@ -20,14 +20,22 @@ static inline int class_variant(const vpt_renderer *r, const PassArgs &a) {
         default: { constexpr int V = VPT_V_REC | VPT_V_FAST | VPT_V_WIDE; return __VA_ARGS__; } }
 // NEAREST / two-channel / float volumes: the HIT tiles through the general kernel of the volume's variant (from a tile list), the MISS
 // tiles through the one-phase sampler of k_mcm_miss (miss_sample_any)
-#define FORMAT_CASES(...) switch (v & (VPT_V_NEAREST | VPT_V_RG | VPT_V_F32)) { \
+#define FORMAT_CASES(...) switch (v & (VPT_V_NEAREST | VPT_V_RG | VPT_V_F32 | VPT_V_SNORM)) { \
         case VPT_V_NEAREST: { constexpr int F = VPT_V_NEAREST; return __VA_ARGS__; } \
         case VPT_V_RG: { constexpr int F = VPT_V_RG; return __VA_ARGS__; } \
         case VPT_V_RG | VPT_V_NEAREST: { constexpr int F = VPT_V_RG | VPT_V_NEAREST; return __VA_ARGS__; } \
         case VPT_V_F32: { constexpr int F = VPT_V_F32; return __VA_ARGS__; } \
         case VPT_V_F32 | VPT_V_NEAREST: { constexpr int F = VPT_V_F32 | VPT_V_NEAREST; return __VA_ARGS__; } \
         case VPT_V_F32 | VPT_V_RG: { constexpr int F = VPT_V_F32 | VPT_V_RG; return __VA_ARGS__; } \
-        default: { constexpr int F = VPT_V_F32 | VPT_V_RG | VPT_V_NEAREST; return __VA_ARGS__; } }
+        case VPT_V_F32 | VPT_V_RG | VPT_V_NEAREST: { constexpr int F = VPT_V_F32 | VPT_V_RG | VPT_V_NEAREST; return __VA_ARGS__; } \
+        default: return nullptr; }
+// the SNORM formats (the general kernel only: no MISS-tile form)
+#define SNORM_CASES(...) switch (v & (VPT_V_NEAREST | VPT_V_RG | VPT_V_F32 | VPT_V_SNORM)) { \
+        case VPT_V_SNORM: { constexpr int F = VPT_V_SNORM; return __VA_ARGS__; } \
+        case VPT_V_SNORM | VPT_V_NEAREST: { constexpr int F = VPT_V_SNORM | VPT_V_NEAREST; return __VA_ARGS__; } \
+        case VPT_V_SNORM | VPT_V_RG: { constexpr int F = VPT_V_SNORM | VPT_V_RG; return __VA_ARGS__; } \
+        case VPT_V_SNORM | VPT_V_RG | VPT_V_NEAREST: { constexpr int F = VPT_V_SNORM | VPT_V_RG | VPT_V_NEAREST; return __VA_ARGS__; } \
+        default: return nullptr; }
 // vpt_mcm_hit.hip: k_mcm_integrate / k_mcm_integrate_early by variant (fuse: + _renderFrame)
 PassKernel mcm_hit_kernel(bool fuse, int v, bool early);                    // v: class_variant()
 PassKernel mcm_format_hit_kernel(bool fuse, int v, bool wide, bool fast);   // v: variant_of(), another volume format

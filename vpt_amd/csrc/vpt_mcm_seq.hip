@@ -44,7 +44,16 @@ int mcm_multi(vpt_renderer *r, const PassArgs &a, uint32_t npasses, uint2 *ring)
         case 40: return ring ? launch_frames(k_mcm_frames<40 | F>, r, a, npasses, ring) : launch_multi(k_mcm_multi<40 | F>, r, a, npasses); \
         case 41: return ring ? launch_frames(k_mcm_frames<41 | F>, r, a, npasses, ring) : launch_multi(k_mcm_multi<41 | F>, r, a, npasses); \
         case 42: return ring ? launch_frames(k_mcm_frames<42 | F>, r, a, npasses, ring) : launch_multi(k_mcm_multi<42 | F>, r, a, npasses); \
-        default: return ring ? launch_frames(k_mcm_frames<43 | F>, r, a, npasses, ring) : launch_multi(k_mcm_multi<43 | F>, r, a, npasses); }
+        case 43: return ring ? launch_frames(k_mcm_frames<43 | F>, r, a, npasses, ring) : launch_multi(k_mcm_multi<43 | F>, r, a, npasses); \
+        case 128: return ring ? launch_frames(k_mcm_frames<128 | F>, r, a, npasses, ring) : launch_multi(k_mcm_multi<128 | F>, r, a, npasses); \
+        case 129: return ring ? launch_frames(k_mcm_frames<129 | F>, r, a, npasses, ring) : launch_multi(k_mcm_multi<129 | F>, r, a, npasses); \
+        case 130: return ring ? launch_frames(k_mcm_frames<130 | F>, r, a, npasses, ring) : launch_multi(k_mcm_multi<130 | F>, r, a, npasses); \
+        case 131: return ring ? launch_frames(k_mcm_frames<131 | F>, r, a, npasses, ring) : launch_multi(k_mcm_multi<131 | F>, r, a, npasses); \
+        case 136: return ring ? launch_frames(k_mcm_frames<136 | F>, r, a, npasses, ring) : launch_multi(k_mcm_multi<136 | F>, r, a, npasses); \
+        case 137: return ring ? launch_frames(k_mcm_frames<137 | F>, r, a, npasses, ring) : launch_multi(k_mcm_multi<137 | F>, r, a, npasses); \
+        case 138: return ring ? launch_frames(k_mcm_frames<138 | F>, r, a, npasses, ring) : launch_multi(k_mcm_multi<138 | F>, r, a, npasses); \
+        case 139: return ring ? launch_frames(k_mcm_frames<139 | F>, r, a, npasses, ring) : launch_multi(k_mcm_multi<139 | F>, r, a, npasses); \
+        default: return fail(VPT_ERR_INVALID, "no frame-sequence kernel for variant %d", variant_of(r)); }
     if (r->fast_math) MULTI_CASES(VPT_V_FAST)
     MULTI_CASES(0)
 #undef MULTI_CASES

@@ -16,6 +16,15 @@ GL_RED, GL_R8, GL_UNSIGNED_BYTE = 6403, 33321, 5121
 GL_RG, GL_RG8 = 33319, 33323              # two-channel volumes (value + e.g. gradient magnitude) of BVP manifests
 GL_RGB, GL_RGB8, GL_RGBA, GL_RGBA8 = 6407, 32849, 6408, 32856      # byte manifests with more channels: texture(uVolume, p).rg reads the first two
 GL_FLOAT, GL_HALF_FLOAT, GL_R32F, GL_R16F = 5126, 5131, 33326, 33325   # float volumes (Volume.js:84-105 maps FLOAT -> Float32Array, HALF_FLOAT -> Uint16Array)
+GL_BYTE = 5120                            # signed-normalised volumes (Volume.js:84-105 maps BYTE -> Int8Array)
+GL_R8_SNORM, GL_RG8_SNORM, GL_RGB8_SNORM, GL_RGBA8_SNORM = 0x8F94, 0x8F95, 0x8F96, 0x8F97
+# packed texel types (Uint16Array / Uint32Array) and the one sized internal format each can be filtered as
+GL_UNSIGNED_SHORT_5_6_5, GL_RGB565 = 0x8363, 0x8D62
+GL_UNSIGNED_SHORT_4_4_4_4, GL_RGBA4 = 0x8033, 0x8056
+GL_UNSIGNED_SHORT_5_5_5_1, GL_RGB5_A1 = 0x8034, 0x8057
+GL_UNSIGNED_INT_2_10_10_10_REV, GL_RGB10_A2 = 0x8368, 0x8059
+GL_UNSIGNED_INT_10F_11F_11F_REV, GL_R11F_G11F_B10F = 0x8C3B, 0x8C3A
+GL_UNSIGNED_INT_5_9_9_9_REV, GL_RGB9_E5 = 0x8C3E, 0x8C3D
 
 
 class AbstractReader:

@@ -8,15 +8,37 @@ from . import _native as N
 from .property_bag import EventTarget, CustomEvent
 
 from .readers import (RAWReader, GL_RED, GL_R8, GL_RG, GL_RG8, GL_UNSIGNED_BYTE, GL_RGB, GL_RGB8, GL_RGBA, GL_RGBA8,      # noqa: F401  (re-exported)
-                      GL_FLOAT, GL_HALF_FLOAT, GL_R32F, GL_R16F)
+                      GL_FLOAT, GL_HALF_FLOAT, GL_R32F, GL_R16F,
+                      GL_BYTE, GL_R8_SNORM, GL_RG8_SNORM, GL_RGB8_SNORM, GL_RGBA8_SNORM,
+                      GL_UNSIGNED_SHORT_5_6_5, GL_RGB565, GL_UNSIGNED_SHORT_4_4_4_4, GL_RGBA4, GL_UNSIGNED_SHORT_5_5_5_1, GL_RGB5_A1,
+                      GL_UNSIGNED_INT_2_10_10_10_REV, GL_RGB10_A2, GL_UNSIGNED_INT_10F_11F_11F_REV, GL_R11F_G11F_B10F,
+                      GL_UNSIGNED_INT_5_9_9_9_REV, GL_RGB9_E5)
+
+# (type, format, internalFormat) -> (native format, channels in the file, numpy dtype of a block) for the formats keyed on all three:
+# SNORM bytes (RGB8_SNORM / RGBA8_SNORM keep their first two channels, as RGB8 / RGBA8 do) and the packed types, one word per texel
+_SIZED = {
+    (GL_BYTE, GL_RED, GL_R8_SNORM): ('FORMAT_R8_SNORM', 1, np.int8),
+    (GL_BYTE, GL_RG, GL_RG8_SNORM): ('FORMAT_RG8_SNORM', 2, np.int8),
+    (GL_BYTE, GL_RGB, GL_RGB8_SNORM): ('FORMAT_RG8_SNORM', 3, np.int8),
+    (GL_BYTE, GL_RGBA, GL_RGBA8_SNORM): ('FORMAT_RG8_SNORM', 4, np.int8),
+    (GL_UNSIGNED_SHORT_5_6_5, GL_RGB, GL_RGB565): ('FORMAT_RGB565', 1, np.uint16),
+    (GL_UNSIGNED_SHORT_4_4_4_4, GL_RGBA, GL_RGBA4): ('FORMAT_RGBA4', 1, np.uint16),
+    (GL_UNSIGNED_SHORT_5_5_5_1, GL_RGBA, GL_RGB5_A1): ('FORMAT_RGB5_A1', 1, np.uint16),
+    (GL_UNSIGNED_INT_2_10_10_10_REV, GL_RGBA, GL_RGB10_A2): ('FORMAT_RGB10_A2', 1, np.uint32),
+    (GL_UNSIGNED_INT_10F_11F_11F_REV, GL_RGB, GL_R11F_G11F_B10F): ('FORMAT_R11F_G11F_B10F', 1, np.uint32),
+    (GL_UNSIGNED_INT_5_9_9_9_REV, GL_RGB, GL_RGB9_E5): ('FORMAT_RGB9_E5', 1, np.uint32),
+}
 
 
 def device_format(modality):
-    """(native format, channels in the file, numpy dtype of a block) for a manifest's (format, type) — Volume.js:58-60 allocates whatever
-    internalFormat the manifest names and :84-105 `_typize` maps the GL type to a typed array.  What a WebGL2 sampler3D can
-    filter is what is taken here: UNSIGNED_BYTE and FLOAT / HALF_FLOAT (half widens to float exactly) with 1-4 channels — the
-    shaders read .rg, so channels past the second are dropped on upload (R8, RG8; R32F, RG32F).  Integer and 16-bit normalised
-    types cannot be sampled through a float sampler in WebGL2 and raise the reference's error."""
+    """(native format, channels in the file, numpy dtype of a block) for a manifest's (type, format, internalFormat) — Volume.js:58-60
+    allocates whatever internalFormat the manifest names and :84-105 `_typize` maps the GL type to a typed array.  What a WebGL2
+    sampler3D can filter is what is taken here: UNSIGNED_BYTE and FLOAT / HALF_FLOAT (half widens to float exactly) with 1-4 channels —
+    the shaders read .rg, so channels past the second are dropped on upload (R8, RG8; R32F, RG32F) —; BYTE with an SNORM internal format
+    (R8_SNORM, RG8_SNORM; RGB8_SNORM / RGBA8_SNORM keep two channels); and the packed types with the one internal format each names
+    (RGB565, RGBA4, RGB5_A1, RGB10_A2, R11F_G11F_B10F, RGB9_E5: uploaded as words, decoded on the device).  Integer textures need a
+    usampler3D / isampler3D, 16-bit normalised ones an extension the reference does not enable, and 3-D depth textures do not exist in
+    ES 3.0: every other combination raises the reference's error."""
     t, f = modality['type'], modality['format']
     if t == GL_UNSIGNED_BYTE and f in (GL_RED, GL_RG, GL_RGB, GL_RGBA):
         n = {GL_RED: 1, GL_RG: 2, GL_RGB: 3, GL_RGBA: 4}[f]
@@ -24,6 +46,9 @@ def device_format(modality):
     if t in (GL_FLOAT, GL_HALF_FLOAT) and f in (GL_RED, GL_RG, GL_RGB, GL_RGBA):
         n = {GL_RED: 1, GL_RG: 2, GL_RGB: 3, GL_RGBA: 4}[f]
         return (N.FORMAT_R32F if n == 1 else N.FORMAT_RG32F), n, (np.float32 if t == GL_FLOAT else np.float16)
+    sized = _SIZED.get((t, f, modality.get('internalFormat')))
+    if sized is not None:
+        return getattr(N, sized[0]), sized[1], sized[2]
     raise RuntimeError('Unknown volume datatype: %s' % t)                   # Volume.js:103
 
 
@@ -76,7 +101,7 @@ class Volume(EventTarget):
             data = np.frombuffer(raw, dtype=dtype) if isinstance(raw, (bytes, bytearray, memoryview)) else np.asarray(raw).view(dtype).reshape(-1)
             if nch > 2:                                   # RGB8 / RGBA8: texture(uVolume, p).rg reads the first two channels
                 data = data.reshape(-1, nch)[:, :2]
-            if dtype is not np.uint8:
+            if dtype in (np.float16, np.float32):
                 data = data.astype(np.float32)            # HALF_FLOAT widens exactly
             data = np.ascontiguousarray(data)
             N.check(L.vpt_volume_upload_block(self.texture, position['x'], position['y'], position['z'],
@@ -100,9 +125,14 @@ class Volume(EventTarget):
 
     # ---- extension: whole-array upload (one block) for synthetic volumes ----
     @classmethod
-    def from_array(cls, gl, array, filter='linear'):
-        """Upload a [depth][height][width] (uint8: R8; float16 / float32: R32F) or [depth][height][width][2] (RG8 / RG32F) array (host -> HBM once)."""
+    def from_array(cls, gl, array, filter='linear', snorm=False):
+        """Upload a [depth][height][width] (uint8: R8; float16 / float32: R32F) or [depth][height][width][2] (RG8 / RG32F) array (host -> HBM once).
+        ``snorm=True``: the array is int8 and becomes an R8_SNORM / RG8_SNORM volume (texel c reads as max(c / 127, -1))."""
         array = np.asarray(array)
+        if snorm:
+            if array.dtype != np.int8:
+                raise ValueError('an SNORM volume is uploaded from an int8 array')
+            return cls._from_snorm_array(gl, array, filter)
         f32 = array.dtype.kind == 'f'
         array = np.ascontiguousarray(array, dtype=np.float32 if f32 else np.uint8)
         if array.ndim == 4 and array.shape[3] != 2:
@@ -139,12 +169,45 @@ class Volume(EventTarget):
         vol.setFilter(filter)
         return vol
 
+    @classmethod
+    def _from_snorm_array(cls, gl, array, filter):
+        array = np.ascontiguousarray(array)
+        if array.ndim == 4 and array.shape[3] != 2:
+            raise ValueError('a two-channel volume is [depth][height][width][2]')
+        d, h, w = array.shape[:3]
+        channels = 2 if array.ndim == 4 else 1
+        vol = cls(gl, RAWReader(array.view(np.uint8), {'width': w * channels, 'height': h, 'depth': d}))
+        L = N.lib()
+        hnd = C.c_void_p()
+        N.check(L.vpt_volume_create(gl._h, w, h, d, N.FORMAT_RG8_SNORM if channels == 2 else N.FORMAT_R8_SNORM, C.byref(hnd)))
+        vol.texture = hnd
+        zs = max(1, (1 << 30) // (w * h * channels))
+        for z0 in range(0, d, zs):
+            chunk = array[z0:min(d, z0 + zs)]
+            N.check(L.vpt_volume_upload_block(hnd, 0, 0, z0, w, h, chunk.shape[0], chunk.ctypes.data_as(C.c_void_p), chunk.nbytes))
+        N.check(L.vpt_volume_finalize(hnd))
+        vol.metadata = vol._reader.readMetadata()
+        vol.modality = vol.metadata['modalities'][0]
+        vol.modality['dimensions']['width'] = w
+        vol.modality['type'] = GL_BYTE
+        vol.modality['format'], vol.modality['internalFormat'] = (GL_RG, GL_RG8_SNORM) if channels == 2 else (GL_RED, GL_R8_SNORM)
+        for b in vol.metadata['blocks']:
+            b['dimensions']['width'] = w
+        vol.ready = True
+        vol.setFilter(filter)
+        return vol
+
     def upload_block(self, x, y, z, block):
         """(extension) texSubImage3D of one more block into the ready volume: `block` is [depth][height][width] in the volume's texel type;
         the device layouts are rebuilt by the next pass that samples the volume"""
         block = np.ascontiguousarray(block)
         d, h, w = block.shape[:3]
         N.check(N.lib().vpt_volume_upload_block(self.texture, int(x), int(y), int(z), w, h, d, block.ctypes.data_as(C.c_void_p), block.nbytes))
+
+    def upload_block_device(self, x, y, z, w, h, d, device_ptr, nbytes):
+        """(extension) the same from memory already in HBM on the context's device (e.g. a torch tensor's data_ptr())"""
+        N.check(N.lib().vpt_volume_upload_block_device(self.texture, int(x), int(y), int(z), int(w), int(h), int(d),
+                                                       C.c_void_p(int(device_ptr)), int(nbytes)))
 
     def set_wide_tables(self, wide):
         """force the > 4 GiB addressing variant of the kernels (automatic above 4 GiB of bricked data)"""
