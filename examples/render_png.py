@@ -3,6 +3,7 @@
 
     python examples/render_png.py --renderer mcm --tonemapper artistic --frames 64 --out out.png
     python examples/render_png.py --volume data.bvp ...        (BVP container)   --volume data.raw --dims 256 256 256
+    python examples/render_png.py --renderer eam --filter quasicubic ...    (volume filter: linear, nearest or quasicubic)
 
 Without --volume a synthetic 128^3 sphere with lattice noise is used.  PNG encoding is plain zlib (no imaging library)."""
 import argparse
@@ -28,12 +29,13 @@ def main():
     ap.add_argument("--frames", type=int, default=32)
     ap.add_argument("--extinction", type=float, default=None)
     ap.add_argument("--tf", default="default", choices=["default", "colour"])
+    ap.add_argument("--filter", default="linear", choices=["linear", "nearest", "quasicubic"])
     ap.add_argument("--yaw", type=float, default=0.6)
     ap.add_argument("--pitch", type=float, default=-0.35)
     ap.add_argument("--out", default="frame.png")
     a = ap.parse_args()
 
-    rc = vpt_amd.RenderingContext({'resolution': (a.width, a.height), 'rng': GoldenRatioRng()})
+    rc = vpt_amd.RenderingContext({'resolution': (a.width, a.height), 'filter': a.filter, 'rng': GoldenRatioRng()})
     rc.resize(a.width, a.height)
     if a.volume.endswith(".bvp"):
         reader = vpt_amd.BVPReader(vpt_amd.FileLoader(a.volume))
@@ -60,7 +62,7 @@ def main():
     for _ in range(a.frames):
         rc.render()
     write_png(a.out, rc.getFrame())
-    print("wrote %s (%s, %s, %d frames, %d volume samples)" % (a.out, a.renderer, a.tonemapper, a.frames, rc.renderer.sample_count()))
+    print("wrote %s (%s, %s, %s filter, %d frames, %d volume samples)" % (a.out, a.renderer, a.tonemapper, a.filter, a.frames, rc.renderer.sample_count()))
     rc.destroy()
 
 

@@ -45,6 +45,9 @@ extern "C" {
 /* Volume.js:115-125 setFilter('linear' | 'nearest') */
 #define VPT_FILTER_NEAREST 0
 #define VPT_FILTER_LINEAR  1
+#define VPT_FILTER_QUASI_CUBIC 2  /* setFilter('quasicubic'): the LINEAR cell and taps with smoothstep weights f' = (f * f) * (3 - 2 f) per axis
+                                   * (src/glsl/mixins/quasiCubicSampling.glsl's formula): C1 where LINEAR is C0, one fetch per sample.  Every
+                                   * renderer and format; not taken by column records or the persistent forms (VPT_OPTION_*_PERSISTENT) */
 
 /* Volume formats (RAWReader.js:36-38: format RED, internalFormat R8, type UNSIGNED_BYTE) */
 #define VPT_FORMAT_R8 0

@@ -467,7 +467,7 @@ static napi_value Init(napi_env env, napi_value exports) {
     CONST(VPT_PLAY_EAGER); CONST(VPT_PLAY_GRAPH); CONST(VPT_PLAY_FUSED); CONST(VPT_PLAY_FRAMES); CONST(VPT_FRAME_SLOTS);
     CONST(VPT_RENDERER_MIP); CONST(VPT_RENDERER_EAM); CONST(VPT_RENDERER_MCS); CONST(VPT_RENDERER_MCM);
     CONST(VPT_RENDERER_ISO); CONST(VPT_RENDERER_DEPTH); CONST(VPT_RENDERER_LAO); CONST(VPT_RENDERER_DOS); CONST(VPT_BUFFER_DOS_OCCLUSION);
-    CONST(VPT_FILTER_NEAREST); CONST(VPT_FILTER_LINEAR); CONST(VPT_FORMAT_R8); CONST(VPT_FORMAT_RG8); CONST(VPT_FORMAT_R32F); CONST(VPT_FORMAT_RG32F);
+    CONST(VPT_FILTER_NEAREST); CONST(VPT_FILTER_LINEAR); CONST(VPT_FILTER_QUASI_CUBIC); CONST(VPT_FORMAT_R8); CONST(VPT_FORMAT_RG8); CONST(VPT_FORMAT_R32F); CONST(VPT_FORMAT_RG32F);
     CONST(VPT_FORMAT_R8_SNORM); CONST(VPT_FORMAT_RG8_SNORM); CONST(VPT_FORMAT_RGB565); CONST(VPT_FORMAT_RGBA4); CONST(VPT_FORMAT_RGB5_A1);
     CONST(VPT_FORMAT_RGB10_A2); CONST(VPT_FORMAT_R11F_G11F_B10F); CONST(VPT_FORMAT_RGB9_E5);
     CONST(VPT_BUFFER_RENDER); CONST(VPT_BUFFER_FRAME); CONST(VPT_BUFFER_ACCUM);

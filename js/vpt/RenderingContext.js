@@ -2,7 +2,8 @@
 // src/js/RenderingContext.js:20-229, headless: the caller of the renderer path (SURVEY section 8b "Caller to
 // reproduce").  Same members and methods minus the browser parts (canvas, WebGL context loss, animators, recording):
 // where the reference blits the tone mapper's texture to the canvas (:199-209), getFrame() reads it back.
-//   new RenderingContext({ resolution, filter, device, rng })     resolution: number or { width, height }
+//   new RenderingContext({ resolution, filter, device, rng })     resolution: number or { width, height }; filter: 'linear' (default),
+//   'nearest' or 'quasicubic'
 const { EventTarget, CustomEvent } = require('./EventTarget.js');
 const { Context } = require('./Context.js');
 const { OrbitCameraAnimator } = require('./animators.js');

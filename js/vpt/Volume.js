@@ -75,6 +75,13 @@ function blockBytes(data, df) {
     return new Uint8Array(f.buffer);
 }
 
+// the VPT_FILTER_* code of a setFilter() name: 'linear', 'quasicubic' (smoothstep-weighted LINEAR cell, C1), anything else 'nearest' (:121)
+function filterCode(N, filter) {
+    if (filter === 'linear') { return N.VPT_FILTER_LINEAR; }
+    if (filter === 'quasicubic') { return N.VPT_FILTER_QUASI_CUBIC; }
+    return N.VPT_FILTER_NEAREST;
+}
+
 class Volume extends EventTarget {
 
 constructor(gl, reader, options) {
@@ -125,8 +132,8 @@ getTexture() { return this.ready ? this.texture : null; }
 setFilter(filter) {
     if (!this.texture) { return; }
     const N = native();
-    N.volumeSetFilter(this.texture, filter === 'linear' ? N.VPT_FILTER_LINEAR : N.VPT_FILTER_NEAREST);
+    N.volumeSetFilter(this.texture, filterCode(N, filter));
 }
 
 }
-module.exports = { Volume, RAWReader };
+module.exports = { Volume, RAWReader, filterCode };

@@ -21,6 +21,7 @@ PLAY_EAGER, PLAY_GRAPH, PLAY_FUSED, PLAY_FRAMES = 0, 1, 2, 3
 FRAME_SLOTS = 16
 RENDERER_MIP, RENDERER_EAM, RENDERER_MCS, RENDERER_MCM, RENDERER_ISO, RENDERER_DEPTH, RENDERER_LAO, RENDERER_DOS = 0, 1, 2, 3, 4, 5, 6, 7
 FILTER_NEAREST, FILTER_LINEAR = 0, 1
+FILTER_QUASI_CUBIC = 2
 FORMAT_R8, FORMAT_RG8, FORMAT_R32F, FORMAT_RG32F = 0, 1, 2, 3
 FORMAT_R8_SNORM, FORMAT_RG8_SNORM = 4, 5
 FORMAT_RGB565, FORMAT_RGBA4, FORMAT_RGB5_A1, FORMAT_RGB10_A2, FORMAT_R11F_G11F_B10F, FORMAT_RGB9_E5 = 6, 7, 8, 9, 10, 11

@@ -274,7 +274,8 @@ extern "C" int vpt_volume_finalize(vpt_volume *v) {
 }
 extern "C" int vpt_volume_set_filter(vpt_volume *v, int filter) {
     if (!v) return fail(VPT_ERR_INVALID, "volume is null");
-    v->filter = (filter == VPT_FILTER_LINEAR) ? VPT_FILTER_LINEAR : VPT_FILTER_NEAREST;   // Volume.js:121
+    // Volume.js:121: anything but LINEAR is NEAREST; VPT_FILTER_QUASI_CUBIC is this library's third filter
+    v->filter = (filter == VPT_FILTER_LINEAR || filter == VPT_FILTER_QUASI_CUBIC) ? filter : VPT_FILTER_NEAREST;
     return VPT_OK;
 }
 extern "C" int vpt_volume_set_wide_tables(vpt_volume *v, int wide) {
@@ -1155,6 +1156,18 @@ static int probe_sample(vpt_renderer *r, const float *xyz, float *rgba, size_t n
             case 137: if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<137>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); else hipLaunchKernelGGL(k_probe_sample<137>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); break;
             case 138: if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<138>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); else hipLaunchKernelGGL(k_probe_sample<138>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); break;
             case 139: if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<139>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); else hipLaunchKernelGGL(k_probe_sample<139>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); break;
+            case 256: if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<256>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); else hipLaunchKernelGGL(k_probe_sample<256>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); break;
+            case 257: if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<257>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); else hipLaunchKernelGGL(k_probe_sample<257>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); break;
+            case 264: if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<264>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); else hipLaunchKernelGGL(k_probe_sample<264>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); break;
+            case 265: if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<265>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); else hipLaunchKernelGGL(k_probe_sample<265>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); break;
+            case 288: if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<288>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); else hipLaunchKernelGGL(k_probe_sample<288>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); break;
+            case 289: if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<289>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); else hipLaunchKernelGGL(k_probe_sample<289>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); break;
+            case 296: if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<296>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); else hipLaunchKernelGGL(k_probe_sample<296>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); break;
+            case 297: if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<297>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); else hipLaunchKernelGGL(k_probe_sample<297>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); break;
+            case 384: if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<384>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); else hipLaunchKernelGGL(k_probe_sample<384>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); break;
+            case 385: if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<385>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); else hipLaunchKernelGGL(k_probe_sample<385>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); break;
+            case 392: if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<392>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); else hipLaunchKernelGGL(k_probe_sample<392>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); break;
+            case 393: if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<393>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); else hipLaunchKernelGGL(k_probe_sample<393>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); break;
             default: hipFree(din); hipFree(dout); return fail(VPT_ERR_INVALID, "no probe kernel for variant %d", variant_of(r));
         }
         e = hipGetLastError();

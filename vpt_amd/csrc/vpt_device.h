@@ -351,6 +351,16 @@ VPT_DEV const uint8_t *cell_addr(const DevVolume &v, const LdsTables &t, uint32_
 #define VPT_V_RG      8   // two-channel (RG8) volume: texture(uVolume, p).rg has both channels, the transfer function is looked up in 2-D
 #define VPT_V_REC     64  // in-cube samples from the column records instead of the bricks (one-channel byte volumes, LINEAR filter; MCM)
 #define VPT_V_SNORM   128 // BYTE texels (R8_SNORM / RG8_SNORM): bricks as R8 / RG8, each tap decoded to fl32(c / 127) and filtered as R32F
+#define VPT_V_QCUBIC  256 // quasi-cubic filter (VPT_FILTER_QUASI_CUBIC): the LINEAR cell and taps, smoothstep weights (qc_weight); never with NEAREST / REC
+// The quasi-cubic weight of a LINEAR cell's fraction f: f' = (f * f) * (3 - 2 f), every operation rounded (the library is built with
+// -ffp-contract=off; 2 f is exact, so even a fused 3 - 2 f would be the same float).  f = 0 -> 0 and f = 1 -> 1 exactly, so every
+// clamped case of linear_cell keeps its exact edge value.  With the cell i = floor(u) and f = fract(u) of u = s N - 0.5 this is the
+// weight that texture((floor(U) + F^2 (3 - 2F) - 0.5) / N) of the U = s N + 0.5, F = fract(U) form gives, without that coordinate's
+// round trip (three IEEE divisions per sample and its rounding): DESIGN.md section 3.  C1 across cell borders where LINEAR is C0.
+VPT_DEV float qc_weight(float f) { return (f * f) * (3.0f - 2.0f * f); }
+template <int V> VPT_DEV float cell_weight(float f) { return (V & VPT_V_QCUBIC) ? qc_weight(f) : f; }
+// linear_cell with the filter's weight: the LINEAR variants are exactly linear_cell
+template <int V> VPT_DEV void filter_cell(float s, float fn, float hi, uint32_t &i, float &f) { linear_cell(s, fn, hi, i, f); f = cell_weight<V>(f); }
 // the eight taps around a cell of one channel's brick and their trilinear blend: taps +0,+1 (y,z) ; +5,+6 (y+1,z) ;
 // +25,+26 (y,z+1) ; +30,+31 (y+1,z+1) = two 8-byte windows of one line.
 // tools/gather_rates.hip (MI355X, L1-resident gathers): a dword-aligned 8/12/16-byte wave load costs ~27-33 cycles
@@ -538,7 +548,8 @@ VPT_DEV float boundary_blend(uint32_t w, float fa, float fb) {
     const float r = lerpf(lerpf(c00, c10, fa), lerpf(c01, c11, fa), fb);
     return SNORM ? r : r * VPT_INV255;
 }
-// texture(uVolume, clamp(p)).rg through the boundary atlas for ANY volume format (V: VPT_V_NEAREST | VPT_V_RG | VPT_V_F32 | VPT_V_SNORM): channel c's faces lie
+// texture(uVolume, clamp(p)).rg through the boundary atlas for ANY volume format and filter (V: VPT_V_NEAREST | VPT_V_RG | VPT_V_F32 | VPT_V_SNORM |
+// VPT_V_QCUBIC): channel c's faces lie
 // 6 * atlas_face cells behind channel c - 1's; float volumes keep four floats per cell.  Same texels, same order of operations as
 // sample_volume_rg<V> at the clamped position (float texels: finite ones, see vpt_volume_finalize).  Precondition as boundary_cell's.
 template <int V>
@@ -546,6 +557,7 @@ VPT_DEV f2 sample_boundary_rg(const DevVolume &v, f3 p) {
     constexpr bool NEAREST = (V & VPT_V_NEAREST) != 0, RG = (V & VPT_V_RG) != 0, F32 = (V & VPT_V_F32) != 0, SNORM = (V & VPT_V_SNORM) != 0;
     float fa, fb;
     const uint32_t idx = boundary_cell_lane<NEAREST>(v, p, fa, fb);
+    fa = cell_weight<V>(fa); fb = cell_weight<V>(fb);                  // (the clamped axis has f = 0 and stays 0)
     float val[2] = { 0.0f, 0.0f };
 #pragma unroll
     for (int c = 0; c < (RG ? 2 : 1); c++) {
@@ -583,9 +595,9 @@ VPT_DEV f2 sample_volume_rg(const DevVolume &v, const LdsTables &t, f3 p) {
             return f2{ b[0], RG ? b[128] : 0.0f };                          // (two channels: the G brick sits 128 floats behind the R brick)
         }
         uint32_t x, y, z; float fx, fy, fz;
-        linear_cell(p.x, v.fnx, v.hx, x, fx);
-        linear_cell(p.y, v.fny, v.hy, y, fy);
-        linear_cell(p.z, v.fnz, v.hz, z, fz);
+        filter_cell<V>(p.x, v.fnx, v.hx, x, fx);
+        filter_cell<V>(p.y, v.fny, v.hy, y, fy);
+        filter_cell<V>(p.z, v.fnz, v.hz, z, fz);
         const float *b0 = (const float *)cell_addr<WIDE>(v, t, x, y, z);
         f2 out = { 0.0f, 0.0f };
 #pragma unroll
@@ -608,9 +620,9 @@ VPT_DEV f2 sample_volume_rg(const DevVolume &v, const LdsTables &t, f3 p) {
         return f2{ (float)a[0] * VPT_INV255, RG ? (float)a[128] * VPT_INV255 : 0.0f };
     }
     uint32_t x, y, z; float fx, fy, fz;
-    linear_cell(p.x, v.fnx, v.hx, x, fx);
-    linear_cell(p.y, v.fny, v.hy, y, fy);
-    linear_cell(p.z, v.fnz, v.hz, z, fz);
+    filter_cell<V>(p.x, v.fnx, v.hx, x, fx);
+    filter_cell<V>(p.y, v.fny, v.hy, y, fy);
+    filter_cell<V>(p.z, v.fnz, v.hz, z, fz);
     if (V & VPT_V_REC) {                                          // (one channel: the launch code never combines REC with RG)
         const uint64_t w = record_load(record_addr<WIDE>(v, t, x, y, z));
         return f2{ record_blend((uint32_t)w, (uint32_t)(w >> 32), fx, fy, fz), 0.0f };

@@ -144,6 +144,18 @@ static int launch_dos(vpt_renderer *r, PassArgs &a, const int rect[4]) {
         case 137: return launch_dos_slice(k_dos_slice<137 | VPT_DOS_TAPS>, r, a, rect);
         case 138: return launch_dos_slice(k_dos_slice<138 | VPT_DOS_TAPS>, r, a, rect);
         case 139: return launch_dos_slice(k_dos_slice<139 | VPT_DOS_TAPS>, r, a, rect);
+        case 256: return launch_dos_slice(k_dos_slice<256 | VPT_DOS_TAPS>, r, a, rect);
+        case 257: return launch_dos_slice(k_dos_slice<257 | VPT_DOS_TAPS>, r, a, rect);
+        case 264: return launch_dos_slice(k_dos_slice<264 | VPT_DOS_TAPS>, r, a, rect);
+        case 265: return launch_dos_slice(k_dos_slice<265 | VPT_DOS_TAPS>, r, a, rect);
+        case 288: return launch_dos_slice(k_dos_slice<288 | VPT_DOS_TAPS>, r, a, rect);
+        case 289: return launch_dos_slice(k_dos_slice<289 | VPT_DOS_TAPS>, r, a, rect);
+        case 296: return launch_dos_slice(k_dos_slice<296 | VPT_DOS_TAPS>, r, a, rect);
+        case 297: return launch_dos_slice(k_dos_slice<297 | VPT_DOS_TAPS>, r, a, rect);
+        case 384: return launch_dos_slice(k_dos_slice<384 | VPT_DOS_TAPS>, r, a, rect);
+        case 385: return launch_dos_slice(k_dos_slice<385 | VPT_DOS_TAPS>, r, a, rect);
+        case 392: return launch_dos_slice(k_dos_slice<392 | VPT_DOS_TAPS>, r, a, rect);
+        case 393: return launch_dos_slice(k_dos_slice<393 | VPT_DOS_TAPS>, r, a, rect);
         default: return fail(VPT_ERR_INVALID, "no DOS kernel for variant %d", variant_of(r));
     }
 }

@@ -347,7 +347,7 @@ static int launch_sampling(K kernel, vpt_renderer *r, const PassArgs &a, unsigne
     }
     return VPT_OK;
 }
-// the instantiation for (addressing, filter, channels): V = VPT_V_WIDE | VPT_V_NEAREST | VPT_V_RG bits
+// the instantiation for (addressing, filter, channels, texels): V = VPT_V_WIDE | VPT_V_NEAREST | VPT_V_RG | VPT_V_F32 | VPT_V_SNORM | VPT_V_QCUBIC bits
 // MCM on a one-channel byte volume with the LINEAR filter: the in-cube samples come from the column records (VPT_OPTION_COLUMN_RECORDS).
 // Measured (round 4, 1080p headline camera, us per frame bricks -> records): 512^3 80.0 -> 83.3, every tile HIT 143.9 -> 157.1, extinction 50
 // 80.3 -> 92.9 — 256 MiB of bricks mostly live in the 256 MB Infinity Cache and a dense medium's short steps re-use brick lines, 512 MiB of
@@ -360,10 +360,12 @@ static inline bool renderer_uses_records(const vpt_renderer *r) {
 }
 static inline int variant_of(const vpt_renderer *r) {
     return ((r->vol->wide || (renderer_uses_records(r) && r->vol->rec_wide)) ? VPT_V_WIDE : 0) | (r->vol->filter == VPT_FILTER_NEAREST ? VPT_V_NEAREST : 0) | (r->vol->channels == 2 ? VPT_V_RG : 0) |
-           (r->vol->f32 ? VPT_V_F32 : 0) | (r->vol->snorm ? VPT_V_SNORM : 0);
+           (r->vol->f32 ? VPT_V_F32 : 0) | (r->vol->snorm ? VPT_V_SNORM : 0) | (r->vol->filter == VPT_FILTER_QUASI_CUBIC ? VPT_V_QCUBIC : 0);
 }
 // an UNSIGNED_BYTE one-channel volume: what the column records and the persistent forms take
 static inline bool unsigned_r8(const vpt_volume *v) { return v->channels == 1 && !v->f32 && !v->snorm; }
+// ... with the LINEAR or NEAREST filter: the persistent forms (VPT_OPTION_*_PERSISTENT) have no quasi-cubic instantiation
+static inline bool persistent_volume(const vpt_volume *v) { return unsigned_r8(v) && v->filter != VPT_FILTER_QUASI_CUBIC; }
 #define LAUNCH_S(KT, r, a) do { \
     unsigned g_ = (unsigned)(r)->ntiles; \
     switch (variant_of(r)) { \
@@ -391,6 +393,18 @@ static inline bool unsigned_r8(const vpt_volume *v) { return v->channels == 1 &&
         case 137: VPT_TRY(launch_sampling(KT(137), (r), (a), g_)); break; \
         case 138: VPT_TRY(launch_sampling(KT(138), (r), (a), g_)); break; \
         case 139: VPT_TRY(launch_sampling(KT(139), (r), (a), g_)); break; \
+        case 256: VPT_TRY(launch_sampling(KT(256), (r), (a), g_)); break; \
+        case 257: VPT_TRY(launch_sampling(KT(257), (r), (a), g_)); break; \
+        case 264: VPT_TRY(launch_sampling(KT(264), (r), (a), g_)); break; \
+        case 265: VPT_TRY(launch_sampling(KT(265), (r), (a), g_)); break; \
+        case 288: VPT_TRY(launch_sampling(KT(288), (r), (a), g_)); break; \
+        case 289: VPT_TRY(launch_sampling(KT(289), (r), (a), g_)); break; \
+        case 296: VPT_TRY(launch_sampling(KT(296), (r), (a), g_)); break; \
+        case 297: VPT_TRY(launch_sampling(KT(297), (r), (a), g_)); break; \
+        case 384: VPT_TRY(launch_sampling(KT(384), (r), (a), g_)); break; \
+        case 385: VPT_TRY(launch_sampling(KT(385), (r), (a), g_)); break; \
+        case 392: VPT_TRY(launch_sampling(KT(392), (r), (a), g_)); break; \
+        case 393: VPT_TRY(launch_sampling(KT(393), (r), (a), g_)); break; \
         default: return fail(VPT_ERR_INVALID, "no sampling kernel for variant %d", variant_of(r)); \
     } } while (0)
 

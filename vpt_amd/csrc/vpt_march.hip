@@ -49,7 +49,7 @@ int march_reset(vpt_renderer *r, const PassArgs &a) {
     return VPT_OK;
 }
 static int launch_mcs(vpt_renderer *r, const PassArgs &a, bool fused) {
-    if (r->mcs_persistent && unsigned_r8(r->vol)) {       // (walks every tile)
+    if (r->mcs_persistent && persistent_volume(r->vol)) {       // (walks every tile)
         if (fused) LAUNCH_MCS_PERSIST(1, r, a); else LAUNCH_MCS_PERSIST(0, r, a);
         return VPT_OK;
     }

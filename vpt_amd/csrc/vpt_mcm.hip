@@ -88,7 +88,10 @@ static int launch_mcm_classes(vpt_renderer *r, const PassArgs &a) {
     // fast-math, 96.1 -> 92.8 bit-exact, rank 3 of 8's share 18.4 -> 17.1 bit-exact but 15.8 -> 16.9 fast-math: there the sample is
     // consumed where the shader takes it
     const bool late = !(fast && early);
-    if (!plain) km = format_miss_kernel<FUSE>(variant_of(r), fast);
+    // a quasi-cubic volume reuses the LINEAR MISS-tile kernel of its format: a MISS tile's sample is executed and discarded (mcm_events_miss),
+    // so the filter cannot change what that kernel writes (tests/test_gpu_quasicubic.py: classes against the general pass, bit for bit)
+    const int vm = variant_of(r) & ~VPT_V_QCUBIC;
+    if (vm & ~VPT_V_WIDE) km = format_miss_kernel<FUSE>(vm, fast);
     else if (check) km = fast ? (late ? (PassKernel)k_mcm_miss<FUSE, VPT_V_FAST, true, true> : (PassKernel)k_mcm_miss<FUSE, VPT_V_FAST, true, false>)
                          : (PassKernel)k_mcm_miss<FUSE, 0, true, true>;
     else km = fast ? (late ? (PassKernel)k_mcm_miss<FUSE, VPT_V_FAST, false, true> : (PassKernel)k_mcm_miss<FUSE, VPT_V_FAST, false, false>)
@@ -254,7 +257,7 @@ static int launch_mcm_pass(vpt_renderer *r, const PassArgs &a) {
     if (two_streams) VPT_TRY(ensure_split_streams(r));
     if (same && r->cls.enabled && mcm_classes_runnable(r, a) && (two_streams || r->cls.one_stream)) return launch_mcm_classes<FUSE>(r, a);
     VPT_TRY(mcm_materialize(r));
-    if (r->mcm_persistent && unsigned_r8(r->vol)) { LAUNCH_MCM_PERSIST(FUSE, r, a); return VPT_OK; }
+    if (r->mcm_persistent && persistent_volume(r->vol)) { LAUNCH_MCM_PERSIST(FUSE, r, a); return VPT_OK; }
     return mcm_general_pass(r, a, FUSE);
 }
 

@@ -36,6 +36,16 @@ static inline int class_variant(const vpt_renderer *r, const PassArgs &a) {
         case VPT_V_SNORM | VPT_V_RG: { constexpr int F = VPT_V_SNORM | VPT_V_RG; return __VA_ARGS__; } \
         case VPT_V_SNORM | VPT_V_RG | VPT_V_NEAREST: { constexpr int F = VPT_V_SNORM | VPT_V_RG | VPT_V_NEAREST; return __VA_ARGS__; } \
         default: return nullptr; }
+// the quasi-cubic filter (VPT_V_QCUBIC) on every format: the HIT tiles through the general kernel of the variant; the MISS tiles reuse the
+// LINEAR MISS-tile kernel of the same format (vpt_mcm.hip launch_mcm_classes)
+#define QC_CASES(...) switch (v & (VPT_V_NEAREST | VPT_V_RG | VPT_V_F32 | VPT_V_SNORM | VPT_V_QCUBIC)) { \
+        case VPT_V_QCUBIC: { constexpr int F = VPT_V_QCUBIC; return __VA_ARGS__; } \
+        case VPT_V_QCUBIC | VPT_V_RG: { constexpr int F = VPT_V_QCUBIC | VPT_V_RG; return __VA_ARGS__; } \
+        case VPT_V_QCUBIC | VPT_V_F32: { constexpr int F = VPT_V_QCUBIC | VPT_V_F32; return __VA_ARGS__; } \
+        case VPT_V_QCUBIC | VPT_V_F32 | VPT_V_RG: { constexpr int F = VPT_V_QCUBIC | VPT_V_F32 | VPT_V_RG; return __VA_ARGS__; } \
+        case VPT_V_QCUBIC | VPT_V_SNORM: { constexpr int F = VPT_V_QCUBIC | VPT_V_SNORM; return __VA_ARGS__; } \
+        case VPT_V_QCUBIC | VPT_V_SNORM | VPT_V_RG: { constexpr int F = VPT_V_QCUBIC | VPT_V_SNORM | VPT_V_RG; return __VA_ARGS__; } \
+        default: return nullptr; }
 // vpt_mcm_hit.hip: k_mcm_integrate / k_mcm_integrate_early by variant (fuse: + _renderFrame)
 PassKernel mcm_hit_kernel(bool fuse, int v, bool early);                    // v: class_variant()
 PassKernel mcm_format_hit_kernel(bool fuse, int v, bool wide, bool fast);   // v: variant_of(), another volume format

@@ -53,6 +53,18 @@ int mcm_multi(vpt_renderer *r, const PassArgs &a, uint32_t npasses, uint2 *ring)
         case 137: return ring ? launch_frames(k_mcm_frames<137 | F>, r, a, npasses, ring) : launch_multi(k_mcm_multi<137 | F>, r, a, npasses); \
         case 138: return ring ? launch_frames(k_mcm_frames<138 | F>, r, a, npasses, ring) : launch_multi(k_mcm_multi<138 | F>, r, a, npasses); \
         case 139: return ring ? launch_frames(k_mcm_frames<139 | F>, r, a, npasses, ring) : launch_multi(k_mcm_multi<139 | F>, r, a, npasses); \
+        case 256: return ring ? launch_frames(k_mcm_frames<256 | F>, r, a, npasses, ring) : launch_multi(k_mcm_multi<256 | F>, r, a, npasses); \
+        case 257: return ring ? launch_frames(k_mcm_frames<257 | F>, r, a, npasses, ring) : launch_multi(k_mcm_multi<257 | F>, r, a, npasses); \
+        case 264: return ring ? launch_frames(k_mcm_frames<264 | F>, r, a, npasses, ring) : launch_multi(k_mcm_multi<264 | F>, r, a, npasses); \
+        case 265: return ring ? launch_frames(k_mcm_frames<265 | F>, r, a, npasses, ring) : launch_multi(k_mcm_multi<265 | F>, r, a, npasses); \
+        case 288: return ring ? launch_frames(k_mcm_frames<288 | F>, r, a, npasses, ring) : launch_multi(k_mcm_multi<288 | F>, r, a, npasses); \
+        case 289: return ring ? launch_frames(k_mcm_frames<289 | F>, r, a, npasses, ring) : launch_multi(k_mcm_multi<289 | F>, r, a, npasses); \
+        case 296: return ring ? launch_frames(k_mcm_frames<296 | F>, r, a, npasses, ring) : launch_multi(k_mcm_multi<296 | F>, r, a, npasses); \
+        case 297: return ring ? launch_frames(k_mcm_frames<297 | F>, r, a, npasses, ring) : launch_multi(k_mcm_multi<297 | F>, r, a, npasses); \
+        case 384: return ring ? launch_frames(k_mcm_frames<384 | F>, r, a, npasses, ring) : launch_multi(k_mcm_multi<384 | F>, r, a, npasses); \
+        case 385: return ring ? launch_frames(k_mcm_frames<385 | F>, r, a, npasses, ring) : launch_multi(k_mcm_multi<385 | F>, r, a, npasses); \
+        case 392: return ring ? launch_frames(k_mcm_frames<392 | F>, r, a, npasses, ring) : launch_multi(k_mcm_multi<392 | F>, r, a, npasses); \
+        case 393: return ring ? launch_frames(k_mcm_frames<393 | F>, r, a, npasses, ring) : launch_multi(k_mcm_multi<393 | F>, r, a, npasses); \
         default: return fail(VPT_ERR_INVALID, "no frame-sequence kernel for variant %d", variant_of(r)); }
     if (r->fast_math) MULTI_CASES(VPT_V_FAST)
     MULTI_CASES(0)

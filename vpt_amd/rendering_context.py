@@ -22,7 +22,7 @@ class RenderingContext(EventTarget):
         self.environmentTexture = np.array([[[255, 255, 255, 255]]], dtype=np.uint8)   # :90-101
         self._rng = options.get('rng')
         self._resolution = options['resolution'] if options.get('resolution') is not None else 512   # :35
-        self.filter = options['filter'] if options.get('filter') is not None else 'linear'           # :36
+        self.filter = options['filter'] if options.get('filter') is not None else 'linear'           # :36 ('linear' | 'nearest' | 'quasicubic')
         self.camera = Node()                                                          # :38-40
         self.camera.transform.localTranslation = [0, 0, 2]
         self.camera.components.append(PerspectiveCamera(self.camera))

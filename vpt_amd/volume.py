@@ -52,6 +52,16 @@ def device_format(modality):
     raise RuntimeError('Unknown volume datatype: %s' % t)                   # Volume.js:103
 
 
+
+def filter_code(filter):
+    """The VPT_FILTER_* code of a setFilter() name: 'linear', 'quasicubic' (smoothstep-weighted LINEAR cell, C1), and anything else
+    'nearest' (Volume.js:121)."""
+    if filter == 'linear':
+        return N.FILTER_LINEAR
+    if filter == 'quasicubic':
+        return N.FILTER_QUASI_CUBIC
+    return N.FILTER_NEAREST
+
 class Volume(EventTarget):
     """Volume.js:3-127.  ``gl`` is a vpt_amd.Context.  ``getTexture()`` returns the native volume handle
     once ``ready`` (the reference returns the WebGLTexture), else None."""
@@ -121,7 +131,7 @@ class Volume(EventTarget):
     def setFilter(self, filter):
         if not self.texture:
             return
-        N.check(N.lib().vpt_volume_set_filter(self.texture, N.FILTER_LINEAR if filter == 'linear' else N.FILTER_NEAREST))
+        N.check(N.lib().vpt_volume_set_filter(self.texture, filter_code(filter)))
 
     # ---- extension: whole-array upload (one block) for synthetic volumes ----
     @classmethod
