@@ -77,6 +77,19 @@ extern "C" {
                                   * texel switches the boundary atlas off, as for any float volume */
 #define VPT_FORMAT_RGB9_E5 11    /* format RGB, internalFormat RGB9_E5, type UNSIGNED_INT_5_9_9_9_REV: r = bits 8-0, g = bits 17-9, shared
                                   * exponent e = bits 31-27: m * 2^(e - 24) */
+/* 16-bit normalised formats (EXT_texture_norm16; opt-in on the hosts, as in WebGL).  Blocks are uploaded as little-endian uint16 (UNORM) or
+ * int16 (SNORM), 2 bytes per channel, and the bricks keep 2 bytes per channel: vpt_volume_bricked_bytes is half that of R32F and twice that
+ * of R8.  Every tap is decoded to the float an R32F volume of the decoded texels holds and filtered in the R32F order (NEAREST, LINEAR and
+ * QUASI_CUBIC): bit-identical to that R32F / RG32F volume in every renderer.  Column records, the persistent forms (VPT_OPTION_*_PERSISTENT)
+ * and VPT_OPTION_BUCKET_KERNEL are not taken, as for R32F: those options fall back to the general kernels.  The MCM tile classes are taken;
+ * the boundary atlas holds the decoded texels as floats */
+#define VPT_FORMAT_R16 12        /* format RED, internalFormat R16_EXT, type UNSIGNED_SHORT: texture(uVolume, p).r = fl32(c / 65535) */
+#define VPT_FORMAT_RG16 13       /* format RG, internalFormat RG16_EXT, type UNSIGNED_SHORT: two interleaved UNORM channels (the RGB16_EXT /
+                                  * RGBA16_EXT manifests' first two channels) */
+#define VPT_FORMAT_R16_SNORM 14  /* format RED, internalFormat R16_SNORM_EXT, type SHORT: texture(uVolume, p).r = max(fl32(c / 32767), -1);
+                                  * -32768 is clamped to -32767 once at finalize */
+#define VPT_FORMAT_RG16_SNORM 15 /* format RG, internalFormat RG16_SNORM_EXT, type SHORT: two interleaved SNORM channels (RGB16 / RGBA16_SNORM_EXT:
+                                  * the first two) */
 
 /* Buffers readable through vpt_renderer_read (SingleBuffer.js / DoubleBuffer.js attachments) */
 #define VPT_BUFFER_RENDER 0      /* RGBA16F, 8 B/pixel  (AbstractRenderer.js:142-155, getTexture() :114-116) */

@@ -470,6 +470,7 @@ static napi_value Init(napi_env env, napi_value exports) {
     CONST(VPT_FILTER_NEAREST); CONST(VPT_FILTER_LINEAR); CONST(VPT_FILTER_QUASI_CUBIC); CONST(VPT_FORMAT_R8); CONST(VPT_FORMAT_RG8); CONST(VPT_FORMAT_R32F); CONST(VPT_FORMAT_RG32F);
     CONST(VPT_FORMAT_R8_SNORM); CONST(VPT_FORMAT_RG8_SNORM); CONST(VPT_FORMAT_RGB565); CONST(VPT_FORMAT_RGBA4); CONST(VPT_FORMAT_RGB5_A1);
     CONST(VPT_FORMAT_RGB10_A2); CONST(VPT_FORMAT_R11F_G11F_B10F); CONST(VPT_FORMAT_RGB9_E5);
+    CONST(VPT_FORMAT_R16); CONST(VPT_FORMAT_RG16); CONST(VPT_FORMAT_R16_SNORM); CONST(VPT_FORMAT_RG16_SNORM);
     CONST(VPT_BUFFER_RENDER); CONST(VPT_BUFFER_FRAME); CONST(VPT_BUFFER_ACCUM);
     CONST(VPT_BUFFER_MCM_POSITION); CONST(VPT_BUFFER_MCM_DIRECTION); CONST(VPT_BUFFER_MCM_TRANSMITTANCE); CONST(VPT_BUFFER_MCM_RADIANCE);
     napi_set_named_property(env, exports, "UNIFORMS_BYTES", number(env, (double)sizeof(vpt_uniforms)));

@@ -20,6 +20,17 @@ const SIZED = [
     [R.GL_UNSIGNED_INT_10F_11F_11F_REV, GL_RGB, R.GL_R11F_G11F_B10F, 'VPT_FORMAT_R11F_G11F_B10F', 1, 'packed'],
     [R.GL_UNSIGNED_INT_5_9_9_9_REV, GL_RGB, R.GL_RGB9_E5, 'VPT_FORMAT_RGB9_E5', 1, 'packed'],
 ];
+// ... and those a context takes once it has enabled EXT_texture_norm16 (gl.getExtension): 16-bit channels uploaded as they are
+const NORM16 = [
+    [R.GL_UNSIGNED_SHORT, GL_RED, R.GL_R16_EXT, 'VPT_FORMAT_R16', 1, 'i16'],
+    [R.GL_UNSIGNED_SHORT, GL_RG, R.GL_RG16_EXT, 'VPT_FORMAT_RG16', 2, 'i16'],
+    [R.GL_UNSIGNED_SHORT, GL_RGB, R.GL_RGB16_EXT, 'VPT_FORMAT_RG16', 3, 'i16'],
+    [R.GL_UNSIGNED_SHORT, GL_RGBA, R.GL_RGBA16_EXT, 'VPT_FORMAT_RG16', 4, 'i16'],
+    [R.GL_SHORT, GL_RED, R.GL_R16_SNORM_EXT, 'VPT_FORMAT_R16_SNORM', 1, 'i16'],
+    [R.GL_SHORT, GL_RG, R.GL_RG16_SNORM_EXT, 'VPT_FORMAT_RG16_SNORM', 2, 'i16'],
+    [R.GL_SHORT, GL_RGB, R.GL_RGB16_SNORM_EXT, 'VPT_FORMAT_RG16_SNORM', 3, 'i16'],
+    [R.GL_SHORT, GL_RGBA, R.GL_RGBA16_SNORM_EXT, 'VPT_FORMAT_RG16_SNORM', 4, 'i16'],
+];
 
 // IEEE half -> float (exact)
 function halfToFloat(h) {
@@ -31,9 +42,10 @@ function halfToFloat(h) {
 
 // (native format, channels in the file, element kind) for a manifest's (type, format, internalFormat): what a WebGL2 sampler3D can
 // filter — UNSIGNED_BYTE and FLOAT / HALF_FLOAT with 1-4 channels (the shaders read .rg: further channels are dropped on upload), BYTE
-// with an SNORM internal format, the packed types with the internal format each names (vpt_amd/volume.py device_format).  Anything
-// else raises the reference's error (Volume.js:103).
-function deviceFormat(N, modality) {
+// with an SNORM internal format, the packed types with the internal format each names (vpt_amd/volume.py device_format); on a context
+// `gl` that has enabled EXT_texture_norm16, UNSIGNED_SHORT / SHORT with that extension's internal formats.  Anything else raises the
+// reference's error (Volume.js:103).
+function deviceFormat(N, modality, gl) {
     const t = modality.type, f = modality.format;
     if (t === GL_UNSIGNED_BYTE && (f === GL_RED || f === GL_RG || f === GL_RGB || f === GL_RGBA)) {
         const n = f === GL_RED ? 1 : (f === GL_RG ? 2 : (f === GL_RGB ? 3 : 4));
@@ -43,15 +55,24 @@ function deviceFormat(N, modality) {
         const n = f === GL_RED ? 1 : (f === GL_RG ? 2 : (f === GL_RGB ? 3 : 4));
         return { fmt: n === 1 ? N.VPT_FORMAT_R32F : N.VPT_FORMAT_RG32F, channels: n, kind: t === GL_FLOAT ? 'f32' : 'f16' };
     }
-    const sized = SIZED.find(e => e[0] === t && e[1] === f && e[2] === modality.internalFormat);
+    let sized = SIZED.find(e => e[0] === t && e[1] === f && e[2] === modality.internalFormat);
+    if (!sized && gl && gl.extensionEnabled && gl.extensionEnabled('EXT_texture_norm16')) {
+        sized = NORM16.find(e => e[0] === t && e[1] === f && e[2] === modality.internalFormat);
+    }
     if (sized) { return { fmt: N[sized[3]], channels: sized[4], kind: sized[5] }; }
     throw new Error('Unknown volume datatype: ' + t);
 }
 
-// a block as the bytes vpt_volume_upload_block takes: (u)int8 with at most two channels, float32, or packed words
+// a block as the bytes vpt_volume_upload_block takes: (u)int8 or (u)int16 with at most two channels, float32, or packed words
 function blockBytes(data, df) {
     const u8 = data instanceof Uint8Array ? data : new Uint8Array(data.buffer || data, data.byteOffset || 0, data.byteLength);
     if (df.kind === 'packed') { return u8; }                 // the words as they are
+    if (df.kind === 'i16') {                                 // 16-bit channels: the first two of each texel, little-endian words as they are
+        if (df.channels <= 2) { return u8; }
+        const n = u8.length / (2 * df.channels), out = new Uint8Array(4 * n);
+        for (let i = 0; i < n; i++) { for (let b = 0; b < 4; b++) { out[4 * i + b] = u8[2 * df.channels * i + b]; } }
+        return out;
+    }
     if (df.kind === 'u8' || df.kind === 'i8') {
         if (df.channels <= 2) { return u8; }
         const n = u8.length / df.channels, out = new Uint8Array(2 * n);
@@ -111,7 +132,7 @@ async readModality(modalityName) {
     if (!modality) { throw new Error(`Modality '${modalityName}' does not exist`); }          // Volume.js:40
     this.modality = modality;
     if (this.texture) { N.volumeDestroy(this.texture); this.texture = null; }
-    const df = deviceFormat(N, modality);                                                       // Volume.js:58-60,84-105
+    const df = deviceFormat(N, modality, this._gl);                                                       // Volume.js:58-60,84-105
     const { width, height, depth } = modality.dimensions;
     this.texture = N.volumeCreate(this._gl._h, width, height, depth, df.fmt);
     for (const { index, position } of modality.placements) {

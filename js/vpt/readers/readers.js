@@ -13,6 +13,10 @@ const GL_R8_SNORM = 0x8F94, GL_RG8_SNORM = 0x8F95, GL_RGB8_SNORM = 0x8F96, GL_RG
 const GL_UNSIGNED_SHORT_5_6_5 = 0x8363, GL_RGB565 = 0x8D62, GL_UNSIGNED_SHORT_4_4_4_4 = 0x8033, GL_RGBA4 = 0x8056;
 const GL_UNSIGNED_SHORT_5_5_5_1 = 0x8034, GL_RGB5_A1 = 0x8057, GL_UNSIGNED_INT_2_10_10_10_REV = 0x8368, GL_RGB10_A2 = 0x8059;
 const GL_UNSIGNED_INT_10F_11F_11F_REV = 0x8C3B, GL_R11F_G11F_B10F = 0x8C3A, GL_UNSIGNED_INT_5_9_9_9_REV = 0x8C3E, GL_RGB9_E5 = 0x8C3D;
+// 16-bit normalised volumes (Volume.js:84-105: Uint16Array / Int16Array), filterable through EXT_texture_norm16
+const GL_UNSIGNED_SHORT = 5123, GL_SHORT = 5122;
+const GL_R16_EXT = 0x822A, GL_RG16_EXT = 0x822C, GL_RGB16_EXT = 0x8054, GL_RGBA16_EXT = 0x805B;
+const GL_R16_SNORM_EXT = 0x8F98, GL_RG16_SNORM_EXT = 0x8F99, GL_RGB16_SNORM_EXT = 0x8F9A, GL_RGBA16_SNORM_EXT = 0x8F9B;
 
 class AbstractReader {                                          // AbstractReader.js:1-15
     constructor(loader) { this._loader = loader; }
@@ -136,4 +140,5 @@ module.exports = { AbstractReader, RAWReader, ZIPReader, BVPReader, ReaderFactor
     GL_RGB, GL_RGB8, GL_RGBA, GL_RGBA8, GL_FLOAT, GL_HALF_FLOAT, GL_R32F, GL_R16F,
     GL_BYTE, GL_R8_SNORM, GL_RG8_SNORM, GL_RGB8_SNORM, GL_RGBA8_SNORM, GL_UNSIGNED_SHORT_5_6_5, GL_RGB565, GL_UNSIGNED_SHORT_4_4_4_4, GL_RGBA4,
     GL_UNSIGNED_SHORT_5_5_5_1, GL_RGB5_A1, GL_UNSIGNED_INT_2_10_10_10_REV, GL_RGB10_A2, GL_UNSIGNED_INT_10F_11F_11F_REV, GL_R11F_G11F_B10F,
-    GL_UNSIGNED_INT_5_9_9_9_REV, GL_RGB9_E5 };
+    GL_UNSIGNED_INT_5_9_9_9_REV, GL_RGB9_E5, GL_UNSIGNED_SHORT, GL_SHORT, GL_R16_EXT, GL_RG16_EXT, GL_RGB16_EXT, GL_RGBA16_EXT,
+    GL_R16_SNORM_EXT, GL_RG16_SNORM_EXT, GL_RGB16_SNORM_EXT, GL_RGBA16_SNORM_EXT };

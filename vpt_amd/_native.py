@@ -25,6 +25,7 @@ FILTER_QUASI_CUBIC = 2
 FORMAT_R8, FORMAT_RG8, FORMAT_R32F, FORMAT_RG32F = 0, 1, 2, 3
 FORMAT_R8_SNORM, FORMAT_RG8_SNORM = 4, 5
 FORMAT_RGB565, FORMAT_RGBA4, FORMAT_RGB5_A1, FORMAT_RGB10_A2, FORMAT_R11F_G11F_B10F, FORMAT_RGB9_E5 = 6, 7, 8, 9, 10, 11
+FORMAT_R16, FORMAT_RG16, FORMAT_R16_SNORM, FORMAT_RG16_SNORM = 12, 13, 14, 15
 BUFFER_RENDER, BUFFER_FRAME, BUFFER_ACCUM = 0, 1, 2
 BUFFER_MCM_POSITION, BUFFER_MCM_DIRECTION, BUFFER_MCM_TRANSMITTANCE, BUFFER_MCM_RADIANCE = 3, 4, 5, 6
 BUFFER_DOS_OCCLUSION = 7

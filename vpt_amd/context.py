@@ -2,6 +2,18 @@
 import ctypes as C
 
 from . import _native as N
+from .readers import (GL_R16_EXT, GL_RG16_EXT, GL_RGB16_EXT, GL_RGBA16_EXT,
+                      GL_R16_SNORM_EXT, GL_RG16_SNORM_EXT, GL_RGB16_SNORM_EXT, GL_RGBA16_SNORM_EXT)
+
+
+class EXTTextureNorm16:
+    """What gl.getExtension('EXT_texture_norm16') returns in WebGL2: the extension's sized internal formats.  Once a context has handed
+    it out, volumes of that context take UNSIGNED_SHORT / SHORT manifests with these internal formats (vpt_amd.volume.device_format)."""
+    R16_EXT, RG16_EXT, RGB16_EXT, RGBA16_EXT = GL_R16_EXT, GL_RG16_EXT, GL_RGB16_EXT, GL_RGBA16_EXT
+    R16_SNORM_EXT, RG16_SNORM_EXT, RGB16_SNORM_EXT, RGBA16_SNORM_EXT = GL_R16_SNORM_EXT, GL_RG16_SNORM_EXT, GL_RGB16_SNORM_EXT, GL_RGBA16_SNORM_EXT
+
+
+_EXTENSIONS = {'EXT_texture_norm16': EXTTextureNorm16}
 
 
 class Context:
@@ -19,6 +31,18 @@ class Context:
             N.check(L.vpt_context_create_on_stream(int(device), C.c_void_p(int(stream)), C.byref(h)))
         self._h = h
         self.device = int(device)
+        self._extensions = {}
+
+    def getExtension(self, name):
+        """WebGL's getExtension: the extension object (enabled on this context from now on), or None for a name this library does not know"""
+        if name not in _EXTENSIONS:
+            return None
+        if name not in self._extensions:
+            self._extensions[name] = _EXTENSIONS[name]()
+        return self._extensions[name]
+
+    def extension_enabled(self, name):
+        return name in self._extensions
 
     @staticmethod
     def device_count():

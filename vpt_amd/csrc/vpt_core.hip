@@ -77,7 +77,7 @@ extern "C" int vpt_context_synchronize(vpt_context *c) {
 // ---------------------------------------------------------------------------------------------
 extern "C" int vpt_volume_create(vpt_context *c, int w, int h, int d, int format, vpt_volume **out) {
     if (!c || !out) return fail(VPT_ERR_INVALID, "null argument");
-    if (format < VPT_FORMAT_R8 || format > VPT_FORMAT_RGB9_E5) return fail(VPT_ERR_UNSUPPORTED, "Unknown volume datatype: %d", format);  // Volume.js:103
+    if (format < VPT_FORMAT_R8 || format > VPT_FORMAT_RG16_SNORM) return fail(VPT_ERR_UNSUPPORTED, "Unknown volume datatype: %d", format);  // Volume.js:103
     if (w < 1 || h < 1 || d < 1 || w > 4096 || h > 4096 || d > 4096)
         return fail(VPT_ERR_INVALID, "volume dimensions %dx%dx%d out of range [1,4096]", w, h, d);
     HIP_TRY(hipSetDevice(c->device));
@@ -85,15 +85,19 @@ extern "C" int vpt_volume_create(vpt_context *c, int w, int h, int d, int format
     memset(v, 0, sizeof(*v));
     v->ctx = c; v->nx = w; v->ny = h; v->nz = d;
     // packed formats (VPT_FORMAT_RGB565 ..): the words are decoded on upload (k_decode_packed) into an RG32F volume
-    v->packed = format >= VPT_FORMAT_RGB565 ? format : 0;
+    v->packed = (format >= VPT_FORMAT_RGB565 && format <= VPT_FORMAT_RGB9_E5) ? format : 0;
     v->packed_bytes = (format == VPT_FORMAT_RGB565 || format == VPT_FORMAT_RGBA4 || format == VPT_FORMAT_RGB5_A1) ? 2 : 4;
-    v->snorm = format == VPT_FORMAT_R8_SNORM || format == VPT_FORMAT_RG8_SNORM;
-    v->channels = (format == VPT_FORMAT_RG8 || format == VPT_FORMAT_RG32F || format == VPT_FORMAT_RG8_SNORM || v->packed) ? 2 : 1;
+    // 16-bit normalised formats: uint16 / int16 channels, kept as they are (2 bytes per channel in the linear storage and the bricks)
+    v->norm16 = format >= VPT_FORMAT_R16 && format <= VPT_FORMAT_RG16_SNORM;
+    v->snorm = format == VPT_FORMAT_R8_SNORM || format == VPT_FORMAT_RG8_SNORM || format == VPT_FORMAT_R16_SNORM || format == VPT_FORMAT_RG16_SNORM;
+    v->channels = (format == VPT_FORMAT_RG8 || format == VPT_FORMAT_RG32F || format == VPT_FORMAT_RG8_SNORM || v->packed ||
+                   format == VPT_FORMAT_RG16 || format == VPT_FORMAT_RG16_SNORM) ? 2 : 1;
     v->f32 = format == VPT_FORMAT_R32F || format == VPT_FORMAT_RG32F || v->packed;
-    v->vox_bytes = v->channels * (v->f32 ? 4 : 1);
-    // RG8: 256-byte slots (R brick at +0, G brick at +128); R32F: 512-byte slots; RG32F: 1024-byte slots (G brick at +512)
-    const int slot_shift = (v->f32 ? 9 : 7) + (v->channels == 2 ? 1 : 0);
-    const uint64_t eb = v->f32 ? 4 : 1;                  // bytes per texel channel
+    const uint64_t eb = v->f32 ? 4 : (v->norm16 ? 2 : 1);  // bytes per texel channel
+    v->vox_bytes = v->channels * (int)eb;
+    // RG8: 256-byte slots (R brick at +0, G brick at +128); R16: 256-byte slots (5^3 words = 250 bytes), RG16: 512-byte slots (G brick at +256);
+    // R32F: 512-byte slots; RG32F: 1024-byte slots (G brick at +512).  The G brick is always 128 texels behind the R brick
+    const int slot_shift = (v->f32 ? 9 : (v->norm16 ? 8 : 7)) + (v->channels == 2 ? 1 : 0);
     v->filter = VPT_FILTER_LINEAR;                       // Volume.js:53-54
     int nbx = (w + 3) / 4, nby = (h + 3) / 4, nbz = (d + 3) / 4;
     // Z-order over the bricks with exactly as many bits per axis as the axis needs: the low bits of x, y, z interleave
@@ -111,12 +115,13 @@ extern "C" int vpt_volume_create(vpt_context *c, int w, int h, int d, int format
     if (e == hipSuccess) e = hipMalloc(&v->bricks, v->brick_bytes + 64);   // +64: the 8-byte tap windows end <= byte 125+7
     if (e == hipSuccess) {
         // boundary atlas: six face images (axis x: ny x nz cells, y: nx x nz, z: nx x ny; low side, high side) with one common
-        // power-of-two row pitch and one common size, one dword (byte volumes) or one float4 (float volumes) per cell and channel
+        // power-of-two row pitch and one common size, one dword (byte volumes) or one float4 (float volumes; 16-bit volumes: the decoded
+        // texels, always finite) per cell and channel
         int pitch = 1, shift = 0;
         while (pitch < std::max(w, h)) { pitch <<= 1; shift++; }
         v->atlas_shift = (uint32_t)shift;
         v->atlas_face = (uint32_t)pitch * (uint32_t)std::max(h, d);
-        v->atlas_dwords = 6 * (size_t)v->atlas_face * (size_t)v->channels * (v->f32 ? 4 : 1);
+        v->atlas_dwords = 6 * (size_t)v->atlas_face * (size_t)v->channels * ((v->f32 || v->norm16) ? 4 : 1);
         e = hipMalloc(&v->atlas, v->atlas_dwords * 4);
         v->atlas_ok = true;
         if (e == hipSuccess && v->f32) e = hipMalloc(&v->atlas_flag, sizeof(uint32_t));
@@ -145,7 +150,7 @@ extern "C" int vpt_volume_create(vpt_context *c, int w, int h, int d, int format
         HIP_TRY(hipMemcpy(v->tab32, t32.data(), t32.size() * 4, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(v->tabc, tc.data(), tc.size() * 4, hipMemcpyHostToDevice));
     }
-    if (v->channels == 1 && !v->f32 && !v->snorm) {
+    if (unsigned_r8(v)) {
         // column records: 2-D Z-order over (x, y) with as many bits per axis as the axis needs, nz records of 4 bytes per column
         int cb[2] = { 0, 0 };
         while ((1 << cb[0]) < w) cb[0]++;
@@ -172,7 +177,7 @@ extern "C" int vpt_volume_create(vpt_context *c, int w, int h, int d, int format
 // The column records (vpt_device.h record_addr) of a one-channel byte volume, (re)built from the linear storage when blocks have been
 // uploaded since the last build.  Allocated on first use: only the MCM renderer samples them (4 bytes per voxel).
 int volume_records(vpt_volume *v) {
-    if (!v || v->channels != 1 || v->f32 || v->snorm) return fail(VPT_ERR_INVALID, "column records exist for one-channel UNSIGNED_BYTE volumes");
+    if (!v || !unsigned_r8(v)) return fail(VPT_ERR_INVALID, "column records exist for one-channel UNSIGNED_BYTE volumes");
     VPT_TRY(vpt_volume_finalize(v));
     if (v->rec_valid) return VPT_OK;
     vpt_context *c = v->ctx;
@@ -239,11 +244,15 @@ extern "C" int vpt_volume_finalize(vpt_volume *v) {
     if (v->snorm) {   // R8_SNORM / RG8_SNORM: -128 reads as -1 = -127 / 127 (GL ES 3.0 2.1.6.1); clamped once, before bricks and atlas
         const size_t n = (size_t)v->nx * v->ny * v->nz * v->channels;
         int grid = (int)((n / 4 + 255) / 256); if (grid > 4096) grid = 4096; if (grid < 1) grid = 1;
-        hipLaunchKernelGGL(k_snorm_clamp, dim3(grid), dim3(256), 0, c->stream, v->linear, n);
+        if (v->norm16) hipLaunchKernelGGL(k_snorm16_clamp, dim3(grid), dim3(256), 0, c->stream, (uint16_t *)v->linear, n);   // (R16_SNORM: -32768)
+        else hipLaunchKernelGGL(k_snorm_clamp, dim3(grid), dim3(256), 0, c->stream, v->linear, n);
     }
     // one-channel volumes with dword-aligned rows go through the LDS-staged kernel (dword loads and stores)
     int fast = (v->channels == 1 && v->nx % 4 == 0) ? strips : 0;
-    if (v->f32) {
+    if (v->norm16) {
+        hipLaunchKernelGGL(k_brickify_16, dim3((unsigned)strips, (unsigned)nby, (unsigned)nbz), dim3(128), 0, c->stream, (const uint16_t *)v->linear, (uint16_t *)v->bricks, v->nx, v->ny, v->nz, v->channels, v->tabc);
+        fast = strips;
+    } else if (v->f32) {
         hipLaunchKernelGGL(k_brickify_f32, dim3((unsigned)strips, (unsigned)nby, (unsigned)nbz), dim3(128), 0, c->stream, (const float *)v->linear, (float *)v->bricks, v->nx, v->ny, v->nz, v->channels, v->tabc);
         fast = strips;                                    // nothing left for the byte kernels
     } else if (fast > 0)
@@ -263,6 +272,11 @@ extern "C" int vpt_volume_finalize(vpt_volume *v) {
             HIP_TRY(hipMemcpyAsync(&bad, v->atlas_flag, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
             HIP_TRY(hipStreamSynchronize(c->stream));
             v->atlas_ok = bad == 0;
+        } else if (v->norm16) {   // the decoded texels, the floats the sampler blends: finite, so the atlas is always in use
+            if (v->snorm) hipLaunchKernelGGL(k_build_atlas<int16_t>, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, c->stream, (const int16_t *)v->linear, (void *)v->atlas,
+                                             v->nx, v->ny, v->nz, v->channels, v->atlas_face, v->atlas_shift);
+            else hipLaunchKernelGGL(k_build_atlas<uint16_t>, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, c->stream, (const uint16_t *)v->linear, (void *)v->atlas,
+                                    v->nx, v->ny, v->nz, v->channels, v->atlas_face, v->atlas_shift);
         } else {
             hipLaunchKernelGGL(k_build_atlas<uint8_t>, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, c->stream, (const uint8_t *)v->linear, (void *)v->atlas,
                                v->nx, v->ny, v->nz, v->channels, v->atlas_face, v->atlas_shift);
@@ -686,8 +700,8 @@ int make_args(vpt_renderer *r, const vpt_uniforms *u, bool need_volume, PassArgs
         a->vol.hx = (float)(v->nx - 1); a->vol.hy = (float)(v->ny - 1); a->vol.hz = (float)(v->nz - 1);
         a->vol.tab32 = v->tab32; a->vol.tabc = v->tabc;
         a->vol.filter = v->filter;
-        a->vol.channels = v->channels; a->vol.slot_shift = (v->f32 ? 9u : 7u) + (v->channels == 2 ? 1u : 0u);
-        a->vol.elem_shift = v->f32 ? 2u : 0u;
+        a->vol.channels = v->channels; a->vol.slot_shift = (v->f32 ? 9u : (v->norm16 ? 8u : 7u)) + (v->channels == 2 ? 1u : 0u);
+        a->vol.elem_shift = v->f32 ? 2u : (v->norm16 ? 1u : 0u);
         a->vol.atlas = (r->boundary_atlas && v->atlas_ok) ? v->atlas : nullptr;
         a->vol.atlas_face = v->atlas_face; a->vol.atlas_shift = v->atlas_shift;
         if (renderer_uses_records(r)) {
@@ -1168,6 +1182,10 @@ static int probe_sample(vpt_renderer *r, const float *xyz, float *rgba, size_t n
             case 385: if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<385>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); else hipLaunchKernelGGL(k_probe_sample<385>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); break;
             case 392: if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<392>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); else hipLaunchKernelGGL(k_probe_sample<392>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); break;
             case 393: if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<393>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); else hipLaunchKernelGGL(k_probe_sample<393>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); break;
+#define PROBE_CASE(v, _) case v: if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<v>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); \
+                             else hipLaunchKernelGGL(k_probe_sample<v>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); break;
+            VPT_NORM16_VARIANTS(PROBE_CASE, 0)
+#undef PROBE_CASE
             default: hipFree(din); hipFree(dout); return fail(VPT_ERR_INVALID, "no probe kernel for variant %d", variant_of(r));
         }
         e = hipGetLastError();

@@ -297,8 +297,8 @@ struct DevVolume {
     float hx, hy, hz;        // (float)(n - 1)
     int filter;              // VPT_FILTER_*
     int channels;            // 1 = R8, 2 = RG8: the G brick follows the R brick in a 256-byte slot (R at +0, G at +128)
-    uint32_t slot_shift;     // log2 of the slot size: 7 (R8) or 8 (RG8)
-    uint32_t elem_shift;     // log2 of the bytes per texel channel: 0 (UNSIGNED_BYTE) or 2 (FLOAT)
+    uint32_t slot_shift;     // log2 of the slot size: 7 (R8) or 8 (RG8); + 1 for 16-bit, + 2 for FLOAT texels
+    uint32_t elem_shift;     // log2 of the bytes per texel channel: 0 (UNSIGNED_BYTE / BYTE), 1 (16-bit normalised) or 2 (FLOAT)
     const uint32_t *atlas;   // boundary atlas (one-channel volumes; null: not built or switched off) — see sample_volume_boundary
     uint32_t atlas_face, atlas_shift;   // dwords per face image, log2 of its row pitch
     // column records (one-channel byte volumes, LINEAR filter; null: not built or switched off) — see record_addr
@@ -352,6 +352,8 @@ VPT_DEV const uint8_t *cell_addr(const DevVolume &v, const LdsTables &t, uint32_
 #define VPT_V_REC     64  // in-cube samples from the column records instead of the bricks (one-channel byte volumes, LINEAR filter; MCM)
 #define VPT_V_SNORM   128 // BYTE texels (R8_SNORM / RG8_SNORM): bricks as R8 / RG8, each tap decoded to fl32(c / 127) and filtered as R32F
 #define VPT_V_QCUBIC  256 // quasi-cubic filter (VPT_FILTER_QUASI_CUBIC): the LINEAR cell and taps, smoothstep weights (qc_weight); never with NEAREST / REC
+#define VPT_V_NORM16  512 // 16-bit normalised texels (R16 / RG16; | VPT_V_SNORM: R16_SNORM / RG16_SNORM): 5^3 words in a 256-byte slot (RG: the G
+                          // brick 256 bytes behind), each tap decoded (norm16_decode) and filtered as R32F
 // The quasi-cubic weight of a LINEAR cell's fraction f: f' = (f * f) * (3 - 2 f), every operation rounded (the library is built with
 // -ffp-contract=off; 2 f is exact, so even a fused 3 - 2 f would be the same float).  f = 0 -> 0 and f = 1 -> 1 exactly, so every
 // clamped case of linear_cell keeps its exact edge value.  With the cell i = floor(u) and f = fract(u) of u = s N - 0.5 this is the
@@ -441,6 +443,66 @@ VPT_DEV float trilinear_taps(const uint8_t *a, float fx, float fy, float fz) {
         l0 = (uint32_t)w0; h0 = (uint32_t)(w0 >> 32); l1 = (uint32_t)w1; h1 = (uint32_t)(w1 >> 32);
     }
     return trilinear_blend<(V & VPT_V_SNORM) != 0>(l0, h0, l1, h1, fx, fy, fz);
+}
+// ---- 16-bit normalised texels (EXT_texture_norm16: VPT_V_NORM16) ---------------------------------------------------------
+// A tap is decoded to the float an R32F volume of the decoded texels holds: UNORM fl32(c / 65535), SNORM fl32(c / 32767) (c >= -32767: the
+// storage is clamped at finalize).  fl32(c * fl32(1/N)) misses that float for 512 of the 65536 UNORM and 1536 of the SNORM values; with
+// 1/N split into two floats hi + lo, fma(c, hi, c * lo) is exact for every c (c * lo rounded on its own: the library is built with
+// -ffp-contract=off; exhaustive check in tests/test_norm16_host.py).
+#define VPT_UNORM16_HI 0x1.0001p-16f     // fl32(1/65535)
+#define VPT_UNORM16_LO 0x1.0001p-48f     // fl32(1/65535 - VPT_UNORM16_HI)
+#define VPT_SNORM16_HI 0x1.0002p-15f     // fl32(1/32767)
+#define VPT_SNORM16_LO 0x1.0002p-45f     // fl32(1/32767 - VPT_SNORM16_HI)
+template <bool SNORM> VPT_DEV float norm16_decode(float c) {
+    return SNORM ? fmaf(c, VPT_SNORM16_HI, c * VPT_SNORM16_LO) : fmaf(c, VPT_UNORM16_HI, c * VPT_UNORM16_LO);
+}
+// word W (0: bits 15-0, 1: bits 31-16) of a loaded dword as the tap's float (the conversion takes the word by an SDWA select)
+template <bool SNORM, int W> VPT_DEV float norm16_word(uint32_t d) {
+    if (SNORM) return norm16_decode<true>((float)(W ? (int32_t)d >> 16 : (int32_t)(int16_t)(uint16_t)d));
+    return norm16_decode<false>((float)(W ? d >> 16 : d & 0xffffu));
+}
+// The eight taps of a cell are elements e, e+1, e+5, e+6 (plane z) and e+25, e+26, e+30, e+31 (plane z + 1): two 14-byte spans at 2-byte
+// alignment.  A plane is ONE 16-byte load; its words as three dwords r0 = (e, e+1), r2 = (e+4, e+5), r3 = (e+6, -), so the taps are
+// lo r0, hi r0, hi r2, lo r3.  The last element a load touches is <= 93 + 25 + 7 = 125 of the slot (e <= 3 + 15 + 75): inside the slot.
+struct Words16 { uint32_t a, b, c, d; };
+struct Plane16 { uint32_t r0, r2, r3; };
+// the dword-aligned load of elements (e & ~1) .. +7, realigned by s = 0 or 2 bytes (v_alignbyte_b32)
+VPT_DEV Plane16 plane16_aligned(const uint8_t *aligned, uint32_t s) {
+    Words16 w;
+    __builtin_memcpy(&w, __builtin_assume_aligned(aligned, 4), 16);
+    return Plane16{ __builtin_amdgcn_alignbyte(w.b, w.a, s), __builtin_amdgcn_alignbyte(w.d, w.c, s), __builtin_amdgcn_alignbyte(w.d, w.d, s) };
+}
+// ... and the 2-byte-aligned load of elements e .. e + 7
+VPT_DEV Plane16 plane16(const uint8_t *a) {
+    Words16 w;
+    __builtin_memcpy(&w, a, 16);
+    return Plane16{ w.a, w.c, w.d };
+}
+// the R32F path's x -> y -> z lerps over the decoded taps, no normalisation afterwards
+template <bool SNORM>
+VPT_DEV float norm16_blend(const Plane16 &p, const Plane16 &q, float fx, float fy, float fz) {
+    float c000 = norm16_word<SNORM, 0>(p.r0), c100 = norm16_word<SNORM, 1>(p.r0);
+    float c010 = norm16_word<SNORM, 1>(p.r2), c110 = norm16_word<SNORM, 0>(p.r3);
+    float c001 = norm16_word<SNORM, 0>(q.r0), c101 = norm16_word<SNORM, 1>(q.r0);
+    float c011 = norm16_word<SNORM, 1>(q.r2), c111 = norm16_word<SNORM, 0>(q.r3);
+    float c00 = lerpf(c000, c100, fx), c10 = lerpf(c010, c110, fx);
+    float c01 = lerpf(c001, c101, fx), c11 = lerpf(c011, c111, fx);
+    return lerpf(lerpf(c00, c10, fy), lerpf(c01, c11, fy), fz);
+}
+// the ALIGNED form from the split address (brick array base + 32-bit byte offset of the cell's first tap; the offset is even)
+template <bool SNORM>
+VPT_DEV float norm16_aligned_taps(const uint8_t *base, uint32_t off, float fx, float fy, float fz) {
+    const uint32_t o1 = off + 50u, s0 = off & 2u, s1 = o1 & 2u;
+    return norm16_blend<SNORM>(plane16_aligned(base + (off - s0), s0), plane16_aligned(base + (o1 - s1), s1), fx, fy, fz);
+}
+template <int V>
+VPT_DEV float norm16_taps(const uint8_t *a, float fx, float fy, float fz) {
+    constexpr bool SNORM = (V & VPT_V_SNORM) != 0;
+    if ((V & VPT_V_ALIGNED)) {
+        const uint32_t s0 = (uint32_t)(uintptr_t)a & 2u, s1 = ((uint32_t)(uintptr_t)a + 50u) & 2u;
+        return norm16_blend<SNORM>(plane16_aligned(a - s0, s0), plane16_aligned(a + 50 - s1, s1), fx, fy, fz);
+    }
+    return norm16_blend<SNORM>(plane16(a), plane16(a + 50), fx, fy, fz);
 }
 // ---- column records (round 4) -------------------------------------------------------------------------------------------
 // The photons of the MCM renderer sample at independent random positions: after its first event no two lanes of a wave share a
@@ -554,7 +616,8 @@ VPT_DEV float boundary_blend(uint32_t w, float fa, float fb) {
 // sample_volume_rg<V> at the clamped position (float texels: finite ones, see vpt_volume_finalize).  Precondition as boundary_cell's.
 template <int V>
 VPT_DEV f2 sample_boundary_rg(const DevVolume &v, f3 p) {
-    constexpr bool NEAREST = (V & VPT_V_NEAREST) != 0, RG = (V & VPT_V_RG) != 0, F32 = (V & VPT_V_F32) != 0, SNORM = (V & VPT_V_SNORM) != 0;
+    // (16-bit normalised volumes keep the decoded texels in a float atlas: the FLOAT path)
+    constexpr bool NEAREST = (V & VPT_V_NEAREST) != 0, RG = (V & VPT_V_RG) != 0, F32 = (V & (VPT_V_F32 | VPT_V_NORM16)) != 0, SNORM = (V & VPT_V_SNORM) != 0;
     float fa, fb;
     const uint32_t idx = boundary_cell_lane<NEAREST>(v, p, fa, fb);
     fa = cell_weight<V>(fa); fb = cell_weight<V>(fb);                  // (the clamped axis has f = 0 and stays 0)
@@ -585,6 +648,24 @@ VPT_DEV f2 sample_volume_rg(const DevVolume &v, const LdsTables &t, f3 p) {
     constexpr bool WIDE = (V & VPT_V_WIDE) != 0;
     constexpr bool RG = (V & VPT_V_RG) != 0;
     constexpr bool SNORM = (V & VPT_V_SNORM) != 0;
+    if (V & VPT_V_NORM16) {
+        // 16-bit normalised texels: the cell of the other formats, the taps decoded and blended as R32F (the G brick 128 words behind the R brick)
+        if (V & VPT_V_NEAREST) {
+            uint32_t x = nearest_cell(p.x, v.fnx, v.hx), y = nearest_cell(p.y, v.fny, v.hy), z = nearest_cell(p.z, v.fnz, v.hz);
+            const uint16_t *b = (const uint16_t *)cell_addr<WIDE>(v, t, x, y, z);
+            return f2{ norm16_word<SNORM, 0>(b[0]), RG ? norm16_word<SNORM, 0>(b[128]) : 0.0f };
+        }
+        uint32_t x, y, z; float fx, fy, fz;
+        filter_cell<V>(p.x, v.fnx, v.hx, x, fx);
+        filter_cell<V>(p.y, v.fny, v.hy, y, fy);
+        filter_cell<V>(p.z, v.fnz, v.hz, z, fz);
+        if ((V & VPT_V_ALIGNED) && !WIDE) {
+            const uint32_t off = t.tx[x] + t.ty[y] + t.tz[z];
+            return f2{ norm16_aligned_taps<SNORM>(v.bricks, off, fx, fy, fz), RG ? norm16_aligned_taps<SNORM>(v.bricks, off + 256u, fx, fy, fz) : 0.0f };
+        }
+        const uint8_t *a = cell_addr<WIDE>(v, t, x, y, z);
+        return f2{ norm16_taps<V>(a, fx, fy, fz), RG ? norm16_taps<V>(a + 256, fx, fy, fz) : 0.0f };
+    }
     if (V & VPT_V_F32) {
         // FLOAT texels (Volume.js:84-105 `FLOAT` / `HALF_FLOAT`; LINEAR filtering of float textures: OES_texture_float_linear,
         // RenderingContext.js:78): the brick holds 5^3 floats, a row's two taps are one dword-aligned 8-byte load; same

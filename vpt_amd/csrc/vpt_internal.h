@@ -51,10 +51,11 @@ struct vpt_volume {
     int nx, ny, nz;
     int channels;          // 1 = R8 / R32F, 2 = RG8 (interleaved)
     bool f32;              // FLOAT texels (VPT_FORMAT_R32F): 4 bytes per voxel, 512-byte brick slots
-    bool snorm;            // BYTE texels (VPT_FORMAT_R8_SNORM / RG8_SNORM): stored like R8 / RG8, sampled through VPT_V_SNORM
+    bool snorm;            // signed normalised texels (VPT_FORMAT_R8_SNORM / RG8_SNORM: stored like R8 / RG8; R16_SNORM / RG16_SNORM): VPT_V_SNORM
+    bool norm16;           // 16-bit normalised texels (VPT_FORMAT_R16 .. RG16_SNORM): 2 bytes per channel, 256-byte brick slots, VPT_V_NORM16
     int packed;            // packed source format (VPT_FORMAT_RGB565 ..; 0: none): uploads are decoded into RG32F storage (f32, 2 channels)
     int packed_bytes;      // bytes per packed source texel: 2 or 4
-    int vox_bytes;         // bytes per voxel of the linear storage: channels * (f32 ? 4 : 1)
+    int vox_bytes;         // bytes per voxel of the linear storage: channels * (f32 ? 4 : norm16 ? 2 : 1)
     int filter;
     uint8_t *linear;       // nx*ny*nz*channels, the "texture storage" blocks are uploaded into
     uint8_t *bricks;       // apron bricks, Morton order
@@ -66,7 +67,8 @@ struct vpt_volume {
     bool any_upload;
     uint8_t *staging; size_t staging_bytes;
     uint32_t *atlas;       // boundary atlas: the six outer voxel planes as 2 x 2-footprint cells (vpt_device.h sample_volume_boundary): one dword per cell
-                           // and channel (byte volumes) or one float4 (float volumes); channel c's faces 6 * atlas_face cells behind c - 1's
+                           // and channel (byte volumes) or one float4 (float volumes; 16-bit volumes: the decoded texels); channel c's faces
+                           // 6 * atlas_face cells behind c - 1's
     size_t atlas_dwords;
     bool atlas_ok;         // float volumes: every texel is finite and < 1e37 (k_scan_finite at finalize): else the atlas is not used
     uint32_t *atlas_flag;
@@ -347,7 +349,8 @@ static int launch_sampling(K kernel, vpt_renderer *r, const PassArgs &a, unsigne
     }
     return VPT_OK;
 }
-// the instantiation for (addressing, filter, channels, texels): V = VPT_V_WIDE | VPT_V_NEAREST | VPT_V_RG | VPT_V_F32 | VPT_V_SNORM | VPT_V_QCUBIC bits
+// the instantiation for (addressing, filter, channels, texels): V = VPT_V_WIDE | VPT_V_NEAREST | VPT_V_RG | VPT_V_F32 | VPT_V_SNORM | VPT_V_QCUBIC |
+// VPT_V_NORM16 bits
 // MCM on a one-channel byte volume with the LINEAR filter: the in-cube samples come from the column records (VPT_OPTION_COLUMN_RECORDS).
 // Measured (round 4, 1080p headline camera, us per frame bricks -> records): 512^3 80.0 -> 83.3, every tile HIT 143.9 -> 157.1, extinction 50
 // 80.3 -> 92.9 — 256 MiB of bricks mostly live in the 256 MB Infinity Cache and a dense medium's short steps re-use brick lines, 512 MiB of
@@ -355,17 +358,26 @@ static int launch_sampling(K kernel, vpt_renderer *r, const PassArgs &a, unsigne
 #define VPT_RECORDS_AUTO_BYTES (512ull << 20)
 static inline bool renderer_uses_records(const vpt_renderer *r) {
     const vpt_volume *v = r->vol;
-    if (!(r->kind == VPT_RENDERER_MCM && v && v->channels == 1 && !v->f32 && !v->snorm && v->filter == VPT_FILTER_LINEAR && v->rtab32 != nullptr)) return false;
+    if (!(r->kind == VPT_RENDERER_MCM && v && v->channels == 1 && !v->f32 && !v->snorm && !v->norm16 && v->filter == VPT_FILTER_LINEAR && v->rtab32 != nullptr)) return false;
     return r->column_records == 1 || (r->column_records == 2 && v->brick_bytes > VPT_RECORDS_AUTO_BYTES);
 }
 static inline int variant_of(const vpt_renderer *r) {
     return ((r->vol->wide || (renderer_uses_records(r) && r->vol->rec_wide)) ? VPT_V_WIDE : 0) | (r->vol->filter == VPT_FILTER_NEAREST ? VPT_V_NEAREST : 0) | (r->vol->channels == 2 ? VPT_V_RG : 0) |
-           (r->vol->f32 ? VPT_V_F32 : 0) | (r->vol->snorm ? VPT_V_SNORM : 0) | (r->vol->filter == VPT_FILTER_QUASI_CUBIC ? VPT_V_QCUBIC : 0);
+           (r->vol->f32 ? VPT_V_F32 : 0) | (r->vol->snorm ? VPT_V_SNORM : 0) | (r->vol->filter == VPT_FILTER_QUASI_CUBIC ? VPT_V_QCUBIC : 0) |
+           (r->vol->norm16 ? VPT_V_NORM16 : 0);
 }
 // an UNSIGNED_BYTE one-channel volume: what the column records and the persistent forms take
-static inline bool unsigned_r8(const vpt_volume *v) { return v->channels == 1 && !v->f32 && !v->snorm; }
+static inline bool unsigned_r8(const vpt_volume *v) { return v->channels == 1 && !v->f32 && !v->snorm && !v->norm16; }
 // ... with the LINEAR or NEAREST filter: the persistent forms (VPT_OPTION_*_PERSISTENT) have no quasi-cubic instantiation
 static inline bool persistent_volume(const vpt_volume *v) { return unsigned_r8(v) && v->filter != VPT_FILTER_QUASI_CUBIC; }
+// the variants of the 16-bit normalised volumes (VPT_V_NORM16, | VPT_V_SNORM): {LINEAR, NEAREST, QUASI_CUBIC} x {R, RG} x {32-bit, wide
+// tables}: X(v, ...) once per variant
+#define VPT_NORM16_VARIANTS(X, ...) \
+    X(512, __VA_ARGS__) X(513, __VA_ARGS__) X(514, __VA_ARGS__) X(515, __VA_ARGS__) X(520, __VA_ARGS__) X(521, __VA_ARGS__) X(522, __VA_ARGS__) \
+    X(523, __VA_ARGS__) X(768, __VA_ARGS__) X(769, __VA_ARGS__) X(776, __VA_ARGS__) X(777, __VA_ARGS__) \
+    X(640, __VA_ARGS__) X(641, __VA_ARGS__) X(642, __VA_ARGS__) X(643, __VA_ARGS__) X(648, __VA_ARGS__) X(649, __VA_ARGS__) X(650, __VA_ARGS__) \
+    X(651, __VA_ARGS__) X(896, __VA_ARGS__) X(897, __VA_ARGS__) X(904, __VA_ARGS__) X(905, __VA_ARGS__)
+#define LAUNCH_S_CASE(v, KT, r, a) case v: VPT_TRY(launch_sampling(KT(v), (r), (a), g_)); break;
 #define LAUNCH_S(KT, r, a) do { \
     unsigned g_ = (unsigned)(r)->ntiles; \
     switch (variant_of(r)) { \
@@ -405,6 +417,7 @@ static inline bool persistent_volume(const vpt_volume *v) { return unsigned_r8(v
         case 385: VPT_TRY(launch_sampling(KT(385), (r), (a), g_)); break; \
         case 392: VPT_TRY(launch_sampling(KT(392), (r), (a), g_)); break; \
         case 393: VPT_TRY(launch_sampling(KT(393), (r), (a), g_)); break; \
+        VPT_NORM16_VARIANTS(LAUNCH_S_CASE, KT, r, a) \
         default: return fail(VPT_ERR_INVALID, "no sampling kernel for variant %d", variant_of(r)); \
     } } while (0)
 

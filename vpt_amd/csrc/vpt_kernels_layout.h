@@ -79,6 +79,11 @@ __global__ void k_snorm_clamp(uint8_t *lin, size_t n) {
     for (size_t t = 4 * n4 + (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (size_t)gridDim.x * blockDim.x)
         if (lin[t] == 0x80u) lin[t] = 0x81u;
 }
+// SNORM16 volumes: word 0x8000 (-32768) -> 0x8001 (-32767) over the linear storage (n words)
+__global__ void k_snorm16_clamp(uint16_t *lin, size_t n) {
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (size_t)gridDim.x * blockDim.x)
+        if (lin[t] == 0x8000u) lin[t] = 0x8001u;
+}
 // linear volume -> apron bricks in Morton order; one 128-thread workgroup per brick
 // (3-D grid: a 1-D grid of 2048^3's 2^27 bricks x 128 threads exceeds HIP's 2^32 work-items per dimension)
 // `ch` = 1 (R8: 128-byte slots) or 2 (RG8: 256-byte slots, the R brick at +0 and the G brick at +128)
@@ -176,8 +181,9 @@ __global__ void __launch_bounds__(256) k_brickify_strip(const uint8_t *lin, uint
 
 // FLOAT volumes: linear floats -> 5^3-float apron bricks in 512-byte slots (slot = brick code << 9; two channels: 1024-byte slots,
 // the G brick 512 bytes behind the R brick); VPT_BRICKIFY_RUN bricks of a brick row per workgroup, thread t < 125 carries local
-// voxel t of each
-__global__ void __launch_bounds__(128) k_brickify_f32(const float *lin, float *bricks, int nx, int ny, int nz, int ch, const uint32_t *codes) {
+// voxel t of each.  T = uint16_t: the same for 16-bit volumes (256- / 512-byte slots, the G brick 256 bytes behind)
+template <typename T>
+VPT_DEV void brickify_elems(const T *lin, T *bricks, int nx, int ny, int nz, int ch, const uint32_t *codes) {
     const int by = (int)blockIdx.y, bz = (int)blockIdx.z, t = (int)threadIdx.x;
     if (t >= 125) return;
     const int nbx = (nx + VPT_BRICK - 1) / VPT_BRICK;
@@ -185,7 +191,7 @@ __global__ void __launch_bounds__(128) k_brickify_f32(const float *lin, float *b
     const int y = min(by * VPT_BRICK + ly, ny - 1), z = min(bz * VPT_BRICK + lz, nz - 1);
     const size_t row = ((size_t)z * ny + y) * nx;
     const uint32_t cyz = codes[nx + 4 * by] + codes[nx + ny + 4 * bz];
-    const int shift = ch == 2 ? 8 : 7;                                          // floats per slot: 128 or 256
+    const int shift = ch == 2 ? 8 : 7;                                          // texels per slot: 128 or 256
     for (int u = 0; u < VPT_BRICKIFY_RUN; u++) {
         int bx = (int)blockIdx.x * VPT_BRICKIFY_RUN + u;
         if (bx >= nbx) break;
@@ -193,6 +199,12 @@ __global__ void __launch_bounds__(128) k_brickify_f32(const float *lin, float *b
         const size_t slot = (size_t)(codes[4 * bx] + cyz) << shift;
         for (int c = 0; c < ch; c++) bricks[slot + (size_t)c * 128 + t] = lin[(row + x) * ch + c];
     }
+}
+__global__ void __launch_bounds__(128) k_brickify_f32(const float *lin, float *bricks, int nx, int ny, int nz, int ch, const uint32_t *codes) {
+    brickify_elems(lin, bricks, nx, ny, nz, ch, codes);
+}
+__global__ void __launch_bounds__(128) k_brickify_16(const uint16_t *lin, uint16_t *bricks, int nx, int ny, int nz, int ch, const uint32_t *codes) {
+    brickify_elems(lin, bricks, nx, ny, nz, ch, codes);
 }
 
 // column records (vpt_device.h record_addr): a workgroup takes 64 voxels of a row x 16 slices of one y, stages the rows y and
@@ -225,8 +237,13 @@ __global__ void __launch_bounds__(256) k_build_records(const uint8_t *lin, uint8
 // boundary atlas (vpt_device.h sample_volume_boundary): thread c of [0, cx + cy + cz) builds cell c of the low-side AND the
 // high-side face of its axis from the linear volume.  Face x: cells (a, b) = (y, z); y: (x, z); z: (x, y); face f = 2 * axis +
 // side at dword f * face, cell (a, b) at (b << shift) + a.
-// T = uint8_t: one dword per cell (four bytes); T = float: one 16-byte cell (four floats).  `ch` interleaved channels in the linear volume:
-// channel c's six face images start 6 * face cells behind channel c - 1's.
+// T = uint8_t: one dword per cell (four bytes); T = float: one 16-byte cell (four floats); T = uint16_t / int16_t (16-bit normalised): one
+// 16-byte cell of the decoded texels (atlas_texel).  `ch` interleaved channels in the linear volume: channel c's six face images start
+// 6 * face cells behind channel c - 1's.
+VPT_DEV float atlas_texel(float t) { return t; }
+VPT_DEV float atlas_texel(uint8_t t) { return (float)t; }          // (not taken: byte cells are packed dwords)
+VPT_DEV float atlas_texel(uint16_t c) { return norm16_decode<false>((float)c); }
+VPT_DEV float atlas_texel(int16_t c) { return norm16_decode<true>((float)c); }
 template <typename T>
 __global__ void __launch_bounds__(256) k_build_atlas(const T *lin, void *atlas, int nx, int ny, int nz, int ch, uint32_t face, uint32_t shift) {
     size_t c = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -250,7 +267,7 @@ __global__ void __launch_bounds__(256) k_build_atlas(const T *lin, void *atlas, 
             if (sizeof(T) == 1)
                 ((uint32_t *)atlas)[cell] = (uint32_t)vox(a, b) | ((uint32_t)vox(a1, b) << 8) | ((uint32_t)vox(a, b1) << 16) | ((uint32_t)vox(a1, b1) << 24);
             else
-                ((float4 *)atlas)[cell] = make_float4((float)vox(a, b), (float)vox(a1, b), (float)vox(a, b1), (float)vox(a1, b1));
+                ((float4 *)atlas)[cell] = make_float4(atlas_texel(vox(a, b)), atlas_texel(vox(a1, b)), atlas_texel(vox(a, b1)), atlas_texel(vox(a1, b1)));
         }
 }
 // float volumes: is every texel finite and small enough that a difference of two texels cannot overflow?  Only then is

@@ -189,7 +189,7 @@ template <int V>
 VPT_DEV float4 mcm_sample(const PassArgs &a, const LdsTables &t, f3 p, bool oob) {
     // (the quasi-cubic filter takes the one-phase sampler as well: with its weights in the two-phase form the fused fast-math kernels
     // spilled two to four VGPRs)
-    if (!(V & (VPT_V_NEAREST | VPT_V_RG | VPT_V_F32 | VPT_V_SNORM | VPT_V_QCUBIC))) return mcm_sample_finish<V>(a, t, mcm_sample_issue<V>(a, t, p, oob));
+    if (!(V & (VPT_V_NEAREST | VPT_V_RG | VPT_V_F32 | VPT_V_SNORM | VPT_V_QCUBIC | VPT_V_NORM16))) return mcm_sample_finish<V>(a, t, mcm_sample_issue<V>(a, t, p, oob));
     float4 vs = sample_volume_color<V>(a, t, p);
     asm volatile("" : "+v"(vs.w));
     return vs;

@@ -7,8 +7,10 @@
 // aligned against 72.3 unaligned on one stream, 52.1 / 63.3 on three; MIP 56.3 / 72.0, 45.1 / 64.1)
 #define K_MIP0(V) (k_mip<0, V | VPT_V_ALIGNED>)
 #define K_MIP1(V) (k_mip<1, V | VPT_V_ALIGNED>)
-#define K_EAM0(V) (k_eam<0, V | VPT_V_ALIGNED>)
-#define K_EAM1(V) (k_eam<1, V | VPT_V_ALIGNED>)
+// (16-bit volumes with brick-code tables: the unaligned 16-byte loads — the realigned words cost EAM a wave per SIMD there, 68 against 63 VGPRs)
+#define VPT_EAM_TAPS(V) ((((V) & VPT_V_NORM16) && ((V) & VPT_V_WIDE)) ? 0 : VPT_V_ALIGNED)
+#define K_EAM0(V) (k_eam<0, V | VPT_EAM_TAPS(V)>)
+#define K_EAM1(V) (k_eam<1, V | VPT_EAM_TAPS(V)>)
 #ifndef VPT_MCS_TAPS
 #define VPT_MCS_TAPS 0
 #endif

@@ -25,9 +25,9 @@ static bool mcm_classes_usable(const vpt_renderer *r, const PassArgs &a) {
     return r->cls.enabled && r->cls.valid && a.blur == 0.0f && memcmp(r->cls.mvp, a.mvp_inv.m, sizeof(r->cls.mvp)) == 0;
 }
 // the kernel side of it: the volume's boundary atlas (what k_mcm_miss samples; every format since round 4), no persistent-wave option
-// (SNORM volumes: the general pass — no MISS-tile kernel form of their own)
+// (SNORM byte volumes: the general pass — no MISS-tile kernel form of their own; 16-bit volumes borrow the FLOAT one, launch_mcm_classes)
 static bool mcm_classes_runnable(const vpt_renderer *r, const PassArgs &a) {
-    return a.vol.atlas != nullptr && !r->mcm_persistent && !r->vol->snorm;
+    return a.vol.atlas != nullptr && !r->mcm_persistent && !(r->vol->snorm && !r->vol->norm16);
 }
 // ... and of the bucket kernels (and of the HIT-tile kernel's early form): LINEAR one-channel byte volumes
 static bool mcm_plain_volume(const vpt_renderer *r) { return (variant_of(r) & ~VPT_V_WIDE) == 0 && unsigned_r8(r->vol); }
@@ -90,7 +90,12 @@ static int launch_mcm_classes(vpt_renderer *r, const PassArgs &a) {
     const bool late = !(fast && early);
     // a quasi-cubic volume reuses the LINEAR MISS-tile kernel of its format: a MISS tile's sample is executed and discarded (mcm_events_miss),
     // so the filter cannot change what that kernel writes (tests/test_gpu_quasicubic.py: classes against the general pass, bit for bit)
-    const int vm = variant_of(r) & ~VPT_V_QCUBIC;
+    // A 16-bit volume's MISS tiles run the MISS-tile kernel of the FLOAT format of the same channels and filter (no k_mcm_miss of their own).
+    // That kernel reads the volume through the boundary atlas alone (miss_sample_any -> sample_boundary_rg: no brick tables, no bricks),
+    // and a 16-bit volume's atlas IS the float atlas of its decoded texels (float4 cells, v->atlas_dwords sized for them, vpt_volume_create):
+    // every gather stays inside that allocation and reads what the R32F twin's would (tests/test_gpu_norm16.py: 1080p classes, atlas on / off).
+    int vm = variant_of(r) & ~VPT_V_QCUBIC;
+    if (vm & VPT_V_NORM16) vm = (vm & ~(VPT_V_NORM16 | VPT_V_SNORM)) | VPT_V_F32;
     if (vm & ~VPT_V_WIDE) km = format_miss_kernel<FUSE>(vm, fast);
     else if (check) km = fast ? (late ? (PassKernel)k_mcm_miss<FUSE, VPT_V_FAST, true, true> : (PassKernel)k_mcm_miss<FUSE, VPT_V_FAST, true, false>)
                          : (PassKernel)k_mcm_miss<FUSE, 0, true, true>;

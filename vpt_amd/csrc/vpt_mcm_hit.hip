@@ -15,6 +15,11 @@ template <bool FUSE> static PassKernel hit_kernel(int v, bool early) {
 }
 PassKernel mcm_hit_kernel(bool fuse, int v, bool early) { return fuse ? hit_kernel<true>(v, early) : hit_kernel<false>(v, early); }
 template <bool FUSE> static PassKernel format_hit_kernel(int v, bool wide, bool fast) {
+    if (v & VPT_V_NORM16) {
+        if (wide) { if (fast) NORM16_CASES((PassKernel)k_mcm_integrate<FUSE, F | VPT_V_WIDE | VPT_V_FAST>) NORM16_CASES((PassKernel)k_mcm_integrate<FUSE, F | VPT_V_WIDE>) }
+        if (fast) NORM16_CASES((PassKernel)k_mcm_integrate<FUSE, F | VPT_V_FAST>)
+        NORM16_CASES((PassKernel)k_mcm_integrate<FUSE, F>)
+    }
     if (v & VPT_V_QCUBIC) {
         if (wide) { if (fast) QC_CASES((PassKernel)k_mcm_integrate<FUSE, F | VPT_V_WIDE | VPT_V_FAST>) QC_CASES((PassKernel)k_mcm_integrate<FUSE, F | VPT_V_WIDE>) }
         if (fast) QC_CASES((PassKernel)k_mcm_integrate<FUSE, F | VPT_V_FAST>)

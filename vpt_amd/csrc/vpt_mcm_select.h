@@ -46,6 +46,22 @@ static inline int class_variant(const vpt_renderer *r, const PassArgs &a) {
         case VPT_V_QCUBIC | VPT_V_SNORM: { constexpr int F = VPT_V_QCUBIC | VPT_V_SNORM; return __VA_ARGS__; } \
         case VPT_V_QCUBIC | VPT_V_SNORM | VPT_V_RG: { constexpr int F = VPT_V_QCUBIC | VPT_V_SNORM | VPT_V_RG; return __VA_ARGS__; } \
         default: return nullptr; }
+// the 16-bit normalised formats (VPT_V_NORM16, | VPT_V_SNORM) with every filter: the HIT tiles through the general kernel of the variant; the
+// MISS tiles through the MISS-tile kernel of the FLOAT format of the same channels and filter (vpt_mcm.hip launch_mcm_classes)
+#define NORM16_CASES(...) switch (v & (VPT_V_NEAREST | VPT_V_RG | VPT_V_F32 | VPT_V_SNORM | VPT_V_QCUBIC | VPT_V_NORM16)) { \
+        case VPT_V_NORM16: { constexpr int F = VPT_V_NORM16; return __VA_ARGS__; } \
+        case VPT_V_NORM16 | VPT_V_NEAREST: { constexpr int F = VPT_V_NORM16 | VPT_V_NEAREST; return __VA_ARGS__; } \
+        case VPT_V_NORM16 | VPT_V_RG: { constexpr int F = VPT_V_NORM16 | VPT_V_RG; return __VA_ARGS__; } \
+        case VPT_V_NORM16 | VPT_V_RG | VPT_V_NEAREST: { constexpr int F = VPT_V_NORM16 | VPT_V_RG | VPT_V_NEAREST; return __VA_ARGS__; } \
+        case VPT_V_NORM16 | VPT_V_QCUBIC: { constexpr int F = VPT_V_NORM16 | VPT_V_QCUBIC; return __VA_ARGS__; } \
+        case VPT_V_NORM16 | VPT_V_QCUBIC | VPT_V_RG: { constexpr int F = VPT_V_NORM16 | VPT_V_QCUBIC | VPT_V_RG; return __VA_ARGS__; } \
+        case VPT_V_NORM16 | VPT_V_SNORM: { constexpr int F = VPT_V_NORM16 | VPT_V_SNORM; return __VA_ARGS__; } \
+        case VPT_V_NORM16 | VPT_V_SNORM | VPT_V_NEAREST: { constexpr int F = VPT_V_NORM16 | VPT_V_SNORM | VPT_V_NEAREST; return __VA_ARGS__; } \
+        case VPT_V_NORM16 | VPT_V_SNORM | VPT_V_RG: { constexpr int F = VPT_V_NORM16 | VPT_V_SNORM | VPT_V_RG; return __VA_ARGS__; } \
+        case VPT_V_NORM16 | VPT_V_SNORM | VPT_V_RG | VPT_V_NEAREST: { constexpr int F = VPT_V_NORM16 | VPT_V_SNORM | VPT_V_RG | VPT_V_NEAREST; return __VA_ARGS__; } \
+        case VPT_V_NORM16 | VPT_V_SNORM | VPT_V_QCUBIC: { constexpr int F = VPT_V_NORM16 | VPT_V_SNORM | VPT_V_QCUBIC; return __VA_ARGS__; } \
+        case VPT_V_NORM16 | VPT_V_SNORM | VPT_V_QCUBIC | VPT_V_RG: { constexpr int F = VPT_V_NORM16 | VPT_V_SNORM | VPT_V_QCUBIC | VPT_V_RG; return __VA_ARGS__; } \
+        default: return nullptr; }
 // vpt_mcm_hit.hip: k_mcm_integrate / k_mcm_integrate_early by variant (fuse: + _renderFrame)
 PassKernel mcm_hit_kernel(bool fuse, int v, bool early);                    // v: class_variant()
 PassKernel mcm_format_hit_kernel(bool fuse, int v, bool wide, bool fast);   // v: variant_of(), another volume format

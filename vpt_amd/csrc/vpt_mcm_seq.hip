@@ -28,6 +28,7 @@ int mcm_multi(vpt_renderer *r, const PassArgs &a, uint32_t npasses, uint2 *ring)
         const int v = class_variant(r, a);
         VARIANT_CASES(ring ? launch_frames(k_mcm_frames<V>, r, a, npasses, ring) : launch_multi(k_mcm_multi<V>, r, a, npasses))
     }
+#define MULTI_CASE(v, F) case v: return ring ? launch_frames(k_mcm_frames<v | F>, r, a, npasses, ring) : launch_multi(k_mcm_multi<v | F>, r, a, npasses);
 #define MULTI_CASES(F) switch (variant_of(r)) { \
         case 0: return ring ? launch_frames(k_mcm_frames<0 | F>, r, a, npasses, ring) : launch_multi(k_mcm_multi<0 | F>, r, a, npasses); \
         case 1: return ring ? launch_frames(k_mcm_frames<1 | F>, r, a, npasses, ring) : launch_multi(k_mcm_multi<1 | F>, r, a, npasses); \
@@ -65,9 +66,11 @@ int mcm_multi(vpt_renderer *r, const PassArgs &a, uint32_t npasses, uint2 *ring)
         case 385: return ring ? launch_frames(k_mcm_frames<385 | F>, r, a, npasses, ring) : launch_multi(k_mcm_multi<385 | F>, r, a, npasses); \
         case 392: return ring ? launch_frames(k_mcm_frames<392 | F>, r, a, npasses, ring) : launch_multi(k_mcm_multi<392 | F>, r, a, npasses); \
         case 393: return ring ? launch_frames(k_mcm_frames<393 | F>, r, a, npasses, ring) : launch_multi(k_mcm_multi<393 | F>, r, a, npasses); \
+        VPT_NORM16_VARIANTS(MULTI_CASE, F) \
         default: return fail(VPT_ERR_INVALID, "no frame-sequence kernel for variant %d", variant_of(r)); }
     if (r->fast_math) MULTI_CASES(VPT_V_FAST)
     MULTI_CASES(0)
 #undef MULTI_CASES
+#undef MULTI_CASE
 }
 

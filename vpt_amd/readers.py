@@ -25,6 +25,10 @@ GL_UNSIGNED_SHORT_5_5_5_1, GL_RGB5_A1 = 0x8034, 0x8057
 GL_UNSIGNED_INT_2_10_10_10_REV, GL_RGB10_A2 = 0x8368, 0x8059
 GL_UNSIGNED_INT_10F_11F_11F_REV, GL_R11F_G11F_B10F = 0x8C3B, 0x8C3A
 GL_UNSIGNED_INT_5_9_9_9_REV, GL_RGB9_E5 = 0x8C3E, 0x8C3D
+# 16-bit normalised volumes (Volume.js:84-105 maps UNSIGNED_SHORT -> Uint16Array, SHORT -> Int16Array), filterable through EXT_texture_norm16
+GL_UNSIGNED_SHORT, GL_SHORT = 5123, 5122
+GL_R16_EXT, GL_RG16_EXT, GL_RGB16_EXT, GL_RGBA16_EXT = 0x822A, 0x822C, 0x8054, 0x805B
+GL_R16_SNORM_EXT, GL_RG16_SNORM_EXT, GL_RGB16_SNORM_EXT, GL_RGBA16_SNORM_EXT = 0x8F98, 0x8F99, 0x8F9A, 0x8F9B
 
 
 class AbstractReader:

@@ -12,7 +12,9 @@ from .readers import (RAWReader, GL_RED, GL_R8, GL_RG, GL_RG8, GL_UNSIGNED_BYTE,
                       GL_BYTE, GL_R8_SNORM, GL_RG8_SNORM, GL_RGB8_SNORM, GL_RGBA8_SNORM,
                       GL_UNSIGNED_SHORT_5_6_5, GL_RGB565, GL_UNSIGNED_SHORT_4_4_4_4, GL_RGBA4, GL_UNSIGNED_SHORT_5_5_5_1, GL_RGB5_A1,
                       GL_UNSIGNED_INT_2_10_10_10_REV, GL_RGB10_A2, GL_UNSIGNED_INT_10F_11F_11F_REV, GL_R11F_G11F_B10F,
-                      GL_UNSIGNED_INT_5_9_9_9_REV, GL_RGB9_E5)
+                      GL_UNSIGNED_INT_5_9_9_9_REV, GL_RGB9_E5,
+                      GL_UNSIGNED_SHORT, GL_SHORT, GL_R16_EXT, GL_RG16_EXT, GL_RGB16_EXT, GL_RGBA16_EXT,
+                      GL_R16_SNORM_EXT, GL_RG16_SNORM_EXT, GL_RGB16_SNORM_EXT, GL_RGBA16_SNORM_EXT)
 
 # (type, format, internalFormat) -> (native format, channels in the file, numpy dtype of a block) for the formats keyed on all three:
 # SNORM bytes (RGB8_SNORM / RGBA8_SNORM keep their first two channels, as RGB8 / RGBA8 do) and the packed types, one word per texel
@@ -28,9 +30,22 @@ _SIZED = {
     (GL_UNSIGNED_INT_10F_11F_11F_REV, GL_RGB, GL_R11F_G11F_B10F): ('FORMAT_R11F_G11F_B10F', 1, np.uint32),
     (GL_UNSIGNED_INT_5_9_9_9_REV, GL_RGB, GL_RGB9_E5): ('FORMAT_RGB9_E5', 1, np.uint32),
 }
+# ... and those a context takes once it has enabled EXT_texture_norm16 (gl.getExtension): 16-bit normalised channels, uploaded as they are
+# (RGB16 / RGBA16 keep their first two channels)
+_NORM16 = {
+    (GL_UNSIGNED_SHORT, GL_RED, GL_R16_EXT): ('FORMAT_R16', 1, np.uint16),
+    (GL_UNSIGNED_SHORT, GL_RG, GL_RG16_EXT): ('FORMAT_RG16', 2, np.uint16),
+    (GL_UNSIGNED_SHORT, GL_RGB, GL_RGB16_EXT): ('FORMAT_RG16', 3, np.uint16),
+    (GL_UNSIGNED_SHORT, GL_RGBA, GL_RGBA16_EXT): ('FORMAT_RG16', 4, np.uint16),
+    (GL_SHORT, GL_RED, GL_R16_SNORM_EXT): ('FORMAT_R16_SNORM', 1, np.int16),
+    (GL_SHORT, GL_RG, GL_RG16_SNORM_EXT): ('FORMAT_RG16_SNORM', 2, np.int16),
+    (GL_SHORT, GL_RGB, GL_RGB16_SNORM_EXT): ('FORMAT_RG16_SNORM', 3, np.int16),
+    (GL_SHORT, GL_RGBA, GL_RGBA16_SNORM_EXT): ('FORMAT_RG16_SNORM', 4, np.int16),
+}
+NORM16_EXTENSION = 'EXT_texture_norm16'
 
 
-def device_format(modality):
+def device_format(modality, gl=None):
     """(native format, channels in the file, numpy dtype of a block) for a manifest's (type, format, internalFormat) — Volume.js:58-60
     allocates whatever internalFormat the manifest names and :84-105 `_typize` maps the GL type to a typed array.  What a WebGL2
     sampler3D can filter is what is taken here: UNSIGNED_BYTE and FLOAT / HALF_FLOAT (half widens to float exactly) with 1-4 channels —
@@ -38,7 +53,8 @@ def device_format(modality):
     (R8_SNORM, RG8_SNORM; RGB8_SNORM / RGBA8_SNORM keep two channels); and the packed types with the one internal format each names
     (RGB565, RGBA4, RGB5_A1, RGB10_A2, R11F_G11F_B10F, RGB9_E5: uploaded as words, decoded on the device).  Integer textures need a
     usampler3D / isampler3D, 16-bit normalised ones an extension the reference does not enable, and 3-D depth textures do not exist in
-    ES 3.0: every other combination raises the reference's error."""
+    ES 3.0: every other combination raises the reference's error.  ``gl``: the volume's context; once it has enabled EXT_texture_norm16
+    (gl.getExtension), UNSIGNED_SHORT / SHORT with that extension's R16 / RG16 / RGB16 / RGBA16 (_SNORM) internal formats are taken too."""
     t, f = modality['type'], modality['format']
     if t == GL_UNSIGNED_BYTE and f in (GL_RED, GL_RG, GL_RGB, GL_RGBA):
         n = {GL_RED: 1, GL_RG: 2, GL_RGB: 3, GL_RGBA: 4}[f]
@@ -47,6 +63,8 @@ def device_format(modality):
         n = {GL_RED: 1, GL_RG: 2, GL_RGB: 3, GL_RGBA: 4}[f]
         return (N.FORMAT_R32F if n == 1 else N.FORMAT_RG32F), n, (np.float32 if t == GL_FLOAT else np.float16)
     sized = _SIZED.get((t, f, modality.get('internalFormat')))
+    if sized is None and gl is not None and gl.extension_enabled(NORM16_EXTENSION):
+        sized = _NORM16.get((t, f, modality.get('internalFormat')))
     if sized is not None:
         return getattr(N, sized[0]), sized[1], sized[2]
     raise RuntimeError('Unknown volume datatype: %s' % t)                   # Volume.js:103
@@ -99,7 +117,7 @@ class Volume(EventTarget):
             L.vpt_volume_destroy(self.texture)
             self.texture = None
         dims = modality['dimensions']
-        fmt, nch, dtype = device_format(modality)
+        fmt, nch, dtype = device_format(modality, self._gl)
         h = C.c_void_p()
         N.check(L.vpt_volume_create(self._gl._h, dims['width'], dims['height'], dims['depth'], fmt, C.byref(h)))
         self.texture = h
@@ -135,14 +153,23 @@ class Volume(EventTarget):
 
     # ---- extension: whole-array upload (one block) for synthetic volumes ----
     @classmethod
-    def from_array(cls, gl, array, filter='linear', snorm=False):
+    def from_array(cls, gl, array, filter='linear', snorm=False, norm16=False):
         """Upload a [depth][height][width] (uint8: R8; float16 / float32: R32F) or [depth][height][width][2] (RG8 / RG32F) array (host -> HBM once).
-        ``snorm=True``: the array is int8 and becomes an R8_SNORM / RG8_SNORM volume (texel c reads as max(c / 127, -1))."""
+        ``snorm=True``: the array is int8 and becomes an R8_SNORM / RG8_SNORM volume (texel c reads as max(c / 127, -1)).
+        ``norm16=True``: the array is uint16 (R16 / RG16: c reads as c / 65535) or int16 (R16_SNORM / RG16_SNORM: max(c / 32767, -1)),
+        kept at 2 bytes per channel (EXT_texture_norm16)."""
         array = np.asarray(array)
         if snorm:
             if array.dtype != np.int8:
                 raise ValueError('an SNORM volume is uploaded from an int8 array')
-            return cls._from_snorm_array(gl, array, filter)
+            return cls._from_raw_array(gl, array, filter, (N.FORMAT_R8_SNORM, N.FORMAT_RG8_SNORM), GL_BYTE, (GL_R8_SNORM, GL_RG8_SNORM))
+        if norm16:
+            if array.dtype == np.uint16:
+                return cls._from_raw_array(gl, array, filter, (N.FORMAT_R16, N.FORMAT_RG16), GL_UNSIGNED_SHORT, (GL_R16_EXT, GL_RG16_EXT))
+            if array.dtype == np.int16:
+                return cls._from_raw_array(gl, array, filter, (N.FORMAT_R16_SNORM, N.FORMAT_RG16_SNORM), GL_SHORT,
+                                           (GL_R16_SNORM_EXT, GL_RG16_SNORM_EXT))
+            raise ValueError('a 16-bit normalised volume is uploaded from a uint16 (UNORM) or int16 (SNORM) array')
         f32 = array.dtype.kind == 'f'
         array = np.ascontiguousarray(array, dtype=np.float32 if f32 else np.uint8)
         if array.ndim == 4 and array.shape[3] != 2:
@@ -180,18 +207,20 @@ class Volume(EventTarget):
         return vol
 
     @classmethod
-    def _from_snorm_array(cls, gl, array, filter):
+    def _from_raw_array(cls, gl, array, filter, formats, gltype, internal_formats):
+        """the texels uploaded as they are: formats / internal_formats = (one channel, two channels)"""
         array = np.ascontiguousarray(array)
         if array.ndim == 4 and array.shape[3] != 2:
             raise ValueError('a two-channel volume is [depth][height][width][2]')
         d, h, w = array.shape[:3]
         channels = 2 if array.ndim == 4 else 1
-        vol = cls(gl, RAWReader(array.view(np.uint8), {'width': w * channels, 'height': h, 'depth': d}))
+        vox = channels * array.dtype.itemsize
+        vol = cls(gl, RAWReader(array.view(np.uint8), {'width': w * vox, 'height': h, 'depth': d}))
         L = N.lib()
         hnd = C.c_void_p()
-        N.check(L.vpt_volume_create(gl._h, w, h, d, N.FORMAT_RG8_SNORM if channels == 2 else N.FORMAT_R8_SNORM, C.byref(hnd)))
+        N.check(L.vpt_volume_create(gl._h, w, h, d, formats[channels - 1], C.byref(hnd)))
         vol.texture = hnd
-        zs = max(1, (1 << 30) // (w * h * channels))
+        zs = max(1, (1 << 30) // (w * h * vox))
         for z0 in range(0, d, zs):
             chunk = array[z0:min(d, z0 + zs)]
             N.check(L.vpt_volume_upload_block(hnd, 0, 0, z0, w, h, chunk.shape[0], chunk.ctypes.data_as(C.c_void_p), chunk.nbytes))
@@ -199,8 +228,8 @@ class Volume(EventTarget):
         vol.metadata = vol._reader.readMetadata()
         vol.modality = vol.metadata['modalities'][0]
         vol.modality['dimensions']['width'] = w
-        vol.modality['type'] = GL_BYTE
-        vol.modality['format'], vol.modality['internalFormat'] = (GL_RG, GL_RG8_SNORM) if channels == 2 else (GL_RED, GL_R8_SNORM)
+        vol.modality['type'] = gltype
+        vol.modality['format'], vol.modality['internalFormat'] = (GL_RG if channels == 2 else GL_RED), internal_formats[channels - 1]
         for b in vol.metadata['blocks']:
             b['dimensions']['width'] = w
         vol.ready = True
