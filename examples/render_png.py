@@ -4,6 +4,7 @@
     python examples/render_png.py --renderer mcm --tonemapper artistic --frames 64 --out out.png
     python examples/render_png.py --volume data.bvp ...        (BVP container)   --volume data.raw --dims 256 256 256
     python examples/render_png.py --renderer eam --filter quasicubic ...    (volume filter: linear, nearest or quasicubic)
+    python examples/render_png.py --renderer mcm --env sky.hdr --tonemapper aces ...   (a Radiance .hdr environment map lights MCS / MCM)
 
 Without --volume a synthetic 128^3 sphere with lattice noise is used.  PNG encoding is plain zlib (no imaging library)."""
 import argparse
@@ -32,6 +33,7 @@ def main():
     ap.add_argument("--filter", default="linear", choices=["linear", "nearest", "quasicubic"])
     ap.add_argument("--yaw", type=float, default=0.6)
     ap.add_argument("--pitch", type=float, default=-0.35)
+    ap.add_argument("--env", default="", help="Radiance .hdr environment map (MCS and MCM are lit by it)")
     ap.add_argument("--out", default="frame.png")
     a = ap.parse_args()
 
@@ -45,6 +47,8 @@ def main():
     else:
         reader = vpt_amd.RAWReader(sphere_volume(128, noise=48.0), {'width': 128, 'height': 128, 'depth': 128})
     rc.setVolume(reader)
+    if a.env:
+        rc.setEnvironmentMap(vpt_amd.read_hdr(a.env))
     # orbit the camera a little so that three faces of the volume are visible
     import math
     from vpt_amd.scene import quat

@@ -174,6 +174,22 @@ VPT_API int vpt_renderer_destroy(vpt_renderer *r);                              
 VPT_API int vpt_renderer_set_volume(vpt_renderer *r, vpt_volume *vol);               /* setVolume() :94-97 (caller resets) */
 VPT_API int vpt_renderer_set_transfer_function(vpt_renderer *r, const uint8_t *rgba, int width, int height); /* :99-104 */
 VPT_API int vpt_renderer_set_environment(vpt_renderer *r, const uint8_t *rgba, int width, int height);       /* RenderingContext.js:90-101,136-141 */
+/* HDR environment maps (no reference counterpart: RenderingContext.js:95 leaves "HDRI & OpenEXR support" as a TODO).  The host texels
+ * are copied raw to the device (4, 8 or 16 bytes per texel) and decoded there into the float4 table vpt_renderer_set_environment
+ * fills, row 0 first (the image's top row, as an RGBA8 map).  The decode is exact:
+ *   RGBA8    c / 255 per channel (correctly rounded; the same table as vpt_renderer_set_environment, bit for bit)
+ *   RGBA16F  IEEE half -> float, subnormals, infinities and NaN payloads included
+ *   RGBA32F  the bits as given
+ *   RGBE8    Radiance shared exponent (r, g, b, e): each channel m * 2^(e - 136), exactly; e == 0 gives (0, 0, 0); alpha 1.  The
+ *            convention of stb_image and three.js's RGBELoader (no +0.5 on the mantissa as in Ward's original).
+ * Texel values are not validated (negative and non-finite floats are accepted, as GL accepts them).  The map is opaque for the MCS
+ * fixed-point rule when every alpha is 1 (RGBA8 255, half 0x3C00, float 1.0f; RGBE always).  width and height in 1..16384;
+ * a null pointer, an unknown format or another size: VPT_ERR_INVALID. */
+#define VPT_ENV_RGBA8   0   /* what vpt_renderer_set_environment takes: c / 255 per channel */
+#define VPT_ENV_RGBA16F 1   /* IEEE half, 8 B per texel */
+#define VPT_ENV_RGBA32F 2   /* float, 16 B per texel */
+#define VPT_ENV_RGBE8   3   /* Radiance shared-exponent bytes (r, g, b, e), 4 B per texel; alpha 1 */
+VPT_API int vpt_renderer_set_environment_texels(vpt_renderer *r, const void *texels, int width, int height, int format);
 /* The transfer-function widget's canvas as data (src/js/ui/TransferFunction/TransferFunction.js:110-121, src/glsl/TransferFunction.glsl:32-35):
  * `count` Gaussian bumps drawn in order into a cleared width x height RGBA8 target with gl.blendFunc(ONE, ONE_MINUS_SRC_ALPHA) —
  * src = color * exp(-|(position - uv) / size|^2) at the pixel centre uv, dst = src + dst * (1 - src.a), stored as UNORM8 after every
@@ -464,6 +480,8 @@ VPT_API int vpt_probe_sample(vpt_renderer *r, const float *xyz, float *rgba, siz
 /* the same through the volume's boundary atlas for positions outside the cube (what the MCM kernels execute for out-of-cube events; positions
  * inside go through the bricks): must equal vpt_probe_sample bit for bit in every volume format */
 VPT_API int vpt_probe_sample_boundary(vpt_renderer *r, const float *xyz, float *rgba, size_t n);
+/* the renderer's decoded environment table: width * height float4 texels, row 0 first, into rgba (room for n texels, n >= width * height) */
+VPT_API int vpt_probe_environment_texels(vpt_renderer *r, float *rgba, size_t n);
 /* The schedule of frame number `frame` of the gather pipeline as a pure host function (no GPU, no communicator needed): ring
  * buffer, event edges, render destination, RCCL operation.  vpt_gather_render / _play execute exactly this plan; exported so
  * that the multi-rank schedule can be checked without more than one GPU (tests/test_gather_schedule.py). */

@@ -201,6 +201,21 @@ static napi_value RendererSetImage(napi_env env, napi_callback_info info, bool t
 }
 static napi_value RendererSetTransferFunction(napi_env env, napi_callback_info info) { return RendererSetImage(env, info, true); }
 static napi_value RendererSetEnvironment(napi_env env, napi_callback_info info) { return RendererSetImage(env, info, false); }
+// (r, data, width, height, format): HDR environment maps (VPT_ENV_*); data holds width * height texels of 4, 8 or 16 bytes
+static napi_value RendererSetEnvironmentTexels(napi_env env, napi_callback_info info) {
+    napi_value a[5]; vpt_renderer *r; void *data; size_t n; int32_t w, h, format;
+    if (!get_args(env, info, 5, a) || !get_handle(env, a[0], &r) || !get_bytes(env, a[1], &data, &n) || !get_i32(env, a[2], &w) ||
+        !get_i32(env, a[3], &h) || !get_i32(env, a[4], &format)) return nullptr;
+    static const size_t texel_bytes[] = { 4, 8, 16, 4 };
+    if (format >= VPT_ENV_RGBA8 && format <= VPT_ENV_RGBE8 && w >= 1 && h >= 1 && n < (size_t)w * (size_t)h * texel_bytes[format]) {
+        char msg[96];
+        snprintf(msg, sizeof msg, "environment data shorter than width*height*%zu bytes", texel_bytes[format]);
+        napi_throw_range_error(env, nullptr, msg);
+        return nullptr;
+    }
+    VPT_CHECK(vpt_renderer_set_environment_texels(r, data, w, h, format));   // (an unknown format or size: the library's error)
+    return undefined(env);
+}
 static napi_value RendererResize(napi_env env, napi_callback_info info) {
     napi_value a[3]; vpt_renderer *r; int32_t w, h;
     if (!get_args(env, info, 3, a) || !get_handle(env, a[0], &r) || !get_i32(env, a[1], &w) || !get_i32(env, a[2], &h)) return nullptr;
@@ -445,6 +460,8 @@ static napi_value Init(napi_env env, napi_value exports) {
     EXPORT("rendererLocalRows", RendererLocalRows); EXPORT("rendererGlobalRow", RendererGlobalRow);
     EXPORT("rendererSetVolume", RendererSetVolume); EXPORT("rendererSetTransferFunction", RendererSetTransferFunction);
     EXPORT("rendererSetEnvironment", RendererSetEnvironment); EXPORT("rendererResize", RendererResize);
+    EXPORT("rendererSetEnvironmentTexels", RendererSetEnvironmentTexels);
+    CONST(VPT_ENV_RGBA8); CONST(VPT_ENV_RGBA16F); CONST(VPT_ENV_RGBA32F); CONST(VPT_ENV_RGBE8);
     EXPORT("rendererReset", RendererReset); EXPORT("rendererGenerate", RendererGenerate); EXPORT("rendererIntegrate", RendererIntegrate);
     EXPORT("rendererRenderFrame", RendererRenderFrame); EXPORT("rendererRender", RendererRender); EXPORT("rendererRead", RendererRead); EXPORT("rendererReadFrameSlot", RendererReadFrameSlot);
     EXPORT("rendererSampleCount", RendererSampleCount); EXPORT("rendererClearSampleCount", RendererClearSampleCount);

@@ -66,7 +66,7 @@ async setVolume(reader) {                                                       
     if (old) { old.destroy(); }                                                        // device memory is not garbage-collected
 }
 
-setEnvironmentMap(image) {                                                            // :135-140 — { data: RGBA8, width, height }
+setEnvironmentMap(image) {                                                            // :135-140 — { data: RGBA8 | HDR, width, height[, format] }
     this.environmentTexture = image;
     if (this.renderer) { this.renderer.setEnvironmentMap(image); }
 }

@@ -2,7 +2,8 @@
 // src/js/renderers/AbstractRenderer.js:15-157, re-hosted: the frame / accumulation / render buffers are HIP device
 // buffers owned by the native renderer; the hooks call the C-ABI through the N-API addon.
 //   new R(gl, volume, camera, environmentTexture, { resolution, transform })
-//   gl = vpt Context; environmentTexture = { data: Uint8Array RGBA8, width, height } or null (1x1 white).
+//   gl = vpt Context; environmentTexture = { data: Uint8Array RGBA8, width, height } or null (1x1 white), or an HDR map
+//   (Float32Array RGBA32F, Uint16Array RGBA16F half bits, or readHDR's { format: 'rgbe' }: see setEnvironmentMap).
 //   options.resolution: number (square, as in the reference) or { width, height }.
 //   options.rng: replaces Math.random() for the per-frame draws (fixed-seed runs).
 //   options.shard: { rank, world, rows } — this process renders only its interleaved row blocks (multi-GPU, FrameGather.js).
@@ -45,9 +46,7 @@ constructor(gl, volume, camera, environmentTexture, options) {
     this._shard = options.shard || null;
     this._boundVolume = undefined;
     this._rebuildBuffers();
-    if (environmentTexture) {
-        native().rendererSetEnvironment(this._h, environmentTexture.data, environmentTexture.width, environmentTexture.height);
-    }
+    if (environmentTexture) { this._uploadEnvironment(environmentTexture); }
 }
 
 _size() {
@@ -98,8 +97,25 @@ setTransferFunction(transferFunction) {
 // the reference re-fills the context-owned environment texture in place (RenderingContext.js:135-140); here the
 // renderer holds a device copy, so the context hands the new image down
 setEnvironmentMap(image) {
+    this._uploadEnvironment(image);
     this._environmentTexture = image;
-    native().rendererSetEnvironment(this._h, image.data, image.width, image.height);
+}
+
+// { data, width, height, format }: bytes without a format are RGBA8 (as the reference's texture); HDR maps (no reference counterpart):
+// a Float32Array is RGBA32F, a Uint16Array RGBA16F half bit patterns, format 'rgbe' the RGBE bytes of readHDR (js/vpt/hdr.js)
+_uploadEnvironment(image) {
+    const N = native(), d = image.data;
+    if (image.format === 'rgbe' && d instanceof Uint8Array) {
+        N.rendererSetEnvironmentTexels(this._h, d, image.width, image.height, N.VPT_ENV_RGBE8);
+    } else if (image.format !== undefined) {
+        throw new TypeError('unknown environment map format ' + image.format);
+    } else if (d instanceof Float32Array) {
+        N.rendererSetEnvironmentTexels(this._h, d, image.width, image.height, N.VPT_ENV_RGBA32F);
+    } else if (d instanceof Uint16Array) {
+        N.rendererSetEnvironmentTexels(this._h, d, image.width, image.height, N.VPT_ENV_RGBA16F);
+    } else {
+        N.rendererSetEnvironment(this._h, d, image.width, image.height);     // RGBA8 bytes, as before (the addon rejects what is no buffer)
+    }
 }
 
 setResolution(resolution) {                                                                  // :106-112

@@ -17,6 +17,7 @@ from .tonemappers import (AbstractToneMapper, ArtisticToneMapper, RangeToneMappe
 from .rendering_context import RenderingContext
 from .animators import CircleAnimator, OrbitCameraAnimator
 from .transfer_function import TransferFunction
+from .hdr import HDRImage, read_hdr
 from ._native import VptError
 
 __all__ = [
@@ -27,4 +28,5 @@ __all__ = [
     'AbstractToneMapper', 'ArtisticToneMapper', 'RangeToneMapper', 'ReinhardToneMapper', 'Reinhard2ToneMapper',
     'Uncharted2ToneMapper', 'FilmicToneMapper', 'UnrealToneMapper', 'AcesToneMapper', 'LottesToneMapper',
     'UchimuraToneMapper', 'ToneMapperFactory', 'RenderingContext', 'CircleAnimator', 'OrbitCameraAnimator', 'TransferFunction',
+    'HDRImage', 'read_hdr',
 ]

@@ -26,6 +26,7 @@ FORMAT_R8, FORMAT_RG8, FORMAT_R32F, FORMAT_RG32F = 0, 1, 2, 3
 FORMAT_R8_SNORM, FORMAT_RG8_SNORM = 4, 5
 FORMAT_RGB565, FORMAT_RGBA4, FORMAT_RGB5_A1, FORMAT_RGB10_A2, FORMAT_R11F_G11F_B10F, FORMAT_RGB9_E5 = 6, 7, 8, 9, 10, 11
 FORMAT_R16, FORMAT_RG16, FORMAT_R16_SNORM, FORMAT_RG16_SNORM = 12, 13, 14, 15
+ENV_RGBA8, ENV_RGBA16F, ENV_RGBA32F, ENV_RGBE8 = 0, 1, 2, 3
 BUFFER_RENDER, BUFFER_FRAME, BUFFER_ACCUM = 0, 1, 2
 BUFFER_MCM_POSITION, BUFFER_MCM_DIRECTION, BUFFER_MCM_TRANSMITTANCE, BUFFER_MCM_RADIANCE = 3, 4, 5, 6
 BUFFER_DOS_OCCLUSION = 7
@@ -46,7 +47,7 @@ SYMBOLS = [
     "vpt_volume_set_filter", "vpt_volume_destroy", "vpt_volume_bricked_bytes", "vpt_volume_set_wide_tables",
     "vpt_renderer_create", "vpt_renderer_set_shard", "vpt_renderer_local_rows", "vpt_renderer_global_row",
     "vpt_renderer_destroy", "vpt_renderer_set_volume", "vpt_renderer_set_transfer_function",
-    "vpt_renderer_set_environment", "vpt_renderer_resize",
+    "vpt_renderer_set_environment", "vpt_renderer_set_environment_texels", "vpt_renderer_resize",
     "vpt_renderer_reset", "vpt_renderer_generate", "vpt_renderer_integrate", "vpt_renderer_render_frame",
     "vpt_renderer_render", "vpt_renderer_play", "vpt_renderer_play_into", "vpt_renderer_play_into_display", "vpt_renderer_read", "vpt_renderer_render_buffer_device",
     "vpt_renderer_set_render_target", "vpt_renderer_join", "vpt_renderer_bucket_launches", "vpt_renderer_read_frame_slot", "vpt_renderer_frame_ring_device",
@@ -56,6 +57,7 @@ SYMBOLS = [
     "vpt_gather_synchronize",
     "vpt_gather_read_frame",
     "vpt_probe_math", "vpt_probe_sample", "vpt_probe_sample_boundary", "vpt_probe_stream_read", "vpt_probe_assemble_rows",
+    "vpt_probe_environment_texels",
     "vpt_tonemapper_create", "vpt_tonemapper_destroy", "vpt_tonemapper_resize", "vpt_tonemapper_set_source",
     "vpt_tonemapper_set_source_image", "vpt_tonemapper_render", "vpt_tonemapper_read", "vpt_tonemapper_rows",
     "vpt_tonemapper_output_device", "vpt_tonemapper_set_option", "vpt_transfer_function_rasterize",
@@ -150,6 +152,7 @@ def lib():
         "vpt_renderer_global_row": [P, I, C.POINTER(I)],
         "vpt_renderer_destroy": [P], "vpt_renderer_set_volume": [P, P],
         "vpt_renderer_set_transfer_function": [P, P, I, I], "vpt_renderer_set_environment": [P, P, I, I],
+        "vpt_renderer_set_environment_texels": [P, P, I, I, I],
         "vpt_renderer_resize": [P, I, I],
         "vpt_renderer_reset": [P, UP], "vpt_renderer_generate": [P, UP], "vpt_renderer_integrate": [P, UP],
         "vpt_renderer_render_frame": [P, UP], "vpt_renderer_render": [P, UP],
@@ -167,6 +170,7 @@ def lib():
         "vpt_renderer_profile": [P, C.POINTER(C.c_double), C.POINTER(C.c_uint32)],
         "vpt_renderer_profile_side": [P, C.POINTER(C.c_double), C.POINTER(C.c_uint32)],
         "vpt_probe_math": [P, I, P, P, SZ], "vpt_probe_sample": [P, P, P, SZ], "vpt_probe_sample_boundary": [P, P, P, SZ], "vpt_probe_stream_read": [P, SZ, I, P], "vpt_probe_assemble_rows": [P, P, I, I, I, I, I, P],
+        "vpt_probe_environment_texels": [P, P, SZ],
         "vpt_tonemapper_create": [P, I, I, I, P], "vpt_tonemapper_destroy": [P], "vpt_tonemapper_resize": [P, I, I],
         "vpt_tonemapper_set_source": [P, P], "vpt_tonemapper_set_source_image": [P, P, I, I],
         "vpt_tonemapper_render": [P, C.POINTER(TonemapParams)], "vpt_tonemapper_read": [P, P, SZ],

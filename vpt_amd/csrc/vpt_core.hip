@@ -436,6 +436,53 @@ extern "C" int vpt_renderer_set_environment(vpt_renderer *r, const uint8_t *rgba
     r->cls.poisoned = true;                                  // (MCS: the fixed points of the ray-missing pixels move with the environment)
     return VPT_OK;
 }
+// every alpha of the host texels is 1 in its format (RGBE8 has none: always opaque)
+static bool env_texels_opaque(const void *texels, size_t n, int format) {
+    if (format == VPT_ENV_RGBA8) {
+        const uint8_t *p = (const uint8_t *)texels;
+        for (size_t i = 0; i < n; i++) if (p[4 * i + 3] != 255) return false;
+    } else if (format == VPT_ENV_RGBA16F) {
+        const uint16_t *p = (const uint16_t *)texels;
+        for (size_t i = 0; i < n; i++) if (p[4 * i + 3] != 0x3C00u) return false;
+    } else if (format == VPT_ENV_RGBA32F) {
+        const float *p = (const float *)texels;
+        for (size_t i = 0; i < n; i++) if (p[4 * i + 3] != 1.0f) return false;
+    }
+    return true;
+}
+extern "C" int vpt_renderer_set_environment_texels(vpt_renderer *r, const void *texels, int w, int h, int format) {
+    if (!r || !texels) return fail(VPT_ERR_INVALID, "null argument");
+    if (format < VPT_ENV_RGBA8 || format > VPT_ENV_RGBE8) return fail(VPT_ERR_INVALID, "unknown environment format %d", format);
+    if (w < 1 || h < 1 || w > 16384 || h > 16384) return fail(VPT_ERR_INVALID, "environment size %dx%d out of range", w, h);
+    VPT_TRY(join_side(r));                                   // side streams may still read the old map
+    vpt_context *c = r->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    static const size_t texel_bytes[] = { 4, 8, 16, 4 };
+    const size_t n = (size_t)w * h, nbytes = n * texel_bytes[format];
+    if (!r->env || (size_t)r->env_w * r->env_h != n) {       // (a table of the same size is overwritten in stream order)
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (r->env) { HIP_TRY(hipFree(r->env)); r->env = nullptr; r->env_w = r->env_h = 0; }
+        HIP_TRY(hipMalloc(&r->env, n * sizeof(float4)));
+    }
+    r->env_w = w; r->env_h = h;
+    uint8_t *staging = nullptr;
+    HIP_TRY(hipMalloc(&staging, nbytes));
+    hipError_t e = hipMemcpyAsync(staging, texels, nbytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) {
+        int grid = (int)((n + 255) / 256); if (grid > 8192) grid = 8192;
+        hipLaunchKernelGGL(k_env_decode, dim3(grid), dim3(256), 0, c->stream, r->env, (const uint8_t *)staging, n, format);
+        e = hipGetLastError();
+    }
+    float4 first = make_float4(0.0f, 0.0f, 0.0f, 0.0f);       // env_const: the decoded texel of a 1x1 map, read back (one decoder)
+    if (e == hipSuccess) e = hipMemcpyAsync(&first, r->env, sizeof(float4), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // (the caller's buffer may be released on return)
+    hipFree(staging);
+    if (e != hipSuccess) return fail(VPT_ERR_HIP, "environment upload: %s", hipGetErrorString(e));
+    r->env_const = first;
+    r->env_opaque = env_texels_opaque(texels, n, format);
+    r->cls.poisoned = true;                                  // (as vpt_renderer_set_environment)
+    return VPT_OK;
+}
 // VPT_OPTION_SPLIT_STREAMS as the library sets it itself (round 4: the measured best form is the default, not an option a caller has to know).
 // MCM: the HIT | MISS kernels of the tile classes need two streams (1080p headline frame 80 us against 108 for the general kernel on one).
 // MIP, EAM, Depth: three ranges on three streams (EAM 256^3 60.0 -> 48.4 us, MIP 50.5 -> 41.3, Depth 55.5 -> 46.7; two: 50.2 / 41.9 / 47.8).
@@ -1197,6 +1244,17 @@ static int probe_sample(vpt_renderer *r, const float *xyz, float *rgba, size_t n
     return VPT_OK;
 }
 
+extern "C" int vpt_probe_environment_texels(vpt_renderer *r, float *rgba, size_t n) {
+    if (!r || !rgba) return fail(VPT_ERR_INVALID, "null argument");
+    const size_t texels = (size_t)r->env_w * r->env_h;
+    if (n < texels) return fail(VPT_ERR_INVALID, "environment table holds %zu texels, room for %zu", texels, n);
+    vpt_context *c = r->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    VPT_TRY(join_side(r));
+    HIP_TRY(hipMemcpyAsync(rgba, r->env, texels * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return VPT_OK;
+}
 extern "C" int vpt_probe_sample(vpt_renderer *r, const float *xyz, float *rgba, size_t n) { return probe_sample(r, xyz, rgba, n, false); }
 extern "C" int vpt_probe_sample_boundary(vpt_renderer *r, const float *xyz, float *rgba, size_t n) { return probe_sample(r, xyz, rgba, n, true); }
 

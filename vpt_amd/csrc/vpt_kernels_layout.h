@@ -67,6 +67,46 @@ __global__ void k_decode_packed(float2 *vol, int nx, int ny, const uint8_t *blk,
         vol[((size_t)(z0 + z) * ny + (y0 + y)) * nx + (x0 + x)] = decode_packed(w, format);
     }
 }
+// ---- HDR environment maps (vpt_renderer_set_environment_texels): raw host texels -> the float4 table, exactly ---------------------
+// IEEE half -> float by its fields (the hardware conversion quiets signalling NaNs; this keeps every payload): subnormal m 2^-24, exact
+VPT_DEV float half_bits_to_float(uint32_t h) {
+    const uint32_t s = (h & 0x8000u) << 16, e = (h >> 10) & 31u, m = h & 1023u;
+    if (e == 0u) return __uint_as_float(s | __float_as_uint((float)m * 0x1p-24f));
+    if (e == 31u) return __uint_as_float(s | 0x7f800000u | (m << 13));
+    return __uint_as_float(s | ((e + 112u) << 23) | (m << 13));
+}
+// Radiance RGBE: m 2^(e - 136) per channel (m < 2^8, e - 136 in -135 .. 119: every value is a float, ldexp is exact); e = 0: black
+VPT_DEV float4 decode_rgbe(uint32_t w) {
+    const int e = (int)(w >> 24);
+    if (e == 0) return make_float4(0.0f, 0.0f, 0.0f, 1.0f);
+    return make_float4(ldexpf((float)(w & 255u), e - 136), ldexpf((float)((w >> 8) & 255u), e - 136),
+                       ldexpf((float)((w >> 16) & 255u), e - 136), 1.0f);
+}
+template <int F> VPT_DEV void env_decode(float4 *dst, const uint8_t *src, size_t n) {
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (size_t)gridDim.x * blockDim.x) {
+        if (F == VPT_ENV_RGBA32F) {                                                      // the bits as given (no float operation touches them)
+            ((uint4 *)dst)[t] = ((const uint4 *)src)[t];
+        } else if (F == VPT_ENV_RGBA16F) {
+            const uint2 w = ((const uint2 *)src)[t];
+            dst[t] = make_float4(half_bits_to_float(w.x & 0xffffu), half_bits_to_float(w.x >> 16),
+                                 half_bits_to_float(w.y & 0xffffu), half_bits_to_float(w.y >> 16));
+        } else {
+            const uint32_t w = ((const uint32_t *)src)[t];
+            if (F == VPT_ENV_RGBE8) dst[t] = decode_rgbe(w);
+            else dst[t] = make_float4((float)(w & 255u) / 255.0f, (float)((w >> 8) & 255u) / 255.0f,      // RGBA8: as the host path divides
+                                      (float)((w >> 16) & 255u) / 255.0f, (float)(w >> 24) / 255.0f);
+        }
+    }
+}
+// n texels of `format` (VPT_ENV_*) at src (staged raw; 4, 8 or 16 bytes each) -> dst[0 .. n)
+__global__ void k_env_decode(float4 *dst, const uint8_t *src, size_t n, int format) {
+    switch (format) {
+        case VPT_ENV_RGBA8: env_decode<VPT_ENV_RGBA8>(dst, src, n); break;
+        case VPT_ENV_RGBA16F: env_decode<VPT_ENV_RGBA16F>(dst, src, n); break;
+        case VPT_ENV_RGBA32F: env_decode<VPT_ENV_RGBA32F>(dst, src, n); break;
+        default: env_decode<VPT_ENV_RGBE8>(dst, src, n); break;
+    }
+}
 // SNORM volumes: byte 0x80 (-128) -> 0x81 (-127) over the linear storage (n bytes), four bytes per thread and step
 __global__ void k_snorm_clamp(uint8_t *lin, size_t n) {
     const size_t n4 = n / 4;

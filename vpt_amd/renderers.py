@@ -7,7 +7,7 @@ Every hook is a thin call into the C-ABI (include/vpt.h); the WebGL framebuffers
 
 Differences that are part of the contract:
   * ``gl`` is a vpt_amd.Context; ``environmentTexture`` is an RGBA8 array [h][w][4] or None (1x1 white,
-    RenderingContext.js:90-101).
+    RenderingContext.js:90-101), or an HDR map: float32 / float16 [h][w][4] (or [h][w][3]) or vpt_amd.hdr.read_hdr's result.
   * ``options['resolution']`` is an int (square, the reference's behaviour) or (width, height).
   * the values the reference draws with Math.random() come from ``self.rng`` (option 'rng', default random.random);
     install a seeded callable for reproducible runs.
@@ -73,15 +73,42 @@ class AbstractRenderer(PropertyBag):
             N.check(L.vpt_renderer_resize(self._h, w, h))
 
     def _upload_environment(self, tex):
-        tex = np.ascontiguousarray(tex, dtype=np.uint8)
-        assert tex.ndim == 3 and tex.shape[2] == 4, 'environment texture is [h][w][4] RGBA8'
-        N.check(N.lib().vpt_renderer_set_environment(self._h, tex.ctypes.data_as(C.c_void_p), tex.shape[1], tex.shape[0]))
+        """uint8 [h][w][4]: RGBA8 (vpt_renderer_set_environment, as before); float32 / float16 [h][w][4]: RGBA32F / RGBA16F; float
+        [h][w][3]: alpha 1 added here; an HDRImage (vpt_amd.hdr.read_hdr): its RGBE bytes (vpt_renderer_set_environment_texels)"""
+        from .hdr import HDRImage
+        if isinstance(tex, HDRImage):
+            data, fmt = np.ascontiguousarray(tex.data, dtype=np.uint8), N.ENV_RGBE8
+            if data.shape != (tex.height, tex.width, 4):
+                raise ValueError('HDR image data is %r, not [%d][%d][4]' % (data.shape, tex.height, tex.width))
+        else:
+            if not isinstance(tex, np.ndarray):
+                raise TypeError('environment texture is a numpy array [h][w][4] or an HDRImage, not %s' % type(tex).__name__)
+            if tex.ndim != 3 or tex.shape[2] not in (3, 4) or (tex.shape[2] == 3 and tex.dtype == np.uint8):
+                raise ValueError('environment texture is [h][w][4] (or float [h][w][3]), not %r %s' % (tex.shape, tex.dtype))
+            if tex.dtype == np.uint8:
+                tex = np.ascontiguousarray(tex)
+                N.check(N.lib().vpt_renderer_set_environment(self._h, tex.ctypes.data_as(C.c_void_p), tex.shape[1], tex.shape[0]))
+                return
+            if tex.dtype not in (np.float32, np.float16):
+                raise TypeError('environment texels are uint8, float16 or float32, not %s' % tex.dtype)
+            if tex.shape[2] == 3:
+                tex = np.concatenate([tex, np.ones(tex.shape[:2] + (1,), tex.dtype)], axis=2)
+            data, fmt = np.ascontiguousarray(tex), (N.ENV_RGBA32F if tex.dtype == np.float32 else N.ENV_RGBA16F)
+        N.check(N.lib().vpt_renderer_set_environment_texels(self._h, data.ctypes.data_as(C.c_void_p), data.shape[1], data.shape[0], fmt))
+
+    def environment_texels(self):
+        """the decoded environment table [h][w][4] float32 as the kernels read it (vpt_probe_environment_texels)"""
+        img = self._environmentTexture
+        h, w = (img.height, img.width) if hasattr(img, 'width') else ((1, 1) if img is None else img.shape[:2])
+        out = np.empty((h, w, 4), np.float32)
+        N.check(N.lib().vpt_probe_environment_texels(self._h, out.ctypes.data_as(C.c_void_p), h * w))
+        return out
 
     def setEnvironmentMap(self, image):
         """the reference re-fills the context-owned environment texture in place (RenderingContext.js:135-140); the
         renderer holds a device copy here, so the context hands the new image down"""
-        self._environmentTexture = image
         self._upload_environment(image)
+        self._environmentTexture = image
 
     def _bind_volume(self):
         tex = self._volume.getTexture() if self._volume is not None else None

@@ -61,7 +61,7 @@ class RenderingContext(EventTarget):
         if old:
             old.destroy()                                                             # device memory is not garbage-collected
 
-    def setEnvironmentMap(self, image):                                               # :135-140 — [h][w][4] RGBA8
+    def setEnvironmentMap(self, image):                                               # :135-140 — RGBA8, float [h][w][4] or read_hdr()'s
         self.environmentTexture = image
         if self.renderer:
             self.renderer.setEnvironmentMap(image)
