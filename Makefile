@@ -10,8 +10,11 @@ test:             ## CPU suite (no GPU needed)
 test-gpu:         ## parity suite on an MI355X
 	$(PY) -m pytest tests -q -m gpu
 
-bench:            ## one JSON line: samples/s, roofline, CPU baselines
+bench:            ## one JSON line: the headline samples/s and ms per step
 	$(PY) bench.py
+
+bench-full:       ## the same line with everything beside it: oracle frame check, per-kernel roofline, CPU baselines, other configurations
+	$(PY) bench.py --full
 
 fixtures:         ## regenerate the golden fixtures (build container only: needs /root/reference and node)
 	node tests/golden/make_mvp_fixture.js
@@ -27,4 +30,4 @@ clean:
 	$(MAKE) -C oracle clean
 	rm -f js/addon/vpt_native.node
 
-.PHONY: build test test-gpu bench fixtures clean
+.PHONY: build test test-gpu bench bench-full fixtures clean

@@ -5,10 +5,13 @@ renderer = one integrate pass of `steps`=8 delta-tracking events per pixel + _re
 inputs resident in HBM.  For N > 1 the image plane is sharded into interleaved row blocks (total work fixed =
 strong scaling) and every frame is gathered over RCCL (all_gather, overlapped with the next frame's kernel).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0 (contract in the task description) with `roofline` and `cpu_baseline` objects.
+Prints ONE JSON line on rank 0 with a `roofline` object.  A plain run does only what that line's headline needs: set up, warm up, time
+the K steps, write --dump-outputs, print.  --full also runs everything measured or checked beside it (FULL_ONLY below: the oracle frame
+check, the HBM stream probe, each kernel alone, the CPU baselines, the other configurations; N > 1: the forms beside the line and the
+single-GPU reference); each of those options given explicitly wins over either default.
 """
 import argparse
 import json
@@ -33,10 +36,15 @@ FAST_MATH_BOUNDS = {"max_abs_d_missing": 1e-6, "min_equal_counts_crossing": 0.97
 # VPT_OPTION_SPLIT_STREAMS as the library sets it by itself (vpt_core.hip default_split): what a run without --split-streams uses
 DEFAULT_SPLIT = {"mcm": 2, "mip": 3, "eam": 3, "iso": 2, "depth": 3, "mcs": 2, "lao": 2}
 DUMP_CAP_BYTES = 60 << 20  # --dump-outputs: at most this many bytes of arrays in all (below 64 MB with the .npy headers)
+# options whose work the headline does not need: off in a plain run, these values with --full (an explicit value wins either way)
+FULL_ONLY = {"check": 1, "stream_probe": 1, "kernels_alone": 1, "other_configs": 1, "cpu_baseline": 1,
+             "bucket_form": 1, "display_form": 1, "cadence_form": 16}
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need (every option of FULL_ONLY on; default: a plain run, all of them off)")
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
@@ -49,16 +57,19 @@ def parse():
                     help="the K-step timed block (barrier + synchronize on both sides) is run this many times; the MEDIAN block is reported "
                          "(default 1: exactly --steps steps are timed); an untimed block of --steps steps, run the same way, goes first")
     ap.add_argument("--warmup-seconds", type=float, default=0.3, help="warm up for at least this long (and at least --warmup steps)")
-    ap.add_argument("--other-configs", type=int, default=1,
+    ap.add_argument("--other-configs", type=int, default=None,
                     help="N = 1: after the timed region also measure BASELINE.json's other single-GPU configurations (C2 EAM 256^3, C3 MCS 512^3, "
-                         "C4 MCM 1024^3, all 1920x1080) and report them in `other_configs`")
-    ap.add_argument("--cpu-baseline", type=int, default=1)
+                         "C4 MCM 1024^3, all 1920x1080) and report them in `other_configs` (default: 1 with --full, else 0)")
+    ap.add_argument("--cpu-baseline", type=int, default=None, help="N = 1: time the C and JS CPU oracles on the same workload (default: 1 with --full, else 0)")
     ap.add_argument("--cpu-threads", type=int, default=0)
-    ap.add_argument("--check", type=int, default=1, help="verify the gathered frame against rank-local rows")
+    ap.add_argument("--check", type=int, default=None,
+                    help="N = 1: replay the passes with the CPU oracle on a band of rows; N > 1: verify the gathered frame against rank-local rows "
+                         "and the same frames rendered unsharded (default: 1 with --full, else 0; `frame_check` null when off)")
     ap.add_argument("--profile-kernel", type=int, default=-1,
                     help="HIP events around every n-th launch of the dominant kernel in the timed region (1 = every launch, 0 = none; default -1 = every "
                          "max(8, steps / 2)-th: an event pair costs its stream a few microseconds, 0.3-1 %% of a 20-step block when every 8th launch carries one)")
-    ap.add_argument("--stream-probe", type=int, default=1, help="also measure the HBM streaming-read rate (second roofline denominator)")
+    ap.add_argument("--stream-probe", type=int, default=None,
+                    help="also measure the HBM streaming-read rate (second roofline denominator; default: 1 with --full, else 0)")
     ap.add_argument("--fused", type=int, default=1, help="0: run the three hooks as separate launches (profiling aid)")
     ap.add_argument("--frames-per-launch", type=int, default=0,
                     help="frames enqueued per host call (vpt_*_play); 0 = 1 (frame by frame)")
@@ -94,25 +105,26 @@ def parse():
     ap.add_argument("--split-streams", type=int, default=0,
                     help="K >= 1 = VPT_OPTION_SPLIT_STREAMS (a pass as K parts on K HIP streams; results identical); 0 (default) = set nothing: the "
                          "library's own default (MCM: 2 = the HIT | MISS kernels of the tile classes)")
-    ap.add_argument("--kernels-alone", type=int, default=1,
+    ap.add_argument("--kernels-alone", type=int, default=None,
                     help="N = 1, MCM with tile classes: after the timed region run the two class kernels one after the other on one stream "
-                         "(VPT_OPTION_TILE_CLASSES 2) and report each kernel's duration alone on the chip in roofline.per_kernel")
+                         "(VPT_OPTION_TILE_CLASSES 2) and report each kernel's duration alone on the chip in roofline.per_kernel "
+                         "(default: 1 with --full, else 0)")
     ap.add_argument("--bucket-kernel", type=int, default=0,
                     help="torch.distributed pipeline, MCM with tile classes: 1 = the line's pipeline runs every bucket of --frames-per-gather frames by ONE launch "
                          "per tile class (VPT_OPTION_BUCKET_KERNEL: photon state in registers across the bucket, launch gap and staging once per bucket); "
                          "0 = one launch per frame and class, as at N = 1 (the default: like for like with the single-GPU line)")
-    ap.add_argument("--display-form", type=int, default=1,
+    ap.add_argument("--display-form", type=int, default=None,
                     help="N > 1: 1 = measure the torch.distributed pipeline once more gathering the frames AS THE TONE MAPPER SHOWS THEM (RGBA8 through the default "
                          "Artistic tone mapper, vpt_renderer_play_into_display: bucket kernels with the table in their frame store, half the bytes per xGMI link) and "
-                         "report it beside the line (config.display_gather_form); never the line's `value`")
-    ap.add_argument("--bucket-form", type=int, default=1,
+                         "report it beside the line (config.display_gather_form); never the line's `value` (default: 1 with --full, else 0)")
+    ap.add_argument("--bucket-form", type=int, default=None,
                     help="N > 1: 1 = after the line's measurement, measure the torch.distributed pipeline once more with VPT_OPTION_BUCKET_KERNEL and report "
-                         "it beside the line (config.bucket_kernel_form); never the line's `value` unless --bucket-kernel 1")
-    ap.add_argument("--cadence-form", type=int, default=16,
+                         "it beside the line (config.bucket_kernel_form); never the line's `value` unless --bucket-kernel 1 (default: 1 with --full, else 0)")
+    ap.add_argument("--cadence-form", type=int, default=None,
                     help="N > 1, MCM: D > 0 = measure once more with the frame gathered at a DISPLAY CADENCE: D passes accumulate on every rank by one launch "
                          "per tile class (VPT_PLAY_FUSED) and only the D-th frame is gathered (RGBA16F all_gather) - what a progressive renderer that shows "
                          "every D-th pass needs from xGMI: 1 / D of the line's bytes per pass.  Reported beside the line (config.display_cadence_form) with the "
-                         "single-GPU figure of the same form; never the line's `value`; 0 = skip")
+                         "single-GPU figure of the same form; never the line's `value`; 0 = skip (default: 16 with --full, else 0)")
     ap.add_argument("--frames-per-gather", type=int, default=16,
                     help="torch.distributed pipeline: frames per all_gather (every frame is delivered, at most F - 1 frames later; one async "
                          "collective costs the host ~25 us whatever its size and a bucket's launches ~10 us per frame, against the ~17 us a "
@@ -128,7 +140,11 @@ def parse():
                          "its pixels, DIR/frame.npy + DIR/frame_pixels.npy).  The timed steps then start from a restarted accumulation "
                          "(reset, per-frame draws from the first), so that the same arguments give the same outputs whatever the "
                          "time-based warm-up ran" % (DUMP_CAP_BYTES >> 20))
-    return ap.parse_args()
+    args = ap.parse_args(argv)
+    for name, value in FULL_ONLY.items():
+        if getattr(args, name) is None:
+            setattr(args, name, value if args.full else 0)
+    return args
 
 
 def dump_outputs(outputs, directory, seed=0):
@@ -1235,7 +1251,7 @@ def main():
             except Exception as e:                                  # reporting only
                 state["alone"] = None
                 print("kernels-alone measurement failed: %r" % (e,), file=sys.stderr)
-        if use_dist and args.renderer == "mcm" and (world > 1 or args.force_dist > 1):
+        if args.full and use_dist and args.renderer == "mcm" and (world > 1 or args.force_dist > 1):
             measure_single_gpu_reference()
         res = min(results, key=lambda x: x["dt_max"])
         if len(results) > 1:

@@ -52,7 +52,7 @@ def test_torch_pipeline_on_one_rank_frame_by_frame_and_with_bucket_kernels():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--force-dist", "1", "--gather", "torch", "--volume", "64", "--width", "640",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--force-dist", "1", "--gather", "torch", "--volume", "64", "--width", "640",
                         "--height", "368", "--steps", "40", "--warmup", "8", "--repeats", "2", "--other-configs", "0", "--cpu-baseline", "0",
                         "--stream-probe", "0"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert p.returncode == 0, p.stderr.decode(errors="replace")[-3000:]
@@ -82,7 +82,7 @@ def test_bench_rehearsal_with_several_ranks_on_one_gpu(world):
     for rank in range(world):
         env = dict(os.environ, RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
                    HSA_ENABLE_IPC_MODE_LEGACY="0")
-        procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--rehearsal", "1", "--volume", "64",
+        procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", str(world), "--rehearsal", "1", "--volume", "64",
                                        "--width", "640", "--height", "368", "--steps", "40", "--warmup", "8", "--repeats", "2", "--stream-probe", "0",
                                        "--warmup-seconds", "0.05", "--watchdog", "500"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE))
     outs = []
