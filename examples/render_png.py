@@ -4,6 +4,8 @@
     python examples/render_png.py --renderer mcm --tonemapper artistic --frames 64 --out out.png
     python examples/render_png.py --volume data.bvp ...        (BVP container)   --volume data.raw --dims 256 256 256
     python examples/render_png.py --renderer eam --filter quasicubic ...    (volume filter: linear, nearest or quasicubic)
+    python examples/render_png.py --renderer eam --tf colour --gradient sobel --gradient-gain 4 ...   (2-D transfer function: the
+                                     gradient magnitude is derived on the device as the volume's second channel)
     python examples/render_png.py --renderer mcm --env sky.hdr --tonemapper aces ...   (a Radiance .hdr environment map lights MCS / MCM)
 
 Without --volume a synthetic 128^3 sphere with lattice noise is used.  PNG encoding is plain zlib (no imaging library)."""
@@ -31,13 +33,16 @@ def main():
     ap.add_argument("--extinction", type=float, default=None)
     ap.add_argument("--tf", default="default", choices=["default", "colour"])
     ap.add_argument("--filter", default="linear", choices=["linear", "nearest", "quasicubic"])
+    ap.add_argument("--gradient", default=None, choices=["central", "sobel"], help="derive the gradient magnitude as second channel (R8 / R16 volumes)")
+    ap.add_argument("--gradient-gain", type=float, default=1.0)
     ap.add_argument("--yaw", type=float, default=0.6)
     ap.add_argument("--pitch", type=float, default=-0.35)
     ap.add_argument("--env", default="", help="Radiance .hdr environment map (MCS and MCM are lit by it)")
     ap.add_argument("--out", default="frame.png")
     a = ap.parse_args()
 
-    rc = vpt_amd.RenderingContext({'resolution': (a.width, a.height), 'filter': a.filter, 'rng': GoldenRatioRng()})
+    rc = vpt_amd.RenderingContext({'resolution': (a.width, a.height), 'filter': a.filter, 'rng': GoldenRatioRng(),
+                                   'gradient': a.gradient, 'gradientGain': a.gradient_gain})
     rc.resize(a.width, a.height)
     if a.volume.endswith(".bvp"):
         reader = vpt_amd.BVPReader(vpt_amd.FileLoader(a.volume))
@@ -59,7 +64,7 @@ def main():
     rc.chooseRenderer(a.renderer)
     rc.chooseToneMapper(a.tonemapper)
     if a.tf == "colour":
-        rc.renderer.setTransferFunction(colour_tf(256, 1))
+        rc.renderer.setTransferFunction(colour_tf(256, 64 if a.gradient else 1))
     if a.extinction is not None and hasattr(rc.renderer, 'extinction'):
         rc.renderer.extinction = a.extinction
     rc.renderer.reset()

@@ -159,6 +159,29 @@ VPT_API int vpt_volume_destroy(vpt_volume *vol);
 VPT_API int vpt_volume_set_wide_tables(vpt_volume *vol, int wide);
 /* bytes of the bricked layout in HBM (for reporting) */
 VPT_API int vpt_volume_bricked_bytes(vpt_volume *vol, uint64_t *nbytes);
+/* ---- volume operations on the device (extension; DESIGN.md "Gradient-magnitude channel") */
+/* The second channel of a 2-D transfer function, derived where the texels already are: a one-channel UNSIGNED NORMALISED volume
+ * (VPT_FORMAT_R8, B = 8, or VPT_FORMAT_R16, B = 16) in, a new two-channel volume (RG8 / RG16) of the same size out; channel 0 is the source
+ * texel, channel 1 the gradient magnitude G.  All in integers, v = the texel, indices clamped per axis (CLAMP_TO_EDGE):
+ *   VPT_GRADIENT_CENTRAL: dx = v(x+1,y,z) - v(x-1,y,z), likewise dy, dz (doubled central differences); shift = 16
+ *   VPT_GRADIENT_SOBEL:   dx = sum over a, b in {-1,0,1} of w(a) w(b) (v(x+1,y+a,z+b) - v(x-1,y+a,z+b)), w = (1, 2, 1), likewise dy, dz; shift = 24
+ *   S = dx^2 + dy^2 + dz^2;  q = floor(gain^2 * 16384 + 0.5) (double, from the float gain);  T = (S * q) >> shift (64-bit unsigned);
+ *   G = min(2^B - 1, floor(sqrt(T))), the exact integer square root.
+ * With gain = 1 that is floor(|grad v|) in texel units per voxel for both operators.  Gains with q outside [1, 4194304] (gain outside
+ * [1/128, 16]) and NaN: VPT_ERR_INVALID.  Float, SNORM, packed and two-channel sources: VPT_ERR_UNSUPPORTED. */
+#define VPT_GRADIENT_CENTRAL 0
+#define VPT_GRADIENT_SOBEL   1
+/* a new, finalized RG8 / RG16 volume on src's context with src's filter, enqueued on the context's stream behind any upload into src;
+ * src is not changed and may be destroyed afterwards.  The result is an ordinary volume (upload_block, set_filter, every renderer) */
+VPT_API int vpt_volume_derive_gradient(vpt_volume *src, int op, float gain, vpt_volume **out);
+/* texSubImage3D's inverse: the texels of a box, in the layout vpt_volume_upload_block takes them for this volume's format (packed
+ * formats: the decoded RG32F texels the storage holds; SNORM: the most negative code reads as the one above it once the volume is
+ * finalized); blocks until the copy has landed */
+VPT_API int vpt_volume_read_block(vpt_volume *vol, int x, int y, int z, int width, int height, int depth, void *host_dst, size_t nbytes);
+/* counts per bin, uint32: one-channel R8 / R16 volumes 256 bins of the value's top 8 bits (nbins = 256); RG8 / RG16 256 x 256 bins of
+ * both channels' top 8 bits, bins[g * 256 + v] (nbins = 65536): what a 2-D transfer-function editor draws behind its bumps.  Other
+ * formats: VPT_ERR_UNSUPPORTED.  Blocks. */
+VPT_API int vpt_volume_histogram(vpt_volume *vol, uint32_t *bins, size_t nbins);
 
 /* ---- renderer: AbstractRenderer.js:17-116 and the four subclasses */
 /* new R(gl, volume, camera, environmentTexture, {resolution}) — AbstractRenderer.js:17-49; width != height is the

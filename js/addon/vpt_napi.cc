@@ -149,6 +149,31 @@ static napi_value VolumeBrickedBytes(napi_env env, napi_callback_info info) {
     VPT_CHECK(vpt_volume_bricked_bytes(v, &n));
     return number(env, (double)n);
 }
+// volumeDeriveGradient(volume, op, gain) -> a new volume handle
+static napi_value VolumeDeriveGradient(napi_env env, napi_callback_info info) {
+    napi_value a[3]; vpt_volume *v; int32_t op; double gain;
+    if (!get_args(env, info, 3, a) || !get_handle(env, a[0], &v) || !get_i32(env, a[1], &op)) return nullptr;
+    if (napi_get_value_double(env, a[2], &gain) != napi_ok) { napi_throw_type_error(env, nullptr, "expected a number"); return nullptr; }
+    vpt_volume *out = nullptr;
+    VPT_CHECK(vpt_volume_derive_gradient(v, op, (float)gain, &out));
+    return make_external(env, out);
+}
+// volumeReadBlock(volume, x, y, z, width, height, depth, dst): the box's texels into dst (a TypedArray of the volume's texel type)
+static napi_value VolumeReadBlock(napi_env env, napi_callback_info info) {
+    napi_value a[8]; vpt_volume *v; int32_t p[6]; void *data; size_t n;
+    if (!get_args(env, info, 8, a) || !get_handle(env, a[0], &v)) return nullptr;
+    for (int i = 0; i < 6; i++) if (!get_i32(env, a[1 + i], &p[i])) return nullptr;
+    if (!get_bytes(env, a[7], &data, &n)) return nullptr;
+    VPT_CHECK(vpt_volume_read_block(v, p[0], p[1], p[2], p[3], p[4], p[5], data, n));
+    return undefined(env);
+}
+// volumeHistogram(volume, bins): bins is a Uint32Array of 256 (one channel) or 65536 (two channels) counts
+static napi_value VolumeHistogram(napi_env env, napi_callback_info info) {
+    napi_value a[2]; vpt_volume *v; void *data; size_t n;
+    if (!get_args(env, info, 2, a) || !get_handle(env, a[0], &v) || !get_bytes(env, a[1], &data, &n)) return nullptr;
+    VPT_CHECK(vpt_volume_histogram(v, (uint32_t *)data, n / sizeof(uint32_t)));
+    return undefined(env);
+}
 
 // ---- renderer -----------------------------------------------------------------------------------------
 static napi_value RendererCreate(napi_env env, napi_callback_info info) {
@@ -456,6 +481,8 @@ static napi_value Init(napi_env env, napi_value exports) {
     EXPORT("contextSynchronize", ContextSynchronize); EXPORT("version", Version);
     EXPORT("volumeCreate", VolumeCreate); EXPORT("volumeUploadBlock", VolumeUploadBlock); EXPORT("volumeFinalize", VolumeFinalize);
     EXPORT("volumeSetFilter", VolumeSetFilter); EXPORT("volumeDestroy", VolumeDestroy); EXPORT("volumeBrickedBytes", VolumeBrickedBytes);
+    EXPORT("volumeDeriveGradient", VolumeDeriveGradient); EXPORT("volumeReadBlock", VolumeReadBlock); EXPORT("volumeHistogram", VolumeHistogram);
+    CONST(VPT_GRADIENT_CENTRAL); CONST(VPT_GRADIENT_SOBEL);
     EXPORT("rendererCreate", RendererCreate); EXPORT("rendererDestroy", RendererDestroy); EXPORT("rendererSetShard", RendererSetShard);
     EXPORT("rendererLocalRows", RendererLocalRows); EXPORT("rendererGlobalRow", RendererGlobalRow);
     EXPORT("rendererSetVolume", RendererSetVolume); EXPORT("rendererSetTransferFunction", RendererSetTransferFunction);

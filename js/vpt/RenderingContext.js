@@ -3,12 +3,14 @@
 // reproduce").  Same members and methods minus the browser parts (canvas, WebGL context loss, animators, recording):
 // where the reference blits the tone mapper's texture to the canvas (:199-209), getFrame() reads it back.
 //   new RenderingContext({ resolution, filter, device, rng })     resolution: number or { width, height }; filter: 'linear' (default),
-//   'nearest' or 'quasicubic'
+//   'nearest' or 'quasicubic'; gradient: null (default), 'central' or 'sobel', gradientGain (default 1): a one-channel R8 / R16 volume gets its
+//   gradient magnitude as second channel when it is loaded (Volume.deriveGradient)
 const { EventTarget, CustomEvent } = require('./EventTarget.js');
 const { Context } = require('./Context.js');
 const { OrbitCameraAnimator } = require('./animators.js');
 const { Node, Transform, PerspectiveCamera } = require('./scene.js');
-const { Volume } = require('./Volume.js');
+const { Volume, gradientArguments } = require('./Volume.js');
+const { native } = require('./native.js');
 const { RendererFactory } = require('./renderers/RendererFactory.js');
 const { ToneMapperFactory } = require('./tonemappers/ToneMapperFactory.js');
 
@@ -18,6 +20,9 @@ constructor(options) {
     super();
     options = options || {};
     this.render = this.render.bind(this);
+    this.gradient = options.gradient !== undefined ? options.gradient : null;
+    this.gradientGain = options.gradientGain !== undefined && options.gradientGain !== null ? options.gradientGain : 1;
+    if (this.gradient !== null) { gradientArguments(native(), this.gradient, this.gradientGain); }   // a bad option fails here, not at the first volume
     this.gl = new Context(options.device || 0);                                   // initGL(), :61-105
     this.environmentTexture = { data: new Uint8Array([255, 255, 255, 255]), width: 1, height: 1 };   // :90-101
     this._rng = options.rng;
@@ -62,6 +67,14 @@ async setVolume(reader) {                                                       
     });
     await this.volume.load();
     this.volume.setFilter(this.filter);
+    if (this.gradient !== null) {
+        const N = native(), fmt = this.volume.nativeFormat();
+        if (fmt === N.VPT_FORMAT_R8 || fmt === N.VPT_FORMAT_R16) {                     // (value, gradient magnitude): the 2-D transfer function's axes
+            const source = this.volume;
+            this.volume = source.deriveGradient({ operator: this.gradient, gain: this.gradientGain });
+            source.destroy();
+        }
+    }
     if (this.renderer) { this.renderer.setVolume(this.volume); }
     if (old) { old.destroy(); }                                                        // device memory is not garbage-collected
 }

@@ -103,6 +103,29 @@ function filterCode(N, filter) {
     return N.VPT_FILTER_NEAREST;
 }
 
+// the volume format behind a loaded modality, looked up like deviceFormat but with the 16-bit formats always known (a derived RG16 volume
+// needs no extension), and the TypedArray of its texels: { fmt, channels (in the storage: 1 or 2), array }
+function texelLayout(N, modality) {
+    const m = modality;
+    const sized = SIZED.find(e => e[0] === m.type && e[1] === m.format && e[2] === m.internalFormat) ||
+                  NORM16.find(e => e[0] === m.type && e[1] === m.format && e[2] === m.internalFormat);
+    const df = sized ? { fmt: N[sized[3]], channels: sized[4], kind: sized[5] } : deviceFormat(N, m, null);
+    if (df.kind === 'packed') { return { fmt: df.fmt, channels: 2, array: Float32Array }; }      // the decoded RG32F texels
+    const channels = Math.min(df.channels, 2);
+    if (df.kind === 'f32' || df.kind === 'f16') { return { fmt: df.fmt, channels, array: Float32Array }; }
+    if (df.kind === 'i16') { return { fmt: df.fmt, channels, array: m.type === R.GL_SHORT ? Int16Array : Uint16Array }; }
+    return { fmt: df.fmt, channels, array: df.kind === 'i8' ? Int8Array : Uint8Array };
+}
+
+// VPT_GRADIENT_* of an operator name; q = floor(gain^2 16384 + 0.5) of the float32 gain must lie in [1, 4194304] (include/vpt.h)
+function gradientArguments(N, operator, gain) {
+    const op = operator === 'central' ? N.VPT_GRADIENT_CENTRAL : (operator === 'sobel' ? N.VPT_GRADIENT_SOBEL : null);
+    if (op === null) { throw new Error(`unknown gradient operator '${operator}' ('central' or 'sobel')`); }
+    const g = Math.fround(Number(gain)), q = Math.floor(g * g * 16384 + 0.5);
+    if (!(q >= 1 && q <= 4194304)) { throw new Error(`gradient gain ${gain} outside [1/128, 16]`); }
+    return { op, gain: g };
+}
+
 class Volume extends EventTarget {
 
 constructor(gl, reader, options) {
@@ -156,5 +179,43 @@ setFilter(filter) {
     N.volumeSetFilter(this.texture, filterCode(N, filter));
 }
 
+// ---- extension: volume operations on the device (include/vpt.h; DESIGN.md "Gradient-magnitude channel") ----
+nativeFormat() { return texelLayout(native(), this.modality).fmt; }
+
+// texSubImage3D's inverse: the texels of a box, [depth][height][width]([2]) in a TypedArray of the volume's texel type
+readBlock(x, y, z, width, height, depth) {
+    const layout = texelLayout(native(), this.modality);
+    const out = new layout.array(width * height * depth * layout.channels);
+    native().volumeReadBlock(this.texture, x, y, z, width, height, depth, out);
+    return out;
 }
-module.exports = { Volume, RAWReader, filterCode };
+
+// Uint32Array counts: 256 bins of the value's top 8 bits (R8 / R16) or 256 x 256, bins[g * 256 + v] (RG8 / RG16)
+histogram() {
+    const layout = texelLayout(native(), this.modality);
+    const bins = new Uint32Array(layout.channels === 2 ? 65536 : 256);
+    native().volumeHistogram(this.texture, bins);
+    return bins;
+}
+
+// a new, ready RG8 / RG16 volume with this volume's filter: channel 0 this (R8 / R16) volume's texels, channel 1 their gradient magnitude
+// ({ operator: 'central' | 'sobel', gain }), derived on the device; this volume is not changed
+deriveGradient(options) {
+    options = options || {};
+    const N = native();
+    const a = gradientArguments(N, options.operator !== undefined ? options.operator : 'central', options.gain !== undefined ? options.gain : 1);
+    const norm16 = this.nativeFormat() === N.VPT_FORMAT_R16;
+    const out = new Volume(this._gl);
+    out.texture = N.volumeDeriveGradient(this.texture, a.op, a.gain);
+    const dimensions = Object.assign({}, this.modality.dimensions);
+    out.modality = { name: this.modality.name || 'default', dimensions, transform: this.modality.transform, format: GL_RG,
+        internalFormat: norm16 ? R.GL_RG16_EXT : R.GL_RG8, type: norm16 ? R.GL_UNSIGNED_SHORT : GL_UNSIGNED_BYTE,
+        placements: [{ index: 0, position: { x: 0, y: 0, z: 0 } }] };
+    out.metadata = { meta: Object.assign({}, (this.metadata || {}).meta), modalities: [out.modality],
+        blocks: [{ url: null, format: 'raw', dimensions: Object.assign({}, dimensions) }] };
+    out.ready = true;
+    return out;
+}
+
+}
+module.exports = { Volume, RAWReader, filterCode, gradientArguments };

@@ -18,6 +18,7 @@ from .rendering_context import RenderingContext
 from .animators import CircleAnimator, OrbitCameraAnimator
 from .transfer_function import TransferFunction
 from .hdr import HDRImage, read_hdr
+from .gradient import gradient_magnitude
 from ._native import VptError
 
 __all__ = [
@@ -28,5 +29,5 @@ __all__ = [
     'AbstractToneMapper', 'ArtisticToneMapper', 'RangeToneMapper', 'ReinhardToneMapper', 'Reinhard2ToneMapper',
     'Uncharted2ToneMapper', 'FilmicToneMapper', 'UnrealToneMapper', 'AcesToneMapper', 'LottesToneMapper',
     'UchimuraToneMapper', 'ToneMapperFactory', 'RenderingContext', 'CircleAnimator', 'OrbitCameraAnimator', 'TransferFunction',
-    'HDRImage', 'read_hdr',
+    'HDRImage', 'read_hdr', 'gradient_magnitude',
 ]

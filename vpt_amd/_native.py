@@ -26,6 +26,7 @@ FORMAT_R8, FORMAT_RG8, FORMAT_R32F, FORMAT_RG32F = 0, 1, 2, 3
 FORMAT_R8_SNORM, FORMAT_RG8_SNORM = 4, 5
 FORMAT_RGB565, FORMAT_RGBA4, FORMAT_RGB5_A1, FORMAT_RGB10_A2, FORMAT_R11F_G11F_B10F, FORMAT_RGB9_E5 = 6, 7, 8, 9, 10, 11
 FORMAT_R16, FORMAT_RG16, FORMAT_R16_SNORM, FORMAT_RG16_SNORM = 12, 13, 14, 15
+GRADIENT_CENTRAL, GRADIENT_SOBEL = 0, 1
 ENV_RGBA8, ENV_RGBA16F, ENV_RGBA32F, ENV_RGBE8 = 0, 1, 2, 3
 BUFFER_RENDER, BUFFER_FRAME, BUFFER_ACCUM = 0, 1, 2
 BUFFER_MCM_POSITION, BUFFER_MCM_DIRECTION, BUFFER_MCM_TRANSMITTANCE, BUFFER_MCM_RADIANCE = 3, 4, 5, 6
@@ -45,6 +46,7 @@ SYMBOLS = [
     "vpt_last_error", "vpt_version",
     "vpt_volume_create", "vpt_volume_upload_block", "vpt_volume_upload_block_device", "vpt_volume_finalize",
     "vpt_volume_set_filter", "vpt_volume_destroy", "vpt_volume_bricked_bytes", "vpt_volume_set_wide_tables",
+    "vpt_volume_derive_gradient", "vpt_volume_read_block", "vpt_volume_histogram",
     "vpt_renderer_create", "vpt_renderer_set_shard", "vpt_renderer_local_rows", "vpt_renderer_global_row",
     "vpt_renderer_destroy", "vpt_renderer_set_volume", "vpt_renderer_set_transfer_function",
     "vpt_renderer_set_environment", "vpt_renderer_set_environment_texels", "vpt_renderer_resize",
@@ -147,6 +149,8 @@ def lib():
         "vpt_volume_upload_block_device": [P, I, I, I, I, I, I, P, SZ],
         "vpt_volume_finalize": [P], "vpt_volume_set_filter": [P, I], "vpt_volume_destroy": [P],
         "vpt_volume_bricked_bytes": [P, C.POINTER(C.c_uint64)], "vpt_volume_set_wide_tables": [P, I],
+        "vpt_volume_derive_gradient": [P, I, C.c_float, PP], "vpt_volume_read_block": [P, I, I, I, I, I, I, P, SZ],
+        "vpt_volume_histogram": [P, C.POINTER(C.c_uint32), SZ],
         "vpt_renderer_create": [P, I, I, I, PP],
         "vpt_renderer_set_shard": [P, I, I, I], "vpt_renderer_local_rows": [P, C.POINTER(I)],
         "vpt_renderer_global_row": [P, I, C.POINTER(I)],

@@ -76,6 +76,9 @@ extern "C" int vpt_context_synchronize(vpt_context *c) {
 // volume — Volume.js:31-78
 // ---------------------------------------------------------------------------------------------
 extern "C" int vpt_volume_create(vpt_context *c, int w, int h, int d, int format, vpt_volume **out) {
+    return volume_create(c, w, h, d, format, true, out);
+}
+int volume_create(vpt_context *c, int w, int h, int d, int format, bool zero_fill, vpt_volume **out) {
     if (!c || !out) return fail(VPT_ERR_INVALID, "null argument");
     if (format < VPT_FORMAT_R8 || format > VPT_FORMAT_RG16_SNORM) return fail(VPT_ERR_UNSUPPORTED, "Unknown volume datatype: %d", format);  // Volume.js:103
     if (w < 1 || h < 1 || d < 1 || w > 4096 || h > 4096 || d > 4096)
@@ -83,7 +86,7 @@ extern "C" int vpt_volume_create(vpt_context *c, int w, int h, int d, int format
     HIP_TRY(hipSetDevice(c->device));
     vpt_volume *v = new vpt_volume();
     memset(v, 0, sizeof(*v));
-    v->ctx = c; v->nx = w; v->ny = h; v->nz = d;
+    v->ctx = c; v->nx = w; v->ny = h; v->nz = d; v->format = format;
     // packed formats (VPT_FORMAT_RGB565 ..): the words are decoded on upload (k_decode_packed) into an RG32F volume
     v->packed = (format >= VPT_FORMAT_RGB565 && format <= VPT_FORMAT_RGB9_E5) ? format : 0;
     v->packed_bytes = (format == VPT_FORMAT_RGB565 || format == VPT_FORMAT_RGBA4 || format == VPT_FORMAT_RGB5_A1) ? 2 : 4;
@@ -133,7 +136,7 @@ extern "C" int vpt_volume_create(vpt_context *c, int w, int h, int d, int format
         delete v;
         return fail(VPT_ERR_HIP, "hipMalloc volume %dx%dx%d: %s", w, h, d, hipGetErrorString(e));
     }
-    HIP_TRY(hipMemsetAsync(v->linear, 0, (size_t)w * h * d * v->vox_bytes, c->stream));   // texStorage3D zero-initialises
+    if (zero_fill) HIP_TRY(hipMemsetAsync(v->linear, 0, (size_t)w * h * d * v->vox_bytes, c->stream));   // texStorage3D zero-initialises
     {   // offset tables: off(x,y,z) = TX[x] + TY[y] + TZ[z]
         std::vector<uint64_t> t64((size_t)w + h + d);
         std::vector<uint32_t> t32(t64.size());

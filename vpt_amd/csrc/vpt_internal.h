@@ -8,6 +8,7 @@
 //   vpt_extra.hip   ISO, Depth, LAO, DOS passes (vpt_kernels_iso_depth.h)
 //   vpt_render.hip  the renderer entry points: the four hooks, render(), frame sequences (vpt_renderer_play*)
 //   vpt_post.hip    what follows a frame: tone mappers, the RCCL frame gather
+//   vpt_volume_ops.hip  volume operations on the device: the gradient-magnitude channel, texel read-back, histograms
 // Nothing device-side crosses a translation unit: a kernel is compiled by the unit that names it (the three MCM units share one header).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -49,6 +50,7 @@ struct vpt_context {
 struct vpt_volume {
     vpt_context *ctx;
     int nx, ny, nz;
+    int format;            // the VPT_FORMAT_* the volume was created with
     int channels;          // 1 = R8 / R32F, 2 = RG8 (interleaved)
     bool f32;              // FLOAT texels (VPT_FORMAT_R32F): 4 bytes per voxel, 512-byte brick slots
     bool snorm;            // signed normalised texels (VPT_FORMAT_R8_SNORM / RG8_SNORM: stored like R8 / RG8; R16_SNORM / RG16_SNORM): VPT_V_SNORM
@@ -227,6 +229,7 @@ void destroy_split_streams(vpt_renderer *r);
 int join_side(vpt_renderer *r);                     // the side streams' work happens-before everything enqueued on the context's stream from here on
 int streams_deal(vpt_renderer *r, Deal d);          // before the launches of a deal: join and fork as the deal needs (StreamSet)
 int make_args(vpt_renderer *r, const vpt_uniforms *u, bool need_volume, PassArgs *a);
+int volume_create(vpt_context *c, int w, int h, int d, int format, bool zero_fill, vpt_volume **out);   // vpt_volume_create; zero_fill = false: the caller writes every texel
 int volume_records(vpt_volume *v);                  // builds the column records of a finalized one-channel byte volume if they are not current
 hipError_t create_overlapping_stream(hipStream_t *out, const vpt_renderer *r);   // overlaps r's context stream and side streams
 bool invert_matrix(const float *m, double out[4][4]);               // column-major float matrix -> its inverse (double); false: singular

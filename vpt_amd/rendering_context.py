@@ -18,6 +18,12 @@ class RenderingContext(EventTarget):
     def __init__(self, options=None):
         super().__init__()
         options = options or {}
+        # (extension) 'central' | 'sobel': a one-channel R8 / R16 volume gets its gradient magnitude as second channel when it is loaded
+        self.gradient = options.get('gradient')
+        self.gradientGain = options['gradientGain'] if options.get('gradientGain') is not None else 1.0
+        if self.gradient is not None:
+            from .gradient import operator_code, gain_factor
+            operator_code(self.gradient); gain_factor(self.gradientGain)              # a bad option fails here, not at the first volume
         self.gl = Context(options.get('device', 0))                                   # initGL(), :61-105
         self.environmentTexture = np.array([[[255, 255, 255, 255]]], dtype=np.uint8)   # :90-101
         self._rng = options.get('rng')
@@ -56,10 +62,19 @@ class RenderingContext(EventTarget):
         self.volume.addEventListener('progress', lambda e: self.dispatchEvent(CustomEvent('progress', {'detail': e.detail})))
         self.volume.load()
         self.volume.setFilter(self.filter)
+        if self.gradient is not None and self._one_channel_unorm(self.volume):
+            source = self.volume
+            self.volume = source.derive_gradient(self.gradient, self.gradientGain)    # (value, gradient magnitude): the 2-D transfer function's axes
+            source.destroy()
         if self.renderer:
             self.renderer.setVolume(self.volume)
         if old:
             old.destroy()                                                             # device memory is not garbage-collected
+
+    @staticmethod
+    def _one_channel_unorm(volume):
+        from . import _native as N
+        return volume.native_format()[0] in (N.FORMAT_R8, N.FORMAT_R16)
 
     def setEnvironmentMap(self, image):                                               # :135-140 — RGBA8, float [h][w][4] or read_hdr()'s
         self.environmentTexture = image

@@ -248,6 +248,64 @@ class Volume(EventTarget):
         N.check(N.lib().vpt_volume_upload_block_device(self.texture, int(x), int(y), int(z), int(w), int(h), int(d),
                                                        C.c_void_p(int(device_ptr)), int(nbytes)))
 
+    # ---- extension: volume operations on the device (include/vpt.h; DESIGN.md "Gradient-magnitude channel") ----
+    def native_format(self):
+        """(VPT_FORMAT_* of the device volume, numpy dtype of a block's texels) from the modality (a 16-bit volume made by from_array
+        needs no extension: its triple is looked up directly)"""
+        m = self.modality
+        key = (m['type'], m['format'], m.get('internalFormat'))
+        sized = _SIZED.get(key) or _NORM16.get(key)
+        if sized is not None:
+            return getattr(N, sized[0]), sized[2]
+        fmt, _, dtype = device_format(m, self._gl)
+        return fmt, dtype
+
+    def _texel_layout(self):
+        """(channels, numpy dtype) of a block as upload_block takes it and read_block returns it (packed formats: the decoded RG32F texels)"""
+        fmt, dtype = self.native_format()
+        if fmt in (N.FORMAT_R32F, N.FORMAT_RG32F):
+            dtype = np.float32                                # HALF_FLOAT was widened on upload
+        if N.FORMAT_RGB565 <= fmt <= N.FORMAT_RGB9_E5:
+            return 2, np.float32
+        two = fmt in (N.FORMAT_RG8, N.FORMAT_RG32F, N.FORMAT_RG8_SNORM, N.FORMAT_RG16, N.FORMAT_RG16_SNORM)
+        return (2 if two else 1), dtype
+
+    def read_block(self, x, y, z, w, h, d):
+        """texSubImage3D's inverse: the texels of a box as a [d][h][w] (one channel) or [d][h][w][2] array in the volume's texel type"""
+        channels, dtype = self._texel_layout()
+        out = np.empty((int(d), int(h), int(w)) + ((2,) if channels == 2 else ()), dtype=dtype)
+        N.check(N.lib().vpt_volume_read_block(self.texture, int(x), int(y), int(z), int(w), int(h), int(d),
+                                              out.ctypes.data_as(C.c_void_p), out.nbytes))
+        return out
+
+    def histogram(self):
+        """uint32 counts: [256] bins of the value's top 8 bits (R8 / R16), or [256][256], [g][v], of both channels' (RG8 / RG16)"""
+        channels, _ = self._texel_layout()
+        bins = np.zeros(65536 if channels == 2 else 256, dtype=np.uint32)
+        N.check(N.lib().vpt_volume_histogram(self.texture, bins.ctypes.data_as(C.POINTER(C.c_uint32)), bins.size))
+        return bins.reshape(256, 256) if channels == 2 else bins
+
+    def derive_gradient(self, operator='central', gain=1.0):
+        """A new, ready RG8 / RG16 volume on this volume's context and with its filter: channel 0 this (R8 / R16) volume's texels, channel 1
+        their gradient magnitude (vpt_amd.gradient_magnitude states it), derived on the device.  This volume is not changed."""
+        from .gradient import operator_code, gain_factor
+        op = operator_code(operator)
+        gain_factor(gain)                                     # raises for gains the contract does not take
+        h = C.c_void_p()
+        N.check(N.lib().vpt_volume_derive_gradient(self.texture, op, float(gain), C.byref(h)))
+        out = type(self)(self._gl)
+        out.texture = h
+        norm16 = self.modality.get('internalFormat') == GL_R16_EXT
+        dims = dict(self.modality['dimensions'])
+        out.modality = {'name': self.modality.get('name', 'default'), 'dimensions': dims, 'transform': self.modality.get('transform'),
+                        'format': GL_RG, 'internalFormat': GL_RG16_EXT if norm16 else GL_RG8,
+                        'type': GL_UNSIGNED_SHORT if norm16 else GL_UNSIGNED_BYTE,
+                        'placements': [{'index': 0, 'position': {'x': 0, 'y': 0, 'z': 0}}]}
+        out.metadata = {'meta': dict((self.metadata or {}).get('meta', {})), 'modalities': [out.modality],
+                        'blocks': [{'url': None, 'format': 'raw', 'dimensions': dict(dims)}]}
+        out.ready = True
+        return out
+
     def set_wide_tables(self, wide):
         """force the > 4 GiB addressing variant of the kernels (automatic above 4 GiB of bricked data)"""
         N.check(N.lib().vpt_volume_set_wide_tables(self.texture, 1 if wide else 0))
