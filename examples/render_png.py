@@ -6,6 +6,8 @@
     python examples/render_png.py --renderer eam --filter quasicubic ...    (volume filter: linear, nearest or quasicubic)
     python examples/render_png.py --renderer eam --tf colour --gradient sobel --gradient-gain 4 ...   (2-D transfer function: the
                                      gradient magnitude is derived on the device as the volume's second channel)
+    python examples/render_png.py --volume ct.raw --dims 512 512 300 --bits 16 --signed --window -200,400 ...   (16-bit samples, placed on the
+                                     transfer function's axis by a window derived on the device; --window auto: the 0.5 / 99.5 percentiles)
     python examples/render_png.py --renderer mcm --env sky.hdr --tonemapper aces ...   (a Radiance .hdr environment map lights MCS / MCM)
 
 Without --volume a synthetic 128^3 sphere with lattice noise is used.  PNG encoding is plain zlib (no imaging library)."""
@@ -35,22 +37,37 @@ def main():
     ap.add_argument("--filter", default="linear", choices=["linear", "nearest", "quasicubic"])
     ap.add_argument("--gradient", default=None, choices=["central", "sobel"], help="derive the gradient magnitude as second channel (R8 / R16 volumes)")
     ap.add_argument("--gradient-gain", type=float, default=1.0)
+    ap.add_argument("--bits", type=int, default=8, choices=[8, 16, 32], help="sample size of a .raw volume: 8, 16 (little-endian integers) or 32 (float)")
+    ap.add_argument("--signed", action="store_true", help="16-bit .raw samples are signed")
+    ap.add_argument("--window", default=None, help="LO,HI | range | auto: window the volume's values to the transfer function's axis "
+                                                   "(auto: the 0.5 / 99.5 percentiles; the range for a float volume)")
+    ap.add_argument("--window-format", default="r8", choices=["r8", "r16"])
     ap.add_argument("--yaw", type=float, default=0.6)
     ap.add_argument("--pitch", type=float, default=-0.35)
     ap.add_argument("--env", default="", help="Radiance .hdr environment map (MCS and MCM are lit by it)")
     ap.add_argument("--out", default="frame.png")
     a = ap.parse_args()
 
+    window = a.window
+    if window not in (None, 'range', 'auto'):
+        lo, hi = (float(x) for x in window.split(','))
+        window = [lo, hi]
     rc = vpt_amd.RenderingContext({'resolution': (a.width, a.height), 'filter': a.filter, 'rng': GoldenRatioRng(),
-                                   'gradient': a.gradient, 'gradientGain': a.gradient_gain})
+                                   'gradient': a.gradient, 'gradientGain': a.gradient_gain,
+                                   'window': None if window == 'auto' else window, 'windowFormat': a.window_format})
     rc.resize(a.width, a.height)
+    rc.gl.getExtension('EXT_texture_norm16')                      # 16-bit volumes are taken
     if a.volume.endswith(".bvp"):
         reader = vpt_amd.BVPReader(vpt_amd.FileLoader(a.volume))
     elif a.volume:
         w, h, d = a.dims
-        reader = vpt_amd.RAWReader(vpt_amd.FileLoader(a.volume), {'width': w, 'height': h, 'depth': d})
+        reader = vpt_amd.RAWReader(vpt_amd.FileLoader(a.volume), {'width': w, 'height': h, 'depth': d, 'bits': a.bits, 'signed': a.signed})
     else:
         reader = vpt_amd.RAWReader(sphere_volume(128, noise=48.0), {'width': 128, 'height': 128, 'depth': 128})
+    if window == 'auto':
+        from vpt_amd.readers import GL_FLOAT, GL_HALF_FLOAT
+        floats = reader.readMetadata()['modalities'][0]['type'] in (GL_FLOAT, GL_HALF_FLOAT)
+        rc.window = 'range' if floats else {'percentiles': [0.5, 99.5]}
     rc.setVolume(reader)
     if a.env:
         rc.setEnvironmentMap(vpt_amd.read_hdr(a.env))

@@ -182,6 +182,31 @@ VPT_API int vpt_volume_read_block(vpt_volume *vol, int x, int y, int z, int widt
  * both channels' top 8 bits, bins[g * 256 + v] (nbins = 65536): what a 2-D transfer-function editor draws behind its bumps.  Other
  * formats: VPT_ERR_UNSUPPORTED.  Blocks. */
 VPT_API int vpt_volume_histogram(vpt_volume *vol, uint32_t *bins, size_t nbins);
+/* ---- value-range window (window / level) on the device (extension; DESIGN.md "Value-range window") */
+/* Places a one-channel volume of any scalar format on the transfer function's [0, 1] axis: a new VPT_FORMAT_R8 (M = 255) or VPT_FORMAT_R16
+ * (M = 65535) volume of the same size whose texel is 0 at or below `lo`, M at or above `hi` and linear in between.  Sources: R8, R16,
+ * R8_SNORM, R16_SNORM, R32F (which includes R16F manifests, widened on upload); two-channel and packed sources: VPT_ERR_UNSUPPORTED,
+ * naming the format.  out_format other than R8 / R16: VPT_ERR_INVALID.
+ * The code c of a texel (integer sources) is the stored integer: 0 .. 2^B - 1 for R8 / R16; the two's-complement value for SNORM, the
+ * most negative code read as the one above it (max(c, -(2^(B-1) - 1)): what finalize does once; these operations apply it themselves,
+ * so their results do not depend on whether the source was finalized).  lo and hi are in code units.
+ *   Integer contract (lo, hi integral, |lo|, |hi| <= 2^31, D = hi - lo >= 1; otherwise VPT_ERR_INVALID), in 64-bit integers, n = c - lo:
+ *     out = 0 if n <= 0;  M if n >= D;  (2 n M + D) div (2 D) otherwise                (round half up)
+ *   so R16 -> R16 with [0, 65535] and R8 -> R8 with [0, 255] are the identity, and the map is monotone.
+ *   Float contract (R32F; lo, hi and hi - lo finite, hi > lo; otherwise VPT_ERR_INVALID), every operation one correctly rounded IEEE
+ *   double operation, nothing fused:
+ *     t = ((double) v - lo) / (hi - lo);   out = 0 if !(t > 0) (NaN and -inf included);  M if t >= 1;  else (uint) floor(t * M + 0.5)
+ * vpt_amd.window_texels states both in numpy.
+ * The result is a new, finalized volume on src's context with src's dimensions and filter, enqueued on the context's stream behind any
+ * upload into src; src is not changed and may be destroyed afterwards.  The result is an ordinary volume (every renderer, set_filter,
+ * upload_block, read_block, histogram, derive_gradient) */
+VPT_API int vpt_volume_window(vpt_volume *src, double lo, double hi, int out_format, vpt_volume **out);
+/* the smallest and the largest code (integer sources) or value (R32F: NaN texels ignored, infinities counted, -0 and +0 equal; a
+ * volume without a texel that is not NaN: VPT_ERR_INVALID) of the same source formats.  Blocks. */
+VPT_API int vpt_volume_range(vpt_volume *vol, double *lo, double *hi);
+/* counts per code at full resolution, uint32: nbins = 2^B (256 or 65536), bin = code for R8 / R16, code + 2^(B-1) for R8_SNORM /
+ * R16_SNORM.  R32F and every other format: VPT_ERR_UNSUPPORTED.  Blocks.  (vpt_volume_histogram counts the top 8 bits.) */
+VPT_API int vpt_volume_code_histogram(vpt_volume *vol, uint32_t *bins, size_t nbins);
 
 /* ---- renderer: AbstractRenderer.js:17-116 and the four subclasses */
 /* new R(gl, volume, camera, environmentTexture, {resolution}) — AbstractRenderer.js:17-49; width != height is the

@@ -174,6 +174,37 @@ static napi_value VolumeHistogram(napi_env env, napi_callback_info info) {
     VPT_CHECK(vpt_volume_histogram(v, (uint32_t *)data, n / sizeof(uint32_t)));
     return undefined(env);
 }
+// volumeWindow(volume, lo, hi, format) -> a new volume handle (format: VPT_FORMAT_R8 or VPT_FORMAT_R16)
+static napi_value VolumeWindow(napi_env env, napi_callback_info info) {
+    napi_value a[4]; vpt_volume *v; double lo, hi; int32_t format;
+    if (!get_args(env, info, 4, a) || !get_handle(env, a[0], &v)) return nullptr;
+    if (napi_get_value_double(env, a[1], &lo) != napi_ok || napi_get_value_double(env, a[2], &hi) != napi_ok) {
+        napi_throw_type_error(env, nullptr, "expected a number"); return nullptr;
+    }
+    if (!get_i32(env, a[3], &format)) return nullptr;
+    vpt_volume *out = nullptr;
+    VPT_CHECK(vpt_volume_window(v, lo, hi, format, &out));
+    return make_external(env, out);
+}
+// volumeRange(volume) -> [lo, hi]: the smallest and the largest code or value
+static napi_value VolumeRange(napi_env env, napi_callback_info info) {
+    napi_value a[1]; vpt_volume *v;
+    if (!get_args(env, info, 1, a) || !get_handle(env, a[0], &v)) return nullptr;
+    double lo = 0.0, hi = 0.0;
+    VPT_CHECK(vpt_volume_range(v, &lo, &hi));
+    napi_value out, e;
+    napi_create_array_with_length(env, 2, &out);
+    napi_create_double(env, lo, &e); napi_set_element(env, out, 0, e);
+    napi_create_double(env, hi, &e); napi_set_element(env, out, 1, e);
+    return out;
+}
+// volumeCodeHistogram(volume, bins): bins is a Uint32Array of 256 (8-bit codes) or 65536 (16-bit codes) counts
+static napi_value VolumeCodeHistogram(napi_env env, napi_callback_info info) {
+    napi_value a[2]; vpt_volume *v; void *data; size_t n;
+    if (!get_args(env, info, 2, a) || !get_handle(env, a[0], &v) || !get_bytes(env, a[1], &data, &n)) return nullptr;
+    VPT_CHECK(vpt_volume_code_histogram(v, (uint32_t *)data, n / sizeof(uint32_t)));
+    return undefined(env);
+}
 
 // ---- renderer -----------------------------------------------------------------------------------------
 static napi_value RendererCreate(napi_env env, napi_callback_info info) {
@@ -483,6 +514,7 @@ static napi_value Init(napi_env env, napi_value exports) {
     EXPORT("volumeSetFilter", VolumeSetFilter); EXPORT("volumeDestroy", VolumeDestroy); EXPORT("volumeBrickedBytes", VolumeBrickedBytes);
     EXPORT("volumeDeriveGradient", VolumeDeriveGradient); EXPORT("volumeReadBlock", VolumeReadBlock); EXPORT("volumeHistogram", VolumeHistogram);
     CONST(VPT_GRADIENT_CENTRAL); CONST(VPT_GRADIENT_SOBEL);
+    EXPORT("volumeWindow", VolumeWindow); EXPORT("volumeRange", VolumeRange); EXPORT("volumeCodeHistogram", VolumeCodeHistogram);
     EXPORT("rendererCreate", RendererCreate); EXPORT("rendererDestroy", RendererDestroy); EXPORT("rendererSetShard", RendererSetShard);
     EXPORT("rendererLocalRows", RendererLocalRows); EXPORT("rendererGlobalRow", RendererGlobalRow);
     EXPORT("rendererSetVolume", RendererSetVolume); EXPORT("rendererSetTransferFunction", RendererSetTransferFunction);

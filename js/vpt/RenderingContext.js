@@ -4,12 +4,14 @@
 // where the reference blits the tone mapper's texture to the canvas (:199-209), getFrame() reads it back.
 //   new RenderingContext({ resolution, filter, device, rng })     resolution: number or { width, height }; filter: 'linear' (default),
 //   'nearest' or 'quasicubic'; gradient: null (default), 'central' or 'sobel', gradientGain (default 1): a one-channel R8 / R16 volume gets its
-//   gradient magnitude as second channel when it is loaded (Volume.deriveGradient)
+//   gradient magnitude as second channel when it is loaded (Volume.deriveGradient); window: null (default), [lo, hi], 'range' or
+//   { percentiles: [a, b] }, windowFormat: 'r8' (default) or 'r16': a one-channel volume is windowed when it is loaded, before the gradient
+//   is derived (Volume.window)
 const { EventTarget, CustomEvent } = require('./EventTarget.js');
 const { Context } = require('./Context.js');
 const { OrbitCameraAnimator } = require('./animators.js');
 const { Node, Transform, PerspectiveCamera } = require('./scene.js');
-const { Volume, gradientArguments } = require('./Volume.js');
+const { Volume, gradientArguments, windowFormatBits } = require('./Volume.js');
 const { native } = require('./native.js');
 const { RendererFactory } = require('./renderers/RendererFactory.js');
 const { ToneMapperFactory } = require('./tonemappers/ToneMapperFactory.js');
@@ -23,6 +25,9 @@ constructor(options) {
     this.gradient = options.gradient !== undefined ? options.gradient : null;
     this.gradientGain = options.gradientGain !== undefined && options.gradientGain !== null ? options.gradientGain : 1;
     if (this.gradient !== null) { gradientArguments(native(), this.gradient, this.gradientGain); }   // a bad option fails here, not at the first volume
+    this.window = options.window !== undefined ? options.window : null;
+    this.windowFormat = options.windowFormat !== undefined && options.windowFormat !== null ? options.windowFormat : 'r8';
+    if (this.window !== null) { windowFormatBits(this.windowFormat); RenderingContext._windowSpec(this.window); }   // likewise
     this.gl = new Context(options.device || 0);                                   // initGL(), :61-105
     this.environmentTexture = { data: new Uint8Array([255, 255, 255, 255]), width: 1, height: 1 };   // :90-101
     this._rng = options.rng;
@@ -67,16 +72,52 @@ async setVolume(reader) {                                                       
     });
     await this.volume.load();
     this.volume.setFilter(this.filter);
-    if (this.gradient !== null) {
-        const N = native(), fmt = this.volume.nativeFormat();
-        if (fmt === N.VPT_FORMAT_R8 || fmt === N.VPT_FORMAT_R16) {                     // (value, gradient magnitude): the 2-D transfer function's axes
-            const source = this.volume;
-            this.volume = source.deriveGradient({ operator: this.gradient, gain: this.gradientGain });
+    try {
+        if (this.window !== null) {                                                    // the transfer function's x axis is [lo, hi]
+            const source = this.volume, w = this._windowOf(source);
+            this.volume = source.window({ lo: w[0], hi: w[1], format: this.windowFormat });
             source.destroy();
         }
+        if (this.gradient !== null) {
+            const N = native(), fmt = this.volume.nativeFormat();
+            if (fmt === N.VPT_FORMAT_R8 || fmt === N.VPT_FORMAT_R16) {                 // (value, gradient magnitude): the 2-D transfer function's axes
+                const source = this.volume;
+                this.volume = source.deriveGradient({ operator: this.gradient, gain: this.gradientGain });
+                source.destroy();
+            }
+        }
+    } catch (e) {                                                                      // the context keeps the volume it had
+        this.volume.destroy();
+        this.volume = old;
+        throw e;
     }
     if (this.renderer) { this.renderer.setVolume(this.volume); }
     if (old) { old.destroy(); }                                                        // device memory is not garbage-collected
+}
+
+// { kind: 'values', lo, hi } | { kind: 'range' } | { kind: 'percentiles', a, b } of a `window` option; throws for anything else
+static _windowSpec(window) {
+    if (window === 'range') { return { kind: 'range' }; }
+    if (Array.isArray(window) && window.length === 2 && typeof window[0] === 'number' && typeof window[1] === 'number') {
+        return { kind: 'values', lo: window[0], hi: window[1] };
+    }
+    if (window && typeof window === 'object' && !Array.isArray(window) && Object.keys(window).length === 1 &&
+        Array.isArray(window.percentiles) && window.percentiles.length === 2) {
+        const a = Number(window.percentiles[0]), b = Number(window.percentiles[1]);
+        if (!(a >= 0 && a <= b && b <= 100)) { throw new Error(`window percentiles ${window.percentiles}: 0 <= a <= b <= 100`); }
+        return { kind: 'percentiles', a, b };
+    }
+    throw new Error("window is null, [lo, hi], 'range' or { percentiles: [a, b] }, not " + JSON.stringify(window));
+}
+
+// [lo, hi] of the `window` option for this volume
+_windowOf(volume) {
+    const spec = RenderingContext._windowSpec(this.window);
+    if (spec.kind === 'values') { return [spec.lo, spec.hi]; }
+    if (spec.kind === 'percentiles') { return volume.percentileWindow(spec.a, spec.b); }
+    const r = volume.range();
+    if (volume.nativeFormat() !== native().VPT_FORMAT_R32F) { r[1] = Math.max(r[1], r[0] + 1); }
+    return r;
 }
 
 setEnvironmentMap(image) {                                                            // :135-140 — { data: RGBA8 | HDR, width, height[, format] }

@@ -126,6 +126,40 @@ function gradientArguments(N, operator, gain) {
     return { op, gain: g };
 }
 
+// 8 or 16 from a windowed volume's format name ('r8' | 'r16')
+function windowFormatBits(format) {
+    if (format === 'r8') { return 8; }
+    if (format === 'r16') { return 16; }
+    throw new Error(`a windowed volume is 'r8' or 'r16', not '${format}'`);
+}
+
+// (lo, hi) in code units from a full-resolution code histogram (256 or 65536 bins; signed: bin = code + 2^(B-1)): with N the sum of the bins
+// and cum(k) the inclusive cumulative count, lo = the smallest code with cum >= max(1, ceil(N pLo / 100)), hi likewise for pHi, then
+// hi = max(hi, lo + 1).  Integers only: a percentile is taken as the exact rational of its floating-point value (vpt_amd/window.py)
+function percentileWindow(bins, pLo, pHi, signed) {
+    if (bins.length !== 256 && bins.length !== 65536) { throw new Error('a code histogram has 256 or 65536 bins, not ' + bins.length); }
+    if (!(pLo >= 0 && pLo <= pHi && pHi <= 100)) { throw new Error(`percentiles ${pLo}, ${pHi}: 0 <= pLo <= pHi <= 100`); }
+    let total = 0;
+    for (let i = 0; i < bins.length; i++) { total += bins[i]; }
+    if (total === 0) { throw new Error('the histogram is empty'); }
+    const need = p => {                                      // max(1, ceil(total * p / 100)), p = m / 2^k exactly
+        let m = p, k = 0;
+        while (!Number.isInteger(m)) { m *= 2; k++; }
+        const num = BigInt(m) * BigInt(total), den = BigInt(100) * (BigInt(1) << BigInt(k));
+        let q = num / den;
+        if (q * den < num) { q += BigInt(1); }
+        return Math.max(1, Number(q));
+    };
+    const code = p => {
+        const want = need(p);
+        let cum = 0;
+        for (let i = 0; i < bins.length; i++) { cum += bins[i]; if (cum >= want) { return i - (signed ? bins.length / 2 : 0); } }
+        return bins.length - 1 - (signed ? bins.length / 2 : 0);
+    };
+    const lo = code(pLo), hi = code(pHi);
+    return [lo, Math.max(hi, lo + 1)];
+}
+
 class Volume extends EventTarget {
 
 constructor(gl, reader, options) {
@@ -217,5 +251,42 @@ deriveGradient(options) {
     return out;
 }
 
+// ---- extension: the value-range window (include/vpt.h; DESIGN.md "Value-range window") ----
+// a new, ready R8 / R16 volume with this volume's filter whose [0, 1] axis is the range [lo, hi] of this one-channel volume (code units for
+// R8 / R16 / R8_SNORM / R16_SNORM, values for R32F): { lo, hi, format: 'r8' (default) | 'r16' }, derived on the device; this volume is not changed
+window(options) {
+    options = options || {};
+    const N = native();
+    const norm16 = windowFormatBits(options.format !== undefined ? options.format : 'r8') === 16;
+    const out = new Volume(this._gl);
+    out.texture = N.volumeWindow(this.texture, Number(options.lo), Number(options.hi), norm16 ? N.VPT_FORMAT_R16 : N.VPT_FORMAT_R8);
+    const dimensions = Object.assign({}, this.modality.dimensions);
+    out.modality = { name: this.modality.name || 'default', dimensions, transform: this.modality.transform, format: GL_RED,
+        internalFormat: norm16 ? R.GL_R16_EXT : R.GL_R8, type: norm16 ? R.GL_UNSIGNED_SHORT : GL_UNSIGNED_BYTE,
+        placements: [{ index: 0, position: { x: 0, y: 0, z: 0 } }] };
+    out.metadata = { meta: Object.assign({}, (this.metadata || {}).meta), modalities: [out.modality],
+        blocks: [{ url: null, format: 'raw', dimensions: Object.assign({}, dimensions) }] };
+    out.ready = true;
+    return out;
 }
-module.exports = { Volume, RAWReader, filterCode, gradientArguments };
+
+// [lo, hi]: the smallest and the largest code (R8 / R16 / R8_SNORM / R16_SNORM) or value (R32F, NaN texels ignored)
+range() { return native().volumeRange(this.texture); }
+
+// Uint32Array counts per code at full resolution: 256 (R8, R8_SNORM) or 65536 (R16, R16_SNORM) bins; bin = code, for SNORM code + 128 / + 32768
+codeHistogram() {
+    const N = native(), fmt = this.nativeFormat();
+    const bins = new Uint32Array(fmt === N.VPT_FORMAT_R16 || fmt === N.VPT_FORMAT_R16_SNORM ? 65536 : 256);
+    N.volumeCodeHistogram(this.texture, bins);
+    return bins;
+}
+
+// [lo, hi] in code units: the pLo-th and pHi-th percentile codes of an integer volume (defaults 0.5 and 99.5)
+percentileWindow(pLo, pHi) {
+    const N = native(), fmt = this.nativeFormat();
+    return percentileWindow(this.codeHistogram(), pLo !== undefined ? pLo : 0.5, pHi !== undefined ? pHi : 99.5,
+        fmt === N.VPT_FORMAT_R8_SNORM || fmt === N.VPT_FORMAT_R16_SNORM);
+}
+
+}
+module.exports = { Volume, RAWReader, filterCode, gradientArguments, windowFormatBits, percentileWindow };

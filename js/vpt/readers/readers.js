@@ -24,22 +24,32 @@ class AbstractReader {                                          // AbstractReade
     async readBlock(block) {}
 }
 
-// RAWReader.js:3-70; `loader` may also be the bytes themselves (extension: wrapped in a BlobLoader)
+// RAWReader.js:3-70; `loader` may also be the bytes themselves (extension: wrapped in a BlobLoader).
+// (extension) options `bits` (8 default, 16, 32) and `signed` (16-bit only): the sample type the reference's volume dialog offers and its
+// reader drops (VolumeLoadDialog.html:23-34, Application.js:174-179, RAWReader.js:36-38,65-70) — 16: little-endian uint16 (R16_EXT) or,
+// signed, int16 (R16_SNORM_EXT), slices of 2 * width * height bytes; 32: little-endian float32 (R32F), 4 * width * height bytes.
 class RAWReader extends AbstractReader {
 
 constructor(loader, options) {
     super(loader instanceof AbstractLoader ? loader : new BlobLoader(loader));
     Object.assign(this, { width: 0, height: 0, depth: 0 }, options || {});
+    if (this.bits === undefined || this.bits === null) { this.bits = 8; }
+    this.signed = !!this.signed;
+    if (this.bits !== 8 && this.bits !== 16 && this.bits !== 32) { throw new Error('RAWReader: bits must be 8, 16 or 32, not ' + this.bits); }
+    if (this.signed && this.bits !== 16) { throw new Error('RAWReader: signed samples are 16-bit'); }
 }
 
 async readMetadata() {                                          // :15-63
+    let triple = [GL_RED, GL_R8, GL_UNSIGNED_BYTE];
+    if (this.bits === 16) { triple = this.signed ? [GL_RED, GL_R16_SNORM_EXT, GL_SHORT] : [GL_RED, GL_R16_EXT, GL_UNSIGNED_SHORT]; }
+    if (this.bits === 32) { triple = [GL_RED, GL_R32F, GL_FLOAT]; }
     const metadata = {
         meta: { version: 1 },
         modalities: [{
             name: 'default',
             dimensions: { width: this.width, height: this.height, depth: this.depth },
             transform: { matrix: [1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1] },
-            format: GL_RED, internalFormat: GL_R8, type: GL_UNSIGNED_BYTE,
+            format: triple[0], internalFormat: triple[1], type: triple[2],
             placements: [],
         }],
         blocks: [],
@@ -52,7 +62,7 @@ async readMetadata() {                                          // :15-63
 }
 
 async readBlock(block) {                                        // :65-70
-    const sliceBytes = this.width * this.height;
+    const sliceBytes = this.width * this.height * (this.bits >> 3);
     return await this._loader.readData(block * sliceBytes, (block + 1) * sliceBytes);
 }
 

@@ -19,6 +19,7 @@ from .animators import CircleAnimator, OrbitCameraAnimator
 from .transfer_function import TransferFunction
 from .hdr import HDRImage, read_hdr
 from .gradient import gradient_magnitude
+from .window import window_texels, percentile_window
 from ._native import VptError
 
 __all__ = [
@@ -29,5 +30,5 @@ __all__ = [
     'AbstractToneMapper', 'ArtisticToneMapper', 'RangeToneMapper', 'ReinhardToneMapper', 'Reinhard2ToneMapper',
     'Uncharted2ToneMapper', 'FilmicToneMapper', 'UnrealToneMapper', 'AcesToneMapper', 'LottesToneMapper',
     'UchimuraToneMapper', 'ToneMapperFactory', 'RenderingContext', 'CircleAnimator', 'OrbitCameraAnimator', 'TransferFunction',
-    'HDRImage', 'read_hdr', 'gradient_magnitude',
+    'HDRImage', 'read_hdr', 'gradient_magnitude', 'window_texels', 'percentile_window',
 ]

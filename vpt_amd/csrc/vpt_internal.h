@@ -9,6 +9,7 @@
 //   vpt_render.hip  the renderer entry points: the four hooks, render(), frame sequences (vpt_renderer_play*)
 //   vpt_post.hip    what follows a frame: tone mappers, the RCCL frame gather
 //   vpt_volume_ops.hip  volume operations on the device: the gradient-magnitude channel, texel read-back, histograms
+//   vpt_volume_window.hip  the value-range window (window / level) of a one-channel volume, its range and its code histogram
 // Nothing device-side crosses a translation unit: a kernel is compiled by the unit that names it (the three MCM units share one header).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -274,6 +275,12 @@ static inline PassArgs frame_args(const PassArgs &a, const FrameVar &v) {      /
     return f;
 }
 
+// the name of a VPT_FORMAT_* for messages
+static inline const char *format_name(int format) {
+    static const char *names[] = { "R8", "RG8", "R32F", "RG32F", "R8_SNORM", "RG8_SNORM", "RGB565", "RGBA4", "RGB5_A1", "RGB10_A2",
+                                   "R11F_G11F_B10F", "RGB9_E5", "R16", "RG16", "R16_SNORM", "RG16_SNORM" };
+    return (format >= 0 && format < (int)(sizeof(names) / sizeof(names[0]))) ? names[format] : "?";
+}
 static inline bool is_march_kind(int k) { return k == VPT_RENDERER_MIP || k == VPT_RENDERER_EAM || k == VPT_RENDERER_MCS; }
 
 // dynamic LDS of the sampling kernels: transfer-function pairs + the three brick-offset tables

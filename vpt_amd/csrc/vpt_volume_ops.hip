@@ -216,12 +216,6 @@ __global__ void k_read_block(const uint8_t *__restrict__ vol, int nx, int ny, ui
 // ---------------------------------------------------------------------------------------------
 // hosts
 // ---------------------------------------------------------------------------------------------
-static const char *format_name(int format) {
-    static const char *names[] = { "R8", "RG8", "R32F", "RG32F", "R8_SNORM", "RG8_SNORM", "RGB565", "RGBA4", "RGB5_A1", "RGB10_A2",
-                                   "R11F_G11F_B10F", "RGB9_E5", "R16", "RG16", "R16_SNORM", "RG16_SNORM" };
-    return (format >= 0 && format < (int)(sizeof(names) / sizeof(names[0]))) ? names[format] : "?";
-}
-
 template <typename T>
 static void launch_gradient(const vpt_volume *src, vpt_volume *dst, int op, unsigned long long q) {
     const dim3 grid((unsigned)((src->nx + GR_TX - 1) / GR_TX), (unsigned)((src->ny + GR_TY - 1) / GR_TY), (unsigned)((src->nz + GR_TZ - 1) / GR_TZ));

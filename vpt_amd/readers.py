@@ -46,7 +46,10 @@ class AbstractReader:
 
 class RAWReader(AbstractReader):
     """src/js/readers/RAWReader.js:3-70: a raw u8 volume exposed as one placement per z slice.
-    ``loader``: an AbstractLoader, or (extension) bytes / a uint8 array, wrapped in a BlobLoader."""
+    ``loader``: an AbstractLoader, or (extension) bytes / a uint8 array, wrapped in a BlobLoader.
+    (extension) options ``bits`` (8 default, 16, 32) and ``signed`` (16-bit only): the sample type the reference's volume dialog offers and
+    its reader drops (VolumeLoadDialog.html:23-34, Application.js:174-179, RAWReader.js:36-38,65-70) — 16: little-endian uint16 (R16_EXT) or,
+    signed, int16 (R16_SNORM_EXT), slices of 2 * width * height bytes; 32: little-endian float32 (R32F), 4 * width * height bytes."""
 
     def __init__(self, loader, options=None):
         super().__init__(loader if isinstance(loader, AbstractLoader) else BlobLoader(loader))
@@ -54,13 +57,25 @@ class RAWReader(AbstractReader):
         self.width = options.get('width', 0)                      # :8-12
         self.height = options.get('height', 0)
         self.depth = options.get('depth', 0)
+        self.bits = options['bits'] if options.get('bits') is not None else 8
+        self.signed = bool(options.get('signed', False))
+        if self.bits not in (8, 16, 32) or isinstance(self.bits, bool):
+            raise RuntimeError('RAWReader: bits must be 8, 16 or 32, not %r' % (self.bits,))
+        if self.signed and self.bits != 16:
+            raise RuntimeError('RAWReader: signed samples are 16-bit')
 
     def readMetadata(self):                                        # :15-63
+        if self.bits == 16:
+            triple = (GL_RED, GL_R16_SNORM_EXT, GL_SHORT) if self.signed else (GL_RED, GL_R16_EXT, GL_UNSIGNED_SHORT)
+        elif self.bits == 32:
+            triple = (GL_RED, GL_R32F, GL_FLOAT)
+        else:
+            triple = (GL_RED, GL_R8, GL_UNSIGNED_BYTE)
         modality = {
             'name': 'default',
             'dimensions': {'width': self.width, 'height': self.height, 'depth': self.depth},
             'transform': {'matrix': [1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1]},
-            'format': GL_RED, 'internalFormat': GL_R8, 'type': GL_UNSIGNED_BYTE,
+            'format': triple[0], 'internalFormat': triple[1], 'type': triple[2],
             'placements': [],
         }
         blocks = []
@@ -71,7 +86,7 @@ class RAWReader(AbstractReader):
         return {'meta': {'version': 1}, 'modalities': [modality], 'blocks': blocks}
 
     def readBlock(self, block):                                    # :65-70
-        slice_bytes = self.width * self.height
+        slice_bytes = self.width * self.height * (self.bits // 8)
         return self._loader.readData(block * slice_bytes, (block + 1) * slice_bytes)
 
 

@@ -24,6 +24,13 @@ class RenderingContext(EventTarget):
         if self.gradient is not None:
             from .gradient import operator_code, gain_factor
             operator_code(self.gradient); gain_factor(self.gradientGain)              # a bad option fails here, not at the first volume
+        # (extension) None | [lo, hi] | 'range' | {'percentiles': [a, b]}: a one-channel volume is windowed to R8 ('r8') / R16 ('r16') when it
+        # is loaded, before the gradient is derived
+        self.window = options.get('window')
+        self.windowFormat = options['windowFormat'] if options.get('windowFormat') is not None else 'r8'
+        if self.window is not None:
+            from .window import format_bits
+            format_bits(self.windowFormat); self._window_spec(self.window)             # a bad option fails here, not at the first volume
         self.gl = Context(options.get('device', 0))                                   # initGL(), :61-105
         self.environmentTexture = np.array([[[255, 255, 255, 255]]], dtype=np.uint8)   # :90-101
         self._rng = options.get('rng')
@@ -62,14 +69,51 @@ class RenderingContext(EventTarget):
         self.volume.addEventListener('progress', lambda e: self.dispatchEvent(CustomEvent('progress', {'detail': e.detail})))
         self.volume.load()
         self.volume.setFilter(self.filter)
-        if self.gradient is not None and self._one_channel_unorm(self.volume):
-            source = self.volume
-            self.volume = source.derive_gradient(self.gradient, self.gradientGain)    # (value, gradient magnitude): the 2-D transfer function's axes
-            source.destroy()
+        try:
+            if self.window is not None:
+                source = self.volume
+                lo, hi = self._window_of(source)
+                self.volume = source.window(lo, hi, self.windowFormat)                # the transfer function's x axis is [lo, hi]
+                source.destroy()
+            if self.gradient is not None and self._one_channel_unorm(self.volume):
+                source = self.volume
+                self.volume = source.derive_gradient(self.gradient, self.gradientGain)    # (value, gradient magnitude): the 2-D transfer function's axes
+                source.destroy()
+        except Exception:                                                             # the context keeps the volume it had
+            self.volume.destroy()
+            self.volume = old
+            raise
         if self.renderer:
             self.renderer.setVolume(self.volume)
         if old:
             old.destroy()                                                             # device memory is not garbage-collected
+
+    @staticmethod
+    def _window_spec(window):
+        """('values', lo, hi) | ('range',) | ('percentiles', a, b) of a `window` option; raises ValueError for anything else"""
+        if window == 'range':
+            return ('range',)
+        if isinstance(window, dict) and set(window) == {'percentiles'} and len(window['percentiles']) == 2:
+            a, b = (float(p) for p in window['percentiles'])
+            if not 0 <= a <= b <= 100:
+                raise ValueError('window percentiles %r: 0 <= a <= b <= 100' % (window['percentiles'],))
+            return ('percentiles', a, b)
+        if isinstance(window, (list, tuple)) and len(window) == 2 and not any(isinstance(x, (str, bool)) for x in window):
+            return ('values', window[0], window[1])
+        raise ValueError("window is None, [lo, hi], 'range' or {'percentiles': [a, b]}, not %r" % (window,))
+
+    def _window_of(self, volume):
+        """(lo, hi) of the `window` option for this volume"""
+        from . import _native as N
+        spec = self._window_spec(self.window)
+        if spec[0] == 'values':
+            return spec[1], spec[2]
+        if spec[0] == 'percentiles':
+            return volume.percentile_window(spec[1], spec[2])
+        lo, hi = volume.range()
+        if volume.native_format()[0] != N.FORMAT_R32F:
+            hi = max(hi, lo + 1)
+        return lo, hi
 
     @staticmethod
     def _one_channel_unorm(volume):

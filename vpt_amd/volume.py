@@ -306,6 +306,49 @@ class Volume(EventTarget):
         out.ready = True
         return out
 
+    # ---- extension: the value-range window (include/vpt.h; DESIGN.md "Value-range window") ----
+    def window(self, lo, hi, format='r8'):
+        """A new, ready R8 / R16 volume on this volume's context and with its filter whose [0, 1] axis is the value range [lo, hi] of
+        this one-channel volume (code units for R8 / R16 / R8_SNORM / R16_SNORM, values for R32F): 0 at or below lo, the largest texel at or
+        above hi (vpt_amd.window_texels states it), derived on the device.  This volume is not changed."""
+        from .window import format_bits
+        norm16 = format_bits(format) == 16
+        h = C.c_void_p()
+        N.check(N.lib().vpt_volume_window(self.texture, float(lo), float(hi), N.FORMAT_R16 if norm16 else N.FORMAT_R8, C.byref(h)))
+        out = type(self)(self._gl)
+        out.texture = h
+        dims = dict(self.modality['dimensions'])
+        out.modality = {'name': self.modality.get('name', 'default'), 'dimensions': dims, 'transform': self.modality.get('transform'),
+                        'format': GL_RED, 'internalFormat': GL_R16_EXT if norm16 else GL_R8,
+                        'type': GL_UNSIGNED_SHORT if norm16 else GL_UNSIGNED_BYTE,
+                        'placements': [{'index': 0, 'position': {'x': 0, 'y': 0, 'z': 0}}]}
+        out.metadata = {'meta': dict((self.metadata or {}).get('meta', {})), 'modalities': [out.modality],
+                        'blocks': [{'url': None, 'format': 'raw', 'dimensions': dict(dims)}]}
+        out.ready = True
+        return out
+
+    def range(self):
+        """(lo, hi): the smallest and the largest code (ints; R8 / R16 / R8_SNORM / R16_SNORM) or value (floats; R32F, NaN texels ignored)"""
+        lo, hi = C.c_double(0), C.c_double(0)
+        N.check(N.lib().vpt_volume_range(self.texture, C.byref(lo), C.byref(hi)))
+        if self.native_format()[0] == N.FORMAT_R32F:
+            return lo.value, hi.value
+        return int(lo.value), int(hi.value)
+
+    def code_histogram(self):
+        """uint32 counts per code at full resolution: [256] (R8, R8_SNORM) or [65536] (R16, R16_SNORM) bins; bin = code, for SNORM
+        code + 128 / code + 32768"""
+        fmt = self.native_format()[0]
+        bins = np.zeros(65536 if fmt in (N.FORMAT_R16, N.FORMAT_R16_SNORM) else 256, dtype=np.uint32)
+        N.check(N.lib().vpt_volume_code_histogram(self.texture, bins.ctypes.data_as(C.POINTER(C.c_uint32)), bins.size))
+        return bins
+
+    def percentile_window(self, p_lo=0.5, p_hi=99.5):
+        """(lo, hi) in code units: the p_lo-th and p_hi-th percentile codes of an integer volume (vpt_amd.percentile_window)"""
+        from .window import percentile_window
+        signed = self.native_format()[0] in (N.FORMAT_R8_SNORM, N.FORMAT_R16_SNORM)
+        return percentile_window(self.code_histogram(), p_lo, p_hi, signed)
+
     def set_wide_tables(self, wide):
         """force the > 4 GiB addressing variant of the kernels (automatic above 4 GiB of bricked data)"""
         N.check(N.lib().vpt_volume_set_wide_tables(self.texture, 1 if wide else 0))
