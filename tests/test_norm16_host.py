@@ -122,7 +122,7 @@ def test_header_native_and_addon_constants():
     addon = open(os.path.join(ROOT, "js", "addon", "vpt_napi.cc")).read()
     for name in want:
         assert "CONST(%s)" % name in addon, name
-    device = open(os.path.join(ROOT, "vpt_amd", "csrc", "vpt_device.h")).read()
+    device = open(os.path.join(ROOT, "vpt_amd", "csrc", "vpt_variants.h")).read()
     assert re.search(r"#define VPT_V_NORM16\s+512\b", device)
 
 

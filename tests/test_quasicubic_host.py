@@ -26,7 +26,7 @@ def test_header_native_and_addon_agree():
     addon = open(os.path.join(ROOT, "js", "addon", "vpt_napi.cc")).read()
     for name in consts:
         assert "CONST(%s)" % name in addon, name
-    device = open(os.path.join(ROOT, "vpt_amd", "csrc", "vpt_device.h")).read()
+    device = open(os.path.join(ROOT, "vpt_amd", "csrc", "vpt_variants.h")).read()
     assert re.search(r"#define VPT_V_QCUBIC\s+256\b", device)
 
 

@@ -87,20 +87,22 @@ int volume_create(vpt_context *c, int w, int h, int d, int format, bool zero_fil
     vpt_volume *v = new vpt_volume();
     memset(v, 0, sizeof(*v));
     v->ctx = c; v->nx = w; v->ny = h; v->nz = d; v->format = format;
+    const VolumeFormat &f = *volume_format(format);
     // packed formats (VPT_FORMAT_RGB565 ..): the words are decoded on upload (k_decode_packed) into an RG32F volume
-    v->packed = (format >= VPT_FORMAT_RGB565 && format <= VPT_FORMAT_RGB9_E5) ? format : 0;
-    v->packed_bytes = (format == VPT_FORMAT_RGB565 || format == VPT_FORMAT_RGBA4 || format == VPT_FORMAT_RGB5_A1) ? 2 : 4;
+    v->packed = f.packed_bytes ? format : 0;
+    v->packed_bytes = f.packed_bytes ? f.packed_bytes : 4;
     // 16-bit normalised formats: uint16 / int16 channels, kept as they are (2 bytes per channel in the linear storage and the bricks)
-    v->norm16 = format >= VPT_FORMAT_R16 && format <= VPT_FORMAT_RG16_SNORM;
-    v->snorm = format == VPT_FORMAT_R8_SNORM || format == VPT_FORMAT_RG8_SNORM || format == VPT_FORMAT_R16_SNORM || format == VPT_FORMAT_RG16_SNORM;
-    v->channels = (format == VPT_FORMAT_RG8 || format == VPT_FORMAT_RG32F || format == VPT_FORMAT_RG8_SNORM || v->packed ||
-                   format == VPT_FORMAT_RG16 || format == VPT_FORMAT_RG16_SNORM) ? 2 : 1;
-    v->f32 = format == VPT_FORMAT_R32F || format == VPT_FORMAT_RG32F || v->packed;
-    const uint64_t eb = v->f32 ? 4 : (v->norm16 ? 2 : 1);  // bytes per texel channel
+    v->norm16 = f.bytes == 2;
+    v->snorm = f.is_signed;
+    v->channels = f.channels;
+    v->f32 = f.is_float;
+    const uint64_t eb = (uint64_t)f.bytes;               // bytes per texel channel
     v->vox_bytes = v->channels * (int)eb;
     // RG8: 256-byte slots (R brick at +0, G brick at +128); R16: 256-byte slots (5^3 words = 250 bytes), RG16: 512-byte slots (G brick at +256);
     // R32F: 512-byte slots; RG32F: 1024-byte slots (G brick at +512).  The G brick is always 128 texels behind the R brick
-    const int slot_shift = (v->f32 ? 9 : (v->norm16 ? 8 : 7)) + (v->channels == 2 ? 1 : 0);
+    v->elem_shift = f.bytes == 4 ? 2u : (f.bytes == 2 ? 1u : 0u);
+    v->slot_shift = 7u + v->elem_shift + (v->channels == 2 ? 1u : 0u);
+    const uint32_t slot_shift = v->slot_shift;
     v->filter = VPT_FILTER_LINEAR;                       // Volume.js:53-54
     int nbx = (w + 3) / 4, nby = (h + 3) / 4, nbz = (d + 3) / 4;
     // Z-order over the bricks with exactly as many bits per axis as the axis needs: the low bits of x, y, z interleave
@@ -750,8 +752,7 @@ int make_args(vpt_renderer *r, const vpt_uniforms *u, bool need_volume, PassArgs
         a->vol.hx = (float)(v->nx - 1); a->vol.hy = (float)(v->ny - 1); a->vol.hz = (float)(v->nz - 1);
         a->vol.tab32 = v->tab32; a->vol.tabc = v->tabc;
         a->vol.filter = v->filter;
-        a->vol.channels = v->channels; a->vol.slot_shift = (v->f32 ? 9u : (v->norm16 ? 8u : 7u)) + (v->channels == 2 ? 1u : 0u);
-        a->vol.elem_shift = v->f32 ? 2u : (v->norm16 ? 1u : 0u);
+        a->vol.channels = v->channels; a->vol.slot_shift = v->slot_shift; a->vol.elem_shift = v->elem_shift;
         a->vol.atlas = (r->boundary_atlas && v->atlas_ok) ? v->atlas : nullptr;
         a->vol.atlas_face = v->atlas_face; a->vol.atlas_shift = v->atlas_shift;
         if (renderer_uses_records(r)) {
@@ -1195,49 +1196,12 @@ static int probe_sample(vpt_renderer *r, const float *xyz, float *rgba, size_t n
     e = hipMemcpyAsync(din, xyz, 3 * n * sizeof(float), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) {
         dim3 grid((unsigned)((n + 255) / 256));
-        switch (variant_of(r)) {
-            case 0: if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<0>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); else hipLaunchKernelGGL(k_probe_sample<0>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); break;
-            case 1: if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<1>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); else hipLaunchKernelGGL(k_probe_sample<1>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); break;
-            case 2: if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<2>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); else hipLaunchKernelGGL(k_probe_sample<2>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); break;
-            case 3: if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<3>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); else hipLaunchKernelGGL(k_probe_sample<3>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); break;
-            case 8: if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<8>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); else hipLaunchKernelGGL(k_probe_sample<8>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); break;
-            case 9: if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<9>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); else hipLaunchKernelGGL(k_probe_sample<9>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); break;
-            case 10: if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<10>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); else hipLaunchKernelGGL(k_probe_sample<10>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); break;
-            case 11: if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<11>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); else hipLaunchKernelGGL(k_probe_sample<11>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); break;
-            case 32: if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<32>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); else hipLaunchKernelGGL(k_probe_sample<32>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); break;
-            case 33: if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<33>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); else hipLaunchKernelGGL(k_probe_sample<33>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); break;
-            case 34: if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<34>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); else hipLaunchKernelGGL(k_probe_sample<34>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); break;
-            case 35: if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<35>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); else hipLaunchKernelGGL(k_probe_sample<35>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); break;
-            case 40: if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<40>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); else hipLaunchKernelGGL(k_probe_sample<40>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); break;
-            case 41: if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<41>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); else hipLaunchKernelGGL(k_probe_sample<41>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); break;
-            case 42: if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<42>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); else hipLaunchKernelGGL(k_probe_sample<42>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); break;
-            case 43: if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<43>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); else hipLaunchKernelGGL(k_probe_sample<43>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); break;
-            case 128: if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<128>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); else hipLaunchKernelGGL(k_probe_sample<128>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); break;
-            case 129: if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<129>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); else hipLaunchKernelGGL(k_probe_sample<129>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); break;
-            case 130: if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<130>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); else hipLaunchKernelGGL(k_probe_sample<130>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); break;
-            case 131: if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<131>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); else hipLaunchKernelGGL(k_probe_sample<131>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); break;
-            case 136: if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<136>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); else hipLaunchKernelGGL(k_probe_sample<136>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); break;
-            case 137: if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<137>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); else hipLaunchKernelGGL(k_probe_sample<137>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); break;
-            case 138: if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<138>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); else hipLaunchKernelGGL(k_probe_sample<138>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); break;
-            case 139: if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<139>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); else hipLaunchKernelGGL(k_probe_sample<139>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); break;
-            case 256: if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<256>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); else hipLaunchKernelGGL(k_probe_sample<256>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); break;
-            case 257: if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<257>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); else hipLaunchKernelGGL(k_probe_sample<257>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); break;
-            case 264: if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<264>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); else hipLaunchKernelGGL(k_probe_sample<264>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); break;
-            case 265: if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<265>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); else hipLaunchKernelGGL(k_probe_sample<265>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); break;
-            case 288: if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<288>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); else hipLaunchKernelGGL(k_probe_sample<288>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); break;
-            case 289: if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<289>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); else hipLaunchKernelGGL(k_probe_sample<289>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); break;
-            case 296: if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<296>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); else hipLaunchKernelGGL(k_probe_sample<296>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); break;
-            case 297: if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<297>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); else hipLaunchKernelGGL(k_probe_sample<297>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); break;
-            case 384: if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<384>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); else hipLaunchKernelGGL(k_probe_sample<384>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); break;
-            case 385: if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<385>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); else hipLaunchKernelGGL(k_probe_sample<385>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); break;
-            case 392: if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<392>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); else hipLaunchKernelGGL(k_probe_sample<392>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); break;
-            case 393: if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<393>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); else hipLaunchKernelGGL(k_probe_sample<393>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); break;
-#define PROBE_CASE(v, _) case v: if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<v>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); \
-                             else hipLaunchKernelGGL(k_probe_sample<v>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n); break;
-            VPT_NORM16_VARIANTS(PROBE_CASE, 0)
-#undef PROBE_CASE
-            default: hipFree(din); hipFree(dout); return fail(VPT_ERR_INVALID, "no probe kernel for variant %d", variant_of(r));
-        }
+        const bool launched = dispatch_sampler_variant(variant_of(r), [&](auto V) {
+            if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<V()>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n);
+            else hipLaunchKernelGGL(k_probe_sample<V()>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n);
+            return true;
+        }, [] { return false; });
+        if (!launched) { hipFree(din); hipFree(dout); return fail(VPT_ERR_INVALID, "no probe kernel for variant %d", variant_of(r)); }
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpyAsync(rgba, dout, n * sizeof(float4), hipMemcpyDeviceToHost, c->stream);

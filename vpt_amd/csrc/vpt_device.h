@@ -15,6 +15,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "vpt_variants.h"
 
 #define VPT_DEV __device__ __forceinline__
 
@@ -341,19 +342,7 @@ VPT_DEV const uint8_t *cell_addr(const DevVolume &v, const LdsTables &t, uint32_
     }
     return v.bricks + (uint32_t)(t.tx[x] + t.ty[y] + t.tz[z]);
 }
-// V: variant bits fixed at launch — bit 0 = 64-bit offset tables (WIDE), bit 1 = NEAREST filter.  No run-time branch
-// inside the sampler: consecutive samples of a ray stay straight-line code, so their loads are issued together.
-#define VPT_V_WIDE    1
-#define VPT_V_NEAREST 2
-#define VPT_V_ALIGNED 4   // fetch the two tap windows as dword-aligned 12-byte loads + v_alignbyte (texture-path bound kernels)
-#define VPT_V_FAST    16  // MCM / MCS: hardware rcp / rsq / sqrt / log / sin / cos and shorter algebraic forms (no bit-exact CPU twin; VPT_OPTION_FAST_MATH)
-#define VPT_V_F32     32  // FLOAT texels (R32F; R16F widened on upload): 5^3 floats in a 512-byte slot, no normalisation
-#define VPT_V_RG      8   // two-channel (RG8) volume: texture(uVolume, p).rg has both channels, the transfer function is looked up in 2-D
-#define VPT_V_REC     64  // in-cube samples from the column records instead of the bricks (one-channel byte volumes, LINEAR filter; MCM)
-#define VPT_V_SNORM   128 // BYTE texels (R8_SNORM / RG8_SNORM): bricks as R8 / RG8, each tap decoded to fl32(c / 127) and filtered as R32F
-#define VPT_V_QCUBIC  256 // quasi-cubic filter (VPT_FILTER_QUASI_CUBIC): the LINEAR cell and taps, smoothstep weights (qc_weight); never with NEAREST / REC
-#define VPT_V_NORM16  512 // 16-bit normalised texels (R16 / RG16; | VPT_V_SNORM: R16_SNORM / RG16_SNORM): 5^3 words in a 256-byte slot (RG: the G
-                          // brick 256 bytes behind), each tap decoded (norm16_decode) and filtered as R32F
+// V: the variant bits fixed at launch (VPT_V_*): vpt_variants.h
 // The quasi-cubic weight of a LINEAR cell's fraction f: f' = (f * f) * (3 - 2 f), every operation rounded (the library is built with
 // -ffp-contract=off; 2 f is exact, so even a fused 3 - 2 f would be the same float).  f = 0 -> 0 and f = 1 -> 1 exactly, so every
 // clamped case of linear_cell keeps its exact edge value.  With the cell i = floor(u) and f = fract(u) of u = s N - 0.5 this is the

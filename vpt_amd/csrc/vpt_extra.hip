@@ -11,14 +11,13 @@
 #ifndef VPT_DOS_TAPS
 #define VPT_DOS_TAPS VPT_V_ALIGNED     // (the DOS sweep: 2.144 -> 2.107 ms; MCS, whose samples are not coherent: 16.2 -> 16.2, stays unaligned)
 #endif
-#define K_ISO0(V) (k_iso<0, V | VPT_EXTRA_TAPS>)
-#define K_ISO1(V) (k_iso<1, V | VPT_EXTRA_TAPS>)
-#define K_ISOR(V) (k_iso_render<V>)
-#define K_DEPTH0(V) (k_depth<0, V | VPT_EXTRA_TAPS>)
-#define K_DEPTH1(V) (k_depth<1, V | VPT_EXTRA_TAPS>)
+constexpr int extra_taps(int) { return VPT_EXTRA_TAPS; }
 // (16-bit volumes: LAO takes the unaligned 16-byte loads — the realigned words cost it a wave per SIMD, 142 against 110 VGPRs)
-#define K_LAO0(V) (k_lao<0, V | (((V) & VPT_V_NORM16) ? 0 : VPT_EXTRA_TAPS)>)
-#define K_LAO1(V) (k_lao<1, V | (((V) & VPT_V_NORM16) ? 0 : VPT_EXTRA_TAPS)>)
+constexpr int lao_taps(int v) { return (v & VPT_V_NORM16) ? 0 : VPT_EXTRA_TAPS; }
+constexpr int dos_taps(int) { return VPT_DOS_TAPS; }
+template <int MODE> static int launch_iso(vpt_renderer *r, const PassArgs &a) { return launch_variant(r, a, [](auto V) { return k_iso<MODE, V() | extra_taps(V())>; }); }
+template <int MODE> static int launch_depth(vpt_renderer *r, const PassArgs &a) { return launch_variant(r, a, [](auto V) { return k_depth<MODE, V() | extra_taps(V())>; }); }
+template <int MODE> static int launch_lao(vpt_renderer *r, const PassArgs &a) { return launch_variant(r, a, [](auto V) { return k_lao<MODE, V() | lao_taps(V())>; }); }
 #define LAUNCH(kernel, r, a, lds) hipLaunchKernelGGL(kernel, tile_grid(r), dim3(VPT_BLOCK), (lds), (r)->ctx->stream, (a))
 
 int extra_reset(vpt_renderer *r, const PassArgs &a) {
@@ -32,12 +31,11 @@ int extra_reset(vpt_renderer *r, const PassArgs &a) {
 }
 int extra_generate(vpt_renderer *r, const PassArgs &a) {
     switch (r->kind) {
-        case VPT_RENDERER_ISO: LAUNCH_S(K_ISO0, r, a); break;
-        case VPT_RENDERER_DEPTH: LAUNCH_S(K_DEPTH0, r, a); break;
-        case VPT_RENDERER_LAO: LAUNCH_S(K_LAO0, r, a); break;
-        default: break;                                                        // DOSRenderer.js has no _generateFrame
+        case VPT_RENDERER_ISO: return launch_iso<0>(r, a);
+        case VPT_RENDERER_DEPTH: return launch_depth<0>(r, a);
+        case VPT_RENDERER_LAO: return launch_lao<0>(r, a);
+        default: return VPT_OK;                                                // DOSRenderer.js has no _generateFrame
     }
-    return VPT_OK;
 }
 int extra_integrate(vpt_renderer *r, const PassArgs &a) {
     switch (r->kind) {
@@ -50,7 +48,7 @@ int extra_integrate(vpt_renderer *r, const PassArgs &a) {
 }
 int extra_render_frame(vpt_renderer *r, const PassArgs &a) {
     switch (r->kind) {
-        case VPT_RENDERER_ISO: LAUNCH_S(K_ISOR, r, a); break;
+        case VPT_RENDERER_ISO: return launch_variant(r, a, [](auto V) { return k_iso_render<V()>; });
         case VPT_RENDERER_DEPTH: LAUNCH(k_depth_render, r, a, 0); break;
         case VPT_RENDERER_LAO: LAUNCH(k_lao_render, r, a, 0); break;           // LAORenderer.glsl:259-261
         default: LAUNCH(k_dos_render, r, a, 0); break;
@@ -59,12 +57,11 @@ int extra_render_frame(vpt_renderer *r, const PassArgs &a) {
 }
 int extra_fused(vpt_renderer *r, const PassArgs &a) {
     switch (r->kind) {
-        case VPT_RENDERER_ISO: LAUNCH_S(K_ISO1, r, a); break;
-        case VPT_RENDERER_DEPTH: LAUNCH_S(K_DEPTH1, r, a); break;
-        case VPT_RENDERER_LAO: LAUNCH_S(K_LAO1, r, a); break;
+        case VPT_RENDERER_ISO: return launch_iso<1>(r, a);
+        case VPT_RENDERER_DEPTH: return launch_depth<1>(r, a);
+        case VPT_RENDERER_LAO: return launch_lao<1>(r, a);
         default: return fail(VPT_ERR_UNSUPPORTED, "the DOS renderer has no single-launch render()");
     }
-    return VPT_OK;
 }
 
 // uOcclusionSamples: the RG32F row of DOSRenderer.js:103-140
@@ -111,57 +108,17 @@ static void dos_tile_rect(const vpt_renderer *r, const float *mvp_inverse, int r
 }
 template <typename K>
 static int launch_dos_slice(K kernel, vpt_renderer *r, PassArgs &a, const int rect[4]) {
-    size_t lds = lds_bytes(r);
-    if (lds > 160 * 1024) return fail(VPT_ERR_UNSUPPORTED, "transfer function + volume tables need %zu B of LDS (> 160 KiB)", lds);
-    if (lds > 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const size_t lds = lds_bytes(r);
+    VPT_TRY(lds_prepare((const void *)kernel, lds));
     a.dos.tile_x0 = rect[0]; a.dos.tile_y0 = rect[1];
     hipLaunchKernelGGL(kernel, dim3((unsigned)(rect[2] - rect[0]), (unsigned)(rect[3] - rect[1])), dim3(VPT_BLOCK), lds, r->ctx->stream, a);
     return VPT_OK;
 }
 static int launch_dos(vpt_renderer *r, PassArgs &a, const int rect[4]) {
     if (rect[2] <= rect[0] || rect[3] <= rect[1]) return VPT_OK;
-    switch (variant_of(r)) {
-        case 0: return launch_dos_slice(k_dos_slice<0 | VPT_DOS_TAPS>, r, a, rect);
-        case 1: return launch_dos_slice(k_dos_slice<1 | VPT_DOS_TAPS>, r, a, rect);
-        case 2: return launch_dos_slice(k_dos_slice<2 | VPT_DOS_TAPS>, r, a, rect);
-        case 3: return launch_dos_slice(k_dos_slice<3 | VPT_DOS_TAPS>, r, a, rect);
-        case 8: return launch_dos_slice(k_dos_slice<8 | VPT_DOS_TAPS>, r, a, rect);
-        case 9: return launch_dos_slice(k_dos_slice<9 | VPT_DOS_TAPS>, r, a, rect);
-        case 10: return launch_dos_slice(k_dos_slice<10 | VPT_DOS_TAPS>, r, a, rect);
-        case 11: return launch_dos_slice(k_dos_slice<11 | VPT_DOS_TAPS>, r, a, rect);
-        case 32: return launch_dos_slice(k_dos_slice<32 | VPT_DOS_TAPS>, r, a, rect);
-        case 33: return launch_dos_slice(k_dos_slice<33 | VPT_DOS_TAPS>, r, a, rect);
-        case 34: return launch_dos_slice(k_dos_slice<34 | VPT_DOS_TAPS>, r, a, rect);
-        case 35: return launch_dos_slice(k_dos_slice<35 | VPT_DOS_TAPS>, r, a, rect);
-        case 40: return launch_dos_slice(k_dos_slice<40 | VPT_DOS_TAPS>, r, a, rect);
-        case 41: return launch_dos_slice(k_dos_slice<41 | VPT_DOS_TAPS>, r, a, rect);
-        case 42: return launch_dos_slice(k_dos_slice<42 | VPT_DOS_TAPS>, r, a, rect);
-        case 43: return launch_dos_slice(k_dos_slice<43 | VPT_DOS_TAPS>, r, a, rect);
-        case 128: return launch_dos_slice(k_dos_slice<128 | VPT_DOS_TAPS>, r, a, rect);
-        case 129: return launch_dos_slice(k_dos_slice<129 | VPT_DOS_TAPS>, r, a, rect);
-        case 130: return launch_dos_slice(k_dos_slice<130 | VPT_DOS_TAPS>, r, a, rect);
-        case 131: return launch_dos_slice(k_dos_slice<131 | VPT_DOS_TAPS>, r, a, rect);
-        case 136: return launch_dos_slice(k_dos_slice<136 | VPT_DOS_TAPS>, r, a, rect);
-        case 137: return launch_dos_slice(k_dos_slice<137 | VPT_DOS_TAPS>, r, a, rect);
-        case 138: return launch_dos_slice(k_dos_slice<138 | VPT_DOS_TAPS>, r, a, rect);
-        case 139: return launch_dos_slice(k_dos_slice<139 | VPT_DOS_TAPS>, r, a, rect);
-        case 256: return launch_dos_slice(k_dos_slice<256 | VPT_DOS_TAPS>, r, a, rect);
-        case 257: return launch_dos_slice(k_dos_slice<257 | VPT_DOS_TAPS>, r, a, rect);
-        case 264: return launch_dos_slice(k_dos_slice<264 | VPT_DOS_TAPS>, r, a, rect);
-        case 265: return launch_dos_slice(k_dos_slice<265 | VPT_DOS_TAPS>, r, a, rect);
-        case 288: return launch_dos_slice(k_dos_slice<288 | VPT_DOS_TAPS>, r, a, rect);
-        case 289: return launch_dos_slice(k_dos_slice<289 | VPT_DOS_TAPS>, r, a, rect);
-        case 296: return launch_dos_slice(k_dos_slice<296 | VPT_DOS_TAPS>, r, a, rect);
-        case 297: return launch_dos_slice(k_dos_slice<297 | VPT_DOS_TAPS>, r, a, rect);
-        case 384: return launch_dos_slice(k_dos_slice<384 | VPT_DOS_TAPS>, r, a, rect);
-        case 385: return launch_dos_slice(k_dos_slice<385 | VPT_DOS_TAPS>, r, a, rect);
-        case 392: return launch_dos_slice(k_dos_slice<392 | VPT_DOS_TAPS>, r, a, rect);
-        case 393: return launch_dos_slice(k_dos_slice<393 | VPT_DOS_TAPS>, r, a, rect);
-#define DOS_CASE(v, _) case v: return launch_dos_slice(k_dos_slice<v | VPT_DOS_TAPS>, r, a, rect);
-        VPT_NORM16_VARIANTS(DOS_CASE, 0)
-#undef DOS_CASE
-        default: return fail(VPT_ERR_INVALID, "no DOS kernel for variant %d", variant_of(r));
-    }
+    const int v = variant_of(r);
+    return dispatch_sampler_variant(v, [&](auto V) { return launch_dos_slice(k_dos_slice<V() | dos_taps(V())>, r, a, rect); },
+                                    [&] { return fail(VPT_ERR_INVALID, "no DOS kernel for variant %d", v); });
 }
 // _integrateFrame of the DOS renderer (DOSRenderer.js:199-259): `count` full-screen passes, pass s with
 // (uOcclusionScale.x, uOcclusionScale.y, uDepth) = slices[3s .. 3s+2]; uSliceDistance = u->step_size, uExtinction = u->extinction

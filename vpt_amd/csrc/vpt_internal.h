@@ -2,7 +2,7 @@
 // error plumbing and the launch helpers.  Translation units (Makefile; built in parallel, linked into one library):
 //   vpt_core.hip    context, volume (upload, re-layout), renderer life cycle, tile classification, options, read-back, probes
 //   vpt_mcm.hip     the MCM passes (vpt_kernels_mcm.h): tile classes, bucket kernels, reset / render / materialise
-//   vpt_mcm_hit.hip the MCM integrate kernels of every variant (k_mcm_integrate*), handed to vpt_mcm.hip by variant (vpt_mcm_select.h)
+//   vpt_mcm_hit.hip the MCM integrate kernels of every variant (k_mcm_integrate*), handed to vpt_mcm.hip by variant (vpt_mcm_select.h, vpt_variants.h)
 //   vpt_mcm_seq.hip MCM frame sequences in one launch (k_mcm_multi, k_mcm_frames)
 //   vpt_march.hip   MIP, EAM, MCS passes (vpt_kernels_march.h)
 //   vpt_extra.hip   ISO, Depth, LAO, DOS passes (vpt_kernels_iso_depth.h)
@@ -10,6 +10,8 @@
 //   vpt_post.hip    what follows a frame: tone mappers, the RCCL frame gather
 //   vpt_volume_ops.hip  volume operations on the device: the gradient-magnitude channel, texel read-back, histograms
 //   vpt_volume_window.hip  the value-range window (window / level) of a one-channel volume, its range and its code histogram
+// vpt_variants.h (through vpt_device.h) holds the variant bits of the sampling kernels and the switch from a run-time variant to a template
+// argument; launch_variant below is its use for a renderer's sampling pass.
 // Nothing device-side crosses a translation unit: a kernel is compiled by the unit that names it (the three MCM units share one header).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -59,6 +61,7 @@ struct vpt_volume {
     int packed;            // packed source format (VPT_FORMAT_RGB565 ..; 0: none): uploads are decoded into RG32F storage (f32, 2 channels)
     int packed_bytes;      // bytes per packed source texel: 2 or 4
     int vox_bytes;         // bytes per voxel of the linear storage: channels * (f32 ? 4 : norm16 ? 2 : 1)
+    uint32_t slot_shift, elem_shift;   // log2 of a brick slot's bytes (two channels: both bricks) and of a stored channel's bytes (DevVolume)
     int filter;
     uint8_t *linear;       // nx*ny*nz*channels, the "texture storage" blocks are uploaded into
     uint8_t *bricks;       // apron bricks, Morton order
@@ -275,18 +278,40 @@ static inline PassArgs frame_args(const PassArgs &a, const FrameVar &v) {      /
     return f;
 }
 
-// the name of a VPT_FORMAT_* for messages
-static inline const char *format_name(int format) {
-    static const char *names[] = { "R8", "RG8", "R32F", "RG32F", "R8_SNORM", "RG8_SNORM", "RGB565", "RGBA4", "RGB5_A1", "RGB10_A2",
-                                   "R11F_G11F_B10F", "RGB9_E5", "R16", "RG16", "R16_SNORM", "RG16_SNORM" };
-    return (format >= 0 && format < (int)(sizeof(names) / sizeof(names[0]))) ? names[format] : "?";
+// what a VPT_FORMAT_* is, indexed by the format: the one place that knows (volume_create fills the vpt_volume fields from it)
+struct VolumeFormat {
+    const char *name;      // for messages
+    int channels;          // of the storage: 1 or 2 (packed formats: their r and g)
+    int bytes;             // per stored channel: 1, 2 (16-bit normalised) or 4 (FLOAT; packed formats are decoded into RG32F on upload)
+    bool is_signed;        // signed normalised texels (VPT_V_SNORM)
+    bool is_float;         // FLOAT storage (VPT_V_F32)
+    int packed_bytes;      // bytes per packed source word (k_decode_packed), 0: not a packed format
+};
+static const VolumeFormat VOLUME_FORMATS[] = {
+    { "R8", 1, 1, false, false, 0 },        { "RG8", 2, 1, false, false, 0 },            { "R32F", 1, 4, false, true, 0 },
+    { "RG32F", 2, 4, false, true, 0 },      { "R8_SNORM", 1, 1, true, false, 0 },        { "RG8_SNORM", 2, 1, true, false, 0 },
+    { "RGB565", 2, 4, false, true, 2 },     { "RGBA4", 2, 4, false, true, 2 },           { "RGB5_A1", 2, 4, false, true, 2 },
+    { "RGB10_A2", 2, 4, false, true, 4 },   { "R11F_G11F_B10F", 2, 4, false, true, 4 },  { "RGB9_E5", 2, 4, false, true, 4 },
+    { "R16", 1, 2, false, false, 0 },       { "RG16", 2, 2, false, false, 0 },           { "R16_SNORM", 1, 2, true, false, 0 },
+    { "RG16_SNORM", 2, 2, true, false, 0 },
+};
+static_assert(sizeof(VOLUME_FORMATS) / sizeof(VOLUME_FORMATS[0]) == VPT_FORMAT_RG16_SNORM + 1, "one row per VPT_FORMAT_*");
+static inline const VolumeFormat *volume_format(int format) {      // null: no such format
+    return (format >= 0 && format <= VPT_FORMAT_RG16_SNORM) ? &VOLUME_FORMATS[format] : nullptr;
 }
+static inline const char *format_name(int format) { return volume_format(format) ? volume_format(format)->name : "?"; }
 static inline bool is_march_kind(int k) { return k == VPT_RENDERER_MIP || k == VPT_RENDERER_EAM || k == VPT_RENDERER_MCS; }
 
 // dynamic LDS of the sampling kernels: transfer-function pairs + the three brick-offset tables
 static inline size_t lds_bytes(const vpt_renderer *r) {
     const vpt_volume *v = r->vol;
     return (size_t)r->tf_w * 2 * sizeof(float4) + (size_t)(v->nx + v->ny + v->nz) * 4;
+}
+// before a launch of `kernel` with `lds` bytes of dynamic LDS: more than a CU has cannot run, more than the default limit has to be asked for
+static inline int lds_prepare(const void *kernel, size_t lds) {
+    if (lds > 160 * 1024) return fail(VPT_ERR_UNSUPPORTED, "transfer function + volume tables need %zu B of LDS (> 160 KiB)", lds);
+    if (lds > 64 * 1024) HIP_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    return VPT_OK;
 }
 static inline dim3 tile_grid(const vpt_renderer *r) { return dim3((unsigned)(r->tiles_x + 7) / 8u * 8u, (unsigned)r->tiles_y); }
 // Ray-marching kernels (MIP, EAM, ISO, Depth, MCS) run as one-wave workgroups when 28 of their LDS images fit a CU: with
@@ -324,10 +349,9 @@ static inline int split_for(const vpt_renderer *r, int tiles) {
     return k;
 }
 template <typename K>
-static int launch_sampling(K kernel, vpt_renderer *r, const PassArgs &a, unsigned) {
-    size_t lds = lds_bytes(r);
-    if (lds > 160 * 1024) return fail(VPT_ERR_UNSUPPORTED, "transfer function + volume tables need %zu B of LDS (> 160 KiB)", lds);
-    if (lds > 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+static int launch_sampling(K kernel, vpt_renderer *r, const PassArgs &a) {
+    const size_t lds = lds_bytes(r);
+    VPT_TRY(lds_prepare((const void *)kernel, lds));
     // one-wave workgroups (the ray marchers when their LDS image is small): four times as many blocks along x, see map_pixel
     const bool wave = wave_blocks(r);
     const unsigned xmul = wave ? 4u : 1u;
@@ -380,56 +404,14 @@ static inline int variant_of(const vpt_renderer *r) {
 static inline bool unsigned_r8(const vpt_volume *v) { return v->channels == 1 && !v->f32 && !v->snorm && !v->norm16; }
 // ... with the LINEAR or NEAREST filter: the persistent forms (VPT_OPTION_*_PERSISTENT) have no quasi-cubic instantiation
 static inline bool persistent_volume(const vpt_volume *v) { return unsigned_r8(v) && v->filter != VPT_FILTER_QUASI_CUBIC; }
-// the variants of the 16-bit normalised volumes (VPT_V_NORM16, | VPT_V_SNORM): {LINEAR, NEAREST, QUASI_CUBIC} x {R, RG} x {32-bit, wide
-// tables}: X(v, ...) once per variant
-#define VPT_NORM16_VARIANTS(X, ...) \
-    X(512, __VA_ARGS__) X(513, __VA_ARGS__) X(514, __VA_ARGS__) X(515, __VA_ARGS__) X(520, __VA_ARGS__) X(521, __VA_ARGS__) X(522, __VA_ARGS__) \
-    X(523, __VA_ARGS__) X(768, __VA_ARGS__) X(769, __VA_ARGS__) X(776, __VA_ARGS__) X(777, __VA_ARGS__) \
-    X(640, __VA_ARGS__) X(641, __VA_ARGS__) X(642, __VA_ARGS__) X(643, __VA_ARGS__) X(648, __VA_ARGS__) X(649, __VA_ARGS__) X(650, __VA_ARGS__) \
-    X(651, __VA_ARGS__) X(896, __VA_ARGS__) X(897, __VA_ARGS__) X(904, __VA_ARGS__) X(905, __VA_ARGS__)
-#define LAUNCH_S_CASE(v, KT, r, a) case v: VPT_TRY(launch_sampling(KT(v), (r), (a), g_)); break;
-#define LAUNCH_S(KT, r, a) do { \
-    unsigned g_ = (unsigned)(r)->ntiles; \
-    switch (variant_of(r)) { \
-        case 0: VPT_TRY(launch_sampling(KT(0), (r), (a), g_)); break; \
-        case 1: VPT_TRY(launch_sampling(KT(1), (r), (a), g_)); break; \
-        case 2: VPT_TRY(launch_sampling(KT(2), (r), (a), g_)); break; \
-        case 3: VPT_TRY(launch_sampling(KT(3), (r), (a), g_)); break; \
-        case 8: VPT_TRY(launch_sampling(KT(8), (r), (a), g_)); break; \
-        case 9: VPT_TRY(launch_sampling(KT(9), (r), (a), g_)); break; \
-        case 10: VPT_TRY(launch_sampling(KT(10), (r), (a), g_)); break; \
-        case 11: VPT_TRY(launch_sampling(KT(11), (r), (a), g_)); break; \
-        case 32: VPT_TRY(launch_sampling(KT(32), (r), (a), g_)); break; \
-        case 33: VPT_TRY(launch_sampling(KT(33), (r), (a), g_)); break; \
-        case 34: VPT_TRY(launch_sampling(KT(34), (r), (a), g_)); break; \
-        case 35: VPT_TRY(launch_sampling(KT(35), (r), (a), g_)); break; \
-        case 40: VPT_TRY(launch_sampling(KT(40), (r), (a), g_)); break; \
-        case 41: VPT_TRY(launch_sampling(KT(41), (r), (a), g_)); break; \
-        case 42: VPT_TRY(launch_sampling(KT(42), (r), (a), g_)); break; \
-        case 43: VPT_TRY(launch_sampling(KT(43), (r), (a), g_)); break; \
-        case 128: VPT_TRY(launch_sampling(KT(128), (r), (a), g_)); break; \
-        case 129: VPT_TRY(launch_sampling(KT(129), (r), (a), g_)); break; \
-        case 130: VPT_TRY(launch_sampling(KT(130), (r), (a), g_)); break; \
-        case 131: VPT_TRY(launch_sampling(KT(131), (r), (a), g_)); break; \
-        case 136: VPT_TRY(launch_sampling(KT(136), (r), (a), g_)); break; \
-        case 137: VPT_TRY(launch_sampling(KT(137), (r), (a), g_)); break; \
-        case 138: VPT_TRY(launch_sampling(KT(138), (r), (a), g_)); break; \
-        case 139: VPT_TRY(launch_sampling(KT(139), (r), (a), g_)); break; \
-        case 256: VPT_TRY(launch_sampling(KT(256), (r), (a), g_)); break; \
-        case 257: VPT_TRY(launch_sampling(KT(257), (r), (a), g_)); break; \
-        case 264: VPT_TRY(launch_sampling(KT(264), (r), (a), g_)); break; \
-        case 265: VPT_TRY(launch_sampling(KT(265), (r), (a), g_)); break; \
-        case 288: VPT_TRY(launch_sampling(KT(288), (r), (a), g_)); break; \
-        case 289: VPT_TRY(launch_sampling(KT(289), (r), (a), g_)); break; \
-        case 296: VPT_TRY(launch_sampling(KT(296), (r), (a), g_)); break; \
-        case 297: VPT_TRY(launch_sampling(KT(297), (r), (a), g_)); break; \
-        case 384: VPT_TRY(launch_sampling(KT(384), (r), (a), g_)); break; \
-        case 385: VPT_TRY(launch_sampling(KT(385), (r), (a), g_)); break; \
-        case 392: VPT_TRY(launch_sampling(KT(392), (r), (a), g_)); break; \
-        case 393: VPT_TRY(launch_sampling(KT(393), (r), (a), g_)); break; \
-        VPT_NORM16_VARIANTS(LAUNCH_S_CASE, KT, r, a) \
-        default: return fail(VPT_ERR_INVALID, "no sampling kernel for variant %d", variant_of(r)); \
-    } } while (0)
+// a renderer's sampling pass through the instantiation of its volume's variant: kernel_of(std::integral_constant<int, V>) names the kernel,
+// adding what the kernel family wants on top of V (tap form, fast arithmetic)
+template <typename KernelOf>
+static int launch_variant(vpt_renderer *r, const PassArgs &a, KernelOf kernel_of) {
+    const int v = variant_of(r);
+    return dispatch_sampler_variant(v, [&](auto V) { return launch_sampling(kernel_of(V), r, a); },
+                                    [&] { return fail(VPT_ERR_INVALID, "no sampling kernel for variant %d", v); });
+}
 
 struct Timed {   // HIP events around the dominant kernel (or around one graph replay of `launches` of them)
     vpt_renderer *r; bool on; size_t idx;

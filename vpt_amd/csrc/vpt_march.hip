@@ -3,26 +3,23 @@
 #include "vpt_internal.h"
 #include "vpt_kernels_march.h"
 
-// (dword-aligned 12-byte taps + v_alignbyte for MIP / EAM — re-measured in round 3 on the HIT tiles only, 256^3 1080p: EAM 63.7 us
+// the tap form of each family, on top of the volume's variant v
+// (dword-aligned 12-byte taps + v_alignbyte, VPT_V_ALIGNED, for MIP / EAM — re-measured in round 3 on the HIT tiles only, 256^3 1080p: EAM 63.7 us
 // aligned against 72.3 unaligned on one stream, 52.1 / 63.3 on three; MIP 56.3 / 72.0, 45.1 / 64.1)
-#define K_MIP0(V) (k_mip<0, V | VPT_V_ALIGNED>)
-#define K_MIP1(V) (k_mip<1, V | VPT_V_ALIGNED>)
 // (16-bit volumes with brick-code tables: the unaligned 16-byte loads — the realigned words cost EAM a wave per SIMD there, 68 against 63 VGPRs)
-#define VPT_EAM_TAPS(V) ((((V) & VPT_V_NORM16) && ((V) & VPT_V_WIDE)) ? 0 : VPT_V_ALIGNED)
-#define K_EAM0(V) (k_eam<0, V | VPT_EAM_TAPS(V)>)
-#define K_EAM1(V) (k_eam<1, V | VPT_EAM_TAPS(V)>)
+constexpr int eam_taps(int v) { return ((v & VPT_V_NORM16) && (v & VPT_V_WIDE)) ? 0 : VPT_V_ALIGNED; }
 #ifndef VPT_MCS_TAPS
 #define VPT_MCS_TAPS 0
 #endif
-#define K_MCS0(V) (k_mcs<0, V | VPT_MCS_TAPS>)
-#define K_MCS1(V) (k_mcs<1, V | VPT_MCS_TAPS>)
+constexpr int mcs_taps(int) { return VPT_MCS_TAPS; }
+template <int MODE> static int launch_mip(vpt_renderer *r, const PassArgs &a) { return launch_variant(r, a, [](auto V) { return k_mip<MODE, V() | VPT_V_ALIGNED>; }); }
+template <int MODE> static int launch_eam(vpt_renderer *r, const PassArgs &a) { return launch_variant(r, a, [](auto V) { return k_eam<MODE, V() | eam_taps(V())>; }); }
 #define LAUNCH(kernel, r, a, lds) hipLaunchKernelGGL(kernel, tile_grid(r), dim3(VPT_BLOCK), (lds), (r)->ctx->stream, (a))
 
 template <typename K>
 static int launch_mcs_persist(K kernel, vpt_renderer *r, const PassArgs &a) {
-    size_t lds = lds_bytes(r);
-    if (lds > 160 * 1024) return fail(VPT_ERR_UNSUPPORTED, "transfer function + volume tables need %zu B of LDS (> 160 KiB)", lds);
-    if (lds > 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const size_t lds = lds_bytes(r);
+    VPT_TRY(lds_prepare((const void *)kernel, lds));
     const size_t counter_bytes = (size_t)VPT_WORK_SHARDS * VPT_WORK_STRIDE * sizeof(uint32_t);
     if (!r->work_counter) HIP_TRY(hipMalloc(&r->work_counter, counter_bytes));
     HIP_TRY(hipMemsetAsync(r->work_counter, 0, counter_bytes, r->ctx->stream));
@@ -32,15 +29,6 @@ static int launch_mcs_persist(K kernel, vpt_renderer *r, const PassArgs &a) {
     hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(VPT_BLOCK), lds, r->ctx->stream, a, r->work_counter, ntx8, ntiles8);
     return VPT_OK;
 }
-#define LAUNCH_MCS_PERSIST(MODE, r, a) do { \
-    int v_ = ((r)->vol->wide ? VPT_V_WIDE : 0) | ((r)->vol->filter == VPT_FILTER_NEAREST ? VPT_V_NEAREST : 0); \
-    switch (v_) { \
-        case 0: VPT_TRY(launch_mcs_persist((k_mcs_persist<MODE, 0>), (r), (a))); break; \
-        case 1: VPT_TRY(launch_mcs_persist((k_mcs_persist<MODE, 1>), (r), (a))); break; \
-        case 2: VPT_TRY(launch_mcs_persist((k_mcs_persist<MODE, 2>), (r), (a))); break; \
-        default: VPT_TRY(launch_mcs_persist((k_mcs_persist<MODE, 3>), (r), (a))); break; \
-    } } while (0)
-
 
 int march_reset(vpt_renderer *r, const PassArgs &a) {
     switch (r->kind) {
@@ -50,21 +38,20 @@ int march_reset(vpt_renderer *r, const PassArgs &a) {
     }
     return VPT_OK;
 }
-static int launch_mcs(vpt_renderer *r, const PassArgs &a, bool fused) {
-    if (r->mcs_persistent && persistent_volume(r->vol)) {       // (walks every tile)
-        if (fused) LAUNCH_MCS_PERSIST(1, r, a); else LAUNCH_MCS_PERSIST(0, r, a);
-        return VPT_OK;
+template <int MODE> static int launch_mcs(vpt_renderer *r, const PassArgs &a) {
+    if (r->mcs_persistent && persistent_volume(r->vol)) {       // (walks every tile; UNSIGNED_BYTE one-channel volumes, LINEAR or NEAREST)
+        const int v = (r->vol->wide ? VPT_V_WIDE : 0) | (r->vol->filter == VPT_FILTER_NEAREST ? VPT_V_NEAREST : 0);
+        return dispatch_variant<VPT_V_WIDE | VPT_V_NEAREST>(v, [&](auto V) { return launch_mcs_persist(k_mcs_persist<MODE, V()>, r, a); },
+                                                            [&] { return fail(VPT_ERR_INVALID, "no persistent MCS kernel for variant %d", v); });
     }
-    if (fused) LAUNCH_S(K_MCS1, r, a); else LAUNCH_S(K_MCS0, r, a);
-    return VPT_OK;
+    return launch_variant(r, a, [](auto V) { return k_mcs<MODE, V() | mcs_taps(V())>; });
 }
 int march_generate(vpt_renderer *r, const PassArgs &a) {                      // _generateFrame
     switch (r->kind) {
-        case VPT_RENDERER_MIP: LAUNCH_S(K_MIP0, r, a); break;
-        case VPT_RENDERER_EAM: LAUNCH_S(K_EAM0, r, a); break;
-        default: return launch_mcs(r, a, false);
+        case VPT_RENDERER_MIP: return launch_mip<0>(r, a);
+        case VPT_RENDERER_EAM: return launch_eam<0>(r, a);
+        default: return launch_mcs<0>(r, a);
     }
-    return VPT_OK;
 }
 int march_integrate(vpt_renderer *r, const PassArgs &a) {                     // _integrateFrame
     switch (r->kind) {
@@ -84,9 +71,8 @@ int march_render_frame(vpt_renderer *r, const PassArgs &a) {                  //
 }
 int march_fused(vpt_renderer *r, const PassArgs &a) {                         // render(): the three hooks in one launch
     switch (r->kind) {
-        case VPT_RENDERER_MIP: LAUNCH_S(K_MIP1, r, a); break;
-        case VPT_RENDERER_EAM: LAUNCH_S(K_EAM1, r, a); break;
-        default: return launch_mcs(r, a, true);
+        case VPT_RENDERER_MIP: return launch_mip<1>(r, a);
+        case VPT_RENDERER_EAM: return launch_eam<1>(r, a);
+        default: return launch_mcs<1>(r, a);
     }
-    return VPT_OK;
 }

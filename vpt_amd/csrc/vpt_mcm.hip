@@ -31,9 +31,10 @@ static bool mcm_classes_runnable(const vpt_renderer *r, const PassArgs &a) {
 }
 // ... and of the bucket kernels (and of the HIT-tile kernel's early form): LINEAR one-channel byte volumes
 static bool mcm_plain_volume(const vpt_renderer *r) { return (variant_of(r) & ~VPT_V_WIDE) == 0 && unsigned_r8(r->vol); }
+// NEAREST / two-channel / float volumes: the MISS tiles through the one-phase sampler of k_mcm_miss (miss_sample_any); v: those three bits
 template <bool FUSE> static PassKernel format_miss_kernel(int v, bool fast) {
-    if (fast) FORMAT_CASES((PassKernel)k_mcm_miss<FUSE, F | VPT_V_FAST, false, true>)
-    FORMAT_CASES((PassKernel)k_mcm_miss<FUSE, F, false, true>)
+    return dispatch_variant<VPT_V_NEAREST | VPT_V_RG | VPT_V_F32>(
+        v, [&](auto F) { return fast ? (PassKernel)k_mcm_miss<FUSE, F() | VPT_V_FAST, false, true> : (PassKernel)k_mcm_miss<FUSE, F(), false, true>; }, no_pass_kernel);
 }
 // position / transmittance of the MISS tiles, as the last pass's arithmetic would have stored them
 int mcm_materialize(vpt_renderer *r) {
@@ -82,8 +83,9 @@ static int launch_mcm_classes(vpt_renderer *r, const PassArgs &a) {
     // whose pass is one wave per SIMD walking a chain of dependent latencies; else the 7-waves form (VPT_HIT_KERNEL_FORM in the environment overrides)
     const bool plain = mcm_plain_volume(r);
     const bool early = plain && (r->hit_form == 2 || (r->hit_form == 0 && r->cls.n_hit <= 1280));
+    // (another volume format: the HIT tiles through the general kernel of the volume's variant, from a tile list)
     if (plain) kh = mcm_hit_kernel(FUSE, class_variant(r, a), early);
-    else kh = mcm_format_hit_kernel(FUSE, variant_of(r), (variant_of(r) & VPT_V_WIDE) != 0, fast);
+    else kh = mcm_general_kernel(FUSE, variant_of(r), fast);
     // the MISS tiles: the sample consumed after the path end (its gather flies under that arithmetic) — whole frame 80.8 -> 79.3-79.7 us
     // fast-math, 96.1 -> 92.8 bit-exact, rank 3 of 8's share 18.4 -> 17.1 bit-exact but 15.8 -> 16.9 fast-math: there the sample is
     // consumed where the shader takes it
@@ -96,15 +98,14 @@ static int launch_mcm_classes(vpt_renderer *r, const PassArgs &a) {
     // every gather stays inside that allocation and reads what the R32F twin's would (tests/test_gpu_norm16.py: 1080p classes, atlas on / off).
     int vm = variant_of(r) & ~VPT_V_QCUBIC;
     if (vm & VPT_V_NORM16) vm = (vm & ~(VPT_V_NORM16 | VPT_V_SNORM)) | VPT_V_F32;
-    if (vm & ~VPT_V_WIDE) km = format_miss_kernel<FUSE>(vm, fast);
+    if (vm & ~VPT_V_WIDE) km = format_miss_kernel<FUSE>(vm & ~VPT_V_WIDE, fast);
     else if (check) km = fast ? (late ? (PassKernel)k_mcm_miss<FUSE, VPT_V_FAST, true, true> : (PassKernel)k_mcm_miss<FUSE, VPT_V_FAST, true, false>)
                          : (PassKernel)k_mcm_miss<FUSE, 0, true, true>;
     else km = fast ? (late ? (PassKernel)k_mcm_miss<FUSE, VPT_V_FAST, false, true> : (PassKernel)k_mcm_miss<FUSE, VPT_V_FAST, false, false>)
                    : (PassKernel)k_mcm_miss<FUSE, 0, false, true>;
     if (!kh || !km) return fail(VPT_ERR_INVALID, "no MCM tile-class kernels for variant %d", variant_of(r));
     const size_t lds_hit = lds_bytes(r), lds_miss = (size_t)r->tf_w * 2 * sizeof(float4);
-    if (lds_hit > 160 * 1024) return fail(VPT_ERR_UNSUPPORTED, "transfer function + volume tables need %zu B of LDS (> 160 KiB)", lds_hit);
-    if (lds_hit > 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void *)kh, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_hit));
+    VPT_TRY(lds_prepare((const void *)kh, lds_hit));
     const int k = split_allowed(r) ? r->split : 1;
     struct Part { PassKernel kernel; const uint32_t *list; int n; size_t lds; };
     Part parts[VPT_MAX_SPLIT]; int np = 0;
@@ -171,8 +172,9 @@ int mcm_bucket_ready(vpt_renderer *r, const PassArgs &a, bool *ready) {
     return VPT_OK;
 }
 template <bool DISPLAY> static BucketKernel bucket_hit_kernel(int v, bool early) {
-    if (early) VARIANT_CASES((BucketKernel)k_mcm_bucket_hit<V, true, DISPLAY>)
-    VARIANT_CASES((BucketKernel)k_mcm_bucket_hit<V, false, DISPLAY>)
+    return dispatch_variant<VPT_V_CLASS_BITS>(
+        v, [&](auto V) { return early ? (BucketKernel)k_mcm_bucket_hit<V(), true, DISPLAY> : (BucketKernel)k_mcm_bucket_hit<V(), false, DISPLAY>; },
+        [] { return (BucketKernel)nullptr; });
 }
 template <bool DISPLAY>
 static void bucket_kernels(int v, bool early, BucketKernel *kh, BucketKernel *km) {
@@ -194,8 +196,7 @@ int mcm_bucket(vpt_renderer *r, const PassArgs &a, const FrameVar *v, int count,
     else bucket_kernels<false>(class_variant(r, a), early, &kh, &km);
     if (!kh || !km) return fail(VPT_ERR_INVALID, "no MCM tile-class kernels for variant %d", variant_of(r));
     const size_t lds_hit = lds_bytes(r), lds_miss = (size_t)r->tf_w * 2 * sizeof(float4);
-    if (lds_hit > 160 * 1024) return fail(VPT_ERR_UNSUPPORTED, "transfer function + volume tables need %zu B of LDS (> 160 KiB)", lds_hit);
-    if (lds_hit > 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void *)kh, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_hit));
+    VPT_TRY(lds_prepare((const void *)kh, lds_hit));
     VPT_TRY(streams_deal(r, Deal{ DEAL_LISTS, 2 }));
     FrameSeeds fs;
     for (int f = 0; f < VPT_BUCKET_FRAMES; f++) fs.seed[f] = f < count ? v[f].seed : 0.0f;
@@ -219,9 +220,8 @@ int mcm_bucket(vpt_renderer *r, const PassArgs &a, const FrameVar *v, int count,
 // persistent MCM: as many workgroups as are resident at once (occupancy query x CUs), never more than there are segments
 template <typename K>
 static int launch_mcm_persist(K kernel, vpt_renderer *r, const PassArgs &a) {
-    size_t lds = lds_bytes(r);
-    if (lds > 160 * 1024) return fail(VPT_ERR_UNSUPPORTED, "transfer function + volume tables need %zu B of LDS (> 160 KiB)", lds);
-    if (lds > 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const size_t lds = lds_bytes(r);
+    VPT_TRY(lds_prepare((const void *)kernel, lds));
     int per_cu = 0;
     HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, VPT_BLOCK, lds));
     if (per_cu < 1) per_cu = 1;

@@ -237,15 +237,11 @@ __global__ __launch_bounds__(256) void k_code_histogram(const void *__restrict__
 // hosts
 // ---------------------------------------------------------------------------------------------
 // the texel kind of a one-channel source, or -1
-static int source_kind(const vpt_volume *v) {
-    switch (v->format) {
-        case VPT_FORMAT_R8: return SRC_U8;
-        case VPT_FORMAT_R16: return SRC_U16;
-        case VPT_FORMAT_R8_SNORM: return SRC_S8;
-        case VPT_FORMAT_R16_SNORM: return SRC_S16;
-        case VPT_FORMAT_R32F: return SRC_F32;
-        default: return -1;
-    }
+static int source_kind(const vpt_volume *v) {                   // -1: not a one-channel volume
+    const VolumeFormat *f = volume_format(v->format);
+    if (!f || f->channels != 1) return -1;
+    if (f->is_float) return SRC_F32;
+    return f->bytes == 2 ? (f->is_signed ? SRC_S16 : SRC_U16) : (f->is_signed ? SRC_S8 : SRC_U8);
 }
 static inline size_t voxels(const vpt_volume *v) { return (size_t)v->nx * v->ny * v->nz; }
 static inline unsigned stream_grid(size_t steps, unsigned cap) { return (unsigned)std::max<size_t>(1, std::min<size_t>((steps + 255) / 256, cap)); }
