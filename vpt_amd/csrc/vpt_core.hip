@@ -3,6 +3,7 @@
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt
 //        -fno-gpu-flush-denormals-to-zero -fPIC (see vpt_amd/csrc/Makefile)
 #include <chrono>
+#include <memory>
 #include "vpt_internal.h"
 #include "vpt_kernels_layout.h"
 #include "vpt_srgb_lut.h"
@@ -78,14 +79,35 @@ extern "C" int vpt_context_synchronize(vpt_context *c) {
 extern "C" int vpt_volume_create(vpt_context *c, int w, int h, int d, int format, vpt_volume **out) {
     return volume_create(c, w, h, d, format, true, out);
 }
+// Z-order over two or three axes with exactly as many bits per axis as the axis needs: the low bits of the coordinates interleave
+// (x lowest, as the classic Morton code), and once an axis runs out of bits the longer axes continue alone — a cube gets the classic
+// code, 4096 x 2 x 3 bricks 2^10 slots instead of 2^30.  The code of a cell is the OR of its coordinates' code(axis, i).
+struct ZOrder {
+    int nbits[3] = { 0, 0, 0 }, bitpos[3][16];
+    ZOrder(int naxes, const int *sizes) {
+        for (int ax = 0; ax < naxes; ax++) while ((1 << nbits[ax]) < sizes[ax]) nbits[ax]++;
+        int total_bits = 0;
+        for (int level = 0; level < 16; level++)
+            for (int ax = 0; ax < naxes; ax++) if (level < nbits[ax]) bitpos[ax][level] = total_bits++;
+    }
+    uint64_t code(int ax, uint32_t i) const {
+        uint64_t c = 0;
+        for (int k = 0; k < nbits[ax]; k++) c |= (uint64_t)((i >> k) & 1u) << bitpos[ax][k];
+        return c;
+    }
+};
+static int upload_words(DevBuf<uint32_t> &dst, const std::vector<uint32_t> &host) {
+    HIP_TRY(dst.alloc(host.size()));
+    HIP_TRY(hipMemcpy(dst, host.data(), host.size() * 4, hipMemcpyHostToDevice));
+    return VPT_OK;
+}
 int volume_create(vpt_context *c, int w, int h, int d, int format, bool zero_fill, vpt_volume **out) {
     if (!c || !out) return fail(VPT_ERR_INVALID, "null argument");
     if (format < VPT_FORMAT_R8 || format > VPT_FORMAT_RG16_SNORM) return fail(VPT_ERR_UNSUPPORTED, "Unknown volume datatype: %d", format);  // Volume.js:103
     if (w < 1 || h < 1 || d < 1 || w > 4096 || h > 4096 || d > 4096)
         return fail(VPT_ERR_INVALID, "volume dimensions %dx%dx%d out of range [1,4096]", w, h, d);
     HIP_TRY(hipSetDevice(c->device));
-    vpt_volume *v = new vpt_volume();
-    memset(v, 0, sizeof(*v));
+    std::unique_ptr<vpt_volume> v(new vpt_volume());          // an early return frees what has been built so far
     v->ctx = c; v->nx = w; v->ny = h; v->nz = d; v->format = format;
     const VolumeFormat &f = *volume_format(format);
     // packed formats (VPT_FORMAT_RGB565 ..): the words are decoded on upload (k_decode_packed) into an RG32F volume
@@ -103,80 +125,63 @@ int volume_create(vpt_context *c, int w, int h, int d, int format, bool zero_fil
     v->elem_shift = f.bytes == 4 ? 2u : (f.bytes == 2 ? 1u : 0u);
     v->slot_shift = 7u + v->elem_shift + (v->channels == 2 ? 1u : 0u);
     const uint32_t slot_shift = v->slot_shift;
-    v->filter = VPT_FILTER_LINEAR;                       // Volume.js:53-54
-    int nbx = (w + 3) / 4, nby = (h + 3) / 4, nbz = (d + 3) / 4;
-    // Z-order over the bricks with exactly as many bits per axis as the axis needs: the low bits of x, y, z interleave
-    // (x lowest, as the classic Morton code), and once an axis runs out of bits the longer axes continue alone — a cube
-    // gets the classic code, a 4096 x 2 x 3 volume 2^10 slots instead of 2^30.  code(bx,by,bz) = CX[bx] | CY[by] | CZ[bz].
-    int nbits[3] = { 0, 0, 0 };
-    { int nb[3] = { nbx, nby, nbz }; for (int ax = 0; ax < 3; ax++) while ((1 << nbits[ax]) < nb[ax]) nbits[ax]++; }
-    int bitpos[3][16]; int total_bits = 0;
-    for (int level = 0; level < 16; level++)
-        for (int ax = 0; ax < 3; ax++) if (level < nbits[ax]) bitpos[ax][level] = total_bits++;
-    auto axis_code = [&](int ax, uint32_t b) { uint64_t c = 0; for (int k = 0; k < nbits[ax]; k++) c |= (uint64_t)((b >> k) & 1u) << bitpos[ax][k]; return c; };
-    size_t max_slot = (size_t)(axis_code(0, (uint32_t)nbx - 1) | axis_code(1, (uint32_t)nby - 1) | axis_code(2, (uint32_t)nbz - 1));
+    const int nb[3] = { (w + 3) / 4, (h + 3) / 4, (d + 3) / 4 };
+    const ZOrder bricks(3, nb);                           // code(bx,by,bz) = CX[bx] | CY[by] | CZ[bz]
+    size_t max_slot = (size_t)(bricks.code(0, (uint32_t)nb[0] - 1) | bricks.code(1, (uint32_t)nb[1] - 1) | bricks.code(2, (uint32_t)nb[2] - 1));
     v->brick_bytes = (max_slot + 1) << slot_shift;
-    hipError_t e = hipMalloc(&v->linear, (size_t)w * h * d * v->vox_bytes);
-    if (e == hipSuccess) e = hipMalloc(&v->bricks, v->brick_bytes + 64);   // +64: the 8-byte tap windows end <= byte 125+7
-    if (e == hipSuccess) {
-        // boundary atlas: six face images (axis x: ny x nz cells, y: nx x nz, z: nx x ny; low side, high side) with one common
-        // power-of-two row pitch and one common size, one dword (byte volumes) or one float4 (float volumes; 16-bit volumes: the decoded
-        // texels, always finite) per cell and channel
-        int pitch = 1, shift = 0;
-        while (pitch < std::max(w, h)) { pitch <<= 1; shift++; }
-        v->atlas_shift = (uint32_t)shift;
-        v->atlas_face = (uint32_t)pitch * (uint32_t)std::max(h, d);
-        v->atlas_dwords = 6 * (size_t)v->atlas_face * (size_t)v->channels * ((v->f32 || v->norm16) ? 4 : 1);
-        e = hipMalloc(&v->atlas, v->atlas_dwords * 4);
-        v->atlas_ok = true;
-        if (e == hipSuccess && v->f32) e = hipMalloc(&v->atlas_flag, sizeof(uint32_t));
-    }
-    if (e != hipSuccess) {
-        if (v->atlas) hipFree(v->atlas);
-        if (v->bricks) hipFree(v->bricks);
-        if (v->linear) hipFree(v->linear);
-        delete v;
-        return fail(VPT_ERR_HIP, "hipMalloc volume %dx%dx%d: %s", w, h, d, hipGetErrorString(e));
-    }
+    // boundary atlas: six face images (axis x: ny x nz cells, y: nx x nz, z: nx x ny; low side, high side) with one common
+    // power-of-two row pitch and one common size, one dword (byte volumes) or one float4 (float volumes; 16-bit volumes: the decoded
+    // texels, always finite) per cell and channel
+    int pitch = 1, shift = 0;
+    while (pitch < std::max(w, h)) { pitch <<= 1; shift++; }
+    v->atlas_shift = (uint32_t)shift;
+    v->atlas_face = (uint32_t)pitch * (uint32_t)std::max(h, d);
+    v->atlas_dwords = 6 * (size_t)v->atlas_face * (size_t)v->channels * ((v->f32 || v->norm16) ? 4 : 1);
+    hipError_t e = v->linear.alloc((size_t)w * h * d * v->vox_bytes);
+    if (e == hipSuccess) e = v->bricks.alloc(v->brick_bytes + 64);   // +64: the 8-byte tap windows end <= byte 125+7
+    if (e == hipSuccess) e = v->atlas.alloc(v->atlas_dwords);
+    if (e == hipSuccess && v->f32) e = v->atlas_flag.alloc(1);
+    if (e != hipSuccess) return fail(VPT_ERR_HIP, "memory for a volume of %dx%dx%d: %s", w, h, d, hipGetErrorString(e));
     if (zero_fill) HIP_TRY(hipMemsetAsync(v->linear, 0, (size_t)w * h * d * v->vox_bytes, c->stream));   // texStorage3D zero-initialises
     {   // offset tables: off(x,y,z) = TX[x] + TY[y] + TZ[z]
         std::vector<uint64_t> t64((size_t)w + h + d);
-        std::vector<uint32_t> t32(t64.size());
-        for (int i = 0; i < w; i++) t64[i] = (axis_code(0, (uint32_t)i >> 2) << slot_shift) + (uint64_t)(i & 3) * eb;
-        for (int i = 0; i < h; i++) t64[(size_t)w + i] = (axis_code(1, (uint32_t)i >> 2) << slot_shift) + (uint64_t)(i & 3) * 5 * eb;
-        for (int i = 0; i < d; i++) t64[(size_t)w + h + i] = (axis_code(2, (uint32_t)i >> 2) << slot_shift) + (uint64_t)(i & 3) * 25 * eb;
-        for (size_t i = 0; i < t64.size(); i++) t32[i] = (uint32_t)t64[i];
-        for (size_t i = 0; i < t64.size(); i++) t64[i] >>= slot_shift;     // the brick's Morton code alone (WIDE variant)
-        std::vector<uint32_t> tc(t64.size());
-        for (size_t i = 0; i < t64.size(); i++) tc[i] = (uint32_t)t64[i];
+        std::vector<uint32_t> t32(t64.size()), tc(t64.size());
+        for (int i = 0; i < w; i++) t64[i] = (bricks.code(0, (uint32_t)i >> 2) << slot_shift) + (uint64_t)(i & 3) * eb;
+        for (int i = 0; i < h; i++) t64[(size_t)w + i] = (bricks.code(1, (uint32_t)i >> 2) << slot_shift) + (uint64_t)(i & 3) * 5 * eb;
+        for (int i = 0; i < d; i++) t64[(size_t)w + h + i] = (bricks.code(2, (uint32_t)i >> 2) << slot_shift) + (uint64_t)(i & 3) * 25 * eb;
+        for (size_t i = 0; i < t64.size(); i++) { t32[i] = (uint32_t)t64[i]; tc[i] = (uint32_t)(t64[i] >> slot_shift); }   // tc: the brick's Morton code alone (WIDE variant)
         v->wide = v->brick_bytes > 0xffffffffull;
-        HIP_TRY(hipMalloc(&v->tab32, t32.size() * 4));
-        HIP_TRY(hipMalloc(&v->tabc, tc.size() * 4));
-        HIP_TRY(hipMemcpy(v->tab32, t32.data(), t32.size() * 4, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(v->tabc, tc.data(), tc.size() * 4, hipMemcpyHostToDevice));
+        VPT_TRY(upload_words(v->tab32, t32));
+        VPT_TRY(upload_words(v->tabc, tc));
     }
-    if (unsigned_r8(v)) {
-        // column records: 2-D Z-order over (x, y) with as many bits per axis as the axis needs, nz records of 4 bytes per column
-        int cb[2] = { 0, 0 };
-        while ((1 << cb[0]) < w) cb[0]++;
-        while ((1 << cb[1]) < h) cb[1]++;
-        int cpos[2][16]; int ctotal = 0;
-        for (int level = 0; level < 16; level++)
-            for (int ax = 0; ax < 2; ax++) if (level < cb[ax]) cpos[ax][level] = ctotal++;
-        auto col_code = [&](int ax, uint32_t i) { uint64_t c = 0; for (int k = 0; k < cb[ax]; k++) c |= (uint64_t)((i >> k) & 1u) << cpos[ax][k]; return c; };
-        const uint64_t ncols = (col_code(0, (uint32_t)w - 1) | col_code(1, (uint32_t)h - 1)) + 1, col_bytes = 4ull * (uint64_t)d;
+    if (unsigned_r8(v.get())) {
+        // column records: 2-D Z-order over (x, y), nz records of 4 bytes per column
+        const int nc[2] = { w, h };
+        const ZOrder cols(2, nc);
+        const uint64_t ncols = (cols.code(0, (uint32_t)w - 1) | cols.code(1, (uint32_t)h - 1)) + 1, col_bytes = 4ull * (uint64_t)d;
         v->rec_bytes = (size_t)(ncols * col_bytes);
         v->rec_wide = ncols * col_bytes > 0x100000000ull;          // (the largest offset used is rec_bytes - 4)
         std::vector<uint32_t> r32((size_t)w + h), rc((size_t)w + h);
-        for (int i = 0; i < w; i++) { rc[i] = (uint32_t)col_code(0, (uint32_t)i); r32[i] = (uint32_t)(col_code(0, (uint32_t)i) * col_bytes); }
-        for (int i = 0; i < h; i++) { rc[(size_t)w + i] = (uint32_t)col_code(1, (uint32_t)i); r32[(size_t)w + i] = (uint32_t)(col_code(1, (uint32_t)i) * col_bytes); }
-        HIP_TRY(hipMalloc(&v->rtab32, r32.size() * 4));
-        HIP_TRY(hipMalloc(&v->rtabc, rc.size() * 4));
-        HIP_TRY(hipMemcpy(v->rtab32, r32.data(), r32.size() * 4, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(v->rtabc, rc.data(), rc.size() * 4, hipMemcpyHostToDevice));
+        for (int i = 0; i < w; i++) { rc[i] = (uint32_t)cols.code(0, (uint32_t)i); r32[i] = (uint32_t)(cols.code(0, (uint32_t)i) * col_bytes); }
+        for (int i = 0; i < h; i++) { rc[(size_t)w + i] = (uint32_t)cols.code(1, (uint32_t)i); r32[(size_t)w + i] = (uint32_t)(cols.code(1, (uint32_t)i) * col_bytes); }
+        VPT_TRY(upload_words(v->rtab32, r32));
+        VPT_TRY(upload_words(v->rtabc, rc));
     }
-    v->dirty = true;
-    *out = v;
+    *out = v.release();
+    return VPT_OK;
+}
+// what vpt_volume_derive_gradient and vpt_volume_window end with: the derived volume `d`, whose texels the caller's kernels have just
+// written, becomes a finalized volume of src's filter and is handed out; on an error it is destroyed
+int volume_finish_derived(const vpt_volume *src, vpt_volume *d, vpt_volume **out) {
+    vpt_context *c = src->ctx;
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { vpt_volume_destroy(d); return fail(VPT_ERR_HIP, "derived volume, kernel launch: %s", hipGetErrorString(e)); }
+    d->filter = src->filter;
+    d->dirty = true; d->any_upload = true;
+    int rc = vpt_volume_finalize(d);
+    if (rc != VPT_OK) { vpt_volume_destroy(d); return rc; }
+    for (vpt_renderer *r : c->renderers) r->streams.mark_dirty();      // side streams of split passes fork behind the build
+    *out = d;
     return VPT_OK;
 }
 // The column records (vpt_device.h record_addr) of a one-channel byte volume, (re)built from the linear storage when blocks have been
@@ -187,7 +192,7 @@ int volume_records(vpt_volume *v) {
     if (v->rec_valid) return VPT_OK;
     vpt_context *c = v->ctx;
     HIP_TRY(hipSetDevice(c->device));
-    if (!v->records) HIP_TRY(hipMalloc(&v->records, v->rec_bytes + 64));      // + the dword behind the last column's last record
+    if (!v->records) HIP_TRY(v->records.alloc(v->rec_bytes + 64));      // + the dword behind the last column's last record
     for (vpt_renderer *r : c->renderers) if (r->vol == v) VPT_TRY(join_side(r));   // passes in flight read the old records
     hipLaunchKernelGGL(k_build_records, dim3((unsigned)((v->nx + 63) / 64), (unsigned)v->ny, (unsigned)((v->nz + 15) / 16)), dim3(256), 0, c->stream,
                        v->linear, v->records, v->nx, v->ny, v->nz, v->rec_wide ? v->rtabc : v->rtab32, v->rec_wide ? 1 : 0);
@@ -213,17 +218,13 @@ static int volume_upload(vpt_volume *v, int x, int y, int z, int w, int h, int d
     } else {
         const uint8_t *src = (const uint8_t *)data;
         if (!on_device) {
-            if (v->staging_bytes < need) {
-                if (v->staging) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(v->staging)); v->staging = nullptr; }
-                HIP_TRY(hipMalloc(&v->staging, need));
-                v->staging_bytes = need;
-            }
+            HIP_TRY(v->staging.reserve(need, c->stream));
             HIP_TRY(hipMemcpyAsync(v->staging, data, need, hipMemcpyHostToDevice, c->stream));
             src = v->staging;
         }
         int grid = (int)((texels + 255) / 256); if (grid > 4096) grid = 4096;
         if (v->packed)   // the (r, g) floats of each word at the block's place in the RG32F storage
-            hipLaunchKernelGGL(k_decode_packed, dim3(grid), dim3(256), 0, c->stream, (float2 *)v->linear, v->nx, v->ny, src, v->packed, x, y, z, w, h, d);
+            hipLaunchKernelGGL(k_decode_packed, dim3(grid), dim3(256), 0, c->stream, (float2 *)v->linear.get(), v->nx, v->ny, src, v->packed, x, y, z, w, h, d);
         else
             hipLaunchKernelGGL(k_blit_block, dim3(grid), dim3(256), 0, c->stream, v->linear, v->nx, v->ny, src, x, y, z, w, h, d, v->vox_bytes);
         HIP_TRY(hipGetLastError());
@@ -249,16 +250,16 @@ extern "C" int vpt_volume_finalize(vpt_volume *v) {
     if (v->snorm) {   // R8_SNORM / RG8_SNORM: -128 reads as -1 = -127 / 127 (GL ES 3.0 2.1.6.1); clamped once, before bricks and atlas
         const size_t n = (size_t)v->nx * v->ny * v->nz * v->channels;
         int grid = (int)((n / 4 + 255) / 256); if (grid > 4096) grid = 4096; if (grid < 1) grid = 1;
-        if (v->norm16) hipLaunchKernelGGL(k_snorm16_clamp, dim3(grid), dim3(256), 0, c->stream, (uint16_t *)v->linear, n);   // (R16_SNORM: -32768)
+        if (v->norm16) hipLaunchKernelGGL(k_snorm16_clamp, dim3(grid), dim3(256), 0, c->stream, (uint16_t *)v->linear.get(), n);   // (R16_SNORM: -32768)
         else hipLaunchKernelGGL(k_snorm_clamp, dim3(grid), dim3(256), 0, c->stream, v->linear, n);
     }
     // one-channel volumes with dword-aligned rows go through the LDS-staged kernel (dword loads and stores)
     int fast = (v->channels == 1 && v->nx % 4 == 0) ? strips : 0;
     if (v->norm16) {
-        hipLaunchKernelGGL(k_brickify_16, dim3((unsigned)strips, (unsigned)nby, (unsigned)nbz), dim3(128), 0, c->stream, (const uint16_t *)v->linear, (uint16_t *)v->bricks, v->nx, v->ny, v->nz, v->channels, v->tabc);
+        hipLaunchKernelGGL(k_brickify_16, dim3((unsigned)strips, (unsigned)nby, (unsigned)nbz), dim3(128), 0, c->stream, (const uint16_t *)v->linear.get(), (uint16_t *)v->bricks.get(), v->nx, v->ny, v->nz, v->channels, v->tabc);
         fast = strips;
     } else if (v->f32) {
-        hipLaunchKernelGGL(k_brickify_f32, dim3((unsigned)strips, (unsigned)nby, (unsigned)nbz), dim3(128), 0, c->stream, (const float *)v->linear, (float *)v->bricks, v->nx, v->ny, v->nz, v->channels, v->tabc);
+        hipLaunchKernelGGL(k_brickify_f32, dim3((unsigned)strips, (unsigned)nby, (unsigned)nbz), dim3(128), 0, c->stream, (const float *)v->linear.get(), (float *)v->bricks.get(), v->nx, v->ny, v->nz, v->channels, v->tabc);
         fast = strips;                                    // nothing left for the byte kernels
     } else if (fast > 0)
         hipLaunchKernelGGL(k_brickify_strip, dim3((unsigned)fast, (unsigned)((nby + VPT_BRICKIFY_ROWS - 1) / VPT_BRICKIFY_ROWS), (unsigned)((nbz + VPT_BRICKIFY_ROWS - 1) / VPT_BRICKIFY_ROWS)), dim3(256), 0, c->stream, v->linear, v->bricks, v->nx, v->ny, v->nz, v->tabc);
@@ -267,23 +268,23 @@ extern "C" int vpt_volume_finalize(vpt_volume *v) {
     if (v->atlas) {
         size_t cells = (size_t)v->ny * v->nz + (size_t)v->nx * v->nz + (size_t)v->nx * v->ny;
         if (v->f32) {
-            hipLaunchKernelGGL(k_build_atlas<float>, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, c->stream, (const float *)v->linear, (void *)v->atlas,
+            hipLaunchKernelGGL(k_build_atlas<float>, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, c->stream, (const float *)v->linear.get(), (void *)v->atlas,
                                v->nx, v->ny, v->nz, v->channels, v->atlas_face, v->atlas_shift);
             // (float texels: the atlas stands for the bricks only while every texel is finite and differences cannot overflow — one scan, one
             // host wait per upload of a float volume)
             uint32_t bad = 0;
             HIP_TRY(hipMemsetAsync(v->atlas_flag, 0, sizeof(uint32_t), c->stream));
-            hipLaunchKernelGGL(k_scan_finite, dim3(2048), dim3(256), 0, c->stream, (const float *)v->linear, (size_t)v->nx * v->ny * v->nz * v->channels, v->atlas_flag);
+            hipLaunchKernelGGL(k_scan_finite, dim3(2048), dim3(256), 0, c->stream, (const float *)v->linear.get(), (size_t)v->nx * v->ny * v->nz * v->channels, v->atlas_flag);
             HIP_TRY(hipMemcpyAsync(&bad, v->atlas_flag, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
             HIP_TRY(hipStreamSynchronize(c->stream));
             v->atlas_ok = bad == 0;
         } else if (v->norm16) {   // the decoded texels, the floats the sampler blends: finite, so the atlas is always in use
-            if (v->snorm) hipLaunchKernelGGL(k_build_atlas<int16_t>, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, c->stream, (const int16_t *)v->linear, (void *)v->atlas,
+            if (v->snorm) hipLaunchKernelGGL(k_build_atlas<int16_t>, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, c->stream, (const int16_t *)v->linear.get(), (void *)v->atlas,
                                              v->nx, v->ny, v->nz, v->channels, v->atlas_face, v->atlas_shift);
-            else hipLaunchKernelGGL(k_build_atlas<uint16_t>, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, c->stream, (const uint16_t *)v->linear, (void *)v->atlas,
+            else hipLaunchKernelGGL(k_build_atlas<uint16_t>, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, c->stream, (const uint16_t *)v->linear.get(), (void *)v->atlas,
                                     v->nx, v->ny, v->nz, v->channels, v->atlas_face, v->atlas_shift);
         } else {
-            hipLaunchKernelGGL(k_build_atlas<uint8_t>, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, c->stream, (const uint8_t *)v->linear, (void *)v->atlas,
+            hipLaunchKernelGGL(k_build_atlas<uint8_t>, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, c->stream, (const uint8_t *)v->linear.get(), (void *)v->atlas,
                                v->nx, v->ny, v->nz, v->channels, v->atlas_face, v->atlas_shift);
         }
     }
@@ -317,16 +318,6 @@ extern "C" int vpt_volume_destroy(vpt_volume *v) {
     for (vpt_renderer *r : v->ctx->renderers) if (r->vol == v) join_side(r);
     hipStreamSynchronize(v->ctx->stream);
     renderers_unbind(v->ctx, v);              // a renderer still bound to it reports "no ready volume" instead of reading freed memory
-    if (v->linear) hipFree(v->linear);
-    if (v->bricks) hipFree(v->bricks);
-    if (v->atlas) hipFree(v->atlas);
-    if (v->atlas_flag) hipFree(v->atlas_flag);
-    if (v->records) hipFree(v->records);
-    if (v->rtab32) hipFree(v->rtab32);
-    if (v->rtabc) hipFree(v->rtabc);
-    if (v->staging) hipFree(v->staging);
-    if (v->tab32) hipFree(v->tab32);
-    if (v->tabc) hipFree(v->tabc);
     delete v;
     return VPT_OK;
 }
@@ -334,28 +325,17 @@ extern "C" int vpt_volume_destroy(vpt_volume *v) {
 // ---------------------------------------------------------------------------------------------
 // renderer
 // ---------------------------------------------------------------------------------------------
-static void renderer_free_buffers(vpt_renderer *r) {
-    if (r->frame) hipFree(r->frame);
-    if (r->acc) hipFree(r->acc);
-    for (int i = 0; i < 4; i++) if (r->st[i]) hipFree(r->st[i]);
-    if (r->render) hipFree(r->render);
-    if (r->scratch) hipFree(r->scratch);
-    if (r->ndc_x) hipFree(r->ndc_x);
-    if (r->ndc_y) hipFree(r->ndc_y);
-    r->ndc_x = r->ndc_y = nullptr;
-    r->frame = r->acc = nullptr; r->render = nullptr; r->scratch = nullptr; r->scratch_bytes = 0;
-    for (int i = 0; i < 4; i++) r->st[i] = nullptr;
-}
 // _rebuildBuffers: AbstractRenderer.js:78-92 (+ the per-renderer buffer specs)
 static int renderer_alloc_buffers(vpt_renderer *r) {
     vpt_context *c = r->ctx;
     if (r->play_graph) { hipStreamSynchronize(c->stream); play_graph_free(r->play_graph); r->play_graph = nullptr; }
     r->render_target = nullptr; r->target_is_callers = false;   // an external target was sized for the old geometry
     r->tm_owner = nullptr; r->tm_valid = false; r->tm_mode = 0;  // a fused tone mapper's output was sized for it too: it re-arms itself
-    if (r->frame_ring) { hipFree(r->frame_ring); r->frame_ring = nullptr; } r->ring_frames = 0;
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    renderer_free_buffers(r);
+    r->frame_ring.reset(); r->ring_frames = 0;
+    r->frame.reset(); r->acc.reset(); r->render.reset(); r->scratch.reset(); r->ndc_x.reset(); r->ndc_y.reset();
+    for (int i = 0; i < 4; i++) r->st[i].reset();
     r->cls.valid = false; r->cls.stale = false;            // new geometry, zeroed state: classes come back with the next reset
     r->cls.built = false;
     r->cls.passes = 0; r->cls.fused_passes = 0; r->cls.reset_seen = false; r->cls.n_complete = 0;   // (zeroed buffers are not a reset: nothing is skipped before one)
@@ -378,8 +358,8 @@ static int renderer_alloc_buffers(vpt_renderer *r) {
     r->valid_pixels = valid;
     size_t fe = frame_elem(r->kind);
     if (fe) {
-        HIP_TRY(hipMalloc(&r->frame, r->npix_padded * fe));
-        HIP_TRY(hipMalloc(&r->acc, r->npix_padded * fe));
+        HIP_TRY(r->frame.alloc(r->npix_padded * fe));
+        HIP_TRY(r->acc.alloc(r->npix_padded * fe));
         HIP_TRY(hipMemsetAsync(r->frame, 0, r->npix_padded * fe, c->stream));
         HIP_TRY(hipMemsetAsync(r->acc, 0, r->npix_padded * fe, c->stream));
     } else {
@@ -387,7 +367,7 @@ static int renderer_alloc_buffers(vpt_renderer *r) {
             // MCM: position (0) and transmittance (2) are 12-byte texels — their fourth float is a constant 0 in the reference's
             // attachments (MCMRenderer.glsl:168,170) and is not stored; DOS keeps float4 / float arrays in the same slots
             size_t texel = (r->kind == VPT_RENDERER_MCM && (i == 0 || i == 2)) ? 3 * sizeof(float) : sizeof(float4);
-            HIP_TRY(hipMalloc(&r->st[i], r->npix_padded * texel));
+            HIP_TRY(r->st[i].alloc(r->npix_padded * texel / sizeof(float4)));    // (npix_padded is a multiple of 256)
             HIP_TRY(hipMemsetAsync(r->st[i], 0, r->npix_padded * texel, c->stream));
         }
     }
@@ -395,22 +375,21 @@ static int renderer_alloc_buffers(vpt_renderer *r) {
         std::vector<float> nx((size_t)r->W), ny((size_t)r->H);
         for (int i = 0; i < r->W; i++) nx[i] = (float)(2 * i + 1) / (float)r->W - 1.0f;
         for (int j = 0; j < r->H; j++) ny[j] = (float)(2 * j + 1) / (float)r->H - 1.0f;
-        HIP_TRY(hipMalloc(&r->ndc_x, nx.size() * sizeof(float)));
-        HIP_TRY(hipMalloc(&r->ndc_y, ny.size() * sizeof(float)));
+        HIP_TRY(r->ndc_x.alloc(nx.size()));
+        HIP_TRY(r->ndc_y.alloc(ny.size()));
         HIP_TRY(hipMemcpy(r->ndc_x, nx.data(), nx.size() * sizeof(float), hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(r->ndc_y, ny.data(), ny.size() * sizeof(float), hipMemcpyHostToDevice));
     }
     size_t rb = (size_t)r->W * r->local_h * sizeof(uint2);
-    HIP_TRY(hipMalloc(&r->render, rb));
+    HIP_TRY(r->render.alloc((size_t)r->W * r->local_h));
     HIP_TRY(hipMemsetAsync(r->render, 0, rb, c->stream));
     return VPT_OK;
 }
-static int upload_table(vpt_context *c, float4 **dst, const std::vector<float4> &host) {
+static int upload_table(vpt_context *c, DevBuf<float4> &dst, const std::vector<float4> &host) {
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (*dst) { HIP_TRY(hipFree(*dst)); *dst = nullptr; }
-    HIP_TRY(hipMalloc(dst, host.size() * sizeof(float4)));
-    HIP_TRY(hipMemcpy(*dst, host.data(), host.size() * sizeof(float4), hipMemcpyHostToDevice));
+    HIP_TRY(dst.alloc(host.size()));
+    HIP_TRY(hipMemcpy(dst, host.data(), host.size() * sizeof(float4), hipMemcpyHostToDevice));
     return VPT_OK;
 }
 extern "C" int vpt_renderer_set_transfer_function(vpt_renderer *r, const uint8_t *rgba, int w, int h) {
@@ -422,7 +401,7 @@ extern "C" int vpt_renderer_set_transfer_function(vpt_renderer *r, const uint8_t
     for (size_t i = 0; i < t.size(); i++)
         t[i] = make_float4(VPT_SRGB_TO_LINEAR[rgba[4 * i]], VPT_SRGB_TO_LINEAR[rgba[4 * i + 1]],
                            VPT_SRGB_TO_LINEAR[rgba[4 * i + 2]], (float)rgba[4 * i + 3] / 255.0f);
-    VPT_TRY(upload_table(r->ctx, &r->tf, t));
+    VPT_TRY(upload_table(r->ctx, r->tf, t));
     r->tf_w = w; r->tf_h = h;
     return VPT_OK;
 }
@@ -434,7 +413,7 @@ extern "C" int vpt_renderer_set_environment(vpt_renderer *r, const uint8_t *rgba
     for (size_t i = 0; i < t.size(); i++)
         t[i] = make_float4((float)rgba[4 * i] / 255.0f, (float)rgba[4 * i + 1] / 255.0f,
                            (float)rgba[4 * i + 2] / 255.0f, (float)rgba[4 * i + 3] / 255.0f);
-    VPT_TRY(upload_table(r->ctx, &r->env, t));
+    VPT_TRY(upload_table(r->ctx, r->env, t));
     r->env_w = w; r->env_h = h; r->env_const = t[0];
     r->env_opaque = true;
     for (size_t i = 0; i < t.size(); i++) if (rgba[4 * i + 3] != 255) { r->env_opaque = false; break; }
@@ -464,25 +443,18 @@ extern "C" int vpt_renderer_set_environment_texels(vpt_renderer *r, const void *
     HIP_TRY(hipSetDevice(c->device));
     static const size_t texel_bytes[] = { 4, 8, 16, 4 };
     const size_t n = (size_t)w * h, nbytes = n * texel_bytes[format];
-    if (!r->env || (size_t)r->env_w * r->env_h != n) {       // (a table of the same size is overwritten in stream order)
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        if (r->env) { HIP_TRY(hipFree(r->env)); r->env = nullptr; r->env_w = r->env_h = 0; }
-        HIP_TRY(hipMalloc(&r->env, n * sizeof(float4)));
-    }
+    if (r->env.capacity() < n) r->env_w = r->env_h = 0;      // (should the allocation fail, the renderer holds no map)
+    HIP_TRY(r->env.reserve(n, c->stream));                   // (a table that is large enough is overwritten in stream order)
     r->env_w = w; r->env_h = h;
-    uint8_t *staging = nullptr;
-    HIP_TRY(hipMalloc(&staging, nbytes));
-    hipError_t e = hipMemcpyAsync(staging, texels, nbytes, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) {
-        int grid = (int)((n + 255) / 256); if (grid > 8192) grid = 8192;
-        hipLaunchKernelGGL(k_env_decode, dim3(grid), dim3(256), 0, c->stream, r->env, (const uint8_t *)staging, n, format);
-        e = hipGetLastError();
-    }
+    DevBuf<uint8_t> staging;
+    HIP_TRY(staging.alloc(nbytes));
+    HIP_TRY(hipMemcpyAsync(staging, texels, nbytes, hipMemcpyHostToDevice, c->stream));
+    int grid = (int)((n + 255) / 256); if (grid > 8192) grid = 8192;
+    hipLaunchKernelGGL(k_env_decode, dim3(grid), dim3(256), 0, c->stream, r->env.get(), (const uint8_t *)staging.get(), n, format);
+    HIP_TRY(hipGetLastError());
     float4 first = make_float4(0.0f, 0.0f, 0.0f, 0.0f);       // env_const: the decoded texel of a 1x1 map, read back (one decoder)
-    if (e == hipSuccess) e = hipMemcpyAsync(&first, r->env, sizeof(float4), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // (the caller's buffer may be released on return)
-    hipFree(staging);
-    if (e != hipSuccess) return fail(VPT_ERR_HIP, "environment upload: %s", hipGetErrorString(e));
+    HIP_TRY(hipMemcpyAsync(&first, r->env, sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));                // (the caller's buffer may be released on return; the staging buffer goes with this scope)
     r->env_const = first;
     r->env_opaque = env_texels_opaque(texels, n, format);
     r->cls.poisoned = true;                                  // (as vpt_renderer_set_environment)
@@ -509,36 +481,20 @@ extern "C" int vpt_renderer_create(vpt_context *c, int kind, int width, int heig
     if (kind < VPT_RENDERER_MIP || kind > VPT_RENDERER_DOS) return fail(VPT_ERR_INVALID, "No suitable class");  // RendererFactory.js:21
     if (width < 1 || height < 1 || width > 32768 || height > 32768) return fail(VPT_ERR_INVALID, "resolution %dx%d out of range", width, height);
     HIP_TRY(hipSetDevice(c->device));
-    vpt_renderer *r = new vpt_renderer();
+    std::unique_ptr<vpt_renderer, int (*)(vpt_renderer *)> owner(new vpt_renderer(), vpt_renderer_destroy);   // an early return destroys what has been built
+    vpt_renderer *r = owner.get();
     r->ctx = c; r->kind = kind; r->W = width; r->H = height;
     c->renderers.push_back(r);
-    r->G = 1; r->g = 0; r->R = 8;
-    r->vol = nullptr; r->tf = nullptr; r->env = nullptr;
-    r->frame = r->acc = nullptr; r->render = nullptr; r->scratch = nullptr; r->scratch_bytes = 0;
-    for (int i = 0; i < 4; i++) r->st[i] = nullptr;
-    r->samples = nullptr; r->samples_host = 0; r->profiling = false; r->events_used = 0; r->profile_every = 1; r->profile_seq = 0;
-    r->side_events_used = 0; r->timed_now = false;
-    r->ndc_x = r->ndc_y = nullptr;
-    r->frame_table = nullptr; r->frame_staging = nullptr; r->frames_played = 0;
-    r->warmed = false; r->play_graph = nullptr;
-    r->fast_math = 0; r->boundary_atlas = 1; r->column_records = 2;
-    r->frame_ring = nullptr; r->ring_frames = 0; r->split = default_split(kind); r->split_auto = true; r->target_is_callers = false; r->no_split = false; r->bucket_call = false; r->stop_events = nullptr; r->stop_used = false; r->mcm_persistent = 0; r->work_counter = nullptr; r->mcs_persistent = false;   // measured slower than k_mcs at every extinction tried
-    r->render_target = nullptr;
-    memset(&r->cls, 0, sizeof(r->cls)); r->cls.enabled = true; { const char *e = getenv("VPT_HIT_KERNEL_FORM"); r->hit_form = (e && (e[0] == '1' || e[0] == '2') && !e[1]) ? e[0] - '0' : 0; } r->bucket_kernel = false; r->bucket_launches = 0;
-    r->tm_owner = nullptr; r->tm_valid = false; r->tm_table = nullptr; r->tm_out = nullptr; r->tm_mode = 0;
-    r->lao = LaoParams{ 1, 0.69f, 1, 0.05f, 1, 0.54f, 10, 0.19f, 1.0f, { 2.0f, 12.0f, 3.0f } };
-    int rc = renderer_alloc_buffers(r);
-    if (rc == VPT_OK) {
-        hipError_t e = hipMalloc(&r->samples, COUNTER_BYTES);
-        if (e == hipSuccess) e = hipMemsetAsync(r->samples, 0, COUNTER_BYTES, c->stream);
-        if (e != hipSuccess) rc = fail(VPT_ERR_HIP, "hipMalloc counter: %s", hipGetErrorString(e));
-    }
+    r->split = default_split(kind);
+    { const char *e = getenv("VPT_HIT_KERNEL_FORM"); r->hit_form = (e && (e[0] == '1' || e[0] == '2') && !e[1]) ? e[0] - '0' : 0; }
+    VPT_TRY(renderer_alloc_buffers(r));
+    HIP_TRY(r->samples.alloc(COUNTER_BYTES / sizeof(unsigned long long)));
+    HIP_TRY(hipMemsetAsync(r->samples, 0, COUNTER_BYTES, c->stream));
     static const uint8_t default_tf[8] = { 255, 0, 0, 0, 255, 0, 0, 255 };   // AbstractRenderer.js:31-44
     static const uint8_t default_env[4] = { 255, 255, 255, 255 };            // RenderingContext.js:90-101
-    if (rc == VPT_OK) rc = vpt_renderer_set_transfer_function(r, default_tf, 2, 1);
-    if (rc == VPT_OK) rc = vpt_renderer_set_environment(r, default_env, 1, 1);
-    if (rc != VPT_OK) { vpt_renderer_destroy(r); return rc; }
-    *out = r;
+    VPT_TRY(vpt_renderer_set_transfer_function(r, default_tf, 2, 1));
+    VPT_TRY(vpt_renderer_set_environment(r, default_env, 1, 1));
+    *out = owner.release();
     return VPT_OK;
 }
 extern "C" int vpt_renderer_destroy(vpt_renderer *r) {
@@ -549,23 +505,12 @@ extern "C" int vpt_renderer_destroy(vpt_renderer *r) {
     tonemappers_unbind(r->ctx, r);            // a tone mapper still bound to this renderer falls back to the white placeholder
     for (size_t i = 0; i < r->ctx->renderers.size(); i++)
         if (r->ctx->renderers[i] == r) { r->ctx->renderers.erase(r->ctx->renderers.begin() + (long)i); break; }
-    renderer_free_buffers(r);                 // renderer-owned buffers only; volume is NOT owned (Volume.js:17-22)
-    if (r->tf) hipFree(r->tf);
-    if (r->env) hipFree(r->env);
-    if (r->samples) hipFree(r->samples);
-    if (r->dos_samples) hipFree(r->dos_samples);
-    if (r->work_counter) hipFree(r->work_counter);
-    if (r->cls.list) hipFree(r->cls.list);
-    if (r->cls.violations) hipFree(r->cls.violations);
-    for (int i = 0; i < 2; i++) { if (r->cls.staging[i]) hipHostFree(r->cls.staging[i]); if (r->cls.staged[i]) hipEventDestroy(r->cls.staged[i]); }
-    if (r->frame_ring) hipFree(r->frame_ring);
-    if (r->frame_table) hipFree(r->frame_table);
-    if (r->frame_staging) hipHostFree(r->frame_staging);
+    for (int i = 0; i < 2; i++) if (r->cls.staged[i]) hipEventDestroy(r->cls.staged[i]);
     destroy_split_streams(r);
     if (r->play_graph) play_graph_free(r->play_graph);
     for (auto &ev : r->events) { hipEventDestroy(ev.first); hipEventDestroy(ev.second); }
     for (auto &ev : r->side_events) { hipEventDestroy(ev.first); hipEventDestroy(ev.second); }
-    delete r;
+    delete r;                                 // the renderer's buffers go with it; the volume is NOT owned (Volume.js:17-22)
     return VPT_OK;
 }
 extern "C" int vpt_renderer_set_shard(vpt_renderer *r, int rank, int world, int rows_per_block) {
@@ -808,7 +753,7 @@ __global__ void k_probe_wait(uint32_t *flag, uint32_t *seen, unsigned long long 
 }
 __global__ void k_probe_raise(uint32_t *flag) { __hip_atomic_store(flag, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM); }
 static bool streams_overlap(hipStream_t a, hipStream_t b) {
-    static uint32_t *words = nullptr;                                // [0] flag, [1] seen: pinned, kept for the life of the process
+    static uint32_t *words = nullptr;                                // [0] flag, [1] seen: pinned, kept for the life of the process, hence a bare pointer: never freed
     if (!words && hipHostMalloc((void **)&words, 2 * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess) { words = nullptr; (void)hipGetLastError(); return true; }
     bool seen = false;
     for (int round = 0; round < 2 && !seen; round++) {               // (round 0 also pays for the code object's first use on these queues)
@@ -904,12 +849,7 @@ int classes_build(vpt_renderer *r, const float *mvp_inverse) {
     if (tx != r->tiles_x || ty != r->tiles_y || tx > 0xffff || ty > 0xffff) return VPT_OK;
     const int n = (int)cls.size(), s = c.stage_next;
     HIP_TRY(hipSetDevice(r->ctx->device));
-    if (c.staging_capacity[s] < n) {
-        if (c.staged[s]) HIP_TRY(hipEventSynchronize(c.staged[s]));
-        if (c.staging[s]) { HIP_TRY(hipHostFree(c.staging[s])); c.staging[s] = nullptr; }
-        HIP_TRY(hipHostMalloc((void **)&c.staging[s], (size_t)n * sizeof(uint32_t), hipHostMallocDefault));
-        c.staging_capacity[s] = n;
-    }
+    HIP_TRY(c.staging[s].reserve((size_t)n, r->ctx->stream));   // (the copies out of it travel on that stream)
     if (!c.staged[s]) HIP_TRY(hipEventCreateWithFlags(&c.staged[s], hipEventDisableTiming));
     else HIP_TRY(hipEventSynchronize(c.staged[s]));            // the copy out of this buffer two builds ago: long done (no wait in practice)
     uint32_t *list = c.staging[s];
@@ -918,14 +858,9 @@ int classes_build(vpt_renderer *r, const float *mvp_inverse) {
         for (int y = 0; y < ty; y++) for (int x = 0; x < tx; x++)
             if ((int)cls[(size_t)y * tx + x] == pass) { list[(size_t)nh + nm] = (uint32_t)x | ((uint32_t)y << 16); (pass ? nm : nh)++; }
     VPT_TRY(join_side(r));                                      // passes in flight read the old lists
-    if (c.capacity < n) {
-        HIP_TRY(hipStreamSynchronize(r->ctx->stream));
-        if (c.list) { HIP_TRY(hipFree(c.list)); c.list = nullptr; }
-        HIP_TRY(hipMalloc(&c.list, (size_t)n * sizeof(uint32_t)));
-        c.capacity = n;
-    }
+    HIP_TRY(c.list.reserve((size_t)n, r->ctx->stream));
     if (!c.violations) {       // [0]: VPT_OPTION_VERIFY_TILE_CLASSES
-        HIP_TRY(hipMalloc(&c.violations, 16 * sizeof(unsigned long long)));
+        HIP_TRY(c.violations.alloc(16));
         HIP_TRY(hipMemsetAsync(c.violations, 0, 16 * sizeof(unsigned long long), r->ctx->stream));
     }
     // (the lists travel on the context's stream, behind the passes that read the old ones; the side streams pick them up at the next fork)
@@ -976,17 +911,13 @@ extern "C" int vpt_renderer_read(vpt_renderer *r, int buffer, void *dst, size_t 
         return fail(VPT_ERR_INVALID, "unknown buffer %d", buffer);
     }
     if (nbytes < npix * elem) return fail(VPT_ERR_INVALID, "destination too small: %zu < %zu", nbytes, npix * elem);
-    if (r->scratch_bytes < npix * elem) {
-        if (r->scratch) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(r->scratch)); r->scratch = nullptr; }
-        HIP_TRY(hipMalloc(&r->scratch, npix * elem));
-        r->scratch_bytes = npix * elem;
-    }
+    HIP_TRY(r->scratch.reserve(npix * elem, c->stream));
     PassArgs a;
     VPT_TRY(make_args(r, nullptr, false, &a));
     if (r->kind == VPT_RENDERER_MCM && (buffer == VPT_BUFFER_MCM_POSITION || buffer == VPT_BUFFER_MCM_TRANSMITTANCE))
-        hipLaunchKernelGGL(k_detile_mcm3, tile_grid(r), dim3(VPT_BLOCK), 0, c->stream, a.pm, (const f3 *)src, (float4 *)r->scratch);
+        hipLaunchKernelGGL(k_detile_mcm3, tile_grid(r), dim3(VPT_BLOCK), 0, c->stream, a.pm, (const f3 *)src, (float4 *)r->scratch.get());
     else
-    hipLaunchKernelGGL(k_detile, tile_grid(r), dim3(VPT_BLOCK), 0, c->stream, a.pm, (const uint8_t *)src, (uint8_t *)r->scratch, (int)elem);
+    hipLaunchKernelGGL(k_detile, tile_grid(r), dim3(VPT_BLOCK), 0, c->stream, a.pm, (const uint8_t *)src, (uint8_t *)r->scratch.get(), (int)elem);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(dst, r->scratch, npix * elem, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -999,7 +930,7 @@ extern "C" int vpt_renderer_read_frame_slot(vpt_renderer *r, int slot, void *dst
     if (nbytes < need) return fail(VPT_ERR_INVALID, "buffer too small: %zu < %zu", nbytes, need);
     VPT_TRY(join_side(r));
     HIP_TRY(hipSetDevice(r->ctx->device));
-    HIP_TRY(hipMemcpyAsync(dst, (const char *)r->frame_ring + (size_t)slot * need, need, hipMemcpyDeviceToHost, r->ctx->stream));
+    HIP_TRY(hipMemcpyAsync(dst, (const char *)r->frame_ring.get() + (size_t)slot * need, need, hipMemcpyDeviceToHost, r->ctx->stream));
     HIP_TRY(hipStreamSynchronize(r->ctx->stream));
     return VPT_OK;
 }
@@ -1166,19 +1097,14 @@ extern "C" int vpt_probe_math(vpt_context *c, int which, const float *in, float 
     if (n == 0) return VPT_OK;
     HIP_TRY(hipSetDevice(c->device));
     size_t nin = (which == VPT_PROBE_ATAN2 || which == VPT_PROBE_MIN || which == VPT_PROBE_MAX || which == VPT_PROBE_POW) ? 2 * n : n;
-    float *din = nullptr, *dout = nullptr;
-    HIP_TRY(hipMalloc(&din, nin * sizeof(float)));
-    hipError_t e = hipMalloc(&dout, n * sizeof(float));
-    if (e != hipSuccess) { hipFree(din); return fail(VPT_ERR_HIP, "hipMalloc: %s", hipGetErrorString(e)); }
-    e = hipMemcpyAsync(din, in, nin * sizeof(float), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_probe_math, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, which, din, dout, n);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(out, dout, n * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    hipFree(din); hipFree(dout);
-    if (e != hipSuccess) return fail(VPT_ERR_HIP, "probe: %s", hipGetErrorString(e));
+    DevBuf<float> din, dout;
+    HIP_TRY(din.alloc(nin));
+    HIP_TRY(dout.alloc(n));
+    HIP_TRY(hipMemcpyAsync(din, in, nin * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_probe_math, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, which, din.get(), dout.get(), n);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, dout, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return VPT_OK;
 }
 static int probe_sample(vpt_renderer *r, const float *xyz, float *rgba, size_t n, bool boundary) {
@@ -1189,25 +1115,20 @@ static int probe_sample(vpt_renderer *r, const float *xyz, float *rgba, size_t n
     PassArgs a;
     VPT_TRY(make_args(r, nullptr, true, &a));
     if (boundary && !a.vol.atlas) return fail(VPT_ERR_UNSUPPORTED, "the volume's boundary atlas is not in use (switched off, or a float volume with non-finite texels)");
-    float *din = nullptr; float4 *dout = nullptr;
-    HIP_TRY(hipMalloc(&din, 3 * n * sizeof(float)));
-    hipError_t e = hipMalloc(&dout, n * sizeof(float4));
-    if (e != hipSuccess) { hipFree(din); return fail(VPT_ERR_HIP, "hipMalloc: %s", hipGetErrorString(e)); }
-    e = hipMemcpyAsync(din, xyz, 3 * n * sizeof(float), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) {
-        dim3 grid((unsigned)((n + 255) / 256));
-        const bool launched = dispatch_sampler_variant(variant_of(r), [&](auto V) {
-            if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<V()>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n);
-            else hipLaunchKernelGGL(k_probe_sample<V()>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din, dout, n);
-            return true;
-        }, [] { return false; });
-        if (!launched) { hipFree(din); hipFree(dout); return fail(VPT_ERR_INVALID, "no probe kernel for variant %d", variant_of(r)); }
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(rgba, dout, n * sizeof(float4), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    hipFree(din); hipFree(dout);
-    if (e != hipSuccess) return fail(VPT_ERR_HIP, "probe: %s", hipGetErrorString(e));
+    DevBuf<float> din; DevBuf<float4> dout;
+    HIP_TRY(din.alloc(3 * n));
+    HIP_TRY(dout.alloc(n));
+    HIP_TRY(hipMemcpyAsync(din, xyz, 3 * n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    dim3 grid((unsigned)((n + 255) / 256));
+    const bool launched = dispatch_sampler_variant(variant_of(r), [&](auto V) {
+        if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<V()>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din.get(), dout.get(), n);
+        else hipLaunchKernelGGL(k_probe_sample<V()>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din.get(), dout.get(), n);
+        return true;
+    }, [] { return false; });
+    if (!launched) return fail(VPT_ERR_INVALID, "no probe kernel for variant %d", variant_of(r));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(rgba, dout, n * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return VPT_OK;
 }
 
@@ -1230,31 +1151,31 @@ extern "C" int vpt_probe_stream_read(vpt_context *c, size_t nbytes, int iteratio
     if (nbytes < (1u << 20) || iterations < 1) return fail(VPT_ERR_INVALID, "need at least 1 MiB and one iteration");
     HIP_TRY(hipSetDevice(c->device));
     size_t n16 = nbytes / 16;
-    uint4 *buf = nullptr; uint32_t *sink = nullptr;
+    DevBuf<uint4> buf; DevBuf<uint32_t> sink;
+    HIP_TRY(buf.alloc(n16));
+    HIP_TRY(sink.alloc(1));
+    HIP_TRY(hipMemsetAsync(buf, 0, n16 * 16, c->stream));
     hipEvent_t e0 = nullptr, e1 = nullptr;
-    hipError_t e = hipMalloc(&buf, n16 * 16);
-    if (e == hipSuccess) e = hipMalloc(&sink, 4);
-    if (e == hipSuccess) e = hipMemsetAsync(buf, 0, n16 * 16, c->stream);
-    if (e == hipSuccess) e = hipEventCreate(&e0);
-    if (e == hipSuccess) e = hipEventCreate(&e1);
     float ms = 0.0f;
-    if (e == hipSuccess) {
+    auto timed = [&]() -> int {
+        HIP_TRY(hipEventCreate(&e0));
+        HIP_TRY(hipEventCreate(&e1));
         dim3 grid(256 * 16);                                  // 16 workgroups per CU
-        hipLaunchKernelGGL(k_stream_read, grid, dim3(VPT_BLOCK), 0, c->stream, buf, n16, sink);    // warm-up
-        e = hipEventRecord(e0, c->stream);
-        for (int i = 0; i < iterations && e == hipSuccess; i++) {
-            hipLaunchKernelGGL(k_stream_read, grid, dim3(VPT_BLOCK), 0, c->stream, buf, n16, sink);
-            e = hipGetLastError();
+        hipLaunchKernelGGL(k_stream_read, grid, dim3(VPT_BLOCK), 0, c->stream, buf.get(), n16, sink.get());    // warm-up
+        HIP_TRY(hipEventRecord(e0, c->stream));
+        for (int i = 0; i < iterations; i++) {
+            hipLaunchKernelGGL(k_stream_read, grid, dim3(VPT_BLOCK), 0, c->stream, buf.get(), n16, sink.get());
+            HIP_TRY(hipGetLastError());
         }
-        if (e == hipSuccess) e = hipEventRecord(e1, c->stream);
-        if (e == hipSuccess) e = hipEventSynchronize(e1);
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-    }
+        HIP_TRY(hipEventRecord(e1, c->stream));
+        HIP_TRY(hipEventSynchronize(e1));
+        HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
+        return VPT_OK;
+    };
+    const int rc = timed();                                   // (the events are destroyed whichever way it ends)
     if (e0) hipEventDestroy(e0);
     if (e1) hipEventDestroy(e1);
-    if (buf) hipFree(buf);
-    if (sink) hipFree(sink);
-    if (e != hipSuccess) return fail(VPT_ERR_HIP, "stream probe: %s", hipGetErrorString(e));
+    VPT_TRY(rc);
     *gb_per_s = (double)(n16 * 16) * iterations / ((double)ms * 1e-3) / 1e9;
     return VPT_OK;
 }

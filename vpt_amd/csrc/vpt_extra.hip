@@ -72,8 +72,8 @@ extern "C" int vpt_renderer_set_occlusion_samples(vpt_renderer *r, const float *
     vpt_context *c = r->ctx;
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (r->dos_samples) { HIP_TRY(hipFree(r->dos_samples)); r->dos_samples = nullptr; r->dos_nsamples = 0; }
-    HIP_TRY(hipMalloc(&r->dos_samples, (size_t)count * sizeof(float2)));
+    if (r->dos_samples.capacity() < (size_t)count) r->dos_nsamples = 0;      // (should the allocation fail, the renderer holds no samples)
+    HIP_TRY(r->dos_samples.reserve((size_t)count, c->stream));
     HIP_TRY(hipMemcpy(r->dos_samples, xy, (size_t)count * sizeof(float2), hipMemcpyHostToDevice));
     r->dos_nsamples = count;
     return VPT_OK;

@@ -12,6 +12,8 @@
 //   vpt_volume_window.hip  the value-range window (window / level) of a one-channel volume, its range and its code histogram
 // vpt_variants.h (through vpt_device.h) holds the variant bits of the sampling kernels and the switch from a run-time variant to a template
 // argument; launch_variant below is its use for a renderer's sampling pass.
+// vpt_buffers.h holds DevBuf<T> / PinnedBuf<T>, the owners of device and pinned host memory: the objects below own their memory through such
+// members and everything else in them has a default member initialiser, so `new` builds a valid object and `delete` frees all of it.
 // Nothing device-side crosses a translation unit: a kernel is compiled by the unit that names it (the three MCM units share one header).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -28,6 +30,7 @@
 
 #include "../../include/vpt.h"
 #include "vpt_kernels.h"
+#include "vpt_buffers.h"
 
 // ---------------------------------------------------------------------------------------------
 // errors
@@ -51,37 +54,37 @@ struct vpt_context {
 };
 
 struct vpt_volume {
-    vpt_context *ctx;
-    int nx, ny, nz;
-    int format;            // the VPT_FORMAT_* the volume was created with
-    int channels;          // 1 = R8 / R32F, 2 = RG8 (interleaved)
-    bool f32;              // FLOAT texels (VPT_FORMAT_R32F): 4 bytes per voxel, 512-byte brick slots
-    bool snorm;            // signed normalised texels (VPT_FORMAT_R8_SNORM / RG8_SNORM: stored like R8 / RG8; R16_SNORM / RG16_SNORM): VPT_V_SNORM
-    bool norm16;           // 16-bit normalised texels (VPT_FORMAT_R16 .. RG16_SNORM): 2 bytes per channel, 256-byte brick slots, VPT_V_NORM16
-    int packed;            // packed source format (VPT_FORMAT_RGB565 ..; 0: none): uploads are decoded into RG32F storage (f32, 2 channels)
-    int packed_bytes;      // bytes per packed source texel: 2 or 4
-    int vox_bytes;         // bytes per voxel of the linear storage: channels * (f32 ? 4 : norm16 ? 2 : 1)
-    uint32_t slot_shift, elem_shift;   // log2 of a brick slot's bytes (two channels: both bricks) and of a stored channel's bytes (DevVolume)
-    int filter;
-    uint8_t *linear;       // nx*ny*nz*channels, the "texture storage" blocks are uploaded into
-    uint8_t *bricks;       // apron bricks, Morton order
-    size_t brick_bytes;
-    uint32_t *tab32;       // separable brick-offset tables TX | TY | TZ (vpt_device.h), 32-bit form
-    uint32_t *tabc;        // brick Morton codes (always built; used when brick_bytes > 4 GiB, vpt_device.h cell_addr<WIDE>)
-    bool wide;
-    bool dirty;            // blocks uploaded since the last brickify
-    bool any_upload;
-    uint8_t *staging; size_t staging_bytes;
-    uint32_t *atlas;       // boundary atlas: the six outer voxel planes as 2 x 2-footprint cells (vpt_device.h sample_volume_boundary): one dword per cell
-                           // and channel (byte volumes) or one float4 (float volumes; 16-bit volumes: the decoded texels); channel c's faces
-                           // 6 * atlas_face cells behind c - 1's
-    size_t atlas_dwords;
-    bool atlas_ok;         // float volumes: every texel is finite and < 1e37 (k_scan_finite at finalize): else the atlas is not used
-    uint32_t *atlas_flag;
-    uint32_t atlas_face, atlas_shift;   // dwords per face image (row pitch x rows), log2 of the row pitch
+    vpt_context *ctx = nullptr;
+    int nx = 0, ny = 0, nz = 0;
+    int format = 0;            // the VPT_FORMAT_* the volume was created with
+    int channels = 0;          // 1 = R8 / R32F, 2 = RG8 (interleaved)
+    bool f32 = false;          // FLOAT texels (VPT_FORMAT_R32F): 4 bytes per voxel, 512-byte brick slots
+    bool snorm = false;        // signed normalised texels (VPT_FORMAT_R8_SNORM / RG8_SNORM: stored like R8 / RG8; R16_SNORM / RG16_SNORM): VPT_V_SNORM
+    bool norm16 = false;       // 16-bit normalised texels (VPT_FORMAT_R16 .. RG16_SNORM): 2 bytes per channel, 256-byte brick slots, VPT_V_NORM16
+    int packed = 0;            // packed source format (VPT_FORMAT_RGB565 ..; 0: none): uploads are decoded into RG32F storage (f32, 2 channels)
+    int packed_bytes = 0;      // bytes per packed source texel: 2 or 4
+    int vox_bytes = 0;         // bytes per voxel of the linear storage: channels * (f32 ? 4 : norm16 ? 2 : 1)
+    uint32_t slot_shift = 0, elem_shift = 0;   // log2 of a brick slot's bytes (two channels: both bricks) and of a stored channel's bytes (DevVolume)
+    int filter = VPT_FILTER_LINEAR;            // Volume.js:53-54
+    DevBuf<uint8_t> linear;    // nx*ny*nz*channels, the "texture storage" blocks are uploaded into
+    DevBuf<uint8_t> bricks;    // apron bricks, Morton order
+    size_t brick_bytes = 0;
+    DevBuf<uint32_t> tab32;    // separable brick-offset tables TX | TY | TZ (vpt_device.h), 32-bit form
+    DevBuf<uint32_t> tabc;     // brick Morton codes (always built; used when brick_bytes > 4 GiB, vpt_device.h cell_addr<WIDE>)
+    bool wide = false;
+    bool dirty = true;         // blocks uploaded since the last brickify
+    bool any_upload = false;
+    DevBuf<uint8_t> staging;   // blocks on their way in or out, grown on demand
+    DevBuf<uint32_t> atlas;    // boundary atlas: the six outer voxel planes as 2 x 2-footprint cells (vpt_device.h sample_volume_boundary): one dword per cell
+                               // and channel (byte volumes) or one float4 (float volumes; 16-bit volumes: the decoded texels); channel c's faces
+                               // 6 * atlas_face cells behind c - 1's
+    size_t atlas_dwords = 0;
+    bool atlas_ok = true;      // float volumes: every texel is finite and < 1e37 (k_scan_finite at finalize): else the atlas is not used
+    DevBuf<uint32_t> atlas_flag;
+    uint32_t atlas_face = 0, atlas_shift = 0;   // dwords per face image (row pitch x rows), log2 of the row pitch
     // column records (vpt_device.h record_addr; one-channel byte volumes): built on the first MCM pass that wants them (volume_records)
-    uint8_t *records; size_t rec_bytes; bool rec_valid, rec_wide;
-    uint32_t *rtab32, *rtabc;           // RX | RY: byte offsets of the columns / their Z-order codes
+    DevBuf<uint8_t> records; size_t rec_bytes = 0; bool rec_valid = false, rec_wide = false;
+    DevBuf<uint32_t> rtab32, rtabc;     // RX | RY: byte offsets of the columns / their Z-order codes
 };
 
 // Tile classes (vpt_kernels.h, "Tile classes"): per reset the host sorts the 16x16 tiles into those none of whose camera rays
@@ -90,28 +93,28 @@ struct vpt_volume {
 // of the MISS tiles are behind and k_mcm_materialize must run before anything but k_mcm_miss looks at them.
 #define VPT_COMPLETE_DESTS 40
 struct TileClasses {
-    bool enabled, verify;          // VPT_OPTION_TILE_CLASSES (default on), VPT_OPTION_VERIFY_TILE_CLASSES
-    bool one_stream;               // VPT_OPTION_TILE_CLASSES = 2: the MCM class kernels also where they must follow each other on one stream (each alone on the chip: measurements)
-    bool valid;                    // the lists describe `mvp` for the present geometry, and every pass since that reset used it
-    float mvp[16];
-    uint32_t *list; int capacity;  // device: n_hit HIT tiles, then n_miss MISS tiles, each tx | ty << 16
-    int n_hit, n_miss;
+    bool enabled = true, verify = false;   // VPT_OPTION_TILE_CLASSES (default on), VPT_OPTION_VERIFY_TILE_CLASSES
+    bool one_stream = false;       // VPT_OPTION_TILE_CLASSES = 2: the MCM class kernels also where they must follow each other on one stream (each alone on the chip: measurements)
+    bool valid = false;            // the lists describe `mvp` for the present geometry, and every pass since that reset used it
+    float mvp[16] = {};
+    DevBuf<uint32_t> list;         // device: n_hit HIT tiles, then n_miss MISS tiles, each tx | ty << 16
+    int n_hit = 0, n_miss = 0;
     // what the lists on the device were built for: a reset with the same matrix and geometry (the interactive case: a transfer function or a
     // parameter changed, the camera did not) re-uses them — no classification, no upload (classes_build)
-    bool built; float built_mvp[16]; int built_geom[6];
+    bool built = false; float built_mvp[16] = {}; int built_geom[6] = {};
     // uploads go through two pinned staging buffers in turn, no host wait: staged[i] = the copy out of staging[i] has been enqueued and completes
-    uint32_t *staging[2]; int staging_capacity[2]; hipEvent_t staged[2]; int stage_next;
-    bool stale, stale_fast;        // MISS tiles' position / transmittance arrays are behind; the pass that left them ran the fast variant
-    unsigned long long *violations;
+    PinnedBuf<uint32_t> staging[2]; hipEvent_t staged[2] = {}; int stage_next = 0;
+    bool stale = false, stale_fast = false;   // MISS tiles' position / transmittance arrays are behind; the pass that left them ran the fast variant
+    DevBuf<unsigned long long> violations;
     // the accumulating ray marchers (MIP, EAM, ISO, MCS, Depth): see marcher_track
-    uint64_t passes, fused_passes; // generate / fused passes since the reset
-    bool poisoned;                 // a pass since the reset used another matrix than the first: nothing can be skipped until the next reset
-    bool first_mix_one;            // the first pass since the reset was a fused pass with mix == 1 (MCS, Depth: accumulator = frame exactly)
-    bool list_now;                 // the launch being enqueued covers the HIT tiles only
-    bool reset_seen;               // vpt_renderer_reset has run on the present buffers (zero-filled buffers are not a reset)
+    uint64_t passes = 0, fused_passes = 0;   // generate / fused passes since the reset
+    bool poisoned = false;         // a pass since the reset used another matrix than the first: nothing can be skipped until the next reset
+    bool first_mix_one = false;    // the first pass since the reset was a fused pass with mix == 1 (MCS, Depth: accumulator = frame exactly)
+    bool list_now = false;         // the launch being enqueued covers the HIT tiles only
+    bool reset_seen = false;       // vpt_renderer_reset has run on the present buffers (zero-filled buffers are not a reset)
     // render destinations (the renderer's own buffer, a caller's target, the slots of a bucket or of the gather ring) that a WHOLE-image fused
     // pass has written since the reset: only there do the skipped tiles hold their final texels (marcher_track)
-    const void *complete[VPT_COMPLETE_DESTS]; int n_complete;
+    const void *complete[VPT_COMPLETE_DESTS] = {}; int n_complete = 0;
 };
 // Split passes (VPT_OPTION_SPLIT_STREAMS = K): a sampling pass is dealt to up to K streams as tile-row ranges or parts of a tile list;
 // range i runs on range_stream(r, i), the context's stream for i = 0 and a private side stream otherwise.  A pixel's pass depends on
@@ -137,75 +140,75 @@ struct StreamSet {
 };
 
 struct vpt_renderer {
-    vpt_context *ctx;
-    int kind;
-    int W, H;
-    int G, g, R;
-    int local_h;
-    int tiles_x, tiles_y, ntiles;
-    size_t npix_padded;     // ntiles * 256
-    uint64_t valid_pixels;  // owned pixels inside the image
-    vpt_volume *vol;
-    float4 *tf; int tf_w, tf_h;
-    float4 *env; int env_w, env_h; float4 env_const; bool env_opaque;   // env_opaque: every texel's alpha is 255
-    void *frame, *acc;
-    float4 *st[4];
-    uint2 *render;
-    uint2 *render_target;          // caller-owned redirect of the render buffer (or null)
-    uint2 *frame_ring; int ring_frames;   // VPT_PLAY_FRAMES: VPT_FRAME_SLOTS frames of W x local_h RGBA16F (allocated on first use); frames of the last call
-    float *ndc_x, *ndc_y;          // pixel-centre NDC tables (W and H entries)
-    FrameVar *frame_table; FrameVar *frame_staging;   // device ring of per-frame uniforms (+ the table of a captured sequence) + pinned staging
-    uint64_t frames_played;        // frames uploaded so far (monotonic): the ring's and the staging ring's cursor
-    bool warmed;                   // at least one eager fused render() has run (lazy allocations done)
-    struct PlayGraph *play_graph;  // cached hipGraph of a frame sequence
-    uint32_t *work_counter;        // tile counter of the persistent MCS kernel
-    bool mcs_persistent;           // use k_mcs_persist (active-ray compaction) for the MCS generate pass
-    LaoParams lao;                 // LAO renderer parameters (vpt_renderer_set_lao_params; defaults LAORenderer.js:17-108)
-    float2 *dos_samples; int dos_nsamples;   // DOS: uOcclusionSamples (vpt_renderer_set_occlusion_samples)
-    int dos_rect[4]; bool dos_rect_valid;   // DOS: tile rectangle [x0, y0, x1, y1) of the previous integrate call (see dos_tile_rect)
-    int dos_cur;                   // DOS: which of the occlusion buffers st[2|3] holds the latest slice (colour: st[0], in place)
+    vpt_context *ctx = nullptr;
+    int kind = 0;
+    int W = 0, H = 0;
+    int G = 1, g = 0, R = 8;
+    int local_h = 0;
+    int tiles_x = 0, tiles_y = 0, ntiles = 0;
+    size_t npix_padded = 0;     // ntiles * 256
+    uint64_t valid_pixels = 0;  // owned pixels inside the image
+    vpt_volume *vol = nullptr;
+    DevBuf<float4> tf; int tf_w = 0, tf_h = 0;
+    DevBuf<float4> env; int env_w = 0, env_h = 0; float4 env_const = {}; bool env_opaque = false;   // env_opaque: every texel's alpha is 255
+    DevBuf<uint8_t> frame, acc;
+    DevBuf<float4> st[4];          // (MCM: 0 and 2 hold 12-byte texels, DOS: 2 and 3 hold floats — renderer_alloc_buffers)
+    DevBuf<uint2> render;
+    uint2 *render_target = nullptr;   // caller-owned redirect of the render buffer (or null)
+    DevBuf<uint2> frame_ring; int ring_frames = 0;   // VPT_PLAY_FRAMES: VPT_FRAME_SLOTS frames of W x local_h RGBA16F (allocated on first use); frames of the last call
+    DevBuf<float> ndc_x, ndc_y;    // pixel-centre NDC tables (W and H entries)
+    DevBuf<FrameVar> frame_table; PinnedBuf<FrameVar> frame_staging;   // device ring of per-frame uniforms (+ the table of a captured sequence) + pinned staging
+    uint64_t frames_played = 0;    // frames uploaded so far (monotonic): the ring's and the staging ring's cursor
+    bool warmed = false;           // at least one eager fused render() has run (lazy allocations done)
+    struct PlayGraph *play_graph = nullptr;  // cached hipGraph of a frame sequence
+    DevBuf<uint32_t> work_counter; // tile counter of the persistent MCS kernel
+    bool mcs_persistent = false;   // use k_mcs_persist (active-ray compaction) for the MCS generate pass: measured slower than k_mcs at every extinction tried
+    LaoParams lao = { 1, 0.69f, 1, 0.05f, 1, 0.54f, 10, 0.19f, 1.0f, { 2.0f, 12.0f, 3.0f } };   // LAO renderer parameters (vpt_renderer_set_lao_params; defaults LAORenderer.js:17-108)
+    DevBuf<float2> dos_samples; int dos_nsamples = 0;   // DOS: uOcclusionSamples (vpt_renderer_set_occlusion_samples)
+    int dos_rect[4] = {}; bool dos_rect_valid = false;   // DOS: tile rectangle [x0, y0, x1, y1) of the previous integrate call (see dos_tile_rect)
+    int dos_cur = 0;               // DOS: which of the occlusion buffers st[2|3] holds the latest slice (colour: st[0], in place)
     // VPT_OPTION_SPLIT_STREAMS = K: a sampling pass may be dealt to up to K streams (split_allowed, StreamSet)
-    bool target_is_callers;        // render_target was set by vpt_renderer_set_render_target (not by the gather pipeline)
-    bool no_split;                 // set while a frame sequence is being captured into a hipGraph (one stream only)
-    bool bucket_call;              // inside vpt_renderer_play_into*: the passes into the caller's bucket may use every stream, the call joins them before it returns
-    hipEvent_t *stop_events;       // gather pipeline: event i is attached to range i's launch (hipExtLaunchKernel stop event: the
-    bool stop_used;                // dispatch packet's own completion signal, no barrier packet behind the kernel)
-    int split; bool split_auto;     // split_auto: the stream count is the library's default and follows the launch size (split_for)
+    bool target_is_callers = false;   // render_target was set by vpt_renderer_set_render_target (not by the gather pipeline)
+    bool no_split = false;         // set while a frame sequence is being captured into a hipGraph (one stream only)
+    bool bucket_call = false;      // inside vpt_renderer_play_into*: the passes into the caller's bucket may use every stream, the call joins them before it returns
+    hipEvent_t *stop_events = nullptr;   // gather pipeline: event i is attached to range i's launch (hipExtLaunchKernel stop event: the
+    bool stop_used = false;        // dispatch packet's own completion signal, no barrier packet behind the kernel)
+    int split = 1; bool split_auto = true;   // split_auto: the stream count is the library's default and follows the launch size (split_for)
     StreamSet streams;
-    int boundary_atlas;            // VPT_OPTION_BOUNDARY_ATLAS (default 1): MCM takes out-of-cube samples from the volume's boundary atlas
-    int fast_math;                 // VPT_OPTION_FAST_MATH: MCM events with hardware rcp / rsq / log / sin / cos (k_mcm_integrate<.., V | VPT_V_FAST>)
-    int mcm_persistent;            // 0: k_mcm_integrate; 1: k_mcm_persist; 2: k_mcm_persist with next-segment prefetch // (persistent waves, state prefetch) for the MCM integrate pass
-    struct TileClasses cls;        // MCM: HIT / MISS tile lists of the last reset's matrix (see classify_tiles)
+    int boundary_atlas = 1;        // VPT_OPTION_BOUNDARY_ATLAS (default 1): MCM takes out-of-cube samples from the volume's boundary atlas
+    int fast_math = 0;             // VPT_OPTION_FAST_MATH: MCM events with hardware rcp / rsq / log / sin / cos (k_mcm_integrate<.., V | VPT_V_FAST>)
+    int mcm_persistent = 0;        // 0: k_mcm_integrate; 1: k_mcm_persist; 2: k_mcm_persist with next-segment prefetch // (persistent waves, state prefetch) for the MCM integrate pass
+    TileClasses cls;               // MCM: HIT / MISS tile lists of the last reset's matrix (see classify_tiles)
     // tone mapping fused into the fused passes' frame store: the armed tone mapper (null: none), whether its output holds the tone-mapped
     // image of what the render buffer holds now, and the store's arguments (PassArgs.tm_*)
-    struct vpt_tonemapper *tm_owner; bool tm_valid; const uint8_t *tm_table; uint32_t *tm_out; int tm_mode;
-    uint64_t bucket_launches;      // buckets of frames run by k_mcm_bucket_* so far (vpt_renderer_bucket_launches)
-    bool bucket_kernel;            // VPT_OPTION_BUCKET_KERNEL: vpt_renderer_play_into runs a bucket's frames by one launch per tile class
-    int hit_form;                  // VPT_HIT_KERNEL_FORM in the environment at creation (A/B and tests): 0 = by the number of HIT tiles, 1 = k_mcm_integrate, 2 = k_mcm_integrate_early
-    int column_records;            // VPT_OPTION_COLUMN_RECORDS: 0 = bricks, 1 = column records, 2 (default) = records where the bricks exceed VPT_RECORDS_AUTO_BYTES
-    unsigned long long *samples;   // device counter (MIP/EAM/MCS)
-    uint64_t samples_host;         // analytic part (MCM)
-    void *scratch; size_t scratch_bytes;
-    bool profiling;
-    int profile_every; uint64_t profile_seq;   // time every n-th launch of the dominant kernel
+    struct vpt_tonemapper *tm_owner = nullptr; bool tm_valid = false; const uint8_t *tm_table = nullptr; uint32_t *tm_out = nullptr; int tm_mode = 0;
+    uint64_t bucket_launches = 0;  // buckets of frames run by k_mcm_bucket_* so far (vpt_renderer_bucket_launches)
+    bool bucket_kernel = false;    // VPT_OPTION_BUCKET_KERNEL: vpt_renderer_play_into runs a bucket's frames by one launch per tile class
+    int hit_form = 0;              // VPT_HIT_KERNEL_FORM in the environment at creation (A/B and tests): 0 = by the number of HIT tiles, 1 = k_mcm_integrate, 2 = k_mcm_integrate_early
+    int column_records = 2;        // VPT_OPTION_COLUMN_RECORDS: 0 = bricks, 1 = column records, 2 (default) = records where the bricks exceed VPT_RECORDS_AUTO_BYTES
+    DevBuf<unsigned long long> samples;   // device counter (MIP/EAM/MCS)
+    uint64_t samples_host = 0;     // analytic part (MCM)
+    DevBuf<uint8_t> scratch;       // vpt_renderer_read: the de-tiled image, grown on demand
+    bool profiling = false;
+    int profile_every = 1; uint64_t profile_seq = 0;   // time every n-th launch of the dominant kernel
     std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
     std::vector<uint32_t> event_launches;   // kernel launches covered by each event pair (1, or the frames of a graph replay)
-    size_t events_used;
+    size_t events_used = 0;
     // the same around the first launch a pass puts on a SIDE stream (tile classes: the MISS-tile kernel), for the passes `events` samples
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> side_events; size_t side_events_used; bool timed_now;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> side_events; size_t side_events_used = 0; bool timed_now = false;
 };
 
 struct vpt_tonemapper {
-    vpt_context *ctx;
-    int kind, W, H;
-    vpt_renderer *source;          // bound renderer (not owned), or null
-    uint2 *image; int image_w, image_rows;    // owned source texture (set_source_image), or null
-    uint32_t *out; size_t out_pixels;         // RGBA8 target, grown on demand
-    int rows;                      // rows of the last render
-    int table_mode;                // VPT_TONEMAPPER_TABLE_*
-    uint8_t *table; bool table_valid; TonemapParams table_params;   // byte table of the current parameters (vpt_tonemap.h)
-    bool fuse;                     // VPT_TONEMAPPER_OPTION_FUSE (default on): arm the bound renderer's fused passes with this table and output
-    TmFuse fuse_args; bool fuse_args_valid;   // what the block behind the table holds (vpt_tonemap.h)
+    vpt_context *ctx = nullptr;
+    int kind = 0, W = 0, H = 0;
+    vpt_renderer *source = nullptr;   // bound renderer (not owned), or null
+    DevBuf<uint2> image; int image_w = 0, image_rows = 0;    // owned source texture (set_source_image), or null
+    DevBuf<uint32_t> out;          // RGBA8 target, grown on demand
+    int rows = 0;                  // rows of the last render
+    int table_mode = VPT_TONEMAPPER_TABLE_AUTO;   // VPT_TONEMAPPER_TABLE_*
+    DevBuf<uint8_t> table; bool table_valid = false; TonemapParams table_params = {};   // byte table of the current parameters (vpt_tonemap.h)
+    bool fuse = true;              // VPT_TONEMAPPER_OPTION_FUSE (default on): arm the bound renderer's fused passes with this table and output
+    TmFuse fuse_args = {}; bool fuse_args_valid = false;   // what the block behind the table holds (vpt_tonemap.h)
 };
 
 static const size_t COUNTER_BYTES = (size_t)VPT_COUNTER_SLOTS * VPT_COUNTER_STRIDE * sizeof(unsigned long long);
@@ -234,6 +237,7 @@ int join_side(vpt_renderer *r);                     // the side streams' work ha
 int streams_deal(vpt_renderer *r, Deal d);          // before the launches of a deal: join and fork as the deal needs (StreamSet)
 int make_args(vpt_renderer *r, const vpt_uniforms *u, bool need_volume, PassArgs *a);
 int volume_create(vpt_context *c, int w, int h, int d, int format, bool zero_fill, vpt_volume **out);   // vpt_volume_create; zero_fill = false: the caller writes every texel
+int volume_finish_derived(const vpt_volume *src, vpt_volume *d, vpt_volume **out);   // the shared tail of the derived volumes (gradient, window): finalize and hand out
 int volume_records(vpt_volume *v);                  // builds the column records of a finalized one-channel byte volume if they are not current
 hipError_t create_overlapping_stream(hipStream_t *out, const vpt_renderer *r);   // overlaps r's context stream and side streams
 bool invert_matrix(const float *m, double out[4][4]);               // column-major float matrix -> its inverse (double); false: singular

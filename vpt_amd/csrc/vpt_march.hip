@@ -21,7 +21,7 @@ static int launch_mcs_persist(K kernel, vpt_renderer *r, const PassArgs &a) {
     const size_t lds = lds_bytes(r);
     VPT_TRY(lds_prepare((const void *)kernel, lds));
     const size_t counter_bytes = (size_t)VPT_WORK_SHARDS * VPT_WORK_STRIDE * sizeof(uint32_t);
-    if (!r->work_counter) HIP_TRY(hipMalloc(&r->work_counter, counter_bytes));
+    if (!r->work_counter) HIP_TRY(r->work_counter.alloc(counter_bytes / sizeof(uint32_t)));
     HIP_TRY(hipMemsetAsync(r->work_counter, 0, counter_bytes, r->ctx->stream));
     int ntx8 = (r->W + 7) / 8, nty8 = (r->local_h + 7) / 8, ntiles8 = ntx8 * nty8;
     int blocks = (ntiles8 + 3) / 4;

@@ -12,7 +12,7 @@
 #define VPT_TIMING_ARG(part, hit) do { } while (0)
 #endif
 #ifdef VPT_EVENT_TIMING
-static unsigned long long *g_timing = nullptr;
+static unsigned long long *g_timing = nullptr;   // (VPT_EVENT_TIMING builds only) kept for the life of the process, hence a bare pointer: never freed
 static unsigned long long *timing_buffer(vpt_renderer *r) {
     if (!g_timing) {
         if (hipMalloc(&g_timing, (size_t)VPT_TIMING_WAVES * 16 * sizeof(unsigned long long)) != hipSuccess) { g_timing = nullptr; return nullptr; }

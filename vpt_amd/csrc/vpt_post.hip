@@ -19,8 +19,7 @@ extern "C" int vpt_tonemapper_create(vpt_context *c, int kind, int width, int he
     if (kind < VPT_TONEMAPPER_ARTISTIC || kind > VPT_TONEMAPPER_UCHIMURA) return fail(VPT_ERR_INVALID, "No suitable class");   // ToneMapperFactory.js:26
     if (width < 1 || height < 1) return fail(VPT_ERR_INVALID, "bad resolution %dx%d", width, height);
     vpt_tonemapper *t = new vpt_tonemapper();
-    memset(t, 0, sizeof(*t));
-    t->ctx = c; t->kind = kind; t->W = width; t->H = height; t->table_mode = VPT_TONEMAPPER_TABLE_AUTO; t->fuse = true;
+    t->ctx = c; t->kind = kind; t->W = width; t->H = height;
     c->tonemappers.push_back(t);
     *out = t;
     return VPT_OK;
@@ -31,9 +30,6 @@ extern "C" int vpt_tonemapper_destroy(vpt_tonemapper *t) {
     if (t->source) join_side(t->source);
     tonemapper_disarm(t);
     hipStreamSynchronize(t->ctx->stream);
-    if (t->image) hipFree(t->image);
-    if (t->out) hipFree(t->out);
-    if (t->table) hipFree(t->table);
     for (size_t i = 0; i < t->ctx->tonemappers.size(); i++)
         if (t->ctx->tonemappers[i] == t) { t->ctx->tonemappers.erase(t->ctx->tonemappers.begin() + (long)i); break; }
     delete t;
@@ -50,7 +46,7 @@ extern "C" int vpt_tonemapper_set_source(vpt_tonemapper *t, vpt_renderer *r) {
     if (!t) return fail(VPT_ERR_INVALID, "tone mapper is null");
     if (r && r->ctx->device != t->ctx->device) return fail(VPT_ERR_INVALID, "renderer and tone mapper live on different devices");
     HIP_TRY(hipSetDevice(t->ctx->device));
-    if (t->image) { HIP_TRY(hipStreamSynchronize(t->ctx->stream)); HIP_TRY(hipFree(t->image)); t->image = nullptr; }
+    if (t->image) { HIP_TRY(hipStreamSynchronize(t->ctx->stream)); t->image.reset(); }
     if (t->source) VPT_TRY(join_side(t->source));
     tonemapper_disarm(t);
     t->source = r;
@@ -62,9 +58,8 @@ extern "C" int vpt_tonemapper_set_source_image(vpt_tonemapper *t, const void *rg
     vpt_context *c = t->ctx;
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (t->image) { HIP_TRY(hipFree(t->image)); t->image = nullptr; }
     size_t bytes = (size_t)width * rows * 8;
-    HIP_TRY(hipMalloc(&t->image, bytes));
+    HIP_TRY(t->image.alloc((size_t)width * rows));
     HIP_TRY(hipMemcpyAsync(t->image, rgba16f, bytes, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     tonemapper_disarm(t);
@@ -80,7 +75,7 @@ static void launch_tonemap(vpt_tonemapper *t, const uint2 *src, size_t n, const 
     bool current = t->table && t->table_valid && memcmp(&t->table_params, &p, sizeof(p)) == 0;
     bool use_table = (KIND != VPT_TM_ARTISTIC || p.saturation == 1.0f) &&
                      (t->table_mode == VPT_TONEMAPPER_TABLE_ALWAYS || (t->table_mode == VPT_TONEMAPPER_TABLE_AUTO && (current || n >= 4 * 65536)));
-    if (use_table && !t->table && hipMalloc(&t->table, VPT_TM_TABLE_BYTES) != hipSuccess) { t->table = nullptr; use_table = false; (void)hipGetLastError(); }
+    if (use_table && !t->table && t->table.alloc(VPT_TM_TABLE_BYTES) != hipSuccess) { use_table = false; (void)hipGetLastError(); }
     // the renderer whose fused passes may carry this map (one context: its streams are ordered against this one by events)
     vpt_renderer *fr = (t->fuse && t->source && src == t->source->render && t->source->ctx == t->ctx) ? t->source : nullptr;
     if (!use_table) {
@@ -164,7 +159,7 @@ extern "C" int vpt_tonemapper_render(vpt_tonemapper *t, const struct vpt_tonemap
     vpt_context *c = t->ctx;
     HIP_TRY(hipSetDevice(c->device));
     const uint2 *src = nullptr; int w = t->W, rows = t->H;
-    uint2 *white = nullptr;
+    DevBuf<uint2> white;
     if (t->source) {
         vpt_renderer *r = t->source;
         src = r->render_target ? r->render_target : r->render; w = r->W; rows = r->local_h;
@@ -176,17 +171,15 @@ extern "C" int vpt_tonemapper_render(vpt_tonemapper *t, const struct vpt_tonemap
         return fail(VPT_ERR_UNSUPPORTED, "source is %dx%d, tone mapper %dx%d: resampling between resolutions is not implemented "
                                          "(the reference keeps them equal, RenderingContext.js:219-228)", w, t->source ? t->source->H : rows, t->W, t->H);
     size_t n = (size_t)w * rows;
-    if (t->out_pixels < n) {
+    if (t->out.capacity() < n) {
         tonemapper_disarm(t);                                  // (the armed renderer holds the old output's address)
-        if (t->out) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(t->out)); t->out = nullptr; t->out_pixels = 0; }
-        HIP_TRY(hipMalloc(&t->out, n * 4));
-        t->out_pixels = n;
+        HIP_TRY(t->out.reserve(n, c->stream));
     }
     if (!src) {                                               // the 1x1 white placeholder texture: a constant image
-        HIP_TRY(hipMalloc(&white, n * 8));
+        HIP_TRY(white.alloc(n));
         uint64_t one4 = 0x3c003c003c003c00ull;                // half(1) x 4
         static_assert(sizeof(uint2) == 8, "texel size");
-        hipLaunchKernelGGL(k_fill_u32, dim3(1024), dim3(256), 0, c->stream, (uint32_t *)white, n * 2, (uint32_t)(one4 & 0xffffffffu));
+        hipLaunchKernelGGL(k_fill_u32, dim3(1024), dim3(256), 0, c->stream, (uint32_t *)white.get(), n * 2, (uint32_t)(one4 & 0xffffffffu));
         src = white;
     }
     switch (t->kind) {
@@ -202,7 +195,7 @@ extern "C" int vpt_tonemapper_render(vpt_tonemapper *t, const struct vpt_tonemap
         default:                        launch_tonemap<VPT_TM_UCHIMURA>(t, src, n, p); break;
     }
     hipError_t e = hipGetLastError();
-    if (white) { hipStreamSynchronize(c->stream); hipFree(white); }
+    if (white) hipStreamSynchronize(c->stream);             // the pass reads the placeholder, which goes with this scope
     if (e != hipSuccess) return fail(VPT_ERR_HIP, "tone-map launch: %s", hipGetErrorString(e));
     t->rows = rows;
     return VPT_OK;
@@ -290,20 +283,17 @@ extern "C" int vpt_transfer_function_rasterize(vpt_context *c, const vpt_tf_bump
     for (int k = 0; k < count; k++)
         if (bumps[k].sx == 0.0f || bumps[k].sy == 0.0f) return fail(VPT_ERR_INVALID, "bump %d has a zero size", k);
     HIP_TRY(hipSetDevice(c->device));
-    vpt_tf_bump *dev_bumps = nullptr; uint32_t *dev_out = nullptr;
-    const size_t nb = (size_t)std::max(count, 1) * sizeof(vpt_tf_bump), no = (size_t)width * height * 4;
-    HIP_TRY(hipMalloc(&dev_bumps, nb));
-    if (hipMalloc(&dev_out, no) != hipSuccess) { hipFree(dev_bumps); return fail(VPT_ERR_HIP, "hipMalloc of %zu bytes failed", no); }
-    int rc = VPT_OK;
-    do {
-        if (count > 0 && hipMemcpyAsync(dev_bumps, bumps, (size_t)count * sizeof(vpt_tf_bump), hipMemcpyHostToDevice, c->stream) != hipSuccess) { rc = fail(VPT_ERR_HIP, "bump upload failed"); break; }
-        hipLaunchKernelGGL(k_tf_rasterize, dim3((unsigned)((width + 15) / 16), (unsigned)((height + 15) / 16)), dim3(256), 0, c->stream,
-                           dev_bumps, count, width, height, unpremultiply, dev_out);
-        if (hipGetLastError() != hipSuccess) { rc = fail(VPT_ERR_HIP, "k_tf_rasterize launch failed"); break; }
-        if (hipMemcpyAsync(rgba_out, dev_out, no, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) { rc = fail(VPT_ERR_HIP, "transfer function read-back failed"); break; }
-    } while (0);
-    hipFree(dev_bumps); hipFree(dev_out);
-    return rc;
+    DevBuf<vpt_tf_bump> dev_bumps; DevBuf<uint32_t> dev_out;
+    const size_t no = (size_t)width * height * 4;
+    HIP_TRY(dev_bumps.alloc((size_t)std::max(count, 1)));
+    HIP_TRY(dev_out.alloc((size_t)width * height));
+    if (count > 0) HIP_TRY(hipMemcpyAsync(dev_bumps, bumps, (size_t)count * sizeof(vpt_tf_bump), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_tf_rasterize, dim3((unsigned)((width + 15) / 16), (unsigned)((height + 15) / 16)), dim3(256), 0, c->stream,
+                       dev_bumps.get(), count, width, height, unpremultiply, dev_out.get());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(rgba_out, dev_out, no, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return VPT_OK;
 }
 extern "C" int vpt_tonemapper_rows(vpt_tonemapper *t, int *rows) {
     if (!t || !rows) return fail(VPT_ERR_INVALID, "null argument");
@@ -376,21 +366,21 @@ static int rccl_load() {
 #define VPT_GATHER_RING 16            // even; 1080p: 16 x (2 MB + 16.6 MB), 2160p: 16 x (8.3 MB + 66 MB) of 288 GB
 #endif
 struct vpt_gather {
-    vpt_renderer *r;
-    int rank, world;
-    int root;                          // -1: every rank receives the frame (all_gather); else only this rank does
-    ncclComm_t_ comm;
-    hipStream_t comm_stream;
-    size_t send_bytes;                 // W * local_h * 8
+    vpt_renderer *r = nullptr;
+    int rank = 0, world = 1;
+    int root = -1;                     // -1: every rank receives the frame (all_gather); else only this rank does
+    ncclComm_t_ comm = nullptr;
+    hipStream_t comm_stream = nullptr;
+    size_t send_bytes = 0;             // W * local_h * 8
     // A ring of VPT_GATHER_RING send / receive buffers: frame k uses buffer k % ring.  Per frame the streams exchange ONE
     // event (kernel done -> the communication stream may send); the reverse edge (buffer free again -> the compute stream
     // may overwrite it) is needed only once per half ring: the gather that ends a half records gathered[half parity], and
     // the compute stream waits for it when it re-enters that half a whole ring later.  (With two buffers the reverse edge
     // was paid every frame: ~11 us of event traffic per frame at a 24 us kernel.)
-    void *send[VPT_GATHER_RING], *recv[VPT_GATHER_RING];
-    hipEvent_t rendered[2][VPT_MAX_SPLIT], gathered[2];   // rendered: per tile-row range (stream) of a split pass
-    uint64_t frames;
-    void *assembled;                   // [H][W] RGBA16F scratch for read_frame
+    DevBuf<uint8_t> send[VPT_GATHER_RING], recv[VPT_GATHER_RING];
+    hipEvent_t rendered[2][VPT_MAX_SPLIT] = {}, gathered[2] = {};   // rendered: per tile-row range (stream) of a split pass
+    uint64_t frames = 0;
+    DevBuf<uint2> assembled;           // [H][W] RGBA16F scratch for read_frame
 };
 
 // gathered [world][local_h][W] -> [H][W]: global row j lives on rank (j / R) % G at local row ((j / R) / G) * R + j % R
@@ -413,19 +403,15 @@ extern "C" int vpt_probe_assemble_rows(vpt_context *c, const void *gathered, int
     if (local_rows < max_local) return fail(VPT_ERR_INVALID, "local_rows %d < %d needed for %d rows over %d ranks", local_rows, max_local, height, world);
     HIP_TRY(hipSetDevice(c->device));
     size_t in_bytes = (size_t)world * local_rows * width * 8, out_bytes = (size_t)width * height * 8;
-    void *din = nullptr, *dout = nullptr;
-    HIP_TRY(hipMalloc(&din, in_bytes));
-    hipError_t e = hipMalloc(&dout, out_bytes);
-    if (e == hipSuccess) e = hipMemcpyAsync(din, gathered, in_bytes, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_assemble_rows, dim3((unsigned)((width + 255) / 256), (unsigned)height), dim3(256), 0, c->stream,
-                           (const uint2 *)din, (uint2 *)dout, width, height, local_rows, world, rows_per_block);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(out, dout, out_bytes, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    hipFree(din); if (dout) hipFree(dout);
-    if (e != hipSuccess) return fail(VPT_ERR_HIP, "assemble probe: %s", hipGetErrorString(e));
+    DevBuf<uint2> din, dout;
+    HIP_TRY(din.alloc(in_bytes / 8));
+    HIP_TRY(dout.alloc(out_bytes / 8));
+    HIP_TRY(hipMemcpyAsync(din, gathered, in_bytes, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_assemble_rows, dim3((unsigned)((width + 255) / 256), (unsigned)height), dim3(256), 0, c->stream,
+                       (const uint2 *)din.get(), dout.get(), width, height, local_rows, world, rows_per_block);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, dout, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return VPT_OK;
 }
 extern "C" int vpt_gather_unique_id(void *id128) {
@@ -444,15 +430,10 @@ extern "C" int vpt_gather_destroy(vpt_gather *g) {
     if (g->comm_stream) hipStreamSynchronize(g->comm_stream);
     vpt_renderer_set_render_target(g->r, nullptr, 0);
     if (g->comm) g_rccl.CommDestroy(g->comm);
-    for (int b = 0; b < VPT_GATHER_RING; b++) {
-        if (g->send[b]) hipFree(g->send[b]);
-        if (g->recv[b]) hipFree(g->recv[b]);
-    }
     for (int b = 0; b < 2; b++) {
         for (int i = 0; i < VPT_MAX_SPLIT; i++) if (g->rendered[b][i]) hipEventDestroy(g->rendered[b][i]);
         if (g->gathered[b]) hipEventDestroy(g->gathered[b]);
     }
-    if (g->assembled) hipFree(g->assembled);
     if (g->comm_stream) hipStreamDestroy(g->comm_stream);
     delete g;
     return VPT_OK;
@@ -464,8 +445,7 @@ extern "C" int vpt_gather_create(vpt_renderer *r, const void *id128, int rank, i
     VPT_TRY(rccl_load());
     HIP_TRY(hipSetDevice(r->ctx->device));
     vpt_gather *g = new vpt_gather();
-    memset(g, 0, sizeof(*g));
-    g->r = r; g->rank = rank; g->world = world; g->root = -1;
+    g->r = r; g->rank = rank; g->world = world;
     g->send_bytes = (size_t)r->W * r->local_h * 8;
     int rc = VPT_OK;
     hipError_t e;
@@ -479,11 +459,11 @@ extern "C" int vpt_gather_create(vpt_renderer *r, const void *id128, int rank, i
         if (e == hipSuccess) e = hipEventCreateWithFlags(&g->gathered[b], hipEventDisableTiming);
     }
     for (int b = 0; b < VPT_GATHER_RING && e == hipSuccess; b++) {
-        e = hipMalloc(&g->send[b], g->send_bytes);
-        if (e == hipSuccess) e = hipMalloc(&g->recv[b], g->send_bytes * world);
+        e = g->send[b].alloc(g->send_bytes);
+        if (e == hipSuccess) e = g->recv[b].alloc(g->send_bytes * world);
         if (e == hipSuccess) e = hipMemset(g->send[b], 0, g->send_bytes);
     }
-    if (e == hipSuccess) e = hipMalloc(&g->assembled, (size_t)r->W * r->H * 8);
+    if (e == hipSuccess) e = g->assembled.alloc((size_t)r->W * r->H);
     if (e != hipSuccess) rc = fail(VPT_ERR_HIP, "gather buffers: %s", hipGetErrorString(e));
     if (rc == VPT_OK) {
         ncclUniqueId_ id;
@@ -583,7 +563,7 @@ static int gather_enqueue_frame(vpt_gather *g, PassArgs &a, hipEvent_t t0 = null
     // the "rendered" events ride on the dispatches themselves (hipExtLaunchKernel stop events): a hipEventRecord behind the kernel
     // is a barrier packet of its own on the compute queue, 3-4.5 us per frame at every frame size (tools/r02_exp24.sh)
     r->stop_events = fused_passes ? nullptr : g->rendered[st.rendered_event]; r->stop_used = false;
-    a.render = st.in_place ? (uint2 *)((char *)g->recv[b] + st.render_offset) : (uint2 *)g->send[b];
+    a.render = st.in_place ? (uint2 *)((char *)g->recv[b].get() + st.render_offset) : (uint2 *)g->send[b].get();
     r->render_target = a.render;                                             // vpt_renderer_read(RENDER) returns the last frame's rows
     a.tm_table = nullptr; r->tm_valid = false;                               // (a fused tone mapper follows the renderer's own buffer only)
     if (t0) HIP_TRY(hipEventRecord(t0, cs));
@@ -612,7 +592,7 @@ static int gather_enqueue_frame(vpt_gather *g, PassArgs &a, hipEvent_t t0 = null
             for (int i = 0; i < st.npeers && ne == 0; i++) {
                 int p; uint64_t off;
                 VPT_TRY(vpt_gather_plan_recv(&st, g->rank, i, g->send_bytes, &p, &off));
-                ne = g_rccl.Recv((char *)g->recv[b] + off, g->send_bytes, /*ncclUint8*/ 1, p, g->comm, g->comm_stream);
+                ne = g_rccl.Recv((char *)g->recv[b].get() + off, g->send_bytes, /*ncclUint8*/ 1, p, g->comm, g->comm_stream);
             }
         } else {
             ne = g_rccl.Send(g->send[b], g->send_bytes, /*ncclUint8*/ 1, st.peer, g->comm, g->comm_stream);
@@ -681,7 +661,7 @@ extern "C" int vpt_gather_read_frame(vpt_gather *g, void *dst, size_t nbytes) {
     HIP_TRY(hipSetDevice(r->ctx->device));
     int b = (int)((g->frames - 1) % VPT_GATHER_RING);       // ordered behind that frame's gather by the communication stream itself
     hipLaunchKernelGGL(k_assemble_rows, dim3((unsigned)((r->W + 255) / 256), (unsigned)r->H), dim3(256), 0, g->comm_stream,
-                       (const uint2 *)g->recv[b], (uint2 *)g->assembled, r->W, r->H, r->local_h, r->G, r->R);
+                       (const uint2 *)g->recv[b].get(), (uint2 *)g->assembled.get(), r->W, r->H, r->local_h, r->G, r->R);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(dst, g->assembled, need, hipMemcpyDeviceToHost, g->comm_stream));
     HIP_TRY(hipStreamSynchronize(g->comm_stream));

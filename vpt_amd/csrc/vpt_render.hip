@@ -1,6 +1,7 @@
 // vpt_render.hip — the renderer entry points of the C-ABI: the four hooks of AbstractRenderer.render() / reset()
 // (AbstractRenderer.js:60-76), the single-launch render(), and frame sequences (vpt_renderer_play*).  The passes themselves are
 // launched by the family units (vpt_mcm.hip, vpt_march.hip, vpt_extra.hip).
+#include <memory>
 #include "vpt_internal.h"
 
 // The accumulating ray marchers (MIP, EAM, ISO; MCS and Depth under a condition).  A pixel whose ray misses the cube contributes a
@@ -165,8 +166,8 @@ extern "C" int vpt_renderer_render(vpt_renderer *r, const vpt_uniforms *u) {
 // frame sequences: `count` render() passes per host call, per-frame uniforms in a device table, optional hipGraph replay
 // ---------------------------------------------------------------------------------------------
 struct PlayGraph {
-    hipGraph_t graph; hipGraphExec_t exec;
-    int count; PassArgs key;
+    hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr;
+    int count = 0; PassArgs key = {};
 };
 void play_graph_free(PlayGraph *g) {
     if (!g) return;
@@ -195,8 +196,8 @@ int play_upload_table(vpt_renderer *r, const float *vars, int count, bool graph,
     vpt_context *c = r->ctx;
     static_assert(sizeof(FrameVar) == 8 * sizeof(float), "FrameVar is 8 floats");
     if (!r->frame_table) {
-        HIP_TRY(hipMalloc(&r->frame_table, (size_t)(VPT_FRAME_RING + VPT_FRAME_RING / 4) * sizeof(FrameVar)));
-        HIP_TRY(hipHostMalloc((void **)&r->frame_staging, (size_t)VPT_FRAME_RING * sizeof(FrameVar), hipHostMallocDefault));
+        HIP_TRY(r->frame_table.alloc((size_t)(VPT_FRAME_RING + VPT_FRAME_RING / 4)));
+        HIP_TRY(r->frame_staging.alloc((size_t)VPT_FRAME_RING));
         r->frames_played = 0;
     }
     // a staging slot (and a ring entry) is reused VPT_FRAME_RING frames later: never let more than half a ring be in flight on any stream
@@ -267,7 +268,8 @@ static int play_graph(vpt_renderer *r, PassArgs &a, const float *frame_vars, int
     PlayGraph *g = r->play_graph;
     if (!g || g->count != count || !play_key_equal(g->key, a)) {
         if (g) { HIP_TRY(hipStreamSynchronize(c->stream)); play_graph_free(g); r->play_graph = nullptr; }
-        g = new PlayGraph(); memset(g, 0, sizeof(*g));
+        std::unique_ptr<PlayGraph, void (*)(PlayGraph *)> fresh(new PlayGraph(), play_graph_free);   // an early return frees it
+        g = fresh.get();
         g->count = count; g->key = a;
         HIP_TRY(hipStreamBeginCapture(c->stream, hipStreamCaptureModeRelaxed));
         int rc = VPT_OK;
@@ -282,8 +284,8 @@ static int play_graph(vpt_renderer *r, PassArgs &a, const float *frame_vars, int
         hipError_t e = hipStreamEndCapture(c->stream, &g->graph);
         if (rc == VPT_OK && e != hipSuccess) rc = fail(VPT_ERR_HIP, "hipStreamEndCapture: %s", hipGetErrorString(e));
         if (rc == VPT_OK) { e = hipGraphInstantiate(&g->exec, g->graph, nullptr, nullptr, 0); if (e != hipSuccess) rc = fail(VPT_ERR_HIP, "hipGraphInstantiate: %s", hipGetErrorString(e)); }
-        if (rc != VPT_OK) { play_graph_free(g); return rc; }
-        r->play_graph = g;
+        VPT_TRY(rc);
+        r->play_graph = fresh.release();
     } else {
         // a cached graph is replayed without passing through launch_fused: the marchers' pass tracking is told by hand
         for (int i = 0; i < count; i++) VPT_TRY(marcher_track(r, a, true, v[i].mix));
@@ -314,7 +316,7 @@ static int play_mcm_multi(vpt_renderer *r, PassArgs &a, const float *frame_vars,
         if (count > VPT_FRAME_SLOTS) return fail(VPT_ERR_INVALID, "VPT_PLAY_FRAMES: %d frames, the ring holds %d", count, VPT_FRAME_SLOTS);
         if (!r->frame_ring) {
             const size_t bytes = (size_t)VPT_FRAME_SLOTS * r->W * r->local_h * 8;
-            HIP_TRY(hipMalloc(&r->frame_ring, bytes));
+            HIP_TRY(r->frame_ring.alloc(bytes / sizeof(uint2)));
             HIP_TRY(hipMemsetAsync(r->frame_ring, 0, bytes, c->stream));   // a shard's padding rows are never written: zero, as in the render buffer
         }
         ring = r->frame_ring; r->ring_frames = count;

@@ -219,7 +219,7 @@ __global__ void k_read_block(const uint8_t *__restrict__ vol, int nx, int ny, ui
 template <typename T>
 static void launch_gradient(const vpt_volume *src, vpt_volume *dst, int op, unsigned long long q) {
     const dim3 grid((unsigned)((src->nx + GR_TX - 1) / GR_TX), (unsigned)((src->ny + GR_TY - 1) / GR_TY), (unsigned)((src->nz + GR_TZ - 1) / GR_TZ));
-    const T *s = (const T *)src->linear; T *d = (T *)dst->linear;
+    const T *s = (const T *)src->linear.get(); T *d = (T *)dst->linear.get();
     hipStream_t st = src->ctx->stream;
     const bool aligned = src->nx % 4 == 0;
     if (op == VPT_GRADIENT_SOBEL) {
@@ -246,15 +246,7 @@ extern "C" int vpt_volume_derive_gradient(vpt_volume *src, int op, float gain, v
     VPT_TRY(volume_create(c, src->nx, src->ny, src->nz, src->norm16 ? VPT_FORMAT_RG16 : VPT_FORMAT_RG8, false, &d));   // every texel is written below
     if (src->norm16) launch_gradient<uint16_t>(src, d, op, (unsigned long long)qd);
     else launch_gradient<uint8_t>(src, d, op, (unsigned long long)qd);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { vpt_volume_destroy(d); return fail(VPT_ERR_HIP, "gradient kernel launch: %s", hipGetErrorString(e)); }
-    d->filter = src->filter;
-    d->dirty = true; d->any_upload = true;
-    int rc = vpt_volume_finalize(d);
-    if (rc != VPT_OK) { vpt_volume_destroy(d); return rc; }
-    for (vpt_renderer *r : c->renderers) r->streams.mark_dirty();      // side streams of split passes fork behind the build
-    *out = d;
-    return VPT_OK;
+    return volume_finish_derived(src, d, out);
 }
 
 extern "C" int vpt_volume_read_block(vpt_volume *v, int x, int y, int z, int w, int h, int d, void *host_dst, size_t nbytes) {
@@ -268,13 +260,9 @@ extern "C" int vpt_volume_read_block(vpt_volume *v, int x, int y, int z, int w, 
     if (x == 0 && y == 0 && w == v->nx && h == v->ny) {        // a run of whole z-slices is contiguous in the linear storage
         HIP_TRY(hipMemcpyAsync(host_dst, v->linear + (size_t)z * v->nx * v->ny * v->vox_bytes, need, hipMemcpyDeviceToHost, c->stream));
     } else {
-        if (v->staging_bytes < need) {
-            if (v->staging) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(v->staging)); v->staging = nullptr; v->staging_bytes = 0; }
-            HIP_TRY(hipMalloc(&v->staging, need));
-            v->staging_bytes = need;
-        }
+        HIP_TRY(v->staging.reserve(need, c->stream));
         int grid = (int)((texels + 255) / 256); if (grid > 4096) grid = 4096;
-        hipLaunchKernelGGL(k_read_block, dim3(grid), dim3(256), 0, c->stream, (const uint8_t *)v->linear, v->nx, v->ny, v->staging, x, y, z, w, h, d, v->vox_bytes);
+        hipLaunchKernelGGL(k_read_block, dim3(grid), dim3(256), 0, c->stream, (const uint8_t *)v->linear.get(), v->nx, v->ny, v->staging, x, y, z, w, h, d, v->vox_bytes);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(host_dst, v->staging, need, hipMemcpyDeviceToHost, c->stream));
     }
@@ -290,22 +278,18 @@ extern "C" int vpt_volume_histogram(vpt_volume *v, uint32_t *bins, size_t nbins)
     if (nbins != want) return fail(VPT_ERR_INVALID, "a histogram of an %s volume has %zu bins, not %zu", format_name(v->format), want, nbins);
     vpt_context *c = v->ctx;
     HIP_TRY(hipSetDevice(c->device));
-    uint32_t *dev = nullptr;
-    HIP_TRY(hipMalloc(&dev, want * sizeof(uint32_t)));
-    hipError_t e = hipMemsetAsync(dev, 0, want * sizeof(uint32_t), c->stream);
-    if (e == hipSuccess) {
-        const size_t nvox = (size_t)v->nx * v->ny * v->nz;
-        const size_t loads = nvox * (size_t)v->vox_bytes / 16 + 1;           // 16 bytes per thread and step
-        unsigned grid = (unsigned)std::min<size_t>((loads + 255) / 256, one ? 2048 : 1024);
-        if (one && v->norm16) hipLaunchKernelGGL(k_histogram<uint16_t>, dim3(grid), dim3(256), 0, c->stream, (const uint16_t *)v->linear, nvox, dev);
-        else if (one) hipLaunchKernelGGL(k_histogram<uint8_t>, dim3(grid), dim3(256), 0, c->stream, (const uint8_t *)v->linear, nvox, dev);
-        else if (v->norm16) hipLaunchKernelGGL(k_histogram_rg<uint16_t>, dim3(grid), dim3(256), 0, c->stream, (const uint16_t *)v->linear, nvox, dev);
-        else hipLaunchKernelGGL(k_histogram_rg<uint8_t>, dim3(grid), dim3(256), 0, c->stream, (const uint8_t *)v->linear, nvox, dev);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(bins, dev, want * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    hipFree(dev);
-    if (e != hipSuccess) return fail(VPT_ERR_HIP, "histogram: %s", hipGetErrorString(e));
+    DevBuf<uint32_t> dev;
+    HIP_TRY(dev.alloc(want));
+    HIP_TRY(hipMemsetAsync(dev, 0, want * sizeof(uint32_t), c->stream));
+    const size_t nvox = (size_t)v->nx * v->ny * v->nz;
+    const size_t loads = nvox * (size_t)v->vox_bytes / 16 + 1;           // 16 bytes per thread and step
+    unsigned grid = (unsigned)std::min<size_t>((loads + 255) / 256, one ? 2048 : 1024);
+    if (one && v->norm16) hipLaunchKernelGGL(k_histogram<uint16_t>, dim3(grid), dim3(256), 0, c->stream, (const uint16_t *)v->linear.get(), nvox, dev.get());
+    else if (one) hipLaunchKernelGGL(k_histogram<uint8_t>, dim3(grid), dim3(256), 0, c->stream, (const uint8_t *)v->linear.get(), nvox, dev.get());
+    else if (v->norm16) hipLaunchKernelGGL(k_histogram_rg<uint16_t>, dim3(grid), dim3(256), 0, c->stream, (const uint16_t *)v->linear.get(), nvox, dev.get());
+    else hipLaunchKernelGGL(k_histogram_rg<uint8_t>, dim3(grid), dim3(256), 0, c->stream, (const uint8_t *)v->linear.get(), nvox, dev.get());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(bins, dev, want * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return VPT_OK;
 }

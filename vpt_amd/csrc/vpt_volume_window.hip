@@ -296,15 +296,7 @@ extern "C" int vpt_volume_window(vpt_volume *src, double lo, double hi, int out_
         case SRC_S16: launch_window<SRC_S16>(src, d, p); break;
         default: launch_window<SRC_F32>(src, d, p); break;
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { vpt_volume_destroy(d); return fail(VPT_ERR_HIP, "window kernel launch: %s", hipGetErrorString(e)); }
-    d->filter = src->filter;
-    d->dirty = true; d->any_upload = true;
-    int rc = vpt_volume_finalize(d);
-    if (rc != VPT_OK) { vpt_volume_destroy(d); return rc; }
-    for (vpt_renderer *r : c->renderers) r->streams.mark_dirty();      // side streams of split passes fork behind the build
-    *out = d;
-    return VPT_OK;
+    return volume_finish_derived(src, d, out);
 }
 
 // enqueues k_range of `v` into dev[0..1] (encoded min, max) on the context's stream
@@ -333,13 +325,12 @@ extern "C" int vpt_volume_range(vpt_volume *v, double *lo, double *hi) {
         return fail(VPT_ERR_UNSUPPORTED, "the range is taken from one-channel volumes (R8, R16, R8_SNORM, R16_SNORM, R32F), not from %s", format_name(v->format));
     vpt_context *c = v->ctx;
     HIP_TRY(hipSetDevice(c->device));
-    uint32_t *dev = nullptr, host[2] = { 0u, 0u };
-    HIP_TRY(hipMalloc(&dev, 2 * sizeof(uint32_t)));
-    hipError_t e = enqueue_range(v, kind, dev);
-    if (e == hipSuccess) e = hipMemcpyAsync(host, dev, sizeof(host), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    hipFree(dev);
-    if (e != hipSuccess) return fail(VPT_ERR_HIP, "range: %s", hipGetErrorString(e));
+    DevBuf<uint32_t> dev;
+    uint32_t host[2] = { 0u, 0u };
+    HIP_TRY(dev.alloc(2));
+    HIP_TRY(enqueue_range(v, kind, dev));
+    HIP_TRY(hipMemcpyAsync(host, dev, sizeof(host), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     if (host[0] > host[1]) return fail(VPT_ERR_INVALID, "the %s volume holds no texel that is not NaN: it has no range", format_name(v->format));
     if (kind == SRC_F32) {
         float f[2];
@@ -367,25 +358,22 @@ extern "C" int vpt_volume_code_histogram(vpt_volume *v, uint32_t *bins, size_t n
     if (nbins != want) return fail(VPT_ERR_INVALID, "a code histogram of an %s volume has %zu bins, not %zu", format_name(v->format), want, nbins);
     vpt_context *c = v->ctx;
     HIP_TRY(hipSetDevice(c->device));
-    uint32_t *dev = nullptr;                                    // the bins, then k_range's two words
-    HIP_TRY(hipMalloc(&dev, (want + 2) * sizeof(uint32_t)));
-    hipError_t e = hipMemsetAsync(dev, 0, want * sizeof(uint32_t), c->stream);
-    if (e == hipSuccess && wide) e = enqueue_range(v, kind, dev + want);
-    if (e == hipSuccess) {
-        const size_t n = voxels(v);
-        const dim3 grid(stream_grid(n * (size_t)v->vox_bytes / 16 + 1, wide ? 1280 : 2048));
-        const void *s = (const void *)v->linear;
-        switch (kind) {
-            case SRC_U8: hipLaunchKernelGGL(k_code_histogram<SRC_U8>, grid, dim3(256), 0, c->stream, s, n, dev, (const uint32_t *)(dev + want)); break;
-            case SRC_S8: hipLaunchKernelGGL(k_code_histogram<SRC_S8>, grid, dim3(256), 0, c->stream, s, n, dev, (const uint32_t *)(dev + want)); break;
-            case SRC_U16: hipLaunchKernelGGL(k_code_histogram<SRC_U16>, grid, dim3(256), 0, c->stream, s, n, dev, (const uint32_t *)(dev + want)); break;
-            default: hipLaunchKernelGGL(k_code_histogram<SRC_S16>, grid, dim3(256), 0, c->stream, s, n, dev, (const uint32_t *)(dev + want)); break;
-        }
-        e = hipGetLastError();
+    DevBuf<uint32_t> buf;                                       // the bins, then k_range's two words
+    HIP_TRY(buf.alloc(want + 2));
+    uint32_t *dev = buf;
+    HIP_TRY(hipMemsetAsync(dev, 0, want * sizeof(uint32_t), c->stream));
+    if (wide) HIP_TRY(enqueue_range(v, kind, dev + want));
+    const size_t n = voxels(v);
+    const dim3 grid(stream_grid(n * (size_t)v->vox_bytes / 16 + 1, wide ? 1280 : 2048));
+    const void *s = (const void *)v->linear;
+    switch (kind) {
+        case SRC_U8: hipLaunchKernelGGL(k_code_histogram<SRC_U8>, grid, dim3(256), 0, c->stream, s, n, dev, (const uint32_t *)(dev + want)); break;
+        case SRC_S8: hipLaunchKernelGGL(k_code_histogram<SRC_S8>, grid, dim3(256), 0, c->stream, s, n, dev, (const uint32_t *)(dev + want)); break;
+        case SRC_U16: hipLaunchKernelGGL(k_code_histogram<SRC_U16>, grid, dim3(256), 0, c->stream, s, n, dev, (const uint32_t *)(dev + want)); break;
+        default: hipLaunchKernelGGL(k_code_histogram<SRC_S16>, grid, dim3(256), 0, c->stream, s, n, dev, (const uint32_t *)(dev + want)); break;
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(bins, dev, want * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    hipFree(dev);
-    if (e != hipSuccess) return fail(VPT_ERR_HIP, "code histogram: %s", hipGetErrorString(e));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(bins, dev, want * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return VPT_OK;
 }
