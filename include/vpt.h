@@ -364,9 +364,21 @@ VPT_API int vpt_renderer_set_render_target(vpt_renderer *r, void *device_ptr, si
  * line.  4 bytes per voxel of HBM.  Same taps, same lerps: results identical.  0 = the apron bricks, as the other renderers; 2 = records
  * where the bricks are beyond the Infinity Cache (> 512 MiB: measured 2-4 % faster there, 4-16 % slower on volumes that fit it). */
 #define VPT_OPTION_COLUMN_RECORDS 10
+/* VPT_OPTION_SETTLED_MISS (default 1; MCM renderer with the tile classes in force, LINEAR filter, one-channel byte volumes; extension): under a
+ * 1x1 environment with finite colour every event of a MISS tile's pixel deposits the same constant, so its running mean stops moving within
+ * the first events after a reset (at once for white or black; the library proves it for the colour at hand, with one 16-byte read-back where
+ * it has to).  From then on the MISS-tile pass neither reads nor writes [radiance, samples] and stores no frame texel — 16 of the 32 state
+ * bytes per pixel each way, no 8-byte texel; every event still runs, draw for draw, its sample executed — as long as the environment has
+ * not been set since the reset, no display table rides on the fused store, the per-pixel sample count stays below 2^24 and (fused passes)
+ * the destination has received every MISS texel once since the reset.  The samples owed are added before anything else reads them
+ * (vpt_renderer_read, whole-image and bucket kernels, another matrix, an environment change, this option set to 0).  Every buffer a caller
+ * can read is identical either way. */
+#define VPT_OPTION_SETTLED_MISS 11
 VPT_API int vpt_renderer_set_option(vpt_renderer *r, int option, int value);
 /* (extension) how many buckets of frames vpt_renderer_play_into has run through the bucket kernels so far (VPT_OPTION_BUCKET_KERNEL) */
 VPT_API int vpt_renderer_bucket_launches(vpt_renderer *r, uint64_t *launches);
+/* (extension) how many passes so far ran their MISS tiles through the settled kernel (VPT_OPTION_SETTLED_MISS) */
+VPT_API int vpt_renderer_settled_passes(vpt_renderer *r, uint64_t *passes);
 /* (extension) tiles of each class under the last reset's matrix (all HIT when no classification is in force) and the
  * VPT_OPTION_VERIFY_TILE_CLASSES counter; any pointer may be null */
 VPT_API int vpt_renderer_tile_classes(vpt_renderer *r, int *hit_tiles, int *miss_tiles, uint64_t *violations);

@@ -336,7 +336,7 @@ static int renderer_alloc_buffers(vpt_renderer *r) {
     r->frame_ring.reset(); r->ring_frames = 0;
     r->frame.reset(); r->acc.reset(); r->render.reset(); r->scratch.reset(); r->ndc_x.reset(); r->ndc_y.reset();
     for (int i = 0; i < 4; i++) r->st[i].reset();
-    r->cls.valid = false; r->cls.stale = false;            // new geometry, zeroed state: classes come back with the next reset
+    r->cls.valid = false; r->cls.stale = false; r->cls.pending = 0;   // new geometry, zeroed state: classes come back with the next reset
     r->cls.built = false;
     r->cls.passes = 0; r->cls.fused_passes = 0; r->cls.reset_seen = false; r->cls.n_complete = 0;   // (zeroed buffers are not a reset: nothing is skipped before one)
     r->dos_cur = 0; r->dos_rect_valid = false;
@@ -409,6 +409,7 @@ extern "C" int vpt_renderer_set_environment(vpt_renderer *r, const uint8_t *rgba
     if (!r || !rgba) return fail(VPT_ERR_INVALID, "null argument");
     VPT_TRY(join_side(r));
     if (w < 1 || h < 1 || w > 16384 || h > 16384) return fail(VPT_ERR_INVALID, "environment size %dx%d out of range", w, h);
+    if (r->kind == VPT_RENDERER_MCM) { VPT_TRY(mcm_catch_up(r)); r->cls.env_changed = true; }   // (the MISS pixels' running mean moves again: k_mcm_miss_settled waits for a reset)
     std::vector<float4> t((size_t)w * h);
     for (size_t i = 0; i < t.size(); i++)
         t[i] = make_float4((float)rgba[4 * i] / 255.0f, (float)rgba[4 * i + 1] / 255.0f,
@@ -439,6 +440,7 @@ extern "C" int vpt_renderer_set_environment_texels(vpt_renderer *r, const void *
     if (format < VPT_ENV_RGBA8 || format > VPT_ENV_RGBE8) return fail(VPT_ERR_INVALID, "unknown environment format %d", format);
     if (w < 1 || h < 1 || w > 16384 || h > 16384) return fail(VPT_ERR_INVALID, "environment size %dx%d out of range", w, h);
     VPT_TRY(join_side(r));                                   // side streams may still read the old map
+    if (r->kind == VPT_RENDERER_MCM) { VPT_TRY(mcm_catch_up(r)); r->cls.env_changed = true; }   // (as vpt_renderer_set_environment)
     vpt_context *c = r->ctx;
     HIP_TRY(hipSetDevice(c->device));
     static const size_t texel_bytes[] = { 4, 8, 16, 4 };
@@ -906,6 +908,7 @@ extern "C" int vpt_renderer_read(vpt_renderer *r, int buffer, void *dst, size_t 
     } else if (buffer >= VPT_BUFFER_MCM_POSITION && buffer <= VPT_BUFFER_MCM_RADIANCE) {
         if (r->kind != VPT_RENDERER_MCM) return fail(VPT_ERR_INVALID, "not an MCM renderer");
         if (buffer == VPT_BUFFER_MCM_POSITION || buffer == VPT_BUFFER_MCM_TRANSMITTANCE) VPT_TRY(mcm_materialize(r));
+        if (buffer == VPT_BUFFER_MCM_RADIANCE) VPT_TRY(mcm_catch_up(r));    // the samples k_mcm_miss_settled has not written yet
         elem = 16; src = r->st[buffer - VPT_BUFFER_MCM_POSITION];
     } else {
         return fail(VPT_ERR_INVALID, "unknown buffer %d", buffer);
@@ -949,6 +952,11 @@ extern "C" int vpt_renderer_render_buffer_device(vpt_renderer *r, void **ptr, si
 extern "C" int vpt_renderer_bucket_launches(vpt_renderer *r, uint64_t *launches) {
     if (!r || !launches) return fail(VPT_ERR_INVALID, "null argument");
     *launches = r->bucket_launches;
+    return VPT_OK;
+}
+extern "C" int vpt_renderer_settled_passes(vpt_renderer *r, uint64_t *passes) {
+    if (!r || !passes) return fail(VPT_ERR_INVALID, "null argument");
+    *passes = r->cls.settled_passes;
     return VPT_OK;
 }
 extern "C" int vpt_renderer_join(vpt_renderer *r) {
@@ -1005,6 +1013,10 @@ extern "C" int vpt_renderer_set_option(vpt_renderer *r, int option, int value) {
         case VPT_OPTION_BUCKET_KERNEL:
             if (r->kind != VPT_RENDERER_MCM) return fail(VPT_ERR_UNSUPPORTED, "VPT_OPTION_BUCKET_KERNEL: an MCM option");
             r->bucket_kernel = value != 0; return VPT_OK;
+        case VPT_OPTION_SETTLED_MISS:
+            if (r->kind != VPT_RENDERER_MCM) return fail(VPT_ERR_UNSUPPORTED, "VPT_OPTION_SETTLED_MISS: an MCM option");
+            if (!value) VPT_TRY(mcm_catch_up(r));
+            r->cls.settled_opt = value != 0; return VPT_OK;
         case VPT_OPTION_VERIFY_TILE_CLASSES:
             if (r->kind != VPT_RENDERER_MCM) return fail(VPT_ERR_UNSUPPORTED, "VPT_OPTION_VERIFY_TILE_CLASSES: an MCM option");
             r->cls.verify = value != 0; return VPT_OK;

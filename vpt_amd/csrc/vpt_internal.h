@@ -115,6 +115,15 @@ struct TileClasses {
     // render destinations (the renderer's own buffer, a caller's target, the slots of a bucket or of the gather ring) that a WHOLE-image fused
     // pass has written since the reset: only there do the skipped tiles hold their final texels (marcher_track)
     const void *complete[VPT_COMPLETE_DESTS] = {}; int n_complete = 0;
+    // MCM, the settled form of the MISS-tile pass (VPT_OPTION_SETTLED_MISS, k_mcm_miss_settled; vpt_mcm.hip "settled").  `complete` holds for
+    // MCM the destinations whose MISS texels all show the settled radiance.
+    bool settled_opt = true;
+    uint64_t events = 0;           // events of every pixel since the reset (= `samples` of a MISS pixel, `pending` included)
+    uint32_t pending = 0;          // events k_mcm_miss_settled has run that the samples array does not show yet (k_mcm_materialize adds them)
+    bool env_changed = false;      // the environment was set since the reset: the MISS pixels' mean is on the move again until the next one
+    int settle = 0, probes = 0;    // 0: not known whether the MISS pixels' radiance is final, 1: proven, 2: given up until the next reset; read-backs spent on it
+    uint64_t complete_events = 0;  // `events` behind the pass that last rebuilt `complete` while settle == 0
+    uint64_t settled_passes = 0;   // passes whose MISS tiles ran the settled kernel (vpt_renderer_settled_passes)
 };
 // Split passes (VPT_OPTION_SPLIT_STREAMS = K): a sampling pass is dealt to up to K streams as tile-row ranges or parts of a tile list;
 // range i runs on range_stream(r, i), the context's stream for i = 0 and a private side stream otherwise.  A pixel's pass depends on
@@ -262,6 +271,7 @@ int mcm_render_frame(vpt_renderer *r, const PassArgs &a);
 int mcm_multi(vpt_renderer *r, const PassArgs &a, uint32_t npasses, uint2 *ring);
 int mcm_before_pass(vpt_renderer *r, const PassArgs &a, bool *same_matrix);
 int mcm_materialize(vpt_renderer *r);
+int mcm_catch_up(vpt_renderer *r);                                            // mcm_materialize if k_mcm_miss_settled left samples pending
 int mcm_bucket_ready(vpt_renderer *r, const PassArgs &a, bool *ready);
 int mcm_bucket(vpt_renderer *r, const PassArgs &a, const FrameVar *v, int count, void *ring, uint32_t slot_pixels, bool last_to_render_buffer,
                const uint8_t *display_table);

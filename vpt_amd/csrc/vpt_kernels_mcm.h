@@ -333,14 +333,17 @@ VPT_DEV FastPixel fast_pixel(const PassArgs &a, float px, float py) {
     c.jx = 0x1p-31f * a.inv_w; c.jy = 0x1p-31f * a.inv_h;
     return c;
 }
-template <bool NOBLUR = false>
+// DEPOSIT = false: resetPhoton alone (k_mcm_miss_settled: the running mean sits at a fixed point, the host counts the samples)
+template <bool NOBLUR = false, bool DEPOSIT = true>
 VPT_DEV void fast_path_end(const PassArgs &a, const FastPixel &c, uint32_t &state, Photon &ph, f3 rad, float px, float py) {
     const float *m = a.mvp_inv.m;
-    ph.samples++;
-    float inv_n = hw_rcp((float)ph.samples);
-    ph.radiance.x = fmaf(rad.x - ph.radiance.x, inv_n, ph.radiance.x);
-    ph.radiance.y = fmaf(rad.y - ph.radiance.y, inv_n, ph.radiance.y);
-    ph.radiance.z = fmaf(rad.z - ph.radiance.z, inv_n, ph.radiance.z);
+    if (DEPOSIT) {
+        ph.samples++;
+        float inv_n = hw_rcp((float)ph.samples);
+        ph.radiance.x = fmaf(rad.x - ph.radiance.x, inv_n, ph.radiance.x);
+        ph.radiance.y = fmaf(rad.y - ph.radiance.y, inv_n, ph.radiance.y);
+        ph.radiance.z = fmaf(rad.z - ph.radiance.z, inv_n, ph.radiance.z);
+    }
     if (NOBLUR || a.blur == 0.0f) {
         state = pcg(pcg(state));                          // the disk sample's two draws (multiplied by blur = 0)
         float ax = fmaf(pcg_float(state), c.jx, -a.inv_w);
@@ -622,7 +625,8 @@ VPT_DEV void miss_sample_any(const PassArgs &a, const float4 *tf, f3 q) {
     }
 }
 // LATE: the sample is consumed after the path end (under whose arithmetic its load flies) instead of right where the shader samples
-template <int V, bool CHECK, bool LATE>
+// DEPOSIT = false: the settled form (k_mcm_miss_settled) — every draw, position and sample as here, without the deposit
+template <int V, bool CHECK, bool LATE, bool DEPOSIT = true>
 VPT_DEV void mcm_events_miss(const PassArgs &a, const float4 *tf, Photon &ph, float px, float py, f3 from0) {
     uint32_t state = hash3(__float_as_uint(ndc_to_uv(px)), __float_as_uint(ndc_to_uv(py)), __float_as_uint(a.seed));
     for (uint32_t s = 0u; s < a.steps; s++) {
@@ -634,13 +638,15 @@ VPT_DEV void mcm_events_miss(const PassArgs &a, const float4 *tf, Photon &ph, fl
         else l = miss_sample_issue<CHECK>(a, ph.position, a.violations);
         if (!LATE && !OTHER) miss_sample_finish(a, tf, l);
         random_uniform(state);                                     // the wheel draw (its value decides nothing out of bounds)
-        float4 env = sample_environment(a.env, ph.direction);      // transmittance is (1, 1, 1): radiance = 1 * env, exactly env
-        photon_deposit(ph, f3{ env.x, env.y, env.z });
+        if (DEPOSIT) {
+            float4 env = sample_environment(a.env, ph.direction);  // transmittance is (1, 1, 1): radiance = 1 * env, exactly env
+            photon_deposit(ph, f3{ env.x, env.y, env.z });
+        }
         reset_photon<true>(state, ph, px, py, a, from0);
         if (LATE && !OTHER) miss_sample_finish(a, tf, l);
     }
 }
-template <int V, bool CHECK, bool LATE>
+template <int V, bool CHECK, bool LATE, bool DEPOSIT = true>
 VPT_DEV void mcm_events_miss_fast(const PassArgs &a, const float4 *tf, const FastPixel &c, Photon &ph, float px, float py) {
     const float ld = -0.6931471805599453f * a.inv_extinction, ld32 = -32.0f * ld;
     uint32_t state = hash3(__float_as_uint(ndc_to_uv(px)), __float_as_uint(ndc_to_uv(py)), __float_as_uint(a.seed));
@@ -653,8 +659,9 @@ VPT_DEV void mcm_events_miss_fast(const PassArgs &a, const float4 *tf, const Fas
         else l = miss_sample_issue<CHECK>(a, ph.position, a.violations);
         if (!LATE && !OTHER) miss_sample_finish(a, tf, l);
         state = pcg(state);                                        // the wheel draw
-        float4 env = sample_environment(a.env, ph.direction);
-        fast_path_end<true>(a, c, state, ph, f3{ env.x, env.y, env.z }, px, py);
+        f3 rad = { 0.0f, 0.0f, 0.0f };
+        if (DEPOSIT) { float4 env = sample_environment(a.env, ph.direction); rad = f3{ env.x, env.y, env.z }; }
+        fast_path_end<true, DEPOSIT>(a, c, state, ph, rad, px, py);
         if (LATE && !OTHER) miss_sample_finish(a, tf, l);
     }
 }
@@ -693,12 +700,53 @@ __attribute__((amdgpu_waves_per_eu(((V & (VPT_V_NEAREST | VPT_V_RG | VPT_V_F32 |
     a.st3[p.k] = make_float4(ph.radiance.x, ph.radiance.y, ph.radiance.z, (float)ph.samples);
     if (FUSE_RENDER) store_frame(a, p, pack_half4(ph.radiance.x, ph.radiance.y, ph.radiance.z, 1.0f));
 }
+// The settled form of k_mcm_miss (VPT_OPTION_SETTLED_MISS; plain LINEAR one-channel byte volumes).  Under a 1x1 environment every deposit of
+// a MISS pixel is the same constant e, so the running mean r += (e - r) / n stops moving once |e - r| / n is below half the spacing of the
+// floats around r — for e with 1 + (e - 1) == e (white, black, ...) from the first event on, else after a handful (the host proves which:
+// vpt_mcm.hip settle_*).  From then on radiance and the frame texel pack_half4(radiance, 1) never change and `samples` rises by `steps` per
+// pass for every MISS pixel alike: this kernel runs the same events, draw for draw, position for position, the sample executed and
+// consumed as in k_mcm_miss, and neither loads nor stores [radiance, samples], runs no running mean and stores no frame texel: 16 B each
+// way per pixel instead of 32 + 32 + 8.  The host counts the events it owes `samples` and k_mcm_materialize adds them before anything
+// else reads that array; a fused pass takes this form only into a destination that already holds every MISS texel.
+template <int V, bool CHECK, bool LATE>
+__global__ void __launch_bounds__(VPT_BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) k_mcm_miss_settled(PassArgs a) {
+    frame_select(a, 0);
+    Pix p = map_pixel(a.pm);
+    float4 s1 = make_float4(0.0f, 0.0f, 1.0f, 0.0f);
+    f3 s0 = { 0.0f, 0.0f, 0.0f };
+    if (p.tile) {
+        s1 = a.st1[p.k];
+        if (a.miss_load_pos) s0 = ((const f3 *)a.st0)[p.k];
+    }
+    extern __shared__ float4 lds_raw[];
+    const float4 *tf = stage_tf(lds_raw, a);
+    if (!p.valid) return;
+    const float px = ndc_col(a.pm, p.i), py = ndc_row(a.pm, p.j);
+    Photon ph;
+    ph.direction = f3{ s1.x, s1.y, s1.z };
+    ph.bounces = 0u;
+    ph.transmittance = f3{ 1.0f, 1.0f, 1.0f };
+    ph.radiance = f3{ 0.0f, 0.0f, 0.0f };
+    ph.samples = 0u;
+    if (V & VPT_V_FAST) {
+        const FastPixel c = fast_pixel(a, px, py);
+        ph.position = a.miss_load_pos ? s0 : photon_start_fast(c.from0, ph.direction);
+        mcm_events_miss_fast<V & ~VPT_V_FAST, CHECK, LATE, false>(a, tf, c, ph, px, py);
+    } else {
+        const f3 from0 = unproject_near(px, py, a);
+        ph.position = a.miss_load_pos ? s0 : photon_start(from0, ph.direction);
+        mcm_events_miss<V, CHECK, LATE, false>(a, tf, ph, px, py, from0);
+    }
+    a.st1[p.k] = make_float4(ph.direction.x, ph.direction.y, ph.direction.z, 0.0f);
+}
 // brings the position / transmittance arrays of the MISS tiles up to date: position = photon_start(from0, direction) in the
-// arithmetic of the variant that ran the last pass, transmittance = (1, 1, 1)
+// arithmetic of the variant that ran the last pass, transmittance = (1, 1, 1); `pending` > 0: the events k_mcm_miss_settled ran since
+// `samples` was last written are added to it (the count as k_mcm_miss would have stored it: both are exact below 2^24)
 template <bool FAST>
-__global__ void __launch_bounds__(VPT_BLOCK) k_mcm_materialize(PassArgs a) {
+__global__ void __launch_bounds__(VPT_BLOCK) k_mcm_materialize(PassArgs a, uint32_t pending) {
     Pix p = map_pixel(a.pm);
     if (!p.valid) return;
+    if (pending) a.st3[p.k].w = (float)((uint32_t)(a.st3[p.k].w + 0.5f) + pending);
     const float px = ndc_col(a.pm, p.i), py = ndc_row(a.pm, p.j);
     const float4 s1 = a.st1[p.k];
     const f3 dir = { s1.x, s1.y, s1.z };

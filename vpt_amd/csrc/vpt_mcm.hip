@@ -46,16 +46,78 @@ int mcm_materialize(vpt_renderer *r) {
     memcpy(a.mvp_inv.m, r->cls.mvp, sizeof(r->cls.mvp));
     a.pm.tile_list = r->cls.list + r->cls.n_hit; a.pm.list_n = r->cls.n_miss;
     if (r->cls.n_miss > 0) {
-        if (r->cls.stale_fast) hipLaunchKernelGGL(k_mcm_materialize<true>, dim3((unsigned)r->cls.n_miss), dim3(VPT_BLOCK), 0, r->ctx->stream, a);
-        else hipLaunchKernelGGL(k_mcm_materialize<false>, dim3((unsigned)r->cls.n_miss), dim3(VPT_BLOCK), 0, r->ctx->stream, a);
+        if (r->cls.stale_fast) hipLaunchKernelGGL(k_mcm_materialize<true>, dim3((unsigned)r->cls.n_miss), dim3(VPT_BLOCK), 0, r->ctx->stream, a, r->cls.pending);
+        else hipLaunchKernelGGL(k_mcm_materialize<false>, dim3((unsigned)r->cls.n_miss), dim3(VPT_BLOCK), 0, r->ctx->stream, a, r->cls.pending);
         HIP_TRY(hipGetLastError());
     }
-    r->cls.stale = false;
+    r->cls.stale = false; r->cls.pending = 0;
     return VPT_OK;
+}
+int mcm_catch_up(vpt_renderer *r) { return r->cls.pending ? mcm_materialize(r) : VPT_OK; }
+
+// ---- the settled form of the MISS-tile pass (k_mcm_miss_settled) ---------------------------------------------------------------------
+// Every event of a MISS pixel deposits the constant e of a 1x1 environment into the running mean r <- r + (e - r) / n, from r = 1 at the
+// reset (k_mcm_reset).  The first deposit (n = 1, and 1 / 1 = 1 in both arithmetic variants) leaves fl(1 + fl(e - 1)): e itself for white,
+// black and every e with 1 + (e - 1) == e — then e - r = 0 for good (settle_from_reset).  Any other e is approached to within a few units in
+// the last place and the mean stops where the step |e - r| / n falls below half the spacing of the floats around r; all MISS pixels hold
+// the same (r, n), so one of them read back between two passes decides it (settle_probe) for both variants: the bound below allows for a
+// reciprocal that is off by an ulp and for a fused or an unfused multiply-add, and the step only shrinks as n grows.
+static bool settle_env_usable(const vpt_renderer *r) {
+    return r->env_w == 1 && r->env_h == 1 && std::isfinite(r->env_const.x) && std::isfinite(r->env_const.y) && std::isfinite(r->env_const.z);
+}
+static bool settle_from_reset(const vpt_renderer *r) {
+    if (!settle_env_usable(r)) return false;
+    const float e[3] = { r->env_const.x, r->env_const.y, r->env_const.z };
+    for (int i = 0; i < 3; i++) {
+        volatile float d = e[i] - 1.0f, r1 = 1.0f + d;
+        if (!(r1 == e[i])) return false;
+    }
+    return true;
+}
+static bool settle_channel_final(float e, float rad, uint64_t n) {
+    if (!std::isfinite(rad)) return false;
+    if (e == rad) return true;
+    if (!std::isnormal(rad)) return false;
+    const double gap = std::min((double)std::nextafter(rad, INFINITY) - (double)rad, (double)rad - (double)std::nextafter(rad, -INFINITY));
+    return std::fabs((double)e - (double)rad) * 1.001 / (double)(n + 1) < 0.49 * gap;
+}
+// reads [radiance, samples] of one MISS pixel back (a host wait: at most a few per reset, and only for an environment colour that
+// settle_from_reset cannot decide)
+static int settle_probe(vpt_renderer *r) {
+    TileClasses &c = r->cls;
+    c.probes++;
+    const uint32_t *list = c.staging[c.stage_next ^ 1];          // the host copy of the lists on the device (classes_build)
+    long long k = -1;
+    for (int i = 0; list && i < c.n_miss && k < 0; i++) {
+        const int tx = (int)(list[c.n_hit + i] & 0xffffu), ty = (int)(list[c.n_hit + i] >> 16), l = ty * VPT_TILE;
+        const int lb = l / r->R, j = r->G == 1 ? l : (lb * r->G + r->g) * r->R + (l - lb * r->R);
+        if (tx < r->tiles_x && l < r->local_h && j < r->H) k = ((long long)ty * r->tiles_x + tx) * VPT_BLOCK;   // the tile's first pixel (map_pixel)
+    }
+    if (k >= 0) {
+        VPT_TRY(join_side(r));
+        float4 v;
+        HIP_TRY(hipMemcpyAsync(&v, r->st[3].get() + k, sizeof(v), hipMemcpyDeviceToHost, r->ctx->stream));
+        HIP_TRY(hipStreamSynchronize(r->ctx->stream));
+        const bool counted = v.w >= 0.0f && (uint64_t)(v.w + 0.5f) == c.events;
+        if (counted && settle_channel_final(r->env_const.x, v.x, c.events) && settle_channel_final(r->env_const.y, v.y, c.events) &&
+            settle_channel_final(r->env_const.z, v.z, c.events)) {
+            c.settle = 1;
+            if (c.complete_events != c.events) c.n_complete = 0;   // destinations written before the last pass show an earlier mean
+            return VPT_OK;
+        }
+    }
+    if (k < 0 || c.probes >= 4) c.settle = 2;
+    return VPT_OK;
+}
+static bool settled_destination(const vpt_renderer *r, const void *dest) {
+    for (int i = 0; i < r->cls.n_complete; i++) if (r->cls.complete[i] == dest) return true;
+    return false;
 }
 // an MCM reset with matrix u->mvp_inverse has just been enqueued
 static int mcm_classify(vpt_renderer *r, const vpt_uniforms *u) {
     r->cls.valid = false; r->cls.stale = false;               // the reset rewrote every array
+    r->cls.events = 0; r->cls.pending = 0; r->cls.env_changed = false; r->cls.n_complete = 0; r->cls.complete_events = 0;
+    r->cls.probes = 0; r->cls.settle = settle_from_reset(r) ? 1 : 0;
     if (!r->cls.enabled || u->blur != 0.0f) return VPT_OK;
     return classes_build(r, u->mvp_inverse);
 }
@@ -104,6 +166,25 @@ static int launch_mcm_classes(vpt_renderer *r, const PassArgs &a) {
     else km = fast ? (late ? (PassKernel)k_mcm_miss<FUSE, VPT_V_FAST, false, true> : (PassKernel)k_mcm_miss<FUSE, VPT_V_FAST, false, false>)
                    : (PassKernel)k_mcm_miss<FUSE, 0, false, true>;
     if (!kh || !km) return fail(VPT_ERR_INVALID, "no MCM tile-class kernels for variant %d", variant_of(r));
+    // the settled form of the MISS part: the radiance of the MISS pixels is proven final, their samples stay countable in a float, and (a
+    // fused pass) the destination already shows every MISS texel and no display table rides on the store
+    TileClasses &c = r->cls;
+    const bool wanted = c.settled_opt && !(vm & ~VPT_V_WIDE) && c.n_miss > 0 && !c.env_changed && !r->no_split && settle_env_usable(r) &&
+                        a.steps >= 1u && c.events >= 1 && c.events + a.steps < (1ull << 24);
+    if (wanted && c.settle == 0 && c.pending == 0) VPT_TRY(settle_probe(r));
+    const bool settled = wanted && c.settle == 1 && (!FUSE || (a.tm_table == nullptr && settled_destination(r, a.render)));
+    if (settled) {
+        if (check) km = fast ? (late ? (PassKernel)k_mcm_miss_settled<VPT_V_FAST, true, true> : (PassKernel)k_mcm_miss_settled<VPT_V_FAST, true, false>)
+                             : (PassKernel)k_mcm_miss_settled<0, true, true>;
+        else km = fast ? (late ? (PassKernel)k_mcm_miss_settled<VPT_V_FAST, false, true> : (PassKernel)k_mcm_miss_settled<VPT_V_FAST, false, false>)
+                       : (PassKernel)k_mcm_miss_settled<0, false, true>;
+    } else {
+        VPT_TRY(mcm_catch_up(r));
+        if (FUSE && c.n_miss > 0 && a.steps >= 1u && c.settle != 2) {     // this pass leaves every MISS texel of its destination behind
+            if (c.settle == 0) { c.n_complete = 0; c.complete_events = c.events + a.steps; }   // (a later proof covers the last pass's texels only)
+            if (!settled_destination(r, a.render) && c.n_complete < VPT_COMPLETE_DESTS) c.complete[c.n_complete++] = (const void *)a.render;
+        }
+    }
     const size_t lds_hit = lds_bytes(r), lds_miss = (size_t)r->tf_w * 2 * sizeof(float4);
     VPT_TRY(lds_prepare((const void *)kh, lds_hit));
     const int k = split_allowed(r) ? r->split : 1;
@@ -156,6 +237,7 @@ static int launch_mcm_classes(vpt_renderer *r, const PassArgs &a) {
         }
     }
     r->cls.stale = r->cls.n_miss > 0; r->cls.stale_fast = fast;
+    if (settled) { c.pending += a.steps; c.settled_passes++; }
     return VPT_OK;
 }
 
@@ -188,6 +270,7 @@ static void bucket_kernels(int v, bool early, BucketKernel *kh, BucketKernel *km
 int mcm_bucket(vpt_renderer *r, const PassArgs &a, const FrameVar *v, int count, void *ring, uint32_t slot_pixels, bool last_to_render_buffer,
                const uint8_t *display_table) {
     if (count < 1 || count > VPT_BUCKET_FRAMES) return fail(VPT_ERR_INVALID, "a bucket launch holds 1..%d frames", VPT_BUCKET_FRAMES);
+    VPT_TRY(mcm_catch_up(r));                                  // k_mcm_bucket_miss counts on from the samples array
     const bool fast = r->fast_math != 0;
     // HIT tiles few enough to be resident at once at the kernel's four waves per SIMD: the form with the early path end (launch_mcm_classes)
     const bool early = r->hit_form == 2 || (r->hit_form == 0 && r->cls.n_hit <= 1024);
@@ -214,6 +297,7 @@ int mcm_bucket(vpt_renderer *r, const PassArgs &a, const FrameVar *v, int count,
     r->cls.stale = r->cls.n_miss > 0; r->cls.stale_fast = fast;
     r->tm_valid = false;
     r->bucket_launches++;
+    r->cls.events += (uint64_t)a.steps * (uint64_t)count;
     return VPT_OK;
 }
 
@@ -260,10 +344,15 @@ static int launch_mcm_pass(vpt_renderer *r, const PassArgs &a) {
     // vpt_renderer_play_into*, a sequence being captured — runs the general kernel.
     const bool two_streams = split_allowed(r);
     if (two_streams) VPT_TRY(ensure_split_streams(r));
-    if (same && r->cls.enabled && mcm_classes_runnable(r, a) && (two_streams || r->cls.one_stream)) return launch_mcm_classes<FUSE>(r, a);
-    VPT_TRY(mcm_materialize(r));
-    if (r->mcm_persistent && persistent_volume(r->vol)) { LAUNCH_MCM_PERSIST(FUSE, r, a); return VPT_OK; }
-    return mcm_general_pass(r, a, FUSE);
+    int rc;
+    if (same && r->cls.enabled && mcm_classes_runnable(r, a) && (two_streams || r->cls.one_stream)) rc = launch_mcm_classes<FUSE>(r, a);
+    else {
+        VPT_TRY(mcm_materialize(r));
+        if (r->mcm_persistent && persistent_volume(r->vol)) { LAUNCH_MCM_PERSIST(FUSE, r, a); rc = VPT_OK; }
+        else rc = mcm_general_pass(r, a, FUSE);
+    }
+    if (rc == VPT_OK) r->cls.events += a.steps;              // every form runs `steps` events of every pixel (launch_mcm_classes looks at the count before its pass)
+    return rc;
 }
 
 // ---- what vpt_render.hip calls ------------------------------------------------------------------------------------------

@@ -290,6 +290,7 @@ static int play_graph(vpt_renderer *r, PassArgs &a, const float *frame_vars, int
         // a cached graph is replayed without passing through launch_fused: the marchers' pass tracking is told by hand
         for (int i = 0; i < count; i++) VPT_TRY(marcher_track(r, a, true, v[i].mix));
         r->cls.list_now = false;
+        if (r->kind == VPT_RENDERER_MCM) r->cls.events += (uint64_t)a.steps * (uint64_t)count;   // (as mcm_pass counts them)
     }
     {
         Timed t(r, true, (uint32_t)count);       // a replay is timed as a whole: events inside a graph cannot be read back

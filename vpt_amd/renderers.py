@@ -332,6 +332,12 @@ class AbstractRenderer(PropertyBag):
         N.check(N.lib().vpt_renderer_bucket_launches(self._h, C.byref(n)))
         return n.value
 
+    def settled_passes(self):
+        """passes so far whose MISS tiles ran the settled kernel (OPTION_SETTLED_MISS)"""
+        n = C.c_uint64(0)
+        N.check(N.lib().vpt_renderer_settled_passes(self._h, C.byref(n)))
+        return n.value
+
     def read_frame_slot(self, slot):
         """frame `slot` of the last play(frames=True) call: [local rows][W][4] float16"""
         out = np.empty((self.local_rows(), self._size()[0], 4), dtype=np.float16)
