@@ -8,6 +8,8 @@
                                      gradient magnitude is derived on the device as the volume's second channel)
     python examples/render_png.py --volume ct.raw --dims 512 512 300 --bits 16 --signed --window -200,400 ...   (16-bit samples, placed on the
                                      transfer function's axis by a window derived on the device; --window auto: the 0.5 / 99.5 percentiles)
+    python examples/render_png.py --window auto --smooth 1 --reduce 1 --gradient sobel ...   (smoothed, then reduced to half resolution, on the
+                                     device, before the gradient is derived)
     python examples/render_png.py --renderer mcm --env sky.hdr --tonemapper aces ...   (a Radiance .hdr environment map lights MCS / MCM)
 
 Without --volume a synthetic 128^3 sphere with lattice noise is used.  PNG encoding is plain zlib (no imaging library)."""
@@ -42,6 +44,8 @@ def main():
     ap.add_argument("--window", default=None, help="LO,HI | range | auto: window the volume's values to the transfer function's axis "
                                                    "(auto: the 0.5 / 99.5 percentiles; the range for a float volume)")
     ap.add_argument("--window-format", default="r8", choices=["r8", "r16"])
+    ap.add_argument("--smooth", type=int, default=None, metavar="N", help="binomial 3 x 3 x 3 smoothing passes (1 .. 8) on the device, behind the window (R8 / R16 volumes)")
+    ap.add_argument("--reduce", type=int, default=None, metavar="N", help="reduce the volume N times to half its resolution on the device, behind the smoothing")
     ap.add_argument("--yaw", type=float, default=0.6)
     ap.add_argument("--pitch", type=float, default=-0.35)
     ap.add_argument("--env", default="", help="Radiance .hdr environment map (MCS and MCM are lit by it)")
@@ -54,7 +58,8 @@ def main():
         window = [lo, hi]
     rc = vpt_amd.RenderingContext({'resolution': (a.width, a.height), 'filter': a.filter, 'rng': GoldenRatioRng(),
                                    'gradient': a.gradient, 'gradientGain': a.gradient_gain,
-                                   'window': None if window == 'auto' else window, 'windowFormat': a.window_format})
+                                   'window': None if window == 'auto' else window, 'windowFormat': a.window_format,
+                                   'smooth': a.smooth, 'reduce': a.reduce})
     rc.resize(a.width, a.height)
     rc.gl.getExtension('EXT_texture_norm16')                      # 16-bit volumes are taken
     if a.volume.endswith(".bvp"):

@@ -208,6 +208,32 @@ VPT_API int vpt_volume_range(vpt_volume *vol, double *lo, double *hi);
  * R16_SNORM.  R32F and every other format: VPT_ERR_UNSUPPORTED.  Blocks.  (vpt_volume_histogram counts the top 8 bits.) */
 VPT_API int vpt_volume_code_histogram(vpt_volume *vol, uint32_t *bins, size_t nbins);
 
+/* ---- the next coarser level and binomial smoothing on the device (extension; DESIGN.md "Binomial smoothing and 2x reduction") */
+/* vpt_volume_reduce: a new volume in src's format with ceil(n / 2) texels per axis (an axis of 1 stays 1).  Result texel (X, Y, Z) is taken
+ * per channel from the eight source texels at x in {2 X, min(2 X + 1, nx - 1)}, likewise y and z: indices are clamped, so on an odd axis the
+ * last cell counts its last texel twice and no data is dropped.
+ *   Integer formats (R8, RG8, R16, RG16, R8_SNORM, RG8_SNORM, R16_SNORM, RG16_SNORM): out = (sum of the eight codes + 4) >> 3 with an
+ *   arithmetic shift: the floor of the mean, halves rounded up.  The code is the stored integer, for SNORM the most negative code read as
+ *   the one above it (as for the window above; the result does not depend on whether the source was finalized).  32 bits hold every sum.
+ *   Float formats (R32F, RG32F; R16F manifests are widened on upload): every texel is widened to double and the eight are added by IEEE
+ *   double additions in this order: the two x-neighbours, then the two y-pairs, then the two z-halves,
+ *     ((a000 + a100) + (a010 + a110)) + ((a001 + a101) + (a011 + a111)),                       a_xyz, nothing fused
+ *   the sum is multiplied by 0.125 (exact) and rounded once to float.  Infinities follow IEEE; a cell that holds a NaN gives a NaN whose
+ *   payload is not part of the contract.
+ *   Packed formats (VPT_FORMAT_RGB565 .. VPT_FORMAT_RGB9_E5): VPT_ERR_UNSUPPORTED, naming the format.
+ * The cube a volume occupies does not change: on an odd axis the reduced grid is therefore stretched by n / (2 ceil(n / 2)) along that axis.
+ * vpt_volume_smooth: a new volume of src's size and format, `passes` (1 .. 8; otherwise VPT_ERR_INVALID) applications of the binomial
+ * 3 x 3 x 3 kernel.  Sources: R8 and R16, the formats the gradient is derived from (smoothing is the step in front of it); every other format:
+ * VPT_ERR_UNSUPPORTED, naming it.  One pass, in integers, v = the texel, indices clamped per axis (CLAMP_TO_EDGE), w = (1, 2, 1):
+ *     W = sum over a, b, c in {-1, 0, 1} of w(a) w(b) w(c) v(x + a, y + b, z + c);   out = (W + 32) >> 6
+ *   W <= 64 (2^B - 1) fits 32 bits and out never exceeds the source's largest texel: nothing saturates.  Each pass rounds once.
+ * vpt_amd.reduce_texels and vpt_amd.smooth_texels state the contracts in numpy.
+ * Both results are new, finalized volumes on src's context with src's filter, enqueued on the context's stream behind any upload into src;
+ * src is not changed and may be destroyed afterwards.  The results are ordinary volumes (every renderer, set_filter, upload_block,
+ * read_block, window, derive_gradient, and these two again) */
+VPT_API int vpt_volume_reduce(vpt_volume *src, vpt_volume **out);
+VPT_API int vpt_volume_smooth(vpt_volume *src, int passes, vpt_volume **out);
+
 /* ---- renderer: AbstractRenderer.js:17-116 and the four subclasses */
 /* new R(gl, volume, camera, environmentTexture, {resolution}) — AbstractRenderer.js:17-49; width != height is the
  * documented extension (uInverseResolution = (1/W, 1/H)).  Buffers are allocated as in _rebuildBuffers :78-92. */

@@ -186,6 +186,22 @@ static napi_value VolumeWindow(napi_env env, napi_callback_info info) {
     VPT_CHECK(vpt_volume_window(v, lo, hi, format, &out));
     return make_external(env, out);
 }
+// volumeReduce(volume) -> a new volume handle: the next coarser level, ceil(n / 2) texels per axis
+static napi_value VolumeReduce(napi_env env, napi_callback_info info) {
+    napi_value a[1]; vpt_volume *v;
+    if (!get_args(env, info, 1, a) || !get_handle(env, a[0], &v)) return nullptr;
+    vpt_volume *out = nullptr;
+    VPT_CHECK(vpt_volume_reduce(v, &out));
+    return make_external(env, out);
+}
+// volumeSmooth(volume, passes) -> a new volume handle: `passes` applications of the binomial 3 x 3 x 3 kernel
+static napi_value VolumeSmooth(napi_env env, napi_callback_info info) {
+    napi_value a[2]; vpt_volume *v; int32_t passes;
+    if (!get_args(env, info, 2, a) || !get_handle(env, a[0], &v) || !get_i32(env, a[1], &passes)) return nullptr;
+    vpt_volume *out = nullptr;
+    VPT_CHECK(vpt_volume_smooth(v, passes, &out));
+    return make_external(env, out);
+}
 // volumeRange(volume) -> [lo, hi]: the smallest and the largest code or value
 static napi_value VolumeRange(napi_env env, napi_callback_info info) {
     napi_value a[1]; vpt_volume *v;
@@ -515,6 +531,7 @@ static napi_value Init(napi_env env, napi_value exports) {
     EXPORT("volumeDeriveGradient", VolumeDeriveGradient); EXPORT("volumeReadBlock", VolumeReadBlock); EXPORT("volumeHistogram", VolumeHistogram);
     CONST(VPT_GRADIENT_CENTRAL); CONST(VPT_GRADIENT_SOBEL);
     EXPORT("volumeWindow", VolumeWindow); EXPORT("volumeRange", VolumeRange); EXPORT("volumeCodeHistogram", VolumeCodeHistogram);
+    EXPORT("volumeReduce", VolumeReduce); EXPORT("volumeSmooth", VolumeSmooth);
     EXPORT("rendererCreate", RendererCreate); EXPORT("rendererDestroy", RendererDestroy); EXPORT("rendererSetShard", RendererSetShard);
     EXPORT("rendererLocalRows", RendererLocalRows); EXPORT("rendererGlobalRow", RendererGlobalRow);
     EXPORT("rendererSetVolume", RendererSetVolume); EXPORT("rendererSetTransferFunction", RendererSetTransferFunction);

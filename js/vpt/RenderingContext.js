@@ -6,12 +6,13 @@
 //   'nearest' or 'quasicubic'; gradient: null (default), 'central' or 'sobel', gradientGain (default 1): a one-channel R8 / R16 volume gets its
 //   gradient magnitude as second channel when it is loaded (Volume.deriveGradient); window: null (default), [lo, hi], 'range' or
 //   { percentiles: [a, b] }, windowFormat: 'r8' (default) or 'r16': a one-channel volume is windowed when it is loaded, before the gradient
-//   is derived (Volume.window)
+//   is derived (Volume.window); smooth: null (default) or passes 1 .. 8: an R8 / R16 volume is smoothed behind the window (Volume.smooth);
+//   reduce: null (default), 0 or levels >= 1: the volume is reduced to half its resolution that many times behind the smoothing (Volume.reduce)
 const { EventTarget, CustomEvent } = require('./EventTarget.js');
 const { Context } = require('./Context.js');
 const { OrbitCameraAnimator } = require('./animators.js');
 const { Node, Transform, PerspectiveCamera } = require('./scene.js');
-const { Volume, gradientArguments, windowFormatBits } = require('./Volume.js');
+const { Volume, gradientArguments, windowFormatBits, checkPasses, checkLevels } = require('./Volume.js');
 const { native } = require('./native.js');
 const { RendererFactory } = require('./renderers/RendererFactory.js');
 const { ToneMapperFactory } = require('./tonemappers/ToneMapperFactory.js');
@@ -28,6 +29,10 @@ constructor(options) {
     this.window = options.window !== undefined ? options.window : null;
     this.windowFormat = options.windowFormat !== undefined && options.windowFormat !== null ? options.windowFormat : 'r8';
     if (this.window !== null) { windowFormatBits(this.windowFormat); RenderingContext._windowSpec(this.window); }   // likewise
+    this.smooth = options.smooth !== undefined ? options.smooth : null;
+    this.reduce = options.reduce !== undefined ? options.reduce : null;
+    if (this.smooth !== null) { checkPasses(this.smooth); }                          // likewise
+    if (this.reduce !== null && this.reduce !== 0) { checkLevels(this.reduce); }
     this.gl = new Context(options.device || 0);                                   // initGL(), :61-105
     this.environmentTexture = { data: new Uint8Array([255, 255, 255, 255]), width: 1, height: 1 };   // :90-101
     this._rng = options.rng;
@@ -76,6 +81,19 @@ async setVolume(reader) {                                                       
         if (this.window !== null) {                                                    // the transfer function's x axis is [lo, hi]
             const source = this.volume, w = this._windowOf(source);
             this.volume = source.window({ lo: w[0], hi: w[1], format: this.windowFormat });
+            source.destroy();
+        }
+        if (this.smooth !== null) {
+            const N = native(), fmt = this.volume.nativeFormat();
+            if (fmt === N.VPT_FORMAT_R8 || fmt === N.VPT_FORMAT_R16) {                 // the formats the gradient takes: any other volume as it is
+                const source = this.volume;
+                this.volume = source.smooth(this.smooth);
+                source.destroy();
+            }
+        }
+        if (this.reduce) {
+            const source = this.volume;
+            this.volume = source.reduce(this.reduce);
             source.destroy();
         }
         if (this.gradient !== null) {

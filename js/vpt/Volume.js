@@ -288,5 +288,51 @@ percentileWindow(pLo, pHi) {
         fmt === N.VPT_FORMAT_R8_SNORM || fmt === N.VPT_FORMAT_R16_SNORM);
 }
 
+// ---- extension: the next coarser level and binomial smoothing (include/vpt.h; DESIGN.md "Binomial smoothing and 2x reduction") ----
+// the ready Volume around a derived native volume of this volume's format with the given dimensions
+_sameFormat(texture, dimensions) {
+    const out = new Volume(this._gl);
+    out.texture = texture;
+    out.modality = Object.assign({}, this.modality, { dimensions: Object.assign({}, dimensions),
+        placements: [{ index: 0, position: { x: 0, y: 0, z: 0 } }] });
+    out.metadata = { meta: Object.assign({}, (this.metadata || {}).meta), modalities: [out.modality],
+        blocks: [{ url: null, format: 'raw', dimensions: Object.assign({}, dimensions) }] };
+    out.ready = true;
+    return out;
 }
-module.exports = { Volume, RAWReader, filterCode, gradientArguments, windowFormatBits, percentileWindow };
+
+// a new, ready volume in this volume's format and with its filter, `levels` (an integer >= 1, default 1) times reduced to ceil(n / 2) texels
+// per axis, every texel the rounded mean of its 2 x 2 x 2 cell, derived on the device; stops early once every axis is 1; packed formats are
+// refused; this volume is not changed
+reduce(levels) {
+    levels = checkLevels(levels !== undefined ? levels : 1);
+    const N = native();
+    let source = this, d = this.modality.dimensions;
+    for (;;) {
+        let texture;
+        try { texture = N.volumeReduce(source.texture); } finally { if (source !== this) { source.destroy(); } }   // the level in between
+        d = { width: (d.width + 1) >> 1, height: (d.height + 1) >> 1, depth: (d.depth + 1) >> 1 };
+        source = this._sameFormat(texture, d);
+        levels--;
+        if (levels === 0 || Math.max(d.width, d.height, d.depth) === 1) { return source; }
+    }
+}
+
+// a new, ready R8 / R16 volume of this (R8 / R16) volume's size and with its filter: `passes` (1 .. 8, default 1) applications of the binomial
+// 3 x 3 x 3 kernel, derived on the device; this volume is not changed
+smooth(passes) {
+    passes = checkPasses(passes !== undefined ? passes : 1);
+    return this._sameFormat(native().volumeSmooth(this.texture, passes), this.modality.dimensions);
+}
+
+}
+// the number of smoothing passes (an integer in 1 .. 8) / of reductions (an integer >= 1); throws for anything else
+function checkPasses(passes) {
+    if (!Number.isInteger(passes) || passes < 1 || passes > 8) { throw new Error('smoothing passes are an integer in 1 .. 8, not ' + JSON.stringify(passes)); }
+    return passes;
+}
+function checkLevels(levels) {
+    if (!Number.isInteger(levels) || levels < 1) { throw new Error('reduction levels are an integer >= 1, not ' + JSON.stringify(levels)); }
+    return levels;
+}
+module.exports = { Volume, RAWReader, filterCode, gradientArguments, windowFormatBits, percentileWindow, checkPasses, checkLevels };

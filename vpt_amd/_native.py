@@ -49,6 +49,7 @@ SYMBOLS = [
     "vpt_volume_set_filter", "vpt_volume_destroy", "vpt_volume_bricked_bytes", "vpt_volume_set_wide_tables",
     "vpt_volume_derive_gradient", "vpt_volume_read_block", "vpt_volume_histogram",
     "vpt_volume_window", "vpt_volume_range", "vpt_volume_code_histogram",
+    "vpt_volume_reduce", "vpt_volume_smooth",
     "vpt_renderer_create", "vpt_renderer_set_shard", "vpt_renderer_local_rows", "vpt_renderer_global_row",
     "vpt_renderer_destroy", "vpt_renderer_set_volume", "vpt_renderer_set_transfer_function",
     "vpt_renderer_set_environment", "vpt_renderer_set_environment_texels", "vpt_renderer_resize",
@@ -155,6 +156,7 @@ def lib():
         "vpt_volume_histogram": [P, C.POINTER(C.c_uint32), SZ],
         "vpt_volume_window": [P, C.c_double, C.c_double, I, PP], "vpt_volume_range": [P, C.POINTER(C.c_double), C.POINTER(C.c_double)],
         "vpt_volume_code_histogram": [P, C.POINTER(C.c_uint32), SZ],
+        "vpt_volume_reduce": [P, PP], "vpt_volume_smooth": [P, I, PP],
         "vpt_renderer_create": [P, I, I, I, PP],
         "vpt_renderer_set_shard": [P, I, I, I], "vpt_renderer_local_rows": [P, C.POINTER(I)],
         "vpt_renderer_global_row": [P, I, C.POINTER(I)],

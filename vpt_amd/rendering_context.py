@@ -31,6 +31,16 @@ class RenderingContext(EventTarget):
         if self.window is not None:
             from .window import format_bits
             format_bits(self.windowFormat); self._window_spec(self.window)             # a bad option fails here, not at the first volume
+        # (extension) None | passes 1 .. 8: an R8 / R16 volume is smoothed (binomial 3 x 3 x 3) when it is loaded, behind the window;
+        # None | 0 | levels >= 1: the volume is reduced to ceil(n / 2) texels per axis that many times, behind the smoothing and before the gradient
+        self.smooth = options.get('smooth')
+        self.reduce = options.get('reduce')
+        if self.smooth is not None:
+            from .pyramid import check_passes
+            check_passes(self.smooth)                                                  # a bad option fails here, not at the first volume
+        if self.reduce is not None and not (self.reduce == 0 and not isinstance(self.reduce, bool)):
+            from .pyramid import check_levels
+            check_levels(self.reduce)
         self.gl = Context(options.get('device', 0))                                   # initGL(), :61-105
         self.environmentTexture = np.array([[[255, 255, 255, 255]]], dtype=np.uint8)   # :90-101
         self._rng = options.get('rng')
@@ -74,6 +84,14 @@ class RenderingContext(EventTarget):
                 source = self.volume
                 lo, hi = self._window_of(source)
                 self.volume = source.window(lo, hi, self.windowFormat)                # the transfer function's x axis is [lo, hi]
+                source.destroy()
+            if self.smooth is not None and self._one_channel_unorm(self.volume):
+                source = self.volume
+                self.volume = source.smooth(self.smooth)
+                source.destroy()
+            if self.reduce:
+                source = self.volume
+                self.volume = source.reduce(self.reduce)
                 source.destroy()
             if self.gradient is not None and self._one_channel_unorm(self.volume):
                 source = self.volume

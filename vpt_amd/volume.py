@@ -349,6 +349,46 @@ class Volume(EventTarget):
         signed = self.native_format()[0] in (N.FORMAT_R8_SNORM, N.FORMAT_R16_SNORM)
         return percentile_window(self.code_histogram(), p_lo, p_hi, signed)
 
+    # ---- extension: the next coarser level and binomial smoothing (include/vpt.h; DESIGN.md "Binomial smoothing and 2x reduction") ----
+    def _same_format(self, handle, dims):
+        """the ready Volume around a derived native volume of this volume's format with the dimensions ``dims``"""
+        out = type(self)(self._gl)
+        out.texture = handle
+        out.modality = dict(self.modality, dimensions=dict(dims), placements=[{'index': 0, 'position': {'x': 0, 'y': 0, 'z': 0}}])
+        out.metadata = {'meta': dict((self.metadata or {}).get('meta', {})), 'modalities': [out.modality],
+                        'blocks': [{'url': None, 'format': 'raw', 'dimensions': dict(dims)}]}
+        out.ready = True
+        return out
+
+    def reduce(self, levels=1):
+        """A new, ready volume in this volume's format and with its filter, ``levels`` times reduced to ceil(n / 2) texels per axis: every
+        texel the rounded mean of its 2 x 2 x 2 cell (vpt_amd.reduce_texels states it), derived on the device.  Stops early once every axis
+        is 1 (the result is then a copy).  Packed formats are refused.  This volume is not changed."""
+        from .pyramid import check_levels
+        levels = check_levels(levels)
+        L = N.lib()
+        source, dims = self, dict(self.modality['dimensions'])
+        while True:
+            h = C.c_void_p()
+            try:
+                N.check(L.vpt_volume_reduce(source.texture, C.byref(h)))
+            finally:
+                if source is not self:
+                    source.destroy()                          # the level in between
+            dims = {k: (dims[k] + 1) // 2 for k in ('width', 'height', 'depth')}
+            source = self._same_format(h, dims)
+            levels -= 1
+            if levels == 0 or max(dims.values()) == 1:
+                return source
+
+    def smooth(self, passes=1):
+        """A new, ready R8 / R16 volume of this (R8 / R16) volume's size and with its filter: ``passes`` (1 .. 8) applications of the binomial
+        3 x 3 x 3 kernel (vpt_amd.smooth_texels states it), derived on the device.  This volume is not changed."""
+        from .pyramid import check_passes
+        h = C.c_void_p()
+        N.check(N.lib().vpt_volume_smooth(self.texture, check_passes(passes), C.byref(h)))
+        return self._same_format(h, self.modality['dimensions'])
+
     def set_wide_tables(self, wide):
         """force the > 4 GiB addressing variant of the kernels (automatic above 4 GiB of bricked data)"""
         N.check(N.lib().vpt_volume_set_wide_tables(self.texture, 1 if wide else 0))
