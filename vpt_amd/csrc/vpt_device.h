@@ -537,18 +537,27 @@ VPT_DEV uint64_t record_load(const uint8_t *a) {
 // instead of two unaligned 8-byte gathers from the bricks.  Face f = 2 * axis + side (side 1 = plane N_k - 1) starts at dword
 // f * atlas_face; cell (a, b) of a face sits at (b << atlas_shift) + a with (a, b) = (y, z), (x, z), (x, y) for axis x, y, z.
 // Precondition: some coordinate of p is > 1 or < 0 (not NaN) — the caller's bounds test.
+template <bool ANY_AXIS = true>
 VPT_DEV uint32_t boundary_cell(const DevVolume &v, f3 p, float &out_fa, float &out_fb) {
     // (members copied into locals first: `c ? v.fny : v.fnx` on struct members is an lvalue conditional — a select of ADDRESSES
     // into the kernel argument block, which then has to live in scratch memory: measured 5x slower)
     const float fnx = v.fnx, fny = v.fny, fnz = v.fnz, hx = v.hx, hy = v.hy, hz = v.hz;
     const uint32_t face = v.atlas_face, sh = v.atlas_shift;
-    const bool ox = (p.x > 1.0f) || (p.x < 0.0f);
-    const bool oy = (p.y > 1.0f) || (p.y < 0.0f);
-    // The face is the first out-of-range axis k; its side follows from the coordinate itself (p_k > 1: plane N_k - 1, p_k < 0:
-    // plane 0), so the clamped axis needs no filter cell at all.  The photons of a wave mostly leave through the same face
-    // (8 x 8 neighbouring pixels): the three wave-uniform cases are separate straight-line paths without per-lane selects,
-    // and only a wave whose lanes disagree takes the generic one.
-    // (ballots of the four compares themselves, OR-ed as scalars: a ballot of `ox` makes the compiler materialise the predicate as
+    // The face is an out-of-range axis k; its side follows from the coordinate itself (p_k > 1: plane N_k - 1, p_k < 0: plane 0), so
+    // the clamped axis needs no filter cell at all.  WHICH out-of-range axis does not matter to the value: (1) every out-of-range axis
+    // has its cell clamped onto the first or last plane with weight exactly 0 (linear_cell), (2) the faces hold the same texels along the
+    // edges and corners they share, and (3) the x -> y -> z lerps with an exact-zero weight return the tap itself (fma(0, b - a, a) = a)
+    // — so the face of axis k sampled at a position that is also out of range in axis m gives, bit for bit, what the face of axis m gives
+    // there: the blend along the one or zero axes that are left.  So the rule is the cheapest one: any axis that is out of range for
+    // EVERY active lane of the wave, tried x, y, z — a straight-line path without per-lane selects (12 instructions against 32) — and the
+    // per-lane first-out-of-range-axis path only for a wave that shares none.  The photons of a wave mostly leave through the same face
+    // (8 x 8 neighbouring pixels); a wave some of whose lanes are out of range in x and all of them in y (12 % of the wave-events of MISS
+    // tiles at the benchmark camera, which the earlier rule "x for nobody, y for everybody" sent down the per-lane path) now takes the
+    // y face.  The z ballots are computed only once x and y have failed.
+    // ANY_AXIS = false: the earlier rule — the y path only when no lane is out of range in x, the z path only when none is in x or y, so
+    // that every lane of a uniform path takes ITS first out-of-range axis.  The out-of-cube lanes of the HIT kernels keep it: a subset of a
+    // wave whose patterns are mixed anyway, where the wave rule's extra ballots and branches cost more than they return (measured).
+    // (ballots of the compares themselves, OR-ed as scalars: a ballot of `ox` makes the compiler materialise the predicate as
     // 0 / 1 in a VGPR and compare it again — four VALU instructions per sample for nothing)
     const unsigned long long act = __builtin_amdgcn_ballot_w64(true);
     const unsigned long long bx = __builtin_amdgcn_ballot_w64(p.x > 1.0f) | __builtin_amdgcn_ballot_w64(p.x < 0.0f);
@@ -557,13 +566,15 @@ VPT_DEV uint32_t boundary_cell(const DevVolume &v, f3 p, float &out_fa, float &o
     if (bx == act) {
         linear_cell(p.y, fny, hy, a, fa); linear_cell(p.z, fnz, hz, b, fb);
         idx = (p.x > 1.0f ? face : 0u) + ((b << sh) + a);
-    } else if (bx == 0ull && by == act) {
+    } else if ((ANY_AXIS || bx == 0ull) && by == act) {
         linear_cell(p.x, fnx, hx, a, fa); linear_cell(p.z, fnz, hz, b, fb);
         idx = (p.y > 1.0f ? 3u * face : 2u * face) + ((b << sh) + a);
-    } else if (bx == 0ull && by == 0ull) {
+    } else if (ANY_AXIS ? (__builtin_amdgcn_ballot_w64(p.z > 1.0f) | __builtin_amdgcn_ballot_w64(p.z < 0.0f)) == act : (bx == 0ull && by == 0ull)) {
         linear_cell(p.x, fnx, hx, a, fa); linear_cell(p.y, fny, hy, b, fb);
         idx = (p.z > 1.0f ? 5u * face : 4u * face) + ((b << sh) + a);
     } else {
+        const bool ox = (p.x > 1.0f) || (p.x < 0.0f);
+        const bool oy = (p.y > 1.0f) || (p.y < 0.0f);
         const bool oxy = ox || oy;
         const float pa = ox ? p.y : p.x, pb = oxy ? p.z : p.y;
         linear_cell(pa, ox ? fny : fnx, ox ? hy : hx, a, fa);
@@ -592,6 +603,13 @@ VPT_DEV uint32_t boundary_cell_lane(const DevVolume &v, f3 p, float &out_fa, flo
     const uint32_t f = (ox ? 0u : (oy ? 2u : 4u)) + (pk > 1.0f ? 1u : 0u);
     out_fa = fa; out_fb = fb;
     return f * v.atlas_face + ((b << v.atlas_shift) + a);
+}
+// the byte atlas's dword of cell `idx` (boundary_cell) in global_load's SGPR-base + 32-bit VGPR-offset form, like aligned_taps: the atlas is
+// at most 6 faces x 2048^2 dwords (96 MiB), so the byte offset fits 32 bits and the gather needs no 64-bit address arithmetic per lane
+VPT_DEV uint32_t atlas_dword(const uint32_t *atlas, uint32_t idx) {
+    uint32_t w;
+    __builtin_memcpy(&w, __builtin_assume_aligned((const uint8_t *)atlas + (idx << 2), 4), 4);
+    return w;
 }
 template <bool SNORM = false>
 VPT_DEV float boundary_blend(uint32_t w, float fa, float fb) {
@@ -628,7 +646,7 @@ VPT_DEV f2 sample_boundary_rg(const DevVolume &v, f3 p) {
 VPT_DEV float sample_volume_boundary(const DevVolume &v, f3 p) {
     float fa, fb;
     const uint32_t idx = boundary_cell(v, p, fa, fb);
-    return boundary_blend(v.atlas[idx], fa, fb);
+    return boundary_blend(atlas_dword(v.atlas, idx), fa, fb);
 }
 // texture(uVolume, p).rg: r always, g only for RG8 volumes (V & VPT_V_RG; an R8 volume has g = 0).  The cell and its
 // brick address are computed once for both channels.

@@ -372,7 +372,10 @@ __global__ void __launch_bounds__(VPT_BLOCK) k_probe_sample_boundary(PassArgs a,
     const f3 q = { xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2] };
     const bool oob = (vmax(vmax(q.x, q.y), q.z) > 1.0f) || (vmin(vmin(q.x, q.y), q.z) < 0.0f);
     if (!oob) { out[i] = sample_volume_color<V>(a, t, q); return; }
-    const f2 rg = sample_boundary_rg<V>(a.vol, q);
+    // LINEAR one-channel byte volumes: through boundary_cell, the sampler of the plain class kernels — its face is chosen per WAVE (an axis
+    // out of range for every active lane), so which path a position takes depends on the 63 positions beside it (tests/test_gpu_miss_wave.py)
+    constexpr bool PLAIN = !(V & (VPT_V_NEAREST | VPT_V_RG | VPT_V_F32 | VPT_V_SNORM | VPT_V_QCUBIC | VPT_V_NORM16));
+    const f2 rg = PLAIN ? f2{ sample_volume_boundary(a.vol, q), 0.0f } : sample_boundary_rg<V>(a.vol, q);
     out[i] = (V & VPT_V_RG) ? sample_tf2d(a.tf, a.tf_w, a.tf_h, rg.x, rg.y) : sample_tf(t.tf, a.tf_fw, a.tf_hi, rg.x);
 }
 template <int V>

@@ -118,13 +118,14 @@ __global__ void __launch_bounds__(VPT_BLOCK) k_mcm_reset(PassArgs a) {
 // per cent slower, and its phases are an upper bound of the shipped kernel's.
 #ifdef VPT_EVENT_TIMING
 #define VPT_TIMING_WAVES 16384
+#define VPT_TIMING_MISS_WAVES 32768   // the MISS-tile kernels' buffer: a 1080p frame has 25 584 MISS waves, each with a slot of its own
 struct EventClock { unsigned long long prev, start; unsigned long long acc[8]; };
 VPT_DEV void ev_start(EventClock &c) { for (int i = 0; i < 8; i++) c.acc[i] = 0ull; c.prev = wall_clock64(); c.start = c.prev; }
 #define EV_MARK(c, slot, WAIT) do { asm volatile(WAIT ::: "memory"); const unsigned long long n_ = wall_clock64(); (c).acc[slot] += n_ - (c).prev; (c).prev = n_; } while (0)
 #define EV_PIN3(v) asm volatile("" : "+v"((v).x), "+v"((v).y), "+v"((v).z))
-VPT_DEV void ev_flush(const EventClock &c, unsigned long long *out) {
+VPT_DEV void ev_flush(const EventClock &c, unsigned long long *out, size_t waves = VPT_TIMING_WAVES) {
     if (((int)threadIdx.x & 63) == 0 && out) {
-        unsigned long long *slot = out + (((size_t)blockIdx.x * 4 + (threadIdx.x >> 6)) & (VPT_TIMING_WAVES - 1)) * 16;
+        unsigned long long *slot = out + (((size_t)blockIdx.x * 4 + (threadIdx.x >> 6)) & (waves - 1)) * 16;
         for (int i = 0; i < 8; i++) slot[i] += c.acc[i];
         slot[8] += 1ull;
         slot[9] = c.start; slot[10] = c.prev;                 // this launch's wave: first and last clock read (absolute)
@@ -153,7 +154,9 @@ VPT_DEV SampleLoads mcm_sample_issue(const PassArgs &a, const LdsTables &t, f3 p
     asm volatile("" : "+v"(s.w0), "+v"(s.w1), "+v"(s.aw));
     const bool at = oob && a.vol.atlas != nullptr;
     if (at) {
-        s.aw = a.vol.atlas[boundary_cell(a.vol, p, s.f0, s.f1)];
+        // (boundary_cell<false>: a HIT wave's out-of-cube lanes keep the rule "each lane's first out-of-range axis, the uniform paths only when
+        // the whole wave agrees on it" — the wave rule of the MISS kernels measured 0.6 us slower here at 1024^3, profiles/experiments.md)
+        s.aw = atlas_dword(a.vol.atlas, boundary_cell<false>(a.vol, p, s.f0, s.f1));
     } else {
         uint32_t x, y, z;
         linear_cell(p.x, a.vol.fnx, a.vol.hx, x, s.f0);
@@ -581,13 +584,18 @@ __global__ void __launch_bounds__(VPT_BLOCK) __attribute__((amdgpu_waves_per_eu(
 // At the benchmark camera ~78 % of the tiles are MISS tiles.  HIT tiles run k_mcm_integrate from their own tile list.
 // CHECK: count the events that contradict the classification (tests / VPT_OPTION_VERIFY_TILE_CLASSES; must stay 0).
 // =============================================================================================
-VPT_DEV const float4 *stage_tf(float4 *lds, const PassArgs &a) {
+// (stage_tf_fill: the workgroup's share of the LDS image without the barrier that makes it visible — the caller's, stage_tf's below)
+VPT_DEV const float4 *stage_tf_fill(float4 *lds, const PassArgs &a) {
     const int nthreads = (int)blockDim.x;
     for (int t = (int)threadIdx.x; t < a.tf_w; t += nthreads) {
         float4 v = a.tf[t], n = a.tf[min(t + 1, a.tf_w - 1)];
         lds[2 * t] = v;
         lds[2 * t + 1] = make_float4(n.x - v.x, n.y - v.y, n.z - v.z, n.w - v.w);
     }
+    return lds;
+}
+VPT_DEV const float4 *stage_tf(float4 *lds, const PassArgs &a) {
+    stage_tf_fill(lds, a);
     __syncthreads();
     return lds;
 }
@@ -599,7 +607,7 @@ struct MissLoad { uint32_t aw; float fa, fb; };
 template <bool CHECK>
 VPT_DEV MissLoad miss_sample_issue(const PassArgs &a, f3 q, unsigned long long *violations) {
     MissLoad l;
-    l.aw = a.vol.atlas[boundary_cell(a.vol, q, l.fa, l.fb)];
+    l.aw = atlas_dword(a.vol.atlas, boundary_cell(a.vol, q, l.fa, l.fb));
     if (CHECK) {
         const bool oob = (vmax(vmax(q.x, q.y), q.z) > 1.0f) || (vmin(vmin(q.x, q.y), q.z) < 0.0f);
         if (!oob) atomicAdd(violations, 1ull);
@@ -624,11 +632,14 @@ VPT_DEV void miss_sample_any(const PassArgs &a, const float4 *tf, f3 q) {
         if (!oob) atomicAdd(a.violations, 1ull);
     }
 }
+// the random stream of a pixel's pass starts from its NDC position and the frame's seed (MCMRenderer.glsl:121)
+VPT_DEV uint32_t pass_seed(float px, float py, float seed) {
+    return hash3(__float_as_uint(ndc_to_uv(px)), __float_as_uint(ndc_to_uv(py)), __float_as_uint(seed));
+}
 // LATE: the sample is consumed after the path end (under whose arithmetic its load flies) instead of right where the shader samples
 // DEPOSIT = false: the settled form (k_mcm_miss_settled) — every draw, position and sample as here, without the deposit
 template <int V, bool CHECK, bool LATE, bool DEPOSIT = true>
-VPT_DEV void mcm_events_miss(const PassArgs &a, const float4 *tf, Photon &ph, float px, float py, f3 from0) {
-    uint32_t state = hash3(__float_as_uint(ndc_to_uv(px)), __float_as_uint(ndc_to_uv(py)), __float_as_uint(a.seed));
+VPT_DEV void mcm_events_miss(const PassArgs &a, const float4 *tf, Photon &ph, float px, float py, f3 from0, uint32_t state) {
     for (uint32_t s = 0u; s < a.steps; s++) {
         float dist = random_exponential(state, a.inv_extinction);
         ph.position = madd3(ph.position, dist, ph.direction);
@@ -647,9 +658,8 @@ VPT_DEV void mcm_events_miss(const PassArgs &a, const float4 *tf, Photon &ph, fl
     }
 }
 template <int V, bool CHECK, bool LATE, bool DEPOSIT = true>
-VPT_DEV void mcm_events_miss_fast(const PassArgs &a, const float4 *tf, const FastPixel &c, Photon &ph, float px, float py) {
+VPT_DEV void mcm_events_miss_fast(const PassArgs &a, const float4 *tf, const FastPixel &c, Photon &ph, float px, float py, uint32_t state) {
     const float ld = -0.6931471805599453f * a.inv_extinction, ld32 = -32.0f * ld;
-    uint32_t state = hash3(__float_as_uint(ndc_to_uv(px)), __float_as_uint(ndc_to_uv(py)), __float_as_uint(a.seed));
     for (uint32_t s = 0u; s < a.steps; s++) {
         float dist = fmaf(hw_log2(pcg_float(state)), ld, ld32);
         ph.position = madd3(ph.position, dist, ph.direction);
@@ -665,40 +675,85 @@ VPT_DEV void mcm_events_miss_fast(const PassArgs &a, const float4 *tf, const Fas
         if (LATE && !OTHER) miss_sample_finish(a, tf, l);
     }
 }
+// The prologue of a MISS-tile wave, in the order its round trips allow (profiles/experiments.md, "MISS wave prologue").  Nothing a pixel
+// needs before its first event depends on the LDS image: the tile-list entry, then the state texels AND the two NDC table entries are
+// loaded together, the workgroup's first threads put the transfer function's loads behind them (stage_tf_fill), and the pixel constants,
+// the seed hash and the photon's start are computed from them BEFORE the workgroup's barrier — one trip to memory where the barrier,
+// then the two table loads (each waited for at once), then the arithmetic used to follow one another.  Behind the barrier a wave waits
+// for nothing it has not already received.  The NDC values still come from the host tables (their bits are the contract's); a lane
+// without a pixel (partial tiles) computes on zeros and leaves at the `!p.valid` return, which stays behind the barrier every wave must reach.
+struct MissPixel { FastPixel c; f3 from0; uint32_t state; };
+template <bool FAST>
+VPT_DEV MissPixel miss_pixel_start(const PassArgs &a, float px, float py, float4 s1, f3 s0, Photon &ph) {
+    MissPixel m;
+    ph.direction = f3{ s1.x, s1.y, s1.z };
+    ph.bounces = 0u;
+    ph.transmittance = f3{ 1.0f, 1.0f, 1.0f };
+    if (FAST) {
+        m.c = fast_pixel(a, px, py);
+        m.from0 = m.c.from0;
+        ph.position = a.miss_load_pos ? s0 : photon_start_fast(m.c.from0, ph.direction);
+    } else {
+        m.from0 = unproject_near(px, py, a);
+        ph.position = a.miss_load_pos ? s0 : photon_start(m.from0, ph.direction);
+    }
+    m.state = pass_seed(px, py, a.seed);
+    // (pinned: the barrier that follows must not be scheduled ahead of this arithmetic)
+    asm volatile("" : "+v"(ph.position.x), "+v"(ph.position.y), "+v"(ph.position.z), "+v"(m.state));
+    return m;
+}
+#ifdef VPT_EVENT_TIMING
+// instrumented build: a MISS wave's life in three phases — prologue up to the first event, [0] the events, [6] epilogue — in the
+// per-wave slots of a buffer of the MISS kernels' own (PassArgs.violations of their launches in such a build; tools/miss_wave_life.py).
+// The prologue is the sum of [1] kernel arguments + tile-list entry (scalar loads), [2] the flight of the state / NDC table / transfer
+// function loads, [3] pixel constants, seed and photon start, [4] the wait at the workgroup's barrier, [5] what is left before the first event
+#define EV_MISS_MARK(evc, slot, WAIT) EV_MARK(evc, slot, WAIT)
+#define EV_MISS_PIN(x) asm volatile("" : "+v"(x))
+#define EV_MISS_BEGIN(evc, ph) do { EV_PIN3((ph).position); EV_MARK(evc, 5, "s_waitcnt vmcnt(0) lgkmcnt(0)"); } while (0)
+#define EV_MISS_EVENTS(evc, ph) do { EV_PIN3((ph).direction); EV_MARK(evc, 0, "s_waitcnt vmcnt(0) lgkmcnt(0)"); } while (0)
+#define EV_MISS_END(evc, a) do { EV_MARK(evc, 6, "s_waitcnt vmcnt(0)"); ev_flush(evc, CHECK ? nullptr : (a).violations, VPT_TIMING_MISS_WAVES); } while (0)
+#else
+#define EV_MISS_MARK(evc, slot, WAIT) do { } while (0)
+#define EV_MISS_PIN(x) do { } while (0)
+#define EV_MISS_BEGIN(evc, ph) do { } while (0)
+#define EV_MISS_EVENTS(evc, ph) do { } while (0)
+#define EV_MISS_END(evc, a) do { } while (0)
+#endif
 // (8 waves per SIMD = 64 VGPRs; the contract arithmetic of the other volume formats needs two more: 7 waves there instead of a spill)
 template <bool FUSE_RENDER, int V, bool CHECK, bool LATE>
 __global__ void __launch_bounds__(VPT_BLOCK)
 __attribute__((amdgpu_waves_per_eu(((V & (VPT_V_NEAREST | VPT_V_RG | VPT_V_F32 | VPT_V_SNORM)) && !(V & VPT_V_FAST)) ? 7 : 8, 8))) k_mcm_miss(PassArgs a) {
+    EV_LOCAL
     frame_select(a, 0);
     Pix p = map_pixel(a.pm);
+    EV_MISS_PIN(p.k); EV_MISS_MARK(evc, 1, "s_waitcnt lgkmcnt(0)");
     float4 s1 = make_float4(0.0f, 0.0f, 1.0f, 0.0f), s3 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     f3 s0 = { 0.0f, 0.0f, 0.0f };
+    float px = 0.0f, py = 0.0f;
     if (p.tile) {
         s1 = a.st1[p.k]; s3 = a.st3[p.k];
         if (a.miss_load_pos) s0 = ((const f3 *)a.st0)[p.k];
     }
+    if (p.valid) { px = ndc_col(a.pm, p.i); py = ndc_row(a.pm, p.j); }
     extern __shared__ float4 lds_raw[];
-    const float4 *tf = stage_tf(lds_raw, a);
-    if (!p.valid) return;
-    const float px = ndc_col(a.pm, p.i), py = ndc_row(a.pm, p.j);
+    const float4 *tf = stage_tf_fill(lds_raw, a);
+    EV_MISS_MARK(evc, 2, "s_waitcnt vmcnt(0)");
     Photon ph;
-    ph.direction = f3{ s1.x, s1.y, s1.z };
-    ph.bounces = 0u;
-    ph.transmittance = f3{ 1.0f, 1.0f, 1.0f };
+    const MissPixel m = miss_pixel_start<(V & VPT_V_FAST) != 0>(a, px, py, s1, s0, ph);
+    EV_MISS_MARK(evc, 3, "");
+    __syncthreads();
+    EV_MISS_MARK(evc, 4, "");
+    if (!p.valid) return;
     ph.radiance = f3{ s3.x, s3.y, s3.z };
     ph.samples = (uint32_t)(s3.w + 0.5f);
-    if (V & VPT_V_FAST) {
-        const FastPixel c = fast_pixel(a, px, py);
-        ph.position = a.miss_load_pos ? s0 : photon_start_fast(c.from0, ph.direction);
-        mcm_events_miss_fast<V & ~VPT_V_FAST, CHECK, LATE>(a, tf, c, ph, px, py);
-    } else {
-        const f3 from0 = unproject_near(px, py, a);
-        ph.position = a.miss_load_pos ? s0 : photon_start(from0, ph.direction);
-        mcm_events_miss<V, CHECK, LATE>(a, tf, ph, px, py, from0);
-    }
+    EV_MISS_BEGIN(evc, ph);
+    if (V & VPT_V_FAST) mcm_events_miss_fast<V & ~VPT_V_FAST, CHECK, LATE>(a, tf, m.c, ph, px, py, m.state);
+    else mcm_events_miss<V, CHECK, LATE>(a, tf, ph, px, py, m.from0, m.state);
+    EV_MISS_EVENTS(evc, ph);
     a.st1[p.k] = make_float4(ph.direction.x, ph.direction.y, ph.direction.z, 0.0f);
     a.st3[p.k] = make_float4(ph.radiance.x, ph.radiance.y, ph.radiance.z, (float)ph.samples);
     if (FUSE_RENDER) store_frame(a, p, pack_half4(ph.radiance.x, ph.radiance.y, ph.radiance.z, 1.0f));
+    EV_MISS_END(evc, a);
 }
 // The settled form of k_mcm_miss (VPT_OPTION_SETTLED_MISS; plain LINEAR one-channel byte volumes).  Under a 1x1 environment every deposit of
 // a MISS pixel is the same constant e, so the running mean r += (e - r) / n stops moving once |e - r| / n is below half the spacing of the
@@ -710,34 +765,35 @@ __attribute__((amdgpu_waves_per_eu(((V & (VPT_V_NEAREST | VPT_V_RG | VPT_V_F32 |
 // else reads that array; a fused pass takes this form only into a destination that already holds every MISS texel.
 template <int V, bool CHECK, bool LATE>
 __global__ void __launch_bounds__(VPT_BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) k_mcm_miss_settled(PassArgs a) {
+    EV_LOCAL
     frame_select(a, 0);
     Pix p = map_pixel(a.pm);
+    EV_MISS_PIN(p.k); EV_MISS_MARK(evc, 1, "s_waitcnt lgkmcnt(0)");
     float4 s1 = make_float4(0.0f, 0.0f, 1.0f, 0.0f);
     f3 s0 = { 0.0f, 0.0f, 0.0f };
+    float px = 0.0f, py = 0.0f;
     if (p.tile) {
         s1 = a.st1[p.k];
         if (a.miss_load_pos) s0 = ((const f3 *)a.st0)[p.k];
     }
+    if (p.valid) { px = ndc_col(a.pm, p.i); py = ndc_row(a.pm, p.j); }
     extern __shared__ float4 lds_raw[];
-    const float4 *tf = stage_tf(lds_raw, a);
-    if (!p.valid) return;
-    const float px = ndc_col(a.pm, p.i), py = ndc_row(a.pm, p.j);
+    const float4 *tf = stage_tf_fill(lds_raw, a);
+    EV_MISS_MARK(evc, 2, "s_waitcnt vmcnt(0)");
     Photon ph;
-    ph.direction = f3{ s1.x, s1.y, s1.z };
-    ph.bounces = 0u;
-    ph.transmittance = f3{ 1.0f, 1.0f, 1.0f };
+    const MissPixel m = miss_pixel_start<(V & VPT_V_FAST) != 0>(a, px, py, s1, s0, ph);
+    EV_MISS_MARK(evc, 3, "");
+    __syncthreads();
+    EV_MISS_MARK(evc, 4, "");
+    if (!p.valid) return;
     ph.radiance = f3{ 0.0f, 0.0f, 0.0f };
     ph.samples = 0u;
-    if (V & VPT_V_FAST) {
-        const FastPixel c = fast_pixel(a, px, py);
-        ph.position = a.miss_load_pos ? s0 : photon_start_fast(c.from0, ph.direction);
-        mcm_events_miss_fast<V & ~VPT_V_FAST, CHECK, LATE, false>(a, tf, c, ph, px, py);
-    } else {
-        const f3 from0 = unproject_near(px, py, a);
-        ph.position = a.miss_load_pos ? s0 : photon_start(from0, ph.direction);
-        mcm_events_miss<V, CHECK, LATE, false>(a, tf, ph, px, py, from0);
-    }
+    EV_MISS_BEGIN(evc, ph);
+    if (V & VPT_V_FAST) mcm_events_miss_fast<V & ~VPT_V_FAST, CHECK, LATE, false>(a, tf, m.c, ph, px, py, m.state);
+    else mcm_events_miss<V, CHECK, LATE, false>(a, tf, ph, px, py, m.from0, m.state);
+    EV_MISS_EVENTS(evc, ph);
     a.st1[p.k] = make_float4(ph.direction.x, ph.direction.y, ph.direction.z, 0.0f);
+    EV_MISS_END(evc, a);
 }
 // brings the position / transmittance arrays of the MISS tiles up to date: position = photon_start(from0, direction) in the
 // arithmetic of the variant that ran the last pass, transmittance = (1, 1, 1); `pending` > 0: the events k_mcm_miss_settled ran since
@@ -864,7 +920,7 @@ k_mcm_bucket_miss(PassArgs a, FrameSeeds fs, uint32_t nframes, void *ring, uint3
         ph.position = a.miss_load_pos ? s0 : photon_start_fast(c.from0, ph.direction);
         for (uint32_t f = 0; f < nframes; f++) {
             a.seed = fs.seed[f];
-            mcm_events_miss_fast<V & ~VPT_V_FAST, false, LATE>(a, tf, c, ph, px, py);
+            mcm_events_miss_fast<V & ~VPT_V_FAST, false, LATE>(a, tf, c, ph, px, py, pass_seed(px, py, a.seed));
             bucket_store<DISPLAY>(a, ring, texel, pack_half4(ph.radiance.x, ph.radiance.y, ph.radiance.z, 1.0f));
             texel += slot_pixels;
         }
@@ -873,7 +929,7 @@ k_mcm_bucket_miss(PassArgs a, FrameSeeds fs, uint32_t nframes, void *ring, uint3
         ph.position = a.miss_load_pos ? s0 : photon_start(from0, ph.direction);
         for (uint32_t f = 0; f < nframes; f++) {
             a.seed = fs.seed[f];
-            mcm_events_miss<V, false, LATE>(a, tf, ph, px, py, from0);
+            mcm_events_miss<V, false, LATE>(a, tf, ph, px, py, from0, pass_seed(px, py, a.seed));
             bucket_store<DISPLAY>(a, ring, texel, pack_half4(ph.radiance.x, ph.radiance.y, ph.radiance.z, 1.0f));
             texel += slot_pixels;
         }

@@ -7,18 +7,23 @@
 
 // ---- MCM passes over the tile classes ---------------------------------------------------------------------------------
 #ifdef VPT_EVENT_TIMING
-#define VPT_TIMING_ARG(part, hit) do { if (hit) (part).violations = timing; } while (0)
+#define VPT_TIMING_ARG(part, hit) do { if (hit) (part).violations = timing; else if (!check) (part).violations = timing_miss; } while (0)
 #else
 #define VPT_TIMING_ARG(part, hit) do { } while (0)
 #endif
 #ifdef VPT_EVENT_TIMING
-static unsigned long long *g_timing = nullptr;   // (VPT_EVENT_TIMING builds only) kept for the life of the process, hence a bare pointer: never freed
-static unsigned long long *timing_buffer(vpt_renderer *r) {
-    if (!g_timing) {
-        if (hipMalloc(&g_timing, (size_t)VPT_TIMING_WAVES * 16 * sizeof(unsigned long long)) != hipSuccess) { g_timing = nullptr; return nullptr; }
-        hipMemsetAsync(g_timing, 0, (size_t)VPT_TIMING_WAVES * 16 * sizeof(unsigned long long), r->ctx->stream);
+// (VPT_EVENT_TIMING builds only) [0]: the HIT-tile kernel's wave slots, [1]: the MISS-tile kernels'; kept for the life of the process,
+// hence bare pointers: never freed
+static unsigned long long *g_timing[2] = { nullptr, nullptr };
+static const size_t g_timing_waves[2] = { VPT_TIMING_WAVES, VPT_TIMING_MISS_WAVES };
+static unsigned long long *timing_buffer(vpt_renderer *r, int which) {
+    if (!g_timing[which]) {
+        const size_t bytes = g_timing_waves[which] * 16 * sizeof(unsigned long long);
+        if (hipMalloc(&g_timing[which], bytes) != hipSuccess) { g_timing[which] = nullptr; return nullptr; }
+        hipMemsetAsync(g_timing[which], 0, bytes, r->ctx->stream);
+        hipStreamSynchronize(r->ctx->stream);                  // (the MISS-tile kernel runs on a side stream)
     }
-    return g_timing;
+    return g_timing[which];
 }
 #endif
 static bool mcm_classes_usable(const vpt_renderer *r, const PassArgs &a) {
@@ -194,7 +199,7 @@ static int launch_mcm_classes(vpt_renderer *r, const PassArgs &a) {
     // 82.7-84.1; four streams 93; one stream, HIT then MISS: 102.  Capping the HIT kernel's residency (dynamic LDS) to 2 / 3 / 4 / 5
     // workgroups per CU so that MISS waves always sit beside its waves: 99 / 91 / 83.4 / 82.2 against 81.6 uncapped — DESIGN.md section 5)
 #ifdef VPT_EVENT_TIMING
-    unsigned long long *const timing = timing_buffer(r);
+    unsigned long long *const timing = timing_buffer(r, 0), *const timing_miss = timing_buffer(r, 1);
 #endif
     // (a frame the volume fills — no MISS tile at all — was tried with the HIT list in k parts on the k streams: 143.9 -> 143.7 us, nothing)
     const int hit_parts = r->cls.n_hit > 0 ? 1 : 0;
@@ -383,24 +388,26 @@ int mcm_render_frame(vpt_renderer *r, const PassArgs &a) {
     return VPT_OK;
 }
 #ifdef VPT_EVENT_TIMING
-// instrumented builds only (tools/r04_event_timing.py binds it by name): the HIT-tile kernel's phase clocks summed over its waves since the last
-// call, in 10 ns ticks — [0..4] per event: free path | cell + tables | load flight | blend + transfer function | decision + path end;
-// [5] prologue, [6] epilogue, [7] one calibration mark per event, [8] waves
-extern "C" VPT_API int vpt_probe_event_timing(vpt_renderer *r, uint64_t *out9) {
-    if (!r || !out9 || !g_timing) return fail(VPT_ERR_INVALID, "no timing buffer (run a classified pass first)");
+// instrumented builds only (tools/r04_event_timing.py, tools/miss_wave_life.py bind them by name): a class kernel's phase clocks summed over
+// its waves since the last call, in 10 ns ticks.  The HIT-tile kernel — [0..4] per event: free path | cell + tables | load flight | blend +
+// transfer function | decision + path end; [5] prologue, [6] epilogue, [7] one calibration mark per event, [8] waves.  The MISS-tile
+// kernels — [0] the pass's events, [5] prologue up to the first event, [6] epilogue, [8] waves.
+static int probe_timing(vpt_renderer *r, int which, uint64_t *out9) {
+    if (!r || !out9 || !g_timing[which]) return fail(VPT_ERR_INVALID, "no timing buffer (run a classified pass first)");
     VPT_TRY(join_side(r));
     HIP_TRY(hipSetDevice(r->ctx->device));
-    std::vector<unsigned long long> host((size_t)VPT_TIMING_WAVES * 16);
-    HIP_TRY(hipMemcpyAsync(host.data(), g_timing, host.size() * 8, hipMemcpyDeviceToHost, r->ctx->stream));
-    HIP_TRY(hipMemsetAsync(g_timing, 0, host.size() * 8, r->ctx->stream));
+    const size_t waves = g_timing_waves[which];
+    std::vector<unsigned long long> host(waves * 16);
+    HIP_TRY(hipMemcpyAsync(host.data(), g_timing[which], host.size() * 8, hipMemcpyDeviceToHost, r->ctx->stream));
+    HIP_TRY(hipMemsetAsync(g_timing[which], 0, host.size() * 8, r->ctx->stream));
     HIP_TRY(hipStreamSynchronize(r->ctx->stream));
     for (int k = 0; k < 9; k++) out9[k] = 0;
-    for (size_t w = 0; w < VPT_TIMING_WAVES; w++) for (int k = 0; k < 9; k++) out9[k] += host[w * 16 + k];
+    for (size_t w = 0; w < waves; w++) for (int k = 0; k < 9; k++) out9[k] += host[w * 16 + k];
     // the LAST launch's timeline: when its waves started and ended, relative to the first wave's start (10 ns ticks): out9[9 ..] =
     // { waves, start p50, start p90, start max, end p10, end p50, end p90, end max }
     std::vector<unsigned long long> st, en;
     unsigned long long t0 = ~0ull;
-    for (size_t w = 0; w < VPT_TIMING_WAVES; w++) if (host[w * 16 + 8]) { st.push_back(host[w * 16 + 9]); en.push_back(host[w * 16 + 10]); t0 = std::min(t0, host[w * 16 + 9]); }
+    for (size_t w = 0; w < waves; w++) if (host[w * 16 + 8]) { st.push_back(host[w * 16 + 9]); en.push_back(host[w * 16 + 10]); t0 = std::min(t0, host[w * 16 + 9]); }
     for (int k = 9; k < 17; k++) out9[k] = 0;
     if (!st.empty()) {
         std::sort(st.begin(), st.end()); std::sort(en.begin(), en.end());
@@ -410,4 +417,6 @@ extern "C" VPT_API int vpt_probe_event_timing(vpt_renderer *r, uint64_t *out9) {
     }
     return VPT_OK;
 }
+extern "C" VPT_API int vpt_probe_event_timing(vpt_renderer *r, uint64_t *out9) { return probe_timing(r, 0, out9); }
+extern "C" VPT_API int vpt_probe_miss_timing(vpt_renderer *r, uint64_t *out9) { return probe_timing(r, 1, out9); }
 #endif
