@@ -12,6 +12,8 @@
  * agree with the C oracle bit for bit except for isolated pixels (tests allow 1e-4 of them).
  * Reference files followed: src/glsl/renderers/{MIP,EAM,MCS,MCM}Renderer.glsl and the mixins they include
  * (cited per function in oracle/vpt_oracle.c, whose structure this mirrors).
+ * Narrower than the C oracle on purpose: the volume filters are LINEAR and NEAREST only (no quasi-cubic filter), and the
+ * environment map is RGBA8 only (no float table).
  */
 const f = Math.fround;
 const fma = (a, b, c) => f(a * b + c);

@@ -27,6 +27,7 @@ class Scene(C.Structure):
         ("tf_rgba", C.c_void_p), ("tf_w", C.c_int32), ("tf_h", C.c_int32),
         ("env_rgba", C.c_void_p), ("env_w", C.c_int32), ("env_h", C.c_int32),
         ("channels", C.c_int32), ("dtype", C.c_int32),
+        ("env_f32", C.c_void_p),
     ]
 
 
@@ -177,17 +178,46 @@ DEFAULT_TF = np.array([[[255, 0, 0, 0], [255, 0, 0, 255]]], dtype=np.uint8)   # 
 DEFAULT_ENV = np.array([[[255, 255, 255, 255]]], dtype=np.uint8)              # RenderingContext.js:93
 
 
+FILTERS = {"nearest": 0, "linear": 1, "quasicubic": 2}
+
+
+def env_float_table(env):
+    """the decoded float32 [h][w][4] table of a float environment map, as include/vpt.h states it for
+    vpt_renderer_set_environment_texels; None for what is not one (RGBA8 bytes, or no map)"""
+    if getattr(env, "format", None) == "rgbe":          # vpt_amd.hdr.HDRImage: m * 2^(e - 136) exactly, e == 0 black, alpha 1
+        data = np.asarray(env.data, dtype=np.uint8).reshape(env.height, env.width, 4)
+        e = data[..., 3].astype(np.int32)
+        out = np.ones(data.shape, np.float32)
+        out[..., :3] = np.ldexp(data[..., :3].astype(np.float32), (e - 136)[..., None])
+        out[..., :3][e == 0] = 0.0
+        return out
+    if env is None or np.asarray(env).dtype.kind != "f":
+        return None
+    env = np.asarray(env)
+    assert env.dtype in (np.float32, np.float16), "environment texels are uint8, float16 or float32"
+    assert env.ndim == 3 and env.shape[2] in (3, 4), "environment map is [h][w][4] (or float [h][w][3])"
+    if env.shape[2] == 3:                               # alpha 1 added, as AbstractRenderer._upload_environment adds it
+        env = np.concatenate([env, np.ones(env.shape[:2] + (1,), env.dtype)], axis=2)
+    return np.ascontiguousarray(env.astype(np.float32))  # half widens exactly
+
+
 class OracleScene:
     """Holds numpy arrays alive and exposes the ctypes Scene."""
 
     def __init__(self, volume, filter="linear", tf=None, env=None):
+        """filter: "quasicubic", "linear", anything else NEAREST; env: RGBA8 bytes [h][w][4], or what
+        AbstractRenderer._upload_environment takes besides (float32 / float16 [h][w][4], float [h][w][3], an HDRImage)"""
         volume = np.asarray(volume)
         f32 = volume.dtype.kind == "f"                 # FLOAT / HALF_FLOAT texels: half widens to float exactly
         volume = np.ascontiguousarray(volume, dtype=np.float32 if f32 else np.uint8)
         assert volume.ndim == 3 or (volume.ndim == 4 and volume.shape[3] == 2), "volume is [z][y][x] (R8 / R32F) or [z][y][x][2] (RG8)"
         self.volume = volume
         self.tf = np.ascontiguousarray(DEFAULT_TF if tf is None else tf, dtype=np.uint8)
-        self.env = np.ascontiguousarray(DEFAULT_ENV if env is None else env, dtype=np.uint8)
+        self.env_f32 = env_float_table(env)
+        if self.env_f32 is not None:
+            self.env = np.zeros(self.env_f32.shape, np.uint8)          # (never read: env_f32 stands in for it)
+        else:
+            self.env = np.ascontiguousarray(DEFAULT_ENV if env is None else env, dtype=np.uint8)
         assert self.tf.ndim == 3 and self.tf.shape[2] == 4
         assert self.env.ndim == 3 and self.env.shape[2] == 4
         s = Scene()
@@ -195,9 +225,10 @@ class OracleScene:
         s.nz, s.ny, s.nx = volume.shape[:3]
         s.channels = 2 if volume.ndim == 4 else 1
         s.dtype = 1 if f32 else 0
-        s.filter = 1 if filter == "linear" else 0
+        s.filter = FILTERS.get(filter, 0)
         s.tf_rgba = _ptr(self.tf); s.tf_h, s.tf_w = self.tf.shape[:2]
         s.env_rgba = _ptr(self.env); s.env_h, s.env_w = self.env.shape[:2]
+        s.env_f32 = _ptr(self.env_f32) if self.env_f32 is not None else None
         self.c = s
 
 

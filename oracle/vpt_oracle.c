@@ -52,7 +52,8 @@ typedef struct { float x, y; } v2;
 typedef struct {
     const uint8_t *volume;      /* linear R8 volume, x fastest (Volume.js:58-75 texSubImage3D) */
     int32_t nx, ny, nz;
-    int32_t filter;             /* 0 = NEAREST, 1 = LINEAR (Volume.js:115-125) */
+    int32_t filter;             /* 0 = NEAREST, 1 = LINEAR (Volume.js:115-125), 2 = quasi-cubic: the LINEAR cell and taps, each fraction
+                                 * replaced by f' = (f * f) * (3 - 2 f) */
     const uint8_t *tf_rgba;     /* SRGB8_ALPHA8 transfer function, row 0 first (AbstractRenderer.js:31-44,99-104) */
     int32_t tf_w, tf_h;
     const uint8_t *env_rgba;    /* RGBA8 environment map, LINEAR/CLAMP (RenderingContext.js:90-101) */
@@ -60,6 +61,8 @@ typedef struct {
     int32_t channels;           /* 1 = R8 (RAWReader.js:36-38), 2 = RG8 interleaved: texture(uVolume, p).rg has both (0 means 1) */
     int32_t dtype;              /* 0 = UNSIGNED_BYTE texels, normalised v/255; 1 = FLOAT texels (R32F / R16F widened exactly): the value itself,
                                  * LINEAR-filtered the same way (OES_texture_float_linear, RenderingContext.js:78); `volume` then points at floats */
+    const float *env_f32;       /* NULL, or a float environment map [env_h][env_w][4] (RGBA32F; RGBA16F / RGBE widened by the caller):
+                                 * taken as the decoded table in place of env_rgba, filtered the same way */
 } vpo_scene;
 
 typedef struct {
@@ -362,6 +365,8 @@ static inline int32_t nearest_coord(float s, int32_t n) {
     return (int32_t)floorf(u);
 }
 static inline float lerpf(float a, float b, float f) { return fmaf(f, b - a, a); }
+/* the quasi-cubic filter's weight of a LINEAR fraction: three roundings, no contraction */
+static inline float qc_weight(float f) { return (f * f) * (3.0f - 2.0f * f); }
 /* texel normalisation: one multiply by fl32(1/255) (255 * VPO_INV255 == 1.0f exactly) */
 #define VPO_INV255 0.00392156862745098f
 
@@ -383,6 +388,7 @@ static float sample_volume_channel(const vpo_scene *sc, v3 p, int channel) {
     linear_coord(p.x, sc->nx, &x0, &x1, &fx);
     linear_coord(p.y, sc->ny, &y0, &y1, &fy);
     linear_coord(p.z, sc->nz, &z0, &z1, &fz);
+    if (sc->filter == 2) { fx = qc_weight(fx); fy = qc_weight(fy); fz = qc_weight(fz); }
     float c000 = TEXEL(x0, y0, z0), c100 = TEXEL(x1, y0, z0);
     float c010 = TEXEL(x0, y1, z0), c110 = TEXEL(x1, y1, z0);
     float c001 = TEXEL(x0, y0, z1), c101 = TEXEL(x1, y0, z1);
@@ -413,6 +419,7 @@ static void tables_init(scene_tables *t, const vpo_scene *sc) {
     }
     n = (size_t)sc->env_w * (size_t)sc->env_h;
     t->env = (v4 *)malloc(n * sizeof(v4));
+    if (sc->env_f32) { memcpy(t->env, sc->env_f32, n * sizeof(v4)); return; }
     for (size_t i = 0; i < n; i++) {
         const uint8_t *c = sc->env_rgba + 4 * i;
         t->env[i].x = from_unorm8(c[0]); t->env[i].y = from_unorm8(c[1]);

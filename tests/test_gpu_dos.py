@@ -45,14 +45,16 @@ class Scene:
         return r
 
 
-def sweep(sc, oracle, r, calls, what, nthreads=4):
-    """reset, then `calls` render() calls, every buffer compared after each"""
+def sweep(sc, oracle, r, calls, what, nthreads=4, compare=True):
+    """reset, then `calls` render() calls, every buffer compared after each (compare=False, inside test_gpu_fuzz.oracle_only(): the
+    oracle's side alone)"""
     o = oracle.OracleRenderer('dos', sc.osc, sc.w, sc.h)
     r.reset()
     fr = oracle.make_frame(sc.w, sc.h, sc.m, nthreads=nthreads)
     o.reset(fr)
-    same_bits(r.read(N.BUFFER_ACCUM), o.color[o.cur], what + " reset colour")
-    same_bits(r.read(N.BUFFER_DOS_OCCLUSION), o.occlusion[o.cur], what + " reset occlusion")
+    if compare:
+        same_bits(r.read(N.BUFFER_ACCUM), o.color[o.cur], what + " reset colour")
+        same_bits(r.read(N.BUFFER_DOS_OCCLUSION), o.occlusion[o.cur], what + " reset occlusion")
     total = 0
     for k in range(calls):
         r.render()
@@ -62,10 +64,12 @@ def sweep(sc, oracle, r, calls, what, nthreads=4):
         o.integrate_slices(fr, r._slices, r._occlusionSamples)
         o.render_frame(fr)
         total += len(r._slices)
+        if not compare:
+            continue
         same_bits(r.read(N.BUFFER_ACCUM), o.color[o.cur], "%s colour after call %d" % (what, k))
         same_bits(r.read(N.BUFFER_DOS_OCCLUSION), o.occlusion[o.cur], "%s occlusion after call %d" % (what, k))
         same_bits(r.getTexture().view(np.uint16), o.out, "%s render after call %d" % (what, k))
-    assert r.sample_count() == o.samples, what
+    assert not compare or r.sample_count() == o.samples, what
     return o, total
 
 
@@ -171,25 +175,36 @@ def test_dos_full_size_oracle(gpu_ctx, oracle):
     r.destroy(); sc.gvol.destroy()
 
 
-@pytest.mark.parametrize("seed", range(*[int(v) for v in os.environ.get("VPT_FUZZ_SEEDS", "0:24").split(":")]))
-def test_dos_random_scene(gpu_ctx, oracle, seed):
-    """the random scenes of test_gpu_fuzz.py (image / volume shapes down to 1, RG8, NEAREST, cameras inside, outside and
-    looking away, scaled / rotated models, 2-D transfer functions) swept by the DOS renderer"""
-    from test_gpu_fuzz import random_case, random_camera
-    rng, vol, (w, h), tf, env, filt, model = random_case(7000 + seed)
+def random_sweep(gpu_ctx, oracle, seed, case, filt=None, compare=True):
+    """a drawn case of test_gpu_fuzz.py (random_case's tuple) swept by the DOS renderer, under the case's own filter or `filt`; returns the
+    OracleRenderer after the last call"""
+    from test_gpu_fuzz import random_camera
+    rng, vol, (w, h), tf, env, case_filt, model = case
+    filt = filt or case_filt
     camera = random_camera(rng, w / h)
     sc = Scene.__new__(Scene)
     sc.vol, sc.w, sc.h, sc.tf, sc.ctx = vol, w, h, tf, gpu_ctx
     sc.osc = oracle.OracleScene(vol, filt, tf=tf)
-    sc.gvol = vpt_amd.Volume.from_array(gpu_ctx, vol, filt)
+    sc.gvol = vpt_amd.Volume.from_array(gpu_ctx, vol, filt) if compare else None
     sc.camera, sc.transform = camera, model
     sc.m = mvp_inverse_matrix(camera, model)
     r = sc.renderer(rng=GoldenRatioRng(int(rng.integers(1, 50))))
     r.slices = int(rng.choice([1, 6, 17, 40])); r.steps = int(rng.choice([1, 5, 50])); r.extinction = float(rng.choice([0.0, 10.0, 100.0, 1000.0]))
     r.aperture = float(rng.choice([0, 10, 30, 75, 89])); r.samples = int(rng.choice([1, 2, 8, 33]))
     r.generateOcclusionSamples()
-    sweep(sc, oracle, r, 3, "dos seed %d (%dx%d image, volume %s, %s)" % (seed, w, h, vol.shape, filt), nthreads=2)
-    r.destroy(); sc.gvol.destroy()
+    o, _ = sweep(sc, oracle, r, 3, "dos seed %d (%dx%d image, volume %s, %s)" % (seed, w, h, vol.shape, filt), nthreads=2, compare=compare)
+    r.destroy()
+    if sc.gvol is not None:
+        sc.gvol.destroy()
+    return o
+
+
+@pytest.mark.parametrize("seed", range(*[int(v) for v in os.environ.get("VPT_FUZZ_SEEDS", "0:24").split(":")]))
+def test_dos_random_scene(gpu_ctx, oracle, seed):
+    """the random scenes of test_gpu_fuzz.py (image / volume shapes down to 1, RG8, NEAREST, cameras inside, outside and
+    looking away, scaled / rotated models, 2-D transfer functions) swept by the DOS renderer"""
+    from test_gpu_fuzz import random_case
+    random_sweep(gpu_ctx, oracle, seed, random_case(7000 + seed))
 
 
 def test_dos_matrix_changes_mid_sweep_and_volume_partly_off_screen(gpu_ctx, oracle):

@@ -2,8 +2,10 @@
 cameras (outside, inside, grazing, looking away), transfer functions (1..256 wide, 1..3 rows), environment maps,
 filters and renderer parameters (zero extinction, zero bounces, one step, strong anisotropy ...), several frames
 each — every buffer of every pass must equal the CPU oracle bit for bit.  Seeds are fixed: the cases never change."""
+import contextlib
 import math
 import os
+import types
 
 import numpy as np
 import pytest
@@ -102,24 +104,54 @@ _SPLIT = int(os.environ.get("VPT_FUZZ_SPLIT", "-1"))
 _LAZY = int(os.environ.get("VPT_FUZZ_LAZY", "-1"))
 
 
-@pytest.mark.parametrize("kind", KINDS)
-@pytest.mark.parametrize("seed", _SEEDS)
-def test_random_scene(gpu_ctx, oracle, kind, seed):
-    rng, vol, (w, h), tf, env, filt, model = random_case(seed * 6 + KINDS.index(kind) if kind != "lao" else 5000 + seed)
+class _NoDevice:
+    """stands in for libvpt_hip.so where only the oracle is to run: every entry succeeds and does nothing, so a renderer object still
+    draws its uniforms frame by frame and the oracle renders the drawn case on a machine without a GPU"""
+
+    def __getattr__(self, name):
+        return lambda *args: 0
+
+
+@contextlib.contextmanager
+def oracle_only():
+    """inside, run_random_scene(None, ...) (and test_gpu_dos.py's sweep(..., compare=False)) renders the oracle's side of a case alone:
+    the conditions a set of drawn cases must meet (tests/test_oracle_filters_env.py) are asserted on that, without a device"""
+    real = N.lib
+    N.lib = lambda: _NoDevice()
+    try:
+        yield types.SimpleNamespace(_h=None)           # (what a renderer takes for its context)
+    finally:
+        N.lib = real
+
+
+def run_random_scene(gpu_ctx, oracle, kind, seed, case, upload=None, nthreads=1, options=(), wide_tables=False):
+    """one drawn case (random_case's tuple, `rng` positioned behind its draws) rendered by `kind` on the device and by the oracle: every
+    buffer of every pass (after the last pass for a lazy case) bit for bit.  `seed` picks split streams and lazy reads as it always has.
+    upload(ctx, filt) -> Volume uploads another storage format whose decoded texels are the case's volume; options: (option, value)
+    pairs for set_option; gpu_ctx None (inside oracle_only()): nothing is compared, the oracle alone renders.  Returns the
+    OracleRenderer after the last pass."""
+    rng, vol, (w, h), tf, env, filt, model = case
+    device = gpu_ctx is not None
     camera = random_camera(rng, w / h)
     m = mvp_inverse_matrix(camera, model)
     osc = oracle.OracleScene(vol, filt, tf=tf, env=env)
-    gvol = vpt_amd.Volume.from_array(gpu_ctx, vol, filt)
+    gvol = None
+    if device:
+        gvol = upload(gpu_ctx, filt) if upload else vpt_amd.Volume.from_array(gpu_ctx, vol, filt)
+        if wide_tables:
+            gvol.set_wide_tables(True)
     fused = bool(rng.integers(0, 2))
     start = int(rng.integers(1, 50))
     opts = {'resolution': (w, h), 'transform': model, 'rng': GoldenRatioRng(start), 'fused': fused}
     if rng.uniform() < 0.3:                           # one rank of a row-sharded run: its rows must be the oracle's rows
         world = int(rng.integers(2, 6))
         opts['shard'] = (int(rng.integers(0, world)), world, int(rng.choice([1, 3, 8, 16])))
-    r = vpt_amd.RendererFactory(kind)(gpu_ctx, gvol, camera, env, opts)
+    r = vpt_amd.RendererFactory(kind)(gpu_ctx if device else types.SimpleNamespace(_h=None), gvol, camera, env, opts)
     if _SPLIT >= 2 or (_SPLIT < 0 and seed % 3 == 1):          # a third of the default cases run their passes on three streams
         r.set_option(N.OPTION_SPLIT_STREAMS, max(_SPLIT, 3) if _SPLIT >= 2 else 3)
-    rows = r.global_rows()
+    for opt, val in options:
+        r.set_option(opt, val)
+    rows = r.global_rows() if device else np.arange(h)
     valid = rows >= 0
 
     def same_rows(got, want, msg):
@@ -156,7 +188,7 @@ def test_random_scene(gpu_ctx, oracle, kind, seed):
     what = "%s seed %d (%dx%d image, volume %s, %s, fused=%s, shard=%s)" % (kind, seed, w, h, vol.shape, filt, fused, opts.get('shard'))
 
     def frame_of(u):
-        fr = oracle.make_frame(w, h, np.array(list(u.mvp_inverse), np.float32))
+        fr = oracle.make_frame(w, h, np.array(list(u.mvp_inverse), np.float32), nthreads=nthreads)
         fr.seed = u.rand_seed; fr.offset = u.offset; fr.step = u.step_size
         fr.extinction = u.extinction; fr.anisotropy = u.anisotropy; fr.max_bounces = u.max_bounces; fr.steps = u.steps
         for i in range(3):
@@ -169,7 +201,8 @@ def test_random_scene(gpu_ctx, oracle, kind, seed):
     if kind == "mcm":
         o.reset(oracle.make_frame(w, h, m, seed=np.float32(GoldenRatioRng(start)())))      # MCMRenderer.js:93: the reset's own draw
         for b, s in zip(MCM_BUFFERS, o.state):
-            same_rows(r.read(b), s, what + " reset buffer %d" % b)
+            if device:
+                same_rows(r.read(b), s, what + " reset buffer %d" % b)
     else:
         o.reset(oracle.make_frame(w, h, m))
     lazy = _LAZY == 1 or (_LAZY < 0 and seed % 3 == 2)
@@ -177,7 +210,7 @@ def test_random_scene(gpu_ctx, oracle, kind, seed):
     for k in range(npasses):
         r.render()
         o.render(frame_of(r._u))
-        if lazy and k + 1 < npasses:
+        if not device or (lazy and k + 1 < npasses):
             continue
         if kind == "mcm":
             for b, s in zip(MCM_BUFFERS, o.state):
@@ -187,9 +220,18 @@ def test_random_scene(gpu_ctx, oracle, kind, seed):
                 same_rows(r.read(N.BUFFER_FRAME), o.frame, what + " frame %d" % k)
             same_rows(r.read(N.BUFFER_ACCUM), o.acc, what + " accumulation %d" % k)
         same_rows(r.getTexture().view(np.uint16), o.out, what + " render %d" % k)
-    if 'shard' not in opts:
+    if device and 'shard' not in opts:
         assert r.sample_count() == o.samples, what
-    r.destroy(); gvol.destroy()
+    r.destroy()
+    if gvol is not None:
+        gvol.destroy()
+    return o
+
+
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("seed", _SEEDS)
+def test_random_scene(gpu_ctx, oracle, kind, seed):
+    run_random_scene(gpu_ctx, oracle, kind, seed, random_case(seed * 6 + KINDS.index(kind) if kind != "lao" else 5000 + seed))
 
 
 @pytest.mark.parametrize("w,h", [(5000, 2), (2, 5000), (4099, 33), (1, 1), (17, 4097)])
