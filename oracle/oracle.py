@@ -155,6 +155,7 @@ def lib():
         L.vpo_mcm_reset.restype = None; L.vpo_mcm_reset.argtypes = [FP, P, P, P, P]
         L.vpo_mcm_integrate.restype = C.c_uint64; L.vpo_mcm_integrate.argtypes = [SP, FP, P, P, P, P]
         L.vpo_mcm_render.restype = None; L.vpo_mcm_render.argtypes = [FP, P, P]
+        L.vpo_mcm_fast64.restype = C.c_uint64; L.vpo_mcm_fast64.argtypes = [SP, FP, P, P, P, P, C.c_double, P, P, P, P]
         L.vpo_sample_volume.restype = C.c_float; L.vpo_sample_volume.argtypes = [SP, C.c_float, C.c_float, C.c_float]
         L.vpo_sample_volume_color.restype = None; L.vpo_sample_volume_color.argtypes = [SP, C.c_float, C.c_float, C.c_float, P]
         L.vpo_sample_environment.restype = None; L.vpo_sample_environment.argtypes = [SP, C.c_float, C.c_float, C.c_float, P]
@@ -253,6 +254,30 @@ def make_frame(width, height, mvp_inv, *, seed=0.0, offset=0.0, steps=64, extinc
     f.isovalue = float(np.float32(isovalue)); f.gradient_step = float(np.float32(gradient_step))
     f.threshold = float(np.float32(threshold))
     return f
+
+
+class FastTwin:
+    """what vpo_mcm_fast64 returns for one pass: the float64 twin of the MCM fast-arithmetic variant"""
+    NULL, SCATTER, OUT_OF_BOUNDS, ABSORB = range(4)
+
+    def __init__(self, n, steps):
+        self.state = np.zeros((n, 14), np.float64)       # position, direction, transmittance, radiance, bounces, samples
+        self.radius = np.zeros((n, 4), np.float64)       # sensitivity radii of position, direction, transmittance, radiance
+        self.codes = np.zeros((n, steps), np.uint8)      # the event of every step
+        self.fragile = np.zeros(n, np.uint8)             # a float32 evaluation may legitimately differ
+
+
+def mcm_fast64(scene, fr, state, slack):
+    """`fr.steps` events of the fast variant in double precision for every pixel, from the four MCM state arrays `state` (float32
+    [h * w * 4] each, read only), with `slack` ulps (of 2^-23) given to the ill-conditioned intermediates -> FastTwin"""
+    st = [np.ascontiguousarray(s, np.float32).reshape(-1) for s in state]
+    n = fr.width * fr.height
+    assert all(s.size == 4 * n for s in st) and fr.y0 == 0 and fr.y1 == fr.height
+    t = FastTwin(n, fr.steps)
+    done = lib().vpo_mcm_fast64(C.byref(scene.c), C.byref(fr), *[_ptr(s) for s in st], float(slack),
+                                _ptr(t.state), _ptr(t.radius), _ptr(t.codes), _ptr(t.fragile))
+    assert done == n, "the twin covers blur == 0 only"
+    return t
 
 
 class OracleRenderer:

@@ -36,6 +36,7 @@
 #include <string.h>
 #include <stdlib.h>
 #include <math.h>
+#include <float.h>
 #ifdef _OPENMP
 #include <omp.h>
 #endif
@@ -1279,4 +1280,284 @@ VPO_API int vpo_max_threads(void) {
 #else
     return 1;
 #endif
+}
+
+/* ==========================================================================================
+ * MCM, fast-arithmetic variant (VPT_OPTION_FAST_MATH; vpt_kernels_mcm.h: mcm_events_fast, mcm_events_fast_early,
+ * mcm_events_miss_fast, sample_hg_fast, photon_start_fast, fast_path_end): its float64 twin.
+ *
+ * NOT a mirror of the kernel's roundings: the same operation — the same integer PCG stream, the same algebraic forms
+ * (-log(u)/rate = (log2(k) - 32) * (-ln 2 / rate); the jitter as k * (2^-31 / W) - 1 / W; M (p + j, 1, 1) = M (p, 1, 1) + j.x col0 + j.y col1;
+ * normalize(to / w - from) = sign(w) normalize(to - w from); the slab entry as -f * iv + min(iv, 0)), the same branch structure (|g| < 1e-5
+ * included), blur = 0 only — evaluated in double.  float(state) is the variant's definition of its uniform and is kept; the volume /
+ * transfer-function sampler and the environment lookup are the contract's own float routines (the fast kernels use the bit-exact
+ * sampler), called on the twin's position / direction rounded to float.
+ *
+ * Besides the next state the twin says where a float32 evaluation may legitimately differ from it.  `A` is the
+ * one "ulps of slack" parameter: an intermediate of magnitude M is perturbed by delta = A * 2^-23 * M, and
+ *   - a DECISION is robust when its margin exceeds what the perturbations move: the position q against the cube's faces (per axis:
+ *     outside by more than delta_q on one axis, or inside by more than delta_q on all three), the wheel against p_abs and against
+ *     p_abs + p_scat (each re-evaluated with q moved by +-delta_q per axis through the sampler, plus delta of the thresholds themselves);
+ *   - an OUTPUT carries a sensitivity radius: the position the deltas of q (or, after a reset, what +-delta of the direction per axis
+ *     moves photon_start by, plus delta of from + t * dir), the direction delta of (to - w from) / |to - w from| after a reset and, after
+ *     a scattering, what +-delta of 1 - |d|^2 (Marsaglia's radius), of hgcos and of each component of cc (before its normalisation)
+ *     move the result by, the transmittance what q's deltas move the sampled colour by.  Over chained events the radii add (a later
+ *     event perturbs its inputs by the radii they arrive with).
+ * A pixel is FRAGILE when a decision of any of its events is not robust, when an output is NaN or when a radius is not finite.
+ * An infinite component of q is a robust out-of-bounds decision; an infinite output has to be met exactly (class and sign).
+ * ======================================================================================== */
+#define VPO_EPS23 0x1p-23
+typedef struct {
+    double pos[3], dir[3], tr[3], rad[3];
+    uint32_t bounces, samples;
+    double r_pos, r_dir, r_tr, r_rad;
+    int fragile;
+} photon64;
+typedef struct { double m[16], from0[3], fb[4], jx, jy, inv_w, inv_h; } pixel64;
+
+static inline double amax3(const double *v) { return fmax(fmax(fabs(v[0]), fabs(v[1])), fabs(v[2])); }
+/* max |a - b| over three components; equal infinities count as no difference, anything else that is not finite as +inf */
+static double diff3(const double *a, const double *b) {
+    double r = 0.0;
+    for (int k = 0; k < 3; k++) {
+        if (a[k] == b[k]) continue;
+        double d = fabs(a[k] - b[k]);
+        if (!(d <= DBL_MAX)) return INFINITY;
+        r = fmax(r, d);
+    }
+    return r;
+}
+static inline double next_k(uint32_t *state) { *state = vpo_pcg(*state); return (double)(float)(*state); }
+
+/* photon_start_fast: from + max(tnear, 0) dir, tnear = max over the slabs of -f * iv + min(iv, 0) */
+static double start64(const double *f, const double *d, double *p) {
+    double t = 0.0;
+    for (int k = 0; k < 3; k++) {
+        double iv = 1.0 / d[k];
+        t = fmax(t, -f[k] * iv + fmin(iv, 0.0));         /* (fmax / fmin: a NaN operand yields the other one, like v_max / v_min) */
+    }
+    for (int k = 0; k < 3; k++) p[k] = f[k] + t * d[k];
+    return t;
+}
+/* fast_path_end's resetPhoton (blur == 0) */
+static void reset64(const pixel64 *c, uint32_t *state, double A, photon64 *ph) {
+    *state = vpo_pcg(vpo_pcg(*state));                   /* the disk sample's two draws (multiplied by blur = 0) */
+    double ax = next_k(state) * c->jx - c->inv_w;
+    double ay = next_k(state) * c->jy - c->inv_h;
+    double th[4], d[3], dd = 0.0, dl[3];
+    for (int i = 0; i < 4; i++) th[i] = c->fb[i] + c->m[i] * ax + c->m[4 + i] * ay;
+    for (int k = 0; k < 3; k++) { d[k] = th[k] - th[3] * c->from0[k]; dd += d[k] * d[k]; }
+    double inv = copysign(1.0 / sqrt(dd), th[3]);
+    for (int k = 0; k < 3; k++) {
+        ph->dir[k] = d[k] * inv;
+        /* delta of the direction: the terms of d relative to its length (their cancellation), at least the unit vector's own */
+        dl[k] = A * VPO_EPS23 * fmax(1.0, fmax(fabs(th[k]), fabs(th[3] * c->from0[k])) * fabs(inv));
+    }
+    double t = start64(c->from0, ph->dir, ph->pos);
+    double r = 0.0, q[3], e[3];
+    for (int k = 0; k < 3; k++)
+        for (int s = -1; s <= 1; s += 2) {
+            memcpy(e, ph->dir, sizeof e);
+            e[k] += s * dl[k];
+            start64(c->from0, e, q);
+            r = fmax(r, diff3(q, ph->pos));
+            if (r != r) r = INFINITY;
+        }
+    double tm[3] = { t * ph->dir[0], t * ph->dir[1], t * ph->dir[2] };
+    double mag = fmax(amax3(c->from0), amax3(tm));
+    ph->r_pos = r + (mag <= DBL_MAX ? A * VPO_EPS23 * mag : 0.0);      /* (an infinite start is met exactly or not at all) */
+    ph->r_dir = fmax(fmax(dl[0], dl[1]), dl[2]);
+    ph->r_tr = 0.0;
+    ph->bounces = 0u;
+    ph->tr[0] = ph->tr[1] = ph->tr[2] = 1.0;
+}
+/* sample_hg_fast from its three uniforms; pn, ph_, pc: perturbations of 1 - |d|^2, of hgcos and of cc */
+static void hg64(double u1, double u2, double u3, double g, int iso, const double *dir, double pn, double ph_, const double *pc, double *out,
+                 double *hg_mag) {
+    double r0 = sqrt(u1), ang = 6.283185307179586476925 * u2;
+    double dx = r0 * cos(ang), dy = r0 * sin(ang);
+    double norm = dy * dy + dx * dx;
+    double radius = 2.0 * sqrt(1.0 - norm + pn);
+    double u[3] = { radius * dx, radius * dy, 1.0 - 2.0 * norm };
+    if (iso) { memcpy(out, u, sizeof u); return; }
+    double g2 = g * g;
+    double den = 2.0 * g * u3 + (1.0 - g);
+    double c = (1.0 - g2) / den;
+    double hgcos = (1.0 + g2 - c * c) / (2.0 * g) + ph_;
+    /* the magnitude hgcos' delta is relative to: the terms of its numerator, and what deltas of 1 - g^2 (of magnitude 1) and of the
+     * denominator (of its larger term) move c * c by */
+    if (hg_mag) *hg_mag = (fmax(1.0 + g2, c * c) + 2.0 * c * c * (1.0 / (1.0 - g2) + fmax(fabs(2.0 * g * u3), 1.0 - g) / fabs(den))) / fabs(2.0 * g);
+    double ud = u[0] * dir[0] + u[1] * dir[1] + u[2] * dir[2];
+    double cc[3], cd = 0.0;
+    for (int k = 0; k < 3; k++) { cc[k] = u[k] - ud * dir[k] + pc[k]; cd += cc[k] * cc[k]; }
+    double sq = sqrt(1.0 - hgcos * hgcos) / sqrt(cd);
+    for (int k = 0; k < 3; k++) out[k] = sq * cc[k] + hgcos * dir[k];
+}
+static void scatter64(uint32_t *state, double A, double g, photon64 *ph) {
+    const double zero[3] = { 0.0, 0.0, 0.0 };
+    double u1 = next_k(state) * 0x1p-32, u2 = next_k(state) * 0x1p-32, u3 = 0.0;
+    const int iso = fabs(g) < (double)1e-5f;
+    if (!iso) u3 = next_k(state) * 0x1p-32;
+    double out[3], e[3], hmag = 1.0, d = A * VPO_EPS23, r = 0.0, rg;
+    hg64(u1, u2, u3, g, iso, ph->dir, 0.0, 0.0, zero, out, &hmag);
+    /* the radii of the groups add; within a group the largest movement counts */
+    hg64(u1, u2, u3, g, iso, ph->dir, d, 0.0, zero, e, NULL); rg = diff3(e, out);
+    hg64(u1, u2, u3, g, iso, ph->dir, -d, 0.0, zero, e, NULL); r += fmax(rg, diff3(e, out));
+    if (!iso) {
+        hg64(u1, u2, u3, g, iso, ph->dir, 0.0, d * hmag, zero, e, NULL); rg = diff3(e, out);
+        hg64(u1, u2, u3, g, iso, ph->dir, 0.0, -d * hmag, zero, e, NULL); r += fmax(rg, diff3(e, out));
+        rg = 0.0;
+        for (int k = 0; k < 3; k++)
+            for (int s = -1; s <= 1; s += 2) {
+                double pc[3] = { 0.0, 0.0, 0.0 };
+                pc[k] = s * d;
+                hg64(u1, u2, u3, g, iso, ph->dir, 0.0, 0.0, pc, e, NULL); rg = fmax(rg, diff3(e, out));
+            }
+        r += rg;
+        if (ph->r_dir > 0.0) {                           /* a chained event: the incoming direction moves within its own radius */
+            rg = 0.0;
+            for (int k = 0; k < 3; k++)
+                for (int s = -1; s <= 1; s += 2) {
+                    double di[3] = { ph->dir[0], ph->dir[1], ph->dir[2] };
+                    di[k] += s * ph->r_dir;
+                    hg64(u1, u2, u3, g, iso, di, 0.0, 0.0, zero, e, NULL); rg = fmax(rg, diff3(e, out));
+                }
+            r += rg;
+        }
+    }
+    if (r != r) r = INFINITY;
+    memcpy(ph->dir, out, sizeof out);
+    ph->r_dir = r;
+    ph->bounces++;
+}
+/* the two thresholds of the wheel and the colour, from the contract's sampler at q rounded to float */
+static void sample64(const scene_tables *t, const double *q, int no_scatter, double *t1, double *t2, double *col) {
+    uint64_t ns = 0;
+    v3 p = { (float)q[0], (float)q[1], (float)q[2] };
+    v4 vs = sample_volume_color(t, p, &ns);
+    col[0] = vs.x; col[1] = vs.y; col[2] = vs.z;
+    double p_null = 1.0 - (double)vs.w;
+    double p_scat = no_scatter ? 0.0 : (double)vs.w * fmax(fmax(col[0], col[1]), col[2]);
+    double p_abs = 1.0 - p_null - p_scat;
+    *t1 = p_abs; *t2 = p_abs + p_scat;
+}
+static void env64(const scene_tables *t, const double *d, double *out) {
+    v3 f = { (float)d[0], (float)d[1], (float)d[2] };
+    v4 e = sample_environment(t, f);
+    out[0] = e.x; out[1] = e.y; out[2] = e.z;
+}
+
+/* out_state [P][14]: position, direction, transmittance, radiance, bounces, samples; out_radius [P][4]: the radii of the four vectors;
+ * out_codes [P][steps]: 0 null collision, 1 scattering, 2 out of bounds, 3 absorption; out_fragile [P].  The state arrays are read only.
+ * Returns the number of pixels, or 0 for a frame the twin does not cover (blur != 0). */
+VPO_API uint64_t vpo_mcm_fast64(const vpo_scene *sc, const vpo_frame *fr, const float *s0, const float *s1, const float *s2, const float *s3,
+                                double A, double *out_state, double *out_radius, uint8_t *out_codes, uint8_t *out_fragile) {
+    if (fr->blur != 0.0f) return 0;
+    scene_tables t; tables_init(&t, sc);
+    const float *const cst[4] = { s0, s1, s2, s3 };
+    uint64_t ns = 0; int nth = clamp_threads(fr);
+    const double ld = -0.6931471805599453094 * (1.0 / (double)fr->extinction);
+    const double g = (double)fr->anisotropy;
+    FOR_ROWS(fr) {
+        for (int32_t i = 0; i < fr->width; i++) {
+            size_t k = (size_t)j * fr->width + i;
+            float px = pixel_ndc(i, fr->width), py = pixel_ndc(j, fr->height);
+            photon pf; photon_load(&pf, cst, k);
+            photon64 ph;
+            ph.pos[0] = pf.position.x; ph.pos[1] = pf.position.y; ph.pos[2] = pf.position.z;
+            ph.dir[0] = pf.direction.x; ph.dir[1] = pf.direction.y; ph.dir[2] = pf.direction.z;
+            ph.tr[0] = pf.transmittance.x; ph.tr[1] = pf.transmittance.y; ph.tr[2] = pf.transmittance.z;
+            ph.rad[0] = pf.radiance.x; ph.rad[1] = pf.radiance.y; ph.rad[2] = pf.radiance.z;
+            ph.bounces = pf.bounces; ph.samples = pf.samples;
+            ph.r_pos = ph.r_dir = ph.r_tr = ph.r_rad = 0.0; ph.fragile = 0;
+            pixel64 c;
+            double nb[4];
+            for (int n = 0; n < 16; n++) c.m[n] = fr->mvp_inv[n];
+            for (int n = 0; n < 4; n++) {
+                double base = c.m[n] * px + c.m[4 + n] * py + c.m[12 + n];
+                nb[n] = base - c.m[8 + n]; c.fb[n] = base + c.m[8 + n];
+            }
+            for (int n = 0; n < 3; n++) c.from0[n] = nb[n] / nb[3];
+            c.inv_w = fr->inv_res[0]; c.inv_h = fr->inv_res[1];
+            c.jx = 0x1p-31 * c.inv_w; c.jy = 0x1p-31 * c.inv_h;
+            uint32_t state = vpo_hash3(f2u(ndc_to_uv(px)), f2u(ndc_to_uv(py)), f2u(fr->seed));
+            for (uint32_t s = 0u; s < fr->steps; s++) {
+                double dist = (log2(next_k(&state)) - 32.0) * ld;
+                double q[3], dq[3], e[3];
+                int oob = 0, inf_q = 0, out_robust = 0, in_robust = 1;
+                for (int n = 0; n < 3; n++) {
+                    q[n] = ph.pos[n] + dist * ph.dir[n];
+                    dq[n] = A * VPO_EPS23 * fmax(fmax(fabs(ph.pos[n]), fabs(dist * ph.dir[n])), fabs(q[n])) + ph.r_pos + fabs(dist) * ph.r_dir;
+                    oob |= (q[n] > 1.0) || (q[n] < 0.0);
+                    inf_q |= isinf(q[n]);
+                    out_robust |= (q[n] - 1.0 > dq[n]) || (-q[n] > dq[n]);
+                    in_robust &= (q[n] > dq[n]) && (1.0 - q[n] > dq[n]);
+                }
+                if (!inf_q && !(oob ? out_robust : in_robust)) ph.fragile = 1;
+                const int no_scatter = ph.bounces >= fr->max_bounces;
+                double t1, t2, col[3], r1 = 0.0, r2 = 0.0, rc = 0.0;
+                sample64(&t, q, no_scatter, &t1, &t2, col);
+                double wheel = next_k(&state) * 0x1p-32;
+                if (!oob) {
+                    for (int n = 0; n < 3; n++)
+                        for (int sg = -1; sg <= 1; sg += 2) {
+                            double u1, u2, cl[3];
+                            memcpy(e, q, sizeof e);
+                            e[n] += sg * dq[n];
+                            sample64(&t, e, no_scatter, &u1, &u2, cl);
+                            r1 = fmax(r1, fabs(u1 - t1)); r2 = fmax(r2, fabs(u2 - t2)); rc = fmax(rc, diff3(cl, col));
+                        }
+                    r1 += A * VPO_EPS23; r2 += A * VPO_EPS23;
+                    if (wheel < t1) { if (!(t1 - wheel > r1)) ph.fragile = 1; }
+                    else if (!(wheel - t1 > r1) || !(fabs(wheel - t2) > r2)) ph.fragile = 1;
+                }
+                uint8_t code;
+                if (oob || wheel < t1) {
+                    double radv[3] = { 0.0, 0.0, 0.0 }, rr = 0.0;
+                    code = oob ? 2 : 3;
+                    if (oob) {
+                        double env[3], ee[3], re = 0.0;
+                        env64(&t, ph.dir, env);
+                        if (ph.r_dir > 0.0)              /* a chained event: the direction looked up is the twin's own, within its radius */
+                            for (int n = 0; n < 3; n++)
+                                for (int sg = -1; sg <= 1; sg += 2) {
+                                    memcpy(e, ph.dir, sizeof e);
+                                    e[n] += sg * ph.r_dir;
+                                    env64(&t, e, ee);
+                                    re = fmax(re, diff3(ee, env));
+                                }
+                        for (int n = 0; n < 3; n++) { radv[n] = ph.tr[n] * env[n]; rr = fmax(rr, ph.r_tr * fabs(env[n]) + fabs(ph.tr[n]) * re); }
+                    }
+                    ph.samples++;
+                    double inv_n = 1.0 / (double)ph.samples;
+                    for (int n = 0; n < 3; n++) ph.rad[n] += (radv[n] - ph.rad[n]) * inv_n;
+                    ph.r_rad = ph.r_rad * (1.0 - inv_n) + rr * inv_n;
+                    reset64(&c, &state, A, &ph);
+                } else {
+                    memcpy(ph.pos, q, sizeof q);
+                    ph.r_pos = fmax(fmax(dq[0], dq[1]), dq[2]);
+                    code = 0;
+                    if (wheel < t2) {
+                        code = 1;
+                        double rt = 0.0;
+                        for (int n = 0; n < 3; n++) { rt = fmax(rt, ph.r_tr * fabs(col[n]) + fabs(ph.tr[n]) * rc); ph.tr[n] *= col[n]; }
+                        ph.r_tr = rt;
+                        scatter64(&state, A, g, &ph);
+                    }
+                }
+                out_codes[k * fr->steps + s] = code;
+            }
+            double *o = out_state + 14 * k;
+            memcpy(o, ph.pos, 24); memcpy(o + 3, ph.dir, 24); memcpy(o + 6, ph.tr, 24); memcpy(o + 9, ph.rad, 24);
+            o[12] = (double)ph.bounces; o[13] = (double)ph.samples;
+            double *rd = out_radius + 4 * k;
+            rd[0] = ph.r_pos; rd[1] = ph.r_dir; rd[2] = ph.r_tr; rd[3] = ph.r_rad;
+            for (int n = 0; n < 12; n++) if (o[n] != o[n]) ph.fragile = 1;
+            for (int n = 0; n < 4; n++) if (!(rd[n] <= DBL_MAX)) ph.fragile = 1;
+            out_fragile[k] = (uint8_t)ph.fragile;
+            ns++;
+        }
+    }
+    tables_free(&t);
+    return ns;
 }

@@ -1,7 +1,9 @@
 """GPU: the fast-arithmetic variant of the MCM integrate pass (VPT_OPTION_FAST_MATH — hardware rcp / rsq / sqrt / log / sin /
 cos and algebraically equal shorter forms, vpt_kernels.h mcm_events_fast) against the CONTRACT oracle.
 
-There is no bit-exact CPU twin of this variant; what is checked (tolerances as in tests/test_plain_reading.py):
+There is no bit-exact CPU mirror of this variant.  Its float64 twin (oracle/vpt_oracle.c vpo_mcm_fast64) is held to this oracle event by
+event in tests/test_fast_twin.py, and the fast kernels to the twin, event by event, in tests/test_gpu_fast_twin.py; what is checked HERE,
+by statistics (tolerances as in tests/test_plain_reading.py):
   * the integer parts agree exactly: samples per pass = P * steps, PCG stream shared;
   * reset buffers are untouched by the option (bit-identical to the oracle);
   * after the first event >= 99.9 % of the pixels took the same branch as the oracle and sit at the same place (1e-4);

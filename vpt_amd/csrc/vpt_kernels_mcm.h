@@ -290,13 +290,21 @@ VPT_DEV void mcm_events_early(const PassArgs &a, const LdsTables &t, Photon &ph,
 //     pixel constant);
 //   * normalize(to.xyz / to.w - from) = sign(to.w) * normalize(to.xyz - to.w * from): no division by w.
 // The integer PCG stream is identical, so the two variants take the same decisions except where a comparison falls
-// within rounding error; there is NO bit-exact CPU twin of this variant — it is checked against the contract oracle by
-// first-event agreement and converged-image statistics (tests/test_gpu_fast_math.py, tolerance in DESIGN.md §3).
+// within rounding error.  There is no bit-exact CPU mirror of this variant; it is checked against the contract oracle by first-event
+// agreement and converged-image statistics (tests/test_gpu_fast_math.py, tolerance in DESIGN.md §3).  oracle/vpt_oracle.c holds its
+// float64 TWIN (vpo_mcm_fast64: the same stream, forms and branches in double; tests/test_fast_twin.py), to which these kernels are held
+// event by event in tests/test_gpu_fast_twin.py.
 VPT_DEV float hw_rcp(float x) { return __builtin_amdgcn_rcpf(x); }        // 1/(+-0) = +-inf, as the slab test needs
 VPT_DEV float hw_rsq(float x) { return __builtin_amdgcn_rsqf(x); }
 VPT_DEV float hw_sqrt(float x) { return __builtin_amdgcn_sqrtf(x); }
 VPT_DEV float hw_log2(float x) { return __builtin_amdgcn_logf(x); }       // log2(0) = -inf
 VPT_DEV float pcg_float(uint32_t &state) { state = pcg(state); return (float)state; }
+// -ln(u * 2^-32) / extinction = fma(log2(u), ld, -32 * ld) with ld = -ln 2 / extinction, kept FINITE here, ahead of the event loop:
+// extinction 0 arrives as inv_extinction = 1 / 0 = +inf (the contract's -log(u) * inf = +inf: every free path leaves the cube), and
+// ld = -inf would make every distance fma(log2 u, -inf, +inf) = NaN: a photon that is never out of bounds and deposits 0.  With the
+// reciprocal held at FLT_MAX, ld = -2.4e38, -32 * ld still overflows to +inf and the distance is +inf; the identity for every finite
+// reciprocal.
+VPT_DEV float fast_log2_scale(float inv_extinction) { return -0.6931471805599453f * vmin(inv_extinction, 3.402823466e+38f); }
 // sampleHenyeyGreenstein with hardware sqrt / sin / cos; v_sin_f32 / v_cos_f32 take their argument in revolutions:
 // sin(TWOPI * u) = v_sin_f32(u)
 VPT_DEV f3 sample_hg_fast(uint32_t &state, float g, f3 dir) {
@@ -368,7 +376,7 @@ template <int V>
 VPT_DEV void mcm_events_fast(const PassArgs &a, const LdsTables &t, Photon &ph, float px, float py EV_PARAM) {
     const FastPixel c = fast_pixel(a, px, py);
     // -ln(u * 2^-32) / extinction = (log2(u) - 32) * ld
-    const float ld = -0.6931471805599453f * a.inv_extinction, ld32 = -32.0f * ld;
+    const float ld = fast_log2_scale(a.inv_extinction), ld32 = -32.0f * ld;
 
     uint32_t state = hash3(__float_as_uint(ndc_to_uv(px)), __float_as_uint(ndc_to_uv(py)), __float_as_uint(a.seed));
     EV_MARK(evc, 5, "s_waitcnt vmcnt(0) lgkmcnt(0)");
@@ -410,7 +418,7 @@ VPT_DEV void mcm_events_fast(const PassArgs &a, const LdsTables &t, Photon &ph, 
 template <int V>
 VPT_DEV void mcm_events_fast_early(const PassArgs &a, const LdsTables &t, Photon &ph, float px, float py) {     // see mcm_events_early
     const FastPixel c = fast_pixel(a, px, py);
-    const float ld = -0.6931471805599453f * a.inv_extinction, ld32 = -32.0f * ld;
+    const float ld = fast_log2_scale(a.inv_extinction), ld32 = -32.0f * ld;
     uint32_t state = hash3(__float_as_uint(ndc_to_uv(px)), __float_as_uint(ndc_to_uv(py)), __float_as_uint(a.seed));
     for (uint32_t s = 0u; s < a.steps; s++) {
         float dist = fmaf(hw_log2(pcg_float(state)), ld, ld32);
@@ -659,7 +667,7 @@ VPT_DEV void mcm_events_miss(const PassArgs &a, const float4 *tf, Photon &ph, fl
 }
 template <int V, bool CHECK, bool LATE, bool DEPOSIT = true>
 VPT_DEV void mcm_events_miss_fast(const PassArgs &a, const float4 *tf, const FastPixel &c, Photon &ph, float px, float py, uint32_t state) {
-    const float ld = -0.6931471805599453f * a.inv_extinction, ld32 = -32.0f * ld;
+    const float ld = fast_log2_scale(a.inv_extinction), ld32 = -32.0f * ld;
     for (uint32_t s = 0u; s < a.steps; s++) {
         float dist = fmaf(hw_log2(pcg_float(state)), ld, ld32);
         ph.position = madd3(ph.position, dist, ph.direction);
