@@ -10,6 +10,8 @@
                                      transfer function's axis by a window derived on the device; --window auto: the 0.5 / 99.5 percentiles)
     python examples/render_png.py --window auto --smooth 1 --reduce 1 --gradient sobel ...   (smoothed, then reduced to half resolution, on the
                                      device, before the gradient is derived)
+    python examples/render_png.py --window auto --rank median --rank-passes 2 --gradient sobel ...   (impulse noise removed by a 3 x 3 x 3 median
+                                     on the device, edges kept, before the gradient is derived; also erode, dilate, open, close)
     python examples/render_png.py --renderer mcm --env sky.hdr --tonemapper aces ...   (a Radiance .hdr environment map lights MCS / MCM)
 
 Without --volume a synthetic 128^3 sphere with lattice noise is used.  PNG encoding is plain zlib (no imaging library)."""
@@ -44,6 +46,9 @@ def main():
     ap.add_argument("--window", default=None, help="LO,HI | range | auto: window the volume's values to the transfer function's axis "
                                                    "(auto: the 0.5 / 99.5 percentiles; the range for a float volume)")
     ap.add_argument("--window-format", default="r8", choices=["r8", "r16"])
+    ap.add_argument("--rank", default=None, choices=["median", "erode", "dilate", "open", "close"], metavar="OP",
+                    help="median | erode | dilate | open | close over the 3 x 3 x 3 box on the device, behind the window and in front of the smoothing (R8 / R16 volumes)")
+    ap.add_argument("--rank-passes", type=int, default=1, metavar="N", help="passes of --rank (1 .. 8)")
     ap.add_argument("--smooth", type=int, default=None, metavar="N", help="binomial 3 x 3 x 3 smoothing passes (1 .. 8) on the device, behind the window (R8 / R16 volumes)")
     ap.add_argument("--reduce", type=int, default=None, metavar="N", help="reduce the volume N times to half its resolution on the device, behind the smoothing")
     ap.add_argument("--yaw", type=float, default=0.6)
@@ -59,7 +64,7 @@ def main():
     rc = vpt_amd.RenderingContext({'resolution': (a.width, a.height), 'filter': a.filter, 'rng': GoldenRatioRng(),
                                    'gradient': a.gradient, 'gradientGain': a.gradient_gain,
                                    'window': None if window == 'auto' else window, 'windowFormat': a.window_format,
-                                   'smooth': a.smooth, 'reduce': a.reduce})
+                                   'rank': a.rank, 'rankPasses': a.rank_passes, 'smooth': a.smooth, 'reduce': a.reduce})
     rc.resize(a.width, a.height)
     rc.gl.getExtension('EXT_texture_norm16')                      # 16-bit volumes are taken
     if a.volume.endswith(".bvp"):

@@ -234,6 +234,29 @@ VPT_API int vpt_volume_code_histogram(vpt_volume *vol, uint32_t *bins, size_t nb
 VPT_API int vpt_volume_reduce(vpt_volume *src, vpt_volume **out);
 VPT_API int vpt_volume_smooth(vpt_volume *src, int passes, vpt_volume **out);
 
+/* ---- median and grey-level morphology on the device (extension; DESIGN.md "Median and morphology") */
+/* vpt_volume_rank: a new volume of src's size and format whose texels are rank statistics of the source's over the 3 x 3 x 3 box: the
+ * edge-preserving denoiser (impulse noise is removed, not smeared) and the morphology in front of a gradient or an iso-surface.  Sources: R8
+ * and R16, the formats the smoothing and the gradient take (the window makes one of any scalar volume); every other format:
+ * VPT_ERR_UNSUPPORTED, naming it.  v = the texel code, indices clamped per axis (CLAMP_TO_EDGE); the neighbourhood N(x, y, z) is the 27
+ * clamped taps v(x + a, y + b, z + c), a, b, c in {-1, 0, 1}, as a multiset: a clamped tap counts as often as it occurs.  One pass:
+ *   VPT_RANK_MEDIAN: the 14th smallest of the 27 taps;   VPT_RANK_ERODE: the smallest;   VPT_RANK_DILATE: the largest.
+ * All compares are unsigned on the whole code (R16 codes at or above 32768 are larger than those below).  `passes` p (1 .. 8; otherwise
+ * VPT_ERR_INVALID): MEDIAN, ERODE and DILATE apply their pass p times; VPT_RANK_OPEN is p erosions, then p dilations; VPT_RANK_CLOSE p
+ * dilations, then p erosions, inside one call (the result is finalized once).  Any other `op`: VPT_ERR_INVALID.
+ *   So dilate(v) = M - erode(M - v) and median(v) = M - median(M - v), M = 2^B - 1; p erosions are the minimum over the clamped
+ *   (2 p + 1)^3 box; erode <= median <= dilate and open <= v <= close; opening and closing are idempotent; a constant volume stays as it is.
+ * vpt_amd.rank_texels states the contract in numpy.
+ * The result is a new, finalized volume on src's context with src's filter, enqueued on the context's stream behind any upload into src;
+ * src is not changed and may be destroyed afterwards.  The result is an ordinary volume (every renderer, set_filter, upload_block,
+ * read_block, histogram, window, smooth, reduce, derive_gradient, and this again) */
+#define VPT_RANK_MEDIAN 0
+#define VPT_RANK_ERODE  1
+#define VPT_RANK_DILATE 2
+#define VPT_RANK_OPEN   3
+#define VPT_RANK_CLOSE  4
+VPT_API int vpt_volume_rank(vpt_volume *src, int op, int passes, vpt_volume **out);
+
 /* ---- renderer: AbstractRenderer.js:17-116 and the four subclasses */
 /* new R(gl, volume, camera, environmentTexture, {resolution}) — AbstractRenderer.js:17-49; width != height is the
  * documented extension (uInverseResolution = (1/W, 1/H)).  Buffers are allocated as in _rebuildBuffers :78-92. */

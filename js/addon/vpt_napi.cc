@@ -202,6 +202,14 @@ static napi_value VolumeSmooth(napi_env env, napi_callback_info info) {
     VPT_CHECK(vpt_volume_smooth(v, passes, &out));
     return make_external(env, out);
 }
+// volumeRank(volume, op, passes) -> a new volume handle: `passes` applications of the rank operator VPT_RANK_* over the 3 x 3 x 3 box
+static napi_value VolumeRank(napi_env env, napi_callback_info info) {
+    napi_value a[3]; vpt_volume *v; int32_t op, passes;
+    if (!get_args(env, info, 3, a) || !get_handle(env, a[0], &v) || !get_i32(env, a[1], &op) || !get_i32(env, a[2], &passes)) return nullptr;
+    vpt_volume *out = nullptr;
+    VPT_CHECK(vpt_volume_rank(v, op, passes, &out));
+    return make_external(env, out);
+}
 // volumeRange(volume) -> [lo, hi]: the smallest and the largest code or value
 static napi_value VolumeRange(napi_env env, napi_callback_info info) {
     napi_value a[1]; vpt_volume *v;
@@ -531,7 +539,7 @@ static napi_value Init(napi_env env, napi_value exports) {
     EXPORT("volumeDeriveGradient", VolumeDeriveGradient); EXPORT("volumeReadBlock", VolumeReadBlock); EXPORT("volumeHistogram", VolumeHistogram);
     CONST(VPT_GRADIENT_CENTRAL); CONST(VPT_GRADIENT_SOBEL);
     EXPORT("volumeWindow", VolumeWindow); EXPORT("volumeRange", VolumeRange); EXPORT("volumeCodeHistogram", VolumeCodeHistogram);
-    EXPORT("volumeReduce", VolumeReduce); EXPORT("volumeSmooth", VolumeSmooth);
+    EXPORT("volumeReduce", VolumeReduce); EXPORT("volumeSmooth", VolumeSmooth); EXPORT("volumeRank", VolumeRank);
     EXPORT("rendererCreate", RendererCreate); EXPORT("rendererDestroy", RendererDestroy); EXPORT("rendererSetShard", RendererSetShard);
     EXPORT("rendererLocalRows", RendererLocalRows); EXPORT("rendererGlobalRow", RendererGlobalRow);
     EXPORT("rendererSetVolume", RendererSetVolume); EXPORT("rendererSetTransferFunction", RendererSetTransferFunction);

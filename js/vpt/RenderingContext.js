@@ -8,11 +8,13 @@
 //   { percentiles: [a, b] }, windowFormat: 'r8' (default) or 'r16': a one-channel volume is windowed when it is loaded, before the gradient
 //   is derived (Volume.window); smooth: null (default) or passes 1 .. 8: an R8 / R16 volume is smoothed behind the window (Volume.smooth);
 //   reduce: null (default), 0 or levels >= 1: the volume is reduced to half its resolution that many times behind the smoothing (Volume.reduce)
+//   rank: null (default), 'median', 'erode', 'dilate', 'open' or 'close', rankPasses 1 .. 8 (default 1): an R8 / R16 volume gets that rank filter
+//   over the 3 x 3 x 3 box behind the window and in front of the smoothing (Volume.rank)
 const { EventTarget, CustomEvent } = require('./EventTarget.js');
 const { Context } = require('./Context.js');
 const { OrbitCameraAnimator } = require('./animators.js');
 const { Node, Transform, PerspectiveCamera } = require('./scene.js');
-const { Volume, gradientArguments, windowFormatBits, checkPasses, checkLevels } = require('./Volume.js');
+const { Volume, gradientArguments, windowFormatBits, checkPasses, checkLevels, rankOperatorCode, checkRankPasses } = require('./Volume.js');
 const { native } = require('./native.js');
 const { RendererFactory } = require('./renderers/RendererFactory.js');
 const { ToneMapperFactory } = require('./tonemappers/ToneMapperFactory.js');
@@ -33,6 +35,10 @@ constructor(options) {
     this.reduce = options.reduce !== undefined ? options.reduce : null;
     if (this.smooth !== null) { checkPasses(this.smooth); }                          // likewise
     if (this.reduce !== null && this.reduce !== 0) { checkLevels(this.reduce); }
+    this.rank = options.rank !== undefined ? options.rank : null;
+    this.rankPasses = options.rankPasses !== undefined && options.rankPasses !== null ? options.rankPasses : 1;
+    if (this.rank !== null) { rankOperatorCode(this.rank); }                         // likewise
+    checkRankPasses(this.rankPasses);
     this.gl = new Context(options.device || 0);                                   // initGL(), :61-105
     this.environmentTexture = { data: new Uint8Array([255, 255, 255, 255]), width: 1, height: 1 };   // :90-101
     this._rng = options.rng;
@@ -82,6 +88,14 @@ async setVolume(reader) {                                                       
             const source = this.volume, w = this._windowOf(source);
             this.volume = source.window({ lo: w[0], hi: w[1], format: this.windowFormat });
             source.destroy();
+        }
+        if (this.rank !== null) {
+            const N = native(), fmt = this.volume.nativeFormat();
+            if (fmt === N.VPT_FORMAT_R8 || fmt === N.VPT_FORMAT_R16) {                 // the formats the smoothing takes: any other volume as it is
+                const source = this.volume;
+                this.volume = source.rank(this.rank, this.rankPasses);
+                source.destroy();
+            }
         }
         if (this.smooth !== null) {
             const N = native(), fmt = this.volume.nativeFormat();

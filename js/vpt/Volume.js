@@ -325,6 +325,20 @@ smooth(passes) {
     return this._sameFormat(native().volumeSmooth(this.texture, passes), this.modality.dimensions);
 }
 
+// ---- extension: median and grey-level morphology (include/vpt.h; DESIGN.md "Median and morphology") ----
+// a new, ready R8 / R16 volume of this (R8 / R16) volume's size and with its filter: `passes` (1 .. 8, default 1) applications of the rank
+// operator `op` ('median' | 'erode' | 'dilate' | 'open' | 'close') over the clamped 3 x 3 x 3 box, derived on the device; this volume is not changed
+rank(op, passes) {
+    const code = rankOperatorCode(op);
+    passes = checkRankPasses(passes !== undefined ? passes : 1);
+    return this._sameFormat(native().volumeRank(this.texture, code, passes), this.modality.dimensions);
+}
+median(passes) { return this.rank('median', passes); }
+erode(passes) { return this.rank('erode', passes); }
+dilate(passes) { return this.rank('dilate', passes); }
+open(passes) { return this.rank('open', passes); }
+close(passes) { return this.rank('close', passes); }
+
 }
 // the number of smoothing passes (an integer in 1 .. 8) / of reductions (an integer >= 1); throws for anything else
 function checkPasses(passes) {
@@ -335,4 +349,16 @@ function checkLevels(levels) {
     if (!Number.isInteger(levels) || levels < 1) { throw new Error('reduction levels are an integer >= 1, not ' + JSON.stringify(levels)); }
     return levels;
 }
-module.exports = { Volume, RAWReader, filterCode, gradientArguments, windowFormatBits, percentileWindow, checkPasses, checkLevels };
+// VPT_RANK_* of 'median' | 'erode' | 'dilate' | 'open' | 'close'; throws for anything else
+const RANK_OPERATORS = ['median', 'erode', 'dilate', 'open', 'close'];
+function rankOperatorCode(name) {
+    const code = typeof name === 'string' ? RANK_OPERATORS.indexOf(name) : -1;
+    if (code < 0) { throw new Error("a rank operator is 'median', 'erode', 'dilate', 'open' or 'close', not " + JSON.stringify(name)); }
+    return code;
+}
+// the number of rank-filter passes (an integer in 1 .. 8); throws for anything else
+function checkRankPasses(passes) {
+    if (!Number.isInteger(passes) || passes < 1 || passes > 8) { throw new Error('rank-filter passes are an integer in 1 .. 8, not ' + JSON.stringify(passes)); }
+    return passes;
+}
+module.exports = { Volume, RAWReader, filterCode, gradientArguments, windowFormatBits, percentileWindow, checkPasses, checkLevels, rankOperatorCode, checkRankPasses };

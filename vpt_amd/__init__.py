@@ -21,6 +21,7 @@ from .hdr import HDRImage, read_hdr
 from .gradient import gradient_magnitude
 from .window import window_texels, percentile_window
 from .pyramid import reduce_texels, smooth_texels
+from .rank import rank_texels
 from ._native import VptError
 
 __all__ = [
@@ -31,5 +32,5 @@ __all__ = [
     'AbstractToneMapper', 'ArtisticToneMapper', 'RangeToneMapper', 'ReinhardToneMapper', 'Reinhard2ToneMapper',
     'Uncharted2ToneMapper', 'FilmicToneMapper', 'UnrealToneMapper', 'AcesToneMapper', 'LottesToneMapper',
     'UchimuraToneMapper', 'ToneMapperFactory', 'RenderingContext', 'CircleAnimator', 'OrbitCameraAnimator', 'TransferFunction',
-    'HDRImage', 'read_hdr', 'gradient_magnitude', 'window_texels', 'percentile_window', 'reduce_texels', 'smooth_texels',
+    'HDRImage', 'read_hdr', 'gradient_magnitude', 'window_texels', 'percentile_window', 'reduce_texels', 'smooth_texels', 'rank_texels',
 ]

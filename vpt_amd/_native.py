@@ -28,6 +28,7 @@ FORMAT_R8_SNORM, FORMAT_RG8_SNORM = 4, 5
 FORMAT_RGB565, FORMAT_RGBA4, FORMAT_RGB5_A1, FORMAT_RGB10_A2, FORMAT_R11F_G11F_B10F, FORMAT_RGB9_E5 = 6, 7, 8, 9, 10, 11
 FORMAT_R16, FORMAT_RG16, FORMAT_R16_SNORM, FORMAT_RG16_SNORM = 12, 13, 14, 15
 GRADIENT_CENTRAL, GRADIENT_SOBEL = 0, 1
+RANK_MEDIAN, RANK_ERODE, RANK_DILATE, RANK_OPEN, RANK_CLOSE = 0, 1, 2, 3, 4
 ENV_RGBA8, ENV_RGBA16F, ENV_RGBA32F, ENV_RGBE8 = 0, 1, 2, 3
 BUFFER_RENDER, BUFFER_FRAME, BUFFER_ACCUM = 0, 1, 2
 BUFFER_MCM_POSITION, BUFFER_MCM_DIRECTION, BUFFER_MCM_TRANSMITTANCE, BUFFER_MCM_RADIANCE = 3, 4, 5, 6
@@ -49,7 +50,7 @@ SYMBOLS = [
     "vpt_volume_set_filter", "vpt_volume_destroy", "vpt_volume_bricked_bytes", "vpt_volume_set_wide_tables",
     "vpt_volume_derive_gradient", "vpt_volume_read_block", "vpt_volume_histogram",
     "vpt_volume_window", "vpt_volume_range", "vpt_volume_code_histogram",
-    "vpt_volume_reduce", "vpt_volume_smooth",
+    "vpt_volume_reduce", "vpt_volume_smooth", "vpt_volume_rank",
     "vpt_renderer_create", "vpt_renderer_set_shard", "vpt_renderer_local_rows", "vpt_renderer_global_row",
     "vpt_renderer_destroy", "vpt_renderer_set_volume", "vpt_renderer_set_transfer_function",
     "vpt_renderer_set_environment", "vpt_renderer_set_environment_texels", "vpt_renderer_resize",
@@ -156,7 +157,7 @@ def lib():
         "vpt_volume_histogram": [P, C.POINTER(C.c_uint32), SZ],
         "vpt_volume_window": [P, C.c_double, C.c_double, I, PP], "vpt_volume_range": [P, C.POINTER(C.c_double), C.POINTER(C.c_double)],
         "vpt_volume_code_histogram": [P, C.POINTER(C.c_uint32), SZ],
-        "vpt_volume_reduce": [P, PP], "vpt_volume_smooth": [P, I, PP],
+        "vpt_volume_reduce": [P, PP], "vpt_volume_smooth": [P, I, PP], "vpt_volume_rank": [P, I, I, PP],
         "vpt_renderer_create": [P, I, I, I, PP],
         "vpt_renderer_set_shard": [P, I, I, I], "vpt_renderer_local_rows": [P, C.POINTER(I)],
         "vpt_renderer_global_row": [P, I, C.POINTER(I)],

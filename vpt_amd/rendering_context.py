@@ -41,6 +41,14 @@ class RenderingContext(EventTarget):
         if self.reduce is not None and not (self.reduce == 0 and not isinstance(self.reduce, bool)):
             from .pyramid import check_levels
             check_levels(self.reduce)
+        # (extension) None | 'median' | 'erode' | 'dilate' | 'open' | 'close', rankPasses 1 .. 8: an R8 / R16 volume gets that rank filter over
+        # the 3 x 3 x 3 box when it is loaded, behind the window and in front of the smoothing
+        self.rank = options.get('rank')
+        self.rankPasses = options['rankPasses'] if options.get('rankPasses') is not None else 1
+        from .rank import operator_code as rank_operator_code, check_passes as check_rank_passes
+        if self.rank is not None:
+            rank_operator_code(self.rank)                                              # a bad option fails here, not at the first volume
+        check_rank_passes(self.rankPasses)
         self.gl = Context(options.get('device', 0))                                   # initGL(), :61-105
         self.environmentTexture = np.array([[[255, 255, 255, 255]]], dtype=np.uint8)   # :90-101
         self._rng = options.get('rng')
@@ -84,6 +92,10 @@ class RenderingContext(EventTarget):
                 source = self.volume
                 lo, hi = self._window_of(source)
                 self.volume = source.window(lo, hi, self.windowFormat)                # the transfer function's x axis is [lo, hi]
+                source.destroy()
+            if self.rank is not None and self._one_channel_unorm(self.volume):
+                source = self.volume
+                self.volume = source.rank(self.rank, self.rankPasses)
                 source.destroy()
             if self.smooth is not None and self._one_channel_unorm(self.volume):
                 source = self.volume

@@ -389,6 +389,31 @@ class Volume(EventTarget):
         N.check(N.lib().vpt_volume_smooth(self.texture, check_passes(passes), C.byref(h)))
         return self._same_format(h, self.modality['dimensions'])
 
+    # ---- extension: median and grey-level morphology (include/vpt.h; DESIGN.md "Median and morphology") ----
+    def rank(self, op, passes=1):
+        """A new, ready R8 / R16 volume of this (R8 / R16) volume's size and with its filter: ``passes`` (1 .. 8) applications of the rank
+        operator ``op`` ('median' | 'erode' | 'dilate' | 'open' | 'close') over the clamped 3 x 3 x 3 box (vpt_amd.rank_texels states it),
+        derived on the device.  This volume is not changed."""
+        from .rank import operator_code, check_passes
+        h = C.c_void_p()
+        N.check(N.lib().vpt_volume_rank(self.texture, operator_code(op), check_passes(passes), C.byref(h)))
+        return self._same_format(h, self.modality['dimensions'])
+
+    def median(self, passes=1):
+        return self.rank('median', passes)
+
+    def erode(self, passes=1):
+        return self.rank('erode', passes)
+
+    def dilate(self, passes=1):
+        return self.rank('dilate', passes)
+
+    def open(self, passes=1):
+        return self.rank('open', passes)
+
+    def close(self, passes=1):
+        return self.rank('close', passes)
+
     def set_wide_tables(self, wide):
         """force the > 4 GiB addressing variant of the kernels (automatic above 4 GiB of bricked data)"""
         N.check(N.lib().vpt_volume_set_wide_tables(self.texture, 1 if wide else 0))
