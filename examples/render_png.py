@@ -12,6 +12,9 @@
                                      device, before the gradient is derived)
     python examples/render_png.py --window auto --rank median --rank-passes 2 --gradient sobel ...   (impulse noise removed by a 3 x 3 x 3 median
                                      on the device, edges kept, before the gradient is derived; also erode, dilate, open, close)
+    python examples/render_png.py --window auto --rank open --components 96,255 --components-min 64 ...   (island removal on the device: only
+                                     connected structures of at least 64 voxels in the codes 96 .. 255 keep their texels; --components-keep 1: the
+                                     largest only; --components-label: a row of the 2-D transfer function per structure)
     python examples/render_png.py --renderer mcm --env sky.hdr --tonemapper aces ...   (a Radiance .hdr environment map lights MCS / MCM)
 
 Without --volume a synthetic 128^3 sphere with lattice noise is used.  PNG encoding is plain zlib (no imaging library)."""
@@ -49,6 +52,13 @@ def main():
     ap.add_argument("--rank", default=None, choices=["median", "erode", "dilate", "open", "close"], metavar="OP",
                     help="median | erode | dilate | open | close over the 3 x 3 x 3 box on the device, behind the window and in front of the smoothing (R8 / R16 volumes)")
     ap.add_argument("--rank-passes", type=int, default=1, metavar="N", help="passes of --rank (1 .. 8)")
+    ap.add_argument("--components", default=None, metavar="LO,HI", help="connected components of the codes LO .. HI on the device (R8 / R16 volumes), behind --rank: "
+                                                                        "without --components-label everything else becomes 0")
+    ap.add_argument("--connectivity", type=int, default=6, choices=[6, 18, 26], help="voxels of a component share faces (6), faces or edges (18), faces, edges or corners (26)")
+    ap.add_argument("--components-min", type=int, default=1, metavar="N", help="components of fewer than N voxels are dropped")
+    mode = ap.add_mutually_exclusive_group()
+    mode.add_argument("--components-keep", type=int, default=None, metavar="N", help="only the N largest components keep their texels (default: all that are not dropped)")
+    mode.add_argument("--components-label", action="store_true", help="the second channel is the component's rank (1 = the largest) instead of a gradient")
     ap.add_argument("--smooth", type=int, default=None, metavar="N", help="binomial 3 x 3 x 3 smoothing passes (1 .. 8) on the device, behind the window (R8 / R16 volumes)")
     ap.add_argument("--reduce", type=int, default=None, metavar="N", help="reduce the volume N times to half its resolution on the device, behind the smoothing")
     ap.add_argument("--yaw", type=float, default=0.6)
@@ -61,7 +71,12 @@ def main():
     if window not in (None, 'range', 'auto'):
         lo, hi = (float(x) for x in window.split(','))
         window = [lo, hi]
-    rc = vpt_amd.RenderingContext({'resolution': (a.width, a.height), 'filter': a.filter, 'rng': GoldenRatioRng(),
+    components = None
+    if a.components is not None:
+        lo, hi = (int(x) for x in a.components.split(','))
+        components = {'lo': lo, 'hi': hi, 'connectivity': a.connectivity, 'minVoxels': a.components_min,
+                      'mode': 'label' if a.components_label else 'keep', 'keep': a.components_keep}
+    rc = vpt_amd.RenderingContext({'resolution': (a.width, a.height), 'components': components, 'filter': a.filter, 'rng': GoldenRatioRng(),
                                    'gradient': a.gradient, 'gradientGain': a.gradient_gain,
                                    'window': None if window == 'auto' else window, 'windowFormat': a.window_format,
                                    'rank': a.rank, 'rankPasses': a.rank_passes, 'smooth': a.smooth, 'reduce': a.reduce})
@@ -91,7 +106,7 @@ def main():
     rc.chooseRenderer(a.renderer)
     rc.chooseToneMapper(a.tonemapper)
     if a.tf == "colour":
-        rc.renderer.setTransferFunction(colour_tf(256, 64 if a.gradient else 1))
+        rc.renderer.setTransferFunction(colour_tf(256, 64 if a.gradient or a.components_label else 1))
     if a.extinction is not None and hasattr(rc.renderer, 'extinction'):
         rc.renderer.extinction = a.extinction
     rc.renderer.reset()

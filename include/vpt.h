@@ -257,6 +257,43 @@ VPT_API int vpt_volume_smooth(vpt_volume *src, int passes, vpt_volume **out);
 #define VPT_RANK_CLOSE  4
 VPT_API int vpt_volume_rank(vpt_volume *src, int op, int passes, vpt_volume **out);
 
+/* ---- connected components of a value range on the device (extension; DESIGN.md "Connected components") */
+/* The step behind an opening or closing: "keep the largest structure", "drop everything smaller than N voxels", "give each structure its own
+ * row of the 2-D transfer function".  Sources: R8 and R16 (the window makes one of any scalar volume); every other format:
+ * VPT_ERR_UNSUPPORTED, naming it.  Volumes of more than 2^32 - 2 voxels: VPT_ERR_UNSUPPORTED (labels and counts are 32-bit).
+ *   Foreground: a voxel whose code c has lo <= c <= hi, compared as whole unsigned codes.  lo > hi, or hi above the format's largest code
+ *   (255 / 65535): VPT_ERR_INVALID.
+ *   Connectivity: 6 (voxels that share a face), 18 (a face or an edge) or 26 (a face, an edge or a corner); anything else VPT_ERR_INVALID.
+ *   Nothing wraps and nothing is clamped: voxels outside the volume are background.  A component is a maximal connected set of foreground.
+ *   Canonical order: a component's root is its voxel with the smallest linear index (z ny + y) nx + x.  Components of fewer than
+ *   `min_voxels` voxels (min_voxels >= 1; 0: VPT_ERR_INVALID) are dropped; the others are listed by voxel count descending, then by root
+ *   index ascending.  The rank of a voxel is the 1-based position of its component in that list (1 = the largest), and 0 for background
+ *   and for the voxels of dropped components.  So no output depends on the order in which the device merges.
+ * vpt_amd.components_texels, keep_texels and label_texels state the contract in numpy.
+ * The handle owns a device copy of the source's texels and one uint32 rank per voxel: src is not changed and may be destroyed afterwards;
+ * a viewer labels once and tries several selections.  vpt_volume_components blocks (the list is ordered on the host). */
+typedef struct vpt_components vpt_components;
+struct vpt_component       { uint32_t root_x, root_y, root_z, voxels; };
+struct vpt_components_info { uint64_t listed, dropped, foreground_voxels, listed_voxels; };   /* components listed / dropped; voxels in range / in listed components */
+VPT_API int vpt_volume_components(vpt_volume *src, uint32_t lo, uint32_t hi, int connectivity, uint32_t min_voxels, vpt_components **out);
+VPT_API int vpt_components_info(vpt_components *c, struct vpt_components_info *info);
+/* components first .. first + n - 1 of the canonical order (first is 0-based); a range not within `listed`: VPT_ERR_INVALID */
+VPT_API int vpt_components_list(vpt_components *c, uint64_t first, uint64_t n, struct vpt_component *dst);
+/* the ranks of a box of voxels, [d][h][w] uint32; the box and nbytes are checked as vpt_volume_read_block checks them.  Blocks. */
+VPT_API int vpt_components_ranks(vpt_components *c, int x, int y, int z, int w, int h, int d, uint32_t *host_dst, size_t nbytes);
+/* a new, finalized volume of the source's size, format and filter: the source code where first_rank <= rank <= last_rank, `fill` elsewhere.
+ * 1 <= first_rank <= last_rank (last_rank may exceed `listed`) and fill <= the format's largest code; otherwise VPT_ERR_INVALID.
+ * keep(1, 1, 0) is "the largest only"; keep(1, UINT64_MAX, 0) behind a min_voxels is island removal. */
+VPT_API int vpt_components_keep(vpt_components *c, uint64_t first_rank, uint64_t last_rank, uint32_t fill, vpt_volume **out);
+/* a new, finalized RG8 / RG16 volume with the source's filter: R the source code, G = min(rank, M), M = 255 / 65535, so a row of the 2-D
+ * transfer function selects a structure; ranks beyond M share the last row (this saturation is part of the contract) */
+VPT_API int vpt_components_label(vpt_components *c, vpt_volume **out);
+/* (for measurements) milliseconds of the phases of vpt_volume_components, ms[VPT_COMPONENTS_PHASES]: tile labelling, merge launches, flatten
+ * launches, sizes, census + compaction, host sort, rank write; launches[2]: merge and flatten launches.  Either pointer may be null. */
+#define VPT_COMPONENTS_PHASES 7
+VPT_API int vpt_components_profile(vpt_components *c, double *ms, uint32_t *launches);
+VPT_API int vpt_components_destroy(vpt_components *c);
+
 /* ---- renderer: AbstractRenderer.js:17-116 and the four subclasses */
 /* new R(gl, volume, camera, environmentTexture, {resolution}) — AbstractRenderer.js:17-49; width != height is the
  * documented extension (uInverseResolution = (1/W, 1/H)).  Buffers are allocated as in _rebuildBuffers :78-92. */

@@ -230,6 +230,82 @@ static napi_value VolumeCodeHistogram(napi_env env, napi_callback_info info) {
     return undefined(env);
 }
 
+// ---- connected components -----------------------------------------------------------------------------
+static bool get_u32(napi_env env, napi_value v, uint32_t *out) {
+    double d;
+    if (napi_get_value_double(env, v, &d) != napi_ok || !(d >= 0.0 && d <= 4294967295.0) || d != (double)(uint32_t)d) {
+        napi_throw_type_error(env, nullptr, "expected an integer in 0 .. 2^32 - 1"); return false;
+    }
+    *out = (uint32_t)d;
+    return true;
+}
+// a non-negative integer as a double; anything at or above 2^64 (Infinity included) is UINT64_MAX
+static bool get_u64(napi_env env, napi_value v, uint64_t *out) {
+    double d;
+    if (napi_get_value_double(env, v, &d) != napi_ok || !(d >= 0.0)) { napi_throw_type_error(env, nullptr, "expected a non-negative number"); return false; }
+    *out = d >= 18446744073709551616.0 ? UINT64_MAX : (uint64_t)d;
+    return true;
+}
+// volumeComponents(volume, lo, hi, connectivity, minVoxels) -> a components handle
+static napi_value VolumeComponents(napi_env env, napi_callback_info info) {
+    napi_value a[5]; vpt_volume *v; uint32_t lo, hi, min_voxels; int32_t connectivity;
+    if (!get_args(env, info, 5, a) || !get_handle(env, a[0], &v) || !get_u32(env, a[1], &lo) || !get_u32(env, a[2], &hi) ||
+        !get_i32(env, a[3], &connectivity) || !get_u32(env, a[4], &min_voxels)) return nullptr;
+    vpt_components *out = nullptr;
+    VPT_CHECK(vpt_volume_components(v, lo, hi, connectivity, min_voxels, &out));
+    return make_external(env, out);
+}
+// componentsInfo(components) -> [listed, dropped, foregroundVoxels, listedVoxels]
+static napi_value ComponentsInfo(napi_env env, napi_callback_info info) {
+    napi_value a[1]; vpt_components *c;
+    if (!get_args(env, info, 1, a) || !get_handle(env, a[0], &c)) return nullptr;
+    struct vpt_components_info i;
+    VPT_CHECK(vpt_components_info(c, &i));
+    const uint64_t f[4] = { i.listed, i.dropped, i.foreground_voxels, i.listed_voxels };
+    napi_value out, e;
+    napi_create_array_with_length(env, 4, &out);
+    for (int k = 0; k < 4; k++) { napi_create_double(env, (double)f[k], &e); napi_set_element(env, out, k, e); }
+    return out;
+}
+// componentsList(components, first, dst): dst is a Uint32Array of 4 n words, (rootX, rootY, rootZ, voxels) of components first .. first + n - 1
+static napi_value ComponentsList(napi_env env, napi_callback_info info) {
+    napi_value a[3]; vpt_components *c; uint64_t first; void *data; size_t n;
+    if (!get_args(env, info, 3, a) || !get_handle(env, a[0], &c) || !get_u64(env, a[1], &first) || !get_bytes(env, a[2], &data, &n)) return nullptr;
+    VPT_CHECK(vpt_components_list(c, first, n / sizeof(struct vpt_component), (struct vpt_component *)data));
+    return undefined(env);
+}
+// componentsRanks(components, x, y, z, width, height, depth, dst): the box's ranks into dst (a Uint32Array)
+static napi_value ComponentsRanks(napi_env env, napi_callback_info info) {
+    napi_value a[8]; vpt_components *c; int32_t p[6]; void *data; size_t n;
+    if (!get_args(env, info, 8, a) || !get_handle(env, a[0], &c)) return nullptr;
+    for (int i = 0; i < 6; i++) if (!get_i32(env, a[1 + i], &p[i])) return nullptr;
+    if (!get_bytes(env, a[7], &data, &n)) return nullptr;
+    VPT_CHECK(vpt_components_ranks(c, p[0], p[1], p[2], p[3], p[4], p[5], (uint32_t *)data, n));
+    return undefined(env);
+}
+// componentsKeep(components, firstRank, lastRank, fill) -> a new volume handle
+static napi_value ComponentsKeep(napi_env env, napi_callback_info info) {
+    napi_value a[4]; vpt_components *c; uint64_t first, last; uint32_t fill;
+    if (!get_args(env, info, 4, a) || !get_handle(env, a[0], &c) || !get_u64(env, a[1], &first) || !get_u64(env, a[2], &last) || !get_u32(env, a[3], &fill)) return nullptr;
+    vpt_volume *out = nullptr;
+    VPT_CHECK(vpt_components_keep(c, first, last, fill, &out));
+    return make_external(env, out);
+}
+// componentsLabel(components) -> a new volume handle
+static napi_value ComponentsLabel(napi_env env, napi_callback_info info) {
+    napi_value a[1]; vpt_components *c;
+    if (!get_args(env, info, 1, a) || !get_handle(env, a[0], &c)) return nullptr;
+    vpt_volume *out = nullptr;
+    VPT_CHECK(vpt_components_label(c, &out));
+    return make_external(env, out);
+}
+static napi_value ComponentsDestroy(napi_env env, napi_callback_info info) {
+    napi_value a[1]; vpt_components *c;
+    if (!get_args(env, info, 1, a) || !get_handle(env, a[0], &c)) return nullptr;
+    VPT_CHECK(vpt_components_destroy(c));
+    return undefined(env);
+}
+
 // ---- renderer -----------------------------------------------------------------------------------------
 static napi_value RendererCreate(napi_env env, napi_callback_info info) {
     napi_value a[4]; vpt_context *c; int32_t kind, w, h;
@@ -540,6 +616,9 @@ static napi_value Init(napi_env env, napi_value exports) {
     CONST(VPT_GRADIENT_CENTRAL); CONST(VPT_GRADIENT_SOBEL);
     EXPORT("volumeWindow", VolumeWindow); EXPORT("volumeRange", VolumeRange); EXPORT("volumeCodeHistogram", VolumeCodeHistogram);
     EXPORT("volumeReduce", VolumeReduce); EXPORT("volumeSmooth", VolumeSmooth); EXPORT("volumeRank", VolumeRank);
+    EXPORT("volumeComponents", VolumeComponents); EXPORT("componentsInfo", ComponentsInfo); EXPORT("componentsList", ComponentsList);
+    EXPORT("componentsRanks", ComponentsRanks); EXPORT("componentsKeep", ComponentsKeep); EXPORT("componentsLabel", ComponentsLabel);
+    EXPORT("componentsDestroy", ComponentsDestroy);
     EXPORT("rendererCreate", RendererCreate); EXPORT("rendererDestroy", RendererDestroy); EXPORT("rendererSetShard", RendererSetShard);
     EXPORT("rendererLocalRows", RendererLocalRows); EXPORT("rendererGlobalRow", RendererGlobalRow);
     EXPORT("rendererSetVolume", RendererSetVolume); EXPORT("rendererSetTransferFunction", RendererSetTransferFunction);

@@ -10,12 +10,17 @@
 //   reduce: null (default), 0 or levels >= 1: the volume is reduced to half its resolution that many times behind the smoothing (Volume.reduce)
 //   rank: null (default), 'median', 'erode', 'dilate', 'open' or 'close', rankPasses 1 .. 8 (default 1): an R8 / R16 volume gets that rank filter
 //   over the 3 x 3 x 3 box behind the window and in front of the smoothing (Volume.rank)
+//   components: null (default), { lo, hi, connectivity: 6, minVoxels: 1, mode: 'keep', keep: n | null } or { ..., mode: 'label' }: the connected
+//   components of the codes lo .. hi of an R8 / R16 volume (Volume.components).  'keep' runs behind the rank filter and in front of the
+//   smoothing: the n largest (null: all of at least minVoxels voxels) keep their codes, everything else becomes 0.  'label' runs where the
+//   gradient runs, on the final scalar volume: the second channel is min(rank, M); it cannot be combined with `gradient`
 const { EventTarget, CustomEvent } = require('./EventTarget.js');
 const { Context } = require('./Context.js');
 const { OrbitCameraAnimator } = require('./animators.js');
 const { Node, Transform, PerspectiveCamera } = require('./scene.js');
 const { Volume, gradientArguments, windowFormatBits, checkPasses, checkLevels, rankOperatorCode, checkRankPasses } = require('./Volume.js');
 const { native } = require('./native.js');
+const { checkConnectivity, checkRange, checkMinVoxels, checkKeep } = require('./components.js');
 const { RendererFactory } = require('./renderers/RendererFactory.js');
 const { ToneMapperFactory } = require('./tonemappers/ToneMapperFactory.js');
 
@@ -39,6 +44,10 @@ constructor(options) {
     this.rankPasses = options.rankPasses !== undefined && options.rankPasses !== null ? options.rankPasses : 1;
     if (this.rank !== null) { rankOperatorCode(this.rank); }                         // likewise
     checkRankPasses(this.rankPasses);
+    this.components = RenderingContext._componentsSpec(options.components);          // likewise
+    if (this.components !== null && this.components.mode === 'label' && this.gradient !== null) {
+        throw new Error("components mode 'label' and gradient both write the second channel: name one of them");
+    }
     this.gl = new Context(options.device || 0);                                   // initGL(), :61-105
     this.environmentTexture = { data: new Uint8Array([255, 255, 255, 255]), width: 1, height: 1 };   // :90-101
     this._rng = options.rng;
@@ -97,6 +106,7 @@ async setVolume(reader) {                                                       
                 source.destroy();
             }
         }
+        if (this.components !== null && this.components.mode === 'keep') { this._derive(found => found.keep(1, this.components.keep)); }
         if (this.smooth !== null) {
             const N = native(), fmt = this.volume.nativeFormat();
             if (fmt === N.VPT_FORMAT_R8 || fmt === N.VPT_FORMAT_R16) {                 // the formats the gradient takes: any other volume as it is
@@ -118,6 +128,7 @@ async setVolume(reader) {                                                       
                 source.destroy();
             }
         }
+        if (this.components !== null && this.components.mode === 'label') { this._derive(found => found.label()); }   // (value, rank)
     } catch (e) {                                                                      // the context keeps the volume it had
         this.volume.destroy();
         this.volume = old;
@@ -125,6 +136,34 @@ async setVolume(reader) {                                                       
     }
     if (this.renderer) { this.renderer.setVolume(this.volume); }
     if (old) { old.destroy(); }                                                        // device memory is not garbage-collected
+}
+
+// replaces this.volume (if it is R8 / R16: any other volume stays as it is) by what emit(components of the `components` option) returns
+_derive(emit) {
+    const N = native(), fmt = this.volume.nativeFormat(), spec = this.components;
+    if (fmt !== N.VPT_FORMAT_R8 && fmt !== N.VPT_FORMAT_R16) { return; }
+    const source = this.volume, largest = fmt === N.VPT_FORMAT_R16 ? 65535 : 255;      // the range is open above: hi may exceed an R8 volume's codes
+    const found = source.components(spec.lo, Math.min(spec.hi, largest), spec.connectivity, spec.minVoxels);
+    try { this.volume = emit(found); } finally { found.destroy(); }
+    source.destroy();
+}
+
+// the `components` option with its defaults filled in, or null; throws for anything the contract does not take
+static _componentsSpec(spec) {
+    if (spec === undefined || spec === null) { return null; }
+    const known = ['lo', 'hi', 'connectivity', 'minVoxels', 'mode', 'keep'];
+    if (typeof spec !== 'object' || Array.isArray(spec) || !Object.keys(spec).every(k => known.includes(k)) || (spec.mode !== 'keep' && spec.mode !== 'label')) {
+        throw new Error("components is null or { lo, hi, connectivity, minVoxels, mode: 'keep' | 'label', keep }, not " + JSON.stringify(spec));
+    }
+    checkRange(spec.lo, spec.hi, 65535);
+    const out = { lo: spec.lo, hi: spec.hi, mode: spec.mode, keep: null,
+        connectivity: checkConnectivity(spec.connectivity !== undefined && spec.connectivity !== null ? spec.connectivity : 6),
+        minVoxels: checkMinVoxels(spec.minVoxels !== undefined && spec.minVoxels !== null ? spec.minVoxels : 1) };
+    if (spec.keep !== undefined && spec.keep !== null) {
+        if (spec.mode === 'label') { throw new Error("components 'keep' goes with mode 'keep'"); }
+        out.keep = checkKeep(1, spec.keep, 0, 65535)[1];
+    }
+    return out;
 }
 
 // { kind: 'values', lo, hi } | { kind: 'range' } | { kind: 'percentiles', a, b } of a `window` option; throws for anything else

@@ -4,6 +4,7 @@ const { EventTarget, CustomEvent } = require('./EventTarget.js');
 const { native } = require('./native.js');
 
 const R = require('./readers/readers.js');
+const { checkConnectivity, checkRange, checkMinVoxels, checkKeep } = require('./components.js');
 const { RAWReader, GL_RED, GL_RG, GL_RGB, GL_RGBA, GL_UNSIGNED_BYTE, GL_FLOAT, GL_HALF_FLOAT, GL_BYTE } = R;
 
 // [type, format, internalFormat, native format name, channels in the file, element kind] of the formats keyed on all three: SNORM bytes
@@ -339,6 +340,93 @@ dilate(passes) { return this.rank('dilate', passes); }
 open(passes) { return this.rank('open', passes); }
 close(passes) { return this.rank('close', passes); }
 
+// ---- extension: connected components of a value range (include/vpt.h; DESIGN.md "Connected components") ----
+// the connected components of the codes lo .. hi of this (R8 / R16) volume as a Components object, labelled on the device: connectivity 6
+// (default), 18 or 26; minVoxels (default 1): smaller components are dropped.  The object owns what it needs; this volume is not changed
+components(lo, hi, connectivity, minVoxels) {
+    const N = native(), norm16 = this.nativeFormat() === N.VPT_FORMAT_R16;
+    checkRange(lo, hi, norm16 ? 65535 : 255);
+    connectivity = checkConnectivity(connectivity !== undefined ? connectivity : 6);
+    minVoxels = checkMinVoxels(minVoxels !== undefined ? minVoxels : 1);
+    return new Components(this, N.volumeComponents(this.texture, lo, hi, connectivity, minVoxels));
+}
+// only the n (default 1) largest components of the codes lo .. hi keep their codes; 0 elsewhere
+keepLargest(lo, hi, n, connectivity) {
+    const c = this.components(lo, hi, connectivity);
+    try { return c.keep(1, n !== undefined ? n : 1); } finally { c.destroy(); }
+}
+// the components of the codes lo .. hi with at least minVoxels voxels keep their codes; 0 elsewhere
+removeIslands(lo, hi, minVoxels, connectivity) {
+    const c = this.components(lo, hi, connectivity, minVoxels);
+    try { return c.keep(1, null); } finally { c.destroy(); }
+}
+
+}
+
+// The connected components of a value range of a volume (Volume.components): per-voxel ranks and the component list on the device.  Label
+// once, select several times.  Outlives the volume it was made from; destroy() frees the device memory.
+class Components {
+
+constructor(source, handle) {
+    const N = native();
+    this._h = handle;
+    this._norm16 = source.nativeFormat() === N.VPT_FORMAT_R16;
+    this._dimensions = Object.assign({}, source.modality.dimensions);
+    this._like = new Volume(source._gl);                       // what a derived volume's description is made from (Volume._sameFormat)
+    this._like.modality = Object.assign({}, source.modality);
+    this._like.metadata = { meta: Object.assign({}, (source.metadata || {}).meta) };
+}
+
+_handle() {
+    if (!this._h) { throw new Error('the components have been destroyed'); }
+    return this._h;
+}
+
+destroy() {
+    if (this._h) { native().componentsDestroy(this._h); this._h = null; }
+}
+
+// { listed, dropped, foregroundVoxels, listedVoxels }
+get info() {
+    const i = native().componentsInfo(this._handle());
+    return { listed: i[0], dropped: i[1], foregroundVoxels: i[2], listedVoxels: i[3] };
+}
+
+// [[rootX, rootY, rootZ, voxels], ...] of the components first .. first + n - 1 of the canonical order (defaults: all)
+list(first, n) {
+    first = first !== undefined ? first : 0;
+    if (n === undefined || n === null) { n = Math.max(this.info.listed - first, 0); }
+    const words = new Uint32Array(4 * n), out = [];
+    native().componentsList(this._handle(), first, words);
+    for (let k = 0; k < n; k++) { out.push([words[4 * k], words[4 * k + 1], words[4 * k + 2], words[4 * k + 3]]); }
+    return out;
+}
+
+// Uint32Array [depth][height][width]: the ranks of a box of voxels (default: the whole volume)
+ranks(x, y, z, width, height, depth) {
+    const d = this._dimensions;
+    x = x || 0; y = y || 0; z = z || 0;
+    width = width !== undefined ? width : d.width - x; height = height !== undefined ? height : d.height - y; depth = depth !== undefined ? depth : d.depth - z;
+    const out = new Uint32Array(width * height * depth);
+    native().componentsRanks(this._handle(), x, y, z, width, height, depth, out);
+    return out;
+}
+
+// a new, ready volume of the source's size, format and filter: the source's code where first <= rank <= last (defaults 1 and every rank),
+// `fill` (default 0) elsewhere
+keep(first, last, fill) {
+    const k = checkKeep(first !== undefined ? first : 1, last, fill !== undefined ? fill : 0, this._norm16 ? 65535 : 255);
+    return this._like._sameFormat(native().componentsKeep(this._handle(), k[0], k[1], k[2]), this._dimensions);
+}
+
+// a new, ready RG8 / RG16 volume with the source's filter: (code, min(rank, M)): the rows of a 2-D transfer function select the structures
+label() {
+    const out = this._like._sameFormat(native().componentsLabel(this._handle()), this._dimensions);
+    Object.assign(out.modality, { format: GL_RG, internalFormat: this._norm16 ? R.GL_RG16_EXT : R.GL_RG8,
+        type: this._norm16 ? R.GL_UNSIGNED_SHORT : GL_UNSIGNED_BYTE });
+    return out;
+}
+
 }
 // the number of smoothing passes (an integer in 1 .. 8) / of reductions (an integer >= 1); throws for anything else
 function checkPasses(passes) {
@@ -361,4 +449,4 @@ function checkRankPasses(passes) {
     if (!Number.isInteger(passes) || passes < 1 || passes > 8) { throw new Error('rank-filter passes are an integer in 1 .. 8, not ' + JSON.stringify(passes)); }
     return passes;
 }
-module.exports = { Volume, RAWReader, filterCode, gradientArguments, windowFormatBits, percentileWindow, checkPasses, checkLevels, rankOperatorCode, checkRankPasses };
+module.exports = { Volume, Components, RAWReader, filterCode, gradientArguments, windowFormatBits, percentileWindow, checkPasses, checkLevels, rankOperatorCode, checkRankPasses };

@@ -6,7 +6,7 @@ constructing a Context does, and raises if it is missing (no CPU fallback)."""
 from .property_bag import PropertyBag, EventTarget, Event, CustomEvent
 from .scene import Node, Transform, PerspectiveCamera, mat4, quat, vec3, default_camera, mvp_inverse_matrix
 from .context import Context
-from .volume import Volume
+from .volume import Volume, Components
 from .loaders import AbstractLoader, BlobLoader, FileLoader, LoaderFactory
 from .readers import AbstractReader, RAWReader, ZIPReader, BVPReader, ReaderFactory
 from .renderers import (AbstractRenderer, MIPRenderer, EAMRenderer, MCSRenderer, MCMRenderer, ISORenderer, DepthRenderer, LAORenderer, DOSRenderer,
@@ -22,6 +22,7 @@ from .gradient import gradient_magnitude
 from .window import window_texels, percentile_window
 from .pyramid import reduce_texels, smooth_texels
 from .rank import rank_texels
+from .components import components_texels, keep_texels, label_texels
 from ._native import VptError
 
 __all__ = [
@@ -33,4 +34,5 @@ __all__ = [
     'Uncharted2ToneMapper', 'FilmicToneMapper', 'UnrealToneMapper', 'AcesToneMapper', 'LottesToneMapper',
     'UchimuraToneMapper', 'ToneMapperFactory', 'RenderingContext', 'CircleAnimator', 'OrbitCameraAnimator', 'TransferFunction',
     'HDRImage', 'read_hdr', 'gradient_magnitude', 'window_texels', 'percentile_window', 'reduce_texels', 'smooth_texels', 'rank_texels',
+    'components_texels', 'keep_texels', 'label_texels', 'Components',
 ]

@@ -51,6 +51,8 @@ SYMBOLS = [
     "vpt_volume_derive_gradient", "vpt_volume_read_block", "vpt_volume_histogram",
     "vpt_volume_window", "vpt_volume_range", "vpt_volume_code_histogram",
     "vpt_volume_reduce", "vpt_volume_smooth", "vpt_volume_rank",
+    "vpt_volume_components", "vpt_components_info", "vpt_components_list", "vpt_components_ranks", "vpt_components_keep",
+    "vpt_components_label", "vpt_components_profile", "vpt_components_destroy",
     "vpt_renderer_create", "vpt_renderer_set_shard", "vpt_renderer_local_rows", "vpt_renderer_global_row",
     "vpt_renderer_destroy", "vpt_renderer_set_volume", "vpt_renderer_set_transfer_function",
     "vpt_renderer_set_environment", "vpt_renderer_set_environment_texels", "vpt_renderer_resize",
@@ -89,6 +91,19 @@ class LaoParams(C.Structure):
                 ("lao_step_size", C.c_float), ("soft_shadows", C.c_int32), ("shadows_weight", C.c_float),
                 ("num_shadow_samples", C.c_int32), ("light_radius", C.c_float), ("light_coefficient", C.c_float),
                 ("light_position", C.c_float * 3)]
+
+
+class Component(C.Structure):
+    """struct vpt_component (include/vpt.h)"""
+    _fields_ = [("root_x", C.c_uint32), ("root_y", C.c_uint32), ("root_z", C.c_uint32), ("voxels", C.c_uint32)]
+
+
+class ComponentsInfo(C.Structure):
+    """struct vpt_components_info (include/vpt.h)"""
+    _fields_ = [("listed", C.c_uint64), ("dropped", C.c_uint64), ("foreground_voxels", C.c_uint64), ("listed_voxels", C.c_uint64)]
+
+
+COMPONENTS_PHASES = 7
 
 
 class TonemapParams(C.Structure):
@@ -158,6 +173,10 @@ def lib():
         "vpt_volume_window": [P, C.c_double, C.c_double, I, PP], "vpt_volume_range": [P, C.POINTER(C.c_double), C.POINTER(C.c_double)],
         "vpt_volume_code_histogram": [P, C.POINTER(C.c_uint32), SZ],
         "vpt_volume_reduce": [P, PP], "vpt_volume_smooth": [P, I, PP], "vpt_volume_rank": [P, I, I, PP],
+        "vpt_volume_components": [P, C.c_uint32, C.c_uint32, I, C.c_uint32, PP], "vpt_components_info": [P, C.POINTER(ComponentsInfo)],
+        "vpt_components_list": [P, C.c_uint64, C.c_uint64, C.POINTER(Component)], "vpt_components_ranks": [P, I, I, I, I, I, I, P, SZ],
+        "vpt_components_keep": [P, C.c_uint64, C.c_uint64, C.c_uint32, PP], "vpt_components_label": [P, PP],
+        "vpt_components_profile": [P, C.POINTER(C.c_double), C.POINTER(C.c_uint32)], "vpt_components_destroy": [P],
         "vpt_renderer_create": [P, I, I, I, PP],
         "vpt_renderer_set_shard": [P, I, I, I], "vpt_renderer_local_rows": [P, C.POINTER(I)],
         "vpt_renderer_global_row": [P, I, C.POINTER(I)],

@@ -49,6 +49,13 @@ class RenderingContext(EventTarget):
         if self.rank is not None:
             rank_operator_code(self.rank)                                              # a bad option fails here, not at the first volume
         check_rank_passes(self.rankPasses)
+        # (extension) None | {'lo', 'hi', 'connectivity': 6, 'minVoxels': 1, 'mode': 'keep', 'keep': n | None} | {..., 'mode': 'label'}: the
+        # connected components of the codes lo .. hi of an R8 / R16 volume.  'keep' runs behind the rank filter and in front of the smoothing:
+        # the n largest components (None: all of at least minVoxels voxels) keep their codes, everything else becomes 0.  'label' runs where
+        # the gradient runs, on the final scalar volume: the second channel is min(rank, M), so it cannot be combined with `gradient`
+        self.components = self._components_spec(options.get('components'))
+        if self.components is not None and self.components['mode'] == 'label' and self.gradient is not None:
+            raise ValueError("components mode 'label' and gradient both write the second channel: name one of them")
         self.gl = Context(options.get('device', 0))                                   # initGL(), :61-105
         self.environmentTexture = np.array([[[255, 255, 255, 255]]], dtype=np.uint8)   # :90-101
         self._rng = options.get('rng')
@@ -97,6 +104,8 @@ class RenderingContext(EventTarget):
                 source = self.volume
                 self.volume = source.rank(self.rank, self.rankPasses)
                 source.destroy()
+            if self.components is not None and self.components['mode'] == 'keep' and self._one_channel_unorm(self.volume):
+                self._derive(lambda source, found: found.keep(1, self.components['keep']))
             if self.smooth is not None and self._one_channel_unorm(self.volume):
                 source = self.volume
                 self.volume = source.smooth(self.smooth)
@@ -109,6 +118,8 @@ class RenderingContext(EventTarget):
                 source = self.volume
                 self.volume = source.derive_gradient(self.gradient, self.gradientGain)    # (value, gradient magnitude): the 2-D transfer function's axes
                 source.destroy()
+            if self.components is not None and self.components['mode'] == 'label' and self._one_channel_unorm(self.volume):
+                self._derive(lambda source, found: found.label())                     # (value, rank): a row of the 2-D transfer function per structure
         except Exception:                                                             # the context keeps the volume it had
             self.volume.destroy()
             self.volume = old
@@ -117,6 +128,40 @@ class RenderingContext(EventTarget):
             self.renderer.setVolume(self.volume)
         if old:
             old.destroy()                                                             # device memory is not garbage-collected
+
+    def _derive(self, emit):
+        """replaces self.volume by what ``emit(source, components of the `components` option)`` returns"""
+        spec = self.components
+        source = self.volume
+        from . import _native as N
+        largest = 65535 if source.native_format()[0] == N.FORMAT_R16 else 255        # the range is open above: hi may exceed an R8 volume's codes
+        found = source.components(spec['lo'], min(spec['hi'], largest), spec['connectivity'], spec['minVoxels'])
+        try:
+            self.volume = emit(source, found)
+        finally:
+            found.destroy()
+        source.destroy()
+
+    @staticmethod
+    def _components_spec(spec):
+        """the `components` option with its defaults filled in, or None; raises ValueError for anything the contract does not take"""
+        if spec is None:
+            return None
+        from .components import check_connectivity, check_min_voxels, check_range, check_keep
+        known = {'lo', 'hi', 'connectivity', 'minVoxels', 'mode', 'keep'}
+        if not isinstance(spec, dict) or not {'lo', 'hi', 'mode'} <= set(spec) or not set(spec) <= known:
+            raise ValueError("components is None or {'lo', 'hi', 'connectivity', 'minVoxels', 'mode': 'keep' | 'label', 'keep'}, not %r" % (spec,))
+        if spec['mode'] not in ('keep', 'label'):
+            raise ValueError("components mode is 'keep' or 'label', not %r" % (spec['mode'],))
+        lo, hi = check_range(spec['lo'], spec['hi'], 65535)
+        out = {'lo': lo, 'hi': hi, 'mode': spec['mode'],
+               'connectivity': check_connectivity(spec['connectivity'] if spec.get('connectivity') is not None else 6),
+               'minVoxels': check_min_voxels(spec['minVoxels'] if spec.get('minVoxels') is not None else 1), 'keep': None}
+        if spec.get('keep') is not None:
+            if spec['mode'] == 'label':
+                raise ValueError("components 'keep' goes with mode 'keep'")
+            out['keep'] = check_keep(1, spec['keep'], 0, 65535)[1]
+        return out
 
     @staticmethod
     def _window_spec(window):

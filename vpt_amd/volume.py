@@ -414,6 +414,34 @@ class Volume(EventTarget):
     def close(self, passes=1):
         return self.rank('close', passes)
 
+    # ---- extension: connected components of a value range (include/vpt.h; DESIGN.md "Connected components") ----
+    def components(self, lo, hi, connectivity=6, min_voxels=1):
+        """The connected components of the codes lo .. hi of this (R8 / R16) volume as a ``Components`` object, labelled on the device
+        (vpt_amd.components_texels states the contract).  The object owns what it needs: this volume is not changed and may be destroyed."""
+        from .components import check_connectivity, check_min_voxels, check_range
+        norm16 = self.native_format()[0] in (N.FORMAT_R16, N.FORMAT_RG16, N.FORMAT_R16_SNORM, N.FORMAT_RG16_SNORM)
+        lo, hi = check_range(lo, hi, 65535 if norm16 else 255)
+        h = C.c_void_p()
+        N.check(N.lib().vpt_volume_components(self.texture, lo, hi, check_connectivity(connectivity), check_min_voxels(min_voxels), C.byref(h)))
+        return Components(self, h)
+
+    def keep_largest(self, lo, hi, n=1, connectivity=6):
+        """A new, ready volume like this one in which only the ``n`` largest components of the codes lo .. hi keep their codes; 0 elsewhere"""
+        c = self.components(lo, hi, connectivity)
+        try:
+            return c.keep(1, n)
+        finally:
+            c.destroy()
+
+    def remove_islands(self, lo, hi, min_voxels, connectivity=6):
+        """A new, ready volume like this one in which the components of the codes lo .. hi with at least ``min_voxels`` voxels keep their
+        codes; 0 elsewhere"""
+        c = self.components(lo, hi, connectivity, min_voxels)
+        try:
+            return c.keep(1, None)
+        finally:
+            c.destroy()
+
     def set_wide_tables(self, wide):
         """force the > 4 GiB addressing variant of the kernels (automatic above 4 GiB of bricked data)"""
         N.check(N.lib().vpt_volume_set_wide_tables(self.texture, 1 if wide else 0))
@@ -422,3 +450,80 @@ class Volume(EventTarget):
         n = C.c_uint64(0)
         N.check(N.lib().vpt_volume_bricked_bytes(self.texture, C.byref(n)))
         return n.value
+
+
+class Components:
+    """The connected components of a value range of a volume (``Volume.components``): per-voxel ranks and the component list on the device.
+    Label once, select several times.  Outlives the volume it was made from; ``destroy()`` frees the device memory."""
+
+    def __init__(self, source, handle):
+        self._h = handle
+        self._gl = source._gl
+        dims = source.modality['dimensions']
+        self._shape = (dims['depth'], dims['height'], dims['width'])
+        self._norm16 = source.modality.get('internalFormat') == GL_R16_EXT
+        # what a derived volume's description is made from (Volume._same_format)
+        self._like = Volume(source._gl)
+        self._like.modality = dict(source.modality)
+        self._like.metadata = {'meta': dict((source.metadata or {}).get('meta', {}))}
+
+    def _handle(self):
+        if not self._h:
+            raise RuntimeError('the components have been destroyed')
+        return self._h
+
+    def destroy(self):
+        if self._h:
+            N.lib().vpt_components_destroy(self._h)
+            self._h = None
+
+    @property
+    def info(self):
+        """{'listed', 'dropped', 'foreground_voxels', 'listed_voxels'}"""
+        i = N.ComponentsInfo()
+        N.check(N.lib().vpt_components_info(self._handle(), C.byref(i)))
+        return {name: int(getattr(i, name)) for name, _ in N.ComponentsInfo._fields_}
+
+    def list(self, first=0, n=None):
+        """[(root_x, root_y, root_z, voxels)] of the components first .. first + n - 1 of the canonical order (n None: to the end)"""
+        if n is None:
+            n = max(self.info['listed'] - int(first), 0)
+        buf = (N.Component * max(int(n), 1))()
+        N.check(N.lib().vpt_components_list(self._handle(), int(first), int(n), buf))
+        return [(c.root_x, c.root_y, c.root_z, c.voxels) for c in buf[:int(n)]]
+
+    def ranks(self, x=0, y=0, z=0, w=None, h=None, d=None):
+        """uint32 [d][h][w]: the ranks of a box of voxels (the whole volume by default)"""
+        w = self._shape[2] - x if w is None else w
+        h = self._shape[1] - y if h is None else h
+        d = self._shape[0] - z if d is None else d
+        out = np.empty((int(d), int(h), int(w)), np.uint32)
+        N.check(N.lib().vpt_components_ranks(self._handle(), int(x), int(y), int(z), int(w), int(h), int(d), out.ctypes.data_as(C.c_void_p), out.nbytes))
+        return out
+
+    def keep(self, first=1, last=None, fill=0):
+        """A new, ready volume of the source's size, format and filter: the source's code where first <= rank <= last (last None: every
+        rank), ``fill`` elsewhere (vpt_amd.keep_texels states it)"""
+        from .components import check_keep
+        first, last, fill = check_keep(first, last, fill, 65535 if self._norm16 else 255)
+        h = C.c_void_p()
+        N.check(N.lib().vpt_components_keep(self._handle(), first, last, fill, C.byref(h)))
+        return self._like._same_format(h, self._like.modality['dimensions'])
+
+    def label(self):
+        """A new, ready RG8 / RG16 volume with the source's filter: (code, min(rank, M)) (vpt_amd.label_texels states it): the rows of a 2-D
+        transfer function select the structures"""
+        h = C.c_void_p()
+        N.check(N.lib().vpt_components_label(self._handle(), C.byref(h)))
+        out = self._like._same_format(h, self._like.modality['dimensions'])
+        out.modality.update({'format': GL_RG, 'internalFormat': GL_RG16_EXT if self._norm16 else GL_RG8,
+                             'type': GL_UNSIGNED_SHORT if self._norm16 else GL_UNSIGNED_BYTE})
+        return out
+
+    def profile(self):
+        """(for measurements) ({phase: milliseconds}, merge launches, flatten launches) of the labelling"""
+        ms = (C.c_double * N.COMPONENTS_PHASES)()
+        launches = (C.c_uint32 * 2)()
+        N.check(N.lib().vpt_components_profile(self._handle(), ms, launches))
+        names = ('tiles', 'merge', 'flatten', 'sizes', 'compaction', 'sort', 'ranks')
+        return dict(zip(names, ms)), int(launches[0]), int(launches[1])
