@@ -658,6 +658,13 @@ VPT_API int vpt_probe_assemble_rows(vpt_context *ctx, const void *gathered, int 
 /* measured HBM streaming-read rate: `iterations` grid-stride 16 B/lane reads of an nbytes scratch buffer (choose it far
  * larger than the 256 MB Infinity Cache); the second denominator SURVEY section 8d asks for next to the 8 TB/s peak */
 VPT_API int vpt_probe_stream_read(vpt_context *ctx, size_t nbytes, int iterations, double *gb_per_s);
+/* (for tests) vpt_volume_components with the two step caps given: the loads a unite of the merge and a voxel of the flatten may take in one
+ * launch (vpt_volume_components passes 1024 and 64).  Small caps make the host's retry loops run on small volumes: the second and later
+ * merge launches behind a unite that gave up, and the second and later flatten launches.  The result is the contract's whatever the caps.
+ * Caps for which the loops' bounds do not hold, merge_steps < 3 or flatten_steps < 1, are VPT_ERR_INVALID, the message naming the smallest
+ * value taken; they are checked before every other argument and before any device call. */
+VPT_API int vpt_volume_components_capped(vpt_volume *src, uint32_t lo, uint32_t hi, int connectivity, uint32_t min_voxels, int merge_steps,
+                                         int flatten_steps, vpt_components **out);
 
 #ifdef __cplusplus
 }

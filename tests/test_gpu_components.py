@@ -61,16 +61,23 @@ def differences(got, want, what):
     assert len(bad) == 0, "%d values differ (%s), first at %s: %d, expected %d" % (len(bad), what, bad[0], got[tuple(bad[0])], want[tuple(bad[0])])
 
 
-def check(ctx, a, lo, hi, connectivity, min_voxels=1, what=''):
-    """labels `a` on the device and holds everything the handle gives to the numpy statement; returns (ranks, list) of the statement"""
-    what = "%s %s %s [%d, %d] c%d m%d" % (what, a.dtype.name, a.shape[::-1], lo, hi, connectivity, min_voxels)
+def statement(a, lo, hi, connectivity, min_voxels=1):
+    """(ranks, list, the number of components of any size) of the numpy statement"""
     ranks, listed = vpt_amd.components_texels(a, lo, hi, connectivity, min_voxels)
-    everything = listed if min_voxels == 1 else vpt_amd.components_texels(a, lo, hi, connectivity)[1]
+    return ranks, listed, len(listed if min_voxels == 1 else vpt_amd.components_texels(a, lo, hi, connectivity)[1])
+
+
+def check(ctx, a, lo, hi, connectivity, min_voxels=1, what='', caps=None, want=None):
+    """labels `a` on the device and holds everything the handle gives to the numpy statement; returns (ranks, list) of the statement.
+    caps: (merge_steps, flatten_steps) of vpt_volume_components_capped; want: statement(a, lo, hi, connectivity, min_voxels), where several
+    calls share it"""
+    what = "%s %s %s [%d, %d] c%d m%d%s" % (what, a.dtype.name, a.shape[::-1], lo, hi, connectivity, min_voxels, '' if caps is None else ' caps %r' % (caps,))
+    ranks, listed, everything = statement(a, lo, hi, connectivity, min_voxels) if want is None else want
     src = upload(ctx, a)
-    found = src.components(lo, hi, connectivity, min_voxels)
+    found = src.components(lo, hi, connectivity, min_voxels, _caps=caps)
     differences(found.ranks(), ranks, what + ': ranks')
     assert found.list() == listed, what + ': list'
-    assert found.info == {'listed': len(listed), 'dropped': len(everything) - len(listed), 'foreground_voxels': int(((a >= lo) & (a <= hi)).sum()),
+    assert found.info == {'listed': len(listed), 'dropped': everything - len(listed), 'foreground_voxels': int(((a >= lo) & (a <= hi)).sum()),
                           'listed_voxels': sum(c[3] for c in listed)}, what + ': info'
     kept, pair = found.keep(), found.label()
     differences(whole(kept), vpt_amd.keep_texels(a, ranks), what + ': keep')

@@ -65,7 +65,7 @@ SYMBOLS = [
     "vpt_gather_synchronize",
     "vpt_gather_read_frame",
     "vpt_probe_math", "vpt_probe_sample", "vpt_probe_sample_boundary", "vpt_probe_stream_read", "vpt_probe_assemble_rows",
-    "vpt_probe_environment_texels",
+    "vpt_probe_environment_texels", "vpt_volume_components_capped",
     "vpt_tonemapper_create", "vpt_tonemapper_destroy", "vpt_tonemapper_resize", "vpt_tonemapper_set_source",
     "vpt_tonemapper_set_source_image", "vpt_tonemapper_render", "vpt_tonemapper_read", "vpt_tonemapper_rows",
     "vpt_tonemapper_output_device", "vpt_tonemapper_set_option", "vpt_transfer_function_rasterize",
@@ -201,6 +201,7 @@ def lib():
         "vpt_renderer_profile_side": [P, C.POINTER(C.c_double), C.POINTER(C.c_uint32)],
         "vpt_probe_math": [P, I, P, P, SZ], "vpt_probe_sample": [P, P, P, SZ], "vpt_probe_sample_boundary": [P, P, P, SZ], "vpt_probe_stream_read": [P, SZ, I, P], "vpt_probe_assemble_rows": [P, P, I, I, I, I, I, P],
         "vpt_probe_environment_texels": [P, P, SZ],
+        "vpt_volume_components_capped": [P, C.c_uint32, C.c_uint32, I, C.c_uint32, I, I, PP],
         "vpt_tonemapper_create": [P, I, I, I, P], "vpt_tonemapper_destroy": [P], "vpt_tonemapper_resize": [P, I, I],
         "vpt_tonemapper_set_source": [P, P], "vpt_tonemapper_set_source_image": [P, P, I, I],
         "vpt_tonemapper_render": [P, C.POINTER(TonemapParams)], "vpt_tonemapper_read": [P, P, SZ],

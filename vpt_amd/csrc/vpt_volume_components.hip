@@ -181,7 +181,7 @@ __global__ __launch_bounds__(256) void k_merge(uint32_t *__restrict__ L, int nx,
     }
 }
 // Every voxel takes the ancestor it reaches within `cap` loads.  Links written meanwhile by other threads name ancestors too, so a voxel at
-// depth d ends at depth <= ceil(d / (cap - 1)); one that could not confirm a root raises W_CHANGED.
+// depth d ends at depth <= ceil(d / (cap + 1)) (flatten_launches has the argument); one that could not confirm a root raises W_CHANGED.
 __global__ __launch_bounds__(256) void k_flatten(uint32_t *__restrict__ L, size_t n, int cap, uint32_t *__restrict__ words) {
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
         const uint32_t own = ld_agent(&L[i]);
@@ -346,13 +346,29 @@ struct vpt_components {
     size_t voxels() const { return (size_t)nx * (size_t)ny * (size_t)nz; }
 };
 
-// chase steps a unite / a voxel's flatten may take in one launch
+// chase steps a unite / a voxel's flatten may take in one launch: what vpt_volume_components passes
 #define CC_MERGE_STEPS 1024
 #define CC_FLATTEN_STEPS 64
-// Flatten launches behind one merge launch.  The forest is at most 2^32 deep (a link points to a smaller 32-bit index) and a launch takes a
-// depth d to at most ceil(d / (CC_FLATTEN_STEPS - 1)) (k_flatten), so after five launches the depth is at most ceil(2^32 / 63^5) = 5 and the
-// sixth confirms every root within its steps and raises nothing.  One more than that is an error.
-#define CC_FLATTEN_LAUNCHES 7
+// The smallest caps for which the bounds of the host's loops (components_build) hold; vpt_volume_components_capped refuses smaller ones.
+// Merge: on a flat forest a unite of two voxels that are not roots takes one step to the first root, confirms it, takes its second step to
+// the other root and must still be below the cap to confirm that one: with fewer than 3 steps a launch without a hook could give up, and
+// the argument that every launch which raises the word has hooked a root would not hold.
+// Flatten: with one step a voxel ends at its grandparent or confirms its parent as the root, so depths at least halve and a flat forest
+// raises nothing (flatten_launches below).
+#define CC_MERGE_STEPS_MIN 3
+#define CC_FLATTEN_STEPS_MIN 1
+// Flatten launches the host makes at most behind one merge launch when a voxel may take `cap` steps; needing one more is an error.  A voxel at depth d starts at its
+// parent (depth d - 1), and every load that does not confirm a root moves it at least one level up the forest as it was when the launch
+// began (links written meanwhile by other threads name ancestors too).  So it confirms the root within d <= cap loads, and otherwise ends
+// on a voxel that was at depth <= d - 1 - cap: by induction over the depth, a launch takes a depth d to at most ceil(d / (cap + 1)).  The
+// forest is at most 2^32 deep (a link points to a smaller 32-bit index).  With j the first number of launches behind which
+// ceil(2^32 / (cap + 1)^j) <= cap, launch j + 1 confirms every root within its steps and raises nothing; the limit is one more than
+// that, j + 2.  64 steps: ceil(2^32 / 65^4) = 241, ceil(2^32 / 65^5) = 4, so j = 5 and the limit is 7; 1 step: j = 32, the limit is 34.
+static int flatten_launches(int cap) {
+    int j = 0;
+    for (uint64_t p = 1; ((1ull << 32) + p - 1) / p > (uint64_t)cap; p *= (uint64_t)cap + 1u) j++;      // p < 2^32 (cap + 1) < 2^64
+    return j + 2;
+}
 
 // grid of a grid-stride kernel over `items`
 static unsigned stream_grid(size_t items) { return (unsigned)std::max<size_t>(1, std::min<size_t>((items + 255) / 256, 8192)); }
@@ -378,17 +394,17 @@ static void launch_label_tiles(const vpt_components *c, int conn, uint32_t lo, u
     else if (conn == 18) hipLaunchKernelGGL((k_label_tiles<T, 18>), grid, dim3(256), 0, st, s, c->ranks.get(), c->nx, c->ny, c->nz, lo, hi, words);
     else hipLaunchKernelGGL((k_label_tiles<T, 26>), grid, dim3(256), 0, st, s, c->ranks.get(), c->nx, c->ny, c->nz, lo, hi, words);
 }
-static void launch_merge(const vpt_components *c, int conn, uint32_t *words) {
+static void launch_merge(const vpt_components *c, int conn, int cap, uint32_t *words) {
     const size_t n = c->voxels();
     const dim3 grid(stream_grid(n));
     hipStream_t st = c->ctx->stream;
-    if (conn == 6) hipLaunchKernelGGL(k_merge<6>, grid, dim3(256), 0, st, c->ranks.get(), c->nx, c->ny, c->nz, n, CC_MERGE_STEPS, words);
-    else if (conn == 18) hipLaunchKernelGGL(k_merge<18>, grid, dim3(256), 0, st, c->ranks.get(), c->nx, c->ny, c->nz, n, CC_MERGE_STEPS, words);
-    else hipLaunchKernelGGL(k_merge<26>, grid, dim3(256), 0, st, c->ranks.get(), c->nx, c->ny, c->nz, n, CC_MERGE_STEPS, words);
+    if (conn == 6) hipLaunchKernelGGL(k_merge<6>, grid, dim3(256), 0, st, c->ranks.get(), c->nx, c->ny, c->nz, n, cap, words);
+    else if (conn == 18) hipLaunchKernelGGL(k_merge<18>, grid, dim3(256), 0, st, c->ranks.get(), c->nx, c->ny, c->nz, n, cap, words);
+    else hipLaunchKernelGGL(k_merge<26>, grid, dim3(256), 0, st, c->ranks.get(), c->nx, c->ny, c->nz, n, cap, words);
 }
 
 // the body of vpt_volume_components behind the argument checks; `c` is freed by the caller on failure
-static int components_build(vpt_components *c, int conn, uint32_t lo, uint32_t hi, uint32_t min_voxels) {
+static int components_build(vpt_components *c, int conn, uint32_t lo, uint32_t hi, uint32_t min_voxels, int merge_steps, int flatten_steps) {
     const size_t n = c->voxels();
     hipStream_t st = c->ctx->stream;
     DevBuf<uint32_t> words, count;
@@ -414,22 +430,23 @@ static int components_build(vpt_components *c, int conn, uint32_t lo, uint32_t h
     // every atomicMin meets a root, so no unite can give up: a merge launch that raises W_CHANGED has hooked at least one root under a
     // smaller one, for good (a root never becomes one again).  There are `tile_roots` roots when the loop begins (k_label_tiles counts
     // them), so at most tile_roots launches raise the word and launch tile_roots + 1 leaves it 0.  In practice the count is one launch per
-    // CC_MERGE_STEPS of chain that the tile components of one structure form (DESIGN.md has the measured counts).
+    // merge_steps of chain that the tile components of one structure form (DESIGN.md has the measured counts).
+    const int flatten_bound = flatten_launches(flatten_steps);
     const uint64_t merge_bound = (uint64_t)host_words[W_TILE_ROOTS] + 1u;
     const bool one_tile = c->nx <= CC_TX && c->ny <= CC_TY && c->nz <= CC_TZ;
     for (uint64_t round = 0; !one_tile; round++) {
         if (round == merge_bound) return fail(VPT_ERR_HIP, "connected components: the merge did not settle within %llu launches", (unsigned long long)merge_bound);
         HIP_TRY(hipMemsetAsync(words + W_CHANGED, 0, sizeof(uint32_t), st));
-        launch_merge(c, conn, words);
+        launch_merge(c, conn, merge_steps, words);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(host_words, words, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         HIP_TRY(clock.lap(&c->ms[1]));
         c->launches[0]++;
         const bool merge_gave_up = host_words[W_CHANGED] != 0u;
         for (int f = 0; ; f++) {
-            if (f == CC_FLATTEN_LAUNCHES) return fail(VPT_ERR_HIP, "connected components: the labels were not flat after %d launches", CC_FLATTEN_LAUNCHES);
+            if (f == flatten_bound) return fail(VPT_ERR_HIP, "connected components: the labels were not flat after %d launches", flatten_bound);
             HIP_TRY(hipMemsetAsync(words + W_CHANGED, 0, sizeof(uint32_t), st));
-            hipLaunchKernelGGL(k_flatten, dim3(stream_grid(n)), dim3(256), 0, st, c->ranks.get(), n, CC_FLATTEN_STEPS, words.get());
+            hipLaunchKernelGGL(k_flatten, dim3(stream_grid(n)), dim3(256), 0, st, c->ranks.get(), n, flatten_steps, words.get());
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipMemcpyAsync(host_words, words, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
             HIP_TRY(clock.lap(&c->ms[2]));
@@ -480,7 +497,9 @@ static int components_build(vpt_components *c, int conn, uint32_t lo, uint32_t h
     return VPT_OK;
 }
 
-extern "C" int vpt_volume_components(vpt_volume *src, uint32_t lo, uint32_t hi, int connectivity, uint32_t min_voxels, vpt_components **out) {
+// vpt_volume_components and vpt_volume_components_capped behind the check of the caps
+static int components_create(vpt_volume *src, uint32_t lo, uint32_t hi, int connectivity, uint32_t min_voxels, int merge_steps, int flatten_steps,
+                             vpt_components **out) {
     if (!src || !out) return fail(VPT_ERR_INVALID, "null argument");
     if (src->format != VPT_FORMAT_R8 && src->format != VPT_FORMAT_R16)
         return fail(VPT_ERR_UNSUPPORTED, "connected components are taken of one-channel unsigned normalised volumes (R8, R16; the window makes one of any scalar volume), not of %s",
@@ -501,10 +520,24 @@ extern "C" int vpt_volume_components(vpt_volume *src, uint32_t lo, uint32_t hi, 
     HIP_TRY(c->texels.alloc(bytes));
     HIP_TRY(c->ranks.alloc((size_t)n));
     HIP_TRY(hipMemcpyAsync(c->texels, src->linear, bytes, hipMemcpyDeviceToDevice, ctx->stream));     // behind any upload into src
-    const int rc = components_build(c.get(), connectivity, lo, hi, min_voxels);
+    const int rc = components_build(c.get(), connectivity, lo, hi, min_voxels, merge_steps, flatten_steps);
     if (rc != VPT_OK) { (void)hipStreamSynchronize(ctx->stream); return rc; }      // the buffers are freed on return: nothing may still use them
     *out = c.release();
     return VPT_OK;
+}
+
+extern "C" int vpt_volume_components(vpt_volume *src, uint32_t lo, uint32_t hi, int connectivity, uint32_t min_voxels, vpt_components **out) {
+    return components_create(src, lo, hi, connectivity, min_voxels, CC_MERGE_STEPS, CC_FLATTEN_STEPS, out);
+}
+
+// (for tests) the caps are checked first: a refused cap touches neither the other arguments nor the device
+extern "C" int vpt_volume_components_capped(vpt_volume *src, uint32_t lo, uint32_t hi, int connectivity, uint32_t min_voxels, int merge_steps,
+                                            int flatten_steps, vpt_components **out) {
+    if (merge_steps < CC_MERGE_STEPS_MIN)
+        return fail(VPT_ERR_INVALID, "merge_steps %d: at least %d are needed for the merge loop's bound to hold", merge_steps, CC_MERGE_STEPS_MIN);
+    if (flatten_steps < CC_FLATTEN_STEPS_MIN)
+        return fail(VPT_ERR_INVALID, "flatten_steps %d: at least %d is needed for the flatten loop's bound to hold", flatten_steps, CC_FLATTEN_STEPS_MIN);
+    return components_create(src, lo, hi, connectivity, min_voxels, merge_steps, flatten_steps, out);
 }
 
 extern "C" int vpt_components_info(vpt_components *c, struct vpt_components_info *info) {

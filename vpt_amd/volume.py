@@ -415,14 +415,20 @@ class Volume(EventTarget):
         return self.rank('close', passes)
 
     # ---- extension: connected components of a value range (include/vpt.h; DESIGN.md "Connected components") ----
-    def components(self, lo, hi, connectivity=6, min_voxels=1):
+    def components(self, lo, hi, connectivity=6, min_voxels=1, _caps=None):
         """The connected components of the codes lo .. hi of this (R8 / R16) volume as a ``Components`` object, labelled on the device
-        (vpt_amd.components_texels states the contract).  The object owns what it needs: this volume is not changed and may be destroyed."""
+        (vpt_amd.components_texels states the contract).  The object owns what it needs: this volume is not changed and may be destroyed.
+        ``_caps`` (for tests): (merge_steps, flatten_steps) of vpt_volume_components_capped."""
         from .components import check_connectivity, check_min_voxels, check_range
         norm16 = self.native_format()[0] in (N.FORMAT_R16, N.FORMAT_RG16, N.FORMAT_R16_SNORM, N.FORMAT_RG16_SNORM)
         lo, hi = check_range(lo, hi, 65535 if norm16 else 255)
+        connectivity, min_voxels = check_connectivity(connectivity), check_min_voxels(min_voxels)
         h = C.c_void_p()
-        N.check(N.lib().vpt_volume_components(self.texture, lo, hi, check_connectivity(connectivity), check_min_voxels(min_voxels), C.byref(h)))
+        if _caps is None:
+            N.check(N.lib().vpt_volume_components(self.texture, lo, hi, connectivity, min_voxels, C.byref(h)))
+        else:
+            merge_steps, flatten_steps = _caps
+            N.check(N.lib().vpt_volume_components_capped(self.texture, lo, hi, connectivity, min_voxels, int(merge_steps), int(flatten_steps), C.byref(h)))
         return Components(self, h)
 
     def keep_largest(self, lo, hi, n=1, connectivity=6):
