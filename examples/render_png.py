@@ -15,6 +15,10 @@
     python examples/render_png.py --window auto --rank open --components 96,255 --components-min 64 ...   (island removal on the device: only
                                      connected structures of at least 64 voxels in the codes 96 .. 255 keep their texels; --components-keep 1: the
                                      largest only; --components-label: a row of the 2-D transfer function per structure)
+    python examples/render_png.py --window auto --components 96,255 --components-keep 1 --distance 96,255 --distance-within 0,25 ...   (a margin on
+                                     the device: the texels within 5 voxels of the largest structure; --distance-seeds rest --distance-within 10,
+                                     peels 3 voxels off it (squared distances); --distance-channel 8: the second axis of the 2-D transfer
+                                     function is the distance from the structure, 8 rows a voxel)
     python examples/render_png.py --renderer mcm --env sky.hdr --tonemapper aces ...   (a Radiance .hdr environment map lights MCS / MCM)
 
 Without --volume a synthetic 128^3 sphere with lattice noise is used.  PNG encoding is plain zlib (no imaging library)."""
@@ -59,6 +63,14 @@ def main():
     mode = ap.add_mutually_exclusive_group()
     mode.add_argument("--components-keep", type=int, default=None, metavar="N", help="only the N largest components keep their texels (default: all that are not dropped)")
     mode.add_argument("--components-label", action="store_true", help="the second channel is the component's rank (1 = the largest) instead of a gradient")
+    ap.add_argument("--distance", default=None, metavar="LO,HI", help="exact squared Euclidean distance d2 of every voxel to the codes LO .. HI on the device (R8 / R16 "
+                                                                      "volumes), behind --components: see --distance-within and --distance-channel")
+    ap.add_argument("--distance-seeds", default="range", choices=["range", "rest"], help="range: the distance to the codes LO .. HI; rest: the depth inside them")
+    how = ap.add_mutually_exclusive_group()
+    how.add_argument("--distance-within", default=None, metavar="FROM,TO", help="the texels with FROM <= d2 <= TO keep their codes, everything else becomes 0 "
+                                                                                 "(squared voxels; TO may be left out: no upper end); the default is 0,")
+    how.add_argument("--distance-channel", type=int, default=None, metavar="STEPS", help="the second channel is the distance, STEPS (1 .. 256) rows of the transfer "
+                                                                                       "function a voxel, instead of a gradient")
     ap.add_argument("--smooth", type=int, default=None, metavar="N", help="binomial 3 x 3 x 3 smoothing passes (1 .. 8) on the device, behind the window (R8 / R16 volumes)")
     ap.add_argument("--reduce", type=int, default=None, metavar="N", help="reduce the volume N times to half its resolution on the device, behind the smoothing")
     ap.add_argument("--yaw", type=float, default=0.6)
@@ -76,7 +88,15 @@ def main():
         lo, hi = (int(x) for x in a.components.split(','))
         components = {'lo': lo, 'hi': hi, 'connectivity': a.connectivity, 'minVoxels': a.components_min,
                       'mode': 'label' if a.components_label else 'keep', 'keep': a.components_keep}
-    rc = vpt_amd.RenderingContext({'resolution': (a.width, a.height), 'components': components, 'filter': a.filter, 'rng': GoldenRatioRng(),
+    distance = None
+    if a.distance is not None:
+        lo, hi = (int(x) for x in a.distance.split(','))
+        if a.distance_channel is not None:
+            distance = {'lo': lo, 'hi': hi, 'seeds': a.distance_seeds, 'mode': 'channel', 'steps': a.distance_channel}
+        else:
+            first, _, last = (a.distance_within or '0,').partition(',')
+            distance = {'lo': lo, 'hi': hi, 'seeds': a.distance_seeds, 'mode': 'within', 'from': int(first), 'to': int(last) if last.strip() else None}
+    rc = vpt_amd.RenderingContext({'resolution': (a.width, a.height), 'components': components, 'distance': distance, 'filter': a.filter, 'rng': GoldenRatioRng(),
                                    'gradient': a.gradient, 'gradientGain': a.gradient_gain,
                                    'window': None if window == 'auto' else window, 'windowFormat': a.window_format,
                                    'rank': a.rank, 'rankPasses': a.rank_passes, 'smooth': a.smooth, 'reduce': a.reduce})
@@ -106,7 +126,7 @@ def main():
     rc.chooseRenderer(a.renderer)
     rc.chooseToneMapper(a.tonemapper)
     if a.tf == "colour":
-        rc.renderer.setTransferFunction(colour_tf(256, 64 if a.gradient or a.components_label else 1))
+        rc.renderer.setTransferFunction(colour_tf(256, 64 if a.gradient or a.components_label or a.distance_channel is not None else 1))
     if a.extinction is not None and hasattr(rc.renderer, 'extinction'):
         rc.renderer.extinction = a.extinction
     rc.renderer.reset()

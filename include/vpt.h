@@ -294,6 +294,43 @@ VPT_API int vpt_components_label(vpt_components *c, vpt_volume **out);
 VPT_API int vpt_components_profile(vpt_components *c, double *ms, uint32_t *launches);
 VPT_API int vpt_components_destroy(vpt_components *c);
 
+/* ---- exact Euclidean distance transform of a value range on the device (extension; DESIGN.md "Distance transform") */
+/* The step behind the structure has been isolated: "the tissue within r voxels of it" (a margin), "peel r voxels off it" (erosion by a
+ * Euclidean ball of any radius), "colour by depth inside, or by distance from, it".  Sources: R8 and R16 (the window makes one of any scalar
+ * volume); every other format: VPT_ERR_UNSUPPORTED, naming it.
+ *   In range: a voxel whose code c has lo <= c <= hi, compared as whole unsigned codes.  lo > hi, or hi above the format's largest code M
+ *   (255 / 65535): VPT_ERR_INVALID.
+ *   Seeds: VPT_DISTANCE_TO_RANGE: the voxels in range (the result is the distance TO the structure, 0 on it); VPT_DISTANCE_TO_REST: the
+ *   voxels not in range (the depth INSIDE the structure, 0 outside it); anything else VPT_ERR_INVALID.
+ *   Distance: d2(v) = min over the seeds s of (vx - sx)^2 + (vy - sy)^2 + (vz - sz)^2, in voxel units, isotropic, uint32 (at most
+ *   3 * 4095^2).  Nothing wraps and nothing is clamped: voxels outside the volume are neither seed nor non-seed, so the volume's border is
+ *   NOT background for TO_REST.  Without any seed every d2 is VPT_DISTANCE_NONE.  The result is unique: only distances are given, never
+ *   "which seed", so there is no tie to break.
+ * vpt_amd.distance_squared_texels, within_texels and channel_texels state the contract in numpy.
+ * The handle owns a device copy of the source's texels and one uint32 d2 per voxel: src is not changed and may be destroyed afterwards; a
+ * viewer transforms once and tries several radii.  vpt_volume_distance blocks.  Two runs give identical bytes. */
+#define VPT_DISTANCE_TO_RANGE 0
+#define VPT_DISTANCE_TO_REST  1
+#define VPT_DISTANCE_NONE 0xFFFFFFFFu
+typedef struct vpt_distance vpt_distance;
+struct vpt_distance_info { uint64_t seeds; uint32_t largest; };   /* the seeds; the largest finite d2, 0 when there is no seed */
+VPT_API int vpt_volume_distance(vpt_volume *src, uint32_t lo, uint32_t hi, int seeds, vpt_distance **out);
+VPT_API int vpt_distance_info(vpt_distance *dist, struct vpt_distance_info *info);
+/* d2 of a box of voxels, [d][h][w] uint32; the box and nbytes are checked as vpt_components_ranks checks them.  Blocks. */
+VPT_API int vpt_distance_squared(vpt_distance *dist, int x, int y, int z, int w, int h, int d, uint32_t *host_dst, size_t nbytes);
+/* a new, finalized volume of the source's size, format and filter: the source code where r2_lo <= d2 <= r2_hi, `fill` elsewhere.
+ * r2_lo > r2_hi, or fill above the format's largest code: VPT_ERR_INVALID.  VPT_DISTANCE_NONE is an ordinary value of d2 here: only
+ * r2_hi = 0xFFFFFFFF selects it.  TO_RANGE and (0, r^2) is the margin of radius r; TO_REST and (r^2 + 1, 0xFFFFFFFF) the erosion by the ball. */
+VPT_API int vpt_distance_within(vpt_distance *dist, uint32_t r2_lo, uint32_t r2_hi, uint32_t fill, vpt_volume **out);
+/* a new, finalized RG8 / RG16 volume with the source's filter: R the source code, G = min(floor(steps sqrt(d2)), M) =
+ * min(isqrt(steps^2 d2), M), isqrt the exact integer square root of the 64-bit product; steps (1 .. 256, otherwise VPT_ERR_INVALID) is
+ * the rows of the 2-D transfer function per voxel of distance.  VPT_DISTANCE_NONE gives M; the saturation at M is part of the contract. */
+VPT_API int vpt_distance_channel(vpt_distance *dist, int steps, vpt_volume **out);
+/* (for measurements) milliseconds of the x, y and z passes of vpt_volume_distance, ms[VPT_DISTANCE_PHASES], the stream drained after each */
+#define VPT_DISTANCE_PHASES 3
+VPT_API int vpt_distance_profile(vpt_distance *dist, double *ms);
+VPT_API int vpt_distance_destroy(vpt_distance *dist);
+
 /* ---- renderer: AbstractRenderer.js:17-116 and the four subclasses */
 /* new R(gl, volume, camera, environmentTexture, {resolution}) — AbstractRenderer.js:17-49; width != height is the
  * documented extension (uInverseResolution = (1/W, 1/H)).  Buffers are allocated as in _rebuildBuffers :78-92. */

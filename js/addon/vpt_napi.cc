@@ -306,6 +306,70 @@ static napi_value ComponentsDestroy(napi_env env, napi_callback_info info) {
     return undefined(env);
 }
 
+// ---- distance transform -------------------------------------------------------------------------------
+// volumeDistance(volume, lo, hi, seeds) -> a distance handle
+static napi_value VolumeDistance(napi_env env, napi_callback_info info) {
+    napi_value a[4]; vpt_volume *v; uint32_t lo, hi; int32_t seeds;
+    if (!get_args(env, info, 4, a) || !get_handle(env, a[0], &v) || !get_u32(env, a[1], &lo) || !get_u32(env, a[2], &hi) || !get_i32(env, a[3], &seeds)) return nullptr;
+    vpt_distance *out = nullptr;
+    VPT_CHECK(vpt_volume_distance(v, lo, hi, seeds, &out));
+    return make_external(env, out);
+}
+// distanceInfo(distance) -> [seeds, largest]
+static napi_value DistanceInfo(napi_env env, napi_callback_info info) {
+    napi_value a[1]; vpt_distance *d;
+    if (!get_args(env, info, 1, a) || !get_handle(env, a[0], &d)) return nullptr;
+    struct vpt_distance_info i;
+    VPT_CHECK(vpt_distance_info(d, &i));
+    napi_value out;
+    napi_create_array_with_length(env, 2, &out);
+    napi_set_element(env, out, 0, number(env, (double)i.seeds));
+    napi_set_element(env, out, 1, number(env, (double)i.largest));
+    return out;
+}
+// distanceSquared(distance, x, y, z, width, height, depth, dst): the box's squared distances into dst (a Uint32Array)
+static napi_value DistanceSquared(napi_env env, napi_callback_info info) {
+    napi_value a[8]; vpt_distance *d; int32_t p[6]; void *data; size_t n;
+    if (!get_args(env, info, 8, a) || !get_handle(env, a[0], &d)) return nullptr;
+    for (int i = 0; i < 6; i++) if (!get_i32(env, a[1 + i], &p[i])) return nullptr;
+    if (!get_bytes(env, a[7], &data, &n)) return nullptr;
+    VPT_CHECK(vpt_distance_squared(d, p[0], p[1], p[2], p[3], p[4], p[5], (uint32_t *)data, n));
+    return undefined(env);
+}
+// distanceWithin(distance, r2Lo, r2Hi, fill) -> a new volume handle
+static napi_value DistanceWithin(napi_env env, napi_callback_info info) {
+    napi_value a[4]; vpt_distance *d; uint32_t r2_lo, r2_hi, fill;
+    if (!get_args(env, info, 4, a) || !get_handle(env, a[0], &d) || !get_u32(env, a[1], &r2_lo) || !get_u32(env, a[2], &r2_hi) || !get_u32(env, a[3], &fill)) return nullptr;
+    vpt_volume *out = nullptr;
+    VPT_CHECK(vpt_distance_within(d, r2_lo, r2_hi, fill, &out));
+    return make_external(env, out);
+}
+// distanceChannel(distance, steps) -> a new volume handle
+static napi_value DistanceChannel(napi_env env, napi_callback_info info) {
+    napi_value a[2]; vpt_distance *d; int32_t steps;
+    if (!get_args(env, info, 2, a) || !get_handle(env, a[0], &d) || !get_i32(env, a[1], &steps)) return nullptr;
+    vpt_volume *out = nullptr;
+    VPT_CHECK(vpt_distance_channel(d, steps, &out));
+    return make_external(env, out);
+}
+// distanceProfile(distance) -> [x, y, z] milliseconds
+static napi_value DistanceProfile(napi_env env, napi_callback_info info) {
+    napi_value a[1]; vpt_distance *d;
+    if (!get_args(env, info, 1, a) || !get_handle(env, a[0], &d)) return nullptr;
+    double ms[VPT_DISTANCE_PHASES];
+    VPT_CHECK(vpt_distance_profile(d, ms));
+    napi_value out;
+    napi_create_array_with_length(env, VPT_DISTANCE_PHASES, &out);
+    for (int k = 0; k < VPT_DISTANCE_PHASES; k++) napi_set_element(env, out, k, number(env, ms[k]));
+    return out;
+}
+static napi_value DistanceDestroy(napi_env env, napi_callback_info info) {
+    napi_value a[1]; vpt_distance *d;
+    if (!get_args(env, info, 1, a) || !get_handle(env, a[0], &d)) return nullptr;
+    VPT_CHECK(vpt_distance_destroy(d));
+    return undefined(env);
+}
+
 // ---- renderer -----------------------------------------------------------------------------------------
 static napi_value RendererCreate(napi_env env, napi_callback_info info) {
     napi_value a[4]; vpt_context *c; int32_t kind, w, h;
@@ -619,6 +683,9 @@ static napi_value Init(napi_env env, napi_value exports) {
     EXPORT("volumeComponents", VolumeComponents); EXPORT("componentsInfo", ComponentsInfo); EXPORT("componentsList", ComponentsList);
     EXPORT("componentsRanks", ComponentsRanks); EXPORT("componentsKeep", ComponentsKeep); EXPORT("componentsLabel", ComponentsLabel);
     EXPORT("componentsDestroy", ComponentsDestroy);
+    EXPORT("volumeDistance", VolumeDistance); EXPORT("distanceInfo", DistanceInfo); EXPORT("distanceSquared", DistanceSquared);
+    EXPORT("distanceWithin", DistanceWithin); EXPORT("distanceChannel", DistanceChannel); EXPORT("distanceProfile", DistanceProfile);
+    EXPORT("distanceDestroy", DistanceDestroy);
     EXPORT("rendererCreate", RendererCreate); EXPORT("rendererDestroy", RendererDestroy); EXPORT("rendererSetShard", RendererSetShard);
     EXPORT("rendererLocalRows", RendererLocalRows); EXPORT("rendererGlobalRow", RendererGlobalRow);
     EXPORT("rendererSetVolume", RendererSetVolume); EXPORT("rendererSetTransferFunction", RendererSetTransferFunction);

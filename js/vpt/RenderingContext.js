@@ -14,6 +14,11 @@
 //   components of the codes lo .. hi of an R8 / R16 volume (Volume.components).  'keep' runs behind the rank filter and in front of the
 //   smoothing: the n largest (null: all of at least minVoxels voxels) keep their codes, everything else becomes 0.  'label' runs where the
 //   gradient runs, on the final scalar volume: the second channel is min(rank, M); it cannot be combined with `gradient`
+//   distance: null (default), { lo, hi, seeds: 'range', mode: 'within', from: 0, to: null, fill: 0 } or { ..., mode: 'channel', steps: 1 }: the
+//   exact squared Euclidean distance d2 of every voxel of an R8 / R16 volume to the codes lo .. hi (seeds 'range') or to the codes outside
+//   them (seeds 'rest') (Volume.distance).  'within' runs behind `components` mode 'keep' and in front of the smoothing: the codes with
+//   from <= d2 <= to (squared voxels; to null: no upper end) stay, everything else becomes `fill`.  'channel' runs where the gradient runs:
+//   the second channel is min(isqrt(steps^2 d2), M); it cannot be combined with `gradient` or with `components` mode 'label'
 const { EventTarget, CustomEvent } = require('./EventTarget.js');
 const { Context } = require('./Context.js');
 const { OrbitCameraAnimator } = require('./animators.js');
@@ -21,6 +26,7 @@ const { Node, Transform, PerspectiveCamera } = require('./scene.js');
 const { Volume, gradientArguments, windowFormatBits, checkPasses, checkLevels, rankOperatorCode, checkRankPasses } = require('./Volume.js');
 const { native } = require('./native.js');
 const { checkConnectivity, checkRange, checkMinVoxels, checkKeep } = require('./components.js');
+const { checkSeeds, checkSteps, checkWithin, checkDistanceRange } = require('./distance.js');
 const { RendererFactory } = require('./renderers/RendererFactory.js');
 const { ToneMapperFactory } = require('./tonemappers/ToneMapperFactory.js');
 
@@ -47,6 +53,13 @@ constructor(options) {
     this.components = RenderingContext._componentsSpec(options.components);          // likewise
     if (this.components !== null && this.components.mode === 'label' && this.gradient !== null) {
         throw new Error("components mode 'label' and gradient both write the second channel: name one of them");
+    }
+    this.distance = RenderingContext._distanceSpec(options.distance);                // likewise
+    if (this.distance !== null && this.distance.mode === 'channel') {
+        if (this.gradient !== null) { throw new Error("distance mode 'channel' and gradient both write the second channel: name one of them"); }
+        if (this.components !== null && this.components.mode === 'label') {
+            throw new Error("distance mode 'channel' and components mode 'label' both write the second channel: name one of them");
+        }
     }
     this.gl = new Context(options.device || 0);                                   // initGL(), :61-105
     this.environmentTexture = { data: new Uint8Array([255, 255, 255, 255]), width: 1, height: 1 };   // :90-101
@@ -107,6 +120,10 @@ async setVolume(reader) {                                                       
             }
         }
         if (this.components !== null && this.components.mode === 'keep') { this._derive(found => found.keep(1, this.components.keep)); }
+        if (this.distance !== null && this.distance.mode === 'within') {
+            const spec = this.distance;
+            this._deriveDistance(found => found.within(spec.from, spec.to, spec.fill));
+        }
         if (this.smooth !== null) {
             const N = native(), fmt = this.volume.nativeFormat();
             if (fmt === N.VPT_FORMAT_R8 || fmt === N.VPT_FORMAT_R16) {                 // the formats the gradient takes: any other volume as it is
@@ -129,6 +146,7 @@ async setVolume(reader) {                                                       
             }
         }
         if (this.components !== null && this.components.mode === 'label') { this._derive(found => found.label()); }   // (value, rank)
+        if (this.distance !== null && this.distance.mode === 'channel') { this._deriveDistance(found => found.channel(this.distance.steps)); }   // (value, distance)
     } catch (e) {                                                                      // the context keeps the volume it had
         this.volume.destroy();
         this.volume = old;
@@ -146,6 +164,37 @@ _derive(emit) {
     const found = source.components(spec.lo, Math.min(spec.hi, largest), spec.connectivity, spec.minVoxels);
     try { this.volume = emit(found); } finally { found.destroy(); }
     source.destroy();
+}
+
+// replaces this.volume (if it is R8 / R16: any other volume stays as it is) by what emit(distances of the `distance` option) returns
+_deriveDistance(emit) {
+    const N = native(), fmt = this.volume.nativeFormat(), spec = this.distance;
+    if (fmt !== N.VPT_FORMAT_R8 && fmt !== N.VPT_FORMAT_R16) { return; }
+    const source = this.volume, largest = fmt === N.VPT_FORMAT_R16 ? 65535 : 255;      // the range is open above: hi may exceed an R8 volume's codes
+    const found = source.distance(spec.lo, Math.min(spec.hi, largest), spec.seeds);
+    try { this.volume = emit(found); } finally { found.destroy(); }
+    source.destroy();
+}
+
+// the `distance` option with its defaults filled in, or null; throws for anything the contract does not take
+static _distanceSpec(spec) {
+    if (spec === undefined || spec === null) { return null; }
+    const known = ['lo', 'hi', 'seeds', 'mode', 'from', 'to', 'fill', 'steps'], given = k => spec[k] !== undefined && spec[k] !== null;
+    if (typeof spec !== 'object' || Array.isArray(spec) || !Object.keys(spec).every(k => known.includes(k)) || (spec.mode !== 'within' && spec.mode !== 'channel')) {
+        throw new Error("distance is null or { lo, hi, seeds, mode: 'within' | 'channel', from, to, fill, steps }, not " + JSON.stringify(spec));
+    }
+    checkDistanceRange(spec.lo, spec.hi, 65535);
+    const out = { lo: spec.lo, hi: spec.hi, seeds: given('seeds') ? spec.seeds : 'range', mode: spec.mode, from: 0, to: null, fill: 0, steps: 1 };
+    checkSeeds(out.seeds);
+    if (spec.mode === 'within') {
+        if (given('steps')) { throw new Error("distance 'steps' goes with mode 'channel'"); }
+        const k = checkWithin(given('from') ? spec.from : 0, spec.to, given('fill') ? spec.fill : 0, 65535);
+        out.from = k[0]; out.to = k[1]; out.fill = k[2];
+    } else {
+        if (given('from') || given('to') || given('fill')) { throw new Error("distance 'from', 'to' and 'fill' go with mode 'within'"); }
+        out.steps = checkSteps(given('steps') ? spec.steps : 1);
+    }
+    return out;
 }
 
 // the `components` option with its defaults filled in, or null; throws for anything the contract does not take

@@ -5,6 +5,7 @@ const { native } = require('./native.js');
 
 const R = require('./readers/readers.js');
 const { checkConnectivity, checkRange, checkMinVoxels, checkKeep } = require('./components.js');
+const { checkSeeds, checkSteps, checkRadius, checkWithin, checkDistanceRange } = require('./distance.js');
 const { RAWReader, GL_RED, GL_RG, GL_RGB, GL_RGBA, GL_UNSIGNED_BYTE, GL_FLOAT, GL_HALF_FLOAT, GL_BYTE } = R;
 
 // [type, format, internalFormat, native format name, channels in the file, element kind] of the formats keyed on all three: SNORM bytes
@@ -361,6 +362,89 @@ removeIslands(lo, hi, minVoxels, connectivity) {
     try { return c.keep(1, null); } finally { c.destroy(); }
 }
 
+// ---- extension: exact Euclidean distance transform of a value range (include/vpt.h; DESIGN.md "Distance transform") ----
+// the squared Euclidean distance of every voxel of this (R8 / R16) volume to the nearest voxel whose code is (seeds 'range', the default) or
+// is not (seeds 'rest') in lo .. hi, as a Distance object, transformed on the device.  The object owns what it needs; this volume is not changed
+distance(lo, hi, seeds) {
+    const N = native(), norm16 = this.nativeFormat() === N.VPT_FORMAT_R16;
+    checkDistanceRange(lo, hi, norm16 ? 65535 : 255);
+    return new Distance(this, N.volumeDistance(this.texture, lo, hi, checkSeeds(seeds !== undefined ? seeds : 'range')));
+}
+// the codes within `radius` voxels of the codes lo .. hi keep their codes; 0 elsewhere
+margin(lo, hi, radius) {
+    const r2 = checkRadius(radius), d = this.distance(lo, hi, 'range');
+    try { return d.within(0, r2); } finally { d.destroy(); }
+}
+// the codes lo .. hi eroded by the Euclidean ball of `radius` voxels keep their codes; 0 elsewhere
+core(lo, hi, radius) {
+    const r2 = checkRadius(radius), d = this.distance(lo, hi, 'rest');
+    try { return d.within(r2 + 1, null); } finally { d.destroy(); }
+}
+
+}
+
+// The squared Euclidean distances to a value range of a volume, or to its complement (Volume.distance): one Uint32 per voxel on the device.
+// Transform once, select several times.  Outlives the volume it was made from; destroy() frees the device memory.
+class Distance {
+
+constructor(source, handle) {
+    const N = native();
+    this._h = handle;
+    this._norm16 = source.nativeFormat() === N.VPT_FORMAT_R16;
+    this._dimensions = Object.assign({}, source.modality.dimensions);
+    this._like = new Volume(source._gl);                       // what a derived volume's description is made from (Volume._sameFormat)
+    this._like.modality = Object.assign({}, source.modality);
+    this._like.metadata = { meta: Object.assign({}, (source.metadata || {}).meta) };
+}
+
+_handle() {
+    if (!this._h) { throw new Error('the distances have been destroyed'); }
+    return this._h;
+}
+
+destroy() {
+    if (this._h) { native().distanceDestroy(this._h); this._h = null; }
+}
+
+// { seeds, largest }: the number of seeds; the largest finite squared distance, 0 without a seed
+get info() {
+    const i = native().distanceInfo(this._handle());
+    return { seeds: i[0], largest: i[1] };
+}
+
+// Uint32Array [depth][height][width]: the squared distances of a box of voxels (default: the whole volume); 0xFFFFFFFF: there is no seed
+squared(x, y, z, width, height, depth) {
+    const d = this._dimensions;
+    x = x || 0; y = y || 0; z = z || 0;
+    width = width !== undefined ? width : d.width - x; height = height !== undefined ? height : d.height - y; depth = depth !== undefined ? depth : d.depth - z;
+    const out = new Uint32Array(width * height * depth);
+    native().distanceSquared(this._handle(), x, y, z, width, height, depth, out);
+    return out;
+}
+
+// a new, ready volume of the source's size, format and filter: the source's code where r2Lo <= d2 <= r2Hi (defaults 0 and 0xFFFFFFFF),
+// `fill` (default 0) elsewhere
+within(r2Lo, r2Hi, fill) {
+    const k = checkWithin(r2Lo !== undefined ? r2Lo : 0, r2Hi, fill !== undefined ? fill : 0, this._norm16 ? 65535 : 255);
+    return this._like._sameFormat(native().distanceWithin(this._handle(), k[0], k[1], k[2]), this._dimensions);
+}
+
+// a new, ready RG8 / RG16 volume with the source's filter: (code, min(isqrt(steps^2 d2), M)): the second axis of a 2-D transfer function is
+// the distance, `steps` (1 .. 256, default 1) rows a voxel
+channel(steps) {
+    steps = checkSteps(steps !== undefined ? steps : 1);
+    const out = this._like._sameFormat(native().distanceChannel(this._handle(), steps), this._dimensions);
+    Object.assign(out.modality, { format: GL_RG, internalFormat: this._norm16 ? R.GL_RG16_EXT : R.GL_RG8,
+        type: this._norm16 ? R.GL_UNSIGNED_SHORT : GL_UNSIGNED_BYTE });
+    return out;
+}
+
+// (for measurements) { x, y, z }: milliseconds of the three passes of the transform
+profile() {
+    const ms = native().distanceProfile(this._handle());
+    return { x: ms[0], y: ms[1], z: ms[2] };
+}
+
 }
 
 // The connected components of a value range of a volume (Volume.components): per-voxel ranks and the component list on the device.  Label
@@ -449,4 +533,4 @@ function checkRankPasses(passes) {
     if (!Number.isInteger(passes) || passes < 1 || passes > 8) { throw new Error('rank-filter passes are an integer in 1 .. 8, not ' + JSON.stringify(passes)); }
     return passes;
 }
-module.exports = { Volume, Components, RAWReader, filterCode, gradientArguments, windowFormatBits, percentileWindow, checkPasses, checkLevels, rankOperatorCode, checkRankPasses };
+module.exports = { Volume, Components, Distance, RAWReader, filterCode, gradientArguments, windowFormatBits, percentileWindow, checkPasses, checkLevels, rankOperatorCode, checkRankPasses };

@@ -1,0 +1,33 @@
+"""CPU: every kernel of the distance-transform unit (vpt_volume_distance.hip) compiles for gfx950 without scratch memory or register
+spills, with at most 64 KiB of LDS per workgroup and an occupancy of at least 2: the conditions of the sibling units
+(tests/test_components_kernel_resources.py).  These are conditions, not measurements (DESIGN.md records the figures the compiler reports)."""
+import re
+import shutil
+
+import pytest
+
+from test_snorm_kernel_resources import resource_usage
+
+
+@pytest.mark.skipif(shutil.which("hipcc") is None, reason="hipcc not installed")
+def test_distance_kernels_use_no_scratch_and_share_a_cu():
+    usage = resource_usage(["vpt_volume_distance"])
+    # k_edt_x<T>: T in {uint8_t (h), uint16_t (t)}
+    rows = {k: v for k, v in usage.items() if re.match(r"_Z7k_edt_xI[ht]E", k)}
+    assert len(rows) == 2, sorted(usage)
+    # k_edt_line<AXIS>: y and z
+    lines = {k: v for k, v in usage.items() if re.match(r"_Z10k_edt_lineILi[12]EE", k)}
+    assert len(lines) == 2, sorted(usage)
+    # the emitters k_within<T> and k_channel<T>
+    emit = {k: v for k, v in usage.items() if re.match(r"_Z(8k_within|9k_channel)I[ht]E", k)}
+    assert len(emit) == 4, sorted(usage)
+    # the largest finite d2, the read-back of a box of d2
+    plain = {k: v for k, v in usage.items() if re.match(r"_Z\d+k_(largest|read_squared)P", k)}
+    assert len(plain) == 2, sorted(usage)
+    assert len(usage) == 10, sorted(usage)                       # no kernel of the unit escapes the conditions below
+    for name, u in usage.items():
+        assert u.get("ScratchSize", 0) == 0 and u.get("VGPRs Spill", 0) == 0 and u.get("SGPRs Spill", 0) == 0, (name, u)
+        assert u.get("LDS Size", 0) <= 64 * 1024, (name, u)
+        assert u.get("Occupancy", 0) >= 2, (name, u)
+    for name, u in list(rows.items()) + list(lines.items()):    # the row and line passes need no LDS
+        assert u.get("LDS Size", 0) == 0, (name, u)

@@ -6,7 +6,7 @@ constructing a Context does, and raises if it is missing (no CPU fallback)."""
 from .property_bag import PropertyBag, EventTarget, Event, CustomEvent
 from .scene import Node, Transform, PerspectiveCamera, mat4, quat, vec3, default_camera, mvp_inverse_matrix
 from .context import Context
-from .volume import Volume, Components
+from .volume import Volume, Components, Distance
 from .loaders import AbstractLoader, BlobLoader, FileLoader, LoaderFactory
 from .readers import AbstractReader, RAWReader, ZIPReader, BVPReader, ReaderFactory
 from .renderers import (AbstractRenderer, MIPRenderer, EAMRenderer, MCSRenderer, MCMRenderer, ISORenderer, DepthRenderer, LAORenderer, DOSRenderer,
@@ -23,6 +23,7 @@ from .window import window_texels, percentile_window
 from .pyramid import reduce_texels, smooth_texels
 from .rank import rank_texels
 from .components import components_texels, keep_texels, label_texels
+from .distance import distance_squared_texels, within_texels, channel_texels, check_seeds, check_steps, check_radius
 from ._native import VptError
 
 __all__ = [
@@ -35,4 +36,5 @@ __all__ = [
     'UchimuraToneMapper', 'ToneMapperFactory', 'RenderingContext', 'CircleAnimator', 'OrbitCameraAnimator', 'TransferFunction',
     'HDRImage', 'read_hdr', 'gradient_magnitude', 'window_texels', 'percentile_window', 'reduce_texels', 'smooth_texels', 'rank_texels',
     'components_texels', 'keep_texels', 'label_texels', 'Components',
+    'distance_squared_texels', 'within_texels', 'channel_texels', 'check_seeds', 'check_steps', 'check_radius', 'Distance',
 ]

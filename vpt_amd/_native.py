@@ -53,6 +53,8 @@ SYMBOLS = [
     "vpt_volume_reduce", "vpt_volume_smooth", "vpt_volume_rank",
     "vpt_volume_components", "vpt_components_info", "vpt_components_list", "vpt_components_ranks", "vpt_components_keep",
     "vpt_components_label", "vpt_components_profile", "vpt_components_destroy",
+    "vpt_volume_distance", "vpt_distance_info", "vpt_distance_squared", "vpt_distance_within", "vpt_distance_channel",
+    "vpt_distance_profile", "vpt_distance_destroy",
     "vpt_renderer_create", "vpt_renderer_set_shard", "vpt_renderer_local_rows", "vpt_renderer_global_row",
     "vpt_renderer_destroy", "vpt_renderer_set_volume", "vpt_renderer_set_transfer_function",
     "vpt_renderer_set_environment", "vpt_renderer_set_environment_texels", "vpt_renderer_resize",
@@ -104,6 +106,16 @@ class ComponentsInfo(C.Structure):
 
 
 COMPONENTS_PHASES = 7
+
+
+class DistanceInfo(C.Structure):
+    """struct vpt_distance_info (include/vpt.h)"""
+    _fields_ = [("seeds", C.c_uint64), ("largest", C.c_uint32)]
+
+
+DISTANCE_TO_RANGE, DISTANCE_TO_REST = 0, 1
+DISTANCE_NONE = 0xFFFFFFFF
+DISTANCE_PHASES = 3
 
 
 class TonemapParams(C.Structure):
@@ -177,6 +189,9 @@ def lib():
         "vpt_components_list": [P, C.c_uint64, C.c_uint64, C.POINTER(Component)], "vpt_components_ranks": [P, I, I, I, I, I, I, P, SZ],
         "vpt_components_keep": [P, C.c_uint64, C.c_uint64, C.c_uint32, PP], "vpt_components_label": [P, PP],
         "vpt_components_profile": [P, C.POINTER(C.c_double), C.POINTER(C.c_uint32)], "vpt_components_destroy": [P],
+        "vpt_volume_distance": [P, C.c_uint32, C.c_uint32, I, PP], "vpt_distance_info": [P, C.POINTER(DistanceInfo)],
+        "vpt_distance_squared": [P, I, I, I, I, I, I, P, SZ], "vpt_distance_within": [P, C.c_uint32, C.c_uint32, C.c_uint32, PP],
+        "vpt_distance_channel": [P, I, PP], "vpt_distance_profile": [P, C.POINTER(C.c_double)], "vpt_distance_destroy": [P],
         "vpt_renderer_create": [P, I, I, I, PP],
         "vpt_renderer_set_shard": [P, I, I, I], "vpt_renderer_local_rows": [P, C.POINTER(I)],
         "vpt_renderer_global_row": [P, I, C.POINTER(I)],

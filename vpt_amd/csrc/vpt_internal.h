@@ -13,6 +13,7 @@
 //   vpt_volume_pyramid.hip  the next coarser level of a volume (2 x 2 x 2 cells averaged) and its binomial smoothing
 //   vpt_volume_rank.hip  the rank filters of a volume over the 3 x 3 x 3 box: median, erosion, dilation, opening and closing
 //   vpt_volume_components.hip  the connected components of a value range: per-voxel ranks, the component list, keep and label volumes
+//   vpt_volume_distance.hip  the exact squared Euclidean distance to a value range (or to its complement): per-voxel d2, within and channel volumes
 // vpt_variants.h (through vpt_device.h) holds the variant bits of the sampling kernels and the switch from a run-time variant to a template
 // argument; launch_variant below is its use for a renderer's sampling pass.
 // vpt_buffers.h holds DevBuf<T> / PinnedBuf<T>, the owners of device and pinned host memory: the objects below own their memory through such

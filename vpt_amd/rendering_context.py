@@ -56,6 +56,18 @@ class RenderingContext(EventTarget):
         self.components = self._components_spec(options.get('components'))
         if self.components is not None and self.components['mode'] == 'label' and self.gradient is not None:
             raise ValueError("components mode 'label' and gradient both write the second channel: name one of them")
+        # (extension) None | {'lo', 'hi', 'seeds': 'range', 'mode': 'within', 'from': 0, 'to': None, 'fill': 0} | {..., 'mode': 'channel',
+        # 'steps': 1}: the exact squared Euclidean distance d2 of every voxel of an R8 / R16 volume to the codes lo .. hi (seeds 'range') or
+        # to the codes outside them (seeds 'rest').  'within' runs behind `components` mode 'keep' and in front of the smoothing: the codes
+        # with from <= d2 <= to (squared voxels; to None: no upper end) stay, everything else becomes `fill`.  'channel' runs where the
+        # gradient runs, on the final scalar volume: the second channel is min(isqrt(steps^2 d2), M), so it cannot be combined with
+        # `gradient` or with `components` mode 'label'
+        self.distance = self._distance_spec(options.get('distance'))
+        if self.distance is not None and self.distance['mode'] == 'channel':
+            if self.gradient is not None:
+                raise ValueError("distance mode 'channel' and gradient both write the second channel: name one of them")
+            if self.components is not None and self.components['mode'] == 'label':
+                raise ValueError("distance mode 'channel' and components mode 'label' both write the second channel: name one of them")
         self.gl = Context(options.get('device', 0))                                   # initGL(), :61-105
         self.environmentTexture = np.array([[[255, 255, 255, 255]]], dtype=np.uint8)   # :90-101
         self._rng = options.get('rng')
@@ -106,6 +118,9 @@ class RenderingContext(EventTarget):
                 source.destroy()
             if self.components is not None and self.components['mode'] == 'keep' and self._one_channel_unorm(self.volume):
                 self._derive(lambda source, found: found.keep(1, self.components['keep']))
+            if self.distance is not None and self.distance['mode'] == 'within' and self._one_channel_unorm(self.volume):
+                spec = self.distance
+                self._derive_distance(lambda found: found.within(spec['from'], spec['to'], spec['fill']))
             if self.smooth is not None and self._one_channel_unorm(self.volume):
                 source = self.volume
                 self.volume = source.smooth(self.smooth)
@@ -120,6 +135,8 @@ class RenderingContext(EventTarget):
                 source.destroy()
             if self.components is not None and self.components['mode'] == 'label' and self._one_channel_unorm(self.volume):
                 self._derive(lambda source, found: found.label())                     # (value, rank): a row of the 2-D transfer function per structure
+            if self.distance is not None and self.distance['mode'] == 'channel' and self._one_channel_unorm(self.volume):
+                self._derive_distance(lambda found: found.channel(self.distance['steps']))   # (value, distance): the 2-D transfer function's axes
         except Exception:                                                             # the context keeps the volume it had
             self.volume.destroy()
             self.volume = old
@@ -141,6 +158,46 @@ class RenderingContext(EventTarget):
         finally:
             found.destroy()
         source.destroy()
+
+    def _derive_distance(self, emit):
+        """replaces self.volume by what ``emit(distances of the `distance` option)`` returns"""
+        spec = self.distance
+        source = self.volume
+        from . import _native as N
+        largest = 65535 if source.native_format()[0] == N.FORMAT_R16 else 255        # the range is open above: hi may exceed an R8 volume's codes
+        found = source.distance(spec['lo'], min(spec['hi'], largest), spec['seeds'])
+        try:
+            self.volume = emit(found)
+        finally:
+            found.destroy()
+        source.destroy()
+
+    @staticmethod
+    def _distance_spec(spec):
+        """the `distance` option with its defaults filled in, or None; raises ValueError for anything the contract does not take"""
+        if spec is None:
+            return None
+        from .distance import check_range, check_seeds, check_steps, check_within
+        known = {'lo', 'hi', 'seeds', 'mode', 'from', 'to', 'fill', 'steps'}
+        if not isinstance(spec, dict) or not {'lo', 'hi', 'mode'} <= set(spec) or not set(spec) <= known:
+            raise ValueError("distance is None or {'lo', 'hi', 'seeds', 'mode': 'within' | 'channel', 'from', 'to', 'fill', 'steps'}, not %r" % (spec,))
+        if spec['mode'] not in ('within', 'channel'):
+            raise ValueError("distance mode is 'within' or 'channel', not %r" % (spec['mode'],))
+        lo, hi = check_range(spec['lo'], spec['hi'], 65535)
+        seeds = spec['seeds'] if spec.get('seeds') is not None else 'range'
+        check_seeds(seeds)
+        out = {'lo': lo, 'hi': hi, 'seeds': seeds, 'mode': spec['mode'], 'from': 0, 'to': None, 'fill': 0, 'steps': 1}
+        if spec['mode'] == 'within':
+            if spec.get('steps') is not None:
+                raise ValueError("distance 'steps' goes with mode 'channel'")
+            r2_lo, r2_hi, fill = check_within(spec['from'] if spec.get('from') is not None else 0, spec.get('to'),
+                                              spec['fill'] if spec.get('fill') is not None else 0, 65535)
+            out.update({'from': r2_lo, 'to': r2_hi, 'fill': fill})
+        else:
+            if any(spec.get(k) is not None for k in ('from', 'to', 'fill')):
+                raise ValueError("distance 'from', 'to' and 'fill' go with mode 'within'")
+            out['steps'] = check_steps(spec['steps'] if spec.get('steps') is not None else 1)
+        return out
 
     @staticmethod
     def _components_spec(spec):

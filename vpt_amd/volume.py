@@ -448,6 +448,39 @@ class Volume(EventTarget):
         finally:
             c.destroy()
 
+    # ---- extension: exact Euclidean distance transform of a value range (include/vpt.h; DESIGN.md "Distance transform") ----
+    def distance(self, lo, hi, seeds='range'):
+        """The squared Euclidean distance of every voxel of this (R8 / R16) volume to the nearest voxel whose code is (seeds 'range') or is
+        not (seeds 'rest') in lo .. hi, as a ``Distance`` object, transformed on the device (vpt_amd.distance_squared_texels states the
+        contract).  The object owns what it needs: this volume is not changed and may be destroyed."""
+        from .distance import check_range, check_seeds
+        norm16 = self.native_format()[0] in (N.FORMAT_R16, N.FORMAT_RG16, N.FORMAT_R16_SNORM, N.FORMAT_RG16_SNORM)
+        lo, hi = check_range(lo, hi, 65535 if norm16 else 255)
+        h = C.c_void_p()
+        N.check(N.lib().vpt_volume_distance(self.texture, lo, hi, check_seeds(seeds), C.byref(h)))
+        return Distance(self, h)
+
+    def margin(self, lo, hi, radius):
+        """A new, ready volume like this one that keeps its codes within ``radius`` voxels of the codes lo .. hi; 0 elsewhere"""
+        from .distance import check_radius
+        r2 = check_radius(radius)
+        d = self.distance(lo, hi, 'range')
+        try:
+            return d.within(0, r2)
+        finally:
+            d.destroy()
+
+    def core(self, lo, hi, radius):
+        """A new, ready volume like this one in which the codes lo .. hi eroded by the Euclidean ball of ``radius`` voxels keep their
+        codes (the voxels deeper than ``radius`` inside the structure); 0 elsewhere"""
+        from .distance import check_radius
+        r2 = check_radius(radius)
+        d = self.distance(lo, hi, 'rest')
+        try:
+            return d.within(r2 + 1, None)
+        finally:
+            d.destroy()
+
     def set_wide_tables(self, wide):
         """force the > 4 GiB addressing variant of the kernels (automatic above 4 GiB of bricked data)"""
         N.check(N.lib().vpt_volume_set_wide_tables(self.texture, 1 if wide else 0))
@@ -533,3 +566,71 @@ class Components:
         N.check(N.lib().vpt_components_profile(self._handle(), ms, launches))
         names = ('tiles', 'merge', 'flatten', 'sizes', 'compaction', 'sort', 'ranks')
         return dict(zip(names, ms)), int(launches[0]), int(launches[1])
+
+
+class Distance:
+    """The squared Euclidean distances to a value range of a volume, or to its complement (``Volume.distance``): one uint32 per voxel on
+    the device.  Transform once, select several times.  Outlives the volume it was made from; ``destroy()`` frees the device memory."""
+
+    def __init__(self, source, handle):
+        self._h = handle
+        self._gl = source._gl
+        dims = source.modality['dimensions']
+        self._shape = (dims['depth'], dims['height'], dims['width'])
+        self._norm16 = source.modality.get('internalFormat') == GL_R16_EXT
+        # what a derived volume's description is made from (Volume._same_format)
+        self._like = Volume(source._gl)
+        self._like.modality = dict(source.modality)
+        self._like.metadata = {'meta': dict((source.metadata or {}).get('meta', {}))}
+
+    def _handle(self):
+        if not self._h:
+            raise RuntimeError('the distances have been destroyed')
+        return self._h
+
+    def destroy(self):
+        if self._h:
+            N.lib().vpt_distance_destroy(self._h)
+            self._h = None
+
+    @property
+    def info(self):
+        """{'seeds', 'largest'}: the number of seeds; the largest finite squared distance, 0 without a seed"""
+        i = N.DistanceInfo()
+        N.check(N.lib().vpt_distance_info(self._handle(), C.byref(i)))
+        return {name: int(getattr(i, name)) for name, _ in N.DistanceInfo._fields_}
+
+    def squared(self, x=0, y=0, z=0, w=None, h=None, d=None):
+        """uint32 [d][h][w]: the squared distances of a box of voxels (the whole volume by default); 0xFFFFFFFF: there is no seed"""
+        w = self._shape[2] - x if w is None else w
+        h = self._shape[1] - y if h is None else h
+        d = self._shape[0] - z if d is None else d
+        out = np.empty((int(d), int(h), int(w)), np.uint32)
+        N.check(N.lib().vpt_distance_squared(self._handle(), int(x), int(y), int(z), int(w), int(h), int(d), out.ctypes.data_as(C.c_void_p), out.nbytes))
+        return out
+
+    def within(self, r2_lo=0, r2_hi=None, fill=0):
+        """A new, ready volume of the source's size, format and filter: the source's code where r2_lo <= d2 <= r2_hi (r2_hi None:
+        0xFFFFFFFF), ``fill`` elsewhere (vpt_amd.within_texels states it)"""
+        from .distance import check_within
+        r2_lo, r2_hi, fill = check_within(r2_lo, r2_hi, fill, 65535 if self._norm16 else 255)
+        h = C.c_void_p()
+        N.check(N.lib().vpt_distance_within(self._handle(), r2_lo, r2_hi, fill, C.byref(h)))
+        return self._like._same_format(h, self._like.modality['dimensions'])
+
+    def channel(self, steps=1):
+        """A new, ready RG8 / RG16 volume with the source's filter: (code, min(isqrt(steps^2 d2), M)) (vpt_amd.channel_texels states it):
+        the second axis of a 2-D transfer function is the distance, ``steps`` rows a voxel"""
+        from .distance import check_steps
+        h = C.c_void_p()
+        N.check(N.lib().vpt_distance_channel(self._handle(), check_steps(steps), C.byref(h)))
+        out = self._like._same_format(h, self._like.modality['dimensions'])
+        out.modality.update({'format': GL_RG, 'internalFormat': GL_RG16_EXT if self._norm16 else GL_RG8,
+                             'type': GL_UNSIGNED_SHORT if self._norm16 else GL_UNSIGNED_BYTE})
+        return out
+
+    def profile(self):
+        """(for measurements) {'x', 'y', 'z'}: milliseconds of the three passes of the transform"""
+        ms = (C.c_double * N.DISTANCE_PHASES)()
+        N.check(N.lib().vpt_distance_profile(self._handle(), ms))
+        return dict(zip(('x', 'y', 'z'), ms))
