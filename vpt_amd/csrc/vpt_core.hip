@@ -36,12 +36,11 @@ extern "C" int vpt_context_create(int device, vpt_context **out) {
     HIP_TRY(hipGetDeviceCount(&n));
     if (device < 0 || device >= n) return fail(VPT_ERR_INVALID, "device %d out of range (%d devices)", device, n);
     HIP_TRY(hipSetDevice(device));
-    vpt_context *c = new vpt_context();
+    std::unique_ptr<vpt_context> c(new vpt_context());
     c->device = device;
-    hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-    if (e != hipSuccess) { delete c; return fail(VPT_ERR_HIP, "hipStreamCreate: %s", hipGetErrorString(e)); }
-    c->owns_stream = true;
-    *out = c;
+    HIP_TRY(c->own.create());
+    c->stream = c->own;
+    *out = c.release();
     return VPT_OK;
 }
 extern "C" int vpt_context_create_on_stream(int device, void *hip_stream, vpt_context **out) {
@@ -52,16 +51,14 @@ extern "C" int vpt_context_create_on_stream(int device, void *hip_stream, vpt_co
     HIP_TRY(hipSetDevice(device));
     vpt_context *c = new vpt_context();
     c->device = device;
-    c->stream = (hipStream_t)hip_stream;
-    c->owns_stream = false;
+    c->stream = (hipStream_t)hip_stream;      // the caller's: `own` stays empty
     *out = c;
     return VPT_OK;
 }
 extern "C" int vpt_context_destroy(vpt_context *c) {
     if (!c) return VPT_OK;
     hipSetDevice(c->device);
-    hipStreamSynchronize(c->stream);
-    if (c->owns_stream) hipStreamDestroy(c->stream);
+    hipStreamSynchronize(c->stream);          // nothing is in flight when the stream goes with the context
     delete c;
     return VPT_OK;
 }
@@ -503,16 +500,12 @@ extern "C" int vpt_renderer_destroy(vpt_renderer *r) {
     if (!r) return VPT_OK;
     join_side(r);
     hipSetDevice(r->ctx->device);
-    hipStreamSynchronize(r->ctx->stream);
+    hipStreamSynchronize(r->ctx->stream);     // everything is idle from here on: the order in which the members go is immaterial
     tonemappers_unbind(r->ctx, r);            // a tone mapper still bound to this renderer falls back to the white placeholder
     for (size_t i = 0; i < r->ctx->renderers.size(); i++)
         if (r->ctx->renderers[i] == r) { r->ctx->renderers.erase(r->ctx->renderers.begin() + (long)i); break; }
-    for (int i = 0; i < 2; i++) if (r->cls.staged[i]) hipEventDestroy(r->cls.staged[i]);
-    destroy_split_streams(r);
     if (r->play_graph) play_graph_free(r->play_graph);
-    for (auto &ev : r->events) { hipEventDestroy(ev.first); hipEventDestroy(ev.second); }
-    for (auto &ev : r->side_events) { hipEventDestroy(ev.first); hipEventDestroy(ev.second); }
-    delete r;                                 // the renderer's buffers go with it; the volume is NOT owned (Volume.js:17-22)
+    delete r;                                 // the renderer's buffers, streams and events go with it; the volume is NOT owned (Volume.js:17-22)
     return VPT_OK;
 }
 extern "C" int vpt_renderer_set_shard(vpt_renderer *r, int rank, int world, int rows_per_block) {
@@ -770,24 +763,22 @@ static bool streams_overlap(hipStream_t a, hipStream_t b) {
     return seen;
 }
 // a new non-blocking stream that overlaps r's context stream and every side stream r has
-hipError_t create_overlapping_stream(hipStream_t *out, const vpt_renderer *r) {
+hipError_t create_overlapping_stream(Stream *out, const vpt_renderer *r) {
     static const bool probe = []() { const char *e = getenv("VPT_STREAM_PROBE"); return !(e && e[0] == '0'); }();
     hipStream_t others[VPT_MAX_SPLIT] = { r->ctx->stream };
     for (int k = 0; k < VPT_MAX_SPLIT - 1; k++) others[1 + k] = r->streams.side[k];
-    hipStream_t tried[8]; int nt = 0; hipStream_t chosen = nullptr;
-    while (nt < 8 && !chosen) {
-        hipStream_t c;
-        hipError_t e = hipStreamCreateWithFlags(&c, hipStreamNonBlocking);
+    Stream tried[8]; int nt = 0, chosen = -1;
+    while (nt < 8 && chosen < 0) {
+        hipError_t e = tried[nt].create();
         if (e != hipSuccess) { if (nt == 0) return e; (void)hipGetLastError(); break; }
-        tried[nt++] = c;
         bool ok = true;
-        for (int i = 0; i < VPT_MAX_SPLIT && ok && probe; i++) if (others[i]) ok = streams_overlap(others[i], c);
-        if (ok) chosen = c;
+        for (int i = 0; i < VPT_MAX_SPLIT && ok && probe; i++) if (others[i]) ok = streams_overlap(others[i], tried[nt]);
+        if (ok) chosen = nt;
+        nt++;
     }
-    if (!chosen) chosen = tried[0];
-    for (int i = 0; i < nt; i++) if (tried[i] != chosen) hipStreamDestroy(tried[i]);
+    *out = std::move(tried[std::max(chosen, 0)]);
+    for (Stream &rejected : tried) rejected.reset();
     (void)hipGetLastError();
-    *out = chosen;
     return hipSuccess;
 }
 
@@ -797,19 +788,14 @@ int ensure_split_streams(vpt_renderer *r) {
     StreamSet &s = r->streams;
     if (r->split < 2 || (s.side[r->split - 2] && s.ev_fork)) return VPT_OK;
     HIP_TRY(hipSetDevice(r->ctx->device));
-    if (!s.ev_fork) HIP_TRY(hipEventCreateWithFlags(&s.ev_fork, hipEventDisableTiming));
+    if (!s.ev_fork) HIP_TRY(s.ev_fork.create(hipEventDisableTiming));
     for (int i = 0; i + 1 < r->split; i++) if (!s.side[i]) {
         HIP_TRY(hipStreamSynchronize(r->ctx->stream));
+        HIP_TRY(s.ev_join[i].create(hipEventDisableTiming));     // (before its stream: a side stream that exists has its join event)
         HIP_TRY(create_overlapping_stream(&s.side[i], r));
-        HIP_TRY(hipEventCreateWithFlags(&s.ev_join[i], hipEventDisableTiming));
     }
     s.mark_dirty();
     return VPT_OK;
-}
-void destroy_split_streams(vpt_renderer *r) {
-    StreamSet &s = r->streams;
-    for (int i = 0; i < VPT_MAX_SPLIT - 1; i++) if (s.side[i]) { hipStreamDestroy(s.side[i]); hipEventDestroy(s.ev_join[i]); }
-    if (s.ev_fork) hipEventDestroy(s.ev_fork);
 }
 // the side stream's work happens-before everything enqueued on the context's stream from here on
 int join_side(vpt_renderer *r) {
@@ -852,7 +838,7 @@ int classes_build(vpt_renderer *r, const float *mvp_inverse) {
     const int n = (int)cls.size(), s = c.stage_next;
     HIP_TRY(hipSetDevice(r->ctx->device));
     HIP_TRY(c.staging[s].reserve((size_t)n, r->ctx->stream));   // (the copies out of it travel on that stream)
-    if (!c.staged[s]) HIP_TRY(hipEventCreateWithFlags(&c.staged[s], hipEventDisableTiming));
+    if (!c.staged[s]) HIP_TRY(c.staged[s].create(hipEventDisableTiming));
     else HIP_TRY(hipEventSynchronize(c.staged[s]));            // the copy out of this buffer two builds ago: long done (no wait in practice)
     uint32_t *list = c.staging[s];
     int nh = 0, nm = 0;
@@ -1067,7 +1053,18 @@ extern "C" int vpt_renderer_set_profiling(vpt_renderer *r, int enabled) {
     r->profiling = enabled != 0;
     r->profile_every = enabled > 1 ? enabled : 1;   // enabled = n > 1: every n-th launch only (events cost ~7 us per launch)
     r->profile_seq = 0;
-    r->events_used = 0; r->side_events_used = 0;
+    r->timing.rewind(); r->side_timing.rewind();
+    return VPT_OK;
+}
+// the elapsed time and the launches of the pairs taken since the last vpt_renderer_set_profiling; the stream they were recorded on is idle
+static int profile_sum(const EventPairs &pairs, double *total_ms, uint32_t *launches) {
+    double sum = 0.0; uint32_t n = 0;
+    for (const EventPairs::Pair *p = pairs.first(); p; p = pairs.after(p)) {
+        float ms = 0.0f;
+        HIP_TRY(hipEventElapsedTime(&ms, p->t0, p->t1));
+        sum += (double)ms; n += p->launches;
+    }
+    *total_ms = sum; *launches = n;
     return VPT_OK;
 }
 extern "C" int vpt_renderer_profile_side(vpt_renderer *r, double *total_ms, uint32_t *launches) {
@@ -1075,29 +1072,13 @@ extern "C" int vpt_renderer_profile_side(vpt_renderer *r, double *total_ms, uint
     HIP_TRY(hipSetDevice(r->ctx->device));
     VPT_TRY(join_side(r));
     HIP_TRY(hipStreamSynchronize(r->ctx->stream));
-    double sum = 0.0;
-    for (size_t i = 0; i < r->side_events_used; i++) {
-        float ms = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&ms, r->side_events[i].first, r->side_events[i].second));
-        sum += (double)ms;
-    }
-    *total_ms = sum; *launches = (uint32_t)r->side_events_used;
-    return VPT_OK;
+    return profile_sum(r->side_timing, total_ms, launches);      // (a side pair brackets one launch)
 }
 extern "C" int vpt_renderer_profile(vpt_renderer *r, double *total_ms, uint32_t *launches) {
     if (!r || !total_ms || !launches) return fail(VPT_ERR_INVALID, "null argument");
     HIP_TRY(hipSetDevice(r->ctx->device));
     HIP_TRY(hipStreamSynchronize(r->ctx->stream));
-    double sum = 0.0;
-    for (size_t i = 0; i < r->events_used; i++) {
-        float ms = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&ms, r->events[i].first, r->events[i].second));
-        sum += (double)ms;
-    }
-    uint32_t n = 0;
-    for (size_t i = 0; i < r->events_used; i++) n += r->event_launches[i];
-    *total_ms = sum; *launches = n;
-    return VPT_OK;
+    return profile_sum(r->timing, total_ms, launches);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1167,27 +1148,20 @@ extern "C" int vpt_probe_stream_read(vpt_context *c, size_t nbytes, int iteratio
     HIP_TRY(buf.alloc(n16));
     HIP_TRY(sink.alloc(1));
     HIP_TRY(hipMemsetAsync(buf, 0, n16 * 16, c->stream));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    Event e0, e1;
     float ms = 0.0f;
-    auto timed = [&]() -> int {
-        HIP_TRY(hipEventCreate(&e0));
-        HIP_TRY(hipEventCreate(&e1));
-        dim3 grid(256 * 16);                                  // 16 workgroups per CU
-        hipLaunchKernelGGL(k_stream_read, grid, dim3(VPT_BLOCK), 0, c->stream, buf.get(), n16, sink.get());    // warm-up
-        HIP_TRY(hipEventRecord(e0, c->stream));
-        for (int i = 0; i < iterations; i++) {
-            hipLaunchKernelGGL(k_stream_read, grid, dim3(VPT_BLOCK), 0, c->stream, buf.get(), n16, sink.get());
-            HIP_TRY(hipGetLastError());
-        }
-        HIP_TRY(hipEventRecord(e1, c->stream));
-        HIP_TRY(hipEventSynchronize(e1));
-        HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-        return VPT_OK;
-    };
-    const int rc = timed();                                   // (the events are destroyed whichever way it ends)
-    if (e0) hipEventDestroy(e0);
-    if (e1) hipEventDestroy(e1);
-    VPT_TRY(rc);
+    HIP_TRY(e0.create());
+    HIP_TRY(e1.create());
+    dim3 grid(256 * 16);                                      // 16 workgroups per CU
+    hipLaunchKernelGGL(k_stream_read, grid, dim3(VPT_BLOCK), 0, c->stream, buf.get(), n16, sink.get());    // warm-up
+    HIP_TRY(hipEventRecord(e0, c->stream));
+    for (int i = 0; i < iterations; i++) {
+        hipLaunchKernelGGL(k_stream_read, grid, dim3(VPT_BLOCK), 0, c->stream, buf.get(), n16, sink.get());
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(e1, c->stream));
+    HIP_TRY(hipEventSynchronize(e1));
+    HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
     *gb_per_s = (double)(n16 * 16) * iterations / ((double)ms * 1e-3) / 1e9;
     return VPT_OK;
 }

@@ -18,6 +18,8 @@
 // argument; launch_variant below is its use for a renderer's sampling pass.
 // vpt_buffers.h holds DevBuf<T> / PinnedBuf<T>, the owners of device and pinned host memory: the objects below own their memory through such
 // members and everything else in them has a default member initialiser, so `new` builds a valid object and `delete` frees all of it.
+// vpt_handles.h holds their siblings for the other two resources: Event and Stream, the owners of a HIP event and of a HIP stream, and
+// EventPairs, the pool of timing event pairs behind vpt_renderer_set_profiling.  The destroy functions leave everything idle and `delete`.
 // Nothing device-side crosses a translation unit: a kernel is compiled by the unit that names it (the three MCM units share one header).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -28,6 +30,7 @@
 #include <string.h>
 #include <algorithm>
 #include <cmath>
+#include <memory>
 #include <string>
 #include <utility>
 #include <vector>
@@ -35,6 +38,7 @@
 #include "../../include/vpt.h"
 #include "vpt_kernels.h"
 #include "vpt_buffers.h"
+#include "vpt_handles.h"
 
 // ---------------------------------------------------------------------------------------------
 // errors
@@ -50,9 +54,9 @@ char *vpt_error_buffer(void);                                                   
 // ---------------------------------------------------------------------------------------------
 struct vpt_tonemapper;
 struct vpt_context {
-    int device;
-    hipStream_t stream;
-    bool owns_stream;
+    int device = 0;
+    hipStream_t stream = nullptr;                // the stream everything is enqueued on: `own`, or the caller's (vpt_context_create_on_stream)
+    Stream own;
     std::vector<vpt_tonemapper *> tonemappers;   // live tone mappers: a destroyed renderer is unbound from them
     std::vector<struct vpt_renderer *> renderers; // live renderers: a destroyed volume is unbound from them
 };
@@ -107,7 +111,7 @@ struct TileClasses {
     // parameter changed, the camera did not) re-uses them — no classification, no upload (classes_build)
     bool built = false; float built_mvp[16] = {}; int built_geom[6] = {};
     // uploads go through two pinned staging buffers in turn, no host wait: staged[i] = the copy out of staging[i] has been enqueued and completes
-    PinnedBuf<uint32_t> staging[2]; hipEvent_t staged[2] = {}; int stage_next = 0;
+    PinnedBuf<uint32_t> staging[2]; Event staged[2]; int stage_next = 0;
     bool stale = false, stale_fast = false;   // MISS tiles' position / transmittance arrays are behind; the pass that left them ran the fast variant
     DevBuf<unsigned long long> violations;
     // the accumulating ray marchers (MIP, EAM, ISO, MCS, Depth): see marcher_track
@@ -144,8 +148,8 @@ struct Deal {
     bool operator!=(const Deal &o) const { return !(*this == o); }
 };
 struct StreamSet {
-    hipStream_t side[VPT_MAX_SPLIT - 1] = {};
-    hipEvent_t ev_fork = nullptr, ev_join[VPT_MAX_SPLIT - 1] = {};
+    Stream side[VPT_MAX_SPLIT - 1];
+    Event ev_fork, ev_join[VPT_MAX_SPLIT - 1];
     bool dirty = true;             // the context's stream has enqueued work the side streams have not waited for
     Deal last;                     // the deal of the last launch since the last join (a join resets it)
     bool busy() const { return last.ranges >= 2; }   // the side streams may hold work the context's stream has not joined
@@ -184,7 +188,7 @@ struct vpt_renderer {
     bool target_is_callers = false;   // render_target was set by vpt_renderer_set_render_target (not by the gather pipeline)
     bool no_split = false;         // set while a frame sequence is being captured into a hipGraph (one stream only)
     bool bucket_call = false;      // inside vpt_renderer_play_into*: the passes into the caller's bucket may use every stream, the call joins them before it returns
-    hipEvent_t *stop_events = nullptr;   // gather pipeline: event i is attached to range i's launch (hipExtLaunchKernel stop event: the
+    const Event *stop_events = nullptr;  // gather pipeline: event i is attached to range i's launch (hipExtLaunchKernel stop event: the
     bool stop_used = false;        // dispatch packet's own completion signal, no barrier packet behind the kernel)
     int split = 1; bool split_auto = true;   // split_auto: the stream count is the library's default and follows the launch size (split_for)
     StreamSet streams;
@@ -204,11 +208,9 @@ struct vpt_renderer {
     DevBuf<uint8_t> scratch;       // vpt_renderer_read: the de-tiled image, grown on demand
     bool profiling = false;
     int profile_every = 1; uint64_t profile_seq = 0;   // time every n-th launch of the dominant kernel
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
-    std::vector<uint32_t> event_launches;   // kernel launches covered by each event pair (1, or the frames of a graph replay)
-    size_t events_used = 0;
-    // the same around the first launch a pass puts on a SIDE stream (tile classes: the MISS-tile kernel), for the passes `events` samples
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> side_events; size_t side_events_used = 0; bool timed_now = false;
+    EventPairs timing;             // the timed launches' event pairs; a pair's launches: 1, or the frames of a graph replay / a fused sequence
+    // the same around the first launch a pass puts on a SIDE stream (tile classes: the MISS-tile kernel), for the passes `timing` samples
+    EventPairs side_timing; bool timed_now = false;
 };
 
 struct vpt_tonemapper {
@@ -245,14 +247,13 @@ static inline size_t frame_elem(int kind) {
 // shared host functions (vpt_core.hip unless noted)
 // ---------------------------------------------------------------------------------------------
 int ensure_split_streams(vpt_renderer *r);          // creates the side streams r->split asks for, if they do not exist yet
-void destroy_split_streams(vpt_renderer *r);
 int join_side(vpt_renderer *r);                     // the side streams' work happens-before everything enqueued on the context's stream from here on
 int streams_deal(vpt_renderer *r, Deal d);          // before the launches of a deal: join and fork as the deal needs (StreamSet)
 int make_args(vpt_renderer *r, const vpt_uniforms *u, bool need_volume, PassArgs *a);
 int volume_create(vpt_context *c, int w, int h, int d, int format, bool zero_fill, vpt_volume **out);   // vpt_volume_create; zero_fill = false: the caller writes every texel
 int volume_finish_derived(const vpt_volume *src, vpt_volume *d, vpt_volume **out);   // the shared tail of the derived volumes (gradient, window, reduce, smooth, rank, components' keep and label): finalize and hand out
 int volume_records(vpt_volume *v);                  // builds the column records of a finalized one-channel byte volume if they are not current
-hipError_t create_overlapping_stream(hipStream_t *out, const vpt_renderer *r);   // overlaps r's context stream and side streams
+hipError_t create_overlapping_stream(Stream *out, const vpt_renderer *r);   // overlaps r's context stream and side streams
 bool invert_matrix(const float *m, double out[4][4]);               // column-major float matrix -> its inverse (double); false: singular
 int classes_build(vpt_renderer *r, const float *mvp_inverse);       // tile lists of `mvp_inverse` on the device (classify_tiles)
 void play_graph_free(PlayGraph *g);                                 // vpt_render.hip
@@ -347,7 +348,7 @@ static inline hipStream_t range_stream(const vpt_renderer *r, int i) { return i 
 template <typename K>
 static void launch_range(K kernel, vpt_renderer *r, dim3 grid, dim3 block, size_t lds, hipStream_t stream, const PassArgs &a, int range) {
     if (r->stop_events) {
-        hipExtLaunchKernelGGL(kernel, grid, block, (uint32_t)lds, stream, nullptr, r->stop_events[range], 0, a);
+        hipExtLaunchKernelGGL(kernel, grid, block, (uint32_t)lds, stream, nullptr, r->stop_events[range].get(), 0, a);
         r->stop_used = true;
     } else {
         hipLaunchKernelGGL(kernel, grid, block, lds, stream, a);
@@ -431,21 +432,18 @@ static int launch_variant(vpt_renderer *r, const PassArgs &a, KernelOf kernel_of
                                     [&] { return fail(VPT_ERR_INVALID, "no sampling kernel for variant %d", v); });
 }
 
+// profiling: the pair of events for the launch about to be enqueued, or null — profiling is off, the launch is not the n-th
+// (vpt_renderer_set_profiling(n)), or the pair could not be created: the launch then goes untimed
+static inline EventPairs::Pair *profile_take(vpt_renderer *r, uint32_t launches) {
+    if (!r->profiling || (r->profile_seq++ % (uint64_t)r->profile_every) != 0) return nullptr;
+    return r->timing.take(launches);
+}
 struct Timed {   // HIP events around the dominant kernel (or around one graph replay of `launches` of them)
-    vpt_renderer *r; bool on; size_t idx;
-    Timed(vpt_renderer *r_, bool dominant, uint32_t launches = 1) : r(r_), on(r_->profiling && dominant), idx(0) {
-        if (on) on = (r->profile_seq++ % (uint64_t)r->profile_every) == 0;
-        if (!on) return;
-        if (r->events_used == r->events.size()) {
-            hipEvent_t a, b;
-            if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) { on = false; return; }
-            r->events.push_back({ a, b });
-            r->event_launches.push_back(1);
-        }
-        idx = r->events_used++;
-        r->event_launches[idx] = launches;
-        hipEventRecord(r->events[idx].first, r->ctx->stream);
+    vpt_renderer *r; const EventPairs::Pair *pair;
+    Timed(vpt_renderer *r_, bool dominant, uint32_t launches = 1) : r(r_), pair(dominant ? profile_take(r_, launches) : nullptr) {
+        if (!pair) return;
+        hipEventRecord(pair->t0, r->ctx->stream);
         r->timed_now = true;
     }
-    ~Timed() { if (on) { hipEventRecord(r->events[idx].second, r->ctx->stream); r->timed_now = false; } }
+    ~Timed() { if (pair) { hipEventRecord(pair->t1, r->ctx->stream); r->timed_now = false; } }
 };

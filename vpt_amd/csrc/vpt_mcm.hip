@@ -130,14 +130,10 @@ static int mcm_classify(vpt_renderer *r, const vpt_uniforms *u) {
 // profiling (inside a Timed pair only): starts on `s` the pair vpt_renderer_profile_side reads, around the first launch a pass puts
 // on a side stream; returns the event to record on `s` behind that launch, or null
 static hipEvent_t side_events_begin(vpt_renderer *r, hipStream_t s) {
-    if (!r->timed_now) return nullptr;
-    if (r->side_events_used == r->side_events.size()) {
-        hipEvent_t a0, a1;
-        if (hipEventCreate(&a0) == hipSuccess && hipEventCreate(&a1) == hipSuccess) r->side_events.push_back({ a0, a1 });
-    }
-    if (r->side_events_used == r->side_events.size()) return nullptr;
-    hipEventRecord(r->side_events[r->side_events_used].first, s);
-    return r->side_events[r->side_events_used++].second;
+    const EventPairs::Pair *pair = r->timed_now ? r->side_timing.take(1) : nullptr;
+    if (!pair) return nullptr;
+    hipEventRecord(pair->t0, s);
+    return pair->t1;
 }
 // one MCM pass (integrate, or render() = integrate + renderFrame) as list launches: the HIT tiles through k_mcm_integrate on the
 // context's stream, the MISS tiles through k_mcm_miss — with VPT_OPTION_SPLIT_STREAMS = K as K - 1 equal parts on the side streams,

@@ -370,7 +370,7 @@ struct vpt_gather {
     int rank = 0, world = 1;
     int root = -1;                     // -1: every rank receives the frame (all_gather); else only this rank does
     ncclComm_t_ comm = nullptr;
-    hipStream_t comm_stream = nullptr;
+    Stream comm_stream;
     size_t send_bytes = 0;             // W * local_h * 8
     // A ring of VPT_GATHER_RING send / receive buffers: frame k uses buffer k % ring.  Per frame the streams exchange ONE
     // event (kernel done -> the communication stream may send); the reverse edge (buffer free again -> the compute stream
@@ -378,7 +378,7 @@ struct vpt_gather {
     // the compute stream waits for it when it re-enters that half a whole ring later.  (With two buffers the reverse edge
     // was paid every frame: ~11 us of event traffic per frame at a 24 us kernel.)
     DevBuf<uint8_t> send[VPT_GATHER_RING], recv[VPT_GATHER_RING];
-    hipEvent_t rendered[2][VPT_MAX_SPLIT] = {}, gathered[2] = {};   // rendered: per tile-row range (stream) of a split pass
+    Event rendered[2][VPT_MAX_SPLIT], gathered[2];   // rendered: per tile-row range (stream) of a split pass
     uint64_t frames = 0;
     DevBuf<uint2> assembled;           // [H][W] RGBA16F scratch for read_frame
 };
@@ -427,16 +427,16 @@ extern "C" int vpt_gather_destroy(vpt_gather *g) {
     hipSetDevice(g->r->ctx->device);
     join_side(g->r);                                         // ranges of split passes still rendering into the ring
     hipStreamSynchronize(g->r->ctx->stream);
-    if (g->comm_stream) hipStreamSynchronize(g->comm_stream);
+    if (g->comm_stream) hipStreamSynchronize(g->comm_stream);   // everything is idle from here on: the order in which the members go is immaterial
     vpt_renderer_set_render_target(g->r, nullptr, 0);
     if (g->comm) g_rccl.CommDestroy(g->comm);
-    for (int b = 0; b < 2; b++) {
-        for (int i = 0; i < VPT_MAX_SPLIT; i++) if (g->rendered[b][i]) hipEventDestroy(g->rendered[b][i]);
-        if (g->gathered[b]) hipEventDestroy(g->gathered[b]);
-    }
-    if (g->comm_stream) hipStreamDestroy(g->comm_stream);
     delete g;
     return VPT_OK;
+}
+static void gather_abandon(vpt_gather *g) {   // of a gather that vpt_gather_create could not finish: the message of what failed outlives the destroy's calls
+    const std::string keep = vpt_error_buffer();
+    vpt_gather_destroy(g);
+    snprintf(vpt_error_buffer(), 512, "%s", keep.c_str());
 }
 extern "C" int vpt_gather_create(vpt_renderer *r, const void *id128, int rank, int world, vpt_gather **out) {
     if (!r || !id128 || !out) return fail(VPT_ERR_INVALID, "null argument");
@@ -444,49 +444,31 @@ extern "C" int vpt_gather_create(vpt_renderer *r, const void *id128, int rank, i
     if (r->G != world || r->g != rank) return fail(VPT_ERR_INVALID, "renderer is sharded %d/%d, gather asked for %d/%d", r->g, r->G, rank, world);
     VPT_TRY(rccl_load());
     HIP_TRY(hipSetDevice(r->ctx->device));
-    vpt_gather *g = new vpt_gather();
+    // the communication stream must overlap the streams the passes run on
+    VPT_TRY(ensure_split_streams(r));
+    VPT_TRY(join_side(r));
+    std::unique_ptr<vpt_gather, void (*)(vpt_gather *)> owner(new vpt_gather(), gather_abandon);   // an early return destroys what has been built
+    vpt_gather *g = owner.get();
     g->r = r; g->rank = rank; g->world = world;
     g->send_bytes = (size_t)r->W * r->local_h * 8;
-    int rc = VPT_OK;
-    hipError_t e;
-    {   // the communication stream must overlap the streams the passes run on
-        { int jr = ensure_split_streams(r); if (jr == VPT_OK) jr = join_side(r); if (jr != VPT_OK) { delete g; return jr; } }
-        hipStreamSynchronize(r->ctx->stream);
-        e = create_overlapping_stream(&g->comm_stream, r);
+    hipStreamSynchronize(r->ctx->stream);
+    HIP_TRY(create_overlapping_stream(&g->comm_stream, r));
+    for (int b = 0; b < 2; b++) {
+        for (int i = 0; i < VPT_MAX_SPLIT; i++) HIP_TRY(g->rendered[b][i].create(hipEventDisableTiming));
+        HIP_TRY(g->gathered[b].create(hipEventDisableTiming));
     }
-    for (int b = 0; b < 2 && e == hipSuccess; b++) {
-        for (int i = 0; i < VPT_MAX_SPLIT && e == hipSuccess; i++) e = hipEventCreateWithFlags(&g->rendered[b][i], hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&g->gathered[b], hipEventDisableTiming);
+    for (int b = 0; b < VPT_GATHER_RING; b++) {
+        HIP_TRY(g->send[b].alloc(g->send_bytes));
+        HIP_TRY(g->recv[b].alloc(g->send_bytes * world));
+        HIP_TRY(hipMemset(g->send[b], 0, g->send_bytes));
     }
-    for (int b = 0; b < VPT_GATHER_RING && e == hipSuccess; b++) {
-        e = g->send[b].alloc(g->send_bytes);
-        if (e == hipSuccess) e = g->recv[b].alloc(g->send_bytes * world);
-        if (e == hipSuccess) e = hipMemset(g->send[b], 0, g->send_bytes);
-    }
-    if (e == hipSuccess) e = g->assembled.alloc((size_t)r->W * r->H);
-    if (e != hipSuccess) rc = fail(VPT_ERR_HIP, "gather buffers: %s", hipGetErrorString(e));
-    if (rc == VPT_OK) {
-        ncclUniqueId_ id;
-        memcpy(&id, id128, sizeof(id));
-        int ne = g_rccl.CommInitRank(&g->comm, world, id, rank);
-        if (ne != 0) { g->comm = nullptr; rc = fail(VPT_ERR_HIP, "ncclCommInitRank failed: %s", g_rccl.GetErrorString(ne)); }
-    }
-    if (rc != VPT_OK) { char keep[512]; strncpy(keep, vpt_error_buffer(), sizeof(keep)); keep[511] = 0; vpt_gather_destroy(g); strncpy(vpt_error_buffer(), keep, 512); return rc; }
-    *out = g;
+    HIP_TRY(g->assembled.alloc((size_t)r->W * r->H));
+    ncclUniqueId_ id;
+    memcpy(&id, id128, sizeof(id));
+    const int ne = g_rccl.CommInitRank(&g->comm, world, id, rank);
+    if (ne != 0) { g->comm = nullptr; return fail(VPT_ERR_HIP, "ncclCommInitRank failed: %s", g_rccl.GetErrorString(ne)); }
+    *out = owner.release();
     return VPT_OK;
-}
-// per-launch timing (vpt_renderer_set_profiling) applies to the pipeline's kernel as well
-static void profile_events(vpt_renderer *r, hipEvent_t *t0, hipEvent_t *t1) {
-    *t0 = *t1 = nullptr;
-    if (!(r->profiling && (r->profile_seq++ % (uint64_t)r->profile_every) == 0)) return;
-    if (r->events_used == r->events.size()) {
-        hipEvent_t e0, e1;
-        if (hipEventCreate(&e0) != hipSuccess) return;
-        if (hipEventCreate(&e1) != hipSuccess) { hipEventDestroy(e0); return; }
-        r->events.push_back({ e0, e1 }); r->event_launches.push_back(1);
-    }
-    *t0 = r->events[r->events_used].first; *t1 = r->events[r->events_used].second;
-    r->event_launches[r->events_used] = 1; r->events_used++;
 }
 // The schedule of one frame of the gather pipeline as a PURE function of (frame index, rank, world, root): which ring buffer,
 // which event edges, where the kernel renders, which RCCL operations.  gather_enqueue_frame executes exactly this plan, and
@@ -531,7 +513,7 @@ extern "C" int vpt_gather_plan_recv(const vpt_gather_step *st, int rank, int i, 
     *peer = p; *offset = (uint64_t)p * send_bytes;
     return VPT_OK;
 }
-static int gather_enqueue_frame(vpt_gather *g, PassArgs &a, hipEvent_t t0, hipEvent_t t1, uint32_t fused_passes);
+static int gather_enqueue_frame(vpt_gather *g, PassArgs &a, const EventPairs::Pair *timed, uint32_t fused_passes);
 extern "C" int vpt_gather_render(vpt_gather *g, const vpt_uniforms *u) {
     if (!g || !u) return fail(VPT_ERR_INVALID, "null argument");
     vpt_renderer *r = g->r;
@@ -539,16 +521,14 @@ extern "C" int vpt_gather_render(vpt_gather *g, const vpt_uniforms *u) {
     if (r->kind == VPT_RENDERER_MIP || r->kind == VPT_RENDERER_EAM) VPT_TRY(check_step(u));
     PassArgs a;
     VPT_TRY(make_args(r, u, true, &a));
-    hipEvent_t t0, t1;
-    profile_events(r, &t0, &t1);
-    VPT_TRY(gather_enqueue_frame(g, a, t0, t1, 0));
+    VPT_TRY(gather_enqueue_frame(g, a, profile_take(r, 1), 0));     // (per-launch timing applies to the pipeline's kernel as well)
     if (r->kind == VPT_RENDERER_MCM) r->samples_host += r->valid_pixels * (uint64_t)u->steps;
     r->warmed = true;
     return VPT_OK;
 }
-// one frame of the gather pipeline on (compute stream cs, communication stream)
+// one frame of the gather pipeline on (compute stream cs, communication stream); timed: the pair of events around its kernel, or null
 // fused_passes > 0: the frame is the result of that many MCM passes run by one k_mcm_multi launch (a carries the frame table)
-static int gather_enqueue_frame(vpt_gather *g, PassArgs &a, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr, uint32_t fused_passes = 0) {
+static int gather_enqueue_frame(vpt_gather *g, PassArgs &a, const EventPairs::Pair *timed, uint32_t fused_passes) {
     vpt_renderer *r = g->r;
     hipStream_t cs = r->ctx->stream;
     if ((size_t)r->W * r->local_h * 8 != g->send_bytes || r->G != g->world || r->g != g->rank)
@@ -566,13 +546,13 @@ static int gather_enqueue_frame(vpt_gather *g, PassArgs &a, hipEvent_t t0 = null
     a.render = st.in_place ? (uint2 *)((char *)g->recv[b].get() + st.render_offset) : (uint2 *)g->send[b].get();
     r->render_target = a.render;                                             // vpt_renderer_read(RENDER) returns the last frame's rows
     a.tm_table = nullptr; r->tm_valid = false;                               // (a fused tone mapper follows the renderer's own buffer only)
-    if (t0) HIP_TRY(hipEventRecord(t0, cs));
+    if (timed) HIP_TRY(hipEventRecord(timed->t0, cs));
     if (fused_passes) {
         VPT_TRY(mcm_multi(r, a, fused_passes, nullptr));
     } else {
         VPT_TRY(launch_fused(r, a));
     }
-    if (t1) HIP_TRY(hipEventRecord(t1, cs));
+    if (timed) HIP_TRY(hipEventRecord(timed->t1, cs));
     // A split pass (VPT_OPTION_SPLIT_STREAMS): the communication stream waits for every range of the pass's deal; the ranges' streams are
     // NOT joined, so range i of the next frame (same deal) starts behind range i of this one, whatever the other ranges and the gather are doing.
     const bool rode = r->stop_used;                                          // the events were attached to the launches themselves
@@ -620,16 +600,11 @@ extern "C" int vpt_gather_play(vpt_gather *g, const vpt_uniforms *base, const fl
         // `count` passes in one launch, then ONE gather of the resulting frame
         if (r->kind != VPT_RENDERER_MCM) return fail(VPT_ERR_UNSUPPORTED, "fused passes are implemented for the MCM renderer only");
         VPT_TRY(play_upload_table(r, frame_vars, count, false, &a));
-        hipEvent_t t0 = nullptr, t1 = nullptr;
-        profile_events(r, &t0, &t1);
-        if (t0) r->event_launches[r->events_used - 1] = (uint32_t)count;
-        VPT_TRY(gather_enqueue_frame(g, a, t0, t1, (uint32_t)count));
+        VPT_TRY(gather_enqueue_frame(g, a, profile_take(r, (uint32_t)count), (uint32_t)count));
     }
     for (int i = 0; i < count && mode == VPT_PLAY_EAGER; i++) {
         PassArgs f = frame_args(a, v[i]);
-        hipEvent_t t0 = nullptr, t1 = nullptr;
-        profile_events(r, &t0, &t1);
-        VPT_TRY(gather_enqueue_frame(g, f, t0, t1, 0));
+        VPT_TRY(gather_enqueue_frame(g, f, profile_take(r, 1), 0));
     }
     HIP_TRY(hipGetLastError());
     r->warmed = true;
