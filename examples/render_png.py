@@ -71,6 +71,13 @@ def main():
                                                                                  "(squared voxels; TO may be left out: no upper end); the default is 0,")
     how.add_argument("--distance-channel", type=int, default=None, metavar="STEPS", help="the second channel is the distance, STEPS (1 .. 256) rows of the transfer "
                                                                                        "function a voxel, instead of a gradient")
+    grid = ap.add_mutually_exclusive_group()
+    grid.add_argument("--resample", default=None, metavar="W,H,D", help="resample the volume to W x H x D texels on the device, behind the window and in front of --rank")
+    grid.add_argument("--spacing", default=None, metavar="SX,SY,SZ", help="the voxel spacing: resample the volume to cubic voxels on the device (see --voxel-pitch)")
+    ap.add_argument("--voxel-pitch", type=float, default=None, metavar="P", help="edge of the cubic voxels of --spacing (default: the smallest spacing; "
+                    "--pitch is the camera's)")
+    ap.add_argument("--resample-mode", default="filtered", choices=["filtered", "nearest"], help="filtered: linear interpolation / area average in integers "
+                    "(R8, RG8, R16, RG16); nearest: texels are copied (labels and masks, every unpacked format)")
     ap.add_argument("--smooth", type=int, default=None, metavar="N", help="binomial 3 x 3 x 3 smoothing passes (1 .. 8) on the device, behind the window (R8 / R16 volumes)")
     ap.add_argument("--reduce", type=int, default=None, metavar="N", help="reduce the volume N times to half its resolution on the device, behind the smoothing")
     ap.add_argument("--yaw", type=float, default=0.6)
@@ -96,10 +103,15 @@ def main():
         else:
             first, _, last = (a.distance_within or '0,').partition(',')
             distance = {'lo': lo, 'hi': hi, 'seeds': a.distance_seeds, 'mode': 'within', 'from': int(first), 'to': int(last) if last.strip() else None}
+    resample = None
+    if a.resample is not None:
+        resample = {'size': [int(x) for x in a.resample.split(',')], 'mode': a.resample_mode}
+    elif a.spacing is not None:
+        resample = {'spacing': [float(x) for x in a.spacing.split(',')], 'pitch': a.voxel_pitch, 'mode': a.resample_mode}
     rc = vpt_amd.RenderingContext({'resolution': (a.width, a.height), 'components': components, 'distance': distance, 'filter': a.filter, 'rng': GoldenRatioRng(),
                                    'gradient': a.gradient, 'gradientGain': a.gradient_gain,
                                    'window': None if window == 'auto' else window, 'windowFormat': a.window_format,
-                                   'rank': a.rank, 'rankPasses': a.rank_passes, 'smooth': a.smooth, 'reduce': a.reduce})
+                                   'rank': a.rank, 'rankPasses': a.rank_passes, 'smooth': a.smooth, 'reduce': a.reduce, 'resample': resample})
     rc.resize(a.width, a.height)
     rc.gl.getExtension('EXT_texture_norm16')                      # 16-bit volumes are taken
     if a.volume.endswith(".bvp"):

@@ -331,6 +331,41 @@ VPT_API int vpt_distance_channel(vpt_distance *dist, int steps, vpt_volume **out
 VPT_API int vpt_distance_profile(vpt_distance *dist, double *ms);
 VPT_API int vpt_distance_destroy(vpt_distance *dist);
 
+/* ---- resampling to any grid size on the device (extension; DESIGN.md "Resampling") */
+/* The step in front of everything that counts voxels (the rank filters' 3 x 3 x 3 box, components, distances "in voxel units"): a volume of
+ * anisotropic voxels is brought to an isotropic grid, one that is too large or too coarse to a chosen size.  The result is a new, finalized
+ * volume of width x height x depth texels (each 1 .. 4096; otherwise VPT_ERR_INVALID) in src's format, on src's context, with src's filter.
+ * The cube the volume occupies does not change, only the grid inside it.  Any other `mode`: VPT_ERR_INVALID.  Below n is a source axis
+ * length, N the matching result axis length, X a result index; every division is a floor division of non-negative integers.
+ *   VPT_RESAMPLE_NEAREST: source index j = ((2 X + 1) n) div (2 N) per axis, the texel whose cell holds the centre of result texel X; the
+ *   texel's bits are copied (NaN payloads included).  Every unpacked format, the ten vpt_volume_reduce takes; packed formats:
+ *   VPT_ERR_UNSUPPORTED, naming the format.  The mode for label and mask volumes (vpt_components_label, vpt_distance_channel, any `fill`).
+ *   VPT_RESAMPLE_FILTERED: R8, RG8, R16 and RG16, per channel, on whole unsigned codes; every other format: VPT_ERR_UNSUPPORTED, naming it.
+ *   Each axis has non-negative integer tap weights with a constant sum S_axis, chosen by that axis alone:
+ *     N >= n (the axis grows or stays): linear interpolation at the renderer's texel alignment, u = s n - 0.5 at s = (X + 0.5) / N, clamped
+ *       to the edge.  num = (2 X + 1) n - N, D = 2 N.  num <= 0: one tap, index 0, weight D.  num >= (n - 1) D: one tap, index n - 1,
+ *       weight D.  Otherwise i = num div D, f = num mod D and the taps are (i, D - f), (i + 1, f).  S_axis = 2 N.  N = n is the identity.
+ *     N < n (the axis shrinks): the area average, nothing aliases and no source texel is dropped.  Source texel j has the weight
+ *       w_j = min((X + 1) n, (j + 1) N) - max(X n, j N) for j = (X n) div N .. ((X + 1) n - 1) div N; every w_j is positive.  S_axis = n.
+ *   With S = S_x S_y S_z and SUM = the sum over all taps of w_x w_y w_z code:   out = (2 SUM + S) div (2 S)
+ *   one rounding, halves up, in 64-bit unsigned integers (S <= 8192^3 = 2^39, SUM <= 65535 S < 2^55, 2 SUM + S < 2^57).  The sum is exact,
+ *   so the result does not depend on the order of the axes.  It lies within [min, max] of the source; a constant volume stays as it is;
+ *   resampling the flipped volume gives the flipped result.  Halving every axis of a volume whose axes are all even equals
+ *   vpt_volume_reduce byte for byte (weights N, N and (sum + 4) >> 3); on an odd axis the two differ: reduce clamps and counts the last
+ *   texel twice, this averages areas.
+ * vpt_amd.resample_texels states both modes in numpy; vpt_amd.isotropic_shape gives the size for cubic voxels from a spacing.
+ * The result is enqueued on the context's stream behind any upload into src; src is not changed and may be destroyed afterwards.  The
+ * result is an ordinary volume (every renderer, set_filter, upload_block, read_block, and every volume operation, this one included).
+ * Two runs give identical bytes.  A result or a workspace (FILTERED: 4 bytes per channel of width x src height x src depth texels, freed
+ * when the call returns) that cannot be allocated: VPT_ERR_HIP, nothing is leaked. */
+#define VPT_RESAMPLE_NEAREST  0
+#define VPT_RESAMPLE_FILTERED 1
+VPT_API int vpt_volume_resample(vpt_volume *src, int width, int height, int depth, int mode, vpt_volume **out);
+/* (for measurements) the same, and the milliseconds of the row pass and of the plane pass of FILTERED in ms[VPT_RESAMPLE_PHASES], the stream
+ * drained after each (NEAREST: zeros) */
+#define VPT_RESAMPLE_PHASES 2
+VPT_API int vpt_volume_resample_timed(vpt_volume *src, int width, int height, int depth, int mode, vpt_volume **out, double *ms);
+
 /* ---- renderer: AbstractRenderer.js:17-116 and the four subclasses */
 /* new R(gl, volume, camera, environmentTexture, {resolution}) — AbstractRenderer.js:17-49; width != height is the
  * documented extension (uInverseResolution = (1/W, 1/H)).  Buffers are allocated as in _rebuildBuffers :78-92. */

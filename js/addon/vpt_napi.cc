@@ -210,6 +210,15 @@ static napi_value VolumeRank(napi_env env, napi_callback_info info) {
     VPT_CHECK(vpt_volume_rank(v, op, passes, &out));
     return make_external(env, out);
 }
+// volumeResample(volume, width, height, depth, mode) -> a new volume handle: the volume on a grid of that size, mode VPT_RESAMPLE_*
+static napi_value VolumeResample(napi_env env, napi_callback_info info) {
+    napi_value a[5]; vpt_volume *v; int32_t w, h, d, mode;
+    if (!get_args(env, info, 5, a) || !get_handle(env, a[0], &v) || !get_i32(env, a[1], &w) || !get_i32(env, a[2], &h) || !get_i32(env, a[3], &d) ||
+        !get_i32(env, a[4], &mode)) return nullptr;
+    vpt_volume *out = nullptr;
+    VPT_CHECK(vpt_volume_resample(v, w, h, d, mode, &out));
+    return make_external(env, out);
+}
 // volumeRange(volume) -> [lo, hi]: the smallest and the largest code or value
 static napi_value VolumeRange(napi_env env, napi_callback_info info) {
     napi_value a[1]; vpt_volume *v;
@@ -679,7 +688,7 @@ static napi_value Init(napi_env env, napi_value exports) {
     EXPORT("volumeDeriveGradient", VolumeDeriveGradient); EXPORT("volumeReadBlock", VolumeReadBlock); EXPORT("volumeHistogram", VolumeHistogram);
     CONST(VPT_GRADIENT_CENTRAL); CONST(VPT_GRADIENT_SOBEL);
     EXPORT("volumeWindow", VolumeWindow); EXPORT("volumeRange", VolumeRange); EXPORT("volumeCodeHistogram", VolumeCodeHistogram);
-    EXPORT("volumeReduce", VolumeReduce); EXPORT("volumeSmooth", VolumeSmooth); EXPORT("volumeRank", VolumeRank);
+    EXPORT("volumeReduce", VolumeReduce); EXPORT("volumeSmooth", VolumeSmooth); EXPORT("volumeRank", VolumeRank); EXPORT("volumeResample", VolumeResample);
     EXPORT("volumeComponents", VolumeComponents); EXPORT("componentsInfo", ComponentsInfo); EXPORT("componentsList", ComponentsList);
     EXPORT("componentsRanks", ComponentsRanks); EXPORT("componentsKeep", ComponentsKeep); EXPORT("componentsLabel", ComponentsLabel);
     EXPORT("componentsDestroy", ComponentsDestroy);

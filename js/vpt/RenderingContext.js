@@ -19,6 +19,10 @@
 //   them (seeds 'rest') (Volume.distance).  'within' runs behind `components` mode 'keep' and in front of the smoothing: the codes with
 //   from <= d2 <= to (squared voxels; to null: no upper end) stay, everything else becomes `fill`.  'channel' runs where the gradient runs:
 //   the second channel is min(isqrt(steps^2 d2), M); it cannot be combined with `gradient` or with `components` mode 'label'
+//   resample: null (default), { size: [w, h, d] } or { spacing: [sx, sy, sz], pitch }, plus mode: 'filtered' (default) | 'nearest': the volume
+//   is resampled to that grid, or to cubic voxels of edge `pitch` (default: the smallest spacing), behind the window and in front of the rank
+//   filter, so rank, components and distance see the resampled grid (Volume.resample, Volume.isotropic); a volume whose format the mode does
+//   not take is left as it is
 const { EventTarget, CustomEvent } = require('./EventTarget.js');
 const { Context } = require('./Context.js');
 const { OrbitCameraAnimator } = require('./animators.js');
@@ -27,6 +31,7 @@ const { Volume, gradientArguments, windowFormatBits, checkPasses, checkLevels, r
 const { native } = require('./native.js');
 const { checkConnectivity, checkRange, checkMinVoxels, checkKeep } = require('./components.js');
 const { checkSeeds, checkSteps, checkWithin, checkDistanceRange } = require('./distance.js');
+const { checkResampleMode, checkResampleSize, checkSpacing } = require('./resample.js');
 const { RendererFactory } = require('./renderers/RendererFactory.js');
 const { ToneMapperFactory } = require('./tonemappers/ToneMapperFactory.js');
 
@@ -61,6 +66,7 @@ constructor(options) {
             throw new Error("distance mode 'channel' and components mode 'label' both write the second channel: name one of them");
         }
     }
+    this.resample = RenderingContext._resampleSpec(options.resample);                // likewise
     this.gl = new Context(options.device || 0);                                   // initGL(), :61-105
     this.environmentTexture = { data: new Uint8Array([255, 255, 255, 255]), width: 1, height: 1 };   // :90-101
     this._rng = options.rng;
@@ -109,6 +115,12 @@ async setVolume(reader) {                                                       
         if (this.window !== null) {                                                    // the transfer function's x axis is [lo, hi]
             const source = this.volume, w = this._windowOf(source);
             this.volume = source.window({ lo: w[0], hi: w[1], format: this.windowFormat });
+            source.destroy();
+        }
+        if (this.resample !== null && RenderingContext._resampleTakes(this.volume, this.resample.mode)) {
+            const source = this.volume, spec = this.resample;
+            this.volume = spec.size !== null ? source.resample(spec.size[0], spec.size[1], spec.size[2], spec.mode)
+                : source.isotropic(spec.spacing, spec.pitch, spec.mode);
             source.destroy();
         }
         if (this.rank !== null) {
@@ -174,6 +186,33 @@ _deriveDistance(emit) {
     const found = source.distance(spec.lo, Math.min(spec.hi, largest), spec.seeds);
     try { this.volume = emit(found); } finally { found.destroy(); }
     source.destroy();
+}
+
+// the `resample` option with its defaults filled in, or null; throws for anything the contract does not take
+static _resampleSpec(spec) {
+    if (spec === undefined || spec === null) { return null; }
+    const known = ['size', 'spacing', 'pitch', 'mode'], given = k => spec[k] !== undefined && spec[k] !== null;
+    if (typeof spec !== 'object' || Array.isArray(spec) || !Object.keys(spec).every(k => known.includes(k)) || ('size' in spec) === ('spacing' in spec)) {
+        throw new Error("resample is null, { size: [w, h, d], mode } or { spacing: [sx, sy, sz], pitch, mode }, not " + JSON.stringify(spec));
+    }
+    const out = { size: null, spacing: null, pitch: null, mode: given('mode') ? spec.mode : 'filtered' };
+    checkResampleMode(out.mode);
+    if ('size' in spec) {
+        if (given('pitch')) { throw new Error("resample 'pitch' goes with 'spacing'"); }
+        if (!Array.isArray(spec.size) || spec.size.length !== 3) { throw new Error('resample size is [w, h, d], not ' + JSON.stringify(spec.size)); }
+        out.size = checkResampleSize(spec.size[0], spec.size[1], spec.size[2]);
+    } else {
+        const k = checkSpacing(spec.spacing, spec.pitch);
+        out.spacing = k[0]; out.pitch = k[1];
+    }
+    return out;
+}
+
+// does the mode take the volume's format?
+static _resampleTakes(volume, mode) {
+    const N = native(), fmt = volume.nativeFormat();
+    if (mode === 'filtered') { return fmt === N.VPT_FORMAT_R8 || fmt === N.VPT_FORMAT_RG8 || fmt === N.VPT_FORMAT_R16 || fmt === N.VPT_FORMAT_RG16; }
+    return !(fmt >= N.VPT_FORMAT_RGB565 && fmt <= N.VPT_FORMAT_RGB9_E5);
 }
 
 // the `distance` option with its defaults filled in, or null; throws for anything the contract does not take

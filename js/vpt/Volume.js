@@ -6,6 +6,7 @@ const { native } = require('./native.js');
 const R = require('./readers/readers.js');
 const { checkConnectivity, checkRange, checkMinVoxels, checkKeep } = require('./components.js');
 const { checkSeeds, checkSteps, checkRadius, checkWithin, checkDistanceRange } = require('./distance.js');
+const { checkResampleMode, checkResampleSize, isotropicShape } = require('./resample.js');
 const { RAWReader, GL_RED, GL_RG, GL_RGB, GL_RGBA, GL_UNSIGNED_BYTE, GL_FLOAT, GL_HALF_FLOAT, GL_BYTE } = R;
 
 // [type, format, internalFormat, native format name, channels in the file, element kind] of the formats keyed on all three: SNORM bytes
@@ -340,6 +341,22 @@ erode(passes) { return this.rank('erode', passes); }
 dilate(passes) { return this.rank('dilate', passes); }
 open(passes) { return this.rank('open', passes); }
 close(passes) { return this.rank('close', passes); }
+
+// ---- extension: resampling to any grid size (include/vpt.h; DESIGN.md "Resampling") ----
+// a new, ready volume in this volume's format and with its filter on a grid of width x height x depth texels (each 1 .. 4096) that fills the
+// same cube: mode 'filtered' (default; R8, RG8, R16, RG16) interpolates linearly along an axis that grows and averages areas along one that
+// shrinks, in integers with one rounding; 'nearest' (every unpacked format) copies the texel under each result texel's centre: the mode for
+// labels and masks; derived on the device; this volume is not changed
+resample(width, height, depth, mode) {
+    const code = checkResampleMode(mode !== undefined ? mode : 'filtered');
+    checkResampleSize(width, height, depth);
+    return this._sameFormat(native().volumeResample(this.texture, width, height, depth, code), { width, height, depth });
+}
+// resample() to cubic voxels of edge `pitch` (default: the smallest spacing) from this volume's voxel spacing = [sx, sy, sz]
+isotropic(spacing, pitch, mode) {
+    const d = this.modality.dimensions, n = isotropicShape([d.width, d.height, d.depth], spacing, pitch);
+    return this.resample(n[0], n[1], n[2], mode);
+}
 
 // ---- extension: connected components of a value range (include/vpt.h; DESIGN.md "Connected components") ----
 // the connected components of the codes lo .. hi of this (R8 / R16) volume as a Components object, labelled on the device: connectivity 6

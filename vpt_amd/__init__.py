@@ -24,6 +24,7 @@ from .pyramid import reduce_texels, smooth_texels
 from .rank import rank_texels
 from .components import components_texels, keep_texels, label_texels
 from .distance import distance_squared_texels, within_texels, channel_texels, check_seeds, check_steps, check_radius
+from .resample import resample_texels, isotropic_shape, axis_taps, nearest_index, count_ties, check_mode, check_size, check_spacing
 from ._native import VptError
 
 __all__ = [
@@ -37,4 +38,5 @@ __all__ = [
     'HDRImage', 'read_hdr', 'gradient_magnitude', 'window_texels', 'percentile_window', 'reduce_texels', 'smooth_texels', 'rank_texels',
     'components_texels', 'keep_texels', 'label_texels', 'Components',
     'distance_squared_texels', 'within_texels', 'channel_texels', 'check_seeds', 'check_steps', 'check_radius', 'Distance',
+    'resample_texels', 'isotropic_shape', 'axis_taps', 'nearest_index', 'count_ties', 'check_mode', 'check_size', 'check_spacing',
 ]

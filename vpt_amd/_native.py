@@ -55,6 +55,7 @@ SYMBOLS = [
     "vpt_components_label", "vpt_components_profile", "vpt_components_destroy",
     "vpt_volume_distance", "vpt_distance_info", "vpt_distance_squared", "vpt_distance_within", "vpt_distance_channel",
     "vpt_distance_profile", "vpt_distance_destroy",
+    "vpt_volume_resample", "vpt_volume_resample_timed",
     "vpt_renderer_create", "vpt_renderer_set_shard", "vpt_renderer_local_rows", "vpt_renderer_global_row",
     "vpt_renderer_destroy", "vpt_renderer_set_volume", "vpt_renderer_set_transfer_function",
     "vpt_renderer_set_environment", "vpt_renderer_set_environment_texels", "vpt_renderer_resize",
@@ -116,6 +117,8 @@ class DistanceInfo(C.Structure):
 DISTANCE_TO_RANGE, DISTANCE_TO_REST = 0, 1
 DISTANCE_NONE = 0xFFFFFFFF
 DISTANCE_PHASES = 3
+RESAMPLE_NEAREST, RESAMPLE_FILTERED = 0, 1
+RESAMPLE_PHASES = 2
 
 
 class TonemapParams(C.Structure):
@@ -192,6 +195,7 @@ def lib():
         "vpt_volume_distance": [P, C.c_uint32, C.c_uint32, I, PP], "vpt_distance_info": [P, C.POINTER(DistanceInfo)],
         "vpt_distance_squared": [P, I, I, I, I, I, I, P, SZ], "vpt_distance_within": [P, C.c_uint32, C.c_uint32, C.c_uint32, PP],
         "vpt_distance_channel": [P, I, PP], "vpt_distance_profile": [P, C.POINTER(C.c_double)], "vpt_distance_destroy": [P],
+        "vpt_volume_resample": [P, I, I, I, I, PP], "vpt_volume_resample_timed": [P, I, I, I, I, PP, C.POINTER(C.c_double)],
         "vpt_renderer_create": [P, I, I, I, PP],
         "vpt_renderer_set_shard": [P, I, I, I], "vpt_renderer_local_rows": [P, C.POINTER(I)],
         "vpt_renderer_global_row": [P, I, C.POINTER(I)],

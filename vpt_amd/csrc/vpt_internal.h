@@ -14,6 +14,7 @@
 //   vpt_volume_rank.hip  the rank filters of a volume over the 3 x 3 x 3 box: median, erosion, dilation, opening and closing
 //   vpt_volume_components.hip  the connected components of a value range: per-voxel ranks, the component list, keep and label volumes
 //   vpt_volume_distance.hip  the exact squared Euclidean distance to a value range (or to its complement): per-voxel d2, within and channel volumes
+//   vpt_volume_resample.hip  a volume resampled to any grid size: nearest texel, or linear interpolation / area average in integers
 // vpt_variants.h (through vpt_device.h) holds the variant bits of the sampling kernels and the switch from a run-time variant to a template
 // argument; launch_variant below is its use for a renderer's sampling pass.
 // vpt_buffers.h holds DevBuf<T> / PinnedBuf<T>, the owners of device and pinned host memory: the objects below own their memory through such
@@ -251,7 +252,7 @@ int join_side(vpt_renderer *r);                     // the side streams' work ha
 int streams_deal(vpt_renderer *r, Deal d);          // before the launches of a deal: join and fork as the deal needs (StreamSet)
 int make_args(vpt_renderer *r, const vpt_uniforms *u, bool need_volume, PassArgs *a);
 int volume_create(vpt_context *c, int w, int h, int d, int format, bool zero_fill, vpt_volume **out);   // vpt_volume_create; zero_fill = false: the caller writes every texel
-int volume_finish_derived(const vpt_volume *src, vpt_volume *d, vpt_volume **out);   // the shared tail of the derived volumes (gradient, window, reduce, smooth, rank, components' keep and label): finalize and hand out
+int volume_finish_derived(const vpt_volume *src, vpt_volume *d, vpt_volume **out);   // the shared tail of the derived volumes (gradient, window, reduce, smooth, rank, resample, components' keep and label): finalize and hand out
 int volume_records(vpt_volume *v);                  // builds the column records of a finalized one-channel byte volume if they are not current
 hipError_t create_overlapping_stream(Stream *out, const vpt_renderer *r);   // overlaps r's context stream and side streams
 bool invert_matrix(const float *m, double out[4][4]);               // column-major float matrix -> its inverse (double); false: singular

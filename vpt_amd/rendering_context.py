@@ -68,6 +68,11 @@ class RenderingContext(EventTarget):
                 raise ValueError("distance mode 'channel' and gradient both write the second channel: name one of them")
             if self.components is not None and self.components['mode'] == 'label':
                 raise ValueError("distance mode 'channel' and components mode 'label' both write the second channel: name one of them")
+        # (extension) None | {'size': [w, h, d]} | {'spacing': [sx, sy, sz], 'pitch': None}, plus 'mode': 'filtered' | 'nearest': the volume is
+        # resampled to that grid, or to cubic voxels of edge `pitch` (None: the smallest spacing), when it is loaded, behind the window and in
+        # front of the rank filter: rank, components and distance see the resampled grid.  A volume whose format the mode does not take is
+        # left as it is
+        self.resample = self._resample_spec(options.get('resample'))
         self.gl = Context(options.get('device', 0))                                   # initGL(), :61-105
         self.environmentTexture = np.array([[[255, 255, 255, 255]]], dtype=np.uint8)   # :90-101
         self._rng = options.get('rng')
@@ -111,6 +116,13 @@ class RenderingContext(EventTarget):
                 source = self.volume
                 lo, hi = self._window_of(source)
                 self.volume = source.window(lo, hi, self.windowFormat)                # the transfer function's x axis is [lo, hi]
+                source.destroy()
+            if self.resample is not None and self._resample_takes(self.volume, self.resample['mode']):
+                source = self.volume
+                if self.resample['size'] is not None:
+                    self.volume = source.resample(*self.resample['size'], mode=self.resample['mode'])
+                else:
+                    self.volume = source.isotropic(self.resample['spacing'], self.resample['pitch'], self.resample['mode'])
                 source.destroy()
             if self.rank is not None and self._one_channel_unorm(self.volume):
                 source = self.volume
@@ -171,6 +183,36 @@ class RenderingContext(EventTarget):
         finally:
             found.destroy()
         source.destroy()
+
+    @staticmethod
+    def _resample_spec(spec):
+        """the `resample` option with its defaults filled in, or None; raises ValueError for anything the contract does not take"""
+        if spec is None:
+            return None
+        from .resample import check_mode, check_size, check_spacing
+        if not isinstance(spec, dict) or not set(spec) <= {'size', 'spacing', 'pitch', 'mode'} or ('size' in spec) == ('spacing' in spec):
+            raise ValueError("resample is None, {'size': [w, h, d], 'mode'} or {'spacing': [sx, sy, sz], 'pitch', 'mode'}, not %r" % (spec,))
+        mode = spec['mode'] if spec.get('mode') is not None else 'filtered'
+        check_mode(mode)
+        out = {'size': None, 'spacing': None, 'pitch': None, 'mode': mode}
+        if 'size' in spec:
+            if spec.get('pitch') is not None:
+                raise ValueError("resample 'pitch' goes with 'spacing'")
+            size = spec['size']
+            if isinstance(size, (str, bytes)) or not hasattr(size, '__len__') or len(size) != 3:
+                raise ValueError('resample size is [w, h, d], not %r' % (size,))
+            out['size'] = check_size(*size)
+        else:
+            out['spacing'], out['pitch'] = check_spacing(spec['spacing'], spec.get('pitch'))
+        return out
+
+    @staticmethod
+    def _resample_takes(volume, mode):
+        from . import _native as N
+        fmt = volume.native_format()[0]
+        if mode == 'filtered':
+            return fmt in (N.FORMAT_R8, N.FORMAT_RG8, N.FORMAT_R16, N.FORMAT_RG16)
+        return not N.FORMAT_RGB565 <= fmt <= N.FORMAT_RGB9_E5
 
     @staticmethod
     def _distance_spec(spec):

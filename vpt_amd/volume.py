@@ -481,6 +481,37 @@ class Volume(EventTarget):
         finally:
             d.destroy()
 
+    # ---- extension: resampling to any grid size (include/vpt.h; DESIGN.md "Resampling") ----
+    def resample(self, width, height, depth, mode='filtered'):
+        """A new, ready volume in this volume's format and with its filter on a grid of width x height x depth texels (each 1 .. 4096) that
+        fills the same cube: 'filtered' (R8, RG8, R16, RG16) interpolates linearly along an axis that grows and averages areas along one
+        that shrinks, in integers with one rounding; 'nearest' (every unpacked format) copies the texel under each result texel's centre:
+        the mode for labels and masks (vpt_amd.resample_texels states both), derived on the device.  This volume is not changed."""
+        from .resample import check_mode, check_size
+        code = check_mode(mode)
+        width, height, depth = check_size(width, height, depth)
+        h = C.c_void_p()
+        N.check(N.lib().vpt_volume_resample(self.texture, width, height, depth, code, C.byref(h)))
+        return self._same_format(h, {'width': width, 'height': height, 'depth': depth})
+
+    def resample_timed(self, width, height, depth, mode='filtered'):
+        """(for measurements) (the volume ``resample`` gives, {'x', 'yz'}: milliseconds of the row pass and of the plane pass of 'filtered',
+        the stream drained after each; zeros for 'nearest')"""
+        from .resample import check_mode, check_size
+        code = check_mode(mode)
+        width, height, depth = check_size(width, height, depth)
+        h = C.c_void_p()
+        ms = (C.c_double * N.RESAMPLE_PHASES)()
+        N.check(N.lib().vpt_volume_resample_timed(self.texture, width, height, depth, code, C.byref(h), ms))
+        return self._same_format(h, {'width': width, 'height': height, 'depth': depth}), dict(zip(('x', 'yz'), ms))
+
+    def isotropic(self, spacing, pitch=None, mode='filtered'):
+        """``resample`` to cubic voxels of edge ``pitch`` (None: the smallest spacing) from this volume's voxel ``spacing`` = (sx, sy, sz):
+        the grid vpt_amd.isotropic_shape gives"""
+        from .resample import isotropic_shape
+        dims = self.modality['dimensions']
+        return self.resample(*isotropic_shape((dims['width'], dims['height'], dims['depth']), spacing, pitch), mode=mode)
+
     def set_wide_tables(self, wide):
         """force the > 4 GiB addressing variant of the kernels (automatic above 4 GiB of bricked data)"""
         N.check(N.lib().vpt_volume_set_wide_tables(self.texture, 1 if wide else 0))
