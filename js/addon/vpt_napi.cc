@@ -71,6 +71,14 @@ static bool get_uniforms(napi_env env, napi_value v, const vpt_uniforms **u, boo
     *u = (const vpt_uniforms *)p;
     return true;
 }
+// (handle, x, y, z, width, height, depth, bytes): what the box transfers of a volume and of a voxel field take
+struct BoxArgs { void *handle; int32_t p[6]; void *data; size_t n; };
+static bool get_box(napi_env env, napi_callback_info info, BoxArgs *b) {
+    napi_value a[8];
+    if (!get_args(env, info, 8, a) || !get_handle(env, a[0], &b->handle)) return false;
+    for (int i = 0; i < 6; i++) if (!get_i32(env, a[1 + i], &b->p[i])) return false;
+    return get_bytes(env, a[7], &b->data, &b->n);
+}
 static napi_value make_external(napi_env env, void *p) {
     napi_value v;
     NAPI_OK(napi_create_external(env, p, nullptr, nullptr, &v));     // explicit destroy() is the contract (AbstractRenderer.js:51-58)
@@ -118,11 +126,9 @@ static napi_value VolumeCreate(napi_env env, napi_callback_info info) {
     return make_external(env, v);
 }
 static napi_value VolumeUploadBlock(napi_env env, napi_callback_info info) {
-    napi_value a[8]; vpt_volume *v; int32_t p[6]; void *data; size_t n;
-    if (!get_args(env, info, 8, a) || !get_handle(env, a[0], &v)) return nullptr;
-    for (int i = 0; i < 6; i++) if (!get_i32(env, a[1 + i], &p[i])) return nullptr;
-    if (!get_bytes(env, a[7], &data, &n)) return nullptr;
-    VPT_CHECK(vpt_volume_upload_block(v, p[0], p[1], p[2], p[3], p[4], p[5], data, n));
+    BoxArgs b;
+    if (!get_box(env, info, &b)) return nullptr;
+    VPT_CHECK(vpt_volume_upload_block((vpt_volume *)b.handle, b.p[0], b.p[1], b.p[2], b.p[3], b.p[4], b.p[5], b.data, b.n));
     return undefined(env);
 }
 static napi_value VolumeFinalize(napi_env env, napi_callback_info info) {
@@ -160,11 +166,9 @@ static napi_value VolumeDeriveGradient(napi_env env, napi_callback_info info) {
 }
 // volumeReadBlock(volume, x, y, z, width, height, depth, dst): the box's texels into dst (a TypedArray of the volume's texel type)
 static napi_value VolumeReadBlock(napi_env env, napi_callback_info info) {
-    napi_value a[8]; vpt_volume *v; int32_t p[6]; void *data; size_t n;
-    if (!get_args(env, info, 8, a) || !get_handle(env, a[0], &v)) return nullptr;
-    for (int i = 0; i < 6; i++) if (!get_i32(env, a[1 + i], &p[i])) return nullptr;
-    if (!get_bytes(env, a[7], &data, &n)) return nullptr;
-    VPT_CHECK(vpt_volume_read_block(v, p[0], p[1], p[2], p[3], p[4], p[5], data, n));
+    BoxArgs b;
+    if (!get_box(env, info, &b)) return nullptr;
+    VPT_CHECK(vpt_volume_read_block((vpt_volume *)b.handle, b.p[0], b.p[1], b.p[2], b.p[3], b.p[4], b.p[5], b.data, b.n));
     return undefined(env);
 }
 // volumeHistogram(volume, bins): bins is a Uint32Array of 256 (one channel) or 65536 (two channels) counts
@@ -285,11 +289,9 @@ static napi_value ComponentsList(napi_env env, napi_callback_info info) {
 }
 // componentsRanks(components, x, y, z, width, height, depth, dst): the box's ranks into dst (a Uint32Array)
 static napi_value ComponentsRanks(napi_env env, napi_callback_info info) {
-    napi_value a[8]; vpt_components *c; int32_t p[6]; void *data; size_t n;
-    if (!get_args(env, info, 8, a) || !get_handle(env, a[0], &c)) return nullptr;
-    for (int i = 0; i < 6; i++) if (!get_i32(env, a[1 + i], &p[i])) return nullptr;
-    if (!get_bytes(env, a[7], &data, &n)) return nullptr;
-    VPT_CHECK(vpt_components_ranks(c, p[0], p[1], p[2], p[3], p[4], p[5], (uint32_t *)data, n));
+    BoxArgs b;
+    if (!get_box(env, info, &b)) return nullptr;
+    VPT_CHECK(vpt_components_ranks((vpt_components *)b.handle, b.p[0], b.p[1], b.p[2], b.p[3], b.p[4], b.p[5], (uint32_t *)b.data, b.n));
     return undefined(env);
 }
 // componentsKeep(components, firstRank, lastRank, fill) -> a new volume handle
@@ -338,11 +340,9 @@ static napi_value DistanceInfo(napi_env env, napi_callback_info info) {
 }
 // distanceSquared(distance, x, y, z, width, height, depth, dst): the box's squared distances into dst (a Uint32Array)
 static napi_value DistanceSquared(napi_env env, napi_callback_info info) {
-    napi_value a[8]; vpt_distance *d; int32_t p[6]; void *data; size_t n;
-    if (!get_args(env, info, 8, a) || !get_handle(env, a[0], &d)) return nullptr;
-    for (int i = 0; i < 6; i++) if (!get_i32(env, a[1 + i], &p[i])) return nullptr;
-    if (!get_bytes(env, a[7], &data, &n)) return nullptr;
-    VPT_CHECK(vpt_distance_squared(d, p[0], p[1], p[2], p[3], p[4], p[5], (uint32_t *)data, n));
+    BoxArgs b;
+    if (!get_box(env, info, &b)) return nullptr;
+    VPT_CHECK(vpt_distance_squared((vpt_distance *)b.handle, b.p[0], b.p[1], b.p[2], b.p[3], b.p[4], b.p[5], (uint32_t *)b.data, b.n));
     return undefined(env);
 }
 // distanceWithin(distance, r2Lo, r2Hi, fill) -> a new volume handle

@@ -294,14 +294,7 @@ percentileWindow(pLo, pHi) {
 // ---- extension: the next coarser level and binomial smoothing (include/vpt.h; DESIGN.md "Binomial smoothing and 2x reduction") ----
 // the ready Volume around a derived native volume of this volume's format with the given dimensions
 _sameFormat(texture, dimensions) {
-    const out = new Volume(this._gl);
-    out.texture = texture;
-    out.modality = Object.assign({}, this.modality, { dimensions: Object.assign({}, dimensions),
-        placements: [{ index: 0, position: { x: 0, y: 0, z: 0 } }] });
-    out.metadata = { meta: Object.assign({}, (this.metadata || {}).meta), modalities: [out.modality],
-        blocks: [{ url: null, format: 'raw', dimensions: Object.assign({}, dimensions) }] };
-    out.ready = true;
-    return out;
+    return derivedVolume(new Volume(this._gl), texture, this.modality, (this.metadata || {}).meta, dimensions);
 }
 
 // a new, ready volume in this volume's format and with its filter, `levels` (an integer >= 1, default 1) times reduced to ceil(n / 2) texels
@@ -400,28 +393,68 @@ core(lo, hi, radius) {
 
 }
 
-// The squared Euclidean distances to a value range of a volume, or to its complement (Volume.distance): one Uint32 per voxel on the device.
-// Transform once, select several times.  Outlives the volume it was made from; destroy() frees the device memory.
-class Distance {
+// the ready Volume `out` around a derived native volume: `modality` with the given dimensions in one block, and a copy of `meta`
+function derivedVolume(out, texture, modality, meta, dimensions) {
+    out.texture = texture;
+    out.modality = Object.assign({}, modality, { dimensions: Object.assign({}, dimensions),
+        placements: [{ index: 0, position: { x: 0, y: 0, z: 0 } }] });
+    out.metadata = { meta: Object.assign({}, meta), modalities: [out.modality],
+        blocks: [{ url: null, format: 'raw', dimensions: Object.assign({}, dimensions) }] };
+    out.ready = true;
+    return out;
+}
 
-constructor(source, handle) {
-    const N = native();
+// What Distance and Components share: the native handle of one Uint32 per voxel over a snapshot of an R8 / R16 volume, the box read-back of
+// those values and the description of the volumes derived from them.  `noun`: of the message thrown once destroyed; `destroy`, `read`: the
+// names of the subclass's native functions.
+class VoxelField {
+
+constructor(source, handle, noun, destroy, read) {
     this._h = handle;
-    this._norm16 = source.nativeFormat() === N.VPT_FORMAT_R16;
+    this._noun = noun; this._destroy = destroy; this._read = read;
+    this._gl = source._gl;
+    this._norm16 = source.nativeFormat() === native().VPT_FORMAT_R16;
     this._dimensions = Object.assign({}, source.modality.dimensions);
-    this._like = new Volume(source._gl);                       // what a derived volume's description is made from (Volume._sameFormat)
-    this._like.modality = Object.assign({}, source.modality);
-    this._like.metadata = { meta: Object.assign({}, (source.metadata || {}).meta) };
+    this._modality = Object.assign({}, source.modality);       // what a derived volume's description is made from (derivedVolume)
+    this._meta = Object.assign({}, (source.metadata || {}).meta);
 }
 
 _handle() {
-    if (!this._h) { throw new Error('the distances have been destroyed'); }
+    if (!this._h) { throw new Error('the ' + this._noun + ' have been destroyed'); }
     return this._h;
 }
 
 destroy() {
-    if (this._h) { native().distanceDestroy(this._h); this._h = null; }
+    if (this._h) { native()[this._destroy](this._h); this._h = null; }
 }
+
+// Uint32Array [depth][height][width]: the values of a box of voxels (default: the whole volume)
+_values(x, y, z, width, height, depth) {
+    const d = this._dimensions;
+    x = x || 0; y = y || 0; z = z || 0;
+    width = width !== undefined ? width : d.width - x; height = height !== undefined ? height : d.height - y; depth = depth !== undefined ? depth : d.depth - z;
+    const out = new Uint32Array(width * height * depth);
+    native()[this._read](this._handle(), x, y, z, width, height, depth, out);
+    return out;
+}
+
+// the ready Volume around a native volume derived from the field: of the source's format, or (pair) RG8 / RG16
+_derived(texture, pair) {
+    const out = derivedVolume(new Volume(this._gl), texture, this._modality, this._meta, this._dimensions);
+    if (pair) {
+        Object.assign(out.modality, { format: GL_RG, internalFormat: this._norm16 ? R.GL_RG16_EXT : R.GL_RG8,
+            type: this._norm16 ? R.GL_UNSIGNED_SHORT : GL_UNSIGNED_BYTE });
+    }
+    return out;
+}
+
+}
+
+// The squared Euclidean distances to a value range of a volume, or to its complement (Volume.distance): one Uint32 per voxel on the device.
+// Transform once, select several times.  Outlives the volume it was made from; destroy() frees the device memory.
+class Distance extends VoxelField {
+
+constructor(source, handle) { super(source, handle, 'distances', 'distanceDestroy', 'distanceSquared'); }
 
 // { seeds, largest }: the number of seeds; the largest finite squared distance, 0 without a seed
 get info() {
@@ -430,30 +463,20 @@ get info() {
 }
 
 // Uint32Array [depth][height][width]: the squared distances of a box of voxels (default: the whole volume); 0xFFFFFFFF: there is no seed
-squared(x, y, z, width, height, depth) {
-    const d = this._dimensions;
-    x = x || 0; y = y || 0; z = z || 0;
-    width = width !== undefined ? width : d.width - x; height = height !== undefined ? height : d.height - y; depth = depth !== undefined ? depth : d.depth - z;
-    const out = new Uint32Array(width * height * depth);
-    native().distanceSquared(this._handle(), x, y, z, width, height, depth, out);
-    return out;
-}
+squared(x, y, z, width, height, depth) { return this._values(x, y, z, width, height, depth); }
 
 // a new, ready volume of the source's size, format and filter: the source's code where r2Lo <= d2 <= r2Hi (defaults 0 and 0xFFFFFFFF),
 // `fill` (default 0) elsewhere
 within(r2Lo, r2Hi, fill) {
     const k = checkWithin(r2Lo !== undefined ? r2Lo : 0, r2Hi, fill !== undefined ? fill : 0, this._norm16 ? 65535 : 255);
-    return this._like._sameFormat(native().distanceWithin(this._handle(), k[0], k[1], k[2]), this._dimensions);
+    return this._derived(native().distanceWithin(this._handle(), k[0], k[1], k[2]));
 }
 
 // a new, ready RG8 / RG16 volume with the source's filter: (code, min(isqrt(steps^2 d2), M)): the second axis of a 2-D transfer function is
 // the distance, `steps` (1 .. 256, default 1) rows a voxel
 channel(steps) {
     steps = checkSteps(steps !== undefined ? steps : 1);
-    const out = this._like._sameFormat(native().distanceChannel(this._handle(), steps), this._dimensions);
-    Object.assign(out.modality, { format: GL_RG, internalFormat: this._norm16 ? R.GL_RG16_EXT : R.GL_RG8,
-        type: this._norm16 ? R.GL_UNSIGNED_SHORT : GL_UNSIGNED_BYTE });
-    return out;
+    return this._derived(native().distanceChannel(this._handle(), steps), true);
 }
 
 // (for measurements) { x, y, z }: milliseconds of the three passes of the transform
@@ -466,26 +489,9 @@ profile() {
 
 // The connected components of a value range of a volume (Volume.components): per-voxel ranks and the component list on the device.  Label
 // once, select several times.  Outlives the volume it was made from; destroy() frees the device memory.
-class Components {
+class Components extends VoxelField {
 
-constructor(source, handle) {
-    const N = native();
-    this._h = handle;
-    this._norm16 = source.nativeFormat() === N.VPT_FORMAT_R16;
-    this._dimensions = Object.assign({}, source.modality.dimensions);
-    this._like = new Volume(source._gl);                       // what a derived volume's description is made from (Volume._sameFormat)
-    this._like.modality = Object.assign({}, source.modality);
-    this._like.metadata = { meta: Object.assign({}, (source.metadata || {}).meta) };
-}
-
-_handle() {
-    if (!this._h) { throw new Error('the components have been destroyed'); }
-    return this._h;
-}
-
-destroy() {
-    if (this._h) { native().componentsDestroy(this._h); this._h = null; }
-}
+constructor(source, handle) { super(source, handle, 'components', 'componentsDestroy', 'componentsRanks'); }
 
 // { listed, dropped, foregroundVoxels, listedVoxels }
 get info() {
@@ -504,29 +510,17 @@ list(first, n) {
 }
 
 // Uint32Array [depth][height][width]: the ranks of a box of voxels (default: the whole volume)
-ranks(x, y, z, width, height, depth) {
-    const d = this._dimensions;
-    x = x || 0; y = y || 0; z = z || 0;
-    width = width !== undefined ? width : d.width - x; height = height !== undefined ? height : d.height - y; depth = depth !== undefined ? depth : d.depth - z;
-    const out = new Uint32Array(width * height * depth);
-    native().componentsRanks(this._handle(), x, y, z, width, height, depth, out);
-    return out;
-}
+ranks(x, y, z, width, height, depth) { return this._values(x, y, z, width, height, depth); }
 
 // a new, ready volume of the source's size, format and filter: the source's code where first <= rank <= last (defaults 1 and every rank),
 // `fill` (default 0) elsewhere
 keep(first, last, fill) {
     const k = checkKeep(first !== undefined ? first : 1, last, fill !== undefined ? fill : 0, this._norm16 ? 65535 : 255);
-    return this._like._sameFormat(native().componentsKeep(this._handle(), k[0], k[1], k[2]), this._dimensions);
+    return this._derived(native().componentsKeep(this._handle(), k[0], k[1], k[2]));
 }
 
 // a new, ready RG8 / RG16 volume with the source's filter: (code, min(rank, M)): the rows of a 2-D transfer function select the structures
-label() {
-    const out = this._like._sameFormat(native().componentsLabel(this._handle()), this._dimensions);
-    Object.assign(out.modality, { format: GL_RG, internalFormat: this._norm16 ? R.GL_RG16_EXT : R.GL_RG8,
-        type: this._norm16 ? R.GL_UNSIGNED_SHORT : GL_UNSIGNED_BYTE });
-    return out;
-}
+label() { return this._derived(native().componentsLabel(this._handle()), true); }
 
 }
 // the number of smoothing passes (an integer in 1 .. 8) / of reductions (an integer >= 1); throws for anything else

@@ -234,6 +234,9 @@ def test_the_handle_and_its_volumes_outlive_the_source_and_runs_repeat(gpu_ctx):
     kept, pair = found.keep(1, 4, 77), found.label()
     assert found.ranks().tobytes() == again.ranks().tobytes() == ranks.tobytes() and found.list() == again.list() == listed
     found.destroy(); again.destroy()                              # the derived volumes own their texels
+    found.destroy()                                               # a second destroy does nothing
+    with pytest.raises(RuntimeError, match='destroyed'):
+        found.ranks()
     assert kept.ready and kept.native_format()[0] == N.FORMAT_R16 and pair.native_format()[0] == N.FORMAT_RG16
     assert kept.modality['dimensions'] == pair.modality['dimensions'] == {'width': nx, 'height': ny, 'depth': nz}
     differences(whole(kept), vpt_amd.keep_texels(a, ranks, 1, 4, 77), 'keep')

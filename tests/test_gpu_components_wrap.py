@@ -1,6 +1,6 @@
 """GPU: connected components of a volume large enough for every streaming kernel's grid-stride loop to go round a second time.
 
-stream_grid (vpt_volume_components.hip) caps k_merge, k_flatten, k_sizes, k_census, k_compact, k_ranks, k_read_ranks, k_keep and k_label at
+stream_grid (vpt_volume_components.hip) caps k_merge, k_flatten, k_sizes, k_census, k_compact, k_ranks, k_read_field, k_select and k_pair at
 8192 workgroups of 256 threads: the loop `i += gridDim.x * 256` wraps above 2 097 152 items, and the emitters, four voxels an item, above
 8 388 608 voxels.  The forms to doubt are the wave-granular ones: `base` of k_sizes and k_compact, whose ballot and shuffle must see whole
 waves on the wrapped step too, and the emitters' tail `quads * 4 + t0` behind a wrapped loop of quads.  The other shapes of the suite stay
@@ -45,7 +45,7 @@ def test_noise_on_a_wrapped_grid_equals_the_contract(gpu_ctx, dtype, connectivit
     ranks2, stay = at_least(ranks, listed, 2)
     assert 64 <= len(stay) <= len(listed) - 64
     check(gpu_ctx, a, lo, hi, connectivity, 2, what='wrap, min 2', want=(ranks2, stay, len(listed)))
-    # a selection, and a box of ranks that is not a run of whole slices and holds more texels than one trip of k_read_ranks
+    # a selection, and a box of ranks that is not a run of whole slices and holds more texels than one trip of k_read_field
     src = upload(gpu_ctx, a)
     found = src.components(lo, hi, connectivity)
     out = found.keep(2, 3, 7)

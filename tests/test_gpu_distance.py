@@ -236,7 +236,8 @@ def test_the_handle_and_its_volumes_outlive_the_source_and_runs_repeat(gpu_ctx):
     assert found.squared().tobytes() == again.squared().tobytes() == d2.tobytes() and found.info == again.info
     assert set(found.profile()) == {'x', 'y', 'z'} and all(ms >= 0 for ms in found.profile().values())
     found.destroy(); again.destroy()                              # the derived volumes own their texels
-    with pytest.raises(RuntimeError):
+    found.destroy()                                               # a second destroy does nothing
+    with pytest.raises(RuntimeError, match='destroyed'):
         found.squared()
     assert kept.ready and kept.native_format()[0] == N.FORMAT_R16 and pair.native_format()[0] == N.FORMAT_RG16
     assert kept.modality['dimensions'] == pair.modality['dimensions'] == {'width': nx, 'height': ny, 'depth': nz}

@@ -168,12 +168,11 @@ int volume_create(vpt_context *c, int w, int h, int d, int format, bool zero_fil
     return VPT_OK;
 }
 // what vpt_volume_derive_gradient and vpt_volume_window end with: the derived volume `d`, whose texels the caller's kernels have just
-// written, becomes a finalized volume of src's filter and is handed out; on an error it is destroyed
-int volume_finish_derived(const vpt_volume *src, vpt_volume *d, vpt_volume **out) {
-    vpt_context *c = src->ctx;
+// written on c's stream, becomes a finalized volume of the source's filter and is handed out; on an error it is destroyed
+int volume_finish_derived(vpt_context *c, int filter, vpt_volume *d, vpt_volume **out) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { vpt_volume_destroy(d); return fail(VPT_ERR_HIP, "derived volume, kernel launch: %s", hipGetErrorString(e)); }
-    d->filter = src->filter;
+    d->filter = filter;
     d->dirty = true; d->any_upload = true;
     int rc = vpt_volume_finalize(d);
     if (rc != VPT_OK) { vpt_volume_destroy(d); return rc; }

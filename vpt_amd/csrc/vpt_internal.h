@@ -13,6 +13,7 @@
 //   vpt_volume_pyramid.hip  the next coarser level of a volume (2 x 2 x 2 cells averaged) and its binomial smoothing
 //   vpt_volume_rank.hip  the rank filters of a volume over the 3 x 3 x 3 box: median, erosion, dilation, opening and closing
 //   vpt_volume_components.hip  the connected components of a value range: per-voxel ranks, the component list, keep and label volumes
+//   vpt_volume_field.hip  what components and distances share (vpt_volume_field.h): a uint32 per voxel over a volume's texels, its read-back and emitters
 //   vpt_volume_distance.hip  the exact squared Euclidean distance to a value range (or to its complement): per-voxel d2, within and channel volumes
 //   vpt_volume_resample.hip  a volume resampled to any grid size: nearest texel, or linear interpolation / area average in integers
 // vpt_variants.h (through vpt_device.h) holds the variant bits of the sampling kernels and the switch from a run-time variant to a template
@@ -30,6 +31,7 @@
 #include <stdio.h>
 #include <string.h>
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <memory>
 #include <string>
@@ -252,7 +254,7 @@ int join_side(vpt_renderer *r);                     // the side streams' work ha
 int streams_deal(vpt_renderer *r, Deal d);          // before the launches of a deal: join and fork as the deal needs (StreamSet)
 int make_args(vpt_renderer *r, const vpt_uniforms *u, bool need_volume, PassArgs *a);
 int volume_create(vpt_context *c, int w, int h, int d, int format, bool zero_fill, vpt_volume **out);   // vpt_volume_create; zero_fill = false: the caller writes every texel
-int volume_finish_derived(const vpt_volume *src, vpt_volume *d, vpt_volume **out);   // the shared tail of the derived volumes (gradient, window, reduce, smooth, rank, resample, components' keep and label): finalize and hand out
+int volume_finish_derived(vpt_context *ctx, int filter, vpt_volume *d, vpt_volume **out);   // the shared tail of the derived volumes (gradient, window, reduce, smooth, rank, resample, the voxel fields' emitters): finalize with the source's filter and hand out
 int volume_records(vpt_volume *v);                  // builds the column records of a finalized one-channel byte volume if they are not current
 hipError_t create_overlapping_stream(Stream *out, const vpt_renderer *r);   // overlaps r's context stream and side streams
 bool invert_matrix(const float *m, double out[4][4]);               // column-major float matrix -> its inverse (double); false: singular
@@ -333,6 +335,21 @@ static inline int lds_prepare(const void *kernel, size_t lds) {
     if (lds > 64 * 1024) HIP_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     return VPT_OK;
 }
+// grid of a grid-stride kernel over `items`, `per` of them a workgroup, `most` workgroups
+static inline unsigned stream_grid(size_t items, size_t per = 256, size_t most = 8192) { return (unsigned)std::max<size_t>(1, std::min<size_t>((items + per - 1) / per, most)); }
+// wall time of a phase, the stream drained at its end: lap() for a phase that runs once, lap_add() for one that comes round many times
+struct PhaseClock {
+    hipStream_t st; std::chrono::steady_clock::time_point t0;
+    explicit PhaseClock(hipStream_t s) : st(s), t0(std::chrono::steady_clock::now()) {}
+    hipError_t lap(double *ms) {
+        const hipError_t e = hipStreamSynchronize(st);
+        const auto t1 = std::chrono::steady_clock::now();
+        *ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
+        t0 = t1;
+        return e;
+    }
+    hipError_t lap_add(double *ms) { double took; const hipError_t e = lap(&took); *ms += took; return e; }
+};
 static inline dim3 tile_grid(const vpt_renderer *r) { return dim3((unsigned)(r->tiles_x + 7) / 8u * 8u, (unsigned)r->tiles_y); }
 // Ray-marching kernels (MIP, EAM, ISO, Depth, MCS) run as one-wave workgroups when 28 of their LDS images fit a CU: with
 // the default camera only ~20 % of the tiles cross the cube, about one resident round of 4-wave workgroups, which the

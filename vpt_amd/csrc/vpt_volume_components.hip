@@ -6,9 +6,7 @@
 // the voxel's rank.  Every link ever written joins two voxels of one component and points to a smaller index, so parents only decrease and
 // the root of a finished component is its smallest voxel whatever the order of arrival.  No workgroup waits for another: launch
 // boundaries order the phases, and within the merge launch L is touched through device-scope integer atomics only.
-#include "vpt_internal.h"
-#include <chrono>
-#include <memory>
+#include "vpt_volume_field.h"
 
 // ---------------------------------------------------------------------------------------------
 // tile labelling: k_label_tiles<T, CONN>
@@ -268,82 +266,17 @@ __global__ __launch_bounds__(256) void k_ranks(uint32_t *__restrict__ L, const u
     }
 }
 
-// ---------------------------------------------------------------------------------------------
-// emitters: k_keep<T>, k_label<T>; read-back of a box of ranks
-// ---------------------------------------------------------------------------------------------
-// Plain gathers over the linear storage, four voxels a thread: the texels as one dword (uint8) or qword (uint16), the ranks as one uint4,
-// the result as one vector store; the last n % 4 voxels one by one.  (Groups of four along the linear index are aligned whatever nx is.)
-template <typename T> struct Four;
-template <> struct Four<uint8_t> {
-    typedef uint32_t in_t; typedef uint2 pair_t;
-    static __device__ __forceinline__ uint32_t get(in_t w, int i) { return (w >> (8 * i)) & 255u; }
-    static __device__ __forceinline__ in_t pack(const uint32_t *v) { return v[0] | (v[1] << 8) | (v[2] << 16) | (v[3] << 24); }
-    static __device__ __forceinline__ pair_t pack2(const uint32_t *v, const uint32_t *g) {
-        return make_uint2(v[0] | (g[0] << 8) | (v[1] << 16) | (g[1] << 24), v[2] | (g[2] << 8) | (v[3] << 16) | (g[3] << 24));
-    }
-};
-template <> struct Four<uint16_t> {
-    typedef uint2 in_t; typedef uint4 pair_t;
-    static __device__ __forceinline__ uint32_t get(in_t w, int i) { return ((i < 2 ? w.x : w.y) >> (16 * (i & 1))) & 65535u; }
-    static __device__ __forceinline__ in_t pack(const uint32_t *v) { return make_uint2(v[0] | (v[1] << 16), v[2] | (v[3] << 16)); }
-    static __device__ __forceinline__ pair_t pack2(const uint32_t *v, const uint32_t *g) {
-        return make_uint4(v[0] | (g[0] << 16), v[1] | (g[1] << 16), v[2] | (g[2] << 16), v[3] | (g[3] << 16));
-    }
-};
-template <typename T>
-__global__ __launch_bounds__(256) void k_keep(const T *__restrict__ src, const uint32_t *__restrict__ ranks, T *__restrict__ dst, size_t n,
-                                             uint32_t first, uint32_t last, uint32_t fill) {
-    typedef Four<T> F;
-    const size_t quads = n / 4, stride = (size_t)gridDim.x * 256, t0 = (size_t)blockIdx.x * 256 + threadIdx.x;
-    for (size_t q = t0; q < quads; q += stride) {
-        const typename F::in_t w = reinterpret_cast<const typename F::in_t *>(src)[q];
-        const uint4 r = reinterpret_cast<const uint4 *>(ranks)[q];
-        const uint32_t rk[4] = { r.x, r.y, r.z, r.w };
-        uint32_t v[4];
-#pragma unroll
-        for (int i = 0; i < 4; i++) v[i] = (rk[i] >= first && rk[i] <= last) ? F::get(w, i) : fill;
-        reinterpret_cast<typename F::in_t *>(dst)[q] = F::pack(v);
-    }
-    for (size_t i = quads * 4 + t0; i < n; i += stride) { const uint32_t r = ranks[i]; dst[i] = (r >= first && r <= last) ? src[i] : (T)fill; }
-}
-template <typename T>
-__global__ __launch_bounds__(256) void k_label(const T *__restrict__ src, const uint32_t *__restrict__ ranks, T *__restrict__ dst, size_t n) {
-    typedef Four<T> F;
-    constexpr uint32_t M = (1u << (8 * sizeof(T))) - 1u;
-    const size_t quads = n / 4, stride = (size_t)gridDim.x * 256, t0 = (size_t)blockIdx.x * 256 + threadIdx.x;
-    for (size_t q = t0; q < quads; q += stride) {
-        const typename F::in_t w = reinterpret_cast<const typename F::in_t *>(src)[q];
-        const uint4 r = reinterpret_cast<const uint4 *>(ranks)[q];
-        const uint32_t g[4] = { min(r.x, M), min(r.y, M), min(r.z, M), min(r.w, M) };
-        uint32_t v[4];
-#pragma unroll
-        for (int i = 0; i < 4; i++) v[i] = F::get(w, i);
-        reinterpret_cast<typename F::pair_t *>(dst)[q] = F::pack2(v, g);
-    }
-    for (size_t i = quads * 4 + t0; i < n; i += stride) { dst[2 * i] = src[i]; dst[2 * i + 1] = (T)min(ranks[i], M); }
-}
-__global__ __launch_bounds__(256) void k_read_ranks(const uint32_t *__restrict__ ranks, int nx, int ny, uint32_t *__restrict__ blk, int x0, int y0, int z0,
-                                                   int bw, int bh, size_t texels) {
-    for (size_t t = (size_t)blockIdx.x * 256 + threadIdx.x; t < texels; t += (size_t)gridDim.x * 256) {
-        const int x = (int)(t % (size_t)bw); const size_t r = t / (size_t)bw; const int y = (int)(r % (size_t)bh), z = (int)(r / (size_t)bh);
-        blk[t] = ranks[((size_t)(z0 + z) * (size_t)ny + (size_t)(y0 + y)) * (size_t)nx + (size_t)(x0 + x)];
-    }
-}
+// the label channel's second value, before k_pair clamps it to the largest code: the rank (vpt_volume_field.h)
+struct RankChannel { __device__ __forceinline__ uint32_t operator()(uint32_t rank) const { return rank; } };
 
 // ---------------------------------------------------------------------------------------------
 // host
 // ---------------------------------------------------------------------------------------------
-struct vpt_components {
-    vpt_context *ctx = nullptr;
-    int nx = 0, ny = 0, nz = 0, format = 0, filter = VPT_FILTER_LINEAR;
-    bool norm16 = false;
-    DevBuf<uint8_t> texels;                 // the source's linear texels at the time of the call
-    DevBuf<uint32_t> ranks;                 // L: one rank per voxel
+struct vpt_components : VoxelField {       // the values are L: at the end one rank per voxel
     std::vector<vpt_component> list;        // canonical order
     struct vpt_components_info info = {};
     double ms[VPT_COMPONENTS_PHASES] = {};
     uint32_t launches[2] = {};
-    size_t voxels() const { return (size_t)nx * (size_t)ny * (size_t)nz; }
 };
 
 // chase steps a unite / a voxel's flatten may take in one launch: what vpt_volume_components passes
@@ -370,37 +303,22 @@ static int flatten_launches(int cap) {
     return j + 2;
 }
 
-// grid of a grid-stride kernel over `items`
-static unsigned stream_grid(size_t items) { return (unsigned)std::max<size_t>(1, std::min<size_t>((items + 255) / 256, 8192)); }
-
-struct PhaseClock {          // wall time of a phase, the stream drained at its end
-    hipStream_t st; std::chrono::steady_clock::time_point t0;
-    explicit PhaseClock(hipStream_t s) : st(s), t0(std::chrono::steady_clock::now()) {}
-    hipError_t lap(double *ms) {
-        const hipError_t e = hipStreamSynchronize(st);
-        const auto t1 = std::chrono::steady_clock::now();
-        *ms += std::chrono::duration<double, std::milli>(t1 - t0).count();
-        t0 = t1;
-        return e;
-    }
-};
-
 template <typename T>
 static void launch_label_tiles(const vpt_components *c, int conn, uint32_t lo, uint32_t hi, uint32_t *words) {
     const dim3 grid((unsigned)((c->nx + CC_TX - 1) / CC_TX), (unsigned)((c->ny + CC_TY - 1) / CC_TY), (unsigned)((c->nz + CC_TZ - 1) / CC_TZ));
     const T *s = (const T *)c->texels.get();
     hipStream_t st = c->ctx->stream;
-    if (conn == 6) hipLaunchKernelGGL((k_label_tiles<T, 6>), grid, dim3(256), 0, st, s, c->ranks.get(), c->nx, c->ny, c->nz, lo, hi, words);
-    else if (conn == 18) hipLaunchKernelGGL((k_label_tiles<T, 18>), grid, dim3(256), 0, st, s, c->ranks.get(), c->nx, c->ny, c->nz, lo, hi, words);
-    else hipLaunchKernelGGL((k_label_tiles<T, 26>), grid, dim3(256), 0, st, s, c->ranks.get(), c->nx, c->ny, c->nz, lo, hi, words);
+    if (conn == 6) hipLaunchKernelGGL((k_label_tiles<T, 6>), grid, dim3(256), 0, st, s, c->values.get(), c->nx, c->ny, c->nz, lo, hi, words);
+    else if (conn == 18) hipLaunchKernelGGL((k_label_tiles<T, 18>), grid, dim3(256), 0, st, s, c->values.get(), c->nx, c->ny, c->nz, lo, hi, words);
+    else hipLaunchKernelGGL((k_label_tiles<T, 26>), grid, dim3(256), 0, st, s, c->values.get(), c->nx, c->ny, c->nz, lo, hi, words);
 }
 static void launch_merge(const vpt_components *c, int conn, int cap, uint32_t *words) {
     const size_t n = c->voxels();
     const dim3 grid(stream_grid(n));
     hipStream_t st = c->ctx->stream;
-    if (conn == 6) hipLaunchKernelGGL(k_merge<6>, grid, dim3(256), 0, st, c->ranks.get(), c->nx, c->ny, c->nz, n, cap, words);
-    else if (conn == 18) hipLaunchKernelGGL(k_merge<18>, grid, dim3(256), 0, st, c->ranks.get(), c->nx, c->ny, c->nz, n, cap, words);
-    else hipLaunchKernelGGL(k_merge<26>, grid, dim3(256), 0, st, c->ranks.get(), c->nx, c->ny, c->nz, n, cap, words);
+    if (conn == 6) hipLaunchKernelGGL(k_merge<6>, grid, dim3(256), 0, st, c->values.get(), c->nx, c->ny, c->nz, n, cap, words);
+    else if (conn == 18) hipLaunchKernelGGL(k_merge<18>, grid, dim3(256), 0, st, c->values.get(), c->nx, c->ny, c->nz, n, cap, words);
+    else hipLaunchKernelGGL(k_merge<26>, grid, dim3(256), 0, st, c->values.get(), c->nx, c->ny, c->nz, n, cap, words);
 }
 
 // the body of vpt_volume_components behind the argument checks; `c` is freed by the caller on failure
@@ -423,7 +341,7 @@ static int components_build(vpt_components *c, int conn, uint32_t lo, uint32_t h
     else launch_label_tiles<uint8_t>(c, conn, lo, hi, words);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(host_words, words, sizeof(host_words), hipMemcpyDeviceToHost, st));
-    HIP_TRY(clock.lap(&c->ms[0]));
+    HIP_TRY(clock.lap_add(&c->ms[0]));
     // ---- 2., 3. merge and flatten until nothing gives up.
     // The bound of the loop.  Every merge launch begins with a flat forest (each voxel names its root: the flatten loop below ends that way,
     // and k_label_tiles leaves it so).  In a launch in which no hook succeeds the forest stays flat, every find ends within two loads and
@@ -440,28 +358,28 @@ static int components_build(vpt_components *c, int conn, uint32_t lo, uint32_t h
         launch_merge(c, conn, merge_steps, words);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(host_words, words, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        HIP_TRY(clock.lap(&c->ms[1]));
+        HIP_TRY(clock.lap_add(&c->ms[1]));
         c->launches[0]++;
         const bool merge_gave_up = host_words[W_CHANGED] != 0u;
         for (int f = 0; ; f++) {
             if (f == flatten_bound) return fail(VPT_ERR_HIP, "connected components: the labels were not flat after %d launches", flatten_bound);
             HIP_TRY(hipMemsetAsync(words + W_CHANGED, 0, sizeof(uint32_t), st));
-            hipLaunchKernelGGL(k_flatten, dim3(stream_grid(n)), dim3(256), 0, st, c->ranks.get(), n, flatten_steps, words.get());
+            hipLaunchKernelGGL(k_flatten, dim3(stream_grid(n)), dim3(256), 0, st, c->values.get(), n, flatten_steps, words.get());
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipMemcpyAsync(host_words, words, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-            HIP_TRY(clock.lap(&c->ms[2]));
+            HIP_TRY(clock.lap_add(&c->ms[2]));
             c->launches[1]++;
             if (host_words[W_CHANGED] == 0u) break;
         }
         if (!merge_gave_up) break;
     }
     // ---- 4. sizes
-    hipLaunchKernelGGL(k_sizes, dim3(stream_grid(n)), dim3(256), 0, st, c->ranks.get(), n, count.get());
+    hipLaunchKernelGGL(k_sizes, dim3(stream_grid(n)), dim3(256), 0, st, c->values.get(), n, count.get());
     HIP_TRY(hipGetLastError());
-    HIP_TRY(clock.lap(&c->ms[3]));
+    HIP_TRY(clock.lap_add(&c->ms[3]));
     // ---- 5. census, then the list of those that stay
     unsigned long long host_sums[Q_WORDS] = {};
-    hipLaunchKernelGGL(k_census, dim3(stream_grid(n)), dim3(256), 0, st, c->ranks.get(), count.get(), n, min_voxels, sums.get());
+    hipLaunchKernelGGL(k_census, dim3(stream_grid(n)), dim3(256), 0, st, c->values.get(), count.get(), n, min_voxels, sums.get());
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(host_sums, sums, sizeof(host_sums), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -472,11 +390,11 @@ static int components_build(vpt_components *c, int conn, uint32_t lo, uint32_t h
     DevBuf<uint2> list;
     if (listed) {
         HIP_TRY(list.alloc(listed));
-        hipLaunchKernelGGL(k_compact, dim3(stream_grid(n)), dim3(256), 0, st, c->ranks.get(), count.get(), n, min_voxels, list.get(), listed, words.get());
+        hipLaunchKernelGGL(k_compact, dim3(stream_grid(n)), dim3(256), 0, st, c->values.get(), count.get(), n, min_voxels, list.get(), listed, words.get());
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(pairs.data(), list, (size_t)listed * sizeof(uint2), hipMemcpyDeviceToHost, st));
     }
-    HIP_TRY(clock.lap(&c->ms[4]));
+    HIP_TRY(clock.lap_add(&c->ms[4]));
     // ---- 6. the canonical order: voxels descending, then root ascending
     std::sort(pairs.begin(), pairs.end(), [](const uint2 &a, const uint2 &b) { return a.y != b.y ? a.y > b.y : a.x < b.x; });
     c->list.resize(listed);
@@ -484,16 +402,16 @@ static int components_build(vpt_components *c, int conn, uint32_t lo, uint32_t h
         const uint32_t i = pairs[k].x;
         c->list[k] = vpt_component{ i % (uint32_t)c->nx, (i / (uint32_t)c->nx) % (uint32_t)c->ny, i / ((uint32_t)c->nx * (uint32_t)c->ny), pairs[k].y };
     }
-    HIP_TRY(clock.lap(&c->ms[5]));
+    HIP_TRY(clock.lap_add(&c->ms[5]));
     // ---- the rank table in the count array, then L in place
     HIP_TRY(hipMemsetAsync(count, 0, n * sizeof(uint32_t), st));
     if (listed) {
         HIP_TRY(hipMemcpyAsync(list, pairs.data(), (size_t)listed * sizeof(uint2), hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(k_rank_table, dim3(stream_grid(listed)), dim3(256), 0, st, list.get(), listed, count.get());
     }
-    hipLaunchKernelGGL(k_ranks, dim3(stream_grid(n)), dim3(256), 0, st, c->ranks.get(), count.get(), n);
+    hipLaunchKernelGGL(k_ranks, dim3(stream_grid(n)), dim3(256), 0, st, c->values.get(), count.get(), n);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(clock.lap(&c->ms[6]));          // `pairs`, `list` and `count` go out of scope behind their last use
+    HIP_TRY(clock.lap_add(&c->ms[6]));          // `pairs`, `list` and `count` go out of scope behind their last use
     return VPT_OK;
 }
 
@@ -515,11 +433,7 @@ static int components_create(vpt_volume *src, uint32_t lo, uint32_t hi, int conn
     HIP_TRY(hipSetDevice(ctx->device));
     if ((src->ny + CC_TY - 1) / CC_TY > 65535 || (src->nz + CC_TZ - 1) / CC_TZ > 65535) return fail(VPT_ERR_UNSUPPORTED, "volume too large");
     std::unique_ptr<vpt_components> c(new vpt_components());
-    c->ctx = ctx; c->nx = src->nx; c->ny = src->ny; c->nz = src->nz; c->format = src->format; c->filter = src->filter; c->norm16 = src->norm16;
-    const size_t bytes = (size_t)n * (size_t)src->vox_bytes;
-    HIP_TRY(c->texels.alloc(bytes));
-    HIP_TRY(c->ranks.alloc((size_t)n));
-    HIP_TRY(hipMemcpyAsync(c->texels, src->linear, bytes, hipMemcpyDeviceToDevice, ctx->stream));     // behind any upload into src
+    VPT_TRY(field_capture(c.get(), src));
     const int rc = components_build(c.get(), connectivity, lo, hi, min_voxels, merge_steps, flatten_steps);
     if (rc != VPT_OK) { (void)hipStreamSynchronize(ctx->stream); return rc; }      // the buffers are freed on return: nothing may still use them
     *out = c.release();
@@ -555,63 +469,22 @@ extern "C" int vpt_components_list(vpt_components *c, uint64_t first, uint64_t n
 }
 
 extern "C" int vpt_components_ranks(vpt_components *c, int x, int y, int z, int w, int h, int d, uint32_t *host_dst, size_t nbytes) {
-    if (!c || !host_dst) return fail(VPT_ERR_INVALID, "null argument");
-    if (w < 1 || h < 1 || d < 1 || x < 0 || y < 0 || z < 0 || x + w > c->nx || y + h > c->ny || z + d > c->nz)
-        return fail(VPT_ERR_INVALID, "block (%d,%d,%d)+(%d,%d,%d) outside volume %dx%dx%d", x, y, z, w, h, d, c->nx, c->ny, c->nz);
-    const size_t texels = (size_t)w * h * d, need = texels * sizeof(uint32_t);
-    if (nbytes < need) return fail(VPT_ERR_INVALID, "block buffer too short: %zu < %zu", nbytes, need);
-    hipStream_t st = c->ctx->stream;
-    HIP_TRY(hipSetDevice(c->ctx->device));
-    if (x == 0 && y == 0 && w == c->nx && h == c->ny) {        // a run of whole z-slices is contiguous
-        HIP_TRY(hipMemcpyAsync(host_dst, c->ranks + (size_t)z * c->nx * c->ny, need, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        return VPT_OK;
-    }
-    DevBuf<uint32_t> block;
-    HIP_TRY(block.alloc(texels));
-    hipLaunchKernelGGL(k_read_ranks, dim3(stream_grid(texels)), dim3(256), 0, st, (const uint32_t *)c->ranks.get(), c->nx, c->ny, block.get(), x, y, z, w, h, texels);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(host_dst, block, need, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return VPT_OK;
+    return field_read(c, x, y, z, w, h, d, host_dst, nbytes);
 }
-
-// what volume_finish_derived reads of a derived volume's source: the context and the filter
-static void source_stand_in(const vpt_components *c, vpt_volume *v) { v->ctx = c->ctx; v->filter = c->filter; }
 
 extern "C" int vpt_components_keep(vpt_components *c, uint64_t first_rank, uint64_t last_rank, uint32_t fill, vpt_volume **out) {
     if (!c || !out) return fail(VPT_ERR_INVALID, "null argument");
     if (first_rank < 1 || first_rank > last_rank)
         return fail(VPT_ERR_INVALID, "ranks %llu .. %llu: 1 <= first <= last is required", (unsigned long long)first_rank, (unsigned long long)last_rank);
-    const uint32_t M = c->norm16 ? 65535u : 255u;
-    if (fill > M) return fail(VPT_ERR_INVALID, "fill %u: the largest code of %s is %u", fill, format_name(c->format), M);
-    HIP_TRY(hipSetDevice(c->ctx->device));
     // ranks are 32-bit: a first rank beyond them keeps nothing (the empty range 1 .. 0), a last rank beyond them is their largest
     const uint32_t first = first_rank > 0xFFFFFFFFull ? 1u : (uint32_t)first_rank;
     const uint32_t last = first_rank > 0xFFFFFFFFull ? 0u : (uint32_t)std::min<uint64_t>(last_rank, 0xFFFFFFFFull);
-    vpt_volume *d = nullptr;
-    VPT_TRY(volume_create(c->ctx, c->nx, c->ny, c->nz, c->format, false, &d));      // every texel is written below
-    const size_t n = c->voxels();
-    const dim3 grid(stream_grid(n / 4 + 1));
-    if (c->norm16) hipLaunchKernelGGL(k_keep<uint16_t>, grid, dim3(256), 0, c->ctx->stream, (const uint16_t *)c->texels.get(), (const uint32_t *)c->ranks.get(), (uint16_t *)d->linear.get(), n, first, last, fill);
-    else hipLaunchKernelGGL(k_keep<uint8_t>, grid, dim3(256), 0, c->ctx->stream, (const uint8_t *)c->texels.get(), (const uint32_t *)c->ranks.get(), d->linear.get(), n, first, last, fill);
-    vpt_volume source;
-    source_stand_in(c, &source);
-    return volume_finish_derived(&source, d, out);
+    return field_select(c, first, last, fill, out);
 }
 
 extern "C" int vpt_components_label(vpt_components *c, vpt_volume **out) {
     if (!c || !out) return fail(VPT_ERR_INVALID, "null argument");
-    HIP_TRY(hipSetDevice(c->ctx->device));
-    vpt_volume *d = nullptr;
-    VPT_TRY(volume_create(c->ctx, c->nx, c->ny, c->nz, c->norm16 ? VPT_FORMAT_RG16 : VPT_FORMAT_RG8, false, &d));      // every texel is written below
-    const size_t n = c->voxels();
-    const dim3 grid(stream_grid(n / 4 + 1));
-    if (c->norm16) hipLaunchKernelGGL(k_label<uint16_t>, grid, dim3(256), 0, c->ctx->stream, (const uint16_t *)c->texels.get(), (const uint32_t *)c->ranks.get(), (uint16_t *)d->linear.get(), n);
-    else hipLaunchKernelGGL(k_label<uint8_t>, grid, dim3(256), 0, c->ctx->stream, (const uint8_t *)c->texels.get(), (const uint32_t *)c->ranks.get(), d->linear.get(), n);
-    vpt_volume source;
-    source_stand_in(c, &source);
-    return volume_finish_derived(&source, d, out);
+    return field_pair(c, RankChannel(), out);
 }
 
 extern "C" int vpt_components_profile(vpt_components *c, double *ms, uint32_t *launches) {
@@ -621,10 +494,4 @@ extern "C" int vpt_components_profile(vpt_components *c, double *ms, uint32_t *l
     return VPT_OK;
 }
 
-extern "C" int vpt_components_destroy(vpt_components *c) {
-    if (!c) return fail(VPT_ERR_INVALID, "null argument");
-    (void)hipSetDevice(c->ctx->device);
-    (void)hipStreamSynchronize(c->ctx->stream);      // an emitter may still read the buffers
-    delete c;
-    return VPT_OK;
-}
+extern "C" int vpt_components_destroy(vpt_components *c) { return field_destroy(c); }

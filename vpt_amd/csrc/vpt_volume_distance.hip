@@ -5,9 +5,7 @@
 // The transform is separable: g0 = 0 on the seeds and NONE elsewhere, then per axis, in the order x, y, z, out[i] = min over the finite
 // g[j] of g[j] + (i - j)^2.  Everything is integer: positions are below 4096, so a d2 is at most 3 * 4095^2 < 2^26 and NONE = 2^32 - 1 never
 // enters a sum.  No workgroup waits for another: launch boundaries order the phases.
-#include "vpt_internal.h"
-#include <chrono>
-#include <memory>
+#include "vpt_volume_field.h"
 
 #define EDT_NONE 0xFFFFFFFFu
 #define EDT_MAX_AXIS 4096          // vpt_volume_create's limit: a row has at most 64 segments of 64 voxels, positions fit 16 bits
@@ -135,7 +133,7 @@ __global__ __launch_bounds__(64) void k_edt_line(const uint32_t *__restrict__ in
 }
 
 // ---------------------------------------------------------------------------------------------
-// the largest finite d2; emitters k_within<T>, k_channel<T>; read-back of a box of d2
+// the largest finite d2; the distance channel
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_largest(const uint32_t *__restrict__ d2, size_t n, uint32_t *__restrict__ largest) {
     uint32_t m = 0u;
@@ -156,90 +154,19 @@ __device__ __forceinline__ uint32_t isqrt64(unsigned long long p) {
     return (uint32_t)r;
 }
 
-// Plain gathers over the linear storage, four voxels a thread (as k_keep / k_label of the components unit): the texels as one dword (uint8)
-// or qword (uint16), d2 as one uint4, the result as one vector store; the last n % 4 voxels one by one.
-template <typename T> struct Four;
-template <> struct Four<uint8_t> {
-    typedef uint32_t in_t; typedef uint2 pair_t;
-    static __device__ __forceinline__ uint32_t get(in_t w, int i) { return (w >> (8 * i)) & 255u; }
-    static __device__ __forceinline__ in_t pack(const uint32_t *v) { return v[0] | (v[1] << 8) | (v[2] << 16) | (v[3] << 24); }
-    static __device__ __forceinline__ pair_t pack2(const uint32_t *v, const uint32_t *g) {
-        return make_uint2(v[0] | (g[0] << 8) | (v[1] << 16) | (g[1] << 24), v[2] | (g[2] << 8) | (v[3] << 16) | (g[3] << 24));
-    }
+// the distance channel's second value, before k_pair clamps it to the largest code: the distance in rows, `steps` a voxel (vpt_volume_field.h)
+struct DistanceChannel {
+    uint32_t steps2;
+    __device__ __forceinline__ uint32_t operator()(uint32_t d2) const { return isqrt64((unsigned long long)steps2 * d2); }
 };
-template <> struct Four<uint16_t> {
-    typedef uint2 in_t; typedef uint4 pair_t;
-    static __device__ __forceinline__ uint32_t get(in_t w, int i) { return ((i < 2 ? w.x : w.y) >> (16 * (i & 1))) & 65535u; }
-    static __device__ __forceinline__ in_t pack(const uint32_t *v) { return make_uint2(v[0] | (v[1] << 16), v[2] | (v[3] << 16)); }
-    static __device__ __forceinline__ pair_t pack2(const uint32_t *v, const uint32_t *g) {
-        return make_uint4(v[0] | (g[0] << 16), v[1] | (g[1] << 16), v[2] | (g[2] << 16), v[3] | (g[3] << 16));
-    }
-};
-template <typename T>
-__global__ __launch_bounds__(256) void k_within(const T *__restrict__ src, const uint32_t *__restrict__ d2, T *__restrict__ dst, size_t n,
-                                               uint32_t r2_lo, uint32_t r2_hi, uint32_t fill) {
-    typedef Four<T> F;
-    const size_t quads = n / 4, stride = (size_t)gridDim.x * 256, t0 = (size_t)blockIdx.x * 256 + threadIdx.x;
-    for (size_t q = t0; q < quads; q += stride) {
-        const typename F::in_t w = reinterpret_cast<const typename F::in_t *>(src)[q];
-        const uint4 r = reinterpret_cast<const uint4 *>(d2)[q];
-        const uint32_t d[4] = { r.x, r.y, r.z, r.w };
-        uint32_t v[4];
-#pragma unroll
-        for (int i = 0; i < 4; i++) v[i] = (d[i] >= r2_lo && d[i] <= r2_hi) ? F::get(w, i) : fill;
-        reinterpret_cast<typename F::in_t *>(dst)[q] = F::pack(v);
-    }
-    for (size_t i = quads * 4 + t0; i < n; i += stride) { const uint32_t d = d2[i]; dst[i] = (d >= r2_lo && d <= r2_hi) ? src[i] : (T)fill; }
-}
-template <typename T>
-__global__ __launch_bounds__(256) void k_channel(const T *__restrict__ src, const uint32_t *__restrict__ d2, T *__restrict__ dst, size_t n, uint32_t steps2) {
-    typedef Four<T> F;
-    constexpr uint32_t M = (1u << (8 * sizeof(T))) - 1u;
-    const size_t quads = n / 4, stride = (size_t)gridDim.x * 256, t0 = (size_t)blockIdx.x * 256 + threadIdx.x;
-    for (size_t q = t0; q < quads; q += stride) {
-        const typename F::in_t w = reinterpret_cast<const typename F::in_t *>(src)[q];
-        const uint4 r = reinterpret_cast<const uint4 *>(d2)[q];
-        const uint32_t d[4] = { r.x, r.y, r.z, r.w };
-        uint32_t v[4], g[4];
-#pragma unroll
-        for (int i = 0; i < 4; i++) { v[i] = F::get(w, i); g[i] = min(isqrt64((unsigned long long)steps2 * d[i]), M); }
-        reinterpret_cast<typename F::pair_t *>(dst)[q] = F::pack2(v, g);
-    }
-    for (size_t i = quads * 4 + t0; i < n; i += stride) { dst[2 * i] = src[i]; dst[2 * i + 1] = (T)min(isqrt64((unsigned long long)steps2 * d2[i]), M); }
-}
-__global__ __launch_bounds__(256) void k_read_squared(const uint32_t *__restrict__ d2, int nx, int ny, uint32_t *__restrict__ blk, int x0, int y0, int z0,
-                                                     int bw, int bh, size_t texels) {
-    for (size_t t = (size_t)blockIdx.x * 256 + threadIdx.x; t < texels; t += (size_t)gridDim.x * 256) {
-        const int x = (int)(t % (size_t)bw); const size_t r = t / (size_t)bw; const int y = (int)(r % (size_t)bh), z = (int)(r / (size_t)bh);
-        blk[t] = d2[((size_t)(z0 + z) * (size_t)ny + (size_t)(y0 + y)) * (size_t)nx + (size_t)(x0 + x)];
-    }
-}
 
 // ---------------------------------------------------------------------------------------------
 // host
 // ---------------------------------------------------------------------------------------------
-struct vpt_distance {
-    vpt_context *ctx = nullptr;
-    int nx = 0, ny = 0, nz = 0, format = 0, filter = VPT_FILTER_LINEAR;
-    bool norm16 = false;
-    DevBuf<uint8_t> texels;                 // the source's linear texels at the time of the call
-    DevBuf<uint32_t> d2;                    // one squared distance per voxel
+struct vpt_distance : VoxelField {         // the values are d2: one squared distance per voxel
     struct vpt_distance_info info = {};
     double ms[VPT_DISTANCE_PHASES] = {};
-    size_t voxels() const { return (size_t)nx * (size_t)ny * (size_t)nz; }
 };
-
-// grid of a grid-stride kernel over `items`, `per` of them a workgroup
-static unsigned stream_grid(size_t items, size_t per = 256, size_t most = 8192) { return (unsigned)std::max<size_t>(1, std::min<size_t>((items + per - 1) / per, most)); }
-
-// wall time of a phase, the stream drained at its end
-static hipError_t lap(hipStream_t st, std::chrono::steady_clock::time_point *t0, double *ms) {
-    const hipError_t e = hipStreamSynchronize(st);
-    const auto t1 = std::chrono::steady_clock::now();
-    *ms = std::chrono::duration<double, std::milli>(t1 - *t0).count();
-    *t0 = t1;
-    return e;
-}
 
 // the body of vpt_volume_distance behind the argument checks; `d` is freed by the caller on failure
 static int distance_build(vpt_distance *d, uint32_t lo, uint32_t hi, int seeds) {
@@ -254,25 +181,25 @@ static int distance_build(vpt_distance *d, uint32_t lo, uint32_t hi, int seeds) 
     HIP_TRY(hipMemsetAsync(largest, 0, sizeof(uint32_t), st));
     HIP_TRY(hipMemsetAsync(count, 0, EDT_COUNT_SLOTS * sizeof(unsigned long long), st));
     HIP_TRY(hipStreamSynchronize(st));
-    auto t0 = std::chrono::steady_clock::now();
+    PhaseClock clock(st);
     // ---- x: the seeds and the row pass
     const size_t rows = (size_t)d->ny * (size_t)d->nz;
     const uint32_t to_rest = seeds == VPT_DISTANCE_TO_REST ? 1u : 0u;
-    if (d->norm16) hipLaunchKernelGGL(k_edt_x<uint16_t>, dim3(stream_grid(rows, 4, 2048)), dim3(256), 0, st, (const uint16_t *)d->texels.get(), d->d2.get(), d->nx, rows, lo, hi, to_rest, count.get());
-    else hipLaunchKernelGGL(k_edt_x<uint8_t>, dim3(stream_grid(rows, 4, 2048)), dim3(256), 0, st, (const uint8_t *)d->texels.get(), d->d2.get(), d->nx, rows, lo, hi, to_rest, count.get());
+    if (d->norm16) hipLaunchKernelGGL(k_edt_x<uint16_t>, dim3(stream_grid(rows, 4, 2048)), dim3(256), 0, st, (const uint16_t *)d->texels.get(), d->values.get(), d->nx, rows, lo, hi, to_rest, count.get());
+    else hipLaunchKernelGGL(k_edt_x<uint8_t>, dim3(stream_grid(rows, 4, 2048)), dim3(256), 0, st, (const uint8_t *)d->texels.get(), d->values.get(), d->nx, rows, lo, hi, to_rest, count.get());
     HIP_TRY(hipGetLastError());
-    HIP_TRY(lap(st, &t0, &d->ms[0]));
+    HIP_TRY(clock.lap(&d->ms[0]));
     // ---- y: d2 -> other
-    hipLaunchKernelGGL(k_edt_line<1>, dim3(stream_grid((size_t)d->nx * (size_t)d->nz, 64)), dim3(64), 0, st, (const uint32_t *)d->d2.get(), other.get(), stack.get(), d->nx, d->ny, d->nz);
+    hipLaunchKernelGGL(k_edt_line<1>, dim3(stream_grid((size_t)d->nx * (size_t)d->nz, 64)), dim3(64), 0, st, (const uint32_t *)d->values.get(), other.get(), stack.get(), d->nx, d->ny, d->nz);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(lap(st, &t0, &d->ms[1]));
+    HIP_TRY(clock.lap(&d->ms[1]));
     // ---- z: other -> d2
-    hipLaunchKernelGGL(k_edt_line<2>, dim3(stream_grid((size_t)d->nx * (size_t)d->ny, 64)), dim3(64), 0, st, (const uint32_t *)other.get(), d->d2.get(), stack.get(), d->nx, d->ny, d->nz);
+    hipLaunchKernelGGL(k_edt_line<2>, dim3(stream_grid((size_t)d->nx * (size_t)d->ny, 64)), dim3(64), 0, st, (const uint32_t *)other.get(), d->values.get(), stack.get(), d->nx, d->ny, d->nz);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(lap(st, &t0, &d->ms[2]));
+    HIP_TRY(clock.lap(&d->ms[2]));
     // ---- info
     unsigned long long host_count[EDT_COUNT_SLOTS] = {}; uint32_t host_largest = 0;
-    hipLaunchKernelGGL(k_largest, dim3(stream_grid(n)), dim3(256), 0, st, (const uint32_t *)d->d2.get(), n, largest.get());
+    hipLaunchKernelGGL(k_largest, dim3(stream_grid(n)), dim3(256), 0, st, (const uint32_t *)d->values.get(), n, largest.get());
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(host_count, count, sizeof(host_count), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(&host_largest, largest, sizeof(host_largest), hipMemcpyDeviceToHost, st));
@@ -296,11 +223,7 @@ extern "C" int vpt_volume_distance(vpt_volume *src, uint32_t lo, uint32_t hi, in
     vpt_context *ctx = src->ctx;
     HIP_TRY(hipSetDevice(ctx->device));
     std::unique_ptr<vpt_distance> d(new vpt_distance());
-    d->ctx = ctx; d->nx = src->nx; d->ny = src->ny; d->nz = src->nz; d->format = src->format; d->filter = src->filter; d->norm16 = src->norm16;
-    const size_t n = d->voxels(), bytes = n * (size_t)src->vox_bytes;
-    HIP_TRY(d->texels.alloc(bytes));
-    HIP_TRY(d->d2.alloc(n));
-    HIP_TRY(hipMemcpyAsync(d->texels, src->linear, bytes, hipMemcpyDeviceToDevice, ctx->stream));     // behind any upload into src
+    VPT_TRY(field_capture(d.get(), src));
     const int rc = distance_build(d.get(), lo, hi, seeds);
     if (rc != VPT_OK) { (void)hipStreamSynchronize(ctx->stream); return rc; }      // the buffers are freed on return: nothing may still use them
     *out = d.release();
@@ -314,61 +237,19 @@ extern "C" int vpt_distance_info(vpt_distance *d, struct vpt_distance_info *info
 }
 
 extern "C" int vpt_distance_squared(vpt_distance *c, int x, int y, int z, int w, int h, int d, uint32_t *host_dst, size_t nbytes) {
-    if (!c || !host_dst) return fail(VPT_ERR_INVALID, "null argument");
-    if (w < 1 || h < 1 || d < 1 || x < 0 || y < 0 || z < 0 || x + w > c->nx || y + h > c->ny || z + d > c->nz)
-        return fail(VPT_ERR_INVALID, "block (%d,%d,%d)+(%d,%d,%d) outside volume %dx%dx%d", x, y, z, w, h, d, c->nx, c->ny, c->nz);
-    const size_t texels = (size_t)w * h * d, need = texels * sizeof(uint32_t);
-    if (nbytes < need) return fail(VPT_ERR_INVALID, "block buffer too short: %zu < %zu", nbytes, need);
-    hipStream_t st = c->ctx->stream;
-    HIP_TRY(hipSetDevice(c->ctx->device));
-    if (x == 0 && y == 0 && w == c->nx && h == c->ny) {        // a run of whole z-slices is contiguous
-        HIP_TRY(hipMemcpyAsync(host_dst, c->d2 + (size_t)z * c->nx * c->ny, need, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        return VPT_OK;
-    }
-    DevBuf<uint32_t> block;
-    HIP_TRY(block.alloc(texels));
-    hipLaunchKernelGGL(k_read_squared, dim3(stream_grid(texels)), dim3(256), 0, st, (const uint32_t *)c->d2.get(), c->nx, c->ny, block.get(), x, y, z, w, h, texels);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(host_dst, block, need, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return VPT_OK;
+    return field_read(c, x, y, z, w, h, d, host_dst, nbytes);
 }
-
-// what volume_finish_derived reads of a derived volume's source: the context and the filter
-static void source_stand_in(const vpt_distance *d, vpt_volume *v) { v->ctx = d->ctx; v->filter = d->filter; }
 
 extern "C" int vpt_distance_within(vpt_distance *c, uint32_t r2_lo, uint32_t r2_hi, uint32_t fill, vpt_volume **out) {
     if (!c || !out) return fail(VPT_ERR_INVALID, "null argument");
     if (r2_lo > r2_hi) return fail(VPT_ERR_INVALID, "squared distances %u .. %u: from exceeds to", r2_lo, r2_hi);
-    const uint32_t M = c->norm16 ? 65535u : 255u;
-    if (fill > M) return fail(VPT_ERR_INVALID, "fill %u: the largest code of %s is %u", fill, format_name(c->format), M);
-    HIP_TRY(hipSetDevice(c->ctx->device));
-    vpt_volume *d = nullptr;
-    VPT_TRY(volume_create(c->ctx, c->nx, c->ny, c->nz, c->format, false, &d));      // every texel is written below
-    const size_t n = c->voxels();
-    const dim3 grid(stream_grid(n / 4 + 1));
-    if (c->norm16) hipLaunchKernelGGL(k_within<uint16_t>, grid, dim3(256), 0, c->ctx->stream, (const uint16_t *)c->texels.get(), (const uint32_t *)c->d2.get(), (uint16_t *)d->linear.get(), n, r2_lo, r2_hi, fill);
-    else hipLaunchKernelGGL(k_within<uint8_t>, grid, dim3(256), 0, c->ctx->stream, (const uint8_t *)c->texels.get(), (const uint32_t *)c->d2.get(), d->linear.get(), n, r2_lo, r2_hi, fill);
-    vpt_volume source;
-    source_stand_in(c, &source);
-    return volume_finish_derived(&source, d, out);
+    return field_select(c, r2_lo, r2_hi, fill, out);
 }
 
 extern "C" int vpt_distance_channel(vpt_distance *c, int steps, vpt_volume **out) {
     if (!c || !out) return fail(VPT_ERR_INVALID, "null argument");
     if (steps < 1 || steps > 256) return fail(VPT_ERR_INVALID, "steps %d: 1 .. 256 rows of the transfer function per voxel of distance are taken", steps);
-    HIP_TRY(hipSetDevice(c->ctx->device));
-    vpt_volume *d = nullptr;
-    VPT_TRY(volume_create(c->ctx, c->nx, c->ny, c->nz, c->norm16 ? VPT_FORMAT_RG16 : VPT_FORMAT_RG8, false, &d));      // every texel is written below
-    const size_t n = c->voxels();
-    const dim3 grid(stream_grid(n / 4 + 1));
-    const uint32_t steps2 = (uint32_t)(steps * steps);
-    if (c->norm16) hipLaunchKernelGGL(k_channel<uint16_t>, grid, dim3(256), 0, c->ctx->stream, (const uint16_t *)c->texels.get(), (const uint32_t *)c->d2.get(), (uint16_t *)d->linear.get(), n, steps2);
-    else hipLaunchKernelGGL(k_channel<uint8_t>, grid, dim3(256), 0, c->ctx->stream, (const uint8_t *)c->texels.get(), (const uint32_t *)c->d2.get(), d->linear.get(), n, steps2);
-    vpt_volume source;
-    source_stand_in(c, &source);
-    return volume_finish_derived(&source, d, out);
+    return field_pair(c, DistanceChannel{ (uint32_t)(steps * steps) }, out);
 }
 
 extern "C" int vpt_distance_profile(vpt_distance *d, double *ms) {
@@ -377,10 +258,4 @@ extern "C" int vpt_distance_profile(vpt_distance *d, double *ms) {
     return VPT_OK;
 }
 
-extern "C" int vpt_distance_destroy(vpt_distance *d) {
-    if (!d) return fail(VPT_ERR_INVALID, "null argument");
-    (void)hipSetDevice(d->ctx->device);
-    (void)hipStreamSynchronize(d->ctx->stream);      // an emitter may still read the buffers
-    delete d;
-    return VPT_OK;
-}
+extern "C" int vpt_distance_destroy(vpt_distance *d) { return field_destroy(d); }

@@ -246,7 +246,7 @@ extern "C" int vpt_volume_derive_gradient(vpt_volume *src, int op, float gain, v
     VPT_TRY(volume_create(c, src->nx, src->ny, src->nz, src->norm16 ? VPT_FORMAT_RG16 : VPT_FORMAT_RG8, false, &d));   // every texel is written below
     if (src->norm16) launch_gradient<uint16_t>(src, d, op, (unsigned long long)qd);
     else launch_gradient<uint8_t>(src, d, op, (unsigned long long)qd);
-    return volume_finish_derived(src, d, out);
+    return volume_finish_derived(src->ctx, src->filter, d, out);
 }
 
 extern "C" int vpt_volume_read_block(vpt_volume *v, int x, int y, int z, int w, int h, int d, void *host_dst, size_t nbytes) {

@@ -280,7 +280,7 @@ extern "C" int vpt_volume_reduce(vpt_volume *src, vpt_volume **out) {
     else if (f->bytes == 2) rc = f->is_signed ? launch_reduce_channels<K_S16>(src, d) : launch_reduce_channels<K_U16>(src, d);
     else rc = f->is_signed ? launch_reduce_channels<K_S8>(src, d) : launch_reduce_channels<K_U8>(src, d);
     if (rc != VPT_OK) { vpt_volume_destroy(d); return rc; }
-    return volume_finish_derived(src, d, out);
+    return volume_finish_derived(src->ctx, src->filter, d, out);
 }
 
 template <typename T>
@@ -313,7 +313,7 @@ extern "C" int vpt_volume_smooth(vpt_volume *src, int passes, vpt_volume **out) 
         else launch_smooth<uint8_t>(src, (const uint8_t *)from, (uint8_t *)to);
         from = to;
     }
-    const int rc = volume_finish_derived(src, d, out);
+    const int rc = volume_finish_derived(src->ctx, src->filter, d, out);
     if (passes > 1) (void)hipStreamSynchronize(c->stream);   // the scratch is freed on return: its last reader has finished
     return rc;
 }

@@ -252,7 +252,7 @@ extern "C" int vpt_volume_rank(vpt_volume *src, int op, int passes, vpt_volume *
         else launch_pass<uint8_t>(src, pass, (const uint8_t *)from, (uint8_t *)to);
         from = to;
     }
-    const int rc = volume_finish_derived(src, d, out);       // finalized once, after the last launch
+    const int rc = volume_finish_derived(src->ctx, src->filter, d, out);       // finalized once, after the last launch
     if (launches > 1) (void)hipStreamSynchronize(c->stream); // the scratch is freed on return: its last reader has finished
     return rc;
 }

@@ -7,7 +7,6 @@
 // uint32 partial sum per (result x, source y, source z) and channel, the plane pass k_resample_yz sums those over the y and z taps in 64-bit
 // integers and divides once.  No workgroup waits for another: the launch boundary orders the passes.  No float arithmetic, no atomics.
 #include "vpt_internal.h"
-#include <chrono>
 
 #define RS_MAX_AXIS 4096           // vpt_volume_create's limit: every product of two indices below fits 32 bits (8191 * 4096 < 2^25)
 #define RS_LDS_DWORDS 4096         // 16 KiB: the longest source row, 4096 texels x 2 channels x 2 bytes
@@ -157,15 +156,6 @@ __global__ __launch_bounds__(256) void k_resample_nearest(const void *__restrict
 // ---------------------------------------------------------------------------------------------
 // host
 // ---------------------------------------------------------------------------------------------
-// wall time of a pass, the stream drained at its end
-static hipError_t lap(hipStream_t st, std::chrono::steady_clock::time_point *t0, double *ms) {
-    const hipError_t e = hipStreamSynchronize(st);
-    const auto t1 = std::chrono::steady_clock::now();
-    *ms = std::chrono::duration<double, std::milli>(t1 - *t0).count();
-    *t0 = t1;
-    return e;
-}
-
 template <int BYTES>
 static void launch_nearest(const vpt_volume *src, vpt_volume *d) {
     constexpr int PER = BYTES < 4 ? 4 / BYTES : 1;
@@ -187,12 +177,12 @@ static int launch_filtered(const vpt_volume *src, vpt_volume *d, uint32_t *part,
     const uint32_t rows = (uint32_t)src->ny * (uint32_t)src->nz;
     // as many rows as 16 KiB of LDS hold, and no more than give a workgroup 16384 results (a short row of a wide result would be one group's work)
     const uint32_t per = (uint32_t)std::max<size_t>(1, std::min<size_t>((size_t)RS_LDS_DWORDS * 4 / row_bytes, (size_t)16384 / (size_t)d->nx));
-    auto t0 = std::chrono::steady_clock::now();
-    if (ms) HIP_TRY(lap(st, &t0, &ms[0]));                       // what is in front of the passes is not theirs
+    PhaseClock clock(st);
+    if (ms) HIP_TRY(clock.lap(&ms[0]));                       // what is in front of the passes is not theirs
     hipLaunchKernelGGL((k_resample_x<T, CH>), dim3((rows + per - 1) / per), dim3(256), 0, st, (const T *)src->linear.get(), part, src->nx, d->nx, rows, per,
                        (size_t)rows * row_bytes);
     HIP_TRY(hipGetLastError());
-    if (ms) HIP_TRY(lap(st, &t0, &ms[0]));
+    if (ms) HIP_TRY(clock.lap(&ms[0]));
     const unsigned long long S = (unsigned long long)(d->nx >= src->nx ? 2 * d->nx : src->nx) * (unsigned long long)(d->ny >= src->ny ? 2 * d->ny : src->ny) *
                                  (unsigned long long)(d->nz >= src->nz ? 2 * d->nz : src->nz);
     const unsigned long long reciprocal = (unsigned long long)((((unsigned __int128)1) << 64) / (unsigned __int128)(2ull * S));      // 2 S >= 16: below 2^64
@@ -200,7 +190,7 @@ static int launch_filtered(const vpt_volume *src, vpt_volume *d, uint32_t *part,
     hipLaunchKernelGGL((k_resample_yz<T>), dim3((unsigned)((cols + 63) / 64), (unsigned)((d->ny + 3) / 4), (unsigned)d->nz), dim3(256), 0, st,
                        (const uint32_t *)part, (T *)d->linear.get(), cols, src->ny, d->ny, src->nz, d->nz, S, reciprocal);
     HIP_TRY(hipGetLastError());
-    if (ms) HIP_TRY(lap(st, &t0, &ms[1]));
+    if (ms) HIP_TRY(clock.lap(&ms[1]));
     return VPT_OK;
 }
 
@@ -228,7 +218,7 @@ static int resample(vpt_volume *src, int width, int height, int depth, int mode,
             case 4: launch_nearest<4>(src, d); break;
             default: launch_nearest<8>(src, d); break;
         }
-        return volume_finish_derived(src, d, out);
+        return volume_finish_derived(src->ctx, src->filter, d, out);
     }
     DevBuf<uint32_t> part;                                       // the row pass's partial sums: freed when the call returns
     hipError_t e = part.alloc((size_t)width * (size_t)src->ny * (size_t)src->nz * (size_t)src->channels);
@@ -237,7 +227,7 @@ static int resample(vpt_volume *src, int width, int height, int depth, int mode,
     if (src->norm16) rc = src->channels == 2 ? launch_filtered<uint16_t, 2>(src, d, part.get(), ms) : launch_filtered<uint16_t, 1>(src, d, part.get(), ms);
     else rc = src->channels == 2 ? launch_filtered<uint8_t, 2>(src, d, part.get(), ms) : launch_filtered<uint8_t, 1>(src, d, part.get(), ms);
     if (rc != VPT_OK) { (void)hipStreamSynchronize(c->stream); vpt_volume_destroy(d); return rc; }
-    rc = volume_finish_derived(src, d, out);
+    rc = volume_finish_derived(src->ctx, src->filter, d, out);
     (void)hipStreamSynchronize(c->stream);                       // the workspace is freed on return: its last reader has finished
     return rc;
 }

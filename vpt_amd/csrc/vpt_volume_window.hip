@@ -244,12 +244,11 @@ static int source_kind(const vpt_volume *v) {                   // -1: not a one
     return f->bytes == 2 ? (f->is_signed ? SRC_S16 : SRC_U16) : (f->is_signed ? SRC_S8 : SRC_U8);
 }
 static inline size_t voxels(const vpt_volume *v) { return (size_t)v->nx * v->ny * v->nz; }
-static inline unsigned stream_grid(size_t steps, unsigned cap) { return (unsigned)std::max<size_t>(1, std::min<size_t>((steps + 255) / 256, cap)); }
 
 template <int SRC, int OUT>
 static void launch_window_out(const vpt_volume *src, vpt_volume *dst, const WindowParams &p) {
     const size_t n = voxels(src);
-    const dim3 grid(stream_grid(n / 16 + 1, 2048));            // eight workgroups per CU, a stride loop beyond 2^23 voxels
+    const dim3 grid(stream_grid(n / 16 + 1, 256, 2048));            // eight workgroups per CU, a stride loop beyond 2^23 voxels
     if (n % 16 == 0) hipLaunchKernelGGL((k_window<SRC, OUT, true>), grid, dim3(256), 0, src->ctx->stream, (const void *)src->linear, (void *)dst->linear, n, p);
     else hipLaunchKernelGGL((k_window<SRC, OUT, false>), grid, dim3(256), 0, src->ctx->stream, (const void *)src->linear, (void *)dst->linear, n, p);
 }
@@ -296,7 +295,7 @@ extern "C" int vpt_volume_window(vpt_volume *src, double lo, double hi, int out_
         case SRC_S16: launch_window<SRC_S16>(src, d, p); break;
         default: launch_window<SRC_F32>(src, d, p); break;
     }
-    return volume_finish_derived(src, d, out);
+    return volume_finish_derived(src->ctx, src->filter, d, out);
 }
 
 // enqueues k_range of `v` into dev[0..1] (encoded min, max) on the context's stream
@@ -306,7 +305,7 @@ static hipError_t enqueue_range(const vpt_volume *v, int kind, uint32_t *dev) {
     if (e == hipSuccess) e = hipMemsetAsync(dev + 1, 0, 4, st);
     if (e != hipSuccess) return e;
     const size_t n = voxels(v);
-    const dim3 grid(stream_grid(n * (size_t)v->vox_bytes / 16 + 1, 2048));
+    const dim3 grid(stream_grid(n * (size_t)v->vox_bytes / 16 + 1, 256, 2048));
     const void *s = (const void *)v->linear;
     switch (kind) {
         case SRC_U8: hipLaunchKernelGGL(k_range<SRC_U8>, grid, dim3(256), 0, st, s, n, dev); break;
@@ -364,7 +363,7 @@ extern "C" int vpt_volume_code_histogram(vpt_volume *v, uint32_t *bins, size_t n
     HIP_TRY(hipMemsetAsync(dev, 0, want * sizeof(uint32_t), c->stream));
     if (wide) HIP_TRY(enqueue_range(v, kind, dev + want));
     const size_t n = voxels(v);
-    const dim3 grid(stream_grid(n * (size_t)v->vox_bytes / 16 + 1, wide ? 1280 : 2048));
+    const dim3 grid(stream_grid(n * (size_t)v->vox_bytes / 16 + 1, 256, wide ? 1280 : 2048));
     const void *s = (const void *)v->linear;
     switch (kind) {
         case SRC_U8: hipLaunchKernelGGL(k_code_histogram<SRC_U8>, grid, dim3(256), 0, c->stream, s, n, dev, (const uint32_t *)(dev + want)); break;

@@ -80,6 +80,17 @@ def filter_code(filter):
         return N.FILTER_QUASI_CUBIC
     return N.FILTER_NEAREST
 
+def _derived_volume(out, handle, modality, meta, dims):
+    """``out``, a new Volume, made ready around the derived native volume ``handle``: ``modality`` with the dimensions ``dims`` in one
+    block, and a copy of ``meta``"""
+    out.texture = handle
+    out.modality = dict(modality, dimensions=dict(dims), placements=[{'index': 0, 'position': {'x': 0, 'y': 0, 'z': 0}}])
+    out.metadata = {'meta': dict(meta), 'modalities': [out.modality],
+                    'blocks': [{'url': None, 'format': 'raw', 'dimensions': dict(dims)}]}
+    out.ready = True
+    return out
+
+
 class Volume(EventTarget):
     """Volume.js:3-127.  ``gl`` is a vpt_amd.Context.  ``getTexture()`` returns the native volume handle
     once ``ready`` (the reference returns the WebGLTexture), else None."""
@@ -352,13 +363,7 @@ class Volume(EventTarget):
     # ---- extension: the next coarser level and binomial smoothing (include/vpt.h; DESIGN.md "Binomial smoothing and 2x reduction") ----
     def _same_format(self, handle, dims):
         """the ready Volume around a derived native volume of this volume's format with the dimensions ``dims``"""
-        out = type(self)(self._gl)
-        out.texture = handle
-        out.modality = dict(self.modality, dimensions=dict(dims), placements=[{'index': 0, 'position': {'x': 0, 'y': 0, 'z': 0}}])
-        out.metadata = {'meta': dict((self.metadata or {}).get('meta', {})), 'modalities': [out.modality],
-                        'blocks': [{'url': None, 'format': 'raw', 'dimensions': dict(dims)}]}
-        out.ready = True
-        return out
+        return _derived_volume(type(self)(self._gl), handle, self.modality, (self.metadata or {}).get('meta', {}), dims)
 
     def reduce(self, levels=1):
         """A new, ready volume in this volume's format and with its filter, ``levels`` times reduced to ceil(n / 2) texels per axis: every
@@ -522,9 +527,11 @@ class Volume(EventTarget):
         return n.value
 
 
-class Components:
-    """The connected components of a value range of a volume (``Volume.components``): per-voxel ranks and the component list on the device.
-    Label once, select several times.  Outlives the volume it was made from; ``destroy()`` frees the device memory."""
+class _VoxelField:
+    """What ``Components`` and ``Distance`` share: the native handle of one uint32 per voxel over a snapshot of an R8 / R16 volume, the box
+    read-back of those values and the description of the volumes derived from them.  A subclass names its native functions and the noun of
+    the message raised once it has been destroyed."""
+    _noun = _destroy = _read = None
 
     def __init__(self, source, handle):
         self._h = handle
@@ -532,20 +539,42 @@ class Components:
         dims = source.modality['dimensions']
         self._shape = (dims['depth'], dims['height'], dims['width'])
         self._norm16 = source.modality.get('internalFormat') == GL_R16_EXT
-        # what a derived volume's description is made from (Volume._same_format)
-        self._like = Volume(source._gl)
-        self._like.modality = dict(source.modality)
-        self._like.metadata = {'meta': dict((source.metadata or {}).get('meta', {}))}
+        # what a derived volume's description is made from (_derived_volume)
+        self._modality = dict(source.modality)
+        self._meta = dict((source.metadata or {}).get('meta', {}))
 
     def _handle(self):
         if not self._h:
-            raise RuntimeError('the components have been destroyed')
+            raise RuntimeError('the %s have been destroyed' % self._noun)
         return self._h
 
     def destroy(self):
         if self._h:
-            N.lib().vpt_components_destroy(self._h)
+            getattr(N.lib(), self._destroy)(self._h)
             self._h = None
+
+    def _values(self, x, y, z, w, h, d):
+        """uint32 [d][h][w]: the values of a box of voxels (the whole volume by default)"""
+        w = self._shape[2] - x if w is None else w
+        h = self._shape[1] - y if h is None else h
+        d = self._shape[0] - z if d is None else d
+        out = np.empty((int(d), int(h), int(w)), np.uint32)
+        N.check(getattr(N.lib(), self._read)(self._handle(), int(x), int(y), int(z), int(w), int(h), int(d), out.ctypes.data_as(C.c_void_p), out.nbytes))
+        return out
+
+    def _derived(self, handle, pair=False):
+        """the ready Volume around a native volume derived from the field: of the source's format, or (``pair``) RG8 / RG16"""
+        out = _derived_volume(Volume(self._gl), handle, self._modality, self._meta, self._modality['dimensions'])
+        if pair:
+            out.modality.update({'format': GL_RG, 'internalFormat': GL_RG16_EXT if self._norm16 else GL_RG8,
+                                 'type': GL_UNSIGNED_SHORT if self._norm16 else GL_UNSIGNED_BYTE})
+        return out
+
+
+class Components(_VoxelField):
+    """The connected components of a value range of a volume (``Volume.components``): per-voxel ranks and the component list on the device.
+    Label once, select several times.  Outlives the volume it was made from; ``destroy()`` frees the device memory."""
+    _noun, _destroy, _read = 'components', 'vpt_components_destroy', 'vpt_components_ranks'
 
     @property
     def info(self):
@@ -564,12 +593,7 @@ class Components:
 
     def ranks(self, x=0, y=0, z=0, w=None, h=None, d=None):
         """uint32 [d][h][w]: the ranks of a box of voxels (the whole volume by default)"""
-        w = self._shape[2] - x if w is None else w
-        h = self._shape[1] - y if h is None else h
-        d = self._shape[0] - z if d is None else d
-        out = np.empty((int(d), int(h), int(w)), np.uint32)
-        N.check(N.lib().vpt_components_ranks(self._handle(), int(x), int(y), int(z), int(w), int(h), int(d), out.ctypes.data_as(C.c_void_p), out.nbytes))
-        return out
+        return self._values(x, y, z, w, h, d)
 
     def keep(self, first=1, last=None, fill=0):
         """A new, ready volume of the source's size, format and filter: the source's code where first <= rank <= last (last None: every
@@ -578,17 +602,14 @@ class Components:
         first, last, fill = check_keep(first, last, fill, 65535 if self._norm16 else 255)
         h = C.c_void_p()
         N.check(N.lib().vpt_components_keep(self._handle(), first, last, fill, C.byref(h)))
-        return self._like._same_format(h, self._like.modality['dimensions'])
+        return self._derived(h)
 
     def label(self):
         """A new, ready RG8 / RG16 volume with the source's filter: (code, min(rank, M)) (vpt_amd.label_texels states it): the rows of a 2-D
         transfer function select the structures"""
         h = C.c_void_p()
         N.check(N.lib().vpt_components_label(self._handle(), C.byref(h)))
-        out = self._like._same_format(h, self._like.modality['dimensions'])
-        out.modality.update({'format': GL_RG, 'internalFormat': GL_RG16_EXT if self._norm16 else GL_RG8,
-                             'type': GL_UNSIGNED_SHORT if self._norm16 else GL_UNSIGNED_BYTE})
-        return out
+        return self._derived(h, pair=True)
 
     def profile(self):
         """(for measurements) ({phase: milliseconds}, merge launches, flatten launches) of the labelling"""
@@ -599,30 +620,10 @@ class Components:
         return dict(zip(names, ms)), int(launches[0]), int(launches[1])
 
 
-class Distance:
+class Distance(_VoxelField):
     """The squared Euclidean distances to a value range of a volume, or to its complement (``Volume.distance``): one uint32 per voxel on
     the device.  Transform once, select several times.  Outlives the volume it was made from; ``destroy()`` frees the device memory."""
-
-    def __init__(self, source, handle):
-        self._h = handle
-        self._gl = source._gl
-        dims = source.modality['dimensions']
-        self._shape = (dims['depth'], dims['height'], dims['width'])
-        self._norm16 = source.modality.get('internalFormat') == GL_R16_EXT
-        # what a derived volume's description is made from (Volume._same_format)
-        self._like = Volume(source._gl)
-        self._like.modality = dict(source.modality)
-        self._like.metadata = {'meta': dict((source.metadata or {}).get('meta', {}))}
-
-    def _handle(self):
-        if not self._h:
-            raise RuntimeError('the distances have been destroyed')
-        return self._h
-
-    def destroy(self):
-        if self._h:
-            N.lib().vpt_distance_destroy(self._h)
-            self._h = None
+    _noun, _destroy, _read = 'distances', 'vpt_distance_destroy', 'vpt_distance_squared'
 
     @property
     def info(self):
@@ -633,12 +634,7 @@ class Distance:
 
     def squared(self, x=0, y=0, z=0, w=None, h=None, d=None):
         """uint32 [d][h][w]: the squared distances of a box of voxels (the whole volume by default); 0xFFFFFFFF: there is no seed"""
-        w = self._shape[2] - x if w is None else w
-        h = self._shape[1] - y if h is None else h
-        d = self._shape[0] - z if d is None else d
-        out = np.empty((int(d), int(h), int(w)), np.uint32)
-        N.check(N.lib().vpt_distance_squared(self._handle(), int(x), int(y), int(z), int(w), int(h), int(d), out.ctypes.data_as(C.c_void_p), out.nbytes))
-        return out
+        return self._values(x, y, z, w, h, d)
 
     def within(self, r2_lo=0, r2_hi=None, fill=0):
         """A new, ready volume of the source's size, format and filter: the source's code where r2_lo <= d2 <= r2_hi (r2_hi None:
@@ -647,7 +643,7 @@ class Distance:
         r2_lo, r2_hi, fill = check_within(r2_lo, r2_hi, fill, 65535 if self._norm16 else 255)
         h = C.c_void_p()
         N.check(N.lib().vpt_distance_within(self._handle(), r2_lo, r2_hi, fill, C.byref(h)))
-        return self._like._same_format(h, self._like.modality['dimensions'])
+        return self._derived(h)
 
     def channel(self, steps=1):
         """A new, ready RG8 / RG16 volume with the source's filter: (code, min(isqrt(steps^2 d2), M)) (vpt_amd.channel_texels states it):
@@ -655,10 +651,7 @@ class Distance:
         from .distance import check_steps
         h = C.c_void_p()
         N.check(N.lib().vpt_distance_channel(self._handle(), check_steps(steps), C.byref(h)))
-        out = self._like._same_format(h, self._like.modality['dimensions'])
-        out.modality.update({'format': GL_RG, 'internalFormat': GL_RG16_EXT if self._norm16 else GL_RG8,
-                             'type': GL_UNSIGNED_SHORT if self._norm16 else GL_UNSIGNED_BYTE})
-        return out
+        return self._derived(h, pair=True)
 
     def profile(self):
         """(for measurements) {'x', 'y', 'z'}: milliseconds of the three passes of the transform"""
