@@ -180,7 +180,8 @@ VPT_API int vpt_volume_derive_gradient(vpt_volume *src, int op, float gain, vpt_
 VPT_API int vpt_volume_read_block(vpt_volume *vol, int x, int y, int z, int width, int height, int depth, void *host_dst, size_t nbytes);
 /* counts per bin, uint32: one-channel R8 / R16 volumes 256 bins of the value's top 8 bits (nbins = 256); RG8 / RG16 256 x 256 bins of
  * both channels' top 8 bits, bins[g * 256 + v] (nbins = 65536): what a 2-D transfer-function editor draws behind its bumps.  Other
- * formats: VPT_ERR_UNSUPPORTED.  Blocks. */
+ * formats: VPT_ERR_UNSUPPORTED.  A volume of more than 2^32 - 1 voxels: VPT_ERR_UNSUPPORTED, naming the count (the bins are 32-bit: one
+ * that held the background of such a volume would wrap; vpt_volume_components refuses likewise).  Blocks. */
 VPT_API int vpt_volume_histogram(vpt_volume *vol, uint32_t *bins, size_t nbins);
 /* ---- value-range window (window / level) on the device (extension; DESIGN.md "Value-range window") */
 /* Places a one-channel volume of any scalar format on the transfer function's [0, 1] axis: a new VPT_FORMAT_R8 (M = 255) or VPT_FORMAT_R16
@@ -205,7 +206,8 @@ VPT_API int vpt_volume_window(vpt_volume *src, double lo, double hi, int out_for
  * volume without a texel that is not NaN: VPT_ERR_INVALID) of the same source formats.  Blocks. */
 VPT_API int vpt_volume_range(vpt_volume *vol, double *lo, double *hi);
 /* counts per code at full resolution, uint32: nbins = 2^B (256 or 65536), bin = code for R8 / R16, code + 2^(B-1) for R8_SNORM /
- * R16_SNORM.  R32F and every other format: VPT_ERR_UNSUPPORTED.  Blocks.  (vpt_volume_histogram counts the top 8 bits.) */
+ * R16_SNORM.  R32F and every other format: VPT_ERR_UNSUPPORTED.  A volume of more than 2^32 - 1 voxels: VPT_ERR_UNSUPPORTED, naming the
+ * count (the bins are 32-bit).  Blocks.  (vpt_volume_histogram counts the top 8 bits.) */
 VPT_API int vpt_volume_code_histogram(vpt_volume *vol, uint32_t *bins, size_t nbins);
 
 /* ---- the next coarser level and binomial smoothing on the device (extension; DESIGN.md "Binomial smoothing and 2x reduction") */

@@ -276,12 +276,13 @@ extern "C" int vpt_volume_histogram(vpt_volume *v, uint32_t *bins, size_t nbins)
     if (!one && !two) return fail(VPT_ERR_UNSUPPORTED, "histograms are counted for R8, R16, RG8 and RG16 volumes, not for %s", format_name(v->format));
     const size_t want = one ? 256 : 65536;
     if (nbins != want) return fail(VPT_ERR_INVALID, "a histogram of an %s volume has %zu bins, not %zu", format_name(v->format), want, nbins);
+    const size_t nvox = (size_t)v->nx * v->ny * v->nz;
+    if (nvox > 0xFFFFFFFFull) return fail(VPT_ERR_UNSUPPORTED, "histogram: %zu voxels exceed 2^32 - 1 (the bins are 32-bit)", nvox);
     vpt_context *c = v->ctx;
     HIP_TRY(hipSetDevice(c->device));
     DevBuf<uint32_t> dev;
     HIP_TRY(dev.alloc(want));
     HIP_TRY(hipMemsetAsync(dev, 0, want * sizeof(uint32_t), c->stream));
-    const size_t nvox = (size_t)v->nx * v->ny * v->nz;
     const size_t loads = nvox * (size_t)v->vox_bytes / 16 + 1;           // 16 bytes per thread and step
     unsigned grid = (unsigned)std::min<size_t>((loads + 255) / 256, one ? 2048 : 1024);
     if (one && v->norm16) hipLaunchKernelGGL(k_histogram<uint16_t>, dim3(grid), dim3(256), 0, c->stream, (const uint16_t *)v->linear.get(), nvox, dev.get());

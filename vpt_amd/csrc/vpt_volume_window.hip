@@ -355,6 +355,7 @@ extern "C" int vpt_volume_code_histogram(vpt_volume *v, uint32_t *bins, size_t n
     const bool wide = kind == SRC_U16 || kind == SRC_S16;
     const size_t want = wide ? 65536 : 256;
     if (nbins != want) return fail(VPT_ERR_INVALID, "a code histogram of an %s volume has %zu bins, not %zu", format_name(v->format), want, nbins);
+    if (voxels(v) > 0xFFFFFFFFull) return fail(VPT_ERR_UNSUPPORTED, "code histogram: %zu voxels exceed 2^32 - 1 (the bins are 32-bit)", voxels(v));
     vpt_context *c = v->ctx;
     HIP_TRY(hipSetDevice(c->device));
     DevBuf<uint32_t> buf;                                       // the bins, then k_range's two words

@@ -290,7 +290,8 @@ class Volume(EventTarget):
         return out
 
     def histogram(self):
-        """uint32 counts: [256] bins of the value's top 8 bits (R8 / R16), or [256][256], [g][v], of both channels' (RG8 / RG16)"""
+        """uint32 counts: [256] bins of the value's top 8 bits (R8 / R16), or [256][256], [g][v], of both channels' (RG8 / RG16).  A volume
+        of more than 2^32 - 1 voxels raises VptError (ERR_UNSUPPORTED): the bins are 32-bit."""
         channels, _ = self._texel_layout()
         bins = np.zeros(65536 if channels == 2 else 256, dtype=np.uint32)
         N.check(N.lib().vpt_volume_histogram(self.texture, bins.ctypes.data_as(C.POINTER(C.c_uint32)), bins.size))
@@ -348,7 +349,8 @@ class Volume(EventTarget):
 
     def code_histogram(self):
         """uint32 counts per code at full resolution: [256] (R8, R8_SNORM) or [65536] (R16, R16_SNORM) bins; bin = code, for SNORM
-        code + 128 / code + 32768"""
+        code + 128 / code + 32768.  A volume of more than 2^32 - 1 voxels raises VptError (ERR_UNSUPPORTED): the bins are 32-bit; so do
+        ``percentile_window`` and a RenderingContext whose window is given in percentiles."""
         fmt = self.native_format()[0]
         bins = np.zeros(65536 if fmt in (N.FORMAT_R16, N.FORMAT_R16_SNORM) else 256, dtype=np.uint32)
         N.check(N.lib().vpt_volume_code_histogram(self.texture, bins.ctypes.data_as(C.POINTER(C.c_uint32)), bins.size))
