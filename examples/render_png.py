@@ -78,6 +78,15 @@ def main():
                     "--pitch is the camera's)")
     ap.add_argument("--resample-mode", default="filtered", choices=["filtered", "nearest"], help="filtered: linear interpolation / area average in integers "
                     "(R8, RG8, R16, RG16); nearest: texels are copied (labels and masks, every unpacked format)")
+    ap.add_argument("--combine", default=None, metavar="FILE", help="a second volume (.bvp, or raw bytes of the primary's --dims; see --combine-bits) combined with the "
+                    "volume on the device: behind --resample and in front of --rank, or ('pair') where --gradient runs")
+    ap.add_argument("--combine-op", default="mask", choices=["mask", "min", "max", "absdiff", "blend", "pair"], help="mask: keep the codes where LO <= second <= HI; "
+                    "blend: ((WA a + WB b + 128) >> 8) + OFFSET, clamped; pair: the second volume becomes the transfer function's second axis")
+    ap.add_argument("--combine-bits", type=int, default=8, choices=[8, 16], help="sample size of a raw --combine file")
+    ap.add_argument("--combine-range", default=None, metavar="LO,HI", help="the codes of the second volume that --combine-op mask keeps (default: 1 and above)")
+    ap.add_argument("--combine-weights", default=None, metavar="WA,WB,OFFSET", help="the weights (1/256 units, -4096 .. 4096) and the offset of --combine-op blend")
+    ap.add_argument("--combine-resample", default=None, choices=["nearest", "filtered"], help="bring a second volume of another size to the volume's grid first "
+                    "(nearest for masks and labels)")
     ap.add_argument("--smooth", type=int, default=None, metavar="N", help="binomial 3 x 3 x 3 smoothing passes (1 .. 8) on the device, behind the window (R8 / R16 volumes)")
     ap.add_argument("--reduce", type=int, default=None, metavar="N", help="reduce the volume N times to half its resolution on the device, behind the smoothing")
     ap.add_argument("--yaw", type=float, default=0.6)
@@ -108,7 +117,21 @@ def main():
         resample = {'size': [int(x) for x in a.resample.split(',')], 'mode': a.resample_mode}
     elif a.spacing is not None:
         resample = {'spacing': [float(x) for x in a.spacing.split(',')], 'pitch': a.voxel_pitch, 'mode': a.resample_mode}
-    rc = vpt_amd.RenderingContext({'resolution': (a.width, a.height), 'components': components, 'distance': distance, 'filter': a.filter, 'rng': GoldenRatioRng(),
+    combine = None
+    if a.combine is not None:
+        if a.combine.endswith(".bvp"):
+            second = vpt_amd.BVPReader(vpt_amd.FileLoader(a.combine))
+        else:
+            w, h, d = a.dims
+            second = vpt_amd.RAWReader(vpt_amd.FileLoader(a.combine), {'width': w, 'height': h, 'depth': d, 'bits': a.combine_bits})
+        combine = {'reader': second, 'op': a.combine_op, 'resample': a.combine_resample}
+        if a.combine_op == 'mask':
+            lo, _, hi = (a.combine_range or '1,').partition(',')
+            combine.update({'lo': int(lo), 'hi': int(hi) if hi.strip() else None})
+        elif a.combine_op == 'blend':
+            wa, wb, offset = (int(x) for x in (a.combine_weights or '128,128,0').split(','))
+            combine.update({'wa': wa, 'wb': wb, 'offset': offset})
+    rc = vpt_amd.RenderingContext({'resolution': (a.width, a.height), 'components': components, 'combine': combine, 'distance': distance, 'filter': a.filter, 'rng': GoldenRatioRng(),
                                    'gradient': a.gradient, 'gradientGain': a.gradient_gain,
                                    'window': None if window == 'auto' else window, 'windowFormat': a.window_format,
                                    'rank': a.rank, 'rankPasses': a.rank_passes, 'smooth': a.smooth, 'reduce': a.reduce, 'resample': resample})
@@ -138,7 +161,7 @@ def main():
     rc.chooseRenderer(a.renderer)
     rc.chooseToneMapper(a.tonemapper)
     if a.tf == "colour":
-        rc.renderer.setTransferFunction(colour_tf(256, 64 if a.gradient or a.components_label or a.distance_channel is not None else 1))
+        rc.renderer.setTransferFunction(colour_tf(256, 64 if a.gradient or a.components_label or a.distance_channel is not None or (a.combine and a.combine_op == 'pair') else 1))
     if a.extinction is not None and hasattr(rc.renderer, 'extinction'):
         rc.renderer.extinction = a.extinction
     rc.renderer.reset()

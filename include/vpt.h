@@ -368,6 +368,46 @@ VPT_API int vpt_volume_resample(vpt_volume *src, int width, int height, int dept
 #define VPT_RESAMPLE_PHASES 2
 VPT_API int vpt_volume_resample_timed(vpt_volume *src, int width, int height, int depth, int mode, vpt_volume **out, double *ms);
 
+/* ---- two volumes combined or compared texel by texel on the device (extension; DESIGN.md "Combining two volumes") */
+/* Every other volume operation takes one volume.  This one brings a second into the chain: a mask made on a filtered copy cuts the
+ * original, a label file becomes the second channel, two acquisitions are subtracted, a volume meets its own derivative (unsharp masking).
+ *   a: R8 or R16.  b: R8, RG8, R16 or RG16; b_channel (0, or 1 for a two-channel b; otherwise VPT_ERR_INVALID) names the channel of b that
+ *   is read.  Every other format: VPT_ERR_UNSUPPORTED, naming it.  a and b belong to one context and have the same width, height and depth,
+ *   otherwise VPT_ERR_INVALID (a size mismatch names both sizes; vpt_volume_resample brings two grids together).  a and b may be the same
+ *   handle.  Below A and B are the whole unsigned codes of a texel of a and of the named channel of the same texel of b, M = 255 / 65535 the
+ *   largest code of a's format and Mb that of b's.
+ *   VPT_COMBINE_MASK: A where lo <= B <= hi, `fill` elsewhere; result in a's format.  b may be 8- or 16-bit whatever a is.  lo > hi,
+ *     hi > Mb or fill > M: VPT_ERR_INVALID.
+ *   VPT_COMBINE_MIN, _MAX, _ABSDIFF: min(A, B), max(A, B), |A - B|; a's format.
+ *   VPT_COMBINE_BLEND: clamp(((wa A + wb B + 128) >> 8) + offset, 0, M); a's format.  wa and wb are in 1/256 units and lie in
+ *     -4096 .. 4096, offset in -65535 .. 65535, otherwise VPT_ERR_INVALID.  >> is the arithmetic shift: the quotient is
+ *     floor(x / 256 + 1 / 2), a half rounds up (-0.5 -> 0, -1.5 -> -1).  |wa A + wb B + 128| <= 2 * 4096 * 65535 + 128 < 2^31: 32-bit
+ *     integers are exact.  (256, 256, 0) is the saturating sum, (256, -256, 0) the saturating difference, (128, 128, 0) the average
+ *     (A + B + 1) >> 1, (-256, 0, M) the inversion, (512, -256, 0) with b = smooth(a) unsharp masking, (0, 256, 0) a channel of b alone.
+ *   VPT_COMBINE_PAIR: (A, B) as an RG8 / RG16 volume.
+ *   Any other op: VPT_ERR_INVALID.  Every op but MASK needs b's channel to be as wide as a's: VPT_ERR_UNSUPPORTED, naming both formats.
+ *   Fields of the params an op does not name are not read.
+ * vpt_amd.combine_texels states the ops in numpy, vpt_amd.compare_stats the counts below.
+ * The result is a new, finalized volume on the sources' context with a's filter, enqueued on the context's stream behind any upload into
+ * a or b (they need not be finalized); neither source is changed and both may be destroyed afterwards.  Every size vpt_volume_create
+ * takes is taken.  Two runs give identical bytes. */
+#define VPT_COMBINE_MASK    0
+#define VPT_COMBINE_MIN     1
+#define VPT_COMBINE_MAX     2
+#define VPT_COMBINE_ABSDIFF 3
+#define VPT_COMBINE_BLEND   4
+#define VPT_COMBINE_PAIR    5
+struct vpt_combine_params { int op; int b_channel; uint32_t lo, hi, fill; int32_t wa, wb, offset; };
+VPT_API int vpt_volume_combine(vpt_volume *a, vpt_volume *b, const struct vpt_combine_params *p, vpt_volume **out);
+/* (for measurements) the same, and in *ms the milliseconds of the combining pass alone, the stream drained in front of it and behind it
+ * (the finalize of the result, which follows, costs more than the pass) */
+VPT_API int vpt_volume_combine_timed(vpt_volume *a, vpt_volume *b, const struct vpt_combine_params *p, vpt_volume **out, double *ms);
+/* a and b as above (mixed widths are taken), no volume is made: out = { voxels, differing (A != B), max |A - B|, sum |A - B|,
+ * sum (A - B)^2, #(lo_a <= A <= hi_a), #(lo_b <= B <= hi_b), #(both) }, exact, on whole codes; a range with lo > hi counts nothing.
+ * More than 2^32 - 1 voxels: VPT_ERR_UNSUPPORTED, naming the count; up to there sum (A - B)^2 <= (2^32 - 1) * 65535^2 < 2^64, so no word
+ * of `out` can wrap.  Dice 2 both / (in_a + in_b), Jaccard, MSE and PSNR follow on the host.  Blocks.  Two runs give identical counts. */
+VPT_API int vpt_volume_compare(vpt_volume *a, vpt_volume *b, int b_channel, uint32_t lo_a, uint32_t hi_a, uint32_t lo_b, uint32_t hi_b, uint64_t out[8]);
+
 /* ---- renderer: AbstractRenderer.js:17-116 and the four subclasses */
 /* new R(gl, volume, camera, environmentTexture, {resolution}) — AbstractRenderer.js:17-49; width != height is the
  * documented extension (uInverseResolution = (1/W, 1/H)).  Buffers are allocated as in _rebuildBuffers :78-92. */

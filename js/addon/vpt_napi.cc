@@ -223,6 +223,53 @@ static napi_value VolumeResample(napi_env env, napi_callback_info info) {
     VPT_CHECK(vpt_volume_resample(v, w, h, d, mode, &out));
     return make_external(env, out);
 }
+// ---- two volumes combined or compared -----------------------------------------------------------------
+static bool get_u32(napi_env env, napi_value v, uint32_t *out);
+// the ten arguments volumeCombine and volumeCombineTimed share: (a, b, op, channel, lo, hi, fill, wa, wb, offset)
+static bool get_combine(napi_env env, napi_callback_info info, vpt_volume **va, vpt_volume **vb, struct vpt_combine_params *p) {
+    napi_value a[10]; int32_t op, channel, wa, wb, offset;
+    if (!get_args(env, info, 10, a) || !get_handle(env, a[0], va) || !get_handle(env, a[1], vb) || !get_i32(env, a[2], &op) || !get_i32(env, a[3], &channel) ||
+        !get_u32(env, a[4], &p->lo) || !get_u32(env, a[5], &p->hi) || !get_u32(env, a[6], &p->fill) || !get_i32(env, a[7], &wa) || !get_i32(env, a[8], &wb) ||
+        !get_i32(env, a[9], &offset)) return false;
+    p->op = op; p->b_channel = channel; p->wa = wa; p->wb = wb; p->offset = offset;
+    return true;
+}
+// volumeCombine(a, b, op, channel, lo, hi, fill, wa, wb, offset) -> a new volume handle: a and channel `channel` of b combined by VPT_COMBINE_*
+static napi_value VolumeCombine(napi_env env, napi_callback_info info) {
+    vpt_volume *va, *vb; struct vpt_combine_params p = {};
+    if (!get_combine(env, info, &va, &vb, &p)) return nullptr;
+    vpt_volume *out = nullptr;
+    VPT_CHECK(vpt_volume_combine(va, vb, &p, &out));
+    return make_external(env, out);
+}
+// volumeCombineTimed(the same) -> [a new volume handle, the milliseconds of the combining pass alone]
+static napi_value VolumeCombineTimed(napi_env env, napi_callback_info info) {
+    vpt_volume *va, *vb; struct vpt_combine_params p = {};
+    if (!get_combine(env, info, &va, &vb, &p)) return nullptr;
+    vpt_volume *out = nullptr; double ms = 0.0;
+    VPT_CHECK(vpt_volume_combine_timed(va, vb, &p, &out, &ms));
+    napi_value pair, e;
+    napi_create_array_with_length(env, 2, &pair);
+    napi_set_element(env, pair, 0, make_external(env, out));
+    napi_create_double(env, ms, &e); napi_set_element(env, pair, 1, e);
+    return pair;
+}
+// volumeCompare(a, b, channel, loA, hiA, loB, hiB) -> the eight 64-bit counts as sixteen numbers, (low, high) 32-bit halves: a count can
+// pass 2^53, which the doubles componentsInfo returns its counts in do not hold exactly
+static napi_value VolumeCompare(napi_env env, napi_callback_info info) {
+    napi_value a[7]; vpt_volume *va, *vb; int32_t channel; uint32_t r[4];
+    if (!get_args(env, info, 7, a) || !get_handle(env, a[0], &va) || !get_handle(env, a[1], &vb) || !get_i32(env, a[2], &channel) || !get_u32(env, a[3], &r[0]) ||
+        !get_u32(env, a[4], &r[1]) || !get_u32(env, a[5], &r[2]) || !get_u32(env, a[6], &r[3])) return nullptr;
+    uint64_t counts[8] = {};
+    VPT_CHECK(vpt_volume_compare(va, vb, channel, r[0], r[1], r[2], r[3], counts));
+    napi_value out, e;
+    napi_create_array_with_length(env, 16, &out);
+    for (int k = 0; k < 8; k++) {
+        napi_create_double(env, (double)(uint32_t)(counts[k] & 0xFFFFFFFFull), &e); napi_set_element(env, out, 2 * k, e);
+        napi_create_double(env, (double)(uint32_t)(counts[k] >> 32), &e); napi_set_element(env, out, 2 * k + 1, e);
+    }
+    return out;
+}
 // volumeRange(volume) -> [lo, hi]: the smallest and the largest code or value
 static napi_value VolumeRange(napi_env env, napi_callback_info info) {
     napi_value a[1]; vpt_volume *v;
@@ -689,6 +736,7 @@ static napi_value Init(napi_env env, napi_value exports) {
     CONST(VPT_GRADIENT_CENTRAL); CONST(VPT_GRADIENT_SOBEL);
     EXPORT("volumeWindow", VolumeWindow); EXPORT("volumeRange", VolumeRange); EXPORT("volumeCodeHistogram", VolumeCodeHistogram);
     EXPORT("volumeReduce", VolumeReduce); EXPORT("volumeSmooth", VolumeSmooth); EXPORT("volumeRank", VolumeRank); EXPORT("volumeResample", VolumeResample);
+    EXPORT("volumeCombine", VolumeCombine); EXPORT("volumeCombineTimed", VolumeCombineTimed); EXPORT("volumeCompare", VolumeCompare);
     EXPORT("volumeComponents", VolumeComponents); EXPORT("componentsInfo", ComponentsInfo); EXPORT("componentsList", ComponentsList);
     EXPORT("componentsRanks", ComponentsRanks); EXPORT("componentsKeep", ComponentsKeep); EXPORT("componentsLabel", ComponentsLabel);
     EXPORT("componentsDestroy", ComponentsDestroy);

@@ -23,6 +23,11 @@
 //   is resampled to that grid, or to cubic voxels of edge `pitch` (default: the smallest spacing), behind the window and in front of the rank
 //   filter, so rank, components and distance see the resampled grid (Volume.resample, Volume.isotropic); a volume whose format the mode does
 //   not take is left as it is
+//   combine: null (default) or { reader | volume, op, channel, lo, hi, fill, wa, wb, offset, resample: null | 'nearest' | 'filtered' }: an
+//   R8 / R16 volume is combined with a second one when it is loaded (Volume.combine).  A `reader` is loaded into a second volume and
+//   destroyed afterwards, a `volume` stays the caller's; with `resample` set and differing sizes the second volume is first resampled to the
+//   primary's current grid in that mode.  The one-channel ops run behind `resample` and in front of `rank`; 'pair' runs where the gradient
+//   runs, so it cannot be combined with `gradient`, `components` mode 'label' or `distance` mode 'channel'
 const { EventTarget, CustomEvent } = require('./EventTarget.js');
 const { Context } = require('./Context.js');
 const { OrbitCameraAnimator } = require('./animators.js');
@@ -32,6 +37,7 @@ const { native } = require('./native.js');
 const { checkConnectivity, checkRange, checkMinVoxels, checkKeep } = require('./components.js');
 const { checkSeeds, checkSteps, checkWithin, checkDistanceRange } = require('./distance.js');
 const { checkResampleMode, checkResampleSize, checkSpacing } = require('./resample.js');
+const { checkCombineOp, checkCombineChannel, checkCombineWeights, checkCombineMask } = require('./combine.js');
 const { RendererFactory } = require('./renderers/RendererFactory.js');
 const { ToneMapperFactory } = require('./tonemappers/ToneMapperFactory.js');
 
@@ -67,6 +73,16 @@ constructor(options) {
         }
     }
     this.resample = RenderingContext._resampleSpec(options.resample);                // likewise
+    this.combine = RenderingContext._combineSpec(options.combine);                   // likewise
+    if (this.combine !== null && this.combine.op === 'pair') {
+        if (this.gradient !== null) { throw new Error("combine op 'pair' and gradient both write the second channel: name one of them"); }
+        if (this.components !== null && this.components.mode === 'label') {
+            throw new Error("combine op 'pair' and components mode 'label' both write the second channel: name one of them");
+        }
+        if (this.distance !== null && this.distance.mode === 'channel') {
+            throw new Error("combine op 'pair' and distance mode 'channel' both write the second channel: name one of them");
+        }
+    }
     this.gl = new Context(options.device || 0);                                   // initGL(), :61-105
     this.environmentTexture = { data: new Uint8Array([255, 255, 255, 255]), width: 1, height: 1 };   // :90-101
     this._rng = options.rng;
@@ -123,6 +139,7 @@ async setVolume(reader) {                                                       
                 : source.isotropic(spec.spacing, spec.pitch, spec.mode);
             source.destroy();
         }
+        if (this.combine !== null && this.combine.op !== 'pair') { await this._combineWith(this.combine); }
         if (this.rank !== null) {
             const N = native(), fmt = this.volume.nativeFormat();
             if (fmt === N.VPT_FORMAT_R8 || fmt === N.VPT_FORMAT_R16) {                 // the formats the smoothing takes: any other volume as it is
@@ -159,6 +176,7 @@ async setVolume(reader) {                                                       
         }
         if (this.components !== null && this.components.mode === 'label') { this._derive(found => found.label()); }   // (value, rank)
         if (this.distance !== null && this.distance.mode === 'channel') { this._deriveDistance(found => found.channel(this.distance.steps)); }   // (value, distance)
+        if (this.combine !== null && this.combine.op === 'pair') { await this._combineWith(this.combine); }                    // (value, the second volume)
     } catch (e) {                                                                      // the context keeps the volume it had
         this.volume.destroy();
         this.volume = old;
@@ -186,6 +204,58 @@ _deriveDistance(emit) {
     const found = source.distance(spec.lo, Math.min(spec.hi, largest), spec.seeds);
     try { this.volume = emit(found); } finally { found.destroy(); }
     source.destroy();
+}
+
+// replaces this.volume (if it is R8 / R16: any other volume stays as it is) by its combination with the second volume of the `combine` option
+async _combineWith(spec) {
+    const N = native(), fmt = this.volume.nativeFormat();
+    if (fmt !== N.VPT_FORMAT_R8 && fmt !== N.VPT_FORMAT_R16) { return; }
+    const source = this.volume;
+    let second = spec.volume, owned = false;
+    if (second === null) {
+        second = new Volume(this.gl, spec.reader); owned = true;
+        await second.load();
+    }
+    try {
+        const d = source.modality.dimensions, o = second.modality.dimensions;
+        if (spec.resample !== null && (d.width !== o.width || d.height !== o.height || d.depth !== o.depth)) {
+            const fitted = second.resample(d.width, d.height, d.depth, spec.resample);
+            if (owned) { second.destroy(); }
+            second = fitted; owned = true;
+        }
+        this.volume = source.combine(second, spec.op, Object.assign({ channel: spec.channel }, spec.params));
+    } finally {
+        if (owned) { second.destroy(); }
+    }
+    source.destroy();
+}
+
+// the `combine` option with its defaults filled in, or null; throws for anything the contract does not take
+static _combineSpec(spec) {
+    if (spec === undefined || spec === null) { return null; }
+    const known = ['reader', 'volume', 'op', 'channel', 'lo', 'hi', 'fill', 'wa', 'wb', 'offset', 'resample'];
+    const given = k => spec[k] !== undefined && spec[k] !== null;
+    if (typeof spec !== 'object' || Array.isArray(spec) || !('op' in spec) || !Object.keys(spec).every(k => known.includes(k)) || given('reader') === given('volume')) {
+        throw new Error("combine is null or { reader | volume, op, channel, lo, hi, fill, wa, wb, offset, resample } with one of 'reader' and 'volume', not " +
+            JSON.stringify(spec, (k, v) => (k === 'reader' || k === 'volume' ? String(v) : v)));
+    }
+    checkCombineOp(spec.op);
+    if (given('volume') && !(spec.volume instanceof Volume)) { throw new Error("combine 'volume' is a Volume"); }
+    const out = { reader: given('reader') ? spec.reader : null, volume: given('volume') ? spec.volume : null, op: spec.op,
+        channel: checkCombineChannel(given('channel') ? spec.channel : 0, 2), params: {}, resample: null };
+    if (given('resample')) { checkResampleMode(spec.resample); out.resample = spec.resample; }
+    if (spec.op !== 'mask' && ['lo', 'hi', 'fill'].some(given)) { throw new Error("combine 'lo', 'hi' and 'fill' go with op 'mask'"); }
+    if (spec.op !== 'blend' && ['wa', 'wb', 'offset'].some(given)) { throw new Error("combine 'wa', 'wb' and 'offset' go with op 'blend'"); }
+    if (spec.op === 'mask') {
+        const lo = given('lo') ? spec.lo : 0, fill = given('fill') ? spec.fill : 0;
+        checkCombineMask(lo, given('hi') ? spec.hi : 65535, fill, 65535, 65535);
+        out.params = { lo, hi: given('hi') ? spec.hi : null, fill };                  // hi null: the second volume's largest code
+    } else if (spec.op === 'blend') {
+        if (!given('wa') || !given('wb')) { throw new Error("combine op 'blend' needs 'wa' and 'wb'"); }
+        const w = checkCombineWeights(spec.wa, spec.wb, given('offset') ? spec.offset : 0);
+        out.params = { wa: w[0], wb: w[1], offset: w[2] };
+    }
+    return out;
 }
 
 // the `resample` option with its defaults filled in, or null; throws for anything the contract does not take

@@ -7,6 +7,7 @@ const R = require('./readers/readers.js');
 const { checkConnectivity, checkRange, checkMinVoxels, checkKeep } = require('./components.js');
 const { checkSeeds, checkSteps, checkRadius, checkWithin, checkDistanceRange } = require('./distance.js');
 const { checkResampleMode, checkResampleSize, isotropicShape } = require('./resample.js');
+const { COMBINE_STATS, checkCombineOp, checkCombineChannel, checkCombineWeights, checkCombineMask, checkCompareRange, compareRatios } = require('./combine.js');
 const { RAWReader, GL_RED, GL_RG, GL_RGB, GL_RGBA, GL_UNSIGNED_BYTE, GL_FLOAT, GL_HALF_FLOAT, GL_BYTE } = R;
 
 // [type, format, internalFormat, native format name, channels in the file, element kind] of the formats keyed on all three: SNORM bytes
@@ -349,6 +350,77 @@ resample(width, height, depth, mode) {
 isotropic(spacing, pitch, mode) {
     const d = this.modality.dimensions, n = isotropicShape([d.width, d.height, d.depth], spacing, pitch);
     return this.resample(n[0], n[1], n[2], mode);
+}
+
+// ---- extension: two volumes combined or compared texel by texel (include/vpt.h; DESIGN.md "Combining two volumes") ----
+// the arguments of native().volumeCombine behind combine(other, op, options), checked as combineTexels of combine.js checks them
+_combineArguments(other, op, options) {
+    options = options || {};
+    const N = native(), code = checkCombineOp(op);
+    if (!(other instanceof Volume) || !other.texture || !this.texture) { throw new Error('combine takes two ready volumes'); }
+    const unknown = Object.keys(options).filter(k => ['channel', 'lo', 'hi', 'fill', 'wa', 'wb', 'offset'].indexOf(k) < 0);
+    if (unknown.length) { throw new Error('combine takes channel, lo, hi, fill (mask) and wa, wb, offset (blend), not ' + unknown.sort().join(', ')); }
+    const layout = texelLayout(N, other.modality);
+    const channel = checkCombineChannel(options.channel !== undefined ? options.channel : 0, layout.channels);
+    const largest = this.nativeFormat() === N.VPT_FORMAT_R16 || this.nativeFormat() === N.VPT_FORMAT_RG16 ? 65535 : 255;
+    let mask = [0, 0, 0], blend = [0, 0, 0];
+    if (op === 'mask') {
+        const largestB = layout.array.BYTES_PER_ELEMENT === 2 ? 65535 : 255;
+        mask = checkCombineMask(options.lo !== undefined ? options.lo : 0, options.hi !== undefined && options.hi !== null ? options.hi : largestB,
+            options.fill !== undefined ? options.fill : 0, largestB, largest);
+    } else if (op === 'blend') {
+        blend = checkCombineWeights(options.wa !== undefined ? options.wa : 256, options.wb !== undefined ? options.wb : 0, options.offset);
+    }
+    return [this.texture, other.texture, code, channel, mask[0], mask[1], mask[2], blend[0], blend[1], blend[2]];
+}
+_combined(texture, op) {
+    const out = this._sameFormat(texture, this.modality.dimensions);
+    if (op === 'pair') {
+        const norm16 = this.nativeFormat() === native().VPT_FORMAT_R16;
+        Object.assign(out.modality, { format: GL_RG, internalFormat: norm16 ? R.GL_RG16_EXT : R.GL_RG8, type: norm16 ? R.GL_UNSIGNED_SHORT : GL_UNSIGNED_BYTE });
+    }
+    return out;
+}
+// a new, ready volume on this (R8 / R16) volume's context and with its filter: this volume's texels A combined with the texels B of channel
+// options.channel (default 0) of `other` (R8, RG8, R16, RG16; same size; may be this volume) by `op`: 'mask' ({ lo, hi, fill }), 'min', 'max',
+// 'absdiff', 'blend' ({ wa, wb, offset }) in this volume's format, or 'pair', the RG8 / RG16 volume (A, B); derived on the device; neither
+// volume is changed
+combine(other, op, options) {
+    const a = this._combineArguments(other, op, options);
+    return this._combined(native().volumeCombine.apply(null, a), op);
+}
+// (for measurements) [the volume combine() gives, the milliseconds of the combining pass alone, the stream drained around it]
+combineTimed(other, op, options) {
+    const a = this._combineArguments(other, op, options);
+    const r = native().volumeCombineTimed.apply(null, a);
+    return [this._combined(r[0], op), r[1]];
+}
+// this volume's codes where lo <= B <= hi, `fill` (default 0) elsewhere; `other` may be 8- or 16-bit whatever this volume is
+mask(other, lo, hi, fill, channel) { return this.combine(other, 'mask', { lo, hi, fill: fill !== undefined ? fill : 0, channel: channel !== undefined ? channel : 0 }); }
+minimum(other, channel) { return this.combine(other, 'min', { channel: channel !== undefined ? channel : 0 }); }
+maximum(other, channel) { return this.combine(other, 'max', { channel: channel !== undefined ? channel : 0 }); }
+absdiff(other, channel) { return this.combine(other, 'absdiff', { channel: channel !== undefined ? channel : 0 }); }
+// clamp(((wa A + wb B + 128) >> 8) + offset, 0, M): weights in 1/256 units; (256, 256) adds, (256, -256) subtracts, (128, 128) averages,
+// (-256, 0, M) inverts, (512, -256) against smooth() is unsharp masking
+blend(other, wa, wb, offset, channel) { return this.combine(other, 'blend', { wa, wb, offset: offset !== undefined ? offset : 0, channel: channel !== undefined ? channel : 0 }); }
+// the RG8 / RG16 volume (A, B): `other` becomes the second axis of the 2-D transfer function
+pair(other, channel) { return this.combine(other, 'pair', { channel: channel !== undefined ? channel : 0 }); }
+// { voxels, differing, maxAbs, sumAbs, sumSq, inA, inB, both }: exact BigInts (sumSq can pass 2^53) over this (R8 / R16) volume's codes A and
+// the codes B of channel `channel` of `other` (mixed widths are taken), counted on the device; inA counts aRange[0] <= A <= aRange[1] (null:
+// every code), inB likewise, both their intersection; plus dice, jaccard, mse, psnr as Numbers, null where a denominator is 0.  More than
+// 2^32 - 1 voxels throw (VPT_ERR_UNSUPPORTED)
+compare(other, aRange, bRange, channel) {
+    const N = native();
+    if (!(other instanceof Volume) || !other.texture || !this.texture) { throw new Error('compare takes two ready volumes'); }
+    const layout = texelLayout(N, other.modality);
+    channel = checkCombineChannel(channel !== undefined ? channel : 0, layout.channels);
+    const largestA = this.nativeFormat() === N.VPT_FORMAT_R16 || this.nativeFormat() === N.VPT_FORMAT_RG16 ? 65535 : 255;
+    const largestB = layout.array.BYTES_PER_ELEMENT === 2 ? 65535 : 255;
+    const ra = checkCompareRange(aRange, largestA, 'aRange'), rb = checkCompareRange(bRange, largestB, 'bRange');
+    const halves = N.volumeCompare(this.texture, other.texture, channel, ra[0], ra[1], rb[0], rb[1]);      // (low, high) 32-bit halves of the eight counts
+    const stats = {};
+    COMBINE_STATS.forEach((name, k) => { stats[name] = (BigInt(halves[2 * k + 1]) << 32n) | BigInt(halves[2 * k]); });
+    return Object.assign(stats, compareRatios(stats, Math.max(largestA, largestB)));
 }
 
 // ---- extension: connected components of a value range (include/vpt.h; DESIGN.md "Connected components") ----

@@ -25,6 +25,7 @@ from .rank import rank_texels
 from .components import components_texels, keep_texels, label_texels
 from .distance import distance_squared_texels, within_texels, channel_texels, check_seeds, check_steps, check_radius
 from .resample import resample_texels, isotropic_shape, axis_taps, nearest_index, count_ties, check_mode, check_size, check_spacing
+from .combine import combine_texels, compare_stats, OPS, check_op, check_weights, check_channel
 from ._native import VptError
 
 __all__ = [
@@ -39,4 +40,5 @@ __all__ = [
     'components_texels', 'keep_texels', 'label_texels', 'Components',
     'distance_squared_texels', 'within_texels', 'channel_texels', 'check_seeds', 'check_steps', 'check_radius', 'Distance',
     'resample_texels', 'isotropic_shape', 'axis_taps', 'nearest_index', 'count_ties', 'check_mode', 'check_size', 'check_spacing',
+    'combine_texels', 'compare_stats', 'OPS', 'check_op', 'check_weights', 'check_channel',
 ]

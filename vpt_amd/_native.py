@@ -56,6 +56,7 @@ SYMBOLS = [
     "vpt_volume_distance", "vpt_distance_info", "vpt_distance_squared", "vpt_distance_within", "vpt_distance_channel",
     "vpt_distance_profile", "vpt_distance_destroy",
     "vpt_volume_resample", "vpt_volume_resample_timed",
+    "vpt_volume_combine", "vpt_volume_combine_timed", "vpt_volume_compare",
     "vpt_renderer_create", "vpt_renderer_set_shard", "vpt_renderer_local_rows", "vpt_renderer_global_row",
     "vpt_renderer_destroy", "vpt_renderer_set_volume", "vpt_renderer_set_transfer_function",
     "vpt_renderer_set_environment", "vpt_renderer_set_environment_texels", "vpt_renderer_resize",
@@ -119,6 +120,13 @@ DISTANCE_NONE = 0xFFFFFFFF
 DISTANCE_PHASES = 3
 RESAMPLE_NEAREST, RESAMPLE_FILTERED = 0, 1
 RESAMPLE_PHASES = 2
+COMBINE_MASK, COMBINE_MIN, COMBINE_MAX, COMBINE_ABSDIFF, COMBINE_BLEND, COMBINE_PAIR = 0, 1, 2, 3, 4, 5
+
+
+class CombineParams(C.Structure):
+    """struct vpt_combine_params (include/vpt.h)"""
+    _fields_ = [("op", C.c_int), ("b_channel", C.c_int), ("lo", C.c_uint32), ("hi", C.c_uint32), ("fill", C.c_uint32),
+                ("wa", C.c_int32), ("wb", C.c_int32), ("offset", C.c_int32)]
 
 
 class TonemapParams(C.Structure):
@@ -196,6 +204,8 @@ def lib():
         "vpt_distance_squared": [P, I, I, I, I, I, I, P, SZ], "vpt_distance_within": [P, C.c_uint32, C.c_uint32, C.c_uint32, PP],
         "vpt_distance_channel": [P, I, PP], "vpt_distance_profile": [P, C.POINTER(C.c_double)], "vpt_distance_destroy": [P],
         "vpt_volume_resample": [P, I, I, I, I, PP], "vpt_volume_resample_timed": [P, I, I, I, I, PP, C.POINTER(C.c_double)],
+        "vpt_volume_combine": [P, P, C.POINTER(CombineParams), PP], "vpt_volume_combine_timed": [P, P, C.POINTER(CombineParams), PP, C.POINTER(C.c_double)],
+        "vpt_volume_compare": [P, P, I, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)],
         "vpt_renderer_create": [P, I, I, I, PP],
         "vpt_renderer_set_shard": [P, I, I, I], "vpt_renderer_local_rows": [P, C.POINTER(I)],
         "vpt_renderer_global_row": [P, I, C.POINTER(I)],

@@ -16,6 +16,7 @@
 //   vpt_volume_field.hip  what components and distances share (vpt_volume_field.h): a uint32 per voxel over a volume's texels, its read-back and emitters
 //   vpt_volume_distance.hip  the exact squared Euclidean distance to a value range (or to its complement): per-voxel d2, within and channel volumes
 //   vpt_volume_resample.hip  a volume resampled to any grid size: nearest texel, or linear interpolation / area average in integers
+//   vpt_volume_combine.hip  two volumes of one grid combined texel by texel (mask, min, max, difference, blend, pair) or compared (exact counts and sums)
 // vpt_variants.h (through vpt_device.h) holds the variant bits of the sampling kernels and the switch from a run-time variant to a template
 // argument; launch_variant below is its use for a renderer's sampling pass.
 // vpt_buffers.h holds DevBuf<T> / PinnedBuf<T>, the owners of device and pinned host memory: the objects below own their memory through such
@@ -254,7 +255,7 @@ int join_side(vpt_renderer *r);                     // the side streams' work ha
 int streams_deal(vpt_renderer *r, Deal d);          // before the launches of a deal: join and fork as the deal needs (StreamSet)
 int make_args(vpt_renderer *r, const vpt_uniforms *u, bool need_volume, PassArgs *a);
 int volume_create(vpt_context *c, int w, int h, int d, int format, bool zero_fill, vpt_volume **out);   // vpt_volume_create; zero_fill = false: the caller writes every texel
-int volume_finish_derived(vpt_context *ctx, int filter, vpt_volume *d, vpt_volume **out);   // the shared tail of the derived volumes (gradient, window, reduce, smooth, rank, resample, the voxel fields' emitters): finalize with the source's filter and hand out
+int volume_finish_derived(vpt_context *ctx, int filter, vpt_volume *d, vpt_volume **out);   // the shared tail of the derived volumes (gradient, window, reduce, smooth, rank, resample, combine, the voxel fields' emitters): finalize with the source's filter and hand out
 int volume_records(vpt_volume *v);                  // builds the column records of a finalized one-channel byte volume if they are not current
 hipError_t create_overlapping_stream(Stream *out, const vpt_renderer *r);   // overlaps r's context stream and side streams
 bool invert_matrix(const float *m, double out[4][4]);               // column-major float matrix -> its inverse (double); false: singular

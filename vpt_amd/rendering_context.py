@@ -73,6 +73,20 @@ class RenderingContext(EventTarget):
         # front of the rank filter: rank, components and distance see the resampled grid.  A volume whose format the mode does not take is
         # left as it is
         self.resample = self._resample_spec(options.get('resample'))
+        # (extension) None | {'reader' | 'volume', 'op', 'channel': 0, 'lo', 'hi', 'fill', 'wa', 'wb', 'offset', 'resample': None | 'nearest' |
+        # 'filtered'}: an R8 / R16 volume is combined with a second one when it is loaded (Volume.combine).  A 'reader' is loaded into a second
+        # volume and destroyed afterwards, a 'volume' stays the caller's; with 'resample' set and differing sizes the second volume is first
+        # resampled to the primary's current grid in that mode.  The one-channel ops run behind `resample` and in front of `rank`; 'pair'
+        # runs where the gradient runs, on the final scalar volume, so it cannot be combined with `gradient`, `components` mode 'label' or
+        # `distance` mode 'channel'
+        self.combine = self._combine_spec(options.get('combine'))
+        if self.combine is not None and self.combine['op'] == 'pair':
+            if self.gradient is not None:
+                raise ValueError("combine op 'pair' and gradient both write the second channel: name one of them")
+            if self.components is not None and self.components['mode'] == 'label':
+                raise ValueError("combine op 'pair' and components mode 'label' both write the second channel: name one of them")
+            if self.distance is not None and self.distance['mode'] == 'channel':
+                raise ValueError("combine op 'pair' and distance mode 'channel' both write the second channel: name one of them")
         self.gl = Context(options.get('device', 0))                                   # initGL(), :61-105
         self.environmentTexture = np.array([[[255, 255, 255, 255]]], dtype=np.uint8)   # :90-101
         self._rng = options.get('rng')
@@ -124,6 +138,8 @@ class RenderingContext(EventTarget):
                 else:
                     self.volume = source.isotropic(self.resample['spacing'], self.resample['pitch'], self.resample['mode'])
                 source.destroy()
+            if self.combine is not None and self.combine['op'] != 'pair' and self._one_channel_unorm(self.volume):
+                self._combine_with(self.combine)
             if self.rank is not None and self._one_channel_unorm(self.volume):
                 source = self.volume
                 self.volume = source.rank(self.rank, self.rankPasses)
@@ -149,6 +165,8 @@ class RenderingContext(EventTarget):
                 self._derive(lambda source, found: found.label())                     # (value, rank): a row of the 2-D transfer function per structure
             if self.distance is not None and self.distance['mode'] == 'channel' and self._one_channel_unorm(self.volume):
                 self._derive_distance(lambda found: found.channel(self.distance['steps']))   # (value, distance): the 2-D transfer function's axes
+            if self.combine is not None and self.combine['op'] == 'pair' and self._one_channel_unorm(self.volume):
+                self._combine_with(self.combine)                                      # (value, the second volume): the 2-D transfer function's axes
         except Exception:                                                             # the context keeps the volume it had
             self.volume.destroy()
             self.volume = old
@@ -183,6 +201,63 @@ class RenderingContext(EventTarget):
         finally:
             found.destroy()
         source.destroy()
+
+    def _combine_with(self, spec):
+        """replaces self.volume by its combination with the second volume of the `combine` option"""
+        source = self.volume
+        second, owned = spec['volume'], False
+        if second is None:
+            second, owned = Volume(self.gl, spec['reader']), True
+            second.load()
+        try:
+            dims, other = source.modality['dimensions'], second.modality['dimensions']
+            if spec['resample'] is not None and any(dims[k] != other[k] for k in ('width', 'height', 'depth')):
+                fitted = second.resample(dims['width'], dims['height'], dims['depth'], spec['resample'])
+                if owned:
+                    second.destroy()
+                second, owned = fitted, True
+            self.volume = source.combine(second, spec['op'], spec['channel'], **spec['params'])
+        finally:
+            if owned:
+                second.destroy()
+        source.destroy()
+
+    @staticmethod
+    def _combine_spec(spec):
+        """the `combine` option with its defaults filled in, or None; raises ValueError for anything the contract does not take"""
+        if spec is None:
+            return None
+        from .combine import check_op, check_channel, check_weights, check_mask
+        from .resample import check_mode
+        known = {'reader', 'volume', 'op', 'channel', 'lo', 'hi', 'fill', 'wa', 'wb', 'offset', 'resample'}
+        if not isinstance(spec, dict) or 'op' not in spec or not set(spec) <= known or (spec.get('reader') is None) == (spec.get('volume') is None):
+            raise ValueError("combine is None or {'reader' | 'volume', 'op', 'channel', 'lo', 'hi', 'fill', 'wa', 'wb', 'offset', 'resample'} with one "
+                             "of 'reader' and 'volume', not %r" % (spec,))
+        op = spec['op']
+        check_op(op)
+        if spec.get('volume') is not None and not isinstance(spec['volume'], Volume):
+            raise ValueError("combine 'volume' is a Volume, not %r" % (spec['volume'],))
+        out = {'reader': spec.get('reader'), 'volume': spec.get('volume'), 'op': op,
+               'channel': check_channel(spec['channel'] if spec.get('channel') is not None else 0, 2), 'params': {}, 'resample': None}
+        if spec.get('resample') is not None:
+            check_mode(spec['resample'])
+            out['resample'] = spec['resample']
+        given = lambda keys: any(spec.get(k) is not None for k in keys)
+        if op != 'mask' and given(('lo', 'hi', 'fill')):
+            raise ValueError("combine 'lo', 'hi' and 'fill' go with op 'mask'")
+        if op != 'blend' and given(('wa', 'wb', 'offset')):
+            raise ValueError("combine 'wa', 'wb' and 'offset' go with op 'blend'")
+        if op == 'mask':
+            lo = spec['lo'] if spec.get('lo') is not None else 0
+            fill = spec['fill'] if spec.get('fill') is not None else 0
+            check_mask(lo, spec['hi'] if spec.get('hi') is not None else 65535, fill, 65535, 65535)
+            out['params'] = {'lo': lo, 'hi': spec.get('hi'), 'fill': fill}           # hi None: the second volume's largest code
+        elif op == 'blend':
+            if spec.get('wa') is None or spec.get('wb') is None:
+                raise ValueError("combine op 'blend' needs 'wa' and 'wb'")
+            wa, wb, offset = check_weights(spec['wa'], spec['wb'], spec['offset'] if spec.get('offset') is not None else 0)
+            out['params'] = {'wa': wa, 'wb': wb, 'offset': offset}
+        return out
 
     @staticmethod
     def _resample_spec(spec):

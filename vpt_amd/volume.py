@@ -519,6 +519,96 @@ class Volume(EventTarget):
         dims = self.modality['dimensions']
         return self.resample(*isotropic_shape((dims['width'], dims['height'], dims['depth']), spacing, pitch), mode=mode)
 
+    # ---- extension: two volumes combined or compared texel by texel (include/vpt.h; DESIGN.md "Combining two volumes") ----
+    def _combine_params(self, other, op, channel, params):
+        """the CombineParams of ``combine(other, op, channel, **params)``, checked as vpt_amd.combine_texels checks them"""
+        from .combine import check_op, check_channel, check_weights, check_mask
+        code = check_op(op)
+        if not isinstance(other, Volume) or not other.texture or not self.texture:
+            raise ValueError('combine takes two ready volumes')
+        unknown = set(params) - {'lo', 'hi', 'fill', 'wa', 'wb', 'offset'}
+        if unknown:
+            raise ValueError('combine takes lo, hi, fill (mask) and wa, wb, offset (blend), not %s' % ', '.join(sorted(unknown)))
+        other_channels, other_dtype = other._texel_layout()
+        p = N.CombineParams(op=code, b_channel=check_channel(channel, other_channels))
+        largest = 65535 if self.native_format()[0] in (N.FORMAT_R16, N.FORMAT_RG16) else 255
+        if op == 'mask':
+            largest_b = 65535 if np.dtype(other_dtype).itemsize == 2 else 255
+            hi = params['hi'] if params.get('hi') is not None else largest_b
+            p.lo, p.hi, p.fill = check_mask(params.get('lo', 0), hi, params.get('fill', 0), largest_b, largest)
+        elif op == 'blend':
+            p.wa, p.wb, p.offset = check_weights(params.get('wa', 256), params.get('wb', 0), params.get('offset', 0))
+        return p
+
+    def _combined(self, handle, op):
+        out = self._same_format(handle, self.modality['dimensions'])
+        if op == 'pair':
+            norm16 = self.native_format()[0] == N.FORMAT_R16
+            out.modality.update({'format': GL_RG, 'internalFormat': GL_RG16_EXT if norm16 else GL_RG8,
+                                 'type': GL_UNSIGNED_SHORT if norm16 else GL_UNSIGNED_BYTE})
+        return out
+
+    def combine(self, other, op, channel=0, **params):
+        """A new, ready volume on this (R8 / R16) volume's context and with its filter: this volume's texels A combined with the texels B of
+        channel ``channel`` of ``other`` (R8, RG8, R16, RG16; same size; may be this volume) by ``op``: 'mask' (lo, hi, fill), 'min', 'max',
+        'absdiff', 'blend' (wa, wb, offset) in this volume's format, or 'pair', the RG8 / RG16 volume (A, B) (vpt_amd.combine_texels states
+        them), derived on the device.  Neither volume is changed."""
+        p = self._combine_params(other, op, channel, params)
+        h = C.c_void_p()
+        N.check(N.lib().vpt_volume_combine(self.texture, other.texture, C.byref(p), C.byref(h)))
+        return self._combined(h, op)
+
+    def combine_timed(self, other, op, channel=0, **params):
+        """(for measurements) (the volume ``combine`` gives, the milliseconds of the combining pass alone, the stream drained around it)"""
+        p = self._combine_params(other, op, channel, params)
+        h = C.c_void_p()
+        ms = C.c_double(0)
+        N.check(N.lib().vpt_volume_combine_timed(self.texture, other.texture, C.byref(p), C.byref(h), C.byref(ms)))
+        return self._combined(h, op), ms.value
+
+    def mask(self, other, lo, hi, fill=0, channel=0):
+        """this volume's codes where lo <= B <= hi, ``fill`` elsewhere; ``other`` may be 8- or 16-bit whatever this volume is"""
+        return self.combine(other, 'mask', channel, lo=lo, hi=hi, fill=fill)
+
+    def minimum(self, other, channel=0):
+        return self.combine(other, 'min', channel)
+
+    def maximum(self, other, channel=0):
+        return self.combine(other, 'max', channel)
+
+    def absdiff(self, other, channel=0):
+        return self.combine(other, 'absdiff', channel)
+
+    def blend(self, other, wa, wb, offset=0, channel=0):
+        """clamp(((wa A + wb B + 128) >> 8) + offset, 0, M): weights in 1/256 units; (256, 256) adds, (256, -256) subtracts, (128, 128)
+        averages, (-256, 0, M) inverts, (512, -256) against ``smooth()`` is unsharp masking"""
+        return self.combine(other, 'blend', channel, wa=wa, wb=wb, offset=offset)
+
+    def pair(self, other, channel=0):
+        """the RG8 / RG16 volume (A, B): ``other`` becomes the second axis of the 2-D transfer function"""
+        return self.combine(other, 'pair', channel)
+
+    def compare(self, other, a_range=None, b_range=None, channel=0):
+        """{'voxels', 'differing', 'max_abs', 'sum_abs', 'sum_sq', 'in_a', 'in_b', 'both'}: exact integers over this (R8 / R16) volume's
+        codes A and the codes B of channel ``channel`` of ``other`` (mixed widths are taken), counted on the device; in_a counts
+        a_range[0] <= A <= a_range[1] (None: every code), in_b likewise, both their intersection; plus 'dice', 'jaccard', 'mse', 'psnr' in
+        IEEE double, None where a denominator is 0 (vpt_amd.compare_stats states all of it).  More than 2^32 - 1 voxels raise VptError
+        (ERR_UNSUPPORTED)."""
+        from .combine import check_channel, check_compare_range, ratios, STATS
+        if not isinstance(other, Volume) or not other.texture or not self.texture:
+            raise ValueError('compare takes two ready volumes')
+        other_channels, other_dtype = other._texel_layout()
+        channel = check_channel(channel, other_channels)
+        largest_a = 65535 if self.native_format()[0] in (N.FORMAT_R16, N.FORMAT_RG16) else 255
+        largest_b = 65535 if np.dtype(other_dtype).itemsize == 2 else 255
+        lo_a, hi_a = check_compare_range(a_range, largest_a, 'a_range')
+        lo_b, hi_b = check_compare_range(b_range, largest_b, 'b_range')
+        out = (C.c_uint64 * 8)()
+        N.check(N.lib().vpt_volume_compare(self.texture, other.texture, channel, lo_a, hi_a, lo_b, hi_b, out))
+        stats = dict(zip(STATS, (int(v) for v in out)))
+        stats.update(ratios(stats, max(largest_a, largest_b)))
+        return stats
+
     def set_wide_tables(self, wide):
         """force the > 4 GiB addressing variant of the kernels (automatic above 4 GiB of bricked data)"""
         N.check(N.lib().vpt_volume_set_wide_tables(self.texture, 1 if wide else 0))
