@@ -1,0 +1,134 @@
+"""The drawn volume chains (tests/volume_chain_cases.py) at the default seeds, held to the conditions without which
+tests/test_gpu_volume_chain_fuzz.py could pass while checking little.  No device: numpy and the vpt_amd statements only."""
+import time
+
+import numpy as np
+
+import volume_chain_cases as V
+
+SEEDS = list(V.default_seeds())
+_START = time.perf_counter()
+CHAINS = {seed: V.chain(seed) for seed in SEEDS}
+GENERATION_SECONDS = time.perf_counter() - _START
+STEPS = [(seed, i, s) for seed in SEEDS for i, s in enumerate(CHAINS[seed]) if s['op'] != 'source']
+PRODUCING = [(seed, i, s) for seed, i, s in STEPS if s['out'] is not None]
+
+
+def test_generation_is_quick_and_repeats_itself():
+    assert GENERATION_SECONDS < 30.0, "%.1f s for %d chains" % (GENERATION_SECONDS, len(SEEDS))
+    for seed in SEEDS[:6]:
+        again = V._build(seed)
+        assert len(again) == len(CHAINS[seed])
+        for a, b in zip(again, CHAINS[seed]):
+            assert a['op'] == b['op'] and a['src'] == b['src'] and a['out'] == b['out']
+            if isinstance(a['expect'], np.ndarray):
+                assert a['expect'].tobytes() == b['expect'].tobytes()
+            else:
+                assert a['expect'] == b['expect']
+
+
+def test_chains_have_the_drawn_form():
+    for seed in SEEDS:
+        steps = CHAINS[seed]
+        assert steps[0]['op'] == 'source' and 3 <= len(steps) - 1 <= 6, seed
+        d, h, w = steps[0]['shape']
+        assert d * h * w <= V.MAX_VOXELS and ((d, h, w) == (1, 1, 1)) == (seed % 16 == 0), seed
+        volumes = 1
+        for s in steps[1:]:
+            assert s['format'] in V.LEGAL[s['op']], (seed, s['op'], s['format'])
+            assert s['src'] < volumes
+            if s['out'] is not None:
+                assert s['out'] == volumes and isinstance(s['expect'], np.ndarray) and s['expect'].size <= V.MAX_VOXELS * 2
+                volumes += 1
+            if s['op'] == 'resample':
+                assert s['shape'][0] * s['shape'][1] * s['shape'][2] <= V.MAX_VOXELS
+        text = V.describe(seed)
+        assert text.count('\n') == len(steps) and 'Volume.from_array' in text
+
+
+def test_few_results_are_constant():
+    judged = [(seed, i, s) for seed, i, s in PRODUCING if s['expect'].size > 1 and np.prod(s['shape']) > 1]
+    constant = [(seed, i, s['op']) for seed, i, s in judged if V._constant(s['expect'])]
+    assert len(judged) >= 100
+    assert len(constant) <= 0.02 * len(judged), "%d of %d volume-producing steps give a constant volume: %s" % (len(constant), len(judged), constant)
+
+
+def test_every_operation_occurs_three_times():
+    count = {entry: 0 for entry in V.ENTRIES}
+    for _, _, s in STEPS:
+        count[(s['op'], s['sub'])] += 1
+    rare = {entry: n for entry, n in count.items() if n < 3}
+    assert not rare, rare
+
+
+def test_every_legal_format_meets_every_operation():
+    seen = {(s['format'], s['op']) for _, _, s in STEPS}
+    missing = [(fmt, op) for op, formats in V.LEGAL.items() for fmt in formats if (fmt, op) not in seen]
+    assert not missing, missing
+    modes = {(s['format'], s['kwargs']['mode']) for _, _, s in STEPS if s['op'] == 'resample'}
+    missing = [(fmt, mode) for fmt in V.FORMATS for mode in ('nearest', 'filtered') if (mode == 'nearest' or fmt in V.RESAMPLE_FILTERED) and (fmt, mode) not in modes]
+    assert not missing, missing
+    windows = {(s['format'], s['kwargs']['format']) for _, _, s in STEPS if s['op'] == 'window'}
+    assert {fmt for fmt, _ in windows} == set(V.LEGAL['window']) and {bits for _, bits in windows} == {'r8', 'r16'}
+
+
+def shapes_of(family):
+    return [s['shape'] for _, _, s in STEPS if V.FAMILY.get(s['op']) == family]
+
+
+def test_every_family_sees_its_tile_edges_on_every_axis():
+    """No extent is ruled out by the voxel cap: the condition is per axis, the largest extent is 257, and the other two axes may be 1."""
+    missing = []
+    for family, tile in V.TILES.items():
+        shapes = shapes_of(family)
+        for axis, name in ((2, 'x'), (1, 'y'), (0, 'z')):
+            for extent in V.tile_extents(tile[2 - axis]):
+                if not any(shape[axis] == extent for shape in shapes):
+                    missing.append((family, name, extent))
+    assert not missing, missing
+
+
+def test_both_forms_of_every_vector_kernel_run():
+    for family in V.VECTOR_FAMILIES + ('resample',):
+        widths = [shape[2] for shape in shapes_of(family)]
+        for modulus in (4, 32):
+            assert any(w % modulus == 0 for w in widths) and any(w % modulus for w in widths), (family, modulus)
+    widths = [s['shape'][2] for _, _, s in STEPS if s['op'] == 'reduce']
+    for modulus in (4, 32):
+        assert any(w % modulus == 0 for w in widths) and any(w % modulus for w in widths), ('reduce', modulus)
+    for op in ('window', 'combine'):                              # 16-byte groups of the whole volume: a last partial group or none
+        voxels = [int(np.prod(s['shape'])) for _, _, s in STEPS if s['op'] == op]
+        assert any(n % 16 == 0 for n in voxels) and any(n % 16 for n in voxels), op
+
+
+def test_every_source_of_a_second_volume_occurs():
+    for op in ('combine', 'compare'):
+        seen = {s['b_source'] for _, _, s in STEPS if s['op'] == op}
+        assert seen == set(V.B_SOURCES), (op, seen)
+    mixed = [s for _, _, s in STEPS if s['op'] == 'combine' and s['b_source'] == 'other_width']
+    assert all(s['sub'] == 'mask' for s in mixed)
+    assert any(s['kwargs']['b'][0] == 'volume' and s['b_source'] == 'rg_channel' for _, _, s in STEPS if s['op'] in ('combine', 'compare'))
+
+
+def test_blocks_are_uploaded_between_derive_steps():
+    between = 0
+    for seed in SEEDS:
+        steps = CHAINS[seed]
+        for i, s in enumerate(steps):
+            if s['op'] == 'upload_block' and any(t['out'] is not None for t in steps[1:i]) and \
+                    any(t['out'] is not None and t['src'] == s['src'] for t in steps[i + 1:]):
+                between += 1
+    assert between >= 10, between
+
+
+def test_a_float_source_holds_the_special_values():
+    found = [seed for seed in SEEDS if CHAINS[seed][0]['kwargs']['texels'].dtype == np.float32 and
+             np.isnan(CHAINS[seed][0]['kwargs']['texels']).any() and np.isinf(CHAINS[seed][0]['kwargs']['texels']).any()]
+    assert found
+    assert any(np.signbit(CHAINS[seed][0]['kwargs']['texels'][CHAINS[seed][0]['kwargs']['texels'] == 0]).any() for seed in found)
+    outside = [seed for seed in SEEDS if CHAINS[seed][0]['kwargs']['texels'].dtype == np.float32 and int(np.prod(CHAINS[seed][0]['shape'])) >= 1000]
+    assert outside
+    for seed in outside:
+        t = CHAINS[seed][0]['kwargs']['texels']
+        finite = t[np.isfinite(t)]
+        assert (finite < 0).any() and (finite > 1).any(), seed
