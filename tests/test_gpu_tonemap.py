@@ -439,6 +439,62 @@ def test_fused_tone_mapping_full_hd_mcm_tile_classes(gpu_ctx, oracle):
     tm.destroy(); r.destroy(); gvol.destroy()
 
 
+@pytest.mark.parametrize("rkind", ["mip", "depth", "mcm"])
+def test_frames_into_a_bucket_that_held_displayed_frames(gpu_ctx, oracle, rkind):
+    """play_into, play_into_display into the same slots, play_into again: the displayed frames replaced the RGBA16F ones, so the last call
+    may not skip the tiles that miss the volume (found by the renderer lives: the slots were still listed as complete destinations)"""
+    import ctypes as C
+    from conftest import orbit_camera
+    w, h = 96, 80
+    gvol = vpt_amd.Volume.from_array(gpu_ctx, sphere_volume(24, noise=40.0), 'linear')
+    aux = vpt_amd.MCMRenderer(gpu_ctx, gvol, orbit_camera(w / h), None, {'resolution': (w, h), 'transform': Transform(Node()), 'rng': GoldenRatioRng()})
+    aux.reset(); aux.play(16, frames=True)
+    p_, n_ = C.c_void_p(), C.c_size_t()
+    N.check(N.lib().vpt_renderer_frame_ring_device(aux._h, C.byref(p_), C.byref(n_)))
+
+    def run(classes):
+        r = vpt_amd.RendererFactory(rkind)(gpu_ctx, gvol, orbit_camera(w / h, 0.7, -0.3, 3.2), None,
+                                           {'resolution': (w, h), 'transform': Transform(Node()), 'rng': GoldenRatioRng()})
+        r.set_option(N.OPTION_TILE_CLASSES, classes)
+        r.reset()
+        r.render(); r.render()
+        r.play_into(2, p_.value, n_.value)
+        r.set_render_target(None, 0)
+        tm = vpt_amd.ToneMapperFactory('unreal')(gpu_ctx, r, {'resolution': (w, h)})
+        tm.set_option(N.TONEMAPPER_OPTION_TABLE, N.TONEMAPPER_TABLE_ALWAYS)
+        tm.render()
+        r.play_into_display(tm, 2, p_.value, w * h * 4)
+        r.set_render_target(None, 0)
+        r.play_into(2, p_.value, n_.value)
+        r.join(); gpu_ctx.synchronize()
+        out = [aux.read_frame_slot(k).copy() for k in range(2)]
+        tm.destroy(); r.destroy()
+        return out
+
+    for k, (a, b) in enumerate(zip(run(0), run(1))):
+        same(b.view(np.uint16), a.view(np.uint16), "%s slot %d" % (rkind, k))
+    aux.destroy(); gvol.destroy()
+
+
+@pytest.mark.parametrize("persistent", [1, 2])
+def test_fused_tone_mapping_follows_the_persistent_mcm_passes(gpu_ctx, oracle, persistent):
+    """VPT_OPTION_MCM_PERSISTENT with a tone mapper armed: the persistent-wave kernel's frame store writes the tone mapper's output too
+    (found by the renderer lives: it wrote the render buffer alone, and the tone mapper went on showing the frame it was armed on)"""
+    from conftest import orbit_camera
+    w, h = 103, 68
+    gvol = vpt_amd.Volume.from_array(gpu_ctx, sphere_volume(0, noise=40.0, dims=(10, 21, 6)), 'linear')
+    r = vpt_amd.MCMRenderer(gpu_ctx, gvol, orbit_camera(w / h, 0.7, -0.3, 3.0), None, {'resolution': (w, h), 'transform': Transform(Node()), 'rng': GoldenRatioRng()})
+    r.extinction = 20; r.steps = 3
+    r.set_option(N.OPTION_MCM_PERSISTENT, persistent)
+    r.reset()
+    tm = vpt_amd.ToneMapperFactory('unreal')(gpu_ctx, r, {'resolution': (w, h)})
+    tm.set_option(N.TONEMAPPER_OPTION_TABLE, N.TONEMAPPER_TABLE_ALWAYS)
+    for k in range(3):
+        r.render(); tm.render()                                               # (the first call arms the tone mapper, the later ones launch nothing)
+        same(tm.getTexture(), oracle.tonemap('unreal', r.getTexture()), "persistent form %d, frame %d" % (persistent, k))
+    tm.destroy(); r.destroy(); gvol.destroy()
+
+
 @pytest.mark.parametrize("rkind,fast", [("mcm", 0), ("mcm", 1), ("eam", 0)])
 @pytest.mark.parametrize("tkind", ["artistic", "range", "aces"])
 def test_play_into_display_equals_the_tone_mapped_frames(gpu_ctx, oracle, rkind, fast, tkind):

@@ -514,8 +514,10 @@ __global__ void __launch_bounds__(VPT_BLOCK) __attribute__((amdgpu_waves_per_eu(
             EV_LOCAL
             mcm_events<V>(a, t, ph, ndc_col(a.pm, i), ndc_row(a.pm, j) EV_ARG);
             photon_store(a, (int)kc, ph);
-            if (FUSE_RENDER)
-                a.render[(size_t)l * a.pm.W + i] = pack_half4(ph.radiance.x, ph.radiance.y, ph.radiance.z, 1.0f);
+            if (FUSE_RENDER) {                   // (store_frame: an armed tone mapper's output follows the render buffer here as in every fused pass)
+                const Pix p = { i, j, l, (int)kc, true, true };
+                store_frame(a, p, pack_half4(ph.radiance.x, ph.radiance.y, ph.radiance.z, 1.0f));
+            }
         }
     }
 }
