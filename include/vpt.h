@@ -290,6 +290,45 @@ VPT_API int vpt_components_keep(vpt_components *c, uint64_t first_rank, uint64_t
 /* a new, finalized RG8 / RG16 volume with the source's filter: R the source code, G = min(rank, M), M = 255 / 65535, so a row of the 2-D
  * transfer function selects a structure; ranks beyond M share the last row (this saturation is part of the contract) */
 VPT_API int vpt_components_label(vpt_components *c, vpt_volume **out);
+/* Per-structure measurements (DESIGN.md "Measuring components"): dst[k] describes the component of rank first + 1 + k, k = 0 .. n - 1 (first
+ * is 0-based, as in vpt_components_list); a range not within `listed`: VPT_ERR_INVALID; n = 0 checks the arguments and writes nothing (dst
+ * may then be null).  Voxels whose rank lies outside the window contribute nothing.  The device table is n records and their n voxel counts (92 n bytes, freed when
+ * the call returns): a caller with millions of components pages through them; a table that cannot be allocated: VPT_ERR_HIP, nothing is
+ * leaked.
+ *   Box and index sums: min / max of the voxel indices (inclusive), and their sums: the centroid is sum / voxels.  `voxels` is the list's.
+ *   The root lies inside the box and root_z = min_z.
+ *   Values: the whole unsigned codes of channel `channel` of `values` under the component's voxels: their min, max, sum and sum of squares.
+ *   `values` null: the handle's own snapshot of the source's texels.  Otherwise an R8, RG8, R16 or RG16 volume (any other format:
+ *   VPT_ERR_UNSUPPORTED, naming it) on the handle's context and of the handle's width, height and depth (otherwise VPT_ERR_INVALID, naming
+ *   both sizes); its width is independent of the labelled source's, and it need not be finalized: the pass is enqueued on the context's
+ *   stream behind any upload into it.  channel: 0, or 1 of a two-channel volume; anything else VPT_ERR_INVALID.  Typical use: label a
+ *   smoothed, opened copy, then measure the original under those labels.
+ *   faces: each voxel has 6 faces; a face counts when its neighbour lies outside the volume or has a different rank (rank 0, background
+ *   and dropped components, is different): the surface in voxel faces, whatever connectivity the labelling used.
+ *   faces = 6 voxels - 2 (face-adjacent pairs inside the component).
+ *   No word can wrap: voxels <= 2^32 - 2 (the handle's limit), sum_x, sum_y, sum_z <= 4095 * 2^32, value_sum <= 65535 * 2^32,
+ *   value_sum_sq <= 2^32 * 65535^2 < 2^64, faces <= 6 * 2^32.
+ * Every field is an integer sum, minimum or maximum, so the result does not depend on the order the device works in: two runs give identical
+ * bytes.  vpt_amd.measure_texels states the contract in numpy; vpt_amd.measure.derive gives centroid, mean, variance, extents and fill ratio.
+ * The call blocks; the handle and `values` are not changed, and `values` may be destroyed afterwards. */
+struct vpt_component_measure {
+    uint64_t voxels;
+    uint32_t min_x, min_y, min_z, max_x, max_y, max_z;   /* bounding box, inclusive */
+    uint32_t value_min, value_max;                       /* whole unsigned codes of the measured channel */
+    uint64_t sum_x, sum_y, sum_z;                        /* sums of voxel indices: centroid = sum / voxels */
+    uint64_t value_sum, value_sum_sq;
+    uint64_t faces;
+};                                                       /* 88 bytes, no padding */
+VPT_API int vpt_components_measure(vpt_components *c, vpt_volume *values, int channel, uint64_t first, uint64_t n, struct vpt_component_measure *dst);
+/* (for measurements) the same, and the milliseconds of the measuring pass alone in *ms, the stream drained either side */
+VPT_API int vpt_components_measure_timed(vpt_components *c, vpt_volume *values, int channel, uint64_t first, uint64_t n,
+                                         struct vpt_component_measure *dst, double *ms);
+/* a new, finalized volume of the source's size, format and filter: the source code where the voxel's rank is one of ranks[0 .. n - 1],
+ * `fill` elsewhere.  Ranks are 1-based: a rank of 0 is VPT_ERR_INVALID; ranks above `listed` are ignored (as vpt_components_keep ignores a
+ * last_rank beyond the list); duplicates are allowed; n = 0 gives a volume of `fill` (ranks may then be null).  fill above the format's
+ * largest code: VPT_ERR_INVALID.  With the ranks a .. b the result equals vpt_components_keep(c, a, b, fill) byte for byte.
+ * vpt_amd.keep_set_texels states it in numpy. */
+VPT_API int vpt_components_keep_set(vpt_components *c, const uint64_t *ranks, uint64_t n, uint32_t fill, vpt_volume **out);
 /* (for measurements) milliseconds of the phases of vpt_volume_components, ms[VPT_COMPONENTS_PHASES]: tile labelling, merge launches, flatten
  * launches, sizes, census + compaction, host sort, rank write; launches[2]: merge and flatten launches.  Either pointer may be null. */
 #define VPT_COMPONENTS_PHASES 7

@@ -357,6 +357,35 @@ static napi_value ComponentsLabel(napi_env env, napi_callback_info info) {
     VPT_CHECK(vpt_components_label(c, &out));
     return make_external(env, out);
 }
+// componentsMeasure(components, values | null, channel, first, dst): dst holds 88 n bytes (any TypedArray / ArrayBuffer), the records
+// (struct vpt_component_measure) of components first .. first + n - 1; js/vpt/Volume.js reads the 64-bit fields out as BigInts
+static bool get_measure(napi_env env, napi_callback_info info, size_t extra, napi_value *a, vpt_components **c, vpt_volume **values, int32_t *channel,
+                        uint64_t *first, void **data, size_t *n) {
+    return get_args(env, info, 5 + extra, a) && get_handle(env, a[0], c) && get_handle(env, a[1], values, true) && get_i32(env, a[2], channel) &&
+           get_u64(env, a[3], first) && get_bytes(env, a[4], data, n);
+}
+static napi_value ComponentsMeasure(napi_env env, napi_callback_info info) {
+    napi_value a[5]; vpt_components *c; vpt_volume *values; int32_t channel; uint64_t first; void *data; size_t n;
+    if (!get_measure(env, info, 0, a, &c, &values, &channel, &first, &data, &n)) return nullptr;
+    VPT_CHECK(vpt_components_measure(c, values, channel, first, n / sizeof(struct vpt_component_measure), (struct vpt_component_measure *)data));
+    return undefined(env);
+}
+// componentsMeasureTimed(the same) -> the milliseconds of the measuring pass alone
+static napi_value ComponentsMeasureTimed(napi_env env, napi_callback_info info) {
+    napi_value a[5]; vpt_components *c; vpt_volume *values; int32_t channel; uint64_t first; void *data; size_t n;
+    if (!get_measure(env, info, 0, a, &c, &values, &channel, &first, &data, &n)) return nullptr;
+    double ms = 0.0;
+    VPT_CHECK(vpt_components_measure_timed(c, values, channel, first, n / sizeof(struct vpt_component_measure), (struct vpt_component_measure *)data, &ms));
+    return number(env, ms);
+}
+// componentsKeepSet(components, ranks, fill) -> a new volume handle; ranks is a BigUint64Array of 1-based ranks
+static napi_value ComponentsKeepSet(napi_env env, napi_callback_info info) {
+    napi_value a[3]; vpt_components *c; void *data; size_t n; uint32_t fill;
+    if (!get_args(env, info, 3, a) || !get_handle(env, a[0], &c) || !get_bytes(env, a[1], &data, &n) || !get_u32(env, a[2], &fill)) return nullptr;
+    vpt_volume *out = nullptr;
+    VPT_CHECK(vpt_components_keep_set(c, (const uint64_t *)data, n / sizeof(uint64_t), fill, &out));
+    return make_external(env, out);
+}
 static napi_value ComponentsDestroy(napi_env env, napi_callback_info info) {
     napi_value a[1]; vpt_components *c;
     if (!get_args(env, info, 1, a) || !get_handle(env, a[0], &c)) return nullptr;
@@ -739,6 +768,7 @@ static napi_value Init(napi_env env, napi_value exports) {
     EXPORT("volumeCombine", VolumeCombine); EXPORT("volumeCombineTimed", VolumeCombineTimed); EXPORT("volumeCompare", VolumeCompare);
     EXPORT("volumeComponents", VolumeComponents); EXPORT("componentsInfo", ComponentsInfo); EXPORT("componentsList", ComponentsList);
     EXPORT("componentsRanks", ComponentsRanks); EXPORT("componentsKeep", ComponentsKeep); EXPORT("componentsLabel", ComponentsLabel);
+    EXPORT("componentsMeasure", ComponentsMeasure); EXPORT("componentsMeasureTimed", ComponentsMeasureTimed); EXPORT("componentsKeepSet", ComponentsKeepSet);
     EXPORT("componentsDestroy", ComponentsDestroy);
     EXPORT("volumeDistance", VolumeDistance); EXPORT("distanceInfo", DistanceInfo); EXPORT("distanceSquared", DistanceSquared);
     EXPORT("distanceWithin", DistanceWithin); EXPORT("distanceChannel", DistanceChannel); EXPORT("distanceProfile", DistanceProfile);

@@ -5,6 +5,7 @@ const { native } = require('./native.js');
 
 const R = require('./readers/readers.js');
 const { checkConnectivity, checkRange, checkMinVoxels, checkKeep } = require('./components.js');
+const { checkWindow, checkRankSet } = require('./measure.js');
 const { checkSeeds, checkSteps, checkRadius, checkWithin, checkDistanceRange } = require('./distance.js');
 const { checkResampleMode, checkResampleSize, isotropicShape } = require('./resample.js');
 const { COMBINE_STATS, checkCombineOp, checkCombineChannel, checkCombineWeights, checkCombineMask, checkCompareRange, compareRatios } = require('./combine.js');
@@ -593,6 +594,49 @@ keep(first, last, fill) {
 
 // a new, ready RG8 / RG16 volume with the source's filter: (code, min(rank, M)): the rows of a 2-D transfer function select the structures
 label() { return this._derived(native().componentsLabel(this._handle()), true); }
+
+// the arguments of the native measure calls and the buffer they fill: 88 bytes a record (struct vpt_component_measure)
+_measureArgs(first, n, values, channel) {
+    const w = checkWindow(first !== undefined ? first : 0, n, this.info.listed);
+    if (values !== undefined && values !== null && !(values instanceof Volume && values.texture)) { throw new Error('measure takes a ready volume as values'); }
+    channel = channel !== undefined ? channel : 0;
+    if (!Number.isInteger(channel)) { throw new Error('channel is 0 or 1, not ' + JSON.stringify(channel)); }
+    return [values ? values.texture : null, channel, w[0], new ArrayBuffer(88 * w[1])];
+}
+static _records(buffer) {
+    const view = new DataView(buffer), out = [];
+    for (let at = 0; at < buffer.byteLength; at += 88) {
+        const u32 = k => view.getUint32(at + 8 + 4 * k, true), u64 = k => view.getBigUint64(at + 40 + 8 * k, true);
+        out.push({ voxels: view.getBigUint64(at, true), minX: u32(0), minY: u32(1), minZ: u32(2), maxX: u32(3), maxY: u32(4), maxZ: u32(5), valueMin: u32(6),
+                   valueMax: u32(7), sumX: u64(0), sumY: u64(1), sumZ: u64(2), valueSum: u64(3), valueSumSq: u64(4), faces: u64(5) });
+    }
+    return out;
+}
+
+// one record per component of rank first + 1 .. first + n (defaults: the whole list): { voxels, minX .. maxZ, valueMin, valueMax, sumX, sumY,
+// sumZ, valueSum, valueSumSq, faces } counted on the device, the 64-bit fields as BigInts; `values` (an R8, RG8, R16 or RG16 volume of this
+// size; default: the labelled texels) and `channel` choose what is measured under the components (measure.js: measureTexels states it,
+// derive gives centroid, mean, variance, extents)
+measure(first, n, values, channel) {
+    const a = this._measureArgs(first, n, values, channel);
+    native().componentsMeasure(this._handle(), a[0], a[1], a[2], a[3]);
+    return Components._records(a[3]);
+}
+
+// (for measurements) [the records, the milliseconds of the measuring pass alone]
+measureTimed(first, n, values, channel) {
+    const a = this._measureArgs(first, n, values, channel);
+    const ms = native().componentsMeasureTimed(this._handle(), a[0], a[1], a[2], a[3]);
+    return [Components._records(a[3]), ms];
+}
+
+// a new, ready volume of the source's size, format and filter: the source's code where the voxel's rank is in `ranks` (an iterable of
+// 1-based ranks, numbers or BigInts, duplicates and ranks beyond the list allowed; or booleans, one per listed component), `fill` elsewhere
+keepSet(ranks, fill) {
+    const set = checkRankSet(ranks, this.info.listed);
+    const k = checkKeep(1, null, fill !== undefined ? fill : 0, this._norm16 ? 65535 : 255);
+    return this._derived(native().componentsKeepSet(this._handle(), BigUint64Array.from(set, BigInt), k[2]));
+}
 
 }
 // the number of smoothing passes (an integer in 1 .. 8) / of reductions (an integer >= 1); throws for anything else

@@ -23,6 +23,7 @@ from .window import window_texels, percentile_window
 from .pyramid import reduce_texels, smooth_texels
 from .rank import rank_texels
 from .components import components_texels, keep_texels, label_texels
+from .measure import measure_texels, keep_set_texels, derive, MEASURE_DTYPE
 from .distance import distance_squared_texels, within_texels, channel_texels, check_seeds, check_steps, check_radius
 from .resample import resample_texels, isotropic_shape, axis_taps, nearest_index, count_ties, check_mode, check_size, check_spacing
 from .combine import combine_texels, compare_stats, OPS, check_op, check_weights, check_channel
@@ -38,6 +39,7 @@ __all__ = [
     'UchimuraToneMapper', 'ToneMapperFactory', 'RenderingContext', 'CircleAnimator', 'OrbitCameraAnimator', 'TransferFunction',
     'HDRImage', 'read_hdr', 'gradient_magnitude', 'window_texels', 'percentile_window', 'reduce_texels', 'smooth_texels', 'rank_texels',
     'components_texels', 'keep_texels', 'label_texels', 'Components',
+    'measure_texels', 'keep_set_texels', 'derive', 'MEASURE_DTYPE',
     'distance_squared_texels', 'within_texels', 'channel_texels', 'check_seeds', 'check_steps', 'check_radius', 'Distance',
     'resample_texels', 'isotropic_shape', 'axis_taps', 'nearest_index', 'count_ties', 'check_mode', 'check_size', 'check_spacing',
     'combine_texels', 'compare_stats', 'OPS', 'check_op', 'check_weights', 'check_channel',

@@ -52,7 +52,8 @@ SYMBOLS = [
     "vpt_volume_window", "vpt_volume_range", "vpt_volume_code_histogram",
     "vpt_volume_reduce", "vpt_volume_smooth", "vpt_volume_rank",
     "vpt_volume_components", "vpt_components_info", "vpt_components_list", "vpt_components_ranks", "vpt_components_keep",
-    "vpt_components_label", "vpt_components_profile", "vpt_components_destroy",
+    "vpt_components_label", "vpt_components_measure", "vpt_components_measure_timed", "vpt_components_keep_set",
+    "vpt_components_profile", "vpt_components_destroy",
     "vpt_volume_distance", "vpt_distance_info", "vpt_distance_squared", "vpt_distance_within", "vpt_distance_channel",
     "vpt_distance_profile", "vpt_distance_destroy",
     "vpt_volume_resample", "vpt_volume_resample_timed",
@@ -108,6 +109,15 @@ class ComponentsInfo(C.Structure):
 
 
 COMPONENTS_PHASES = 7
+
+
+class ComponentMeasure(C.Structure):
+    """struct vpt_component_measure (include/vpt.h): 88 bytes, no padding (vpt_amd.measure.MEASURE_DTYPE is its numpy form)"""
+    _fields_ = [("voxels", C.c_uint64),
+                ("min_x", C.c_uint32), ("min_y", C.c_uint32), ("min_z", C.c_uint32), ("max_x", C.c_uint32), ("max_y", C.c_uint32), ("max_z", C.c_uint32),
+                ("value_min", C.c_uint32), ("value_max", C.c_uint32),
+                ("sum_x", C.c_uint64), ("sum_y", C.c_uint64), ("sum_z", C.c_uint64),
+                ("value_sum", C.c_uint64), ("value_sum_sq", C.c_uint64), ("faces", C.c_uint64)]
 
 
 class DistanceInfo(C.Structure):
@@ -200,6 +210,9 @@ def lib():
         "vpt_components_list": [P, C.c_uint64, C.c_uint64, C.POINTER(Component)], "vpt_components_ranks": [P, I, I, I, I, I, I, P, SZ],
         "vpt_components_keep": [P, C.c_uint64, C.c_uint64, C.c_uint32, PP], "vpt_components_label": [P, PP],
         "vpt_components_profile": [P, C.POINTER(C.c_double), C.POINTER(C.c_uint32)], "vpt_components_destroy": [P],
+        "vpt_components_measure": [P, P, I, C.c_uint64, C.c_uint64, C.POINTER(ComponentMeasure)],
+        "vpt_components_measure_timed": [P, P, I, C.c_uint64, C.c_uint64, C.POINTER(ComponentMeasure), C.POINTER(C.c_double)],
+        "vpt_components_keep_set": [P, C.POINTER(C.c_uint64), C.c_uint64, C.c_uint32, PP],
         "vpt_volume_distance": [P, C.c_uint32, C.c_uint32, I, PP], "vpt_distance_info": [P, C.POINTER(DistanceInfo)],
         "vpt_distance_squared": [P, I, I, I, I, I, I, P, SZ], "vpt_distance_within": [P, C.c_uint32, C.c_uint32, C.c_uint32, PP],
         "vpt_distance_channel": [P, I, PP], "vpt_distance_profile": [P, C.POINTER(C.c_double)], "vpt_distance_destroy": [P],

@@ -6,7 +6,7 @@
 // the voxel's rank.  Every link ever written joins two voxels of one component and points to a smaller index, so parents only decrease and
 // the root of a finished component is its smallest voxel whatever the order of arrival.  No workgroup waits for another: launch
 // boundaries order the phases, and within the merge launch L is touched through device-scope integer atomics only.
-#include "vpt_volume_field.h"
+#include "vpt_volume_components.h"
 
 // ---------------------------------------------------------------------------------------------
 // tile labelling: k_label_tiles<T, CONN>
@@ -272,12 +272,7 @@ struct RankChannel { __device__ __forceinline__ uint32_t operator()(uint32_t ran
 // ---------------------------------------------------------------------------------------------
 // host
 // ---------------------------------------------------------------------------------------------
-struct vpt_components : VoxelField {       // the values are L: at the end one rank per voxel
-    std::vector<vpt_component> list;        // canonical order
-    struct vpt_components_info info = {};
-    double ms[VPT_COMPONENTS_PHASES] = {};
-    uint32_t launches[2] = {};
-};
+// struct vpt_components: vpt_volume_components.h (vpt_volume_measure.hip reads the handle too)
 
 // chase steps a unite / a voxel's flatten may take in one launch: what vpt_volume_components passes
 #define CC_MERGE_STEPS 1024

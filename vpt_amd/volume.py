@@ -703,6 +703,46 @@ class Components(_VoxelField):
         N.check(N.lib().vpt_components_label(self._handle(), C.byref(h)))
         return self._derived(h, pair=True)
 
+    def _measure_args(self, first, n, values, channel):
+        from .measure import check_window, MEASURE_DTYPE
+        first, n = check_window(first, n, self.info['listed'])
+        if values is not None and (not isinstance(values, Volume) or not values.texture):
+            raise ValueError('measure takes a ready volume as values')
+        if isinstance(channel, bool) or not isinstance(channel, (int, np.integer)):
+            raise ValueError('channel is 0 or 1, not %r' % (channel,))
+        out = np.zeros(n, MEASURE_DTYPE)
+        return (self._handle(), values.texture if values is not None else None, int(channel), first, n,
+                out.ctypes.data_as(C.POINTER(N.ComponentMeasure))), out
+
+    def measure(self, first=0, n=None, values=None, channel=0):
+        """A structured array (vpt_amd.MEASURE_DTYPE), one record per component of rank first + 1 .. first + n (n None: to the end of the
+        list): voxels, bounding box, index sums, min / max / sum / sum of squares of channel ``channel`` of ``values`` (an R8, RG8, R16 or
+        RG16 volume of this size; None: the labelled texels themselves) under the component, and its surface in voxel faces, all exact
+        integers counted on the device (vpt_amd.measure_texels states them; vpt_amd.derive gives centroid, mean, variance, extents)."""
+        args, out = self._measure_args(first, n, values, channel)
+        N.check(N.lib().vpt_components_measure(*args))
+        return out
+
+    def measure_timed(self, first=0, n=None, values=None, channel=0):
+        """(for measurements) (the records ``measure`` gives, the milliseconds of the measuring pass alone, the stream drained around it)"""
+        args, out = self._measure_args(first, n, values, channel)
+        ms = C.c_double(0)
+        N.check(N.lib().vpt_components_measure_timed(*(args + (C.byref(ms),))))
+        return out, ms.value
+
+    def keep_set(self, ranks, fill=0):
+        """A new, ready volume of the source's size, format and filter: the source's code where the voxel's rank is in ``ranks`` (an
+        iterable of 1-based ranks; duplicates and ranks beyond the list are allowed; or a boolean array with one entry per listed
+        component), ``fill`` elsewhere (vpt_amd.keep_set_texels states it)"""
+        from .components import check_keep
+        from .measure import check_rank_set
+        ranks = check_rank_set(ranks, self.info['listed'])
+        fill = check_keep(1, None, fill, 65535 if self._norm16 else 255)[2]
+        buf = (C.c_uint64 * max(len(ranks), 1))(*ranks)
+        h = C.c_void_p()
+        N.check(N.lib().vpt_components_keep_set(self._handle(), buf, len(ranks), fill, C.byref(h)))
+        return self._derived(h)
+
     def profile(self):
         """(for measurements) ({phase: milliseconds}, merge launches, flatten launches) of the labelling"""
         ms = (C.c_double * N.COMPONENTS_PHASES)()
