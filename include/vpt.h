@@ -447,6 +447,58 @@ VPT_API int vpt_volume_combine_timed(vpt_volume *a, vpt_volume *b, const struct 
  * of `out` can wrap.  Dice 2 both / (in_a + in_b), Jaccard, MSE and PSNR follow on the host.  Blocks.  Two runs give identical counts. */
 VPT_API int vpt_volume_compare(vpt_volume *a, vpt_volume *b, int b_channel, uint32_t lo_a, uint32_t hi_a, uint32_t lo_b, uint32_t hi_b, uint64_t out[8]);
 
+/* ---- grey-level morphological reconstruction and the geodesic operations on the device (extension; DESIGN.md "Geodesic reconstruction") */
+/* The rank filters work over a fixed 3 x 3 x 3 box.  These propagate a value THROUGH a structure as far as it reaches: fill the cavities of
+ * a structure, remove what touches the border, suppress maxima shallower than h, find the regional maxima of a distance channel (the seeds
+ * that tell two touching structures apart).  All of them are one primitive, the reconstruction of a marker under a mask.
+ *   Sources: R8, RG8, R16 and RG16 with a channel argument (0, or 1 of a two-channel volume; anything else VPT_ERR_INVALID); every other
+ *   format: VPT_ERR_UNSUPPORTED, naming it.  marker and mask belong to one context and have the same width, height and depth, otherwise
+ *   VPT_ERR_INVALID (a size mismatch names both sizes), and channels of the same width, otherwise VPT_ERR_UNSUPPORTED, naming both
+ *   formats; they may be the same handle.  Connectivity c: 6, 18 or 26 as vpt_volume_components; anything else VPT_ERR_INVALID.  Nothing
+ *   wraps and nothing is clamped: a neighbour outside the volume does not exist.  All compares are unsigned on whole codes; M = 255 / 65535.
+ *   Reconstruction by dilation, R_d(marker, mask): r0 = min(marker, mask) (a marker above the mask is clamped, not refused),
+ *     r_k+1(v) = min(mask(v), max(r_k(v), max over the c-neighbours u of v of r_k(u))), and the result is the first r_k with r_k+1 = r_k.
+ *     Equivalently R(v) is the maximum, over all voxels s and all c-connected paths from s to v, of min(r0(s), min of the mask along the
+ *     path): the result is unique, whatever order the device works in.
+ *   Reconstruction by erosion: R_e(marker, mask) = M - R_d(M - marker, M - mask): r0 = max(marker, mask), min and max exchanged.
+ *   vpt_volume_geodesic makes the marker on the device (it never exists as a volume).  h is 0 for the operations that take none and at
+ *   most M, otherwise VPT_ERR_INVALID; any other op: VPT_ERR_INVALID.
+ *     FILL_HOLES    R_e(m, src), m = src on the voxels of the volume's six faces, M elsewhere: every regional minimum not connected to
+ *                   the border is raised to its rim; c is the connectivity of the path to the border
+ *     CLEAR_BORDER  src - R_d(m, src), m = src on the six faces, 0 elsewhere
+ *     HMAX          R_d(max(src - h, 0), src); h = 0 gives src
+ *     HMIN          R_e(min(src + h, M), src)
+ *     DOME          src - HMAX_h(src)
+ *     MAXIMA        M where src > HMAX_1(src), 0 elsewhere: the plateaus without a higher c-neighbour.  A voxel of code 0 is never a
+ *                   maximum; this is part of the contract
+ *     MINIMA        M where src < HMIN_1(src), 0 elsewhere.  A voxel of code M is never a minimum
+ * vpt_amd.reconstruct_texels and geodesic_texels state all of it in numpy.
+ * The result is a new, finalized ONE-channel R8 / R16 volume of the sources' size and channel width on their context, with the filter of
+ * marker / src: an ordinary volume for every renderer and every other volume operation.  The calls block (the host reads a word between
+ * launches); the sources are not changed, need not be finalized and may be destroyed afterwards.  Two runs give identical bytes.  Volumes
+ * of more than 2^32 - 2 voxels: VPT_ERR_UNSUPPORTED, like the components. */
+#define VPT_RECONSTRUCT_DILATION 0
+#define VPT_RECONSTRUCT_EROSION  1
+#define VPT_GEODESIC_FILL_HOLES   0
+#define VPT_GEODESIC_CLEAR_BORDER 1
+#define VPT_GEODESIC_HMAX         2
+#define VPT_GEODESIC_HMIN         3
+#define VPT_GEODESIC_DOME         4
+#define VPT_GEODESIC_MAXIMA       5
+#define VPT_GEODESIC_MINIMA       6
+VPT_API int vpt_volume_reconstruct(vpt_volume *marker, int marker_channel, vpt_volume *mask, int mask_channel, int op, int connectivity, vpt_volume **out);
+VPT_API int vpt_volume_geodesic(vpt_volume *src, int channel, int op, uint32_t h, int connectivity, vpt_volume **out);
+/* (for measurements) the same, and in *ms the milliseconds of the call up to the finalize of the result, the stream drained either side;
+ * in *launches the launches of the propagation kernel and, unless it is null, in *tile_runs the tiles that did work, summed over them */
+VPT_API int vpt_volume_reconstruct_timed(vpt_volume *marker, int marker_channel, vpt_volume *mask, int mask_channel, int op, int connectivity,
+                                         vpt_volume **out, double *ms, uint32_t *launches, uint64_t *tile_runs);
+VPT_API int vpt_volume_geodesic_timed(vpt_volume *src, int channel, int op, uint32_t h, int connectivity, vpt_volume **out, double *ms,
+                                      uint32_t *launches, uint64_t *tile_runs);
+/* (for tests) vpt_volume_reconstruct with the rounds a tile may make in LDS per launch given (the library's own: 2049, which no tile can
+ * need); tile_rounds < 1: VPT_ERR_INVALID.  The result is the contract's whatever the cap; ms and launches as above, either may be null. */
+VPT_API int vpt_volume_reconstruct_capped(vpt_volume *marker, int marker_channel, vpt_volume *mask, int mask_channel, int op, int connectivity,
+                                          int tile_rounds, vpt_volume **out, double *ms, uint32_t *launches);
+
 /* ---- renderer: AbstractRenderer.js:17-116 and the four subclasses */
 /* new R(gl, volume, camera, environmentTexture, {resolution}) — AbstractRenderer.js:17-49; width != height is the
  * documented extension (uInverseResolution = (1/W, 1/H)).  Buffers are allocated as in _rebuildBuffers :78-92. */

@@ -270,6 +270,55 @@ static napi_value VolumeCompare(napi_env env, napi_callback_info info) {
     }
     return out;
 }
+// ---- morphological reconstruction and the geodesic operations ---------------------------------------------
+// [a new volume handle, milliseconds, launches of the propagation kernel, tile runs] of the timed forms
+static napi_value recon_profile(napi_env env, vpt_volume *out, double ms, uint32_t launches, uint64_t tile_runs) {
+    napi_value r, e;
+    napi_create_array_with_length(env, 4, &r);
+    napi_set_element(env, r, 0, make_external(env, out));
+    napi_create_double(env, ms, &e); napi_set_element(env, r, 1, e);
+    napi_create_double(env, (double)launches, &e); napi_set_element(env, r, 2, e);
+    napi_create_double(env, (double)tile_runs, &e); napi_set_element(env, r, 3, e);
+    return r;
+}
+// volumeReconstruct(marker, markerChannel, mask, maskChannel, op, connectivity) -> a new volume handle: VPT_RECONSTRUCT_* of the marker under the mask
+static napi_value VolumeReconstruct(napi_env env, napi_callback_info info) {
+    napi_value a[6]; vpt_volume *m, *k; int32_t mc, kc, op, conn;
+    if (!get_args(env, info, 6, a) || !get_handle(env, a[0], &m) || !get_i32(env, a[1], &mc) || !get_handle(env, a[2], &k) || !get_i32(env, a[3], &kc) ||
+        !get_i32(env, a[4], &op) || !get_i32(env, a[5], &conn)) return nullptr;
+    vpt_volume *out = nullptr;
+    VPT_CHECK(vpt_volume_reconstruct(m, mc, k, kc, op, conn, &out));
+    return make_external(env, out);
+}
+// volumeReconstructTimed(the same, tileRounds) -> [handle, ms, launches, tile runs]; tileRounds 0: the library's own round cap, otherwise
+// vpt_volume_reconstruct_capped (no tile runs)
+static napi_value VolumeReconstructTimed(napi_env env, napi_callback_info info) {
+    napi_value a[7]; vpt_volume *m, *k; int32_t mc, kc, op, conn, rounds;
+    if (!get_args(env, info, 7, a) || !get_handle(env, a[0], &m) || !get_i32(env, a[1], &mc) || !get_handle(env, a[2], &k) || !get_i32(env, a[3], &kc) ||
+        !get_i32(env, a[4], &op) || !get_i32(env, a[5], &conn) || !get_i32(env, a[6], &rounds)) return nullptr;
+    vpt_volume *out = nullptr; double ms = 0.0; uint32_t launches = 0; uint64_t runs = 0;
+    if (rounds == 0) VPT_CHECK(vpt_volume_reconstruct_timed(m, mc, k, kc, op, conn, &out, &ms, &launches, &runs));
+    else VPT_CHECK(vpt_volume_reconstruct_capped(m, mc, k, kc, op, conn, rounds, &out, &ms, &launches));
+    return recon_profile(env, out, ms, launches, runs);
+}
+// volumeGeodesic(volume, channel, op, h, connectivity) -> a new volume handle: the geodesic operation VPT_GEODESIC_*
+static napi_value VolumeGeodesic(napi_env env, napi_callback_info info) {
+    napi_value a[5]; vpt_volume *v; int32_t channel, op, conn; uint32_t h;
+    if (!get_args(env, info, 5, a) || !get_handle(env, a[0], &v) || !get_i32(env, a[1], &channel) || !get_i32(env, a[2], &op) || !get_u32(env, a[3], &h) ||
+        !get_i32(env, a[4], &conn)) return nullptr;
+    vpt_volume *out = nullptr;
+    VPT_CHECK(vpt_volume_geodesic(v, channel, op, h, conn, &out));
+    return make_external(env, out);
+}
+// volumeGeodesicTimed(the same) -> [handle, ms, launches, tile runs]
+static napi_value VolumeGeodesicTimed(napi_env env, napi_callback_info info) {
+    napi_value a[5]; vpt_volume *v; int32_t channel, op, conn; uint32_t h;
+    if (!get_args(env, info, 5, a) || !get_handle(env, a[0], &v) || !get_i32(env, a[1], &channel) || !get_i32(env, a[2], &op) || !get_u32(env, a[3], &h) ||
+        !get_i32(env, a[4], &conn)) return nullptr;
+    vpt_volume *out = nullptr; double ms = 0.0; uint32_t launches = 0; uint64_t runs = 0;
+    VPT_CHECK(vpt_volume_geodesic_timed(v, channel, op, h, conn, &out, &ms, &launches, &runs));
+    return recon_profile(env, out, ms, launches, runs);
+}
 // volumeRange(volume) -> [lo, hi]: the smallest and the largest code or value
 static napi_value VolumeRange(napi_env env, napi_callback_info info) {
     napi_value a[1]; vpt_volume *v;
@@ -766,6 +815,8 @@ static napi_value Init(napi_env env, napi_value exports) {
     EXPORT("volumeWindow", VolumeWindow); EXPORT("volumeRange", VolumeRange); EXPORT("volumeCodeHistogram", VolumeCodeHistogram);
     EXPORT("volumeReduce", VolumeReduce); EXPORT("volumeSmooth", VolumeSmooth); EXPORT("volumeRank", VolumeRank); EXPORT("volumeResample", VolumeResample);
     EXPORT("volumeCombine", VolumeCombine); EXPORT("volumeCombineTimed", VolumeCombineTimed); EXPORT("volumeCompare", VolumeCompare);
+    EXPORT("volumeReconstruct", VolumeReconstruct); EXPORT("volumeReconstructTimed", VolumeReconstructTimed);
+    EXPORT("volumeGeodesic", VolumeGeodesic); EXPORT("volumeGeodesicTimed", VolumeGeodesicTimed);
     EXPORT("volumeComponents", VolumeComponents); EXPORT("componentsInfo", ComponentsInfo); EXPORT("componentsList", ComponentsList);
     EXPORT("componentsRanks", ComponentsRanks); EXPORT("componentsKeep", ComponentsKeep); EXPORT("componentsLabel", ComponentsLabel);
     EXPORT("componentsMeasure", ComponentsMeasure); EXPORT("componentsMeasureTimed", ComponentsMeasureTimed); EXPORT("componentsKeepSet", ComponentsKeepSet);

@@ -28,6 +28,9 @@
 //   destroyed afterwards, a `volume` stays the caller's; with `resample` set and differing sizes the second volume is first resampled to the
 //   primary's current grid in that mode.  The one-channel ops run behind `resample` and in front of `rank`; 'pair' runs where the gradient
 //   runs, so it cannot be combined with `gradient`, `components` mode 'label' or `distance` mode 'channel'
+//   geodesic: null (default) or { op: 'fill_holes' | 'clear_border' | 'hmax' | 'hmin' | 'dome' | 'maxima' | 'minima', h: 0, connectivity: 6 }: an
+//   R8 / R16 volume gets that geodesic operation (Volume.geodesic) behind the rank filter and in front of `components` mode 'keep' and the
+//   smoothing
 const { EventTarget, CustomEvent } = require('./EventTarget.js');
 const { Context } = require('./Context.js');
 const { OrbitCameraAnimator } = require('./animators.js');
@@ -38,6 +41,7 @@ const { checkConnectivity, checkRange, checkMinVoxels, checkKeep } = require('./
 const { checkSeeds, checkSteps, checkWithin, checkDistanceRange } = require('./distance.js');
 const { checkResampleMode, checkResampleSize, checkSpacing } = require('./resample.js');
 const { checkCombineOp, checkCombineChannel, checkCombineWeights, checkCombineMask } = require('./combine.js');
+const { checkGeodesicH } = require('./reconstruct.js');
 const { RendererFactory } = require('./renderers/RendererFactory.js');
 const { ToneMapperFactory } = require('./tonemappers/ToneMapperFactory.js');
 
@@ -83,6 +87,7 @@ constructor(options) {
             throw new Error("combine op 'pair' and distance mode 'channel' both write the second channel: name one of them");
         }
     }
+    this.geodesic = RenderingContext._geodesicSpec(options.geodesic);                // likewise
     this.gl = new Context(options.device || 0);                                   // initGL(), :61-105
     this.environmentTexture = { data: new Uint8Array([255, 255, 255, 255]), width: 1, height: 1 };   // :90-101
     this._rng = options.rng;
@@ -145,6 +150,14 @@ async setVolume(reader) {                                                       
             if (fmt === N.VPT_FORMAT_R8 || fmt === N.VPT_FORMAT_R16) {                 // the formats the smoothing takes: any other volume as it is
                 const source = this.volume;
                 this.volume = source.rank(this.rank, this.rankPasses);
+                source.destroy();
+            }
+        }
+        if (this.geodesic !== null) {
+            const N = native(), fmt = this.volume.nativeFormat();
+            if (fmt === N.VPT_FORMAT_R8 || fmt === N.VPT_FORMAT_R16) {                 // any other volume as it is
+                const source = this.volume, spec = this.geodesic;
+                this.volume = source.geodesic(spec.op, Math.min(spec.h, fmt === N.VPT_FORMAT_R16 ? 65535 : 255), spec.connectivity);
                 source.destroy();
             }
         }
@@ -304,6 +317,16 @@ static _distanceSpec(spec) {
         out.steps = checkSteps(given('steps') ? spec.steps : 1);
     }
     return out;
+}
+
+// the `geodesic` option with its defaults filled in, or null; throws for anything the contract does not take
+static _geodesicSpec(spec) {
+    if (spec === undefined || spec === null) { return null; }
+    if (typeof spec !== 'object' || Array.isArray(spec) || spec.op === undefined || Object.keys(spec).some(k => ['op', 'h', 'connectivity'].indexOf(k) < 0)) {
+        throw new Error('geodesic is null or { op, h, connectivity }, not ' + JSON.stringify(spec));
+    }
+    const h = checkGeodesicH(spec.op, spec.h !== undefined && spec.h !== null ? spec.h : 0, 65535);      // h is open above: an R8 volume takes min(h, 255)
+    return { op: spec.op, h, connectivity: checkConnectivity(spec.connectivity !== undefined && spec.connectivity !== null ? spec.connectivity : 6) };
 }
 
 // the `components` option with its defaults filled in, or null; throws for anything the contract does not take

@@ -9,6 +9,7 @@ const { checkWindow, checkRankSet } = require('./measure.js');
 const { checkSeeds, checkSteps, checkRadius, checkWithin, checkDistanceRange } = require('./distance.js');
 const { checkResampleMode, checkResampleSize, isotropicShape } = require('./resample.js');
 const { COMBINE_STATS, checkCombineOp, checkCombineChannel, checkCombineWeights, checkCombineMask, checkCompareRange, compareRatios } = require('./combine.js');
+const { checkReconstructOp, checkGeodesicOp, checkGeodesicH, checkSourceChannel } = require('./reconstruct.js');
 const { RAWReader, GL_RED, GL_RG, GL_RGB, GL_RGBA, GL_UNSIGNED_BYTE, GL_FLOAT, GL_HALF_FLOAT, GL_BYTE } = R;
 
 // [type, format, internalFormat, native format name, channels in the file, element kind] of the formats keyed on all three: SNORM bytes
@@ -423,6 +424,81 @@ compare(other, aRange, bRange, channel) {
     COMBINE_STATS.forEach((name, k) => { stats[name] = (BigInt(halves[2 * k + 1]) << 32n) | BigInt(halves[2 * k]); });
     return Object.assign(stats, compareRatios(stats, Math.max(largestA, largestB)));
 }
+
+// ---- extension: morphological reconstruction and the geodesic operations (include/vpt.h; DESIGN.md "Geodesic reconstruction") ----
+// the ready one-channel R8 / R16 Volume around a native volume derived from this (R8, RG8, R16 or RG16) one
+_oneChannel(texture) {
+    const N = native(), norm16 = this.nativeFormat() === N.VPT_FORMAT_R16 || this.nativeFormat() === N.VPT_FORMAT_RG16;
+    const modality = Object.assign({}, this.modality, { format: GL_RED, internalFormat: norm16 ? R.GL_R16_EXT : R.GL_R8,
+        type: norm16 ? R.GL_UNSIGNED_SHORT : GL_UNSIGNED_BYTE });
+    return derivedVolume(new Volume(this._gl), texture, modality, (this.metadata || {}).meta, this.modality.dimensions);
+}
+// the arguments of native().volumeReconstruct behind reconstruct(mask, options)
+_reconstructArguments(mask, options) {
+    options = options || {};
+    const N = native(), code = checkReconstructOp(options.op !== undefined ? options.op : 'dilation');
+    const connectivity = checkConnectivity(options.connectivity !== undefined ? options.connectivity : 6);
+    if (!(mask instanceof Volume) || !mask.texture || !this.texture) { throw new Error('reconstruct takes two ready volumes'); }
+    const unknown = Object.keys(options).filter(k => ['op', 'connectivity', 'channel', 'maskChannel', 'tileRounds'].indexOf(k) < 0);
+    if (unknown.length) { throw new Error('reconstruct takes op, connectivity, channel and maskChannel, not ' + unknown.sort().join(', ')); }
+    const channel = checkSourceChannel(options.channel !== undefined ? options.channel : 0, texelLayout(N, this.modality).channels);
+    const maskChannel = checkSourceChannel(options.maskChannel !== undefined ? options.maskChannel : 0, texelLayout(N, mask.modality).channels);
+    return [this.texture, channel, mask.texture, maskChannel, code, connectivity];
+}
+// a new, ready one-channel R8 / R16 volume on this volume's context and with its filter: the morphological reconstruction, by options.op
+// 'dilation' (default) or 'erosion', of channel options.channel of this volume (the marker) under channel options.maskChannel of `mask` (R8,
+// RG8, R16, RG16 either; same size and channel width; may be this volume) with options.connectivity 6 (default), 18 or 26, propagated on
+// the device; neither volume is changed
+reconstruct(mask, options) {
+    return this._oneChannel(native().volumeReconstruct.apply(null, this._reconstructArguments(mask, options)));
+}
+// (for measurements) [the volume reconstruct() gives, { ms, launches, tileRuns }]: the milliseconds of the call up to the result's finalize,
+// the stream drained either side, the launches of the propagation kernel and the tiles that worked, summed over them; options.tileRounds
+// (for tests): the rounds a tile may make per launch (no tileRuns then)
+reconstructTimed(mask, options) {
+    const rounds = options && options.tileRounds !== undefined ? options.tileRounds : 0;
+    if (!Number.isInteger(rounds) || (options && options.tileRounds !== undefined && rounds < 1)) { throw new Error('tileRounds is an integer >= 1'); }
+    const r = native().volumeReconstructTimed.apply(null, this._reconstructArguments(mask, options).concat([rounds]));
+    return [this._oneChannel(r[0]), { ms: r[1], launches: r[2], tileRuns: r[3] }];
+}
+_geodesicArguments(op, h, connectivity, channel) {
+    const N = native(), code = checkGeodesicOp(op);
+    connectivity = checkConnectivity(connectivity !== undefined ? connectivity : 6);
+    if (!this.texture) { throw new Error('a geodesic operation takes a ready volume'); }
+    const layout = texelLayout(N, this.modality);
+    channel = checkSourceChannel(channel !== undefined ? channel : 0, layout.channels);
+    h = checkGeodesicH(op, h !== undefined ? h : 0, layout.array.BYTES_PER_ELEMENT === 2 ? 65535 : 255);
+    return [this.texture, channel, code, h, connectivity];
+}
+// a new, ready one-channel R8 / R16 volume on this (R8, RG8, R16 or RG16) volume's context and with its filter: the geodesic operation `op`
+// ('fill_holes' | 'clear_border' | 'hmax' | 'hmin' | 'dome' | 'maxima' | 'minima'; h for 'hmax', 'hmin' and 'dome') of channel `channel`, on the
+// device; this volume is not changed
+geodesic(op, h, connectivity, channel) {
+    return this._oneChannel(native().volumeGeodesic.apply(null, this._geodesicArguments(op, h, connectivity, channel)));
+}
+// (for measurements) [the volume geodesic() gives, { ms, launches, tileRuns }] as reconstructTimed()
+geodesicTimed(op, h, connectivity, channel) {
+    const r = native().volumeGeodesicTimed.apply(null, this._geodesicArguments(op, h, connectivity, channel));
+    return [this._oneChannel(r[0]), { ms: r[1], launches: r[2], tileRuns: r[3] }];
+}
+// every regional minimum not connected to the volume's border raised to its rim
+fillHoles(connectivity, channel) { return this.geodesic('fill_holes', 0, connectivity, channel); }
+fillHolesTimed(connectivity, channel) { return this.geodesicTimed('fill_holes', 0, connectivity, channel); }
+// what is connected to the volume's border removed, grey values kept
+clearBorder(connectivity, channel) { return this.geodesic('clear_border', 0, connectivity, channel); }
+clearBorderTimed(connectivity, channel) { return this.geodesicTimed('clear_border', 0, connectivity, channel); }
+// maxima / minima shallower than h suppressed; dome: this - hmax(h)
+hmax(h, connectivity, channel) { return this.geodesic('hmax', h, connectivity, channel); }
+hmaxTimed(h, connectivity, channel) { return this.geodesicTimed('hmax', h, connectivity, channel); }
+hmin(h, connectivity, channel) { return this.geodesic('hmin', h, connectivity, channel); }
+hminTimed(h, connectivity, channel) { return this.geodesicTimed('hmin', h, connectivity, channel); }
+dome(h, connectivity, channel) { return this.geodesic('dome', h, connectivity, channel); }
+domeTimed(h, connectivity, channel) { return this.geodesicTimed('dome', h, connectivity, channel); }
+// M on the plateaus without a higher (lower) neighbour, 0 elsewhere; a voxel of code 0 (M) is never a maximum (minimum)
+regionalMaxima(connectivity, channel) { return this.geodesic('maxima', 0, connectivity, channel); }
+regionalMaximaTimed(connectivity, channel) { return this.geodesicTimed('maxima', 0, connectivity, channel); }
+regionalMinima(connectivity, channel) { return this.geodesic('minima', 0, connectivity, channel); }
+regionalMinimaTimed(connectivity, channel) { return this.geodesicTimed('minima', 0, connectivity, channel); }
 
 // ---- extension: connected components of a value range (include/vpt.h; DESIGN.md "Connected components") ----
 // the connected components of the codes lo .. hi of this (R8 / R16) volume as a Components object, labelled on the device: connectivity 6

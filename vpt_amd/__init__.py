@@ -27,6 +27,7 @@ from .measure import measure_texels, keep_set_texels, derive, MEASURE_DTYPE
 from .distance import distance_squared_texels, within_texels, channel_texels, check_seeds, check_steps, check_radius
 from .resample import resample_texels, isotropic_shape, axis_taps, nearest_index, count_ties, check_mode, check_size, check_spacing
 from .combine import combine_texels, compare_stats, OPS, check_op, check_weights, check_channel
+from .reconstruct import reconstruct_texels, geodesic_texels, RECONSTRUCT_OPS, GEODESIC_OPS
 from ._native import VptError
 
 __all__ = [
@@ -43,4 +44,5 @@ __all__ = [
     'distance_squared_texels', 'within_texels', 'channel_texels', 'check_seeds', 'check_steps', 'check_radius', 'Distance',
     'resample_texels', 'isotropic_shape', 'axis_taps', 'nearest_index', 'count_ties', 'check_mode', 'check_size', 'check_spacing',
     'combine_texels', 'compare_stats', 'OPS', 'check_op', 'check_weights', 'check_channel',
+    'reconstruct_texels', 'geodesic_texels', 'RECONSTRUCT_OPS', 'GEODESIC_OPS',
 ]

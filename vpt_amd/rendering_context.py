@@ -87,6 +87,10 @@ class RenderingContext(EventTarget):
                 raise ValueError("combine op 'pair' and components mode 'label' both write the second channel: name one of them")
             if self.distance is not None and self.distance['mode'] == 'channel':
                 raise ValueError("combine op 'pair' and distance mode 'channel' both write the second channel: name one of them")
+        # (extension) None | {'op': 'fill_holes' | 'clear_border' | 'hmax' | 'hmin' | 'dome' | 'maxima' | 'minima', 'h': 0, 'connectivity': 6}: an
+        # R8 / R16 volume gets that geodesic operation (Volume.geodesic) when it is loaded, behind the rank filter and in front of
+        # `components` mode 'keep' and the smoothing
+        self.geodesic = self._geodesic_spec(options.get('geodesic'))
         self.gl = Context(options.get('device', 0))                                   # initGL(), :61-105
         self.environmentTexture = np.array([[[255, 255, 255, 255]]], dtype=np.uint8)   # :90-101
         self._rng = options.get('rng')
@@ -143,6 +147,10 @@ class RenderingContext(EventTarget):
             if self.rank is not None and self._one_channel_unorm(self.volume):
                 source = self.volume
                 self.volume = source.rank(self.rank, self.rankPasses)
+                source.destroy()
+            if self.geodesic is not None and self._one_channel_unorm(self.volume):
+                source = self.volume
+                self.volume = source.geodesic(self.geodesic['op'], min(self.geodesic['h'], self._largest_code(source)), self.geodesic['connectivity'])
                 source.destroy()
             if self.components is not None and self.components['mode'] == 'keep' and self._one_channel_unorm(self.volume):
                 self._derive(lambda source, found: found.keep(1, self.components['keep']))
@@ -221,6 +229,23 @@ class RenderingContext(EventTarget):
             if owned:
                 second.destroy()
         source.destroy()
+
+    @staticmethod
+    def _largest_code(volume):
+        from . import _native as N
+        return 65535 if volume.native_format()[0] == N.FORMAT_R16 else 255
+
+    @staticmethod
+    def _geodesic_spec(spec):
+        """the `geodesic` option with its defaults filled in, or None; raises ValueError for anything the contract does not take"""
+        if spec is None:
+            return None
+        from .components import check_connectivity
+        from .reconstruct import check_h
+        if not isinstance(spec, dict) or 'op' not in spec or not set(spec) <= {'op', 'h', 'connectivity'}:
+            raise ValueError("geodesic is None or {'op', 'h', 'connectivity'}, not %r" % (spec,))
+        h = check_h(spec['op'], spec['h'] if spec.get('h') is not None else 0, 65535)      # h is open above: an R8 volume takes min(h, 255)
+        return {'op': spec['op'], 'h': h, 'connectivity': check_connectivity(spec['connectivity'] if spec.get('connectivity') is not None else 6)}
 
     @staticmethod
     def _combine_spec(spec):

@@ -609,6 +609,124 @@ class Volume(EventTarget):
         stats.update(ratios(stats, max(largest_a, largest_b)))
         return stats
 
+    # ---- extension: morphological reconstruction and the geodesic operations (include/vpt.h; DESIGN.md "Geodesic reconstruction") ----
+    def _one_channel(self, handle):
+        """the ready one-channel R8 / R16 Volume around a native volume derived from this (R8, RG8, R16 or RG16) one"""
+        norm16 = self.native_format()[0] in (N.FORMAT_R16, N.FORMAT_RG16)
+        modality = dict(self.modality, format=GL_RED, internalFormat=GL_R16_EXT if norm16 else GL_R8,
+                        type=GL_UNSIGNED_SHORT if norm16 else GL_UNSIGNED_BYTE)
+        return _derived_volume(type(self)(self._gl), handle, modality, (self.metadata or {}).get('meta', {}), self.modality['dimensions'])
+
+    def _reconstruct(self, mask, op, connectivity, channel, mask_channel, timed, tile_rounds=None):
+        from .components import check_connectivity
+        from .reconstruct import check_reconstruct_op, check_source_channel
+        code, connectivity = check_reconstruct_op(op), check_connectivity(connectivity)
+        if not isinstance(mask, Volume) or not mask.texture or not self.texture:
+            raise ValueError('reconstruct takes two ready volumes')
+        channel = check_source_channel(channel, self._texel_layout()[0])
+        mask_channel = check_source_channel(mask_channel, mask._texel_layout()[0])
+        h, ms, launches, runs = C.c_void_p(), C.c_double(0), C.c_uint32(0), C.c_uint64(0)
+        L = N.lib()
+        if tile_rounds is not None:
+            N.check(L.vpt_volume_reconstruct_capped(self.texture, channel, mask.texture, mask_channel, code, connectivity, int(tile_rounds), C.byref(h),
+                                                    C.byref(ms), C.byref(launches)))
+        elif timed:
+            N.check(L.vpt_volume_reconstruct_timed(self.texture, channel, mask.texture, mask_channel, code, connectivity, C.byref(h), C.byref(ms),
+                                                   C.byref(launches), C.byref(runs)))
+        else:
+            N.check(L.vpt_volume_reconstruct(self.texture, channel, mask.texture, mask_channel, code, connectivity, C.byref(h)))
+            return self._one_channel(h)
+        return self._one_channel(h), {'ms': ms.value, 'launches': launches.value, 'tile_runs': runs.value}
+
+    def reconstruct(self, mask, op='dilation', connectivity=6, channel=0, mask_channel=0):
+        """A new, ready one-channel R8 / R16 volume on this volume's context and with its filter: the morphological reconstruction, by
+        'dilation' or 'erosion', of channel ``channel`` of this volume (the marker) under channel ``mask_channel`` of ``mask`` (R8, RG8, R16,
+        RG16 either; same size and channel width; may be this volume) with 6-, 18- or 26-connectivity (vpt_amd.reconstruct_texels states
+        it), propagated on the device.  Neither volume is changed."""
+        return self._reconstruct(mask, op, connectivity, channel, mask_channel, False)
+
+    def reconstruct_timed(self, mask, op='dilation', connectivity=6, channel=0, mask_channel=0, _tile_rounds=None):
+        """(for measurements) (the volume ``reconstruct`` gives, {'ms': the milliseconds of the call up to the result's finalize, the
+        stream drained either side, 'launches': the launches of the propagation kernel, 'tile_runs': the tiles that worked, summed over
+        them}).  ``_tile_rounds`` (for tests): the rounds a tile may make per launch, through vpt_volume_reconstruct_capped (no tile_runs)."""
+        return self._reconstruct(mask, op, connectivity, channel, mask_channel, True, _tile_rounds)
+
+    def _geodesic(self, op, h, connectivity, channel, timed):
+        from .components import check_connectivity
+        from .reconstruct import check_geodesic_op, check_h, check_source_channel
+        code, connectivity = check_geodesic_op(op), check_connectivity(connectivity)
+        if not self.texture:
+            raise ValueError('a geodesic operation takes a ready volume')
+        channels, dtype = self._texel_layout()
+        channel = check_source_channel(channel, channels)
+        h = check_h(op, h, 65535 if np.dtype(dtype).itemsize == 2 else 255)
+        out = C.c_void_p()
+        if not timed:
+            N.check(N.lib().vpt_volume_geodesic(self.texture, channel, code, h, connectivity, C.byref(out)))
+            return self._one_channel(out)
+        ms, launches, runs = C.c_double(0), C.c_uint32(0), C.c_uint64(0)
+        N.check(N.lib().vpt_volume_geodesic_timed(self.texture, channel, code, h, connectivity, C.byref(out), C.byref(ms), C.byref(launches), C.byref(runs)))
+        return self._one_channel(out), {'ms': ms.value, 'launches': launches.value, 'tile_runs': runs.value}
+
+    def geodesic(self, op, h=0, connectivity=6, channel=0):
+        """A new, ready one-channel R8 / R16 volume on this (R8, RG8, R16 or RG16) volume's context and with its filter: the geodesic
+        operation ``op`` ('fill_holes' | 'clear_border' | 'hmax' | 'hmin' | 'dome' | 'maxima' | 'minima'; ``h`` for 'hmax', 'hmin' and 'dome')
+        of channel ``channel`` (vpt_amd.geodesic_texels states them), on the device.  This volume is not changed."""
+        return self._geodesic(op, h, connectivity, channel, False)
+
+    def geodesic_timed(self, op, h=0, connectivity=6, channel=0):
+        """(for measurements) (the volume ``geodesic`` gives, {'ms', 'launches', 'tile_runs'} as ``reconstruct_timed``)"""
+        return self._geodesic(op, h, connectivity, channel, True)
+
+    def fill_holes(self, connectivity=6, channel=0):
+        """every regional minimum not connected to the volume's border (by ``connectivity``) raised to its rim"""
+        return self.geodesic('fill_holes', 0, connectivity, channel)
+
+    def fill_holes_timed(self, connectivity=6, channel=0):
+        return self.geodesic_timed('fill_holes', 0, connectivity, channel)
+
+    def clear_border(self, connectivity=6, channel=0):
+        """what is connected to the volume's border removed, grey values kept: src - R_d(border marker, src)"""
+        return self.geodesic('clear_border', 0, connectivity, channel)
+
+    def clear_border_timed(self, connectivity=6, channel=0):
+        return self.geodesic_timed('clear_border', 0, connectivity, channel)
+
+    def hmax(self, h, connectivity=6, channel=0):
+        """maxima shallower than ``h`` suppressed: R_d(max(src - h, 0), src)"""
+        return self.geodesic('hmax', h, connectivity, channel)
+
+    def hmax_timed(self, h, connectivity=6, channel=0):
+        return self.geodesic_timed('hmax', h, connectivity, channel)
+
+    def hmin(self, h, connectivity=6, channel=0):
+        """minima shallower than ``h`` suppressed: R_e(min(src + h, M), src)"""
+        return self.geodesic('hmin', h, connectivity, channel)
+
+    def hmin_timed(self, h, connectivity=6, channel=0):
+        return self.geodesic_timed('hmin', h, connectivity, channel)
+
+    def dome(self, h, connectivity=6, channel=0):
+        """src - hmax(h): the caps of height at most ``h`` on the maxima"""
+        return self.geodesic('dome', h, connectivity, channel)
+
+    def dome_timed(self, h, connectivity=6, channel=0):
+        return self.geodesic_timed('dome', h, connectivity, channel)
+
+    def regional_maxima(self, connectivity=6, channel=0):
+        """M on the plateaus without a higher neighbour, 0 elsewhere (a voxel of code 0 is never a maximum)"""
+        return self.geodesic('maxima', 0, connectivity, channel)
+
+    def regional_maxima_timed(self, connectivity=6, channel=0):
+        return self.geodesic_timed('maxima', 0, connectivity, channel)
+
+    def regional_minima(self, connectivity=6, channel=0):
+        """M on the plateaus without a lower neighbour, 0 elsewhere (a voxel of code M is never a minimum)"""
+        return self.geodesic('minima', 0, connectivity, channel)
+
+    def regional_minima_timed(self, connectivity=6, channel=0):
+        return self.geodesic_timed('minima', 0, connectivity, channel)
+
     def set_wide_tables(self, wide):
         """force the > 4 GiB addressing variant of the kernels (automatic above 4 GiB of bricked data)"""
         N.check(N.lib().vpt_volume_set_wide_tables(self.texture, 1 if wide else 0))
