@@ -158,6 +158,7 @@ def lib():
         L.vpo_mcm_fast64.restype = C.c_uint64; L.vpo_mcm_fast64.argtypes = [SP, FP, P, P, P, P, C.c_double, P, P, P, P]
         L.vpo_sample_volume.restype = C.c_float; L.vpo_sample_volume.argtypes = [SP, C.c_float, C.c_float, C.c_float]
         L.vpo_sample_volume_color.restype = None; L.vpo_sample_volume_color.argtypes = [SP, C.c_float, C.c_float, C.c_float, P]
+        L.vpo_sample_volume_colors.restype = None; L.vpo_sample_volume_colors.argtypes = [SP, P, C.c_size_t, P]
         L.vpo_sample_environment.restype = None; L.vpo_sample_environment.argtypes = [SP, C.c_float, C.c_float, C.c_float, P]
         L.vpo_unproject.restype = None; L.vpo_unproject.argtypes = [P, C.c_float, C.c_float, P, P]
         L.vpo_intersect_cube.restype = None; L.vpo_intersect_cube.argtypes = [P, P, P]

@@ -1257,6 +1257,17 @@ VPO_API void vpo_sample_volume_color(const vpo_scene *sc, float x, float y, floa
     out4[0] = c.x; out4[1] = c.y; out4[2] = c.z; out4[3] = c.w;
     tables_free(&t);
 }
+/* vpo_sample_volume_color at n positions (xyz triples) -> n colours: the same function, the tables decoded once */
+VPO_API void vpo_sample_volume_colors(const vpo_scene *sc, const float *xyz, size_t n, float *out4) {
+    scene_tables t; tables_init(&t, sc);
+    uint64_t ns = 0;
+    for (size_t i = 0; i < n; i++) {
+        v3 p = { xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2] };
+        v4 c = sample_volume_color(&t, p, &ns);
+        out4[4 * i] = c.x; out4[4 * i + 1] = c.y; out4[4 * i + 2] = c.z; out4[4 * i + 3] = c.w;
+    }
+    tables_free(&t);
+}
 VPO_API void vpo_sample_environment(const vpo_scene *sc, float x, float y, float z, float *out4) {
     scene_tables t; tables_init(&t, sc);
     v3 d = { x, y, z };

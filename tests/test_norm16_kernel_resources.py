@@ -2,12 +2,13 @@
 kernels, the ray marchers, ISO / Depth / LAO / DOS and the probes compile for gfx950 within the budgets of the byte and R32F forms
 (tests/test_kernel_resources.py): the per-tap decode of two-byte texels must not cost the hot kernels their occupancy or push them into
 scratch memory."""
+import os
 import re
 import shutil
 
 import pytest
 
-from test_snorm_kernel_resources import resource_usage
+from test_snorm_kernel_resources import ROOT, resource_usage
 
 
 def variant(name):
@@ -34,11 +35,17 @@ def test_norm16_kernels_fit_the_budgets():
     # every other 16-bit instantiation against its R32F twin (the same bits with VPT_V_F32 for VPT_V_NORM16 | VPT_V_SNORM): at least the twin's
     # occupancy (two channels: one wave less, the rule the SNORM and quasi-cubic budgets hold), and one channel no scratch memory, except
     # where the twin's own form has some: k_mcm_multi (the 64-byte allowance of tests/test_kernel_resources.py) and the fused quasi-cubic
-    # MCM integrate forms (up to 16 bytes, as tests/test_quasicubic_kernel_resources.py allows their R8 twins)
+    # MCM integrate forms (up to 16 bytes, as tests/test_quasicubic_kernel_resources.py allows their R8 twins).
+    # A kernel compiled FOR a number of waves (k_mip: VPT_MIP_WAVES, the measured choice of vpt_kernels.h) is held to that number where
+    # its twin happens to come out above it: inside the budget the allocator is free.  The R32F forms moved by a wave in both directions
+    # when their sampler learnt GL's index clamp (the fused k_mip<1, 36 | 292>: 73 / 74 VGPRs -> 69 / 70); the 16-bit forms, whose
+    # code did not change, stay at 74.
     kernels = {k: v for k, v in usage.items()
                if re.search(r"k_(mip|eam|mcs|iso|iso_render|depth|lao|dos_slice|mcm_integrate|mcm_multi|probe_sample|probe_sample_boundary)I", k)
                and variant(k)[1]}
     assert len(kernels) >= 500, len(kernels)
+    mip_waves = int(re.search(r"#define VPT_MIP_WAVES (\d+)", open(os.path.join(ROOT, "vpt_amd", "csrc", "vpt_kernels.h")).read()).group(1))
+    assert 6 <= mip_waves <= 8
     for name, u in kernels.items():
         m, v = variant(name)
         start = name.index("I") + m.start()
@@ -47,7 +54,8 @@ def test_norm16_kernels_fit_the_budgets():
         twin = next((t for t in twins if t in usage), None)
         assert twin is not None, (name, twins)
         t = usage[twin]
-        assert u.get("Occupancy", 0) >= min(t.get("Occupancy", 0), 7) - (1 if v & 8 else 0), (name, u, t)
+        budget = mip_waves if "k_mipI" in name else 7
+        assert u.get("Occupancy", 0) >= min(t.get("Occupancy", 0), 7, budget) - (1 if v & 8 else 0), (name, u, t)
         if not v & 8:
             if "mcm_multi" in name:
                 allowance = 64

@@ -315,8 +315,13 @@ struct LdsTables {
 };
 
 // LINEAR filter cell: u = s*N - 0.5 clamped to [0, N-1]; i = trunc(u); f = u - i.
-// Equal to the GL definition (taps clamp(i0), clamp(i0+1) of the unclamped u; oracle linear_coord) because every
-// clamped case degenerates to an exact edge value: u < 0 -> (t[0], f = 0); u >= N-1 -> (t[N-1], apron = t[N-1]).
+// The GL definition (oracle linear_coord) clamps the tap INDICES of the unclamped u, clamp(i0) and clamp(i0 + 1), not u.  The two agree
+//   * for u >= N-1: the cell is (t[N-1], apron = t[N-1]) with f = 0 here, (t[N-1], t[N-1]) with some f there, and lerp(t, t, f) =
+//     fma(f, t - t, t) does not depend on f for any t (t for a finite t, NaN for an infinite or NaN one);
+//   * for u < 0 (and a NaN u, which the oracle takes as -1) ONLY while t[1] - t[0] is finite: the cell here is (t[0], t[1]) with f = 0,
+//     there (t[0], t[0]), and fma(0, t[1] - t[0], t[0]) is t[0] for a finite difference but NaN for an infinite or NaN t[1] and for two
+//     finite texels whose difference overflows.  Byte, SNORM and 16-bit texels always meet the condition and use the cell as it is; the
+//     FLOAT path of sample_volume_rg replaces the second tap of such an axis by the first (below_first), as the index clamp does.
 // 4 instructions: v_fma, v_med3 (clamp; a NaN operand makes it return min3 of the others = 0), v_fract (= u - floor(u),
 // exact for u >= 0), v_cvt_u32 (truncation == floor for u >= 0).
 VPT_DEV void linear_cell(float s, float fn, float hi, uint32_t &i, float &f) {
@@ -324,6 +329,9 @@ VPT_DEV void linear_cell(float s, float fn, float hi, uint32_t &i, float &f) {
     f = __builtin_amdgcn_fractf(u);
     i = (uint32_t)u;
 }
+// is the unclamped u of linear_cell below 0 (or NaN)?  Then GL's clamp(i0 + 1) is texel 0 as well: both taps of the axis are t[0].  At
+// u == 0 exactly the second tap is t[1] in the oracle too (weight 0), so the comparison is strict.
+VPT_DEV bool below_first(float s, float fn) { return !(fmaf(s, fn, -0.5f) >= 0.0f); }
 VPT_DEV uint32_t nearest_cell(float s, float fn, float hi) {
     return (uint32_t)__builtin_amdgcn_fmed3f(s * fn, 0.0f, hi);   // u >= 0: truncation == floor
 }
@@ -620,7 +628,10 @@ VPT_DEV float boundary_blend(uint32_t w, float fa, float fb) {
 // texture(uVolume, clamp(p)).rg through the boundary atlas for ANY volume format and filter (V: VPT_V_NEAREST | VPT_V_RG | VPT_V_F32 | VPT_V_SNORM |
 // VPT_V_QCUBIC): channel c's faces lie
 // 6 * atlas_face cells behind channel c - 1's; float volumes keep four floats per cell.  Same texels, same order of operations as
-// sample_volume_rg<V> at the clamped position (float texels: finite ones, see vpt_volume_finalize).  Precondition as boundary_cell's.
+// sample_volume_rg<V> at the clamped position.  Float texels: the atlas is in use only while every texel is finite and below 1e37
+// (k_scan_finite at vpt_volume_finalize), where fma(0, t' - t, t) == t — the cells here keep linear_cell's (t[0], t[1]) at weight 0 below the
+// first texel centre of an in-face axis and need no second-tap select (below_first), which gives the same t[0] for such texels.
+// Precondition as boundary_cell's.
 template <int V>
 VPT_DEV f2 sample_boundary_rg(const DevVolume &v, f3 p) {
     // (16-bit normalised volumes keep the decoded texels in a float atlas: the FLOAT path)
@@ -687,6 +698,11 @@ VPT_DEV f2 sample_volume_rg(const DevVolume &v, const LdsTables &t, f3 p) {
         filter_cell<V>(p.y, v.fny, v.hy, y, fy);
         filter_cell<V>(p.z, v.fnz, v.hz, z, fz);
         const float *b0 = (const float *)cell_addr<WIDE>(v, t, x, y, z);
+        // a float texel can be infinite, NaN or huge: below the first texel centre of an axis the cell's second tap is the first one, as GL's
+        // index clamp gives it (linear_cell: the weight 0 alone does not keep t[1] out of fma(0, t[1] - t[0], t[0])).  Twelve v_cndmask per
+        // channel right behind the loads, three compares per sample.  (Selecting the BLENDS of y and z instead — c10 = c00, c1 = c0: seven
+        // selects, the same values — keeps more of them alive: k_lao, k_eam and k_mcs lost a wave of occupancy to it.)
+        const bool lx = below_first(p.x, v.fnx), ly = below_first(p.y, v.fny), lz = below_first(p.z, v.fnz);
         f2 out = { 0.0f, 0.0f };
 #pragma unroll
         for (int c = 0; c < (RG ? 2 : 1); c++) {
@@ -694,6 +710,9 @@ VPT_DEV f2 sample_volume_rg(const DevVolume &v, const LdsTables &t, f3 p) {
             // (the taps are dword-aligned, not 8-byte aligned: loaded through memcpy — still one global_load_dwordx2 each)
             float2 r00, r10, r01, r11;
             __builtin_memcpy(&r00, b, 8); __builtin_memcpy(&r10, b + 5, 8); __builtin_memcpy(&r01, b + 25, 8); __builtin_memcpy(&r11, b + 30, 8);
+            if (lx) { r00.y = r00.x; r10.y = r10.x; r01.y = r01.x; r11.y = r11.x; }
+            if (ly) { r10 = r00; r11 = r01; }
+            if (lz) { r01 = r00; r11 = r10; }
             float c00 = lerpf(r00.x, r00.y, fx), c10 = lerpf(r10.x, r10.y, fx);
             float c01 = lerpf(r01.x, r01.y, fx), c11 = lerpf(r11.x, r11.y, fx);
             const float val = lerpf(lerpf(c00, c10, fy), lerpf(c01, c11, fy), fz);

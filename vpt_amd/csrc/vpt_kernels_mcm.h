@@ -630,8 +630,9 @@ VPT_DEV void miss_sample_finish(const PassArgs &a, const float4 *tf, const MissL
 }
 // The same executed-and-discarded sample for the other volume formats (round 4): NEAREST filter, two channels (RG8 / RG32F: the G atlas 6 faces
 // behind the R atlas, the transfer function looked up in 2-D from HBM), float texels (one float4 per cell, no normalisation).  Same texels,
-// same order of operations as sample_volume_rg<V> at the clamped position: bit-identical (float texels: finite ones — the library does not
-// use the atlas of a float volume that holds others, vpt_volume_finalize).  One phase: these variants are not the benchmark's.
+// same order of operations as sample_volume_rg<V> at the clamped position: bit-identical (float texels: finite ones below 1e37 — the library
+// does not use the atlas of a float volume that holds others, vpt_volume_finalize; for those the bricks' second-tap select below the first
+// texel centre, vpt_device.h below_first, changes no value, so the atlas cells need none).  One phase: these variants are not the benchmark's.
 template <int V>
 VPT_DEV void miss_sample_any(const PassArgs &a, const float4 *tf, f3 q) {
     const f2 rg = sample_boundary_rg<V>(a.vol, q);
