@@ -19,7 +19,15 @@ ap.add_argument("--out", default="build/miss_wave_life")
 ap.add_argument("--volume", type=int, default=512)
 ap.add_argument("--frames", type=int, default=200)
 ap.add_argument("--settled", default="1,0", help="VPT_OPTION_SETTLED_MISS values to run: 1 = k_mcm_miss_settled (the headline's), 0 = k_mcm_miss")
+ap.add_argument("--order", default="wave", choices=["wave", "workgroup"],
+                help="what the prologue's slots 1-5 of the build mean: 'wave' = the plain variants' order without a workgroup barrier "
+                     "(vpt_kernels_mcm.h miss_wave_start); 'workgroup' = a build from before it (staged table, barrier)")
 args = ap.parse_args()
+SLOTS = {"wave": ["kernel_arguments_and_tile_list_entry_scalar_loads", "ndc_table_loads_flight_alpha_column_and_state_behind_them",
+                  "pixel_constants_seed_alpha_column_writes", "state_texel_flight_left_after_the_arithmetic",
+                  "photon_start_and_rest_up_to_the_first_event"],
+         "workgroup": ["kernel_arguments_and_tile_list_entry_scalar_loads", "state_ndc_table_and_transfer_function_loads_flight",
+                       "pixel_constants_seed_photon_start", "wait_at_the_workgroup_barrier", "rest_up_to_the_first_event"]}
 os.environ["VPT_HIP_LIBRARY"] = os.path.abspath(args.lib)
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -93,8 +101,7 @@ for fast in (1, 0):
                      "hit_tiles": hit, "miss_tiles": miss, "miss_waves_per_frame": waves / args.frames, "settled_passes": r.settled_passes(),
                      "frame_us_wall_instrumented": wall,
                      "miss_wave_ns": {"prologue_up_to_the_first_event": pro, "events": ev, "epilogue_state_store": epi, "life": life},
-                     "prologue_ns": dict(zip(["kernel_arguments_and_tile_list_entry_scalar_loads", "state_ndc_table_and_transfer_function_loads_flight",
-                                              "pixel_constants_seed_photon_start", "wait_at_the_workgroup_barrier", "rest_up_to_the_first_event"], parts)),
+                     "prologue_ns": dict(zip(SLOTS[args.order], parts)),
                      "share_of_life": {"prologue": pro / life, "events": ev / life, "epilogue": epi / life},
                      "hit_wave_life_ns_instrumented": 10.0 * sum(th[:8]) / max(th[8], 1),
                      "last_launch_timeline_us_after_the_first_miss_wave_started": {

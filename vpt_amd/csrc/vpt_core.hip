@@ -1112,12 +1112,22 @@ static int probe_sample(vpt_renderer *r, const float *xyz, float *rgba, size_t n
     HIP_TRY(dout.alloc(n));
     HIP_TRY(hipMemcpyAsync(din, xyz, 3 * n * sizeof(float), hipMemcpyHostToDevice, c->stream));
     dim3 grid((unsigned)((n + 255) / 256));
+    // (the boundary probe of a plain volume stages the MISS-tile kernels' alpha columns, tf_w * 8 bytes for each of its four waves, behind the
+    // image: twice the transfer function's share of the LDS, so a wide one passes 64 KiB sooner — lds_prepare asks for it or refuses)
+    const size_t lds = boundary ? lds_bytes(r) + 4 + (size_t)r->tf_w * 32 : lds_bytes(r);
+    int prepared = VPT_OK;
     const bool launched = dispatch_sampler_variant(variant_of(r), [&](auto V) {
-        if (boundary) hipLaunchKernelGGL(k_probe_sample_boundary<V()>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din.get(), dout.get(), n);
-        else hipLaunchKernelGGL(k_probe_sample<V()>, grid, dim3(VPT_BLOCK), lds_bytes(r), c->stream, a, din.get(), dout.get(), n);
+        if (boundary) {
+            prepared = lds_prepare((const void *)k_probe_sample_boundary<V()>, lds);
+            if (prepared == VPT_OK) hipLaunchKernelGGL(k_probe_sample_boundary<V()>, grid, dim3(VPT_BLOCK), lds, c->stream, a, din.get(), dout.get(), n);
+        } else {
+            prepared = lds_prepare((const void *)k_probe_sample<V()>, lds);
+            if (prepared == VPT_OK) hipLaunchKernelGGL(k_probe_sample<V()>, grid, dim3(VPT_BLOCK), lds, c->stream, a, din.get(), dout.get(), n);
+        }
         return true;
     }, [] { return false; });
     if (!launched) return fail(VPT_ERR_INVALID, "no probe kernel for variant %d", variant_of(r));
+    VPT_TRY(prepared);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(rgba, dout, n * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));

@@ -754,6 +754,15 @@ VPT_DEV float4 sample_tf(const float4 *tf_pairs, float tf_fw, float tf_hi, float
     float4 a = tf_pairs[2 * i], d = tf_pairs[2 * i + 1];
     return make_float4(fmaf(f, d.x, a.x), fmaf(f, d.y, a.y), fmaf(f, d.z, a.z), fmaf(f, d.w, a.w));
 }
+// the alpha of sample_tf alone, from the alpha column of the pairs { tf[t].w, tf[min(t + 1, w - 1)].w - tf[t].w } (vpt_kernels.h tf_alpha_*):
+// the same index arithmetic, the same two values, the same fma — the same bits as sample_tf(...).w
+VPT_DEV float sample_tf_alpha(const float2 *alpha_pairs, float tf_fw, float tf_hi, float r) {
+    float u = __builtin_amdgcn_fmed3f(fmaf(r, tf_fw, -0.5f), 0.0f, tf_hi);
+    float f = __builtin_amdgcn_fractf(u);
+    uint32_t i = (uint32_t)u;
+    float2 p = alpha_pairs[i];
+    return fmaf(f, p.y, p.x);
+}
 
 // environment map (RGBA8 decoded to float4 in HBM): MCSRenderer.glsl:59-62 / MCMRenderer.glsl:80-83
 struct DevEnv {

@@ -122,6 +122,21 @@ VPT_DEV Pix map_pixel(const PixMap &m) {
 // pixel-centre NDC from the host-built tables (the IEEE divisions (2i+1)/W are done once per image size, not per pixel)
 VPT_DEV float ndc_col(const PixMap &m, int i) { return m.ndc_x[i]; }
 VPT_DEV float ndc_row(const PixMap &m, int j) { return m.ndc_y[j]; }
+// map_pixel for the one launch shape of the MISS-tile kernels (k_mcm_miss, k_mcm_miss_settled): a 1-D grid over a tile list, 256-thread
+// workgroups, `t` = the workgroup's list entry tx | ty << 16 (the caller loads it: tile_list[blockIdx.x], blockIdx.x < list_n).  No 2-D-grid
+// branch and no blockDim test: nothing here waits for more than the kernel arguments.  Same pixels, same buffer order.
+VPT_DEV Pix map_listed_pixel(const PixMap &m, uint32_t t) {
+    const int tx = (int)(t & 0xffffu), ty = (int)(t >> 16);
+    const int w = (int)threadIdx.x >> 6, lane = (int)threadIdx.x & 63;
+    Pix p;
+    p.i = tx * VPT_TILE + (w & 1) * 8 + (lane & 7);
+    p.l = ty * VPT_TILE + (w >> 1) * 8 + (lane >> 3);
+    p.k = (ty * m.tiles_x + tx) * VPT_BLOCK + w * 64 + lane;
+    p.j = global_row(m, p.l);
+    p.valid = (p.i < m.W) && (p.l < m.local_h) && (p.j < m.H);
+    p.tile = tx < m.tiles_x;
+    return p;
+}
 
 struct LaoParams {               // = struct vpt_lao_params (include/vpt.h)
     int local_ambient_occlusion; float lao_weight; int num_lao_samples; float lao_step_size;
@@ -202,6 +217,26 @@ VPT_DEV LdsTables stage_lds(float4 *lds, const PassArgs &a) {
     r.tf = lds;
     r.tx = tab; r.ty = tab + a.vol.nx; r.tz = tab + (a.vol.nx + a.vol.ny);
     return r;
+}
+// The alpha column of the transfer function, one copy per WAVE (the MISS-tile kernels keep nothing of a sample but its alpha, and a wave that
+// stages its own copy meets no other wave at a barrier): tf_w pairs { tf[t].w, tf[min(t + 1, tf_w - 1)].w - tf[t].w } — the subtraction
+// stage_lds performs, so the pairs hold the same bits — in the wave's quarter of tf_w * 32 bytes of dynamic LDS.  Lane l takes the entries
+// l, l + 64, ...; every lane of the wave takes part, whether it has a pixel or not.  In three steps, so that a caller can put other loads
+// and arithmetic between them: tf_alpha_load issues the two loads of an entry, tf_alpha_store writes the pair, tf_alpha_fence orders the
+// wave's writes before its reads (wavefront scope: the LDS serves one wave's accesses in order, the fence only binds the compiler).
+struct TfAlpha { float w, n; };
+VPT_DEV float2 *tf_alpha_column(void *lds, int tf_w) { return (float2 *)lds + ((int)threadIdx.x >> 6) * tf_w; }
+VPT_DEV TfAlpha tf_alpha_load(const float4 *tf, int tf_w, int t) { return TfAlpha{ tf[t].w, tf[min(t + 1, tf_w - 1)].w }; }
+VPT_DEV void tf_alpha_store(float2 *col, int t, TfAlpha v) { col[t] = make_float2(v.w, v.n - v.w); }
+VPT_DEV void tf_alpha_fence() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+// the entries past the first 64 (a transfer function wider than a wave), loaded and written at once
+VPT_DEV void tf_alpha_stage_rest(float2 *col, const float4 *tf, int tf_w) {
+#pragma unroll 1
+    for (int t = ((int)threadIdx.x & 63) + 64; t < tf_w; t += 64) tf_alpha_store(col, t, tf_alpha_load(tf, tf_w, t));
 }
 // sampleVolumeColor: MIPRenderer.glsl:45-49 (= EAM :46-50, MCS :64-68, MCM :85-89)
 template <int V>

@@ -367,16 +367,28 @@ template <int V>
 __global__ void __launch_bounds__(VPT_BLOCK) k_probe_sample_boundary(PassArgs a, const float *xyz, float4 *out, size_t n) {
     extern __shared__ float4 lds_raw[];
     LdsTables t = stage_lds<(V & VPT_V_WIDE) != 0>(lds_raw, a);
+    // LINEAR one-channel byte volumes: through boundary_cell, the sampler of the plain class kernels — its face is chosen per WAVE (an axis
+    // out of range for every active lane), so which path a position takes depends on the 63 positions beside it (tests/test_gpu_miss_wave.py)
+    constexpr bool PLAIN = !(V & (VPT_V_NEAREST | VPT_V_RG | VPT_V_F32 | VPT_V_SNORM | VPT_V_QCUBIC | VPT_V_NORM16));
+    // ... and their alpha from the per-wave alpha column those kernels stage (tf_alpha_*), here behind the LDS image (vpt_core.hip probe_sample sizes the launch)
+    float2 *col = nullptr;
+    if (PLAIN) {
+        const int ntab = a.vol.nx + a.vol.ny + a.vol.nz;
+        col = tf_alpha_column((float2 *)lds_raw + 4 * a.tf_w + ((ntab + 1) >> 1), a.tf_w);
+        const int lane = (int)threadIdx.x & 63;
+        if (lane < a.tf_w) tf_alpha_store(col, lane, tf_alpha_load(a.tf, a.tf_w, lane));
+        tf_alpha_stage_rest(col, a.tf, a.tf_w);
+        tf_alpha_fence();
+    }
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const f3 q = { xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2] };
     const bool oob = (vmax(vmax(q.x, q.y), q.z) > 1.0f) || (vmin(vmin(q.x, q.y), q.z) < 0.0f);
     if (!oob) { out[i] = sample_volume_color<V>(a, t, q); return; }
-    // LINEAR one-channel byte volumes: through boundary_cell, the sampler of the plain class kernels — its face is chosen per WAVE (an axis
-    // out of range for every active lane), so which path a position takes depends on the 63 positions beside it (tests/test_gpu_miss_wave.py)
-    constexpr bool PLAIN = !(V & (VPT_V_NEAREST | VPT_V_RG | VPT_V_F32 | VPT_V_SNORM | VPT_V_QCUBIC | VPT_V_NORM16));
     const f2 rg = PLAIN ? f2{ sample_volume_boundary(a.vol, q), 0.0f } : sample_boundary_rg<V>(a.vol, q);
-    out[i] = (V & VPT_V_RG) ? sample_tf2d(a.tf, a.tf_w, a.tf_h, rg.x, rg.y) : sample_tf(t.tf, a.tf_fw, a.tf_hi, rg.x);
+    float4 c = (V & VPT_V_RG) ? sample_tf2d(a.tf, a.tf_w, a.tf_h, rg.x, rg.y) : sample_tf(t.tf, a.tf_fw, a.tf_hi, rg.x);
+    if (PLAIN) c.w = sample_tf_alpha(col, a.tf_fw, a.tf_hi, rg.x);
+    out[i] = c;
 }
 template <int V>
 __global__ void __launch_bounds__(VPT_BLOCK) k_probe_sample(PassArgs a, const float *xyz, float4 *out, size_t n) {

@@ -628,6 +628,11 @@ VPT_DEV void miss_sample_finish(const PassArgs &a, const float4 *tf, const MissL
     float4 vs = sample_tf(tf, a.tf_fw, a.tf_hi, boundary_blend(l.aw, l.fa, l.fb));
     asm volatile("" : "+v"(vs.w));
 }
+// ... with the transfer function as the wave's alpha column (k_mcm_miss, k_mcm_miss_settled): alpha is all that is kept alive
+VPT_DEV void miss_sample_finish(const PassArgs &a, const float2 *tf_alpha, const MissLoad &l) {
+    float w = sample_tf_alpha(tf_alpha, a.tf_fw, a.tf_hi, boundary_blend(l.aw, l.fa, l.fb));
+    asm volatile("" : "+v"(w));
+}
 // The same executed-and-discarded sample for the other volume formats (round 4): NEAREST filter, two channels (RG8 / RG32F: the G atlas 6 faces
 // behind the R atlas, the transfer function looked up in 2-D from HBM), float texels (one float4 per cell, no normalisation).  Same texels,
 // same order of operations as sample_volume_rg<V> at the clamped position: bit-identical (float texels: finite ones below 1e37 — the library
@@ -649,50 +654,53 @@ VPT_DEV uint32_t pass_seed(float px, float py, float seed) {
 }
 // LATE: the sample is consumed after the path end (under whose arithmetic its load flies) instead of right where the shader samples
 // DEPOSIT = false: the settled form (k_mcm_miss_settled) — every draw, position and sample as here, without the deposit
-template <int V, bool CHECK, bool LATE, bool DEPOSIT = true>
-VPT_DEV void mcm_events_miss(const PassArgs &a, const float4 *tf, Photon &ph, float px, float py, f3 from0, uint32_t state) {
+// TF: the staged float4 pairs (const float4 *: the bucket kernels and the other volume formats) or the wave's alpha column (const float2 *)
+template <int V, bool CHECK, bool LATE, bool DEPOSIT = true, typename TF>
+VPT_DEV void mcm_events_miss(const PassArgs &a, TF tf, Photon &ph, float px, float py, f3 from0, uint32_t state) {
     for (uint32_t s = 0u; s < a.steps; s++) {
         float dist = random_exponential(state, a.inv_extinction);
         ph.position = madd3(ph.position, dist, ph.direction);
         constexpr bool OTHER = (V & (VPT_V_NEAREST | VPT_V_RG | VPT_V_F32 | VPT_V_SNORM)) != 0;      // another volume format: the one-phase sample
         MissLoad l = { 0u, 0.0f, 0.0f };
-        if (OTHER) miss_sample_any<V>(a, tf, ph.position);
+        if constexpr (OTHER) miss_sample_any<V>(a, tf, ph.position);
         else l = miss_sample_issue<CHECK>(a, ph.position, a.violations);
-        if (!LATE && !OTHER) miss_sample_finish(a, tf, l);
+        if constexpr (!LATE && !OTHER) miss_sample_finish(a, tf, l);
         random_uniform(state);                                     // the wheel draw (its value decides nothing out of bounds)
         if (DEPOSIT) {
             float4 env = sample_environment(a.env, ph.direction);  // transmittance is (1, 1, 1): radiance = 1 * env, exactly env
             photon_deposit(ph, f3{ env.x, env.y, env.z });
         }
         reset_photon<true>(state, ph, px, py, a, from0);
-        if (LATE && !OTHER) miss_sample_finish(a, tf, l);
+        if constexpr (LATE && !OTHER) miss_sample_finish(a, tf, l);
     }
 }
-template <int V, bool CHECK, bool LATE, bool DEPOSIT = true>
-VPT_DEV void mcm_events_miss_fast(const PassArgs &a, const float4 *tf, const FastPixel &c, Photon &ph, float px, float py, uint32_t state) {
+template <int V, bool CHECK, bool LATE, bool DEPOSIT = true, typename TF>
+VPT_DEV void mcm_events_miss_fast(const PassArgs &a, TF tf, const FastPixel &c, Photon &ph, float px, float py, uint32_t state) {
     const float ld = fast_log2_scale(a.inv_extinction), ld32 = -32.0f * ld;
     for (uint32_t s = 0u; s < a.steps; s++) {
         float dist = fmaf(hw_log2(pcg_float(state)), ld, ld32);
         ph.position = madd3(ph.position, dist, ph.direction);
         constexpr bool OTHER = (V & (VPT_V_NEAREST | VPT_V_RG | VPT_V_F32 | VPT_V_SNORM)) != 0;
         MissLoad l = { 0u, 0.0f, 0.0f };
-        if (OTHER) miss_sample_any<V>(a, tf, ph.position);
+        if constexpr (OTHER) miss_sample_any<V>(a, tf, ph.position);
         else l = miss_sample_issue<CHECK>(a, ph.position, a.violations);
-        if (!LATE && !OTHER) miss_sample_finish(a, tf, l);
+        if constexpr (!LATE && !OTHER) miss_sample_finish(a, tf, l);
         state = pcg(state);                                        // the wheel draw
         f3 rad = { 0.0f, 0.0f, 0.0f };
         if (DEPOSIT) { float4 env = sample_environment(a.env, ph.direction); rad = f3{ env.x, env.y, env.z }; }
         fast_path_end<true, DEPOSIT>(a, c, state, ph, rad, px, py);
-        if (LATE && !OTHER) miss_sample_finish(a, tf, l);
+        if constexpr (LATE && !OTHER) miss_sample_finish(a, tf, l);
     }
 }
-// The prologue of a MISS-tile wave, in the order its round trips allow (profiles/experiments.md, "MISS wave prologue").  Nothing a pixel
+// The prologue of a MISS-tile wave of the OTHER volume formats (k_mcm_miss with miss_sample_any), in the order its round trips allow
+// (profiles/experiments.md, "MISS wave prologue").  Nothing a pixel
 // needs before its first event depends on the LDS image: the tile-list entry, then the state texels AND the two NDC table entries are
 // loaded together, the workgroup's first threads put the transfer function's loads behind them (stage_tf_fill), and the pixel constants,
 // the seed hash and the photon's start are computed from them BEFORE the workgroup's barrier — one trip to memory where the barrier,
 // then the two table loads (each waited for at once), then the arithmetic used to follow one another.  Behind the barrier a wave waits
 // for nothing it has not already received.  The NDC values still come from the host tables (their bits are the contract's); a lane
 // without a pixel (partial tiles) computes on zeros and leaves at the `!p.valid` return, which stays behind the barrier every wave must reach.
+// (The plain variants have a prologue without a barrier: miss_wave_start below.)
 struct MissPixel { FastPixel c; f3 from0; uint32_t state; };
 template <bool FAST>
 VPT_DEV MissPixel miss_pixel_start(const PassArgs &a, float px, float py, float4 s1, f3 s0, Photon &ph) {
@@ -716,8 +724,10 @@ VPT_DEV MissPixel miss_pixel_start(const PassArgs &a, float px, float py, float4
 #ifdef VPT_EVENT_TIMING
 // instrumented build: a MISS wave's life in three phases — prologue up to the first event, [0] the events, [6] epilogue — in the
 // per-wave slots of a buffer of the MISS kernels' own (PassArgs.violations of their launches in such a build; tools/miss_wave_life.py).
-// The prologue is the sum of [1] kernel arguments + tile-list entry (scalar loads), [2] the flight of the state / NDC table / transfer
-// function loads, [3] pixel constants, seed and photon start, [4] the wait at the workgroup's barrier, [5] what is left before the first event
+// The prologue of the plain variants (miss_wave_start) is the sum of [1] kernel arguments + tile-list entry (scalar loads), [2] the flight of
+// the NDC table entries (the alpha column's and the state's loads are in flight behind them), [3] pixel constants, seed and the column's LDS
+// writes, [4] what is left of the state texel's flight after that arithmetic (there is no workgroup barrier), [5] the photon's start and
+// what is left before the first event.  The other volume formats keep the earlier order: [2] all loads, [3] arithmetic, [4] the barrier.
 #define EV_MISS_MARK(evc, slot, WAIT) EV_MARK(evc, slot, WAIT)
 #define EV_MISS_PIN(x) asm volatile("" : "+v"(x))
 #define EV_MISS_BEGIN(evc, ph) do { EV_PIN3((ph).position); EV_MARK(evc, 5, "s_waitcnt vmcnt(0) lgkmcnt(0)"); } while (0)
@@ -730,11 +740,95 @@ VPT_DEV MissPixel miss_pixel_start(const PassArgs &a, float px, float py, float4
 #define EV_MISS_EVENTS(evc, ph) do { } while (0)
 #define EV_MISS_END(evc, a) do { } while (0)
 #endif
+// The prologue of a MISS-tile wave of the plain variants (LINEAR one-channel byte volumes; k_mcm_miss and k_mcm_miss_settled), without a
+// workgroup barrier and in the order its round trips allow (profiles/experiments.md, "MISS prologue without a barrier"):
+//   1. kernel arguments -> the tile-list entry (and the frame-table entry, if a table is passed: both addresses depend on arguments only);
+//      the mapping is map_listed_pixel; a wave none of whose lanes has a pixel (partial tiles) leaves here, before any vector load;
+//   2. the loads, shortest first: the two NDC table entries and the wave's share of the transfer function's alpha column (they hit the
+//      L2: every wave reads the same few hundred bytes), THEN the state texel(s), which come from beyond it.  Loads return in order, so
+//      the wait for the NDC values leaves the state outstanding;
+//   3. under the state's flight: the pixel constants (fast_pixel / unproject_near), the seed hash and the column's LDS writes — all the
+//      arithmetic that needs no direction;
+//   4. the first use of the direction: photon_start(_fast).
+// The order is pinned by compiler-only barriers between the groups of loads and by empty asm statements on the values (the second of
+// them takes the direction: the full vmcnt wait sits in front of it, behind the arithmetic).  The alpha column is the wave's own (tf_alpha_*,
+// vpt_kernels.h): written by all 64 lanes, valid or not, ordered by a wavefront-scope fence; no other wave is waited for.  The NDC values
+// still come from the host tables (their bits are the contract's); a lane without a pixel computes on zeros and leaves at the end.
+struct MissWave { Pix p; float px, py; const float2 *tf_alpha; MissPixel m; float4 s3; };
+template <bool FAST, bool RADIANCE>
+VPT_DEV bool miss_wave_start(PassArgs &a, void *lds, MissWave &w, Photon &ph EV_PARAM) {
+    // (the kernel arguments in ONE pinned batch of scalar loads was tried and lost: profiles/experiments.md, "MISS prologue without a barrier")
+    const int e = (int)blockIdx.x;
+    if (e >= a.pm.list_n) return false;
+    const uint32_t entry = a.pm.tile_list[e];
+    frame_select(a, 0);
+    w.p = map_listed_pixel(a.pm, entry);
+    const Pix &p = w.p;
+    if (__ballot(p.valid) == 0ull) return false;
+    EV_MISS_PIN(w.p.k); EV_MISS_MARK(evc, 1, "s_waitcnt lgkmcnt(0)");
+    float px = 0.0f, py = 0.0f;
+    if (p.valid) { px = ndc_col(a.pm, p.i); py = ndc_row(a.pm, p.j); }
+    const int lane = (int)threadIdx.x & 63, tf_w = a.tf_w;
+    float2 *const col = tf_alpha_column(lds, tf_w);
+    TfAlpha c0 = { 0.0f, 0.0f };
+    if (lane < tf_w) c0 = tf_alpha_load(a.tf, tf_w, lane);
+    asm volatile("" ::: "memory");                            // (the loads above are issued before the loads below)
+    float4 s1 = a.st1[p.k];
+    // (s0 is read only where it was loaded.  On the first classified pass — miss_load_pos set — the compiler still copies two of its
+    // registers inside the branch and waits vmcnt(0) there, in front of the arithmetic: that one pass per reset has no overlap)
+    f3 s0;
+    if (a.miss_load_pos) s0 = ((const f3 *)a.st0)[p.k];
+    w.s3 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (RADIANCE) w.s3 = a.st3[p.k];
+    asm volatile("" ::: "memory");
+    EV_MISS_PIN(px); EV_MISS_PIN(py); EV_MISS_MARK(evc, 2, "");
+    MissPixel &m = w.m;
+    if (FAST) m.c = fast_pixel(a, px, py);
+    else m.c.from0 = unproject_near(px, py, a);
+    m.state = pass_seed(px, py, a.seed);
+    if (lane < tf_w) tf_alpha_store(col, lane, c0);
+    // (pinned: this arithmetic and the column's writes stay in front of the wait for the direction)
+    if (FAST) asm volatile("" : "+v"(m.c.fb.x), "+v"(m.c.fb.y), "+v"(m.c.fb.z), "+v"(m.c.fb.w));
+    asm volatile("" : "+v"(m.c.from0.x), "+v"(m.c.from0.y), "+v"(m.c.from0.z), "+v"(m.state) : : "memory");
+    EV_MISS_MARK(evc, 3, "");
+    asm volatile("" : "+v"(s1.x), "+v"(s1.y), "+v"(s1.z), "+v"(m.c.from0.x), "+v"(m.c.from0.y), "+v"(m.c.from0.z), "+v"(m.state));
+    EV_MISS_MARK(evc, 4, "");
+    if (tf_w > 64) tf_alpha_stage_rest(col, a.tf, tf_w);     // (a transfer function wider than a wave: the further rounds, not overlapped)
+    tf_alpha_fence();
+    m.from0 = m.c.from0;
+    ph.direction = f3{ s1.x, s1.y, s1.z };
+    ph.bounces = 0u;
+    ph.transmittance = f3{ 1.0f, 1.0f, 1.0f };
+    if (FAST) ph.position = a.miss_load_pos ? s0 : photon_start_fast(m.from0, ph.direction);
+    else ph.position = a.miss_load_pos ? s0 : photon_start(m.from0, ph.direction);
+    w.px = px; w.py = py; w.tf_alpha = col;
+    return p.valid;
+}
 // (8 waves per SIMD = 64 VGPRs; the contract arithmetic of the other volume formats needs two more: 7 waves there instead of a spill)
 template <bool FUSE_RENDER, int V, bool CHECK, bool LATE>
 __global__ void __launch_bounds__(VPT_BLOCK)
 __attribute__((amdgpu_waves_per_eu(((V & (VPT_V_NEAREST | VPT_V_RG | VPT_V_F32 | VPT_V_SNORM)) && !(V & VPT_V_FAST)) ? 7 : 8, 8))) k_mcm_miss(PassArgs a) {
     EV_LOCAL
+    if constexpr (!(V & (VPT_V_NEAREST | VPT_V_RG | VPT_V_F32 | VPT_V_SNORM))) {
+        // the plain variants: no workgroup barrier (miss_wave_start)
+        extern __shared__ float4 lds_raw[];
+        MissWave w;
+        Photon ph;
+        if (!miss_wave_start<(V & VPT_V_FAST) != 0, true>(a, lds_raw, w, ph EV_ARG)) return;
+        const Pix &p = w.p;
+        ph.radiance = f3{ w.s3.x, w.s3.y, w.s3.z };
+        ph.samples = (uint32_t)(w.s3.w + 0.5f);
+        EV_MISS_BEGIN(evc, ph);
+        if (V & VPT_V_FAST) mcm_events_miss_fast<V & ~VPT_V_FAST, CHECK, LATE>(a, w.tf_alpha, w.m.c, ph, w.px, w.py, w.m.state);
+        else mcm_events_miss<V, CHECK, LATE>(a, w.tf_alpha, ph, w.px, w.py, w.m.from0, w.m.state);
+        EV_MISS_EVENTS(evc, ph);
+        a.st1[p.k] = make_float4(ph.direction.x, ph.direction.y, ph.direction.z, 0.0f);
+        a.st3[p.k] = make_float4(ph.radiance.x, ph.radiance.y, ph.radiance.z, (float)ph.samples);
+        if (FUSE_RENDER) store_frame(a, p, pack_half4(ph.radiance.x, ph.radiance.y, ph.radiance.z, 1.0f));
+        EV_MISS_END(evc, a);
+        return;
+    }
+    // the other volume formats: the staged table behind the workgroup's barrier, as before
     frame_select(a, 0);
     Pix p = map_pixel(a.pm);
     EV_MISS_PIN(p.k); EV_MISS_MARK(evc, 1, "s_waitcnt lgkmcnt(0)");
@@ -777,33 +871,17 @@ __attribute__((amdgpu_waves_per_eu(((V & (VPT_V_NEAREST | VPT_V_RG | VPT_V_F32 |
 template <int V, bool CHECK, bool LATE>
 __global__ void __launch_bounds__(VPT_BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) k_mcm_miss_settled(PassArgs a) {
     EV_LOCAL
-    frame_select(a, 0);
-    Pix p = map_pixel(a.pm);
-    EV_MISS_PIN(p.k); EV_MISS_MARK(evc, 1, "s_waitcnt lgkmcnt(0)");
-    float4 s1 = make_float4(0.0f, 0.0f, 1.0f, 0.0f);
-    f3 s0 = { 0.0f, 0.0f, 0.0f };
-    float px = 0.0f, py = 0.0f;
-    if (p.tile) {
-        s1 = a.st1[p.k];
-        if (a.miss_load_pos) s0 = ((const f3 *)a.st0)[p.k];
-    }
-    if (p.valid) { px = ndc_col(a.pm, p.i); py = ndc_row(a.pm, p.j); }
     extern __shared__ float4 lds_raw[];
-    const float4 *tf = stage_tf_fill(lds_raw, a);
-    EV_MISS_MARK(evc, 2, "s_waitcnt vmcnt(0)");
+    MissWave w;
     Photon ph;
-    const MissPixel m = miss_pixel_start<(V & VPT_V_FAST) != 0>(a, px, py, s1, s0, ph);
-    EV_MISS_MARK(evc, 3, "");
-    __syncthreads();
-    EV_MISS_MARK(evc, 4, "");
-    if (!p.valid) return;
+    if (!miss_wave_start<(V & VPT_V_FAST) != 0, false>(a, lds_raw, w, ph EV_ARG)) return;
     ph.radiance = f3{ 0.0f, 0.0f, 0.0f };
     ph.samples = 0u;
     EV_MISS_BEGIN(evc, ph);
-    if (V & VPT_V_FAST) mcm_events_miss_fast<V & ~VPT_V_FAST, CHECK, LATE, false>(a, tf, m.c, ph, px, py, m.state);
-    else mcm_events_miss<V, CHECK, LATE, false>(a, tf, ph, px, py, m.from0, m.state);
+    if (V & VPT_V_FAST) mcm_events_miss_fast<V & ~VPT_V_FAST, CHECK, LATE, false>(a, w.tf_alpha, w.m.c, ph, w.px, w.py, w.m.state);
+    else mcm_events_miss<V, CHECK, LATE, false>(a, w.tf_alpha, ph, w.px, w.py, w.m.from0, w.m.state);
     EV_MISS_EVENTS(evc, ph);
-    a.st1[p.k] = make_float4(ph.direction.x, ph.direction.y, ph.direction.z, 0.0f);
+    a.st1[w.p.k] = make_float4(ph.direction.x, ph.direction.y, ph.direction.z, 0.0f);
     EV_MISS_END(evc, a);
 }
 // brings the position / transmittance arrays of the MISS tiles up to date: position = photon_start(from0, direction) in the
