@@ -499,6 +499,55 @@ VPT_API int vpt_volume_geodesic_timed(vpt_volume *src, int channel, int op, uint
 VPT_API int vpt_volume_reconstruct_capped(vpt_volume *marker, int marker_channel, vpt_volume *mask, int mask_channel, int op, int connectivity,
                                           int tile_rounds, vpt_volume **out, double *ms, uint32_t *launches);
 
+/* ---- watershed by steepest descent on a lower-completed relief on the device (extension; DESIGN.md "Watershed") */
+/* The step behind the seeds: the regional maxima of a depth channel tell two touching structures apart, the watershed splits them.  The
+ * result is an ordinary vpt_components handle whose components are the basins: info, list, ranks, keep, label, measure, keep_set and
+ * destroy work on it unchanged.  Most watershed definitions depend on the order of flooding; here every step is a pure function of the
+ * input, so no output depends on the order the device works in.
+ *   Sources: `relief` is R8, RG8, R16 or RG16 with a `channel` argument read as vpt_volume_reconstruct reads one (0, or 1 of a two-channel
+ *   volume; anything else VPT_ERR_INVALID); every other format: VPT_ERR_UNSUPPORTED, naming it.  M = 255 / 65535.  All compares are
+ *   unsigned on whole codes.  Nothing wraps and nothing is clamped: a neighbour outside the volume does not exist.  Connectivity c: 6, 18
+ *   or 26; anything else VPT_ERR_INVALID.  Volumes of more than 2^32 - 2 voxels: VPT_ERR_UNSUPPORTED, as for the components.
+ *   Domain: D = { v : lo <= relief(v) <= hi }; lo > hi or hi > M: VPT_ERR_INVALID.  Only voxels of D are flooded and only voxels of D count
+ *   as neighbours; everything else has rank 0.
+ *   Polarity: VPT_WATERSHED_MINIMA floods from the minima, k(v) = relief(v); VPT_WATERSHED_MAXIMA from the maxima, k(v) = M - relief(v):
+ *   the form for a depth channel.  Anything else: VPT_ERR_INVALID.
+ *   Lower completion: d(v) = 0 if v has a c-neighbour u in D with k(u) < k(v); otherwise d(v) = 1 + min of d(u) over the c-neighbours u
+ *   in D with k(u) = k(v); d(v) = infinity when no such chain reaches a voxel with d = 0.  So d is the geodesic step count, inside the
+ *   level set, to the plateau's lower border, and the voxels with d = infinity are exactly the regional minima of k within D.  Two adjacent
+ *   minimum voxels always have equal k.
+ *   Descent: each voxel that is no minimum has one pointer p(v).  d(v) = 0: among the c-neighbours u in D with k(u) < k(v) the one of
+ *   smallest k(u), then of smallest linear index (z ny + y) nx + x.  0 < d(v) < infinity: among the c-neighbours u in D with k(u) = k(v)
+ *   and d(u) = d(v) - 1 the one of smallest linear index.  (k, d) falls lexicographically along p, so every walk ends on a minimum voxel.
+ *   Basins: the connected components of the graph on D with the edges {v, p(v)}, and {u, v} for c-adjacent minimum voxels: a regional
+ *   minimum together with every voxel whose walk ends in it.  There are no watershed-line voxels: every voxel of D belongs to exactly one
+ *   basin.  Canonical order as vpt_volume_components: a basin's root is its smallest linear index; basins of fewer than `min_voxels` voxels
+ *   (0: VPT_ERR_INVALID) are dropped, with rank 0; the others are ranked by voxel count descending, then by root ascending.
+ *   info.foreground_voxels is |D|.
+ *   The handle's texel snapshot (what keep, keep_set and label emit, and what measure reads without `values`): `texels` null: the chosen
+ *   channel of the relief as a one-channel R8 / R16 snapshot.  Otherwise an R8 / R16 volume (any other format: VPT_ERR_UNSUPPORTED) of
+ *   the relief's context, size and channel width (a mismatch: VPT_ERR_INVALID, naming both), whose filter the emitted volumes then carry:
+ *   the emitters speak of the original volume, not of its depth.
+ * vpt_amd.watershed_texels states the contract in numpy.  The calls block; the sources are not changed, need not be finalized and may be
+ * destroyed afterwards.  Two runs give identical bytes. */
+#define VPT_WATERSHED_MINIMA 0
+#define VPT_WATERSHED_MAXIMA 1
+VPT_API int vpt_volume_watershed(vpt_volume *relief, int channel, vpt_volume *texels, uint32_t lo, uint32_t hi, int polarity, int connectivity,
+                                 uint32_t min_voxels, vpt_components **out);
+/* (for measurements) the same, and ms[VPT_WATERSHED_PHASES]: the milliseconds of classify, the plateau launches and the links inside the
+ * tiles (together they are phase 0 of vpt_components_profile, which has the common tail: merge, flatten, sizes, ...); *plateau_launches:
+ * the launches of the plateau kernel.  Neither pointer may be null. */
+#define VPT_WATERSHED_PHASES 3
+VPT_API int vpt_volume_watershed_timed(vpt_volume *relief, int channel, vpt_volume *texels, uint32_t lo, uint32_t hi, int polarity, int connectivity,
+                                       uint32_t min_voxels, vpt_components **out, double *ms, uint32_t *plateau_launches);
+/* (for tests) vpt_volume_watershed with the caps given: merge_steps and flatten_steps as vpt_volume_components_capped, tile_rounds as
+ * vpt_volume_reconstruct_capped (the rounds a tile of the plateau kernel may make in LDS per launch).  Caps below those siblings' minima
+ * (3, 1, 1) are VPT_ERR_INVALID before any other check.  The result is the contract's whatever the caps; ms and plateau_launches as
+ * above, either may be null. */
+VPT_API int vpt_volume_watershed_capped(vpt_volume *relief, int channel, vpt_volume *texels, uint32_t lo, uint32_t hi, int polarity, int connectivity,
+                                        uint32_t min_voxels, int merge_steps, int flatten_steps, int tile_rounds, vpt_components **out, double *ms,
+                                        uint32_t *plateau_launches);
+
 /* ---- renderer: AbstractRenderer.js:17-116 and the four subclasses */
 /* new R(gl, volume, camera, environmentTexture, {resolution}) — AbstractRenderer.js:17-49; width != height is the
  * documented extension (uInverseResolution = (1/W, 1/H)).  Buffers are allocated as in _rebuildBuffers :78-92. */

@@ -364,6 +364,39 @@ static napi_value VolumeComponents(napi_env env, napi_callback_info info) {
     VPT_CHECK(vpt_volume_components(v, lo, hi, connectivity, min_voxels, &out));
     return make_external(env, out);
 }
+// the eight arguments volumeWatershed and volumeWatershedTimed share: (relief, channel, texels | null, lo, hi, polarity, connectivity, minVoxels)
+struct WatershedArgs { vpt_volume *relief, *texels; int32_t channel, polarity, connectivity; uint32_t lo, hi, min_voxels; };
+static bool get_watershed(napi_env env, const napi_value *a, WatershedArgs *w) {
+    return get_handle(env, a[0], &w->relief) && get_i32(env, a[1], &w->channel) && get_handle(env, a[2], &w->texels, true) && get_u32(env, a[3], &w->lo) &&
+           get_u32(env, a[4], &w->hi) && get_i32(env, a[5], &w->polarity) && get_i32(env, a[6], &w->connectivity) && get_u32(env, a[7], &w->min_voxels);
+}
+// volumeWatershed(relief, channel, texels | null, lo, hi, polarity, connectivity, minVoxels) -> a components handle: the basins (VPT_WATERSHED_*)
+static napi_value VolumeWatershed(napi_env env, napi_callback_info info) {
+    napi_value a[8]; WatershedArgs w;
+    if (!get_args(env, info, 8, a) || !get_watershed(env, a, &w)) return nullptr;
+    vpt_components *out = nullptr;
+    VPT_CHECK(vpt_volume_watershed(w.relief, w.channel, w.texels, w.lo, w.hi, w.polarity, w.connectivity, w.min_voxels, &out));
+    return make_external(env, out);
+}
+// volumeWatershedTimed(the same, mergeSteps, flattenSteps, tileRounds) -> [handle, ms classify, ms plateau, ms links, plateau launches]; the
+// three caps 0: the library's own, otherwise vpt_volume_watershed_capped
+static napi_value VolumeWatershedTimed(napi_env env, napi_callback_info info) {
+    napi_value a[11]; WatershedArgs w; int32_t merge_steps, flatten_steps, tile_rounds;
+    if (!get_args(env, info, 11, a) || !get_watershed(env, a, &w) || !get_i32(env, a[8], &merge_steps) || !get_i32(env, a[9], &flatten_steps) ||
+        !get_i32(env, a[10], &tile_rounds)) return nullptr;
+    vpt_components *out = nullptr; double ms[VPT_WATERSHED_PHASES] = {}; uint32_t launches = 0;
+    if (merge_steps == 0 && flatten_steps == 0 && tile_rounds == 0)
+        VPT_CHECK(vpt_volume_watershed_timed(w.relief, w.channel, w.texels, w.lo, w.hi, w.polarity, w.connectivity, w.min_voxels, &out, ms, &launches));
+    else
+        VPT_CHECK(vpt_volume_watershed_capped(w.relief, w.channel, w.texels, w.lo, w.hi, w.polarity, w.connectivity, w.min_voxels, merge_steps, flatten_steps,
+                                              tile_rounds, &out, ms, &launches));
+    napi_value r, e;
+    napi_create_array_with_length(env, 2 + VPT_WATERSHED_PHASES, &r);
+    napi_set_element(env, r, 0, make_external(env, out));
+    for (int k = 0; k < VPT_WATERSHED_PHASES; k++) { napi_create_double(env, ms[k], &e); napi_set_element(env, r, 1 + k, e); }
+    napi_create_double(env, (double)launches, &e); napi_set_element(env, r, 1 + VPT_WATERSHED_PHASES, e);
+    return r;
+}
 // componentsInfo(components) -> [listed, dropped, foregroundVoxels, listedVoxels]
 static napi_value ComponentsInfo(napi_env env, napi_callback_info info) {
     napi_value a[1]; vpt_components *c;
@@ -817,6 +850,7 @@ static napi_value Init(napi_env env, napi_value exports) {
     EXPORT("volumeCombine", VolumeCombine); EXPORT("volumeCombineTimed", VolumeCombineTimed); EXPORT("volumeCompare", VolumeCompare);
     EXPORT("volumeReconstruct", VolumeReconstruct); EXPORT("volumeReconstructTimed", VolumeReconstructTimed);
     EXPORT("volumeGeodesic", VolumeGeodesic); EXPORT("volumeGeodesicTimed", VolumeGeodesicTimed);
+    EXPORT("volumeWatershed", VolumeWatershed); EXPORT("volumeWatershedTimed", VolumeWatershedTimed);
     EXPORT("volumeComponents", VolumeComponents); EXPORT("componentsInfo", ComponentsInfo); EXPORT("componentsList", ComponentsList);
     EXPORT("componentsRanks", ComponentsRanks); EXPORT("componentsKeep", ComponentsKeep); EXPORT("componentsLabel", ComponentsLabel);
     EXPORT("componentsMeasure", ComponentsMeasure); EXPORT("componentsMeasureTimed", ComponentsMeasureTimed); EXPORT("componentsKeepSet", ComponentsKeepSet);

@@ -31,6 +31,10 @@
 //   geodesic: null (default) or { op: 'fill_holes' | 'clear_border' | 'hmax' | 'hmin' | 'dome' | 'maxima' | 'minima', h: 0, connectivity: 6 }: an
 //   R8 / R16 volume gets that geodesic operation (Volume.geodesic) behind the rank filter and in front of `components` mode 'keep' and the
 //   smoothing
+//   split: null (default) or { lo, hi, h: 2, steps: 4, connectivity: 26, minVoxels: 1 }: the structures of the codes lo .. hi of an R8 / R16
+//   volume with touching ones split by the watershed of their depth (Volume.split).  It runs where the gradient runs, on the final scalar
+//   volume: the second channel is min(rank of the basin, M), so it cannot be combined with `gradient`, `components` mode 'label', `distance`
+//   mode 'channel' or `combine` op 'pair'
 const { EventTarget, CustomEvent } = require('./EventTarget.js');
 const { Context } = require('./Context.js');
 const { OrbitCameraAnimator } = require('./animators.js');
@@ -42,6 +46,7 @@ const { checkSeeds, checkSteps, checkWithin, checkDistanceRange } = require('./d
 const { checkResampleMode, checkResampleSize, checkSpacing } = require('./resample.js');
 const { checkCombineOp, checkCombineChannel, checkCombineWeights, checkCombineMask } = require('./combine.js');
 const { checkGeodesicH } = require('./reconstruct.js');
+const { checkSplit } = require('./watershed.js');
 const { RendererFactory } = require('./renderers/RendererFactory.js');
 const { ToneMapperFactory } = require('./tonemappers/ToneMapperFactory.js');
 
@@ -88,6 +93,17 @@ constructor(options) {
         }
     }
     this.geodesic = RenderingContext._geodesicSpec(options.geodesic);                // likewise
+    this.split = checkSplit(options.split);                                          // likewise
+    if (this.split !== null) {
+        if (this.gradient !== null) { throw new Error('split and gradient both write the second channel: name one of them'); }
+        if (this.components !== null && this.components.mode === 'label') {
+            throw new Error("split and components mode 'label' both write the second channel: name one of them");
+        }
+        if (this.distance !== null && this.distance.mode === 'channel') {
+            throw new Error("split and distance mode 'channel' both write the second channel: name one of them");
+        }
+        if (this.combine !== null && this.combine.op === 'pair') { throw new Error("split and combine op 'pair' both write the second channel: name one of them"); }
+    }
     this.gl = new Context(options.device || 0);                                   // initGL(), :61-105
     this.environmentTexture = { data: new Uint8Array([255, 255, 255, 255]), width: 1, height: 1 };   // :90-101
     this._rng = options.rng;
@@ -190,6 +206,16 @@ async setVolume(reader) {                                                       
         if (this.components !== null && this.components.mode === 'label') { this._derive(found => found.label()); }   // (value, rank)
         if (this.distance !== null && this.distance.mode === 'channel') { this._deriveDistance(found => found.channel(this.distance.steps)); }   // (value, distance)
         if (this.combine !== null && this.combine.op === 'pair') { await this._combineWith(this.combine); }                    // (value, the second volume)
+        if (this.split !== null) {
+            const N = native(), fmt = this.volume.nativeFormat();
+            if (fmt === N.VPT_FORMAT_R8 || fmt === N.VPT_FORMAT_R16) {                 // (value, basin): any other volume as it is
+                const source = this.volume, spec = this.split, largest = fmt === N.VPT_FORMAT_R16 ? 65535 : 255;      // hi and h are open above
+                const found = source.split(spec.lo, Math.min(spec.hi, largest),
+                    { h: Math.min(spec.h, largest), steps: spec.steps, connectivity: spec.connectivity, minVoxels: spec.minVoxels });
+                try { this.volume = found.label(); } finally { found.destroy(); }
+                source.destroy();
+            }
+        }
     } catch (e) {                                                                      // the context keeps the volume it had
         this.volume.destroy();
         this.volume = old;

@@ -10,6 +10,7 @@ const { checkSeeds, checkSteps, checkRadius, checkWithin, checkDistanceRange } =
 const { checkResampleMode, checkResampleSize, isotropicShape } = require('./resample.js');
 const { COMBINE_STATS, checkCombineOp, checkCombineChannel, checkCombineWeights, checkCombineMask, checkCompareRange, compareRatios } = require('./combine.js');
 const { checkReconstructOp, checkGeodesicOp, checkGeodesicH, checkSourceChannel } = require('./reconstruct.js');
+const { checkPolarity } = require('./watershed.js');
 const { RAWReader, GL_RED, GL_RG, GL_RGB, GL_RGBA, GL_UNSIGNED_BYTE, GL_FLOAT, GL_HALF_FLOAT, GL_BYTE } = R;
 
 // [type, format, internalFormat, native format name, channels in the file, element kind] of the formats keyed on all three: SNORM bytes
@@ -499,6 +500,72 @@ regionalMaxima(connectivity, channel) { return this.geodesic('maxima', 0, connec
 regionalMaximaTimed(connectivity, channel) { return this.geodesicTimed('maxima', 0, connectivity, channel); }
 regionalMinima(connectivity, channel) { return this.geodesic('minima', 0, connectivity, channel); }
 regionalMinimaTimed(connectivity, channel) { return this.geodesicTimed('minima', 0, connectivity, channel); }
+
+// ---- extension: watershed by steepest descent on a lower-completed relief (include/vpt.h; DESIGN.md "Watershed") ----
+// the arguments of native().volumeWatershed behind watershed(lo, hi, options), and the volume the handle speaks of
+_watershedArguments(lo, hi, options, timed) {
+    options = options || {};
+    const N = native();
+    if (!this.texture) { throw new Error('a watershed takes a ready volume'); }
+    const known = ['polarity', 'connectivity', 'minVoxels', 'channel', 'texels'].concat(timed ? ['caps'] : []);      // caps: the timed form's, for tests
+    const unknown = Object.keys(options).filter(k => known.indexOf(k) < 0);
+    if (unknown.length) { throw new Error('watershed takes polarity, connectivity, minVoxels, channel and texels, not ' + unknown.sort().join(', ')); }
+    const layout = texelLayout(N, this.modality), norm16 = layout.array.BYTES_PER_ELEMENT === 2;
+    const channel = checkSourceChannel(options.channel !== undefined ? options.channel : 0, layout.channels);
+    checkRange(lo, hi, norm16 ? 65535 : 255);
+    const polarity = checkPolarity(options.polarity !== undefined ? options.polarity : 'minima');
+    const connectivity = checkConnectivity(options.connectivity !== undefined ? options.connectivity : 6);
+    const minVoxels = checkMinVoxels(options.minVoxels !== undefined ? options.minVoxels : 1);
+    const texels = options.texels !== undefined ? options.texels : null;
+    if (texels !== null && (!(texels instanceof Volume) || !texels.texture)) { throw new Error('watershed takes a ready volume as texels'); }
+    // the handle speaks of the volume whose texels it holds: `texels`, or the chosen channel of this one
+    let source = texels !== null ? texels : this;
+    if (texels === null && layout.channels === 2) {
+        const modality = Object.assign({}, this.modality, { format: GL_RED, internalFormat: norm16 ? R.GL_R16_EXT : R.GL_R8,
+            type: norm16 ? R.GL_UNSIGNED_SHORT : GL_UNSIGNED_BYTE });
+        source = { _gl: this._gl, modality, metadata: this.metadata, nativeFormat: () => (norm16 ? N.VPT_FORMAT_R16 : N.VPT_FORMAT_R8) };
+    }
+    return { source, args: [this.texture, channel, texels !== null ? texels.texture : null, lo, hi, polarity, connectivity, minVoxels] };
+}
+// the basins of channel options.channel (0) of this (R8, RG8, R16 or RG16) volume, the relief, over the domain of the codes lo .. hi, as a
+// Components object: the watershed by steepest descent on the lower completion, flooded from the options.polarity 'minima' (default) or
+// 'maxima' (a depth channel), with options.connectivity 6 (default), 18 or 26, basins smaller than options.minVoxels (1) dropped, on the
+// device (js/vpt/watershed.js states the contract).  options.texels (an R8 / R16 volume of this size and channel width; default: the relief's
+// channel) is what keep, keepSet and label emit.  Neither volume is changed; both may be destroyed
+watershed(lo, hi, options) {
+    const w = this._watershedArguments(lo, hi, options, false);
+    return new Components(w.source, native().volumeWatershed.apply(null, w.args));
+}
+// (for measurements) [the basins watershed() gives, { ms: { classify, plateau, links }, plateauLaunches }]; the common tail is the basins'
+// profile().  options.caps (for tests): [mergeSteps, flattenSteps, tileRounds] of vpt_volume_watershed_capped
+watershedTimed(lo, hi, options) {
+    const w = this._watershedArguments(lo, hi, options, true), caps = options && options.caps !== undefined ? options.caps : [0, 0, 0];
+    if (!Array.isArray(caps) || caps.length !== 3 || !caps.every(Number.isInteger)) { throw new Error('caps are [mergeSteps, flattenSteps, tileRounds]'); }
+    const r = native().volumeWatershedTimed.apply(null, w.args.concat(caps));
+    return [new Components(w.source, r[0]), { ms: { classify: r[1], plateau: r[2], links: r[3] }, plateauLaunches: r[4] }];
+}
+_split(lo, hi, options, timed) {
+    options = options || {};
+    const unknown = Object.keys(options).filter(k => ['h', 'steps', 'connectivity', 'minVoxels'].indexOf(k) < 0);
+    if (unknown.length) { throw new Error('split takes h, steps, connectivity and minVoxels, not ' + unknown.sort().join(', ')); }
+    const norm16 = this.nativeFormat() === native().VPT_FORMAT_R16;
+    const h = options.h !== undefined ? options.h : 2, steps = options.steps !== undefined ? options.steps : 4;
+    const connectivity = options.connectivity !== undefined ? options.connectivity : 26;
+    const d = this.distance(lo, hi, 'rest');
+    let depth, flattened;
+    try { depth = d.channel(steps); } finally { d.destroy(); }
+    try { flattened = depth.hmax(h, connectivity, 1); } finally { depth.destroy(); }
+    try {
+        const w = { polarity: 'maxima', connectivity, minVoxels: options.minVoxels !== undefined ? options.minVoxels : 1, texels: this };
+        return timed ? flattened.watershedTimed(1, norm16 ? 65535 : 255, w) : flattened.watershed(1, norm16 ? 65535 : 255, w);
+    } finally { flattened.destroy(); }
+}
+// the structures of the codes lo .. hi of this (R8 / R16) volume with touching ones split, as a Components object whose emitters speak of
+// this volume: distance(lo, hi, 'rest') -> channel(steps) -> hmax(h, connectivity, 1) -> watershed(1, M, { polarity: 'maxima', connectivity,
+// minVoxels, texels: this }), all on the device; options = { h: 2, steps: 4, connectivity: 26, minVoxels: 1 }.  The intermediates are destroyed
+split(lo, hi, options) { return this._split(lo, hi, options, false); }
+// (for measurements) [the basins split() gives, what watershedTimed() reports of its watershed step]
+splitTimed(lo, hi, options) { return this._split(lo, hi, options, true); }
 
 // ---- extension: connected components of a value range (include/vpt.h; DESIGN.md "Connected components") ----
 // the connected components of the codes lo .. hi of this (R8 / R16) volume as a Components object, labelled on the device: connectivity 6

@@ -28,6 +28,7 @@ from .distance import distance_squared_texels, within_texels, channel_texels, ch
 from .resample import resample_texels, isotropic_shape, axis_taps, nearest_index, count_ties, check_mode, check_size, check_spacing
 from .combine import combine_texels, compare_stats, OPS, check_op, check_weights, check_channel
 from .reconstruct import reconstruct_texels, geodesic_texels, RECONSTRUCT_OPS, GEODESIC_OPS
+from .watershed import watershed_texels, descent_texels, split_texels, POLARITIES, check_polarity, check_split
 from ._native import VptError
 
 __all__ = [
@@ -45,4 +46,5 @@ __all__ = [
     'resample_texels', 'isotropic_shape', 'axis_taps', 'nearest_index', 'count_ties', 'check_mode', 'check_size', 'check_spacing',
     'combine_texels', 'compare_stats', 'OPS', 'check_op', 'check_weights', 'check_channel',
     'reconstruct_texels', 'geodesic_texels', 'RECONSTRUCT_OPS', 'GEODESIC_OPS',
+    'watershed_texels', 'descent_texels', 'split_texels', 'POLARITIES', 'check_polarity', 'check_split',
 ]

@@ -59,6 +59,7 @@ SYMBOLS = [
     "vpt_volume_resample", "vpt_volume_resample_timed",
     "vpt_volume_combine", "vpt_volume_combine_timed", "vpt_volume_compare",
     "vpt_volume_reconstruct", "vpt_volume_geodesic", "vpt_volume_reconstruct_timed", "vpt_volume_geodesic_timed", "vpt_volume_reconstruct_capped",
+    "vpt_volume_watershed", "vpt_volume_watershed_timed", "vpt_volume_watershed_capped",
     "vpt_renderer_create", "vpt_renderer_set_shard", "vpt_renderer_local_rows", "vpt_renderer_global_row",
     "vpt_renderer_destroy", "vpt_renderer_set_volume", "vpt_renderer_set_transfer_function",
     "vpt_renderer_set_environment", "vpt_renderer_set_environment_texels", "vpt_renderer_resize",
@@ -134,6 +135,8 @@ RESAMPLE_PHASES = 2
 COMBINE_MASK, COMBINE_MIN, COMBINE_MAX, COMBINE_ABSDIFF, COMBINE_BLEND, COMBINE_PAIR = 0, 1, 2, 3, 4, 5
 RECONSTRUCT_DILATION, RECONSTRUCT_EROSION = 0, 1
 (GEODESIC_FILL_HOLES, GEODESIC_CLEAR_BORDER, GEODESIC_HMAX, GEODESIC_HMIN, GEODESIC_DOME, GEODESIC_MAXIMA, GEODESIC_MINIMA) = range(7)
+WATERSHED_MINIMA, WATERSHED_MAXIMA = 0, 1
+WATERSHED_PHASES = 3
 
 
 class CombineParams(C.Structure):
@@ -226,6 +229,9 @@ def lib():
         "vpt_volume_reconstruct_timed": [P, I, P, I, I, I, PP, C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)],
         "vpt_volume_geodesic_timed": [P, I, I, C.c_uint32, I, PP, C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)],
         "vpt_volume_reconstruct_capped": [P, I, P, I, I, I, I, PP, C.POINTER(C.c_double), C.POINTER(C.c_uint32)],
+        "vpt_volume_watershed": [P, I, P, C.c_uint32, C.c_uint32, I, I, C.c_uint32, PP],
+        "vpt_volume_watershed_timed": [P, I, P, C.c_uint32, C.c_uint32, I, I, C.c_uint32, PP, C.POINTER(C.c_double), C.POINTER(C.c_uint32)],
+        "vpt_volume_watershed_capped": [P, I, P, C.c_uint32, C.c_uint32, I, I, C.c_uint32, I, I, I, PP, C.POINTER(C.c_double), C.POINTER(C.c_uint32)],
         "vpt_renderer_create": [P, I, I, I, PP],
         "vpt_renderer_set_shard": [P, I, I, I], "vpt_renderer_local_rows": [P, C.POINTER(I)],
         "vpt_renderer_global_row": [P, I, C.POINTER(I)],

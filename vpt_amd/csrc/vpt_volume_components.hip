@@ -17,31 +17,8 @@
 // follows label -> label of the voxel it names twice (pointer jumping); a voxel's label is written by its owner only, and a value read
 // while a neighbour's owner writes is the old or the new label, both labels of the same component.  A round without a change leaves every
 // component with its smallest voxel's index.  Each changing round lowers a label, and a label moves at least one voxel per round along a
-// shortest path, so CC_VOX rounds always suffice: that is the loop's bound.
-#define CC_TX 64
-#define CC_TY 8
-#define CC_TZ 4
-#define CC_VOX (CC_TX * CC_TY * CC_TZ)
-#define CC_PX (CC_TX + 2)
-#define CC_PY (CC_TY + 2)
-#define CC_PZ (CC_TZ + 2)
-#define CC_PAD (CC_PX * CC_PY * CC_PZ)
-#define CC_BG 0xFFFFu
-static_assert(CC_VOX == 2048 && CC_PAD < 0xFFFF, "eight voxels a thread; LDS indices fit 16 bits");
-
-// words of the control block on the device
-enum { W_CHANGED = 0, W_TILE_ROOTS = 1, W_SLOT = 2, W_WORDS = 4 };
-enum { Q_LISTED = 0, Q_DROPPED = 1, Q_FOREGROUND = 2, Q_LISTED_VOXELS = 3, Q_WORDS = 4 };
-
-__device__ __forceinline__ uint32_t ld_agent(const uint32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void st_agent(uint32_t *p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// is the offset (dx, dy, dz) != 0 a neighbour under CONN?
-template <int CONN> __device__ __forceinline__ constexpr bool is_neighbour(int dx, int dy, int dz) {
-    const int m = (dx != 0) + (dy != 0) + (dz != 0);
-    return m >= 1 && m <= (CONN == 6 ? 1 : CONN == 18 ? 2 : 3);
-}
-
+// shortest path, so CC_VOX rounds always suffice: that is the loop's bound.  (The tile's geometry, the control words and is_neighbour:
+// vpt_volume_components.h, shared with the watershed's tile passes.)
 template <typename T, int CONN>
 __global__ __launch_bounds__(256) void k_label_tiles(const T *__restrict__ src, uint32_t *__restrict__ L, int nx, int ny, int nz, uint32_t lo, uint32_t hi,
                                                     uint32_t *__restrict__ words) {
@@ -127,31 +104,7 @@ __global__ __launch_bounds__(256) void k_label_tiles(const T *__restrict__ src, 
 // ---------------------------------------------------------------------------------------------
 // merging across tile faces: k_merge<CONN>; flatten: k_flatten
 // ---------------------------------------------------------------------------------------------
-// Label equivalence on L.  find follows parents to a root, at most `cap` loads for a whole unite; unite hooks the larger of two roots under
-// the smaller with atomicMin.  If the word was no longer a root's (another thread hooked it in between), the atomicMin has at worst
-// replaced that thread's link a -> p by a -> b with b < p, so the unite goes on with (p, b): nothing that was joined before the launch is
-// ever parted (only words found to be roots IN this launch are written, and those held no link when it began).  A unite that runs out of
-// steps gives up and raises W_CHANGED; the host flattens and launches again.
-__device__ __forceinline__ bool find_root(const uint32_t *L, uint32_t &i, int &steps, int cap) {
-    for (; steps < cap; steps++) {
-        const uint32_t p = ld_agent(&L[i]) - 1u;
-        if (p == i) return true;
-        i = p;
-    }
-    return false;
-}
-__device__ __forceinline__ void unite(uint32_t *L, uint32_t a, uint32_t b, int cap, uint32_t *words) {
-    int steps = 0;
-    for (int tries = 0; tries < cap; tries++) {
-        if (!find_root(L, a, steps, cap) || !find_root(L, b, steps, cap)) break;
-        if (a == b) return;
-        if (a < b) { const uint32_t t = a; a = b; b = t; }                   // a > b: a goes under b
-        const uint32_t old = __hip_atomic_fetch_min(&L[a], b + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (old == a + 1u) return;                                          // a was a root still: hooked
-        a = old - 1u;                                                       // the parent a had: it belongs with b too
-    }
-    st_agent(&words[W_CHANGED], 1u);
-}
+// The label equivalence on L (find_root, unite): vpt_volume_components.h.
 // One thread a voxel; a foreground voxel unites with each foreground neighbour of smaller linear index that lies in ANOTHER tile (every
 // pair once; pairs inside a tile were joined by k_label_tiles).
 template <int CONN>
@@ -274,9 +227,8 @@ struct RankChannel { __device__ __forceinline__ uint32_t operator()(uint32_t ran
 // ---------------------------------------------------------------------------------------------
 // struct vpt_components: vpt_volume_components.h (vpt_volume_measure.hip reads the handle too)
 
-// chase steps a unite / a voxel's flatten may take in one launch: what vpt_volume_components passes
-#define CC_MERGE_STEPS 1024
-#define CC_FLATTEN_STEPS 64
+// chase steps a unite / a voxel's flatten may take in one launch: CC_MERGE_STEPS and CC_FLATTEN_STEPS (vpt_volume_components.h) are what
+// vpt_volume_components passes.
 // The smallest caps for which the bounds of the host's loops (components_build) hold; vpt_volume_components_capped refuses smaller ones.
 // Merge: on a flat forest a unite of two voxels that are not roots takes one step to the first root, confirms it, takes its second step to
 // the other root and must still be below the cap to confirm that one: with fewer than 3 steps a launch without a hook could give up, and
@@ -316,8 +268,9 @@ static void launch_merge(const vpt_components *c, int conn, int cap, uint32_t *w
     else hipLaunchKernelGGL(k_merge<26>, grid, dim3(256), 0, st, c->values.get(), c->nx, c->ny, c->nz, n, cap, words);
 }
 
-// the body of vpt_volume_components behind the argument checks; `c` is freed by the caller on failure
-static int components_build(vpt_components *c, int conn, uint32_t lo, uint32_t hi, uint32_t min_voxels, int merge_steps, int flatten_steps) {
+// the body of vpt_volume_components and vpt_volume_watershed behind the argument checks (ComponentsPasses: vpt_volume_components.h); `c` is
+// freed by the caller on failure
+int components_build(vpt_components *c, uint32_t min_voxels, int merge_steps, int flatten_steps, const ComponentsPasses &passes) {
     const size_t n = c->voxels();
     hipStream_t st = c->ctx->stream;
     DevBuf<uint32_t> words, count;
@@ -332,8 +285,7 @@ static int components_build(vpt_components *c, int conn, uint32_t lo, uint32_t h
     uint32_t host_words[W_WORDS] = {};
     PhaseClock clock(st);
     // ---- 1. tile labelling
-    if (c->norm16) launch_label_tiles<uint16_t>(c, conn, lo, hi, words);
-    else launch_label_tiles<uint8_t>(c, conn, lo, hi, words);
+    VPT_TRY(passes.tiles(words.get()));
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(host_words, words, sizeof(host_words), hipMemcpyDeviceToHost, st));
     HIP_TRY(clock.lap_add(&c->ms[0]));
@@ -348,16 +300,16 @@ static int components_build(vpt_components *c, int conn, uint32_t lo, uint32_t h
     const uint64_t merge_bound = (uint64_t)host_words[W_TILE_ROOTS] + 1u;
     const bool one_tile = c->nx <= CC_TX && c->ny <= CC_TY && c->nz <= CC_TZ;
     for (uint64_t round = 0; !one_tile; round++) {
-        if (round == merge_bound) return fail(VPT_ERR_HIP, "connected components: the merge did not settle within %llu launches", (unsigned long long)merge_bound);
+        if (round == merge_bound) return fail(VPT_ERR_HIP, "%s: the merge did not settle within %llu launches", passes.what, (unsigned long long)merge_bound);
         HIP_TRY(hipMemsetAsync(words + W_CHANGED, 0, sizeof(uint32_t), st));
-        launch_merge(c, conn, merge_steps, words);
+        passes.merge(merge_steps, words.get());
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(host_words, words, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         HIP_TRY(clock.lap_add(&c->ms[1]));
         c->launches[0]++;
         const bool merge_gave_up = host_words[W_CHANGED] != 0u;
         for (int f = 0; ; f++) {
-            if (f == flatten_bound) return fail(VPT_ERR_HIP, "connected components: the labels were not flat after %d launches", flatten_bound);
+            if (f == flatten_bound) return fail(VPT_ERR_HIP, "%s: the labels were not flat after %d launches", passes.what, flatten_bound);
             HIP_TRY(hipMemsetAsync(words + W_CHANGED, 0, sizeof(uint32_t), st));
             hipLaunchKernelGGL(k_flatten, dim3(stream_grid(n)), dim3(256), 0, st, c->values.get(), n, flatten_steps, words.get());
             HIP_TRY(hipGetLastError());
@@ -429,9 +381,26 @@ static int components_create(vpt_volume *src, uint32_t lo, uint32_t hi, int conn
     if ((src->ny + CC_TY - 1) / CC_TY > 65535 || (src->nz + CC_TZ - 1) / CC_TZ > 65535) return fail(VPT_ERR_UNSUPPORTED, "volume too large");
     std::unique_ptr<vpt_components> c(new vpt_components());
     VPT_TRY(field_capture(c.get(), src));
-    const int rc = components_build(c.get(), connectivity, lo, hi, min_voxels, merge_steps, flatten_steps);
+    vpt_components *h = c.get();
+    const ComponentsPasses passes = {
+        "connected components",
+        [=](uint32_t *words) {
+            if (h->norm16) launch_label_tiles<uint16_t>(h, connectivity, lo, hi, words);
+            else launch_label_tiles<uint8_t>(h, connectivity, lo, hi, words);
+            return (int)VPT_OK;
+        },
+        [=](int cap, uint32_t *words) { launch_merge(h, connectivity, cap, words); } };
+    const int rc = components_build(h, min_voxels, merge_steps, flatten_steps, passes);
     if (rc != VPT_OK) { (void)hipStreamSynchronize(ctx->stream); return rc; }      // the buffers are freed on return: nothing may still use them
     *out = c.release();
+    return VPT_OK;
+}
+
+int components_check_caps(int merge_steps, int flatten_steps) {
+    if (merge_steps < CC_MERGE_STEPS_MIN)
+        return fail(VPT_ERR_INVALID, "merge_steps %d: at least %d are needed for the merge loop's bound to hold", merge_steps, CC_MERGE_STEPS_MIN);
+    if (flatten_steps < CC_FLATTEN_STEPS_MIN)
+        return fail(VPT_ERR_INVALID, "flatten_steps %d: at least %d is needed for the flatten loop's bound to hold", flatten_steps, CC_FLATTEN_STEPS_MIN);
     return VPT_OK;
 }
 
@@ -442,10 +411,7 @@ extern "C" int vpt_volume_components(vpt_volume *src, uint32_t lo, uint32_t hi, 
 // (for tests) the caps are checked first: a refused cap touches neither the other arguments nor the device
 extern "C" int vpt_volume_components_capped(vpt_volume *src, uint32_t lo, uint32_t hi, int connectivity, uint32_t min_voxels, int merge_steps,
                                             int flatten_steps, vpt_components **out) {
-    if (merge_steps < CC_MERGE_STEPS_MIN)
-        return fail(VPT_ERR_INVALID, "merge_steps %d: at least %d are needed for the merge loop's bound to hold", merge_steps, CC_MERGE_STEPS_MIN);
-    if (flatten_steps < CC_FLATTEN_STEPS_MIN)
-        return fail(VPT_ERR_INVALID, "flatten_steps %d: at least %d is needed for the flatten loop's bound to hold", flatten_steps, CC_FLATTEN_STEPS_MIN);
+    VPT_TRY(components_check_caps(merge_steps, flatten_steps));
     return components_create(src, lo, hi, connectivity, min_voxels, merge_steps, flatten_steps, out);
 }
 

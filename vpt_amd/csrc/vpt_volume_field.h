@@ -16,6 +16,9 @@ struct VoxelField {
     size_t voxels() const { return (size_t)nx * (size_t)ny * (size_t)nz; }
 };
 
+// fills `f` from `src` but for the texels: context, dimensions, filter and channel width, `format` (R8 / R16: the snapshot's, one channel of
+// src's width), and both buffers; the caller enqueues what fills the texels (vpt_volume_watershed.hip: one channel of a two-channel relief)
+int field_describe(VoxelField *f, const vpt_volume *src, int format);
 // fills `f` from the R8 / R16 volume `src` (the caller has checked it): dimensions, format and filter, both buffers, and the copy of src's
 // texels on the context's stream, behind any upload into src
 int field_capture(VoxelField *f, const vpt_volume *src);

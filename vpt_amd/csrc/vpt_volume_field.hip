@@ -27,11 +27,17 @@ __global__ __launch_bounds__(256) void k_read_field(const uint32_t *__restrict__
     }
 }
 
-int field_capture(VoxelField *f, const vpt_volume *src) {
-    f->ctx = src->ctx; f->nx = src->nx; f->ny = src->ny; f->nz = src->nz; f->format = src->format; f->filter = src->filter; f->norm16 = src->norm16;
-    const size_t n = f->voxels(), bytes = n * (size_t)src->vox_bytes;
-    HIP_TRY(f->texels.alloc(bytes));
+int field_describe(VoxelField *f, const vpt_volume *src, int format) {
+    f->ctx = src->ctx; f->nx = src->nx; f->ny = src->ny; f->nz = src->nz; f->format = format; f->filter = src->filter; f->norm16 = src->norm16;
+    const size_t n = f->voxels();
+    HIP_TRY(f->texels.alloc(n * (size_t)(src->norm16 ? 2 : 1)));
     HIP_TRY(f->values.alloc(n));
+    return VPT_OK;
+}
+
+int field_capture(VoxelField *f, const vpt_volume *src) {
+    VPT_TRY(field_describe(f, src, src->format));
+    const size_t bytes = f->voxels() * (size_t)src->vox_bytes;         // one channel: what field_describe allocated
     HIP_TRY(hipMemcpyAsync(f->texels, src->linear, bytes, hipMemcpyDeviceToDevice, f->ctx->stream));     // behind any upload into src
     return VPT_OK;
 }

@@ -11,6 +11,7 @@ from .renderers import RendererFactory
 from .scene import Node, Transform, PerspectiveCamera
 from .tonemappers import ToneMapperFactory
 from .volume import Volume
+from .watershed import check_split
 
 
 class RenderingContext(EventTarget):
@@ -91,6 +92,20 @@ class RenderingContext(EventTarget):
         # R8 / R16 volume gets that geodesic operation (Volume.geodesic) when it is loaded, behind the rank filter and in front of
         # `components` mode 'keep' and the smoothing
         self.geodesic = self._geodesic_spec(options.get('geodesic'))
+        # (extension) None | {'lo', 'hi', 'h': 2, 'steps': 4, 'connectivity': 26, 'minVoxels': 1}: the structures of the codes lo .. hi of an
+        # R8 / R16 volume with touching ones split by the watershed of their depth (Volume.split).  It runs where the gradient runs, on the
+        # final scalar volume: the second channel is min(rank of the basin, M), so it cannot be combined with `gradient`, `components` mode
+        # 'label', `distance` mode 'channel' or `combine` op 'pair'
+        self.split = check_split(options.get('split'))
+        if self.split is not None:
+            if self.gradient is not None:
+                raise ValueError("split and gradient both write the second channel: name one of them")
+            if self.components is not None and self.components['mode'] == 'label':
+                raise ValueError("split and components mode 'label' both write the second channel: name one of them")
+            if self.distance is not None and self.distance['mode'] == 'channel':
+                raise ValueError("split and distance mode 'channel' both write the second channel: name one of them")
+            if self.combine is not None and self.combine['op'] == 'pair':
+                raise ValueError("split and combine op 'pair' both write the second channel: name one of them")
         self.gl = Context(options.get('device', 0))                                   # initGL(), :61-105
         self.environmentTexture = np.array([[[255, 255, 255, 255]]], dtype=np.uint8)   # :90-101
         self._rng = options.get('rng')
@@ -175,6 +190,16 @@ class RenderingContext(EventTarget):
                 self._derive_distance(lambda found: found.channel(self.distance['steps']))   # (value, distance): the 2-D transfer function's axes
             if self.combine is not None and self.combine['op'] == 'pair' and self._one_channel_unorm(self.volume):
                 self._combine_with(self.combine)                                      # (value, the second volume): the 2-D transfer function's axes
+            if self.split is not None and self._one_channel_unorm(self.volume):
+                spec, source = self.split, self.volume
+                largest = self._largest_code(source)                                  # the range is open above, and h is at most M
+                found = source.split(spec['lo'], min(spec['hi'], largest), min(spec['h'], largest), spec['steps'], spec['connectivity'],
+                                     spec['minVoxels'])
+                try:
+                    self.volume = found.label()                                       # (value, basin): a row of the 2-D transfer function per structure
+                finally:
+                    found.destroy()
+                source.destroy()
         except Exception:                                                             # the context keeps the volume it had
             self.volume.destroy()
             self.volume = old

@@ -727,6 +727,79 @@ class Volume(EventTarget):
     def regional_minima_timed(self, connectivity=6, channel=0):
         return self.geodesic_timed('minima', 0, connectivity, channel)
 
+    # ---- extension: watershed by steepest descent on a lower-completed relief (include/vpt.h; DESIGN.md "Watershed") ----
+    def _watershed(self, lo, hi, polarity, connectivity, min_voxels, channel, texels, timed, caps):
+        from .components import check_connectivity, check_min_voxels, check_range
+        from .reconstruct import check_source_channel
+        from .watershed import check_polarity
+        if not self.texture:
+            raise ValueError('a watershed takes a ready volume')
+        channels, dtype = self._texel_layout()
+        norm16 = np.dtype(dtype).itemsize == 2
+        channel = check_source_channel(channel, channels)
+        lo, hi = check_range(lo, hi, 65535 if norm16 else 255)
+        polarity, connectivity, min_voxels = check_polarity(polarity), check_connectivity(connectivity), check_min_voxels(min_voxels)
+        if texels is not None and (not isinstance(texels, Volume) or not texels.texture):
+            raise ValueError('watershed takes a ready volume as texels')
+        args = (self.texture, channel, texels.texture if texels is not None else None, lo, hi, polarity, connectivity, min_voxels)
+        h, ms, launches = C.c_void_p(), (C.c_double * N.WATERSHED_PHASES)(), C.c_uint32(0)
+        if caps is not None:
+            merge_steps, flatten_steps, tile_rounds = caps
+            N.check(N.lib().vpt_volume_watershed_capped(*(args + (int(merge_steps), int(flatten_steps), int(tile_rounds), C.byref(h), ms, C.byref(launches)))))
+        elif timed:
+            N.check(N.lib().vpt_volume_watershed_timed(*(args + (C.byref(h), ms, C.byref(launches)))))
+        else:
+            N.check(N.lib().vpt_volume_watershed(*(args + (C.byref(h),))))
+        # the handle speaks of the volume whose texels it holds: `texels`, or the chosen channel of this one
+        basins = Components(texels if texels is not None else (self if channels == 1 else _OneChannelOf(self, norm16)), h)
+        if not timed:
+            return basins
+        return basins, {'ms': dict(zip(('classify', 'plateau', 'links'), ms)), 'plateau_launches': launches.value}
+
+    def watershed(self, lo, hi, polarity='minima', connectivity=6, min_voxels=1, channel=0, texels=None, _caps=None):
+        """The basins of channel ``channel`` of this (R8, RG8, R16 or RG16) volume, the relief, over the domain of the codes lo .. hi, as a
+        ``Components`` object: the watershed by steepest descent on the lower completion, flooded from the 'minima' or from the 'maxima'
+        (a depth channel), on the device (vpt_amd.watershed_texels states the contract).  Every voxel of the domain belongs to exactly one
+        basin; ``info``, ``list``, ``ranks``, ``keep``, ``label``, ``measure`` and ``keep_set`` work as on components.  ``texels`` (an R8 /
+        R16 volume of this size and channel width; None: the relief's channel) is what ``keep``, ``keep_set`` and ``label`` emit.  Neither
+        volume is changed; both may be destroyed.  ``_caps`` (for tests): (merge_steps, flatten_steps, tile_rounds) of
+        vpt_volume_watershed_capped."""
+        return self._watershed(lo, hi, polarity, connectivity, min_voxels, channel, texels, False, _caps)
+
+    def watershed_timed(self, lo, hi, polarity='minima', connectivity=6, min_voxels=1, channel=0, texels=None, _caps=None):
+        """(for measurements) (the basins ``watershed`` gives, {'ms': {'classify', 'plateau', 'links'} in milliseconds, 'plateau_launches'});
+        the common tail is the basins' ``profile()``.  ``_caps`` (for tests): (merge_steps, flatten_steps, tile_rounds) of
+        vpt_volume_watershed_capped."""
+        return self._watershed(lo, hi, polarity, connectivity, min_voxels, channel, texels, True, _caps)
+
+    def _split(self, lo, hi, h, steps, connectivity, min_voxels, timed):
+        norm16 = np.dtype(self._texel_layout()[1]).itemsize == 2
+        d = self.distance(lo, hi, 'rest')
+        try:
+            depth = d.channel(steps)
+        finally:
+            d.destroy()
+        try:
+            flattened = depth.hmax(h, connectivity, channel=1)
+        finally:
+            depth.destroy()
+        try:
+            return flattened._watershed(1, 65535 if norm16 else 255, 'maxima', connectivity, min_voxels, 0, self, timed, None)
+        finally:
+            flattened.destroy()
+
+    def split(self, lo, hi, h=2, steps=4, connectivity=26, min_voxels=1):
+        """The structures of the codes lo .. hi of this (R8 / R16) volume with touching ones split, as a ``Components`` object whose
+        emitters speak of this volume: the watershed, from the maxima, of the depth inside the structures (``steps`` rows a voxel) with
+        maxima shallower than ``h`` suppressed: distance(lo, hi, 'rest') -> channel(steps) -> hmax(h, connectivity, channel=1) ->
+        watershed(1, M, 'maxima', connectivity, min_voxels, texels=self), all on the device (vpt_amd.split_texels states it).  The
+        intermediates are destroyed."""
+        return self._split(lo, hi, h, steps, connectivity, min_voxels, False)
+
+    def split_timed(self, lo, hi, h=2, steps=4, connectivity=26, min_voxels=1):
+        """(for measurements) (the basins ``split`` gives, what ``watershed_timed`` reports of its watershed step)"""
+        return self._split(lo, hi, h, steps, connectivity, min_voxels, True)
+
     def set_wide_tables(self, wide):
         """force the > 4 GiB addressing variant of the kernels (automatic above 4 GiB of bricked data)"""
         N.check(N.lib().vpt_volume_set_wide_tables(self.texture, 1 if wide else 0))
@@ -735,6 +808,16 @@ class Volume(EventTarget):
         n = C.c_uint64(0)
         N.check(N.lib().vpt_volume_bricked_bytes(self.texture, C.byref(n)))
         return n.value
+
+
+class _OneChannelOf:
+    """what ``_VoxelField`` reads of its source, for one channel of a two-channel volume: the description of an R8 / R16 volume"""
+
+    def __init__(self, source, norm16):
+        self._gl = source._gl
+        self.modality = dict(source.modality, format=GL_RED, internalFormat=GL_R16_EXT if norm16 else GL_R8,
+                             type=GL_UNSIGNED_SHORT if norm16 else GL_UNSIGNED_BYTE)
+        self.metadata = source.metadata
 
 
 class _VoxelField:
