@@ -372,6 +372,35 @@ VPT_API int vpt_distance_channel(vpt_distance *dist, int steps, vpt_volume **out
 VPT_API int vpt_distance_profile(vpt_distance *dist, double *ms);
 VPT_API int vpt_distance_destroy(vpt_distance *dist);
 
+/* ---- local thickness: the largest inscribed ball, on the device (extension; DESIGN.md "Local thickness") */
+/* The measurement behind the depth: at a voxel, the radius of the largest ball that fits inside the structure and contains the voxel
+ * (trabecular thickness and spacing, vessel calibre, pore size; "colour the structure by how thick it is here", "keep the parts an
+ * r-voxel ball fits into").  A voxel on the rim of a thick wall has depth 1 and thickness "the wall".
+ *   Input: a vpt_distance handle `src` of either seed mode; D(c) is its squared distance at the voxel c.
+ *   Centre: a voxel c with D(c) > 0.  Its ball: { v in the volume : |v - c|^2 < D(c) }: open, so it holds no seed; it may stick out of the
+ *   volume, where no voxel exists (as in the distance transform, the border is not background).
+ *   T2(v) = max { D(c) : v lies in the ball of c }, 0 when no ball holds v.  A maximum over integers: unique, whatever the order of work.
+ *   In numpy:  T2 = zeros;  for c in argwhere(D > 0): T2[|grid - c|^2 < D[c]] = maximum(., D[c])       (vpt_amd.thickness_squared_texels
+ *   states it by level sets; js/vpt/thickness.js in plain JS).
+ *   It follows that T2(v) = 0 exactly where D(v) = 0; T2 >= D everywhere; max T2 = max D; { T2 >= t } is the union of the balls with
+ *   D >= t.  With TO_REST the result is the thickness of the structure, with TO_RANGE that of its complement (pore size, separation).
+ *   A src without any seed (info.seeds == 0) has D = VPT_DISTANCE_NONE everywhere: the result is VPT_DISTANCE_NONE everywhere (no kernel runs).
+ * The result is an ordinary vpt_distance handle whose values are T2: vpt_distance_squared, _within, _channel, _info and _destroy work on it
+ * unchanged; texel snapshot, format and filter are copied from src, device to device; info.seeds is src's, info.largest the largest finite
+ * T2 (= src's).  within(r^2 + 1, 0xFFFFFFFF) is "the parts some inscribed ball of radius > r covers": the opening by Euclidean balls, at
+ * every radius from one transform.  channel(steps) is (code, local radius in rows); steps = 2 gives the diameter in voxels; the pair
+ * volume is a valid `values` argument of vpt_components_measure (mean and maximum thickness per structure).  vpt_distance_profile of the
+ * result gives zeros.
+ * The calls block.  src is not changed and may be destroyed afterwards.  Two runs give identical bytes.  Sizes: those vpt_volume_distance
+ * takes.  A null argument, or unknown flag bits: VPT_ERR_INVALID.  A failed allocation: VPT_ERR_HIP, nothing is leaked. */
+VPT_API int vpt_distance_thickness(vpt_distance *src, vpt_distance **out);
+/* (for measurements) ms[VPT_THICKNESS_PHASES]: tile maxima and their ordering, the cover, info; the stream drained after each.  tiles: the
+ * tiles that hold a centre (one workgroup each); visited: the centre tiles those workgroups ran over, summed. */
+#define VPT_THICKNESS_PHASES 3      /* tile maxima + ordering, cover, info */
+VPT_API int vpt_distance_thickness_timed(vpt_distance *src, vpt_distance **out, double *ms, uint64_t *tiles, uint64_t *visited);
+/* (for tests) flags bit 0: no value cull, bit 1: no reach cull; the result is the contract's whatever the flags.  ms and visited may be null. */
+VPT_API int vpt_distance_thickness_capped(vpt_distance *src, int flags, vpt_distance **out, double *ms, uint64_t *visited);
+
 /* ---- resampling to any grid size on the device (extension; DESIGN.md "Resampling") */
 /* The step in front of everything that counts voxels (the rank filters' 3 x 3 x 3 box, components, distances "in voxel units"): a volume of
  * anisotropic voxels is brought to an isotropic grid, one that is too large or too coarse to a chosen size.  The result is a new, finalized

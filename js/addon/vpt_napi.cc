@@ -530,6 +530,30 @@ static napi_value DistanceProfile(napi_env env, napi_callback_info info) {
     for (int k = 0; k < VPT_DISTANCE_PHASES; k++) napi_set_element(env, out, k, number(env, ms[k]));
     return out;
 }
+// distanceThickness(distance) -> a distance handle: the local thickness
+static napi_value DistanceThickness(napi_env env, napi_callback_info info) {
+    napi_value a[1]; vpt_distance *d;
+    if (!get_args(env, info, 1, a) || !get_handle(env, a[0], &d)) return nullptr;
+    vpt_distance *out = nullptr;
+    VPT_CHECK(vpt_distance_thickness(d, &out));
+    return make_external(env, out);
+}
+// distanceThicknessTimed(distance, flags) -> [handle, ms tiles, ms cover, ms info, tiles, visited]; flags < 0: vpt_distance_thickness_timed,
+// otherwise vpt_distance_thickness_capped (tiles is then 0)
+static napi_value DistanceThicknessTimed(napi_env env, napi_callback_info info) {
+    napi_value a[2]; vpt_distance *d; int32_t flags;
+    if (!get_args(env, info, 2, a) || !get_handle(env, a[0], &d) || !get_i32(env, a[1], &flags)) return nullptr;
+    vpt_distance *out = nullptr; double ms[VPT_THICKNESS_PHASES] = {}; uint64_t tiles = 0, visited = 0;
+    if (flags < 0) VPT_CHECK(vpt_distance_thickness_timed(d, &out, ms, &tiles, &visited));
+    else VPT_CHECK(vpt_distance_thickness_capped(d, flags, &out, ms, &visited));
+    napi_value r;
+    napi_create_array_with_length(env, 3 + VPT_THICKNESS_PHASES, &r);
+    napi_set_element(env, r, 0, make_external(env, out));
+    for (int k = 0; k < VPT_THICKNESS_PHASES; k++) napi_set_element(env, r, 1 + k, number(env, ms[k]));
+    napi_set_element(env, r, 1 + VPT_THICKNESS_PHASES, number(env, (double)tiles));
+    napi_set_element(env, r, 2 + VPT_THICKNESS_PHASES, number(env, (double)visited));
+    return r;
+}
 static napi_value DistanceDestroy(napi_env env, napi_callback_info info) {
     napi_value a[1]; vpt_distance *d;
     if (!get_args(env, info, 1, a) || !get_handle(env, a[0], &d)) return nullptr;
@@ -857,7 +881,7 @@ static napi_value Init(napi_env env, napi_value exports) {
     EXPORT("componentsDestroy", ComponentsDestroy);
     EXPORT("volumeDistance", VolumeDistance); EXPORT("distanceInfo", DistanceInfo); EXPORT("distanceSquared", DistanceSquared);
     EXPORT("distanceWithin", DistanceWithin); EXPORT("distanceChannel", DistanceChannel); EXPORT("distanceProfile", DistanceProfile);
-    EXPORT("distanceDestroy", DistanceDestroy);
+    EXPORT("distanceDestroy", DistanceDestroy); EXPORT("distanceThickness", DistanceThickness); EXPORT("distanceThicknessTimed", DistanceThicknessTimed);
     EXPORT("rendererCreate", RendererCreate); EXPORT("rendererDestroy", RendererDestroy); EXPORT("rendererSetShard", RendererSetShard);
     EXPORT("rendererLocalRows", RendererLocalRows); EXPORT("rendererGlobalRow", RendererGlobalRow);
     EXPORT("rendererSetVolume", RendererSetVolume); EXPORT("rendererSetTransferFunction", RendererSetTransferFunction);

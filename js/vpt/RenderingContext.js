@@ -19,6 +19,9 @@
 //   them (seeds 'rest') (Volume.distance).  'within' runs behind `components` mode 'keep' and in front of the smoothing: the codes with
 //   from <= d2 <= to (squared voxels; to null: no upper end) stay, everything else becomes `fill`.  'channel' runs where the gradient runs:
 //   the second channel is min(isqrt(steps^2 d2), M); it cannot be combined with `gradient` or with `components` mode 'label'
+//   thickness: null (default) or the keys of `distance`, with seeds 'rest' and steps 2 by default: the squared local thickness T2 (the largest
+//   inscribed ball that holds the voxel; Distance.thickness) in the place of d2, applied where `distance` is and conflicting as it does:
+//   'within' from r^2 + 1 is the opening by the ball of radius r, 'channel' with steps 2 the diameter in voxels.  Naming both throws.
 //   resample: null (default), { size: [w, h, d] } or { spacing: [sx, sy, sz], pitch }, plus mode: 'filtered' (default) | 'nearest': the volume
 //   is resampled to that grid, or to cubic voxels of edge `pitch` (default: the smallest spacing), behind the window and in front of the rank
 //   filter, so rank, components and distance see the resampled grid (Volume.resample, Volume.isotropic); a volume whose format the mode does
@@ -81,6 +84,16 @@ constructor(options) {
             throw new Error("distance mode 'channel' and components mode 'label' both write the second channel: name one of them");
         }
     }
+    this.thickness = RenderingContext._distanceSpec(options.thickness, 'thickness'); // likewise
+    if (this.thickness !== null) {
+        if (this.distance !== null) { throw new Error('distance and thickness are two readings of one transform: name one of them'); }
+        if (this.thickness.mode === 'channel') {
+            if (this.gradient !== null) { throw new Error("thickness mode 'channel' and gradient both write the second channel: name one of them"); }
+            if (this.components !== null && this.components.mode === 'label') {
+                throw new Error("thickness mode 'channel' and components mode 'label' both write the second channel: name one of them");
+            }
+        }
+    }
     this.resample = RenderingContext._resampleSpec(options.resample);                // likewise
     this.combine = RenderingContext._combineSpec(options.combine);                   // likewise
     if (this.combine !== null && this.combine.op === 'pair') {
@@ -90,6 +103,9 @@ constructor(options) {
         }
         if (this.distance !== null && this.distance.mode === 'channel') {
             throw new Error("combine op 'pair' and distance mode 'channel' both write the second channel: name one of them");
+        }
+        if (this.thickness !== null && this.thickness.mode === 'channel') {
+            throw new Error("combine op 'pair' and thickness mode 'channel' both write the second channel: name one of them");
         }
     }
     this.geodesic = RenderingContext._geodesicSpec(options.geodesic);                // likewise
@@ -101,6 +117,9 @@ constructor(options) {
         }
         if (this.distance !== null && this.distance.mode === 'channel') {
             throw new Error("split and distance mode 'channel' both write the second channel: name one of them");
+        }
+        if (this.thickness !== null && this.thickness.mode === 'channel') {
+            throw new Error("split and thickness mode 'channel' both write the second channel: name one of them");
         }
         if (this.combine !== null && this.combine.op === 'pair') { throw new Error("split and combine op 'pair' both write the second channel: name one of them"); }
     }
@@ -182,6 +201,10 @@ async setVolume(reader) {                                                       
             const spec = this.distance;
             this._deriveDistance(found => found.within(spec.from, spec.to, spec.fill));
         }
+        if (this.thickness !== null && this.thickness.mode === 'within') {
+            const spec = this.thickness;
+            this._deriveDistance(found => found.within(spec.from, spec.to, spec.fill), true);
+        }
         if (this.smooth !== null) {
             const N = native(), fmt = this.volume.nativeFormat();
             if (fmt === N.VPT_FORMAT_R8 || fmt === N.VPT_FORMAT_R16) {                 // the formats the gradient takes: any other volume as it is
@@ -205,6 +228,7 @@ async setVolume(reader) {                                                       
         }
         if (this.components !== null && this.components.mode === 'label') { this._derive(found => found.label()); }   // (value, rank)
         if (this.distance !== null && this.distance.mode === 'channel') { this._deriveDistance(found => found.channel(this.distance.steps)); }   // (value, distance)
+        if (this.thickness !== null && this.thickness.mode === 'channel') { this._deriveDistance(found => found.channel(this.thickness.steps), true); }   // (value, local thickness)
         if (this.combine !== null && this.combine.op === 'pair') { await this._combineWith(this.combine); }                    // (value, the second volume)
         if (this.split !== null) {
             const N = native(), fmt = this.volume.nativeFormat();
@@ -235,12 +259,17 @@ _derive(emit) {
     source.destroy();
 }
 
-// replaces this.volume (if it is R8 / R16: any other volume stays as it is) by what emit(distances of the `distance` option) returns
-_deriveDistance(emit) {
-    const N = native(), fmt = this.volume.nativeFormat(), spec = this.distance;
+// replaces this.volume (if it is R8 / R16: any other volume stays as it is) by what emit(distances of the `distance` option) returns, or
+// (thickness) emit(local thickness of the `thickness` option)
+_deriveDistance(emit, thickness) {
+    const N = native(), fmt = this.volume.nativeFormat(), spec = thickness ? this.thickness : this.distance;
     if (fmt !== N.VPT_FORMAT_R8 && fmt !== N.VPT_FORMAT_R16) { return; }
     const source = this.volume, largest = fmt === N.VPT_FORMAT_R16 ? 65535 : 255;      // the range is open above: hi may exceed an R8 volume's codes
-    const found = source.distance(spec.lo, Math.min(spec.hi, largest), spec.seeds);
+    let found = source.distance(spec.lo, Math.min(spec.hi, largest), spec.seeds);
+    if (thickness) {
+        const depth = found;
+        try { found = depth.thickness(); } finally { depth.destroy(); }
+    }
     try { this.volume = emit(found); } finally { found.destroy(); }
     source.destroy();
 }
@@ -324,23 +353,27 @@ static _resampleTakes(volume, mode) {
     return !(fmt >= N.VPT_FORMAT_RGB565 && fmt <= N.VPT_FORMAT_RGB9_E5);
 }
 
-// the `distance` option with its defaults filled in, or null; throws for anything the contract does not take
-static _distanceSpec(spec) {
+// the `distance` option (or, under its name, the `thickness` option: seeds 'rest' and steps 2 by default) with its defaults filled in, or
+// null; throws for anything the contract does not take
+static _distanceSpec(spec, name) {
+    name = name || 'distance';
+    const thickness = name === 'thickness';
     if (spec === undefined || spec === null) { return null; }
     const known = ['lo', 'hi', 'seeds', 'mode', 'from', 'to', 'fill', 'steps'], given = k => spec[k] !== undefined && spec[k] !== null;
     if (typeof spec !== 'object' || Array.isArray(spec) || !Object.keys(spec).every(k => known.includes(k)) || (spec.mode !== 'within' && spec.mode !== 'channel')) {
-        throw new Error("distance is null or { lo, hi, seeds, mode: 'within' | 'channel', from, to, fill, steps }, not " + JSON.stringify(spec));
+        throw new Error(name + " is null or { lo, hi, seeds, mode: 'within' | 'channel', from, to, fill, steps }, not " + JSON.stringify(spec));
     }
     checkDistanceRange(spec.lo, spec.hi, 65535);
-    const out = { lo: spec.lo, hi: spec.hi, seeds: given('seeds') ? spec.seeds : 'range', mode: spec.mode, from: 0, to: null, fill: 0, steps: 1 };
+    const out = { lo: spec.lo, hi: spec.hi, seeds: given('seeds') ? spec.seeds : (thickness ? 'rest' : 'range'), mode: spec.mode, from: 0, to: null, fill: 0,
+        steps: thickness ? 2 : 1 };
     checkSeeds(out.seeds);
     if (spec.mode === 'within') {
-        if (given('steps')) { throw new Error("distance 'steps' goes with mode 'channel'"); }
+        if (given('steps')) { throw new Error(name + " 'steps' goes with mode 'channel'"); }
         const k = checkWithin(given('from') ? spec.from : 0, spec.to, given('fill') ? spec.fill : 0, 65535);
         out.from = k[0]; out.to = k[1]; out.fill = k[2];
     } else {
-        if (given('from') || given('to') || given('fill')) { throw new Error("distance 'from', 'to' and 'fill' go with mode 'within'"); }
-        out.steps = checkSteps(given('steps') ? spec.steps : 1);
+        if (given('from') || given('to') || given('fill')) { throw new Error(name + " 'from', 'to' and 'fill' go with mode 'within'"); }
+        out.steps = checkSteps(given('steps') ? spec.steps : out.steps);
     }
     return out;
 }

@@ -607,6 +607,27 @@ core(lo, hi, radius) {
     try { return d.within(r2 + 1, null); } finally { d.destroy(); }
 }
 
+// ---- extension: local thickness, the largest inscribed ball (include/vpt.h; DESIGN.md "Local thickness") ----
+_thickness(lo, hi, seeds, emit) {
+    const d = this.distance(lo, hi, seeds);
+    let t;
+    try { t = d.thickness(); } finally { d.destroy(); }
+    try { return emit(t); } finally { t.destroy(); }
+}
+// a new, ready RG8 / RG16 volume (code, local thickness): the second channel is, in `steps` (default 2: the diameter in voxels) rows a voxel,
+// the radius of the largest ball that fits inside the structure of the codes lo .. hi (seeds 'rest', the default; 'range': inside its
+// complement) and holds the voxel: distance -> thickness -> channel(steps) on the device.  A valid `values` of Components.measure
+thickness(lo, hi, steps, seeds) {
+    steps = checkSteps(steps !== undefined ? steps : 2);
+    return this._thickness(lo, hi, seeds !== undefined ? seeds : 'rest', (t) => t.channel(steps));
+}
+// the codes lo .. hi opened by the Euclidean ball of `radius` voxels keep their codes (the parts some inscribed ball of a radius above
+// `radius` covers); `fill` (default 0) elsewhere: the counterpart of core that gives the peeled rim back
+openBall(lo, hi, radius, fill) {
+    const r2 = checkRadius(radius);
+    return this._thickness(lo, hi, 'rest', (t) => t.within(r2 + 1, null, fill));
+}
+
 }
 
 // the ready Volume `out` around a derived native volume: `modality` with the given dimensions in one block, and a copy of `meta`
@@ -693,6 +714,26 @@ within(r2Lo, r2Hi, fill) {
 channel(steps) {
     steps = checkSteps(steps !== undefined ? steps : 1);
     return this._derived(native().distanceChannel(this._handle(), steps), true);
+}
+
+// a Distance around another native handle over the same snapshot
+_sibling(handle) {
+    const other = Object.assign(Object.create(Distance.prototype), this);
+    other._dimensions = Object.assign({}, this._dimensions); other._modality = Object.assign({}, this._modality); other._meta = Object.assign({}, this._meta);
+    other._h = handle;
+    return other;
+}
+
+// the local thickness, as another Distance whose values are T2: per voxel the largest squared distance D(c) among the open balls
+// { |v - c|^2 < D(c) } of these distances that hold the voxel, 0 where none does (thicknessSquaredTexels states it), on the device.
+// within(r^2 + 1, null) of the result is the opening by the ball of radius r, channel(2) the local diameter.  This object is not changed
+thickness() { return this._sibling(native().distanceThickness(this._handle())); }
+
+// (for measurements) [what thickness gives, { ms: { tiles, cover, info }, tiles, visited }]; flags (for tests): those of
+// vpt_distance_thickness_capped (1: no value cull, 2: no reach cull); tiles is then null
+thicknessTimed(flags) {
+    const r = native().distanceThicknessTimed(this._handle(), flags !== undefined && flags !== null ? flags : -1);
+    return [this._sibling(r[0]), { ms: { tiles: r[1], cover: r[2], info: r[3] }, tiles: flags !== undefined && flags !== null ? null : r[4], visited: r[5] }];
 }
 
 // (for measurements) { x, y, z }: milliseconds of the three passes of the transform

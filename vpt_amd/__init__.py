@@ -25,6 +25,7 @@ from .rank import rank_texels
 from .components import components_texels, keep_texels, label_texels
 from .measure import measure_texels, keep_set_texels, derive, MEASURE_DTYPE
 from .distance import distance_squared_texels, within_texels, channel_texels, check_seeds, check_steps, check_radius
+from .distance import thickness_squared_texels, thickness_texels, open_ball_texels
 from .resample import resample_texels, isotropic_shape, axis_taps, nearest_index, count_ties, check_mode, check_size, check_spacing
 from .combine import combine_texels, compare_stats, OPS, check_op, check_weights, check_channel
 from .reconstruct import reconstruct_texels, geodesic_texels, RECONSTRUCT_OPS, GEODESIC_OPS
@@ -43,6 +44,7 @@ __all__ = [
     'components_texels', 'keep_texels', 'label_texels', 'Components',
     'measure_texels', 'keep_set_texels', 'derive', 'MEASURE_DTYPE',
     'distance_squared_texels', 'within_texels', 'channel_texels', 'check_seeds', 'check_steps', 'check_radius', 'Distance',
+    'thickness_squared_texels', 'thickness_texels', 'open_ball_texels',
     'resample_texels', 'isotropic_shape', 'axis_taps', 'nearest_index', 'count_ties', 'check_mode', 'check_size', 'check_spacing',
     'combine_texels', 'compare_stats', 'OPS', 'check_op', 'check_weights', 'check_channel',
     'reconstruct_texels', 'geodesic_texels', 'RECONSTRUCT_OPS', 'GEODESIC_OPS',

@@ -56,6 +56,7 @@ SYMBOLS = [
     "vpt_components_profile", "vpt_components_destroy",
     "vpt_volume_distance", "vpt_distance_info", "vpt_distance_squared", "vpt_distance_within", "vpt_distance_channel",
     "vpt_distance_profile", "vpt_distance_destroy",
+    "vpt_distance_thickness", "vpt_distance_thickness_timed", "vpt_distance_thickness_capped",
     "vpt_volume_resample", "vpt_volume_resample_timed",
     "vpt_volume_combine", "vpt_volume_combine_timed", "vpt_volume_compare",
     "vpt_volume_reconstruct", "vpt_volume_geodesic", "vpt_volume_reconstruct_timed", "vpt_volume_geodesic_timed", "vpt_volume_reconstruct_capped",
@@ -137,6 +138,7 @@ RECONSTRUCT_DILATION, RECONSTRUCT_EROSION = 0, 1
 (GEODESIC_FILL_HOLES, GEODESIC_CLEAR_BORDER, GEODESIC_HMAX, GEODESIC_HMIN, GEODESIC_DOME, GEODESIC_MAXIMA, GEODESIC_MINIMA) = range(7)
 WATERSHED_MINIMA, WATERSHED_MAXIMA = 0, 1
 WATERSHED_PHASES = 3
+THICKNESS_PHASES = 3
 
 
 class CombineParams(C.Structure):
@@ -222,6 +224,9 @@ def lib():
         "vpt_volume_distance": [P, C.c_uint32, C.c_uint32, I, PP], "vpt_distance_info": [P, C.POINTER(DistanceInfo)],
         "vpt_distance_squared": [P, I, I, I, I, I, I, P, SZ], "vpt_distance_within": [P, C.c_uint32, C.c_uint32, C.c_uint32, PP],
         "vpt_distance_channel": [P, I, PP], "vpt_distance_profile": [P, C.POINTER(C.c_double)], "vpt_distance_destroy": [P],
+        "vpt_distance_thickness": [P, PP],
+        "vpt_distance_thickness_timed": [P, PP, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
+        "vpt_distance_thickness_capped": [P, I, PP, C.POINTER(C.c_double), C.POINTER(C.c_uint64)],
         "vpt_volume_resample": [P, I, I, I, I, PP], "vpt_volume_resample_timed": [P, I, I, I, I, PP, C.POINTER(C.c_double)],
         "vpt_volume_combine": [P, P, C.POINTER(CombineParams), PP], "vpt_volume_combine_timed": [P, P, C.POINTER(CombineParams), PP, C.POINTER(C.c_double)],
         "vpt_volume_compare": [P, P, I, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)],

@@ -5,9 +5,8 @@
 // The transform is separable: g0 = 0 on the seeds and NONE elsewhere, then per axis, in the order x, y, z, out[i] = min over the finite
 // g[j] of g[j] + (i - j)^2.  Everything is integer: positions are below 4096, so a d2 is at most 3 * 4095^2 < 2^26 and NONE = 2^32 - 1 never
 // enters a sum.  No workgroup waits for another: launch boundaries order the phases.
-#include "vpt_volume_field.h"
+#include "vpt_volume_distance.h"
 
-#define EDT_NONE 0xFFFFFFFFu
 #define EDT_MAX_AXIS 4096          // vpt_volume_create's limit: a row has at most 64 segments of 64 voxels, positions fit 16 bits
 
 // ---------------------------------------------------------------------------------------------
@@ -163,10 +162,11 @@ struct DistanceChannel {
 // ---------------------------------------------------------------------------------------------
 // host
 // ---------------------------------------------------------------------------------------------
-struct vpt_distance : VoxelField {         // the values are d2: one squared distance per voxel
-    struct vpt_distance_info info = {};
-    double ms[VPT_DISTANCE_PHASES] = {};
-};
+int distance_largest(hipStream_t st, const uint32_t *d2, size_t n, uint32_t *largest) {
+    hipLaunchKernelGGL(k_largest, dim3(stream_grid(n)), dim3(256), 0, st, d2, n, largest);
+    HIP_TRY(hipGetLastError());
+    return VPT_OK;
+}
 
 // the body of vpt_volume_distance behind the argument checks; `d` is freed by the caller on failure
 static int distance_build(vpt_distance *d, uint32_t lo, uint32_t hi, int seeds) {
@@ -199,8 +199,7 @@ static int distance_build(vpt_distance *d, uint32_t lo, uint32_t hi, int seeds) 
     HIP_TRY(clock.lap(&d->ms[2]));
     // ---- info
     unsigned long long host_count[EDT_COUNT_SLOTS] = {}; uint32_t host_largest = 0;
-    hipLaunchKernelGGL(k_largest, dim3(stream_grid(n)), dim3(256), 0, st, (const uint32_t *)d->values.get(), n, largest.get());
-    HIP_TRY(hipGetLastError());
+    VPT_TRY(distance_largest(st, d->values.get(), n, largest.get()));
     HIP_TRY(hipMemcpyAsync(host_count, count, sizeof(host_count), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(&host_largest, largest, sizeof(host_largest), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));                  // `other`, `stack` and the two words go out of scope behind their last use

@@ -151,6 +151,84 @@ def channel_texels(array, d2, steps=1):
     return np.ascontiguousarray(np.stack([array, g], axis=-1))
 
 
+_PAIRS = 1 << 21                                                # voxel-centre pairs looked at in one piece
+
+
+def _covered(shape, centres, values, voxels):
+    """of the voxels (flat indices): which lie in the open ball { |v - c|^2 < D_c } of one of the centres ([k][3] z, y, x; D_c = values):
+    the distance to the set of centres, each lowered by its D_c, is below 0.  Only the box of the voxels, widened by the largest radius, is
+    looked at: no ball from outside it reaches a voxel."""
+    z, y, x = np.unravel_index(voxels, shape)
+    reach = int(math.isqrt(int(values.max()))) + 1
+    first = [max(int(a.min()) - reach, 0) for a in (z, y, x)]
+    last = [min(int(a.max()) + reach + 1, m) for a, m in zip((z, y, x), shape)]
+    inside = np.all((centres >= first) & (centres < last), axis=1)
+    g = np.full([b - a for a, b in zip(first, last)], np.int64(_FAR))
+    c = centres[inside] - first
+    np.minimum.at(g, (c[:, 0], c[:, 1], c[:, 2]), -values[inside])
+    for axis in (2, 1, 0):
+        g = _along(g, axis)
+    return g[z - first[0], y - first[1], x - first[2]] < 0
+
+
+def _cover(shape, out, centres, values, voxels):
+    """out[v] = the largest D_c among the balls that hold v, for the voxels (flat indices) that some ball holds; `values` is descending.
+    Few pairs are looked at one by one.  Otherwise the centres are halved: a voxel that a ball of the upper half holds has its maximum
+    there (every value of the lower half is no larger), every other voxel has it in the lower half or nowhere: the level sets
+    { T2 >= t } = the union of the balls with D >= t, asked for the middle value first."""
+    if not len(voxels) or not len(values):
+        return
+    if len(voxels) * len(values) <= _PAIRS or len(values) == 1:
+        piece = max(1, _PAIRS // len(values))
+        for first in range(0, len(voxels), piece):
+            v = voxels[first:first + piece]
+            at = np.stack(np.unravel_index(v, shape), axis=-1).astype(np.int64)
+            held = ((at[:, None, :] - centres[None, :, :]) ** 2).sum(axis=-1) < values[None, :]
+            out[v] = np.where(held, values[None, :], 0).max(axis=1)
+        return
+    half = len(values) // 2
+    upper = _covered(shape, centres[:half], values[:half], voxels)
+    _cover(shape, out, centres[:half], values[:half], voxels[upper])
+    _cover(shape, out, centres[half:], values[half:], voxels[~upper])
+
+
+def thickness_squared_texels(d2):
+    """uint32 [depth][height][width]: the squared local thickness T2 of squared distances d2 (``distance_squared_texels``): a voxel c with
+    d2(c) > 0 is a centre, its ball the voxels v of the array with |v - c|^2 < d2(c) (open: it holds no seed), and T2(v) is the largest
+    d2(c) among the balls that hold v, 0 when none does: what ``Distance.thickness()`` holds on the device.  By level sets: for each
+    distinct value t of d2, descending, the voxels not yet set take t where their squared distance to { d2 = t } is below t (``_cover``
+    asks several levels at once).  NONE everywhere (no seed) gives NONE everywhere."""
+    d2 = np.asarray(d2)
+    if d2.ndim != 3 or 0 in d2.shape or d2.dtype.kind not in 'ui':
+        raise ValueError('squared distances are a [depth][height][width] array of unsigned integers')
+    d = d2.astype(np.int64)
+    none = d == NONE
+    if none.all():
+        return np.full(d2.shape, NONE, np.uint32)
+    if none.any() or int(d.min()) < 0 or int(d.max()) > NONE:
+        raise ValueError('squared distances are finite everywhere, or NONE everywhere')
+    out = np.zeros(d.size, np.int64)
+    voxels = np.flatnonzero(d.ravel() > 0)
+    values = d.ravel()[voxels]
+    order = np.argsort(-values, kind='stable')
+    centres = np.stack(np.unravel_index(voxels[order], d.shape), axis=-1).astype(np.int64)
+    _cover(d.shape, out, centres, values[order], voxels)
+    return np.ascontiguousarray(out.reshape(d.shape), dtype=np.uint32)
+
+
+def thickness_texels(array, lo, hi, steps=2, seeds='rest'):
+    """[depth][height][width][2] in the array's dtype: (code, min(isqrt(steps^2 T2), M)), T2 the squared local thickness of the codes
+    lo .. hi (seeds 'rest') or of their complement (seeds 'range'); steps 2: the diameter in voxels: what
+    ``Volume.thickness(lo, hi, steps, seeds)`` holds"""
+    return channel_texels(array, thickness_squared_texels(distance_squared_texels(array, lo, hi, seeds)), steps)
+
+
+def open_ball_texels(array, lo, hi, radius, fill=0):
+    """the codes lo .. hi opened by the Euclidean ball of ``radius`` voxels: the codes that an inscribed ball of a radius above
+    ``radius`` covers, ``fill`` elsewhere: what ``Volume.open_ball(lo, hi, radius)`` holds"""
+    return within_texels(array, thickness_squared_texels(distance_squared_texels(array, lo, hi, 'rest')), check_radius(radius) + 1, None, fill)
+
+
 def margin_texels(array, lo, hi, radius, fill=0):
     """the codes within ``radius`` voxels of the codes lo .. hi, ``fill`` elsewhere: what ``Volume.margin(lo, hi, radius)`` holds"""
     return within_texels(array, distance_squared_texels(array, lo, hi, 'range'), 0, check_radius(radius), fill)

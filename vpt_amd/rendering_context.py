@@ -69,6 +69,20 @@ class RenderingContext(EventTarget):
                 raise ValueError("distance mode 'channel' and gradient both write the second channel: name one of them")
             if self.components is not None and self.components['mode'] == 'label':
                 raise ValueError("distance mode 'channel' and components mode 'label' both write the second channel: name one of them")
+        # (extension) None | the keys of `distance`, with seeds 'rest' and steps 2 by default: the local thickness T2 of the structure of the
+        # codes lo .. hi (seeds 'rest'; 'range': of its complement), the squared radius of the largest inscribed ball that holds the voxel
+        # (Distance.thickness), in the place of d2: 'within' keeps the codes with from <= T2 <= to (from r^2 + 1: the opening by the ball of
+        # radius r), 'channel' writes min(isqrt(steps^2 T2), M) (steps 2: the diameter in voxels).  It is applied where `distance` is and
+        # conflicts as `distance` does; naming both is refused
+        self.thickness = self._distance_spec(options.get('thickness'), 'thickness')
+        if self.thickness is not None:
+            if self.distance is not None:
+                raise ValueError("distance and thickness are two readings of one transform: name one of them")
+            if self.thickness['mode'] == 'channel':
+                if self.gradient is not None:
+                    raise ValueError("thickness mode 'channel' and gradient both write the second channel: name one of them")
+                if self.components is not None and self.components['mode'] == 'label':
+                    raise ValueError("thickness mode 'channel' and components mode 'label' both write the second channel: name one of them")
         # (extension) None | {'size': [w, h, d]} | {'spacing': [sx, sy, sz], 'pitch': None}, plus 'mode': 'filtered' | 'nearest': the volume is
         # resampled to that grid, or to cubic voxels of edge `pitch` (None: the smallest spacing), when it is loaded, behind the window and in
         # front of the rank filter: rank, components and distance see the resampled grid.  A volume whose format the mode does not take is
@@ -88,6 +102,8 @@ class RenderingContext(EventTarget):
                 raise ValueError("combine op 'pair' and components mode 'label' both write the second channel: name one of them")
             if self.distance is not None and self.distance['mode'] == 'channel':
                 raise ValueError("combine op 'pair' and distance mode 'channel' both write the second channel: name one of them")
+            if self.thickness is not None and self.thickness['mode'] == 'channel':
+                raise ValueError("combine op 'pair' and thickness mode 'channel' both write the second channel: name one of them")
         # (extension) None | {'op': 'fill_holes' | 'clear_border' | 'hmax' | 'hmin' | 'dome' | 'maxima' | 'minima', 'h': 0, 'connectivity': 6}: an
         # R8 / R16 volume gets that geodesic operation (Volume.geodesic) when it is loaded, behind the rank filter and in front of
         # `components` mode 'keep' and the smoothing
@@ -104,6 +120,8 @@ class RenderingContext(EventTarget):
                 raise ValueError("split and components mode 'label' both write the second channel: name one of them")
             if self.distance is not None and self.distance['mode'] == 'channel':
                 raise ValueError("split and distance mode 'channel' both write the second channel: name one of them")
+            if self.thickness is not None and self.thickness['mode'] == 'channel':
+                raise ValueError("split and thickness mode 'channel' both write the second channel: name one of them")
             if self.combine is not None and self.combine['op'] == 'pair':
                 raise ValueError("split and combine op 'pair' both write the second channel: name one of them")
         self.gl = Context(options.get('device', 0))                                   # initGL(), :61-105
@@ -172,6 +190,9 @@ class RenderingContext(EventTarget):
             if self.distance is not None and self.distance['mode'] == 'within' and self._one_channel_unorm(self.volume):
                 spec = self.distance
                 self._derive_distance(lambda found: found.within(spec['from'], spec['to'], spec['fill']))
+            if self.thickness is not None and self.thickness['mode'] == 'within' and self._one_channel_unorm(self.volume):
+                spec = self.thickness
+                self._derive_distance(lambda found: found.within(spec['from'], spec['to'], spec['fill']), thickness=True)
             if self.smooth is not None and self._one_channel_unorm(self.volume):
                 source = self.volume
                 self.volume = source.smooth(self.smooth)
@@ -188,6 +209,8 @@ class RenderingContext(EventTarget):
                 self._derive(lambda source, found: found.label())                     # (value, rank): a row of the 2-D transfer function per structure
             if self.distance is not None and self.distance['mode'] == 'channel' and self._one_channel_unorm(self.volume):
                 self._derive_distance(lambda found: found.channel(self.distance['steps']))   # (value, distance): the 2-D transfer function's axes
+            if self.thickness is not None and self.thickness['mode'] == 'channel' and self._one_channel_unorm(self.volume):
+                self._derive_distance(lambda found: found.channel(self.thickness['steps']), thickness=True)   # (value, local thickness)
             if self.combine is not None and self.combine['op'] == 'pair' and self._one_channel_unorm(self.volume):
                 self._combine_with(self.combine)                                      # (value, the second volume): the 2-D transfer function's axes
             if self.split is not None and self._one_channel_unorm(self.volume):
@@ -222,13 +245,20 @@ class RenderingContext(EventTarget):
             found.destroy()
         source.destroy()
 
-    def _derive_distance(self, emit):
-        """replaces self.volume by what ``emit(distances of the `distance` option)`` returns"""
-        spec = self.distance
+    def _derive_distance(self, emit, thickness=False):
+        """replaces self.volume by what ``emit(distances of the `distance` option)`` returns, or (``thickness``)
+        ``emit(local thickness of the `thickness` option)``"""
+        spec = self.thickness if thickness else self.distance
         source = self.volume
         from . import _native as N
         largest = 65535 if source.native_format()[0] == N.FORMAT_R16 else 255        # the range is open above: hi may exceed an R8 volume's codes
         found = source.distance(spec['lo'], min(spec['hi'], largest), spec['seeds'])
+        if thickness:
+            depth = found
+            try:
+                found = depth.thickness()
+            finally:
+                depth.destroy()
         try:
             self.volume = emit(found)
         finally:
@@ -340,30 +370,32 @@ class RenderingContext(EventTarget):
         return not N.FORMAT_RGB565 <= fmt <= N.FORMAT_RGB9_E5
 
     @staticmethod
-    def _distance_spec(spec):
-        """the `distance` option with its defaults filled in, or None; raises ValueError for anything the contract does not take"""
+    def _distance_spec(spec, name='distance'):
+        """the `distance` option (or, under its name, the `thickness` option: seeds 'rest' and steps 2 by default) with its defaults filled
+        in, or None; raises ValueError for anything the contract does not take"""
         if spec is None:
             return None
         from .distance import check_range, check_seeds, check_steps, check_within
         known = {'lo', 'hi', 'seeds', 'mode', 'from', 'to', 'fill', 'steps'}
         if not isinstance(spec, dict) or not {'lo', 'hi', 'mode'} <= set(spec) or not set(spec) <= known:
-            raise ValueError("distance is None or {'lo', 'hi', 'seeds', 'mode': 'within' | 'channel', 'from', 'to', 'fill', 'steps'}, not %r" % (spec,))
+            raise ValueError("%s is None or {'lo', 'hi', 'seeds', 'mode': 'within' | 'channel', 'from', 'to', 'fill', 'steps'}, not %r" % (name, spec))
         if spec['mode'] not in ('within', 'channel'):
-            raise ValueError("distance mode is 'within' or 'channel', not %r" % (spec['mode'],))
+            raise ValueError("%s mode is 'within' or 'channel', not %r" % (name, spec['mode']))
         lo, hi = check_range(spec['lo'], spec['hi'], 65535)
-        seeds = spec['seeds'] if spec.get('seeds') is not None else 'range'
+        thickness = name == 'thickness'
+        seeds = spec['seeds'] if spec.get('seeds') is not None else ('rest' if thickness else 'range')
         check_seeds(seeds)
-        out = {'lo': lo, 'hi': hi, 'seeds': seeds, 'mode': spec['mode'], 'from': 0, 'to': None, 'fill': 0, 'steps': 1}
+        out = {'lo': lo, 'hi': hi, 'seeds': seeds, 'mode': spec['mode'], 'from': 0, 'to': None, 'fill': 0, 'steps': 2 if thickness else 1}
         if spec['mode'] == 'within':
             if spec.get('steps') is not None:
-                raise ValueError("distance 'steps' goes with mode 'channel'")
+                raise ValueError("%s 'steps' goes with mode 'channel'" % name)
             r2_lo, r2_hi, fill = check_within(spec['from'] if spec.get('from') is not None else 0, spec.get('to'),
                                               spec['fill'] if spec.get('fill') is not None else 0, 65535)
             out.update({'from': r2_lo, 'to': r2_hi, 'fill': fill})
         else:
             if any(spec.get(k) is not None for k in ('from', 'to', 'fill')):
-                raise ValueError("distance 'from', 'to' and 'fill' go with mode 'within'")
-            out['steps'] = check_steps(spec['steps'] if spec.get('steps') is not None else 1)
+                raise ValueError("%s 'from', 'to' and 'fill' go with mode 'within'" % name)
+            out['steps'] = check_steps(spec['steps'] if spec.get('steps') is not None else out['steps'])
         return out
 
     @staticmethod

@@ -488,6 +488,35 @@ class Volume(EventTarget):
         finally:
             d.destroy()
 
+    # ---- extension: local thickness, the largest inscribed ball (include/vpt.h; DESIGN.md "Local thickness") ----
+    def _thickness(self, lo, hi, seeds, emit):
+        d = self.distance(lo, hi, seeds)
+        try:
+            t = d.thickness()
+        finally:
+            d.destroy()
+        try:
+            return emit(t)
+        finally:
+            t.destroy()
+
+    def thickness(self, lo, hi, steps=2, seeds='rest'):
+        """A new, ready RG8 / RG16 volume (code, local thickness): the second channel is, in ``steps`` rows a voxel (2: the diameter in
+        voxels), the radius of the largest ball that fits inside the structure of the codes lo .. hi (seeds 'rest'; 'range': inside its
+        complement: pore size, separation) and holds the voxel: distance(lo, hi, seeds) -> thickness() -> channel(steps), all on the
+        device (vpt_amd.thickness_texels states it).  A valid ``values`` argument of ``Components.measure``."""
+        from .distance import check_steps
+        steps = check_steps(steps)
+        return self._thickness(lo, hi, seeds, lambda t: t.channel(steps))
+
+    def open_ball(self, lo, hi, radius, fill=0):
+        """A new, ready volume like this one in which the codes lo .. hi opened by the Euclidean ball of ``radius`` voxels keep their
+        codes (the parts some inscribed ball of radius > ``radius`` covers), ``fill`` elsewhere (vpt_amd.open_ball_texels states it): the
+        counterpart of ``core`` that gives the peeled rim back"""
+        from .distance import check_radius
+        r2 = check_radius(radius)
+        return self._thickness(lo, hi, 'rest', lambda t: t.within(r2 + 1, None, fill))
+
     # ---- extension: resampling to any grid size (include/vpt.h; DESIGN.md "Resampling") ----
     def resample(self, width, height, depth, mode='filtered'):
         """A new, ready volume in this volume's format and with its filter on a grid of width x height x depth texels (each 1 .. 4096) that
@@ -985,6 +1014,37 @@ class Distance(_VoxelField):
         h = C.c_void_p()
         N.check(N.lib().vpt_distance_channel(self._handle(), check_steps(steps), C.byref(h)))
         return self._derived(h, pair=True)
+
+    def _sibling(self, handle):
+        """a ``Distance`` around another native handle over the same snapshot"""
+        other = Distance.__new__(Distance)
+        other.__dict__.update(self.__dict__)
+        other._modality, other._meta = dict(self._modality), dict(self._meta)
+        other._h = handle
+        return other
+
+    def thickness(self):
+        """The local thickness, as another ``Distance`` object whose values are T2: per voxel the largest squared distance D(c) among the
+        open balls { |v - c|^2 < D(c) } of these distances that hold the voxel, 0 where none does (vpt_amd.thickness_squared_texels states
+        it), on the device.  ``within(r^2 + 1, None)`` of the result is the opening by the Euclidean ball of radius r, ``channel(2)`` the
+        local diameter.  This object is not changed and may be destroyed."""
+        h = C.c_void_p()
+        N.check(N.lib().vpt_distance_thickness(self._handle(), C.byref(h)))
+        return self._sibling(h)
+
+    def thickness_timed(self, _flags=None):
+        """(for measurements) (what ``thickness`` gives, {'ms': {'tiles', 'cover', 'info'} in milliseconds, 'tiles': the tiles that hold a
+        centre, 'visited': the centre tiles their workgroups ran over}).  ``_flags`` (for tests): the flags of
+        vpt_distance_thickness_capped (1: no value cull, 2: no reach cull); 'tiles' is then None."""
+        h = C.c_void_p()
+        ms = (C.c_double * N.THICKNESS_PHASES)()
+        tiles, visited = C.c_uint64(0), C.c_uint64(0)
+        if _flags is None:
+            N.check(N.lib().vpt_distance_thickness_timed(self._handle(), C.byref(h), ms, C.byref(tiles), C.byref(visited)))
+        else:
+            N.check(N.lib().vpt_distance_thickness_capped(self._handle(), int(_flags), C.byref(h), ms, C.byref(visited)))
+        return self._sibling(h), {'ms': dict(zip(('tiles', 'cover', 'info'), ms)), 'tiles': None if _flags is not None else int(tiles.value),
+                                  'visited': int(visited.value)}
 
     def profile(self):
         """(for measurements) {'x', 'y', 'z'}: milliseconds of the three passes of the transform"""
