@@ -733,7 +733,7 @@ VPT_API int vpt_renderer_set_render_target(vpt_renderer *r, void *device_ptr, si
  * line.  4 bytes per voxel of HBM.  Same taps, same lerps: results identical.  0 = the apron bricks, as the other renderers; 2 = records
  * where the bricks are beyond the Infinity Cache (> 512 MiB: measured 2-4 % faster there, 4-16 % slower on volumes that fit it). */
 #define VPT_OPTION_COLUMN_RECORDS 10
-/* VPT_OPTION_SETTLED_MISS (default 1; MCM renderer with the tile classes in force, LINEAR filter, one-channel byte volumes; extension): under a
+/* VPT_OPTION_SETTLED_MISS (0 off, 1 the settled form, 2 its packed form; default 2; MCM renderer with the tile classes in force, LINEAR filter, one-channel byte volumes; extension): under a
  * 1x1 environment with finite colour every event of a MISS tile's pixel deposits the same constant, so its running mean stops moving within
  * the first events after a reset (at once for white or black; the library proves it for the colour at hand, with one 16-byte read-back where
  * it has to).  From then on the MISS-tile pass neither reads nor writes [radiance, samples] and stores no frame texel — 16 of the 32 state
@@ -741,7 +741,9 @@ VPT_API int vpt_renderer_set_render_target(vpt_renderer *r, void *device_ptr, si
  * not been set since the reset, no display table rides on the fused store, the per-pixel sample count stays below 2^24 and (fused passes)
  * the destination has received every MISS texel once since the reset.  The samples owed are added before anything else reads them
  * (vpt_renderer_read, whole-image and bucket kernels, another matrix, an environment change, this option set to 0).  Every buffer a caller
- * can read is identical either way. */
+ * can read is identical either way.  2: the pass also carries two 32-bit words of the random stream per pixel (the last reset's jitter
+ * draws) instead of the 16-byte direction texel they determine, and the direction array of the MISS tiles is rebuilt from them before anything
+ * else reads it; same preconditions, same buffers. */
 #define VPT_OPTION_SETTLED_MISS 11
 VPT_API int vpt_renderer_set_option(vpt_renderer *r, int option, int value);
 /* (extension) how many buckets of frames vpt_renderer_play_into has run through the bucket kernels so far (VPT_OPTION_BUCKET_KERNEL) */

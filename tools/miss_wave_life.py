@@ -18,7 +18,7 @@ ap.add_argument("--tag", default="", help="names the build in the output (for in
 ap.add_argument("--out", default="build/miss_wave_life")
 ap.add_argument("--volume", type=int, default=512)
 ap.add_argument("--frames", type=int, default=200)
-ap.add_argument("--settled", default="1,0", help="VPT_OPTION_SETTLED_MISS values to run: 1 = k_mcm_miss_settled (the headline's), 0 = k_mcm_miss")
+ap.add_argument("--settled", default="1,0", help="VPT_OPTION_SETTLED_MISS values to run: 2 = k_mcm_miss_packed (the headline's), 1 = k_mcm_miss_settled, 0 = k_mcm_miss")
 ap.add_argument("--order", default="wave", choices=["wave", "workgroup"],
                 help="what the prologue's slots 1-5 of the build mean: 'wave' = the plain variants' order without a workgroup barrier "
                      "(vpt_kernels_mcm.h miss_wave_start); 'workgroup' = a build from before it (staged table, barrier)")

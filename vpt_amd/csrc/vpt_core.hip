@@ -7,6 +7,7 @@
 #include "vpt_internal.h"
 #include "vpt_kernels_layout.h"
 #include "vpt_srgb_lut.h"
+#include "vpt_mat4_sums.h"
 
 // ---------------------------------------------------------------------------------------------
 // errors
@@ -332,6 +333,7 @@ static int renderer_alloc_buffers(vpt_renderer *r) {
     r->frame_ring.reset(); r->ring_frames = 0;
     r->frame.reset(); r->acc.reset(); r->render.reset(); r->scratch.reset(); r->ndc_x.reset(); r->ndc_y.reset();
     for (int i = 0; i < 4; i++) r->st[i].reset();
+    r->cls.miss_words.reset(); r->cls.words_fresh = false;
     r->cls.valid = false; r->cls.stale = false; r->cls.pending = 0;   // new geometry, zeroed state: classes come back with the next reset
     r->cls.built = false;
     r->cls.passes = 0; r->cls.fused_passes = 0; r->cls.reset_seen = false; r->cls.n_complete = 0;   // (zeroed buffers are not a reset: nothing is skipped before one)
@@ -673,6 +675,8 @@ extern "C" int vpt_classify_tiles(int width, int height, int rank, int world, in
     return VPT_OK;
 }
 
+// the constant part of mvp_inv * (x, y, -+1, 1) (vpt_mat4_sums.h).  Whoever changes a->mvp_inv calls it.
+void mat4_sums(PassArgs *a) { mat4_point_sums(a->mvp_inv.m, a->mvp_near, a->mvp_far); }
 int make_args(vpt_renderer *r, const vpt_uniforms *u, bool need_volume, PassArgs *a) {
     memset(a, 0, sizeof(*a));
     a->pm.W = r->W; a->pm.H = r->H; a->pm.local_h = r->local_h;
@@ -703,6 +707,7 @@ int make_args(vpt_renderer *r, const vpt_uniforms *u, bool need_volume, PassArgs
     a->tf = r->tf; a->tf_w = r->tf_w; a->tf_h = r->tf_h; a->tf_fw = (float)r->tf_w; a->tf_hi = (float)(r->tf_w - 1);
     if (u) {
         memcpy(a->mvp_inv.m, u->mvp_inverse, sizeof(float) * 16);
+        mat4_sums(a);
         a->seed = u->rand_seed; a->offset = u->offset; a->step = u->step_size;
         a->extinction = u->extinction; a->anisotropy = u->anisotropy;
         a->inv_extinction = 1.0f / u->extinction;      // -log(u)/rate is evaluated as -log(u) * (1/rate)
@@ -716,6 +721,7 @@ int make_args(vpt_renderer *r, const vpt_uniforms *u, bool need_volume, PassArgs
     a->inv_h = (float)(1.0 / (double)r->H);
     a->frame = r->frame; a->acc = r->acc;
     a->st0 = r->st[0]; a->st1 = r->st[1]; a->st2 = r->st[2]; a->st3 = r->st[3];
+    a->miss_words = r->cls.miss_words;
     if (r->kind == VPT_RENDERER_DOS) {            // colour: st[0], in place; occlusion: in = the latest of st[2|3], out = the other
         a->st1 = nullptr; a->st2 = r->st[2 + r->dos_cur]; a->st3 = r->st[3 - r->dos_cur];
     }
@@ -893,7 +899,7 @@ extern "C" int vpt_renderer_read(vpt_renderer *r, int buffer, void *dst, size_t 
     } else if (buffer >= VPT_BUFFER_MCM_POSITION && buffer <= VPT_BUFFER_MCM_RADIANCE) {
         if (r->kind != VPT_RENDERER_MCM) return fail(VPT_ERR_INVALID, "not an MCM renderer");
         if (buffer == VPT_BUFFER_MCM_POSITION || buffer == VPT_BUFFER_MCM_TRANSMITTANCE) VPT_TRY(mcm_materialize(r));
-        if (buffer == VPT_BUFFER_MCM_RADIANCE) VPT_TRY(mcm_catch_up(r));    // the samples k_mcm_miss_settled has not written yet
+        else VPT_TRY(mcm_catch_up(r));    // radiance: the samples the settled forms have not written yet; direction: k_mcm_miss_packed's records
         elem = 16; src = r->st[buffer - VPT_BUFFER_MCM_POSITION];
     } else {
         return fail(VPT_ERR_INVALID, "unknown buffer %d", buffer);
@@ -1000,8 +1006,9 @@ extern "C" int vpt_renderer_set_option(vpt_renderer *r, int option, int value) {
             r->bucket_kernel = value != 0; return VPT_OK;
         case VPT_OPTION_SETTLED_MISS:
             if (r->kind != VPT_RENDERER_MCM) return fail(VPT_ERR_UNSUPPORTED, "VPT_OPTION_SETTLED_MISS: an MCM option");
-            if (!value) VPT_TRY(mcm_catch_up(r));
-            r->cls.settled_opt = value != 0; return VPT_OK;
+            if (value < 0 || value > 2) return fail(VPT_ERR_INVALID, "VPT_OPTION_SETTLED_MISS: 0 (off), 1 (settled) or 2 (packed)");
+            if (!value || (value != 2 && r->cls.words_fresh)) VPT_TRY(mcm_catch_up(r));   // (1: k_mcm_miss_settled reads the direction array)
+            r->cls.settled_opt = value; return VPT_OK;
         case VPT_OPTION_VERIFY_TILE_CLASSES:
             if (r->kind != VPT_RENDERER_MCM) return fail(VPT_ERR_UNSUPPORTED, "VPT_OPTION_VERIFY_TILE_CLASSES: an MCM option");
             r->cls.verify = value != 0; return VPT_OK;

@@ -242,6 +242,17 @@ VPT_DEV float4 mat4_mul_point(const Mat4 &M, float x, float y, float z) {
     r.w = fmaf(m[7], y, fmaf(m[3], x, fmaf(m[11], z, m[15])));
     return r;
 }
+// ... with the constant part c[i] = fl(m[8+i] * z + m[12+i]) summed once on the host (z = -1: m[12+i] - m[8+i], z = +1: m[12+i] + m[8+i]; the
+// fma with z = -+1 rounds once, like the subtraction and the addition): the sums are wave-uniform, and a lane has no scalar float unit to share them
+VPT_DEV float4 mat4_mul_point(const Mat4 &M, const float *c, float x, float y) {
+    const float *m = M.m;
+    float4 r;
+    r.x = fmaf(m[4], y, fmaf(m[0], x, c[0]));
+    r.y = fmaf(m[5], y, fmaf(m[1], x, c[1]));
+    r.z = fmaf(m[6], y, fmaf(m[2], x, c[2]));
+    r.w = fmaf(m[7], y, fmaf(m[3], x, c[3]));
+    return r;
+}
 VPT_DEV f3 dehomogenize(float4 v) { float i = rcp_nr(v.w); return f3{ v.x * i, v.y * i, v.z * i }; }   // xyz / w
 // mixins/unproject.glsl:3-10
 VPT_DEV void unproject(float px, float py, const Mat4 &M, f3 &from, f3 &to) {

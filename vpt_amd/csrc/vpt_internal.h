@@ -133,8 +133,13 @@ struct TileClasses {
     const void *complete[VPT_COMPLETE_DESTS] = {}; int n_complete = 0;
     // MCM, the settled form of the MISS-tile pass (VPT_OPTION_SETTLED_MISS, k_mcm_miss_settled; vpt_mcm.hip "settled").  `complete` holds for
     // MCM the destinations whose MISS texels all show the settled radiance.
-    bool settled_opt = true;
-    uint64_t events = 0;           // events of every pixel since the reset (= `samples` of a MISS pixel, `pending` included)
+    int settled_opt = 2;           // VPT_OPTION_SETTLED_MISS: 0 off, 1 k_mcm_miss_settled, 2 k_mcm_miss_packed
+    // the packed form's records: the two jitter words of every MISS pixel's last reset, npix_padded of them in the state arrays' tile order
+    // (allocated with the first packed pass).  words_fresh: the last pass of the MISS tiles was a packed one — the records are newer than
+    // the direction array (then `stale` holds too), and k_mcm_materialize rebuilds it from them
+    DevBuf<uint2> miss_words;
+    bool words_fresh = false;
+    uint64_t events = 0;          // events of every pixel since the reset (= `samples` of a MISS pixel, `pending` included)
     uint32_t pending = 0;          // events k_mcm_miss_settled has run that the samples array does not show yet (k_mcm_materialize adds them)
     bool env_changed = false;      // the environment was set since the reset: the MISS pixels' mean is on the move again until the next one
     int settle = 0, probes = 0;    // 0: not known whether the MISS pixels' radiance is final, 1: proven, 2: given up until the next reset; read-backs spent on it
@@ -278,13 +283,14 @@ int extra_generate(vpt_renderer *r, const PassArgs &a);
 int extra_integrate(vpt_renderer *r, const PassArgs &a);
 int extra_render_frame(vpt_renderer *r, const PassArgs &a);
 int extra_fused(vpt_renderer *r, const PassArgs &a);
+void mat4_sums(PassArgs *a);                                        // vpt_core.hip: mvp_near / mvp_far of a->mvp_inv (make_args calls it)
 int mcm_reset(vpt_renderer *r, const PassArgs &a, const vpt_uniforms *u);     // vpt_mcm.hip
 int mcm_pass(vpt_renderer *r, const PassArgs &a, bool fuse_render);           // one integrate pass (tile classes where they are in force)
 int mcm_render_frame(vpt_renderer *r, const PassArgs &a);
 int mcm_multi(vpt_renderer *r, const PassArgs &a, uint32_t npasses, uint2 *ring);
 int mcm_before_pass(vpt_renderer *r, const PassArgs &a, bool *same_matrix);
 int mcm_materialize(vpt_renderer *r);
-int mcm_catch_up(vpt_renderer *r);                                            // mcm_materialize if k_mcm_miss_settled left samples pending
+int mcm_catch_up(vpt_renderer *r);                                            // mcm_materialize if the settled forms left samples pending or the direction array behind
 int mcm_bucket_ready(vpt_renderer *r, const PassArgs &a, bool *ready);
 int mcm_bucket(vpt_renderer *r, const PassArgs &a, const FrameVar *v, int count, void *ring, uint32_t slot_pixels, bool last_to_render_buffer,
                const uint8_t *display_table);

@@ -153,6 +153,7 @@ struct PassArgs {
     DevEnv env;
     const float4 *tf; int tf_w, tf_h; float tf_fw, tf_hi;   // decoded row 0 of the transfer function; (float)w, (float)(w-1)
     Mat4 mvp_inv;
+    float mvp_near[4], mvp_far[4];   // m[12+i] - m[8+i], m[12+i] + m[8+i]: the constant part of mvp_inv * (x, y, -+1, 1), summed on the host (mat4_sums)
     float seed, offset, step, extinction, inv_extinction, anisotropy;
     uint32_t max_bounces, steps;
     f3 light;
@@ -164,11 +165,13 @@ struct PassArgs {
     };
     uint32_t multi_passes;       // > 1: the fused (MODE 1) kernels run that many passes per pixel in one launch (VPT_PLAY_FUSED)
     uint32_t miss_load_pos;      // k_mcm_miss: 1 = the position array is up to date (first classified pass after a reset or a whole-image pass): load it
+    uint32_t miss_load_dir;      // k_mcm_miss_packed: 1 = the direction array is newer than the records (first packed pass after any other kind of pass): load it
     uint32_t miss_verify;        // k_mcm_miss of the other volume formats: 1 = count the events inside the cube (VPT_OPTION_VERIFY_TILE_CLASSES; a run-time flag there)
     unsigned long long *violations;   // k_mcm_miss<.., CHECK>: events of "miss" tiles that were inside the cube (must stay 0)
     void *frame;                 // tile order
     void *acc;                   // tile order (ping-pong collapsed: each pixel reads and writes only itself)
     float4 *st0, *st1, *st2, *st3;   // MCM photon state, tile order
+    uint2 *miss_words;           // k_mcm_miss_packed: the two jitter words of a MISS pixel's last reset (reset_draws), tile order like the state
     uint2 *render;               // RGBA16F, row-major local rows
     unsigned long long *samples; // volume-sample counter
     // frame sequences (vpt_renderer_play, vpt_gather_play): pass f of a launch takes its per-frame uniforms from entry

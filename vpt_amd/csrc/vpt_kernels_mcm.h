@@ -12,23 +12,43 @@ struct Photon {
 // mixins/unprojectRand.glsl:3-24.  The near-plane point depends on the pixel only when blur == 0 (the reference
 // always passes 0: MCMRenderer.js:93,157): the two disk uniforms are still drawn, their product with 0 is an exact
 // zero, so `from` equals the un-jittered unprojection `from0` computed once per pixel.
-// NOBLUR: the caller knows blur == 0 (k_mcm_miss: the tile classes are only used with it), the general branch is not compiled
-template <bool NOBLUR = false>
-VPT_DEV void unproject_rand(uint32_t &state, float px, float py, const PassArgs &a, f3 from0, f3 &from, f3 &to) {
-    if (NOBLUR || a.blur == 0.0f) {
-        random_uniform(state); random_uniform(state);
-        from = from0;
-    } else {
-        f2 d = random_disk(state);
-        from = dehomogenize(mat4_mul_point(a.mvp_inv, px + d.x * a.blur, py + d.y * a.blur, -1.0f));
-    }
-    float sx = random_uniform(state), sy = random_uniform(state);
+// With blur == 0 resetPhoton falls into two halves (both arithmetic variants; k_mcm_miss_packed runs them in different passes):
+//   draws: the state moves over the two disk draws and the two jitter draws; the two jitter STATES are all the rest depends on;
+//   aim:   from those two words and the pixel constants, the direction and the photon's start (reset_aim, fast_reset_aim).
+VPT_DEV uint2 reset_draws(uint32_t &state) {
+    state = pcg(pcg(state));                              // the disk sample's two draws (multiplied by blur = 0)
+    uint2 w;
+    w.x = state = pcg(state); w.y = state = pcg(state);
+    return w;
+}
+// inverseMvp * (x, y, -+1, 1).  SUMS: with the constant part the host summed (PassArgs.mvp_near / mvp_far: the same single rounding, the same
+// bits) — the plain MISS-tile kernels, whose prologue is vector issue; the HIT-tile kernels keep the per-lane fma: with the sums in scalar
+// registers they ran 4-6 % slower on a frame the volume fills (profiles/experiments.md, "Settled MISS pass: two RNG words")
+template <bool SUMS> VPT_DEV float4 unproject_plane_near(const PassArgs &a, float x, float y) {
+    return SUMS ? mat4_mul_point(a.mvp_inv, a.mvp_near, x, y) : mat4_mul_point(a.mvp_inv, x, y, -1.0f);
+}
+template <bool SUMS> VPT_DEV float4 unproject_plane_far(const PassArgs &a, float x, float y) {
+    return SUMS ? mat4_mul_point(a.mvp_inv, a.mvp_far, x, y) : mat4_mul_point(a.mvp_inv, x, y, 1.0f);
+}
+// the far-plane point of the jittered ray, from the two jitter words (random_uniform's value of a state: float(state) * 2^-32)
+template <bool SUMS = false>
+VPT_DEV f3 unproject_far(uint2 w, float px, float py, const PassArgs &a) {
+    float sx = (float)w.x * 0x1p-32f, sy = (float)w.y * 0x1p-32f;
     float ax = fmaf(sx, 2.0f, -1.0f) * a.inv_w;
     float ay = fmaf(sy, 2.0f, -1.0f) * a.inv_h;
-    to = dehomogenize(mat4_mul_point(a.mvp_inv, px + ax, py + ay, 1.0f));
+    return dehomogenize(unproject_plane_far<SUMS>(a, px + ax, py + ay));
 }
+// blur != 0: the near-plane point moves with the disk sample
+VPT_DEV void unproject_rand(uint32_t &state, float px, float py, const PassArgs &a, f3 &from, f3 &to) {
+    f2 d = random_disk(state);
+    from = dehomogenize(mat4_mul_point(a.mvp_inv, px + d.x * a.blur, py + d.y * a.blur, -1.0f));
+    uint2 w;
+    w.x = state = pcg(state); w.y = state = pcg(state);
+    to = unproject_far(w, px, py, a);
+}
+template <bool SUMS = false>
 VPT_DEV f3 unproject_near(float px, float py, const PassArgs &a) {
-    return dehomogenize(mat4_mul_point(a.mvp_inv, px + 0.0f, py + 0.0f, -1.0f));
+    return dehomogenize(unproject_plane_near<SUMS>(a, px + 0.0f, py + 0.0f));
 }
 // resetPhoton: MCMRenderer.glsl:70-78
 // the photon's start on its ray: from + max(tnear, 0) * direction (MCMRenderer.glsl:75-77).  A function of (from, direction) alone:
@@ -37,14 +57,34 @@ VPT_DEV f3 photon_start(f3 from, f3 dir) {
     float tnear = vmax(intersect_cube_near(from, dir), 0.0f);
     return madd3(from, tnear, dir);
 }
+struct Aim { f3 direction, position; };
+VPT_DEV void photon_aim(Photon &ph, const Aim &t) {
+    ph.direction = t.direction;
+    ph.bounces = 0u;
+    ph.position = t.position;
+    ph.transmittance = f3{ 1.0f, 1.0f, 1.0f };
+}
+VPT_DEV Aim reset_aim_at(f3 from, f3 to) {
+    Aim t;
+    t.direction = normalize3(sub3(to, from));
+    t.position = photon_start(from, t.direction);
+    return t;
+}
+// the aim half with blur == 0: the ray starts at the pixel's own near-plane point from0
+template <bool SUMS = false>
+VPT_DEV Aim reset_aim(const PassArgs &a, uint2 w, float px, float py, f3 from0) {
+    return reset_aim_at(from0, unproject_far<SUMS>(w, px, py, a));
+}
+// NOBLUR: the caller knows blur == 0 (k_mcm_miss: the tile classes are only used with it), the general branch is not compiled
 template <bool NOBLUR = false>
 VPT_DEV void reset_photon(uint32_t &state, Photon &ph, float px, float py, const PassArgs &a, f3 from0) {
-    f3 from, to;
-    unproject_rand<NOBLUR>(state, px, py, a, from0, from, to);
-    ph.direction = normalize3(sub3(to, from));
-    ph.bounces = 0u;
-    ph.position = photon_start(from, ph.direction);
-    ph.transmittance = f3{ 1.0f, 1.0f, 1.0f };
+    if (NOBLUR || a.blur == 0.0f) {
+        photon_aim(ph, reset_aim(a, reset_draws(state), px, py, from0));
+    } else {
+        f3 from, to;
+        unproject_rand(state, px, py, a, from, to);
+        photon_aim(ph, reset_aim_at(from, to));
+    }
 }
 // sampleHenyeyGreensteinAngleCosine: MCMRenderer.glsl:91-95
 VPT_DEV float hg_cos(uint32_t &state, float g) {
@@ -335,19 +375,33 @@ VPT_DEV f3 photon_start_fast(f3 from0, f3 dir) {
     return madd3(from0, tnear, dir);
 }
 // the pixel constants of the fast variant's resetPhoton with blur == 0: the near-plane point and the far-plane base point (homogeneous)
+template <bool SUMS = false>
 VPT_DEV FastPixel fast_pixel(const PassArgs &a, float px, float py) {
     FastPixel c;
-    const float4 nb = mat4_mul_point(a.mvp_inv, px, py, -1.0f);
+    const float4 nb = unproject_plane_near<SUMS>(a, px, py);
     const float inw = hw_rcp(nb.w);
     c.from0 = f3{ nb.x * inw, nb.y * inw, nb.z * inw };
-    c.fb = mat4_mul_point(a.mvp_inv, px, py, 1.0f);
+    c.fb = unproject_plane_far<SUMS>(a, px, py);
     c.jx = 0x1p-31f * a.inv_w; c.jy = 0x1p-31f * a.inv_h;
     return c;
+}
+// the aim half of the fast variant's resetPhoton with blur == 0 (the draws half is reset_draws)
+VPT_DEV Aim fast_reset_aim(const PassArgs &a, const FastPixel &c, uint2 w) {
+    const float *m = a.mvp_inv.m;
+    float ax = fmaf((float)w.x, c.jx, -a.inv_w);
+    float ay = fmaf((float)w.y, c.jy, -a.inv_h);
+    float4 th = { fmaf(m[4], ay, fmaf(m[0], ax, c.fb.x)), fmaf(m[5], ay, fmaf(m[1], ax, c.fb.y)),
+                  fmaf(m[6], ay, fmaf(m[2], ax, c.fb.z)), fmaf(m[7], ay, fmaf(m[3], ax, c.fb.w)) };
+    f3 d = { fmaf(-th.w, c.from0.x, th.x), fmaf(-th.w, c.from0.y, th.y), fmaf(-th.w, c.from0.z, th.z) };
+    float inv = __builtin_copysignf(hw_rsq(dot3(d, d)), th.w);
+    Aim t;
+    t.direction = f3{ d.x * inv, d.y * inv, d.z * inv };
+    t.position = photon_start_fast(c.from0, t.direction);
+    return t;
 }
 // DEPOSIT = false: resetPhoton alone (k_mcm_miss_settled: the running mean sits at a fixed point, the host counts the samples)
 template <bool NOBLUR = false, bool DEPOSIT = true>
 VPT_DEV void fast_path_end(const PassArgs &a, const FastPixel &c, uint32_t &state, Photon &ph, f3 rad, float px, float py) {
-    const float *m = a.mvp_inv.m;
     if (DEPOSIT) {
         ph.samples++;
         float inv_n = hw_rcp((float)ph.samples);
@@ -356,18 +410,7 @@ VPT_DEV void fast_path_end(const PassArgs &a, const FastPixel &c, uint32_t &stat
         ph.radiance.z = fmaf(rad.z - ph.radiance.z, inv_n, ph.radiance.z);
     }
     if (NOBLUR || a.blur == 0.0f) {
-        state = pcg(pcg(state));                          // the disk sample's two draws (multiplied by blur = 0)
-        float ax = fmaf(pcg_float(state), c.jx, -a.inv_w);
-        float ay = fmaf(pcg_float(state), c.jy, -a.inv_h);
-        float4 th = { fmaf(m[4], ay, fmaf(m[0], ax, c.fb.x)), fmaf(m[5], ay, fmaf(m[1], ax, c.fb.y)),
-                      fmaf(m[6], ay, fmaf(m[2], ax, c.fb.z)), fmaf(m[7], ay, fmaf(m[3], ax, c.fb.w)) };
-        f3 d = { fmaf(-th.w, c.from0.x, th.x), fmaf(-th.w, c.from0.y, th.y), fmaf(-th.w, c.from0.z, th.z) };
-        float inv = __builtin_copysignf(hw_rsq(dot3(d, d)), th.w);
-        f3 dir = { d.x * inv, d.y * inv, d.z * inv };
-        ph.direction = dir;
-        ph.position = photon_start_fast(c.from0, dir);
-        ph.bounces = 0u;
-        ph.transmittance = f3{ 1.0f, 1.0f, 1.0f };
+        photon_aim(ph, fast_reset_aim(a, c, reset_draws(state)));
     } else {
         reset_photon(state, ph, px, py, a, c.from0);      // depth-of-field runs: the contract's general path
     }
@@ -655,42 +698,68 @@ VPT_DEV uint32_t pass_seed(float px, float py, float seed) {
 // LATE: the sample is consumed after the path end (under whose arithmetic its load flies) instead of right where the shader samples
 // DEPOSIT = false: the settled form (k_mcm_miss_settled) — every draw, position and sample as here, without the deposit
 // TF: the staged float4 pairs (const float4 *: the bucket kernels and the other volume formats) or the wave's alpha column (const float2 *)
+// AIM = false (k_mcm_miss_packed, the last event of a pass; DEPOSIT is off there): the event ends behind the draws half of its reset and
+// returns the two jitter words; the direction and the start they stand for are computed by the next pass
+template <int V, bool CHECK, bool LATE, bool DEPOSIT, bool AIM, typename TF>
+VPT_DEV uint2 mcm_event_miss(const PassArgs &a, TF tf, Photon &ph, float px, float py, f3 from0, uint32_t &state) {
+    float dist = random_exponential(state, a.inv_extinction);
+    ph.position = madd3(ph.position, dist, ph.direction);
+    constexpr bool OTHER = (V & (VPT_V_NEAREST | VPT_V_RG | VPT_V_F32 | VPT_V_SNORM)) != 0;      // another volume format: the one-phase sample
+    MissLoad l = { 0u, 0.0f, 0.0f };
+    if constexpr (OTHER) miss_sample_any<V>(a, tf, ph.position);
+    else l = miss_sample_issue<CHECK>(a, ph.position, a.violations);
+    if constexpr (!LATE && !OTHER) miss_sample_finish(a, tf, l);
+    random_uniform(state);                                     // the wheel draw (its value decides nothing out of bounds)
+    if (DEPOSIT) {
+        float4 env = sample_environment(a.env, ph.direction);  // transmittance is (1, 1, 1): radiance = 1 * env, exactly env
+        photon_deposit(ph, f3{ env.x, env.y, env.z });
+    }
+    uint2 w = { 0u, 0u };
+    constexpr bool SUMS = !OTHER;                              // (the plain kernels, as their prologue: miss_wave_start)
+    if constexpr (AIM) photon_aim(ph, reset_aim<SUMS>(a, reset_draws(state), px, py, from0));   // resetPhoton with blur == 0
+    else w = reset_draws(state);
+    if constexpr (LATE && !OTHER) miss_sample_finish(a, tf, l);
+    return w;
+}
 template <int V, bool CHECK, bool LATE, bool DEPOSIT = true, typename TF>
 VPT_DEV void mcm_events_miss(const PassArgs &a, TF tf, Photon &ph, float px, float py, f3 from0, uint32_t state) {
-    for (uint32_t s = 0u; s < a.steps; s++) {
-        float dist = random_exponential(state, a.inv_extinction);
-        ph.position = madd3(ph.position, dist, ph.direction);
-        constexpr bool OTHER = (V & (VPT_V_NEAREST | VPT_V_RG | VPT_V_F32 | VPT_V_SNORM)) != 0;      // another volume format: the one-phase sample
-        MissLoad l = { 0u, 0.0f, 0.0f };
-        if constexpr (OTHER) miss_sample_any<V>(a, tf, ph.position);
-        else l = miss_sample_issue<CHECK>(a, ph.position, a.violations);
-        if constexpr (!LATE && !OTHER) miss_sample_finish(a, tf, l);
-        random_uniform(state);                                     // the wheel draw (its value decides nothing out of bounds)
-        if (DEPOSIT) {
-            float4 env = sample_environment(a.env, ph.direction);  // transmittance is (1, 1, 1): radiance = 1 * env, exactly env
-            photon_deposit(ph, f3{ env.x, env.y, env.z });
-        }
-        reset_photon<true>(state, ph, px, py, a, from0);
-        if constexpr (LATE && !OTHER) miss_sample_finish(a, tf, l);
-    }
+    for (uint32_t s = 0u; s < a.steps; s++) mcm_event_miss<V, CHECK, LATE, DEPOSIT, true>(a, tf, ph, px, py, from0, state);
+}
+template <int V, bool CHECK, bool LATE, bool DEPOSIT, bool AIM, typename TF>
+VPT_DEV uint2 mcm_event_miss_fast(const PassArgs &a, TF tf, const FastPixel &c, Photon &ph, float px, float py, uint32_t &state, float ld, float ld32) {
+    float dist = fmaf(hw_log2(pcg_float(state)), ld, ld32);
+    ph.position = madd3(ph.position, dist, ph.direction);
+    constexpr bool OTHER = (V & (VPT_V_NEAREST | VPT_V_RG | VPT_V_F32 | VPT_V_SNORM)) != 0;
+    MissLoad l = { 0u, 0.0f, 0.0f };
+    if constexpr (OTHER) miss_sample_any<V>(a, tf, ph.position);
+    else l = miss_sample_issue<CHECK>(a, ph.position, a.violations);
+    if constexpr (!LATE && !OTHER) miss_sample_finish(a, tf, l);
+    state = pcg(state);                                        // the wheel draw
+    f3 rad = { 0.0f, 0.0f, 0.0f };
+    if (DEPOSIT) { float4 env = sample_environment(a.env, ph.direction); rad = f3{ env.x, env.y, env.z }; }
+    uint2 w = { 0u, 0u };
+    if constexpr (AIM) fast_path_end<true, DEPOSIT>(a, c, state, ph, rad, px, py);
+    else w = reset_draws(state);
+    if constexpr (LATE && !OTHER) miss_sample_finish(a, tf, l);
+    return w;
 }
 template <int V, bool CHECK, bool LATE, bool DEPOSIT = true, typename TF>
 VPT_DEV void mcm_events_miss_fast(const PassArgs &a, TF tf, const FastPixel &c, Photon &ph, float px, float py, uint32_t state) {
     const float ld = fast_log2_scale(a.inv_extinction), ld32 = -32.0f * ld;
-    for (uint32_t s = 0u; s < a.steps; s++) {
-        float dist = fmaf(hw_log2(pcg_float(state)), ld, ld32);
-        ph.position = madd3(ph.position, dist, ph.direction);
-        constexpr bool OTHER = (V & (VPT_V_NEAREST | VPT_V_RG | VPT_V_F32 | VPT_V_SNORM)) != 0;
-        MissLoad l = { 0u, 0.0f, 0.0f };
-        if constexpr (OTHER) miss_sample_any<V>(a, tf, ph.position);
-        else l = miss_sample_issue<CHECK>(a, ph.position, a.violations);
-        if constexpr (!LATE && !OTHER) miss_sample_finish(a, tf, l);
-        state = pcg(state);                                        // the wheel draw
-        f3 rad = { 0.0f, 0.0f, 0.0f };
-        if (DEPOSIT) { float4 env = sample_environment(a.env, ph.direction); rad = f3{ env.x, env.y, env.z }; }
-        fast_path_end<true, DEPOSIT>(a, c, state, ph, rad, px, py);
-        if constexpr (LATE && !OTHER) miss_sample_finish(a, tf, l);
-    }
+    for (uint32_t s = 0u; s < a.steps; s++) mcm_event_miss_fast<V, CHECK, LATE, DEPOSIT, true>(a, tf, c, ph, px, py, state, ld, ld32);
+}
+// the events of k_mcm_miss_packed: 1 .. steps - 1 as in the settled form, the last one without the aim half; returns its jitter words
+// (steps >= 1: the host's precondition of the settled forms)
+template <int V, bool CHECK, bool LATE, typename TF>
+VPT_DEV uint2 mcm_events_miss_packed(const PassArgs &a, TF tf, Photon &ph, float px, float py, f3 from0, uint32_t state) {
+    for (uint32_t s = 1u; s < a.steps; s++) mcm_event_miss<V, CHECK, LATE, false, true>(a, tf, ph, px, py, from0, state);
+    return mcm_event_miss<V, CHECK, LATE, false, false>(a, tf, ph, px, py, from0, state);
+}
+template <int V, bool CHECK, bool LATE, typename TF>
+VPT_DEV uint2 mcm_events_miss_fast_packed(const PassArgs &a, TF tf, const FastPixel &c, Photon &ph, float px, float py, uint32_t state) {
+    const float ld = fast_log2_scale(a.inv_extinction), ld32 = -32.0f * ld;
+    for (uint32_t s = 1u; s < a.steps; s++) mcm_event_miss_fast<V, CHECK, LATE, false, true>(a, tf, c, ph, px, py, state, ld, ld32);
+    return mcm_event_miss_fast<V, CHECK, LATE, false, false>(a, tf, c, ph, px, py, state, ld, ld32);
 }
 // The prologue of a MISS-tile wave of the OTHER volume formats (k_mcm_miss with miss_sample_any), in the order its round trips allow
 // (profiles/experiments.md, "MISS wave prologue").  Nothing a pixel
@@ -754,8 +823,11 @@ VPT_DEV MissPixel miss_pixel_start(const PassArgs &a, float px, float py, float4
 // them takes the direction: the full vmcnt wait sits in front of it, behind the arithmetic).  The alpha column is the wave's own (tf_alpha_*,
 // vpt_kernels.h): written by all 64 lanes, valid or not, ordered by a wavefront-scope fence; no other wave is waited for.  The NDC values
 // still come from the host tables (their bits are the contract's); a lane without a pixel computes on zeros and leaves at the end.
+// PACKED (k_mcm_miss_packed): the state is the pixel's 8-byte record of jitter words (PassArgs.miss_words) in place of the direction texel,
+// and step 4 is the aim half of the last pass's reset (reset_aim / fast_reset_aim): direction and start from the record.  With miss_load_dir
+// set (wave-uniform, a kernel argument like miss_load_pos) the records are behind the direction array and the wave starts as the other forms do.
 struct MissWave { Pix p; float px, py; const float2 *tf_alpha; MissPixel m; float4 s3; };
-template <bool FAST, bool RADIANCE>
+template <bool FAST, bool RADIANCE, bool PACKED = false>
 VPT_DEV bool miss_wave_start(PassArgs &a, void *lds, MissWave &w, Photon &ph EV_PARAM) {
     // (the kernel arguments in ONE pinned batch of scalar loads was tried and lost: profiles/experiments.md, "MISS prologue without a barrier")
     const int e = (int)blockIdx.x;
@@ -773,34 +845,43 @@ VPT_DEV bool miss_wave_start(PassArgs &a, void *lds, MissWave &w, Photon &ph EV_
     TfAlpha c0 = { 0.0f, 0.0f };
     if (lane < tf_w) c0 = tf_alpha_load(a.tf, tf_w, lane);
     asm volatile("" ::: "memory");                            // (the loads above are issued before the loads below)
-    float4 s1 = a.st1[p.k];
+    const bool words = PACKED && !a.miss_load_dir;
+    float4 s1 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    uint2 rec = { 0u, 0u };
+    if (words) rec = a.miss_words[p.k];
+    else s1 = a.st1[p.k];
     // (s0 is read only where it was loaded.  On the first classified pass — miss_load_pos set — the compiler still copies two of its
     // registers inside the branch and waits vmcnt(0) there, in front of the arithmetic: that one pass per reset has no overlap)
     f3 s0;
-    if (a.miss_load_pos) s0 = ((const f3 *)a.st0)[p.k];
+    if (!words && a.miss_load_pos) s0 = ((const f3 *)a.st0)[p.k];
     w.s3 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     if (RADIANCE) w.s3 = a.st3[p.k];
     asm volatile("" ::: "memory");
     EV_MISS_PIN(px); EV_MISS_PIN(py); EV_MISS_MARK(evc, 2, "");
     MissPixel &m = w.m;
-    if (FAST) m.c = fast_pixel(a, px, py);
-    else m.c.from0 = unproject_near(px, py, a);
+    if (FAST) m.c = fast_pixel<true>(a, px, py);
+    else m.c.from0 = unproject_near<true>(px, py, a);
     m.state = pass_seed(px, py, a.seed);
     if (lane < tf_w) tf_alpha_store(col, lane, c0);
     // (pinned: this arithmetic and the column's writes stay in front of the wait for the direction)
     if (FAST) asm volatile("" : "+v"(m.c.fb.x), "+v"(m.c.fb.y), "+v"(m.c.fb.z), "+v"(m.c.fb.w));
     asm volatile("" : "+v"(m.c.from0.x), "+v"(m.c.from0.y), "+v"(m.c.from0.z), "+v"(m.state) : : "memory");
     EV_MISS_MARK(evc, 3, "");
-    asm volatile("" : "+v"(s1.x), "+v"(s1.y), "+v"(s1.z), "+v"(m.c.from0.x), "+v"(m.c.from0.y), "+v"(m.c.from0.z), "+v"(m.state));
+    if (words) asm volatile("" : "+v"(rec.x), "+v"(rec.y), "+v"(m.c.from0.x), "+v"(m.c.from0.y), "+v"(m.c.from0.z), "+v"(m.state));
+    else asm volatile("" : "+v"(s1.x), "+v"(s1.y), "+v"(s1.z), "+v"(m.c.from0.x), "+v"(m.c.from0.y), "+v"(m.c.from0.z), "+v"(m.state));
     EV_MISS_MARK(evc, 4, "");
     if (tf_w > 64) tf_alpha_stage_rest(col, a.tf, tf_w);     // (a transfer function wider than a wave: the further rounds, not overlapped)
     tf_alpha_fence();
     m.from0 = m.c.from0;
-    ph.direction = f3{ s1.x, s1.y, s1.z };
-    ph.bounces = 0u;
-    ph.transmittance = f3{ 1.0f, 1.0f, 1.0f };
-    if (FAST) ph.position = a.miss_load_pos ? s0 : photon_start_fast(m.from0, ph.direction);
-    else ph.position = a.miss_load_pos ? s0 : photon_start(m.from0, ph.direction);
+    Aim t;
+    if (words) {
+        t = FAST ? fast_reset_aim(a, m.c, rec) : reset_aim<true>(a, rec, px, py, m.from0);
+    } else {
+        t.direction = f3{ s1.x, s1.y, s1.z };
+        if (FAST) t.position = a.miss_load_pos ? s0 : photon_start_fast(m.from0, t.direction);
+        else t.position = a.miss_load_pos ? s0 : photon_start(m.from0, t.direction);
+    }
+    photon_aim(ph, t);
     w.px = px; w.py = py; w.tf_alpha = col;
     return p.valid;
 }
@@ -884,20 +965,51 @@ __global__ void __launch_bounds__(VPT_BLOCK) __attribute__((amdgpu_waves_per_eu(
     a.st1[w.p.k] = make_float4(ph.direction.x, ph.direction.y, ph.direction.z, 0.0f);
     EV_MISS_END(evc, a);
 }
+// The packed form of the settled pass (VPT_OPTION_SETTLED_MISS = 2).  The direction a settled pass leaves behind is a function of the pixel
+// and of the last reset's two jitter draws, and the start the last event computes is computed again by the next pass's prologue.  This
+// kernel is k_mcm_miss_settled — every draw, position and sample of it — except that its last event stops behind the draws half of the reset
+// (mcm_events_miss*_packed) and the pass stores the two jitter words, 8 B per pixel each way instead of 16; the aim half runs once, in the
+// next pass's prologue (miss_wave_start<.., PACKED>), by the same functions on the same values: the same bits.  The direction array of the MISS
+// tiles is behind from then on; k_mcm_materialize rebuilds it from the records before anything else reads it.
+template <int V, bool CHECK, bool LATE>
+__global__ void __launch_bounds__(VPT_BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) k_mcm_miss_packed(PassArgs a) {
+    EV_LOCAL
+    extern __shared__ float4 lds_raw[];
+    MissWave w;
+    Photon ph;
+    if (!miss_wave_start<(V & VPT_V_FAST) != 0, false, true>(a, lds_raw, w, ph EV_ARG)) return;
+    ph.radiance = f3{ 0.0f, 0.0f, 0.0f };
+    ph.samples = 0u;
+    EV_MISS_BEGIN(evc, ph);
+    uint2 rec;
+    if (V & VPT_V_FAST) rec = mcm_events_miss_fast_packed<V & ~VPT_V_FAST, CHECK, LATE>(a, w.tf_alpha, w.m.c, ph, w.px, w.py, w.m.state);
+    else rec = mcm_events_miss_packed<V, CHECK, LATE>(a, w.tf_alpha, ph, w.px, w.py, w.m.from0, w.m.state);
+    EV_MISS_EVENTS(evc, ph);
+    a.miss_words[w.p.k] = rec;
+    EV_MISS_END(evc, a);
+}
 // brings the position / transmittance arrays of the MISS tiles up to date: position = photon_start(from0, direction) in the
 // arithmetic of the variant that ran the last pass, transmittance = (1, 1, 1); `pending` > 0: the events k_mcm_miss_settled ran since
-// `samples` was last written are added to it (the count as k_mcm_miss would have stored it: both are exact below 2^24)
+// `samples` was last written are added to it (the count as k_mcm_miss would have stored it: both are exact below 2^24); `words`: the last
+// pass was k_mcm_miss_packed — the direction array is rebuilt first, (direction, 0) from the pixel's record by that variant's aim half
 template <bool FAST>
-__global__ void __launch_bounds__(VPT_BLOCK) k_mcm_materialize(PassArgs a, uint32_t pending) {
+__global__ void __launch_bounds__(VPT_BLOCK) k_mcm_materialize(PassArgs a, uint32_t pending, uint32_t words) {
     Pix p = map_pixel(a.pm);
     if (!p.valid) return;
     if (pending) a.st3[p.k].w = (float)((uint32_t)(a.st3[p.k].w + 0.5f) + pending);
     const float px = ndc_col(a.pm, p.i), py = ndc_row(a.pm, p.j);
-    const float4 s1 = a.st1[p.k];
-    const f3 dir = { s1.x, s1.y, s1.z };
     f3 pos;
-    if (FAST) pos = photon_start_fast(fast_pixel(a, px, py).from0, dir);
-    else pos = photon_start(unproject_near(px, py, a), dir);
+    if (words) {
+        const uint2 rec = a.miss_words[p.k];
+        const Aim t = FAST ? fast_reset_aim(a, fast_pixel<true>(a, px, py), rec) : reset_aim<true>(a, rec, px, py, unproject_near<true>(px, py, a));
+        a.st1[p.k] = make_float4(t.direction.x, t.direction.y, t.direction.z, 0.0f);
+        pos = t.position;
+    } else {
+        const float4 s1 = a.st1[p.k];
+        const f3 dir = { s1.x, s1.y, s1.z };
+        if (FAST) pos = photon_start_fast(fast_pixel(a, px, py).from0, dir);
+        else pos = photon_start(unproject_near(px, py, a), dir);
+    }
     ((f3 *)a.st0)[p.k] = pos;
     ((f3 *)a.st2)[p.k] = f3{ 1.0f, 1.0f, 1.0f };
 }

@@ -49,16 +49,18 @@ int mcm_materialize(vpt_renderer *r) {
     PassArgs a;
     VPT_TRY(make_args(r, nullptr, false, &a));
     memcpy(a.mvp_inv.m, r->cls.mvp, sizeof(r->cls.mvp));
+    mat4_sums(&a);
     a.pm.tile_list = r->cls.list + r->cls.n_hit; a.pm.list_n = r->cls.n_miss;
     if (r->cls.n_miss > 0) {
-        if (r->cls.stale_fast) hipLaunchKernelGGL(k_mcm_materialize<true>, dim3((unsigned)r->cls.n_miss), dim3(VPT_BLOCK), 0, r->ctx->stream, a, r->cls.pending);
-        else hipLaunchKernelGGL(k_mcm_materialize<false>, dim3((unsigned)r->cls.n_miss), dim3(VPT_BLOCK), 0, r->ctx->stream, a, r->cls.pending);
+        const uint32_t words = r->cls.words_fresh ? 1u : 0u;   // the direction array first, from k_mcm_miss_packed's records
+        if (r->cls.stale_fast) hipLaunchKernelGGL(k_mcm_materialize<true>, dim3((unsigned)r->cls.n_miss), dim3(VPT_BLOCK), 0, r->ctx->stream, a, r->cls.pending, words);
+        else hipLaunchKernelGGL(k_mcm_materialize<false>, dim3((unsigned)r->cls.n_miss), dim3(VPT_BLOCK), 0, r->ctx->stream, a, r->cls.pending, words);
         HIP_TRY(hipGetLastError());
     }
-    r->cls.stale = false; r->cls.pending = 0;
+    r->cls.stale = false; r->cls.pending = 0; r->cls.words_fresh = false;
     return VPT_OK;
 }
-int mcm_catch_up(vpt_renderer *r) { return r->cls.pending ? mcm_materialize(r) : VPT_OK; }
+int mcm_catch_up(vpt_renderer *r) { return (r->cls.pending || r->cls.words_fresh) ? mcm_materialize(r) : VPT_OK; }
 
 // ---- the settled form of the MISS-tile pass (k_mcm_miss_settled) ---------------------------------------------------------------------
 // Every event of a MISS pixel deposits the constant e of a 1x1 environment into the running mean r <- r + (e - r) / n, from r = 1 at the
@@ -120,7 +122,7 @@ static bool settled_destination(const vpt_renderer *r, const void *dest) {
 }
 // an MCM reset with matrix u->mvp_inverse has just been enqueued
 static int mcm_classify(vpt_renderer *r, const vpt_uniforms *u) {
-    r->cls.valid = false; r->cls.stale = false;               // the reset rewrote every array
+    r->cls.valid = false; r->cls.stale = false; r->cls.words_fresh = false;   // the reset rewrote every array
     r->cls.events = 0; r->cls.pending = 0; r->cls.env_changed = false; r->cls.n_complete = 0; r->cls.complete_events = 0;
     r->cls.probes = 0; r->cls.settle = settle_from_reset(r) ? 1 : 0;
     if (!r->cls.enabled || u->blur != 0.0f) return VPT_OK;
@@ -174,7 +176,16 @@ static int launch_mcm_classes(vpt_renderer *r, const PassArgs &a) {
                         a.steps >= 1u && c.events >= 1 && c.events + a.steps < (1ull << 24);
     if (wanted && c.settle == 0 && c.pending == 0) VPT_TRY(settle_probe(r));
     const bool settled = wanted && c.settle == 1 && (!FUSE || (a.tm_table == nullptr && settled_destination(r, a.render)));
-    if (settled) {
+    // ... in its packed form (VPT_OPTION_SETTLED_MISS = 2): 8-byte records of jitter words in place of the direction texels
+    const bool packed = settled && c.settled_opt == 2;
+    if (packed) {
+        if (!c.miss_words) HIP_TRY(c.miss_words.alloc(r->npix_padded));   // (every record is written by a pass before one reads it: miss_load_dir)
+        if (check) km = fast ? (late ? (PassKernel)k_mcm_miss_packed<VPT_V_FAST, true, true> : (PassKernel)k_mcm_miss_packed<VPT_V_FAST, true, false>)
+                             : (PassKernel)k_mcm_miss_packed<0, true, true>;
+        else km = fast ? (late ? (PassKernel)k_mcm_miss_packed<VPT_V_FAST, false, true> : (PassKernel)k_mcm_miss_packed<VPT_V_FAST, false, false>)
+                       : (PassKernel)k_mcm_miss_packed<0, false, true>;
+    } else if (settled) {
+        if (c.words_fresh) VPT_TRY(mcm_materialize(r));        // (k_mcm_miss_settled reads the direction array)
         if (check) km = fast ? (late ? (PassKernel)k_mcm_miss_settled<VPT_V_FAST, true, true> : (PassKernel)k_mcm_miss_settled<VPT_V_FAST, true, false>)
                              : (PassKernel)k_mcm_miss_settled<0, true, true>;
         else km = fast ? (late ? (PassKernel)k_mcm_miss_settled<VPT_V_FAST, false, true> : (PassKernel)k_mcm_miss_settled<VPT_V_FAST, false, false>)
@@ -213,6 +224,7 @@ static int launch_mcm_classes(vpt_renderer *r, const PassArgs &a) {
         PassArgs part = a;
         part.pm.tile_list = parts[i].list; part.pm.list_n = parts[i].n; part.miss_load_pos = r->cls.stale ? 0u : 1u; part.violations = r->cls.violations;
         part.miss_verify = check ? 1u : 0u;
+        part.miss_words = c.miss_words; part.miss_load_dir = c.words_fresh ? 0u : 1u;
         VPT_TIMING_ARG(part, i < hit_parts);
         return part;
     };
@@ -239,6 +251,7 @@ static int launch_mcm_classes(vpt_renderer *r, const PassArgs &a) {
     }
     r->cls.stale = r->cls.n_miss > 0; r->cls.stale_fast = fast;
     if (settled) { c.pending += a.steps; c.settled_passes++; }
+    c.words_fresh = packed;
     return VPT_OK;
 }
 
