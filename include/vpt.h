@@ -401,6 +401,59 @@ VPT_API int vpt_distance_thickness_timed(vpt_distance *src, vpt_distance **out, 
 /* (for tests) flags bit 0: no value cull, bit 1: no reach cull; the result is the contract's whatever the flags.  ms and visited may be null. */
 VPT_API int vpt_distance_thickness_capped(vpt_distance *src, int flags, vpt_distance **out, double *ms, uint64_t *visited);
 
+/* ---- curve skeleton and topological kernel by thinning, on the device (extension; DESIGN.md "Skeleton") */
+/* The question behind "how thick": the centreline of vessels, airways, trabeculae, fibres and pore networks (how many branches, where they
+ * meet, how thick along the centreline), and the homotopic erosion of any depth.  A subfield thinning: its result is a pure function of
+ * the input, whatever the order of work.
+ *   Input: an R8 or R16 volume `src`, a code range lo <= hi, a `mode`, a pass cap `passes`.  The object X is the set of voxels with
+ *   lo <= code <= hi; everything else is background, and so is everything outside the volume (a voxel on a face of the volume has a
+ *   background 6-neighbour).  Topology is (26, 6): the object is 26-connected, the background 6-connected.
+ *   For a voxel p and the current X: N26(p) its 26 neighbours, N18(p) those with at most two non-zero offset components, N6(p) the six face
+ *   neighbours; obj(p) = N26(p) ∩ X; C(p) = the number of 26-connected components of obj(p), adjacency taken inside N26(p), p excluded;
+ *   B(p) = the number of 6-connected components of N18(p) \ X that contain a voxel of N6(p), adjacency taken inside N18(p).  p is simple
+ *   iff C(p) == 1 && B(p) == 1 (Malandain-Bertrand).  Subfield of p = (x & 1) | (y & 1) << 1 | (z & 1) << 2.
+ *   One pass k = 1, 2, ...:
+ *     1. Border = the voxels of X that have a background 6-neighbour, taken from X as it is when the pass starts.
+ *     2. For s = 0 .. 7 in this order, every p in Border ∩ X with subfield s is decided from the X at the start of the sub-step (they do
+ *        not see each other: no two are 26-adjacent, so deciding them one by one in any order gives the same X):
+ *          VPT_THIN_KERNEL:  delete p if it is simple.
+ *          VPT_THIN_ENDS:    skip p if |obj(p)| == 1 (a curve end); otherwise delete p if it is simple.
+ *          VPT_THIN_ISTHMUS: skip p if it carries the isthmus mark; otherwise, if C(p) >= 2, give p the mark (for good) and skip it;
+ *                            otherwise delete p if it is simple.
+ *     3. The run ends after the first pass that deletes nothing and marks nothing (converged = 1), and after pass `passes` when
+ *        passes > 0 (converged says whether that pass was idle too).  passes == 0: to the fixed point.
+ *   In numpy: vpt_amd.skeleton_burn_texels; in plain JS: js/vpt/skeleton.js.
+ * The result is a voxel field like components and distances.  Its uint32 value per voxel is the burn pass: 0 for a voxel outside the
+ * range, k for a voxel deleted in pass k, VPT_THIN_KEPT for a voxel that survived.  { value >= k } is the object after k - 1 passes: one run
+ * serves a homotopic erosion of any depth.  An empty range runs no thinning kernel: passes 0, converged 1.  A single object voxel is not
+ * simple (C = 0) and survives in every mode.
+ * The calls block.  src is not changed and may be destroyed afterwards.  Two runs give identical bytes.  Formats other than R8 / R16:
+ * VPT_ERR_UNSUPPORTED, naming the format.  Sizes: those vpt_volume_distance takes.  A null argument, lo > hi, hi beyond the format's largest
+ * code, an unknown mode or passes < 0: VPT_ERR_INVALID.  A failed allocation: VPT_ERR_HIP, nothing is leaked. */
+#define VPT_THIN_KERNEL  0
+#define VPT_THIN_ENDS    1
+#define VPT_THIN_ISTHMUS 2
+#define VPT_THIN_KEPT 0xFFFFFFFFu
+typedef struct vpt_skeleton vpt_skeleton;
+/* passes: the passes run, the idle last one included; isolated, ends, regular, junctions: the kept voxels with 0, 1, 2 and >= 3 kept
+ * 26-neighbours (they add up to kept_voxels) */
+struct vpt_skeleton_info { uint64_t object_voxels, kept_voxels, passes, converged, isolated, ends, regular, junctions; };
+VPT_API int vpt_volume_skeleton(vpt_volume *src, uint32_t lo, uint32_t hi, int mode, int passes, vpt_skeleton **out);
+VPT_API int vpt_skeleton_info(vpt_skeleton *sk, struct vpt_skeleton_info *info);
+/* the burn passes of a box of voxels, [d][h][w] uint32; the box and nbytes are checked as vpt_components_ranks checks them.  Blocks. */
+VPT_API int vpt_skeleton_burn(vpt_skeleton *sk, int x, int y, int z, int w, int h, int d, uint32_t *host_dst, size_t nbytes);
+/* a new, finalized volume of the source's size, format and filter: the source code where k_lo <= value <= k_hi, `fill` elsewhere.
+ * k_lo <= k_hi and fill <= the format's largest code; otherwise VPT_ERR_INVALID.  within(VPT_THIN_KEPT, VPT_THIN_KEPT, 0) is the skeleton
+ * as a volume: the renderers draw it, vpt_volume_combine cuts a thickness channel with it, vpt_volume_components labels its branches. */
+VPT_API int vpt_skeleton_within(vpt_skeleton *sk, uint32_t k_lo, uint32_t k_hi, uint32_t fill, vpt_volume **out);
+/* (for measurements) ms[VPT_SKELETON_PHASES]: seed, border marking, sub-steps, closing census, the stream drained after each (the passes'
+ * times summed); launches: kernels launched; tiles: the tiles the sub-step launches worked on, summed */
+#define VPT_SKELETON_PHASES 4
+VPT_API int vpt_skeleton_profile(vpt_skeleton *sk, double *ms, uint64_t *launches, uint64_t *tiles);
+/* (for tests) flags bit 0: no tile cull (every tile takes part in every pass); the result is the contract's whatever the flags */
+VPT_API int vpt_volume_skeleton_capped(vpt_volume *src, uint32_t lo, uint32_t hi, int mode, int passes, int flags, vpt_skeleton **out);
+VPT_API int vpt_skeleton_destroy(vpt_skeleton *sk);
+
 /* ---- resampling to any grid size on the device (extension; DESIGN.md "Resampling") */
 /* The step in front of everything that counts voxels (the rank filters' 3 x 3 x 3 box, components, distances "in voxel units"): a volume of
  * anisotropic voxels is brought to an isotropic grid, one that is too large or too coarse to a chosen size.  The result is a new, finalized

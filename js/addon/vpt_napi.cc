@@ -554,6 +554,63 @@ static napi_value DistanceThicknessTimed(napi_env env, napi_callback_info info) 
     napi_set_element(env, r, 2 + VPT_THICKNESS_PHASES, number(env, (double)visited));
     return r;
 }
+// ---- skeleton -------------------------------------------------------------------------------------------
+// volumeSkeleton(volume, lo, hi, mode, passes, flags) -> a skeleton handle; flags < 0: vpt_volume_skeleton, otherwise vpt_volume_skeleton_capped
+static napi_value VolumeSkeleton(napi_env env, napi_callback_info info) {
+    napi_value a[6]; vpt_volume *v; uint32_t lo, hi; int32_t mode, passes, flags;
+    if (!get_args(env, info, 6, a) || !get_handle(env, a[0], &v) || !get_u32(env, a[1], &lo) || !get_u32(env, a[2], &hi) || !get_i32(env, a[3], &mode) ||
+        !get_i32(env, a[4], &passes) || !get_i32(env, a[5], &flags)) return nullptr;
+    vpt_skeleton *out = nullptr;
+    if (flags < 0) VPT_CHECK(vpt_volume_skeleton(v, lo, hi, mode, passes, &out));
+    else VPT_CHECK(vpt_volume_skeleton_capped(v, lo, hi, mode, passes, flags, &out));
+    return make_external(env, out);
+}
+// skeletonInfo(skeleton) -> [object_voxels, kept_voxels, passes, converged, isolated, ends, regular, junctions]
+static napi_value SkeletonInfo(napi_env env, napi_callback_info info) {
+    napi_value a[1]; vpt_skeleton *k;
+    if (!get_args(env, info, 1, a) || !get_handle(env, a[0], &k)) return nullptr;
+    struct vpt_skeleton_info i;
+    VPT_CHECK(vpt_skeleton_info(k, &i));
+    const uint64_t fields[8] = { i.object_voxels, i.kept_voxels, i.passes, i.converged, i.isolated, i.ends, i.regular, i.junctions };
+    napi_value out;
+    napi_create_array_with_length(env, 8, &out);
+    for (int f = 0; f < 8; f++) napi_set_element(env, out, f, number(env, (double)fields[f]));
+    return out;
+}
+// skeletonBurn(skeleton, x, y, z, width, height, depth, dst): the box's burn passes into dst (a Uint32Array)
+static napi_value SkeletonBurn(napi_env env, napi_callback_info info) {
+    BoxArgs b;
+    if (!get_box(env, info, &b)) return nullptr;
+    VPT_CHECK(vpt_skeleton_burn((vpt_skeleton *)b.handle, b.p[0], b.p[1], b.p[2], b.p[3], b.p[4], b.p[5], (uint32_t *)b.data, b.n));
+    return undefined(env);
+}
+// skeletonWithin(skeleton, kLo, kHi, fill) -> a new volume handle
+static napi_value SkeletonWithin(napi_env env, napi_callback_info info) {
+    napi_value a[4]; vpt_skeleton *k; uint32_t k_lo, k_hi, fill;
+    if (!get_args(env, info, 4, a) || !get_handle(env, a[0], &k) || !get_u32(env, a[1], &k_lo) || !get_u32(env, a[2], &k_hi) || !get_u32(env, a[3], &fill)) return nullptr;
+    vpt_volume *out = nullptr;
+    VPT_CHECK(vpt_skeleton_within(k, k_lo, k_hi, fill, &out));
+    return make_external(env, out);
+}
+// skeletonProfile(skeleton) -> [ms seed, ms border, ms steps, ms census, launches, tiles]
+static napi_value SkeletonProfile(napi_env env, napi_callback_info info) {
+    napi_value a[1]; vpt_skeleton *k;
+    if (!get_args(env, info, 1, a) || !get_handle(env, a[0], &k)) return nullptr;
+    double ms[VPT_SKELETON_PHASES]; uint64_t launches = 0, tiles = 0;
+    VPT_CHECK(vpt_skeleton_profile(k, ms, &launches, &tiles));
+    napi_value out;
+    napi_create_array_with_length(env, VPT_SKELETON_PHASES + 2, &out);
+    for (int p = 0; p < VPT_SKELETON_PHASES; p++) napi_set_element(env, out, p, number(env, ms[p]));
+    napi_set_element(env, out, VPT_SKELETON_PHASES, number(env, (double)launches));
+    napi_set_element(env, out, VPT_SKELETON_PHASES + 1, number(env, (double)tiles));
+    return out;
+}
+static napi_value SkeletonDestroy(napi_env env, napi_callback_info info) {
+    napi_value a[1]; vpt_skeleton *k;
+    if (!get_args(env, info, 1, a) || !get_handle(env, a[0], &k)) return nullptr;
+    VPT_CHECK(vpt_skeleton_destroy(k));
+    return undefined(env);
+}
 static napi_value DistanceDestroy(napi_env env, napi_callback_info info) {
     napi_value a[1]; vpt_distance *d;
     if (!get_args(env, info, 1, a) || !get_handle(env, a[0], &d)) return nullptr;
@@ -882,6 +939,8 @@ static napi_value Init(napi_env env, napi_value exports) {
     EXPORT("volumeDistance", VolumeDistance); EXPORT("distanceInfo", DistanceInfo); EXPORT("distanceSquared", DistanceSquared);
     EXPORT("distanceWithin", DistanceWithin); EXPORT("distanceChannel", DistanceChannel); EXPORT("distanceProfile", DistanceProfile);
     EXPORT("distanceDestroy", DistanceDestroy); EXPORT("distanceThickness", DistanceThickness); EXPORT("distanceThicknessTimed", DistanceThicknessTimed);
+    EXPORT("volumeSkeleton", VolumeSkeleton); EXPORT("skeletonInfo", SkeletonInfo); EXPORT("skeletonBurn", SkeletonBurn); EXPORT("skeletonWithin", SkeletonWithin);
+    EXPORT("skeletonProfile", SkeletonProfile); EXPORT("skeletonDestroy", SkeletonDestroy);
     EXPORT("rendererCreate", RendererCreate); EXPORT("rendererDestroy", RendererDestroy); EXPORT("rendererSetShard", RendererSetShard);
     EXPORT("rendererLocalRows", RendererLocalRows); EXPORT("rendererGlobalRow", RendererGlobalRow);
     EXPORT("rendererSetVolume", RendererSetVolume); EXPORT("rendererSetTransferFunction", RendererSetTransferFunction);

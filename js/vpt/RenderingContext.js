@@ -22,6 +22,9 @@
 //   thickness: null (default) or the keys of `distance`, with seeds 'rest' and steps 2 by default: the squared local thickness T2 (the largest
 //   inscribed ball that holds the voxel; Distance.thickness) in the place of d2, applied where `distance` is and conflicting as it does:
 //   'within' from r^2 + 1 is the opening by the ball of radius r, 'channel' with steps 2 the diameter in voxels.  Naming both throws.
+//   skeleton: null (default) or { lo, hi, mode: 'kernel' | 'ends' (default) | 'isthmus', passes: 0, fill: 0 }: the volume is replaced by the
+//   skeleton of the codes lo .. hi (Volume.skeleton): the voxels that survive the thinning keep their codes, everything else becomes
+//   `fill`.  It is applied where `thickness` mode 'within' is; naming it together with `distance` or `thickness` mode 'within' throws.
 //   resample: null (default), { size: [w, h, d] } or { spacing: [sx, sy, sz], pitch }, plus mode: 'filtered' (default) | 'nearest': the volume
 //   is resampled to that grid, or to cubic voxels of edge `pitch` (default: the smallest spacing), behind the window and in front of the rank
 //   filter, so rank, components and distance see the resampled grid (Volume.resample, Volume.isotropic); a volume whose format the mode does
@@ -50,6 +53,7 @@ const { checkResampleMode, checkResampleSize, checkSpacing } = require('./resamp
 const { checkCombineOp, checkCombineChannel, checkCombineWeights, checkCombineMask } = require('./combine.js');
 const { checkGeodesicH } = require('./reconstruct.js');
 const { checkSplit } = require('./watershed.js');
+const { checkSkeleton, THIN_KEPT } = require('./skeleton.js');
 const { RendererFactory } = require('./renderers/RendererFactory.js');
 const { ToneMapperFactory } = require('./tonemappers/ToneMapperFactory.js');
 
@@ -92,6 +96,15 @@ constructor(options) {
             if (this.components !== null && this.components.mode === 'label') {
                 throw new Error("thickness mode 'channel' and components mode 'label' both write the second channel: name one of them");
             }
+        }
+    }
+    this.skeleton = checkSkeleton(options.skeleton);                                 // likewise
+    if (this.skeleton !== null) {
+        if (this.distance !== null && this.distance.mode === 'within') {
+            throw new Error("skeleton and distance mode 'within' both replace the volume by a selection of it: name one of them");
+        }
+        if (this.thickness !== null && this.thickness.mode === 'within') {
+            throw new Error("skeleton and thickness mode 'within' both replace the volume by a selection of it: name one of them");
         }
     }
     this.resample = RenderingContext._resampleSpec(options.resample);                // likewise
@@ -204,6 +217,15 @@ async setVolume(reader) {                                                       
         if (this.thickness !== null && this.thickness.mode === 'within') {
             const spec = this.thickness;
             this._deriveDistance(found => found.within(spec.from, spec.to, spec.fill), true);
+        }
+        if (this.skeleton !== null) {
+            const N = native(), fmt = this.volume.nativeFormat(), spec = this.skeleton;
+            if (fmt === N.VPT_FORMAT_R8 || fmt === N.VPT_FORMAT_R16) {                 // any other volume as it is
+                const source = this.volume, largest = fmt === N.VPT_FORMAT_R16 ? 65535 : 255;      // the range is open above
+                const found = source.skeleton(spec.lo, Math.min(spec.hi, largest), spec.mode, spec.passes);
+                try { this.volume = found.within(THIN_KEPT, THIN_KEPT, Math.min(spec.fill, largest)); } finally { found.destroy(); }
+                source.destroy();
+            }
         }
         if (this.smooth !== null) {
             const N = native(), fmt = this.volume.nativeFormat();

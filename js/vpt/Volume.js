@@ -11,6 +11,7 @@ const { checkResampleMode, checkResampleSize, isotropicShape } = require('./resa
 const { COMBINE_STATS, checkCombineOp, checkCombineChannel, checkCombineWeights, checkCombineMask, checkCompareRange, compareRatios } = require('./combine.js');
 const { checkReconstructOp, checkGeodesicOp, checkGeodesicH, checkSourceChannel } = require('./reconstruct.js');
 const { checkPolarity } = require('./watershed.js');
+const { THIN_KEPT, SKELETON_INFO_FIELDS, checkThinMode, checkSkeletonRange, checkThinPasses, checkBurnWithin } = require('./skeleton.js');
 const { RAWReader, GL_RED, GL_RG, GL_RGB, GL_RGBA, GL_UNSIGNED_BYTE, GL_FLOAT, GL_HALF_FLOAT, GL_BYTE } = R;
 
 // [type, format, internalFormat, native format name, channels in the file, element kind] of the formats keyed on all three: SNORM bytes
@@ -628,6 +629,24 @@ openBall(lo, hi, radius, fill) {
     return this._thickness(lo, hi, 'rest', (t) => t.within(r2 + 1, null, fill));
 }
 
+// ---- extension: curve skeleton and topological kernel by thinning (include/vpt.h; DESIGN.md "Skeleton") ----
+// the burn passes of thinning the codes lo .. hi of this (R8 / R16) volume, as a Skeleton object, thinned on the device: mode 'kernel'
+// shrinks every structure to its topological kernel, 'ends' (the default) keeps curve ends (the centreline), 'isthmus' keeps the voxels that
+// once held two parts together; passes caps the passes (default 0: to the fixed point).  The object owns what it needs; this volume is not
+// changed.  flags (for tests): those of vpt_volume_skeleton_capped (1: no tile cull)
+skeleton(lo, hi, mode, passes, flags) {
+    const N = native(), norm16 = this.nativeFormat() === N.VPT_FORMAT_R16;
+    checkSkeletonRange(lo, hi, norm16 ? 65535 : 255);
+    const code = checkThinMode(mode !== undefined ? mode : 'ends');
+    passes = checkThinPasses(passes !== undefined ? passes : 0);
+    return new Skeleton(this, N.volumeSkeleton(this.texture, lo, hi, code, passes, flags !== undefined && flags !== null ? flags : -1));
+}
+// the voxels of the codes lo .. hi that survive the thinning (mode default 'ends') keep their codes; 0 elsewhere
+centreline(lo, hi, mode) {
+    const k = this.skeleton(lo, hi, mode);
+    try { return k.volume(); } finally { k.destroy(); }
+}
+
 }
 
 // the ready Volume `out` around a derived native volume: `modality` with the given dimensions in one block, and a copy of `meta`
@@ -684,6 +703,44 @@ _derived(texture, pair) {
     }
     return out;
 }
+
+}
+
+// The burn passes of a thinning of a value range of a volume (Volume.skeleton): one Uint32 per voxel on the device, 0 outside the range, k for
+// a voxel deleted in pass k, THIN_KEPT for a voxel that survived.  Thin once, select several times.  Outlives the volume it was made from;
+// destroy() (or close()) frees the device memory.
+class Skeleton extends VoxelField {
+
+constructor(source, handle) { super(source, handle, 'burn passes', 'skeletonDestroy', 'skeletonBurn'); }
+
+// { object_voxels, kept_voxels, passes, converged, isolated, ends, regular, junctions }: the last four count the kept voxels with 0, 1, 2
+// and >= 3 kept 26-neighbours
+get info() {
+    const i = native().skeletonInfo(this._handle()), out = {};
+    SKELETON_INFO_FIELDS.forEach((f, k) => { out[f] = i[k]; });
+    return out;
+}
+
+// Uint32Array [depth][height][width]: the burn passes of a box of voxels (default: the whole volume)
+burn(x, y, z, width, height, depth) { return this._values(x, y, z, width, height, depth); }
+
+// a new, ready volume of the source's size, format and filter: the source's code where kLo <= burn pass <= kHi (defaults THIN_KEPT and
+// 0xFFFFFFFF), `fill` (default 0) elsewhere; within(k) is the object after k - 1 passes
+within(kLo, kHi, fill) {
+    const k = checkBurnWithin(kLo !== undefined ? kLo : THIN_KEPT, kHi, fill !== undefined ? fill : 0, this._norm16 ? 65535 : 255);
+    return this._derived(native().skeletonWithin(this._handle(), k[0], k[1], k[2]));
+}
+
+// the skeleton as a volume: within(THIN_KEPT, THIN_KEPT, 0)
+volume() { return this.within(THIN_KEPT, THIN_KEPT, 0); }
+
+// (for measurements) { ms: { seed, border, steps, census }, launches, tiles }
+profile() {
+    const r = native().skeletonProfile(this._handle());
+    return { ms: { seed: r[0], border: r[1], steps: r[2], census: r[3] }, launches: r[4], tiles: r[5] };
+}
+
+close() { this.destroy(); }
 
 }
 
@@ -844,4 +901,4 @@ function checkRankPasses(passes) {
     if (!Number.isInteger(passes) || passes < 1 || passes > 8) { throw new Error('rank-filter passes are an integer in 1 .. 8, not ' + JSON.stringify(passes)); }
     return passes;
 }
-module.exports = { Volume, Components, Distance, RAWReader, filterCode, gradientArguments, windowFormatBits, percentileWindow, checkPasses, checkLevels, rankOperatorCode, checkRankPasses };
+module.exports = { Volume, Components, Distance, Skeleton, RAWReader, filterCode, gradientArguments, windowFormatBits, percentileWindow, checkPasses, checkLevels, rankOperatorCode, checkRankPasses };

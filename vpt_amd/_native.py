@@ -57,6 +57,8 @@ SYMBOLS = [
     "vpt_volume_distance", "vpt_distance_info", "vpt_distance_squared", "vpt_distance_within", "vpt_distance_channel",
     "vpt_distance_profile", "vpt_distance_destroy",
     "vpt_distance_thickness", "vpt_distance_thickness_timed", "vpt_distance_thickness_capped",
+    "vpt_volume_skeleton", "vpt_volume_skeleton_capped", "vpt_skeleton_info", "vpt_skeleton_burn", "vpt_skeleton_within", "vpt_skeleton_profile",
+    "vpt_skeleton_destroy",
     "vpt_volume_resample", "vpt_volume_resample_timed",
     "vpt_volume_combine", "vpt_volume_combine_timed", "vpt_volume_compare",
     "vpt_volume_reconstruct", "vpt_volume_geodesic", "vpt_volume_reconstruct_timed", "vpt_volume_geodesic_timed", "vpt_volume_reconstruct_capped",
@@ -139,6 +141,14 @@ RECONSTRUCT_DILATION, RECONSTRUCT_EROSION = 0, 1
 WATERSHED_MINIMA, WATERSHED_MAXIMA = 0, 1
 WATERSHED_PHASES = 3
 THICKNESS_PHASES = 3
+THIN_KERNEL, THIN_ENDS, THIN_ISTHMUS = 0, 1, 2
+THIN_KEPT = 0xFFFFFFFF
+SKELETON_PHASES = 4
+
+
+class SkeletonInfo(C.Structure):
+    """struct vpt_skeleton_info (include/vpt.h)"""
+    _fields_ = [(name, C.c_uint64) for name in ("object_voxels", "kept_voxels", "passes", "converged", "isolated", "ends", "regular", "junctions")]
 
 
 class CombineParams(C.Structure):
@@ -227,6 +237,10 @@ def lib():
         "vpt_distance_thickness": [P, PP],
         "vpt_distance_thickness_timed": [P, PP, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
         "vpt_distance_thickness_capped": [P, I, PP, C.POINTER(C.c_double), C.POINTER(C.c_uint64)],
+        "vpt_volume_skeleton": [P, C.c_uint32, C.c_uint32, I, I, PP], "vpt_volume_skeleton_capped": [P, C.c_uint32, C.c_uint32, I, I, I, PP],
+        "vpt_skeleton_info": [P, C.POINTER(SkeletonInfo)], "vpt_skeleton_burn": [P, I, I, I, I, I, I, P, SZ],
+        "vpt_skeleton_within": [P, C.c_uint32, C.c_uint32, C.c_uint32, PP],
+        "vpt_skeleton_profile": [P, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)], "vpt_skeleton_destroy": [P],
         "vpt_volume_resample": [P, I, I, I, I, PP], "vpt_volume_resample_timed": [P, I, I, I, I, PP, C.POINTER(C.c_double)],
         "vpt_volume_combine": [P, P, C.POINTER(CombineParams), PP], "vpt_volume_combine_timed": [P, P, C.POINTER(CombineParams), PP, C.POINTER(C.c_double)],
         "vpt_volume_compare": [P, P, I, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)],

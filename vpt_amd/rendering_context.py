@@ -11,6 +11,7 @@ from .renderers import RendererFactory
 from .scene import Node, Transform, PerspectiveCamera
 from .tonemappers import ToneMapperFactory
 from .volume import Volume
+from .skeleton import check_skeleton
 from .watershed import check_split
 
 
@@ -83,6 +84,16 @@ class RenderingContext(EventTarget):
                     raise ValueError("thickness mode 'channel' and gradient both write the second channel: name one of them")
                 if self.components is not None and self.components['mode'] == 'label':
                     raise ValueError("thickness mode 'channel' and components mode 'label' both write the second channel: name one of them")
+        # (extension) None | {'lo', 'hi', 'mode': 'ends', 'passes': 0, 'fill': 0}: the volume is replaced by the skeleton of the codes
+        # lo .. hi of an R8 / R16 volume (Volume.skeleton; mode 'kernel' | 'ends' | 'isthmus'): the voxels that survive the thinning keep
+        # their codes, everything else becomes `fill`.  It is applied where `thickness` mode 'within' is; naming it together with
+        # `distance` or `thickness` mode 'within' is refused
+        self.skeleton = check_skeleton(options.get('skeleton'))
+        if self.skeleton is not None:
+            if self.distance is not None and self.distance['mode'] == 'within':
+                raise ValueError("skeleton and distance mode 'within' both replace the volume by a selection of it: name one of them")
+            if self.thickness is not None and self.thickness['mode'] == 'within':
+                raise ValueError("skeleton and thickness mode 'within' both replace the volume by a selection of it: name one of them")
         # (extension) None | {'size': [w, h, d]} | {'spacing': [sx, sy, sz], 'pitch': None}, plus 'mode': 'filtered' | 'nearest': the volume is
         # resampled to that grid, or to cubic voxels of edge `pitch` (None: the smallest spacing), when it is loaded, behind the window and in
         # front of the rank filter: rank, components and distance see the resampled grid.  A volume whose format the mode does not take is
@@ -193,6 +204,14 @@ class RenderingContext(EventTarget):
             if self.thickness is not None and self.thickness['mode'] == 'within' and self._one_channel_unorm(self.volume):
                 spec = self.thickness
                 self._derive_distance(lambda found: found.within(spec['from'], spec['to'], spec['fill']), thickness=True)
+            if self.skeleton is not None and self._one_channel_unorm(self.volume):
+                spec, source = self.skeleton, self.volume
+                found = source.skeleton(spec['lo'], min(spec['hi'], self._largest_code(source)), spec['mode'], spec['passes'])
+                try:
+                    self.volume = found.within(found.KEPT, found.KEPT, min(spec['fill'], self._largest_code(source)))
+                finally:
+                    found.destroy()
+                source.destroy()
             if self.smooth is not None and self._one_channel_unorm(self.volume):
                 source = self.volume
                 self.volume = source.smooth(self.smooth)

@@ -517,6 +517,33 @@ class Volume(EventTarget):
         r2 = check_radius(radius)
         return self._thickness(lo, hi, 'rest', lambda t: t.within(r2 + 1, None, fill))
 
+    # ---- extension: curve skeleton and topological kernel by thinning (include/vpt.h; DESIGN.md "Skeleton") ----
+    def skeleton(self, lo, hi, mode='ends', passes=0, _flags=None):
+        """The burn passes of thinning the codes lo .. hi of this (R8 / R16) volume, as a ``Skeleton`` object, thinned on the device
+        (vpt_amd.skeleton_burn_texels states the contract): mode 'kernel' shrinks every structure to its topological kernel (a ball to a
+        voxel, a torus to a closed curve), 'ends' keeps curve ends (the centreline), 'isthmus' keeps the voxels that once held two parts
+        together; ``passes`` caps the passes (0: to the fixed point).  The object owns what it needs: this volume is not changed and may
+        be destroyed.  ``_flags`` (for tests): the flags of vpt_volume_skeleton_capped (1: no tile cull)."""
+        from .skeleton import check_mode, check_passes, check_range
+        norm16 = self.native_format()[0] in (N.FORMAT_R16, N.FORMAT_RG16, N.FORMAT_R16_SNORM, N.FORMAT_RG16_SNORM)
+        lo, hi = check_range(lo, hi, 65535 if norm16 else 255)
+        code, passes = check_mode(mode), check_passes(passes)
+        h = C.c_void_p()
+        if _flags is None:
+            N.check(N.lib().vpt_volume_skeleton(self.texture, lo, hi, code, passes, C.byref(h)))
+        else:
+            N.check(N.lib().vpt_volume_skeleton_capped(self.texture, lo, hi, code, passes, int(_flags), C.byref(h)))
+        return Skeleton(self, h)
+
+    def centreline(self, lo, hi, mode='ends'):
+        """A new, ready volume like this one in which the voxels of the codes lo .. hi that survive the thinning keep their codes; 0
+        elsewhere (vpt_amd.skeleton_texels states it)"""
+        k = self.skeleton(lo, hi, mode)
+        try:
+            return k.volume()
+        finally:
+            k.destroy()
+
     # ---- extension: resampling to any grid size (include/vpt.h; DESIGN.md "Resampling") ----
     def resample(self, width, height, depth, mode='filtered'):
         """A new, ready volume in this volume's format and with its filter on a grid of width x height x depth texels (each 1 .. 4096) that
@@ -1051,3 +1078,46 @@ class Distance(_VoxelField):
         ms = (C.c_double * N.DISTANCE_PHASES)()
         N.check(N.lib().vpt_distance_profile(self._handle(), ms))
         return dict(zip(('x', 'y', 'z'), ms))
+
+
+class Skeleton(_VoxelField):
+    """The burn passes of a thinning of a value range of a volume (``Volume.skeleton``): one uint32 per voxel on the device, 0 outside the
+    range, k for a voxel deleted in pass k, KEPT for a voxel that survived.  Thin once, select several times.  Outlives the volume it was
+    made from; ``destroy()`` (or ``close()``) frees the device memory."""
+    _noun, _destroy, _read = 'burn passes', 'vpt_skeleton_destroy', 'vpt_skeleton_burn'
+    KEPT = N.THIN_KEPT
+
+    @property
+    def info(self):
+        """{'object_voxels', 'kept_voxels', 'passes', 'converged', 'isolated', 'ends', 'regular', 'junctions'}: the last four count the kept
+        voxels with 0, 1, 2 and >= 3 kept 26-neighbours"""
+        i = N.SkeletonInfo()
+        N.check(N.lib().vpt_skeleton_info(self._handle(), C.byref(i)))
+        return {name: int(getattr(i, name)) for name, _ in N.SkeletonInfo._fields_}
+
+    def burn(self, x=0, y=0, z=0, w=None, h=None, d=None):
+        """uint32 [d][h][w]: the burn passes of a box of voxels (the whole volume by default)"""
+        return self._values(x, y, z, w, h, d)
+
+    def within(self, k_lo=N.THIN_KEPT, k_hi=None, fill=0):
+        """A new, ready volume of the source's size, format and filter: the source's code where k_lo <= burn pass <= k_hi (k_hi None:
+        0xFFFFFFFF), ``fill`` elsewhere (vpt_amd.burn_within_texels states it).  ``within(k)`` is the object after k - 1 passes."""
+        from .skeleton import check_within
+        k_lo, k_hi, fill = check_within(k_lo, k_hi, fill, 65535 if self._norm16 else 255)
+        h = C.c_void_p()
+        N.check(N.lib().vpt_skeleton_within(self._handle(), k_lo, k_hi, fill, C.byref(h)))
+        return self._derived(h)
+
+    def volume(self):
+        """The skeleton as a volume: ``within(KEPT, KEPT, 0)``"""
+        return self.within(N.THIN_KEPT, N.THIN_KEPT, 0)
+
+    def profile(self):
+        """(for measurements) ({'seed', 'border', 'steps', 'census'} in milliseconds, kernel launches, the tiles the sub-step launches
+        worked on, summed)"""
+        ms = (C.c_double * N.SKELETON_PHASES)()
+        launches, tiles = C.c_uint64(0), C.c_uint64(0)
+        N.check(N.lib().vpt_skeleton_profile(self._handle(), ms, C.byref(launches), C.byref(tiles)))
+        return dict(zip(('seed', 'border', 'steps', 'census'), ms)), int(launches.value), int(tiles.value)
+
+    close = _VoxelField.destroy
