@@ -5,7 +5,15 @@ passing vacuously.
 
 Even seeds destroy every volume once no later step reads it, before the result that was made from it is read back; odd seeds keep all
 of them and read two earlier results again at the end.  Every case reads one random sub-box; every second case renders its last volume
-and a volume uploaded from the expected texels with MIP and MCM, NEAREST and LINEAR, and the buffers must be bit-identical.
+and a volume uploaded from the expected texels with MIP and MCM, NEAREST and LINEAR, and the buffers must be bit-identical (a thickness
+pair or a label volume through the 2-D transfer function).
+
+Seeds 0 .. 127 are the chains of the first units, unchanged; seeds 128 .. 223 are drawn by the later rules of volume_chain_cases and put
+geodesic operations, reconstructions, watersheds, splits, rank sets, measurements, thickness and thinning behind each other and behind the
+first units.  Their field handles (basins, components, distances, thickness, skeleton) are made, used once and destroyed like the others.
+A step that carries 'forced' runs twice, plainly and through the unit's test hook (skeleton _flags, thickness_timed _flags,
+reconstruct_timed _tile_rounds, watershed _caps): the forced result must be the statement's and, byte for byte, the plain call's.
+The slowest of the new seeds measured on an MI355X is seed 148 at 0.65 s (the 96 together: 6 s), most of it the statements on the CPU.
 
 VPT_VOLFUZZ_SEEDS=a:b widens the sweep."""
 import os
@@ -14,6 +22,7 @@ import numpy as np
 import pytest
 
 import vpt_amd
+from vpt_amd.distance import check_radius
 from vpt_amd.scene import Transform, Node
 from vpt_amd.synthetic import colour_tf, GoldenRatioRng
 
@@ -58,7 +67,12 @@ def same_texels(got, want, what):
 
 
 def same_scalar(got, want, what):
-    if isinstance(want, np.ndarray):
+    if isinstance(want, np.ndarray) and want.dtype.names:         # the records of a measure: every field of every record
+        got = np.asarray(got)
+        assert got.dtype == want.dtype and got.shape == want.shape, "%s: %s %s, expected %s %s" % (what, got.dtype, got.shape, want.dtype, want.shape)
+        wrong = [(k, name, got[name][k], want[name][k]) for name in want.dtype.names for k in np.flatnonzero(got[name] != want[name])[:1]]
+        assert not wrong, "%s: (record, field, got, want) %r" % (what, wrong[:6])
+    elif isinstance(want, np.ndarray):
         got = np.asarray(got)
         assert got.shape == want.shape and np.array_equal(got.astype(np.int64), want.astype(np.int64)), \
             "%s: %d values differ" % (what, int((got.astype(np.int64) != want.astype(np.int64)).sum()) if got.shape == want.shape else -1)
@@ -95,7 +109,8 @@ class Replay:
         self.destroys = seed % 2 == 0
         self.last_use = {}
         for i, s in enumerate(self.steps):
-            for k in [s['src']] + ([s['kwargs']['b'][1]] if s['kwargs'].get('b', (None,))[0] == 'volume' else []):
+            others = [s['kwargs'].get(key) for key in ('b', 'texels')] if i else []
+            for k in [s['src']] + [other[1] for other in others if other is not None and other[0] == 'volume']:
                 if k is not None:
                     self.last_use[k] = i
 
@@ -108,9 +123,9 @@ class Replay:
                 vol.destroy()
         self.vols, self.extra = [], []
 
-    def second(self, kw):
-        """(the Volume B of a combine / compare, whether this step made it)"""
-        kind, value = kw['b']
+    def second(self, kw, key='b'):
+        """(the Volume B of a combine / compare, the mask, values or texels of a later unit's step; whether this step made it)"""
+        kind, value = kw[key]
         if kind == 'volume':
             return self.vols[value], False
         vol = upload(self.ctx, value)
@@ -122,6 +137,110 @@ class Replay:
         if V.FAMILY[s['op']] == 'components':
             return src.components(kw['lo'], kw['hi'], kw['connectivity'], kw['min_voxels'])
         return src.distance(kw['lo'], kw['hi'], kw['seeds'])
+
+    @staticmethod
+    def selected(f, tail, kw, values):
+        """``tail`` of a Components object: (the new Volume or None, the scalar or None)"""
+        if tail == 'keep':
+            return f.keep(kw['first'], kw['last'], kw['fill']), None
+        if tail == 'label':
+            return f.label(), None
+        if tail == 'keep_set':
+            return f.keep_set(kw['ranks'], kw['fill']), None
+        if tail == 'info':
+            return None, f.info
+        if tail == 'list':
+            return None, f.list(kw['first'], kw['n'])
+        if tail == 'ranks':
+            return None, f.ranks(*kw['box'])
+        return None, f.measure(kw['first'], kw['n'], values, kw['values_channel'])
+
+    def later_once(self, s, hook, others):
+        """a step of the later units, plainly (``hook`` None) or through the hook that forces the unit's slow path; every field handle
+        is made, used once and destroyed"""
+        op, kw, src = s['op'], s['kwargs'], self.vols[s['src']]
+        family = V.FAMILY[op]
+        if op == 'geodesic':
+            return src.geodesic(kw['op'], kw['h'], kw['connectivity'], kw['channel']), None
+        if op == 'reconstruct':
+            args = (others['b'], kw['op'], kw['connectivity'], kw['channel'], kw['mask_channel'])
+            return (src.reconstruct(*args) if hook is None else src.reconstruct_timed(*args, _tile_rounds=hook)[0]), None
+        if op.startswith('basins_') or op.startswith('split_') or op in ('keep_set', 'measure'):
+            if op.startswith('basins_'):
+                f = src.watershed(kw['lo'], kw['hi'], kw['polarity'], kw['connectivity'], kw['min_voxels'], kw['channel'], texels=others.get('texels'), _caps=hook)
+            elif op.startswith('split_'):
+                f = src.split(kw['lo'], kw['hi'], kw['h'], kw['steps'], kw['connectivity'], kw['min_voxels'])
+            else:
+                f = src.components(kw['lo'], kw['hi'], kw['connectivity'], kw['min_voxels'])
+            try:
+                return self.selected(f, op.split('_', 1)[1] if op not in ('keep_set', 'measure') else op, kw, others.get('b'))
+            finally:
+                f.destroy()
+        if family == 'thickness':
+            if hook is None and op == 'thickness':
+                return src.thickness(kw['lo'], kw['hi'], kw['steps'], kw['seeds']), None
+            if hook is None and op == 'open_ball':
+                return src.open_ball(kw['lo'], kw['hi'], kw['radius'], kw['fill']), None
+            d = src.distance(kw['lo'], kw['hi'], kw.get('seeds', 'rest'))
+            try:
+                t = d.thickness() if hook is None else d.thickness_timed(_flags=hook)[0]
+            finally:
+                d.destroy()
+            try:
+                if op in ('thickness', 'thickness_channel'):
+                    return t.channel(kw['steps']), None
+                if op == 'open_ball':
+                    return t.within(check_radius(kw['radius']) + 1, None, kw['fill']), None
+                if op == 'thickness_within':
+                    return t.within(kw['r2_lo'], kw['r2_hi'], kw['fill']), None
+                return None, (t.info if op == 'thickness_info' else t.squared(*kw['box']))
+            finally:
+                t.destroy()
+        assert family == 'skeleton', op
+        if hook is None and op == 'centreline':
+            return src.centreline(kw['lo'], kw['hi'], kw['mode']), None
+        k = src.skeleton(kw['lo'], kw['hi'], kw['mode'], kw.get('passes', 0), _flags=hook)
+        try:
+            if op == 'centreline':
+                return k.volume(), None
+            if op == 'skeleton_within':
+                return k.within(kw['k_lo'], kw['k_hi'], kw['fill']), None
+            return None, (k.info if op == 'skeleton_info' else k.burn(*kw['box']))
+        finally:
+            k.destroy()
+
+    def later(self, i):
+        """step i of the later units; where the case forces the slow path, again through the hook: the same bytes, the same scalar"""
+        s = self.steps[i]
+        others, mine = {}, []
+        try:
+            for key in ('b', 'texels'):
+                if s['kwargs'].get(key) is not None:
+                    others[key], made_here = self.second(s['kwargs'], key)
+                    if made_here:
+                        mine.append(others[key])
+            made, scalar = self.later_once(s, None, others)
+            if s['forced'] is not None:
+                try:
+                    again, scalar_again = self.later_once(s, s['forced'], others)
+                    what = "%s, forced through %r" % (self.what(i), s['forced'])
+                    if again is not None:
+                        try:
+                            same_texels(whole(again), s['expect'], what)
+                            assert whole(again).tobytes() == whole(made).tobytes(), what
+                        finally:
+                            again.destroy()
+                    else:
+                        same_scalar(scalar_again, s['expect'], what)
+                except BaseException:
+                    if made is not None:
+                        made.destroy()
+                    raise
+            return made, scalar
+        finally:
+            for vol in mine:
+                self.extra.remove(vol)
+                vol.destroy()
 
     def call(self, i):
         """run step i: (the new Volume or None, the scalar result or None)"""
@@ -139,7 +258,9 @@ class Replay:
             return src.rank(kw['op'], kw['passes']), None
         if op == 'resample':
             return src.resample(kw['width'], kw['height'], kw['depth'], kw['mode']), None
-        if op in V.FAMILY:                                        # components and distances: made, used once, destroyed
+        if op in V.LATER:
+            return self.later(i)
+        if op in V.FAMILY and op != 'resample':                   # components and distances: made, used once, destroyed
             f = self.field(src, s)
             try:
                 if op == 'keep':

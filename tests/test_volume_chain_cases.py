@@ -1,5 +1,11 @@
 """The drawn volume chains (tests/volume_chain_cases.py) at the default seeds, held to the conditions without which
-tests/test_gpu_volume_chain_fuzz.py could pass while checking little.  No device: numpy and the vpt_amd statements only."""
+tests/test_gpu_volume_chain_fuzz.py could pass while checking little.  No device: numpy and the vpt_amd statements only.
+
+The first tests hold for the whole set.  Those from ``test_the_first_seeds_are_drawn_by_the_first_rules`` on are about the seeds of the
+later rules (128 ..): that the thinning steps make several passes and cross a word and a tile along x, that the thickness steps list more
+centre tiles than one step of the walk takes and hold a ball that reaches past the neighbouring tile, that reconstructions propagate and
+clamp, that watersheds split and a basin crosses tiles, that a block of the measuring kernel holds more ranks than its table has slots, and
+that every forced slow path occurs.  The counts come from each step's 'facts', taken from the statements when the step was drawn."""
 import time
 
 import numpy as np
@@ -16,7 +22,7 @@ PRODUCING = [(seed, i, s) for seed, i, s in STEPS if s['out'] is not None]
 
 def test_generation_is_quick_and_repeats_itself():
     assert GENERATION_SECONDS < 30.0, "%.1f s for %d chains" % (GENERATION_SECONDS, len(SEEDS))
-    for seed in SEEDS[:6]:
+    for seed in SEEDS[:6] + SEEDS[V.LATER_SEEDS:V.LATER_SEEDS + 6]:
         again = V._build(seed)
         assert len(again) == len(CHAINS[seed])
         for a, b in zip(again, CHAINS[seed]):
@@ -82,7 +88,7 @@ def test_every_family_sees_its_tile_edges_on_every_axis():
     for family, tile in V.TILES.items():
         shapes = shapes_of(family)
         for axis, name in ((2, 'x'), (1, 'y'), (0, 'z')):
-            for extent in V.tile_extents(tile[2 - axis]):
+            for extent in V.tile_extents(tile[2 - axis], V.WORD.get((family, name))):
                 if not any(shape[axis] == extent for shape in shapes):
                     missing.append((family, name, extent))
     assert not missing, missing
@@ -132,3 +138,95 @@ def test_a_float_source_holds_the_special_values():
         t = CHAINS[seed][0]['kwargs']['texels']
         finite = t[np.isfinite(t)]
         assert (finite < 0).any() and (finite > 1).any(), seed
+
+
+# ---- the later units: every count below is of the drawn set, taken from the statements when the step was drawn (its 'facts') ------------
+LATER_STEPS = [(seed, i, s) for seed, i, s in STEPS if s['op'] in V.LATER]
+
+
+def facts_of(family):
+    return [s['facts'] for _, _, s in LATER_STEPS if V.FAMILY[s['op']] == family]
+
+
+def test_the_first_seeds_are_drawn_by_the_first_rules():
+    for seed in SEEDS[:V.LATER_SEEDS]:
+        assert all(s['op'] in V.OLD_OPS + ('source',) for s in CHAINS[seed]), seed
+    assert len(SEEDS) % 16 == 0 and SEEDS[0] == 0 and len(SEEDS) > V.LATER_SEEDS
+
+
+def test_a_later_chain_has_two_later_steps_and_one_reads_a_derived_volume():
+    for seed in SEEDS[V.LATER_SEEDS:]:
+        later = [s for s in CHAINS[seed][1:] if s['op'] in V.LATER]
+        assert len(later) >= 2 and any(V._reads_derived(s) for s in later), seed
+        for s in later:
+            if V.FAMILY[s['op']] in V.SLOW_FAMILIES:
+                assert int(np.prod(s['shape'])) <= V.SLOW_VOXELS, (seed, s['op'], s['shape'])
+    # a skeleton, a thickness pair and a reconstruction each stand in front of another derive step
+    for family in ('skeleton', 'thickness', 'reconstruct'):
+        read = 0
+        for seed in SEEDS[V.LATER_SEEDS:]:
+            steps = CHAINS[seed]
+            made = {s['out'] for s in steps[1:] if s['out'] is not None and V.FAMILY.get(s['op']) == family and s['op'] in V.LATER}
+            read += sum(1 for s in steps[1:] if s['out'] is not None and s['src'] in made)
+        assert read >= 10, (family, read)
+
+
+def test_the_thinning_steps_thin():
+    facts = facts_of('skeleton')
+    assert len(facts) >= 20
+    assert 2 * sum(f['passes'] >= 3 for f in facts) >= len(facts)
+    assert 2 * sum(0 < f['kept_voxels'] < f['object_voxels'] for f in facts) >= len(facts)
+    assert sum(f['both_tiles'] for f in facts) >= 3
+    wide = {s['facts']['mode'] for _, _, s in LATER_STEPS if V.FAMILY[s['op']] == 'skeleton' and s['shape'][2] > 32}
+    assert wide == set(V.SKELETON_MODES), wide
+
+
+def test_the_thickness_steps_walk_and_reach():
+    facts = facts_of('thickness')
+    assert len(facts) >= 20
+    assert 2 * sum(f['differs_from_distance'] for f in facts) >= len(facts)
+    assert sum(f['centre_tiles'] > 64 for f in facts) >= 2 and sum(f['centre_tiles'] > 128 for f in facts) >= 1      # a second and a third step of the walk
+    assert sum(f['largest_in_a_tile'] > 64 for f in facts) >= 1                                                  # a ball past the neighbouring tile
+    for key in ('seeds', 'steps'):
+        assert len({s['kwargs'][key] for _, _, s in LATER_STEPS if s['op'] == 'thickness'}) == {'seeds': 2, 'steps': 4}[key], key
+
+
+def test_the_reconstructions_propagate():
+    facts = [s['facts'] for _, _, s in LATER_STEPS if s['op'] == 'reconstruct']
+    assert len(facts) >= 10
+    assert 2 * sum(f['differs_from_both'] for f in facts) >= len(facts), (sum(f['differs_from_both'] for f in facts), len(facts))
+    assert sum(f['marker_not_under_mask'] for f in facts) >= 3
+    assert {s['b_source'] for _, _, s in LATER_STEPS if s['op'] == 'reconstruct'} == set(V.B_SOURCES[:4])
+    geodesic = [s for _, _, s in LATER_STEPS if s['op'] == 'geodesic' and s['sub'] in V.TAKES_H]
+    assert any(s['kwargs']['h'] == 0 for s in geodesic) and any(s['facts']['h_above_range'] for s in geodesic)
+    assert {s['kwargs']['channel'] for _, _, s in LATER_STEPS if s['op'] == 'geodesic'} == {0, 1}
+
+
+def test_the_watersheds_split():
+    steps = [s for _, _, s in LATER_STEPS if s['op'].startswith('basins_')]
+    assert len(steps) >= 20
+    assert 2 * sum(s['facts']['listed'] >= 2 for s in steps) >= len(steps)
+    assert sum(s['facts']['spans_tiles'] for s in steps) >= 3
+    assert {s['kwargs']['polarity'] for s in steps} == {'minima', 'maxima'}
+    assert sum(s['kwargs']['texels'] is not None for s in steps) >= 3
+    assert any(s['kwargs']['texels'] is not None and s['kwargs']['texels'][0] == 'volume' for s in steps)
+    assert {s['kwargs']['channel'] for s in steps} == {0, 1}
+
+
+def test_the_measuring_table_overflows_and_values_are_derived():
+    steps = [s for _, _, s in LATER_STEPS if s['op'] in ('measure', 'basins_measure')]
+    assert any(s['facts']['block_ranks'] > 512 for s in steps), max(s['facts']['block_ranks'] for s in steps)       # MS_SLOTS
+    assert any(s['facts'].get('values_of_a_derived_pair') for s in steps)
+    assert any(s['kwargs']['b'] is None for s in steps) and any(s['kwargs']['first'] > 0 for s in steps) and any(s['kwargs']['n'] is not None for s in steps)
+    sets = [s['kwargs']['ranks'] for _, _, s in LATER_STEPS if s['op'] in ('keep_set', 'basins_keep_set')]
+    assert any(isinstance(r, np.ndarray) for r in sets)
+    lists = [r for r in sets if isinstance(r, tuple) and r]
+    assert any(len(set(r)) < len(r) for r in lists) and any(max(r) > (1 << 32) for r in lists)
+
+
+def test_every_forced_slow_path_occurs_three_times():
+    count = {(family, hook): 0 for family, hooks in V.FORCED.items() for hook in hooks}
+    for _, _, s in LATER_STEPS:
+        if s['forced'] is not None:
+            count[(V.FAMILY[s['op']], s['forced'])] += 1
+    assert all(n >= 3 for n in count.values()), count

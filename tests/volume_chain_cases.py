@@ -11,7 +11,9 @@ _native): the cases of tests/test_gpu_volume_chain_fuzz.py; tests/test_volume_ch
   expect   the statement's result: the texels of volume ``out`` (upload_block: of volume ``src`` from then on), or the scalar result
   shape    (depth, height, width) of the volume the kernels of the step run over (resample: the target grid)
   format   the format of volume ``src``
-  b_source for combine / compare: where B comes from (B_SOURCES)
+  b_source for combine / compare, and the mask of a reconstruct and the values of a measure: where B comes from (B_SOURCES)
+  facts    (steps of the later units) what the statements said of the step when it was drawn
+  forced   (steps of the later units) None, or the value of the hook through which the step runs a second time
 
 How a case is drawn.  Every sixteenth seed is one voxel.  The next PLANNED seeds take their shape from PLANS, which walks each kernel
 family's tile extents (1, one below the tile, the tile, one above, two tiles plus one on every axis), and begin with that family's
@@ -20,7 +22,27 @@ be smoothed.  Every other seed draws each axis from the three pools (1 .. 9; 1 .
 Steps: 3 .. 6; a step is upload_block with probability 0.25 (never first, last or twice in a row), a scalar with 0.25, a volume-producing operation otherwise, uniform among
 the entries legal for the current format, the entries the chain has not used yet first; each seed also has three wishes, taken by turns
 from the whole entry list, that go first where they are legal.  48 seeds did not reach every entry three times; the default 128 do.  A volume-producing step whose
-expected texels are constant is drawn again, up to 8 times (constancy cascades: every later step would see a constant volume)."""
+expected texels are constant is drawn again, up to 8 times (constancy cascades: every later step would see a constant volume).
+
+Seeds 0 .. 127 are drawn by these rules from the entries of the first units (OLD_ENTRIES) and are, chain for chain and byte for byte, what
+they were before the later units (LATER: geodesic, reconstruct, watershed, split, keep_set, measure, thickness, skeleton) joined.
+
+Seeds from LATER_SEEDS = 128 on are drawn by the later rules (``_draw_later_chain``).  A source is R8, R16, RG8 or RG16, one voxel every
+sixteenth seed; the next len(LATER_PLANS) seeds take shape, first entries and style from LATER_PLANS (the tile extents of the later
+kernel families, 31 / 32 / 33 for the words of the skeleton's bit planes, and the shapes the conditions name); the others draw their axes
+as above under 20 000 voxels (every third: 40 000) and a style among noise, sphere, sparse and blobs (smoothed noise).  A step is
+upload_block with probability 0.2, a scalar with 0.25, else volume-producing; three times in four it is an entry of the later units, else
+one of the first; the first step makes a volume; wishes run over LATER_ENTRIES.  A thinning or thickness step is legal up to SLOW_VOXELS
+voxels only (their statements take seconds beyond).  The mask of a reconstruct, the values of a measure and the ``texels`` of a watershed
+are second volumes drawn as B is (fresh, earlier, self, a channel of a two-channel volume).  A chain must hold two steps of the later
+units, one of which reads a volume a derive step made, else it is drawn again from the seed's next stream.  Every fourth seed (seed % 4
+== 3) forces the slow paths: its steps of the families of FORCED carry 'forced', the hook's value, and run plainly and through the hook.
+A later step carries 'facts': what the statements said of it when it was drawn (passes, basins, centre tiles ...), for the conditions.
+
+DEFAULT_SEEDS ends at 224: the smallest multiple of 16 at which every condition of tests/test_volume_chain_cases.py holds.  The last to
+come are every (format, entry) pair (RG8 basins_label first occurs in 208 .. 223), a labelling with more than 512 ranks in one block
+of the measuring kernel together with values from a derived pair's second channel (192 .. 207), and three steps of every forced hook
+(reconstruct's: 192 .. 207)."""
 import functools
 
 import numpy as np
@@ -28,16 +50,23 @@ import numpy as np
 import vpt_amd
 from vpt_amd.combine import combine_texels, compare_stats
 from vpt_amd.components import components_texels, keep_texels, label_texels
-from vpt_amd.distance import distance_squared_texels, within_texels, channel_texels
+from vpt_amd.distance import (distance_squared_texels, within_texels, channel_texels, thickness_squared_texels, thickness_texels, open_ball_texels,
+                              check_radius)
 from vpt_amd.gradient import gradient_magnitude
 from vpt_amd.pyramid import reduce_texels, smooth_texels
+from vpt_amd.measure import measure_texels, keep_set_texels
 from vpt_amd.rank import rank_texels, OPERATORS as RANK_OPERATORS
+from vpt_amd.reconstruct import geodesic_texels, reconstruct_texels, GEODESIC_OPS, RECONSTRUCT_OPS, TAKES_H
 from vpt_amd.resample import resample_texels
+from vpt_amd.skeleton import skeleton_burn_texels, burn_within_texels, skeleton_texels, KEPT, MODES as SKELETON_MODES
+from vpt_amd.watershed import watershed_texels, split_texels
 from vpt_amd.window import window_texels, percentile_window
 
 CONSTANT = 20261019
-DEFAULT_SEEDS = (0, 128)
+DEFAULT_SEEDS = (0, 224)
+LATER_SEEDS = 128                                      # the first seed drawn by the later rules (module docstring)
 MAX_VOXELS = 100000
+SLOW_VOXELS = 20000                                    # the thinning and thickness statements: seconds beyond (tests/test_gpu_thickness_fuzz.py's cap)
 MAX_ROW_PASS = 400000                                  # resample: target width x source height x source depth (the row pass's workspace)
 REDRAWS = 8
 
@@ -59,24 +88,51 @@ LEGAL = {
     'range': _ONE, 'histogram': _UNORM, 'code_histogram': _INT1, 'percentile_window': _INT1, 'compare': _U1,
     'components_info': _U1, 'components_list': _U1, 'components_ranks': _U1, 'distance_info': _U1, 'distance_squared': _U1,
 }
+OLD_OPS = tuple(LEGAL)
+# the later units: reconstruction, watershed, measurements, thickness, skeleton
+LATER = {
+    'geodesic': _UNORM, 'reconstruct': _UNORM,         # sub: the operation; the mask of a reconstruct: a B source of the marker's width
+    'basins_keep': _UNORM, 'basins_label': _UNORM, 'basins_keep_set': _UNORM,      # Volume.watershed(...) -> Components.keep / .label / .keep_set
+    'split_keep': _U1, 'split_label': _U1,             # Volume.split(...) -> Components.keep / .label
+    'keep_set': _U1,                                   # Volume.components(...) -> Components.keep_set
+    'thickness': _U1, 'open_ball': _U1,
+    'thickness_within': _U1, 'thickness_channel': _U1,      # Volume.distance(...) -> Distance.thickness() -> .within / .channel
+    'centreline': _U1, 'skeleton_within': _U1,         # sub of centreline: the mode; Volume.skeleton(...) -> Skeleton.within
+    'basins_info': _UNORM, 'basins_list': _UNORM, 'basins_ranks': _UNORM, 'measure': _U1, 'basins_measure': _UNORM,
+    'thickness_squared': _U1, 'thickness_info': _U1, 'skeleton_burn': _U1, 'skeleton_info': _U1,
+}
+LEGAL.update(LATER)
 RESAMPLE_FILTERED = _UNORM
 COMBINE_OPS = ('mask', 'min', 'max', 'absdiff', 'blend', 'pair')
 SCALAR_OPS = ('range', 'histogram', 'code_histogram', 'percentile_window', 'compare', 'components_info', 'components_list',
               'components_ranks', 'distance_info', 'distance_squared')
+LATER_SCALAR_OPS = ('basins_info', 'basins_list', 'basins_ranks', 'measure', 'basins_measure', 'thickness_squared', 'thickness_info',
+                    'skeleton_burn', 'skeleton_info')
 B_SOURCES = ('fresh', 'earlier', 'self', 'rg_channel', 'other_width')
+SUBS = {'rank': tuple(RANK_OPERATORS), 'combine': COMBINE_OPS, 'geodesic': tuple(GEODESIC_OPS), 'reconstruct': tuple(RECONSTRUCT_OPS),
+        'centreline': tuple(SKELETON_MODES)}
+# the hooks that force a unit's slow path (include/vpt.h "(for tests)"), by the step's family: the step runs plainly and forced
+FORCED = {'skeleton': (1,), 'thickness': (1, 2, 3), 'reconstruct': (1,), 'watershed': ((3, 1, 1),)}
+UNHOOKED = ('geodesic', 'split_keep', 'split_label')    # of those families, the public methods without a hook
 
 
 def _entries(ops):
     out = []
     for op in ops:
-        subs = RANK_OPERATORS if op == 'rank' else COMBINE_OPS if op == 'combine' else (None,)
-        out += [(op, sub) for sub in subs]
+        out += [(op, sub) for sub in SUBS.get(op, (None,))]
     return out
 
 
-VOLUME_ENTRIES = _entries(op for op in LEGAL if op not in SCALAR_OPS and op != 'upload_block')
-SCALAR_ENTRIES = _entries(SCALAR_OPS)
-ENTRIES = VOLUME_ENTRIES + SCALAR_ENTRIES + [('upload_block', None)]
+# the entries seeds 0 .. 127 are drawn from: those chains stay what they were before the later units joined
+OLD_VOLUME_ENTRIES = _entries(op for op in OLD_OPS if op not in SCALAR_OPS and op != 'upload_block')
+OLD_SCALAR_ENTRIES = _entries(SCALAR_OPS)
+OLD_ENTRIES = OLD_VOLUME_ENTRIES + OLD_SCALAR_ENTRIES + [('upload_block', None)]
+LATER_VOLUME_ENTRIES = _entries(op for op in LATER if op not in LATER_SCALAR_OPS)
+LATER_SCALAR_ENTRIES = _entries(LATER_SCALAR_OPS)
+LATER_ENTRIES = LATER_VOLUME_ENTRIES + LATER_SCALAR_ENTRIES
+VOLUME_ENTRIES = OLD_VOLUME_ENTRIES + LATER_VOLUME_ENTRIES
+SCALAR_ENTRIES = OLD_SCALAR_ENTRIES + LATER_SCALAR_ENTRIES
+ENTRIES = OLD_ENTRIES + LATER_ENTRIES
 
 # kernel family -> the extents (x, y, z) of its tile; None: the kernel has no tile along that axis
 TILES = {
@@ -86,18 +142,36 @@ TILES = {
     'components': (64, 8, 4),                          # CC_TX, CC_TY, CC_TZ (vpt_volume_components.hip)
     'distance': (64, None, None),                      # the 64-voxel row segments of k_edt_x (vpt_volume_distance.hip); y and z are marched whole
     'resample': (64, 4, None),                         # k_resample_yz: 64 columns x 4 rows of the TARGET grid a workgroup, one plane each
+    'reconstruct': (64, 8, 4),                         # RC_TX, RC_TY, RC_TZ (vpt_volume_reconstruct.hip)
+    'watershed': (64, 8, 4),                           # the plateau kernel's tile and the labelling's (vpt_volume_watershed.hip)
+    'skeleton': (64, 8, 4),                            # SK_TX, SK_TY, SK_TZ; a word of a bit plane is 32 voxels of a row (vpt_volume_skeleton.hip)
+    'measure': (64, 8, 8),                             # the block of one MS_SLOTS table (vpt_volume_measure.hip)
+    'thickness': (8, 8, 4),                            # TH_TX, TH_TY, TH_TZ (vpt_volume_thickness.hip)
 }
 FAMILY = {'derive_gradient': 'gradient', 'smooth': 'smooth', 'rank': 'rank', 'keep': 'components', 'label': 'components',
           'components_info': 'components', 'components_list': 'components', 'components_ranks': 'components', 'within': 'distance',
-          'channel': 'distance', 'distance_info': 'distance', 'distance_squared': 'distance', 'resample': 'resample'}
+          'channel': 'distance', 'distance_info': 'distance', 'distance_squared': 'distance', 'resample': 'resample',
+          'geodesic': 'reconstruct', 'reconstruct': 'reconstruct', 'basins_keep': 'watershed', 'basins_label': 'watershed',
+          'basins_keep_set': 'watershed', 'basins_info': 'watershed', 'basins_list': 'watershed', 'basins_ranks': 'watershed',
+          'split_keep': 'watershed', 'split_label': 'watershed', 'keep_set': 'components', 'measure': 'measure', 'basins_measure': 'measure',
+          'thickness': 'thickness', 'open_ball': 'thickness', 'thickness_within': 'thickness', 'thickness_channel': 'thickness',
+          'thickness_squared': 'thickness', 'thickness_info': 'thickness', 'centreline': 'skeleton', 'skeleton_within': 'skeleton',
+          'skeleton_burn': 'skeleton', 'skeleton_info': 'skeleton'}
+SLOW_FAMILIES = ('thickness', 'skeleton')              # at most SLOW_VOXELS voxels a step
 # the kernels with a vector form and a texel-by-texel form, chosen by the row length: nx % 4 (gradient, smooth, rank: ALIGNED), the row's
 # bytes % 32 (k_reduce); window and combine go by 16-byte groups of the whole volume
 VECTOR_FAMILIES = ('gradient', 'smooth', 'rank')
 
 
-def tile_extents(tile):
-    """the extents an axis with this tile must be seen at"""
-    return (1,) if tile is None else (1, tile - 1, tile, tile + 1, 2 * tile + 1)
+def tile_extents(tile, word=None):
+    """the extents an axis with this tile must be seen at; ``word``: the voxels of a machine word along the axis (the skeleton's bit
+    planes along x: 32), seen at one below, at and one above it as well"""
+    if tile is None:
+        return (1,)
+    return (1, tile - 1, tile, tile + 1, 2 * tile + 1) + ((word - 1, word, word + 1) if word else ())
+
+
+WORD = {('skeleton', 'x'): 32}                         # (family, axis) -> the ``word`` of tile_extents
 
 
 EDGES = (1, 15, 16, 17, 31, 32, 33, 63, 64, 65, 127, 128, 129, 130, 132, 133, 255, 256, 257, 260)
@@ -125,6 +199,45 @@ def _plans():
 
 PLANS = _plans()
 PLANNED = len(PLANS)
+
+
+def _later_plans():
+    """[(shape, the entries the chain begins with, the source's style)] of the seeds from LATER_SEEDS on: per tile geometry of the later
+    units five shapes rotated as in ``_plans``, each beginning with one entry of every family of the geometry (so every family sees every
+    extent), the skeleton's word extents, and the shapes the conditions of tests/test_volume_chain_cases.py name: 129 x 17 x 9, the
+    largest a thinning or thickness step takes (153 thickness tiles, three skeleton tiles along x), 27^3 (a ball deeper than a
+    thickness tile is wide) and two tiles of noise for the measuring table"""
+    plans = []
+    reconstruct = [('reconstruct', 'dilation'), ('geodesic', 'hmax'), ('reconstruct', 'erosion'), ('geodesic', 'fill_holes'), ('geodesic', 'dome')]
+    watershed = [('basins_keep', None), ('basins_ranks', None), ('basins_keep_set', None), ('split_keep', None), ('basins_list', None)]
+    skeleton = [('centreline', 'ends'), ('skeleton_within', None), ('centreline', 'kernel'), ('skeleton_burn', None), ('centreline', 'isthmus')]
+    thickness = [('thickness', None), ('open_ball', None), ('thickness_within', None), ('thickness_channel', None), ('thickness_squared', None)]
+    measure = [('basins_measure', None), ('measure', None)]
+
+    def walk(family, begins, styles):
+        tx, ty, tz = TILES[family]
+        xs, ys, zs = tile_extents(tx), tile_extents(ty), tile_extents(tz)
+        for k in range(5):
+            shape = (zs[(k + 2) % 5], ys[(k + 1) % 5], xs[k])
+            begin = [b[k % len(b)] for b in begins]
+            plans.append((shape, begin[k % len(begin):] + begin[:k % len(begin)], styles[k % len(styles)]))
+
+    walk('skeleton', (skeleton, reconstruct, watershed), ('blobs', 'noise', 'sphere'))
+    for shape, k in (((5, 9, 31), 0), ((4, 7, 32), 2), ((9, 8, 33), 4)):             # the word of the skeleton's bit planes
+        plans.append((shape, [skeleton[k], thickness[k], skeleton[1]], 'blobs'))
+    walk('measure', (measure, measure[::-1], [('keep_set', None)] * 5), ('noise',))
+    walk('thickness', (thickness, thickness[2:] + thickness[:2], [('thickness_info', None)] * 5), ('blobs', 'noise', 'sphere'))
+    plans.append(((9, 17, 129), [('thickness_squared', None), ('skeleton_burn', None), ('basins_keep', None)], 'noise'))
+    plans.append(((9, 17, 129), [('thickness', None), ('centreline', 'ends'), ('basins_measure', None)], 'blobs'))
+    plans.append(((5, 17, 129), [('skeleton_within', None), ('thickness_channel', None), ('geodesic', 'maxima')], 'blobs'))
+    plans.append(((27, 27, 27), [('thickness_within', None), ('open_ball', None), ('centreline', 'kernel')], 'sphere'))
+    plans.append(((17, 17, 129), [('basins_label', None), ('basins_measure', None), ('measure', None)], 'noise'))
+    for shape, _, _ in plans:
+        assert shape[0] * shape[1] * shape[2] <= MAX_VOXELS
+    return plans
+
+
+LATER_PLANS = _later_plans()
 
 
 # ---- texels --------------------------------------------------------------------------------------------------------------------
@@ -166,6 +279,12 @@ def draw_texels(rng, fmt, shape, style=None, specials=False):
     elif style == 'sphere':
         base = _sphere(shape).reshape(tuple(shape) + (1,) * (len(full) - 3))
         v = info.min + base * (info.max - info.min) + rng.normal(0, 0.06 * (info.max - info.min), full)
+    elif style == 'blobs':                                        # (asked for by name only) noise averaged over 3 x 3 x 3 boxes twice, over every code
+        v = rng.random(full)
+        for _ in range(2):
+            p = np.pad(v, [(1, 1)] * 3 + [(0, 0)] * (len(full) - 3), mode='edge')
+            v = sum(p[dz:dz + shape[0], dy:dy + shape[1], dx:dx + shape[2]] for dz in range(3) for dy in range(3) for dx in range(3)) / 27.0
+        v = info.min + (v - v.min()) / max(float(v.max() - v.min()), 1e-9) * (info.max - info.min)
     else:
         background = 0 if info.min == 0 else int(info.min)        # SNORM: the most negative code, which storage reads as the one above it
         v = np.where(rng.random(full) < 0.7, background, rng.integers(info.min, info.max + 1, size=full))
@@ -224,6 +343,7 @@ class _Chain:
         self.steps = []
         self.texels = []                                          # the expected texels of every volume, as they are now
         self.used = set()
+        self.fine = False                                         # (later plans) measure everything over a watershed of noise
 
     def add_volume(self, texels):
         self.texels.append(texels)
@@ -436,6 +556,242 @@ def _draw_step(c, cur, entry):
     return step, made
 
 
+# ---- the later units: geodesic, reconstruct, watershed, measure, thickness, skeleton -------------------------------------------------
+def _channel_of(texels, channel):
+    return texels[..., channel] if texels.ndim == 4 else texels
+
+
+def _draw_other(c, cur, formats, kinds=B_SOURCES[:4]):
+    """(kind, ('volume', index) | ('fresh', texels), channel, the texels) of a second volume on the grid of volume ``cur`` in one of
+    ``formats``: the mask of a reconstruct, the values of a measure, the texels of a watershed.  A two-channel volume of the grid that
+    the chain made (a thickness pair, a label or depth channel) is taken half of the times there is one."""
+    rng = c.rng
+    grid = c.texels[cur].shape[:3]
+    kind = kinds[int(rng.integers(len(kinds)))]
+    found = [k for k in c.same_grid(cur, formats) if k != cur]
+    two = [k for k in c.same_grid(cur, formats) if c.texels[k].ndim == 4]
+    if two and 'rg_channel' in kinds and rng.random() < 0.5:
+        kind = 'rg_channel'
+    if (kind == 'self' and format_of(c.texels[cur]) not in formats) or (kind == 'earlier' and not found):
+        kind = 'fresh'
+    if kind == 'self' or (kind == 'earlier') or (kind == 'rg_channel' and two):
+        pool = [cur] if kind == 'self' else found if kind == 'earlier' else two
+        k = pool[int(rng.integers(len(pool)))]
+        b = c.texels[k]
+        return kind, ('volume', k), (int(rng.integers(2)) if b.ndim == 4 else 0), b
+    fmts = [f for f in formats if FORMATS[f][1] == 2] if kind == 'rg_channel' else list(formats)
+    b = draw_texels(rng, fmts[int(rng.integers(len(fmts)))], grid)
+    return kind, ('fresh', b), (int(rng.integers(2)) if b.ndim == 4 else 0), b
+
+
+def _draw_selection(rng, listed):
+    """the ``ranks`` of a keep_set: a boolean array over the list, or ranks with a duplicate and ranks beyond the list"""
+    if rng.random() < 0.35:
+        return rng.random(listed) < 0.5
+    ranks = [int(r) for r in rng.integers(1, min(listed, 40) + 3, size=int(rng.integers(0, 25)))]
+    if ranks:
+        ranks += [ranks[0], listed + 1, (1 << 40) + 7]
+    return tuple(ranks)
+
+
+def _object_range(rng, one):
+    """(lo, hi) of a structure to thin or to measure: most of the times everything from a quantile up (a solid: several passes, balls
+    deeper than a voxel), else everything up to a quantile, else two quantiles"""
+    M = int(np.iinfo(one.dtype).max)
+    flat = np.sort(one.reshape(-1))
+    roll = rng.random()
+    if roll < 0.6:
+        return max(int(flat[int(rng.uniform(0.2, 0.6) * (flat.size - 1))]), 1), M
+    if roll < 0.75:
+        return 0, min(int(flat[int(rng.uniform(0.4, 0.8) * (flat.size - 1))]), M - 1)
+    return _quantiles(rng, one)
+
+
+def _tiles_of(shape, tile):
+    """int64 [depth][height][width]: the number of the (tx, ty, tz) tile every voxel lies in"""
+    d, h, w = shape
+    tx, ty, tz = tile
+    z, y, x = np.arange(d) // tz, np.arange(h) // ty, np.arange(w) // tx
+    return (z[:, None, None] * (int(y[-1]) + 1) + y[None, :, None]) * (int(x[-1]) + 1) + x[None, None, :]
+
+
+def _rank_facts(ranks, listed):
+    """what the conditions ask of a labelling: the number of structures listed, whether one has voxels in two tiles of the labelling
+    kernels, the largest number of distinct ranks in one block of the measuring kernel"""
+    top = int(ranks.max()) + 1
+    inside = ranks > 0
+    pairs = np.unique(_tiles_of(ranks.shape, TILES['watershed'])[inside] * top + ranks[inside].astype(np.int64))
+    spans = bool(len(pairs) and np.bincount(pairs % top).max() > 1)
+    pairs = np.unique(_tiles_of(ranks.shape, TILES['measure'])[inside] * top + ranks[inside].astype(np.int64))
+    return {'listed': len(listed), 'spans_tiles': spans, 'block_ranks': int(np.bincount(pairs // top).max()) if len(pairs) else 0}
+
+
+def _draw_later_step(c, cur, entry):
+    """``_draw_step`` for the entries of the later units; the step carries 'facts', what tests/test_volume_chain_cases.py asks of it"""
+    rng, (op, sub) = c.rng, entry
+    a = c.texels[cur]
+    fmt = format_of(a)
+    M = int(np.iinfo(a.dtype).max)
+    narrow = ('R8', 'RG8') if a.dtype == np.uint8 else ('R16', 'RG16')
+    grid = a.shape[:3]
+    kw, made, expect, b_source, facts = {}, None, None, None, {}
+    fill = lambda: int(rng.integers(0, M + 1)) if rng.random() < 0.5 else 0
+    connectivity = lambda: (6, 18, 26)[int(rng.integers(3))]
+    if op == 'geodesic':
+        channel = int(rng.integers(2)) if a.ndim == 4 else 0
+        one = _channel_of(a, channel)
+        h = 0
+        if sub in TAKES_H:
+            spread = int(one.max()) - int(one.min())
+            roll = rng.random()
+            h = 0 if roll < 0.2 else min(spread + 1 + int(rng.integers(3)), M) if roll < 0.4 else int(rng.integers(1, max(spread, 1) + 1))
+        kw = {'op': sub, 'h': h, 'connectivity': connectivity(), 'channel': channel}
+        made = geodesic_texels(a, sub, h, kw['connectivity'], channel)
+        facts = {'h_above_range': sub in TAKES_H and h > int(one.max()) - int(one.min())}
+    elif op == 'reconstruct':
+        b_source, b, mask_channel, mask = _draw_other(c, cur, narrow, ('fresh',) * 4 + ('earlier',) * 2 + ('self', 'rg_channel'))
+        channel = int(rng.integers(2)) if a.ndim == 4 else 0
+        kw = {'b': b, 'op': sub, 'connectivity': connectivity(), 'channel': channel, 'mask_channel': mask_channel}
+        made = reconstruct_texels(a, mask, sub, kw['connectivity'], channel, mask_channel)
+        marker, under = _channel_of(a, channel), _channel_of(mask, mask_channel)
+        facts = {'differs_from_both': bool((made != marker).any() and (made != under).any()),
+                 'marker_not_under_mask': bool((marker < under).any() if sub == 'erosion' else (marker > under).any())}
+    elif op.startswith('basins_'):
+        channel = int(rng.integers(2)) if a.ndim == 4 else 0
+        relief = _channel_of(a, channel)
+        lo, hi = (0, M) if rng.random() < 0.5 else _quantiles(rng, relief)
+        kw = {'lo': lo, 'hi': hi, 'polarity': ('minima', 'maxima')[int(rng.integers(2))], 'connectivity': connectivity(),
+              'min_voxels': (1, 1, 2, 5, 40)[int(rng.integers(5))], 'channel': channel, 'texels': None}
+        if c.fine and op == 'basins_measure':                     # every face-connected dip of the noise is a basin: hundreds a block
+            channel, relief, lo, hi = 0, _channel_of(a, 0), 0, M
+            kw.update({'lo': 0, 'hi': M, 'connectivity': 6, 'min_voxels': 1, 'channel': 0})
+        emitted = relief
+        if rng.random() < 0.35:                                   # what the emitters speak of: another volume of the relief's width
+            _, kw['texels'], _, emitted = _draw_other(c, cur, narrow[:1], ('fresh', 'earlier'))
+        ranks, listed = watershed_texels(a, lo, hi, kw['polarity'], kw['connectivity'], kw['min_voxels'], channel)
+        facts = _rank_facts(ranks, listed)
+        made, expect = _draw_selected(c, cur, op[len('basins_'):], kw, emitted, ranks, listed, facts,
+                                      lambda: watershed_texels(a, lo, hi, kw['polarity'], kw['connectivity'], 1, channel)[1],
+                                      int(np.count_nonzero((relief >= lo) & (relief <= hi))))
+        b_source = kw.pop('b_source', None)
+    elif op in ('split_keep', 'split_label'):
+        lo, hi = _object_range(rng, a)
+        kw = {'lo': lo, 'hi': hi, 'h': (0, 1, 2, 5)[int(rng.integers(4))], 'steps': (1, 2, 4)[int(rng.integers(3))], 'connectivity': connectivity(),
+              'min_voxels': (1, 1, 2, 5)[int(rng.integers(4))]}
+        ranks, listed = split_texels(a, **kw)
+        facts = _rank_facts(ranks, listed)
+        made, expect = _draw_selected(c, cur, op[len('split_'):], kw, a, ranks, listed, facts, None, None)
+    elif op in ('keep_set', 'measure'):
+        lo, hi = _field_args(c, a)
+        kw = {'lo': lo, 'hi': hi, 'connectivity': connectivity(), 'min_voxels': (1, 1, 2, 5, 40)[int(rng.integers(5))]}
+        ranks, listed = components_texels(a, **kw)
+        facts = _rank_facts(ranks, listed)
+        made, expect = _draw_selected(c, cur, op, kw, a, ranks, listed, facts, None, None)
+        b_source = kw.pop('b_source', None)
+    elif FAMILY[op] == 'thickness':
+        lo, hi = _object_range(rng, a)
+        seeds = 'rest' if op == 'open_ball' or rng.random() < 0.7 else 'range'      # open_ball is of the structure
+        kw = {'lo': lo, 'hi': hi, 'seeds': seeds}
+        d2 = distance_squared_texels(a, lo, hi, seeds)
+        t2 = thickness_squared_texels(d2)
+        centres = (d2 > 0) & (d2 != 0xFFFFFFFF)
+        tiles = _tiles_of(grid, TILES['thickness'])
+        facts = {'differs_from_distance': bool((t2 != d2).any()), 'centre_tiles': len(np.unique(tiles[centres])),
+                 'largest_in_a_tile': int(d2[centres].max()) if centres.any() else 0}
+        largest = int(t2[t2 != 0xFFFFFFFF].max()) if (t2 != 0xFFFFFFFF).any() else 0
+        if op == 'thickness':
+            kw['steps'] = int(rng.integers(1, 5))
+            made = channel_texels(a, t2, kw['steps'])
+            assert a.size > 4096 or made.tobytes() == thickness_texels(a, lo, hi, kw['steps'], seeds).tobytes()
+        elif op == 'open_ball':
+            kw = {'lo': lo, 'hi': hi, 'radius': float(np.round(rng.uniform(0, 1.2 * np.sqrt(largest) + 0.5), 2)), 'fill': fill()}
+            made = within_texels(a, t2, check_radius(kw['radius']) + 1, None, kw['fill'])
+            assert a.size > 4096 or made.tobytes() == open_ball_texels(a, **kw).tobytes()
+        elif op == 'thickness_within':
+            r2_lo = int(rng.integers(0, largest + 1)) if rng.random() < 0.6 else 0
+            sel = {'r2_lo': r2_lo, 'r2_hi': None if rng.random() < 0.3 else int(rng.integers(r2_lo, largest + 2)), 'fill': fill()}
+            made = within_texels(a, t2, **sel)
+            kw.update(sel)
+        elif op == 'thickness_channel':
+            kw['steps'] = (1, 2, 7, 256)[int(rng.integers(4))]
+            made = channel_texels(a, t2, kw['steps'])
+        elif op == 'thickness_info':
+            expect = {'seeds': int(np.count_nonzero(d2 == 0)), 'largest': largest}
+        else:
+            x, y, z, w, h, d = kw['box'] = _box(rng, grid)
+            expect = np.ascontiguousarray(t2[z:z + d, y:y + h, x:x + w])
+    elif FAMILY[op] == 'skeleton':
+        lo, hi = _object_range(rng, a)
+        mode = sub if op == 'centreline' else tuple(SKELETON_MODES)[int(rng.integers(3))]
+        passes = 0 if op == 'centreline' or rng.random() < 0.5 else int(rng.integers(1, 5))
+        kw = {'lo': lo, 'hi': hi, 'mode': mode}
+        burn, info = skeleton_burn_texels(a, lo, hi, mode, passes)
+        inside = (a >= lo) & (a <= hi)
+        facts = dict(info, mode=mode, both_tiles=bool(grid[2] > 64 and inside[:, :, :64].any() and inside[:, :, 64:].any()))
+        if op == 'centreline':
+            made = burn_within_texels(a, burn, KEPT, KEPT, 0)
+            assert a.size > 4096 or made.tobytes() == skeleton_texels(a, lo, hi, mode).tobytes()
+        else:
+            kw['passes'] = passes
+            if op == 'skeleton_within':
+                k_lo = KEPT if rng.random() < 0.3 else int(rng.integers(0, info['passes'] + 2))
+                sel = {'k_lo': k_lo, 'k_hi': None if rng.random() < 0.5 else KEPT if k_lo == KEPT else int(rng.integers(k_lo, info['passes'] + 2)), 'fill': fill()}
+                made = burn_within_texels(a, burn, **sel)
+                kw.update(sel)
+            elif op == 'skeleton_info':
+                expect = info
+            else:
+                x, y, z, w, h, d = kw['box'] = _box(rng, grid)
+                expect = np.ascontiguousarray(burn[z:z + d, y:y + h, x:x + w])
+    else:
+        raise ValueError(op)
+    step = {'op': op, 'sub': sub, 'src': cur, 'out': None, 'kwargs': kw, 'expect': made if made is not None else expect, 'shape': tuple(grid),
+            'format': fmt, 'b_source': b_source, 'facts': facts, 'forced': None}
+    return step, made
+
+
+def _draw_selected(c, cur, tail, kw, emitted, ranks, listed, facts, every, foreground):
+    """(the texels made, the scalar expected) of ``tail`` (keep, label, keep_set, info, list, ranks, measure) of a labelling of volume
+    ``cur`` whose emitters speak of ``emitted``; fills ``kw`` in"""
+    rng = c.rng
+    M = int(np.iinfo(emitted.dtype).max)
+    fill = int(rng.integers(0, M + 1)) if rng.random() < 0.5 else 0
+    if tail == 'keep':
+        top = max(len(listed), 1)
+        first = int(rng.integers(1, top + 1))
+        sel = {'first': first, 'last': None if rng.random() < 0.4 else int(rng.integers(first, top + 2)), 'fill': fill}
+        kw.update(sel)
+        return keep_texels(emitted, ranks, **sel), None
+    if tail == 'label':
+        return label_texels(emitted, ranks), None
+    if tail == 'keep_set':
+        kw.update({'ranks': _draw_selection(rng, len(listed)), 'fill': fill})
+        return keep_set_texels(emitted, ranks, kw['ranks'], fill), None
+    if tail == 'info':
+        dropped = 0 if kw['min_voxels'] == 1 else len(every()) - len(listed)
+        return None, {'listed': len(listed), 'dropped': dropped, 'foreground_voxels': foreground, 'listed_voxels': int(sum(v for _, _, _, v in listed))}
+    if tail == 'list':
+        first = int(rng.integers(0, len(listed) + 1))
+        n = None if rng.random() < 0.5 else int(rng.integers(0, len(listed) - first + 1))
+        kw.update({'first': first, 'n': n})
+        return None, listed[first:] if n is None else listed[first:first + n]
+    if tail == 'ranks':
+        x, y, z, w, h, d = kw['box'] = _box(rng, ranks.shape)
+        return None, np.ascontiguousarray(ranks[z:z + d, y:y + h, x:x + w])
+    assert tail == 'measure'
+    first = int(rng.integers(0, len(listed) + 1)) if rng.random() < 0.5 else 0
+    n = None if rng.random() < 0.5 else int(rng.integers(0, len(listed) - first + 1))
+    if c.fine:                                                    # every rank of a block meets in the block's table
+        first, n = 0, None
+    values, kw['b'], kw['values_channel'] = emitted, None, 0
+    if rng.random() < 0.7:
+        kw['b_source'], kw['b'], kw['values_channel'], other = _draw_other(c, cur, _UNORM)
+        values = _channel_of(other, kw['values_channel'])
+        facts['values_of_a_derived_pair'] = bool(kw['b'][0] == 'volume' and kw['b'][1] > 0 and other.ndim == 4 and kw['values_channel'] == 1)
+    kw.update({'first': first, 'n': n})
+    return None, measure_texels(ranks, values, first, n)
+
+
 def _constant(texels):
     flat = texels.reshape(-1)
     if flat.dtype.kind == 'f':
@@ -449,10 +805,12 @@ def _legal(entry, fmt, texels):
         return False
     if op == 'range' and fmt == 'R32F' and np.isnan(texels).all():
         return False
+    if FAMILY.get(op) in SLOW_FAMILIES and op in LATER and int(np.prod(texels.shape[:3])) > SLOW_VOXELS:
+        return False
     return True
 
 
-def _build(seed):
+def _build_old(seed):
     c = _Chain(seed)
     rng = c.rng
     tiny = seed % 16 == 0
@@ -480,7 +838,7 @@ def _build(seed):
                     'shape': tuple(shape), 'format': fmt, 'b_source': None})
     begin = list(plan[1]) if plan is not None else []
     target = plan[2] if plan is not None else None
-    wishes = [ENTRIES[(3 * seed + j) % len(ENTRIES)] for j in range(3)]
+    wishes = [OLD_ENTRIES[(3 * seed + j) % len(OLD_ENTRIES)] for j in range(3)]
     count = max(int(rng.integers(3, 7)), min(len(begin), 4))
     for k in range(count):
         if begin and not _legal(begin[0], format_of(c.texels[cur]), c.texels[cur]):
@@ -493,7 +851,7 @@ def _build(seed):
             else:
                 roll = rng.random()
                 pool = [('upload_block', None)] if roll < 0.25 and 0 < k < count - 1 and c.steps[-1]['op'] != 'upload_block' else \
-                    SCALAR_ENTRIES if roll < 0.50 else VOLUME_ENTRIES
+                    OLD_SCALAR_ENTRIES if roll < 0.50 else OLD_VOLUME_ENTRIES
                 wished = [e for e in wishes if e not in c.used and _legal(e, fmt, texels)]
                 legal = [e for e in pool if _legal(e, fmt, texels)]
                 fresh = [e for e in legal if e not in c.used]
@@ -502,7 +860,7 @@ def _build(seed):
                 elif fresh or legal:
                     entry = (fresh or legal)[int(rng.integers(len(fresh or legal)))]
                 else:                                             # e.g. RG32F: no scalar takes it
-                    legal = [e for e in VOLUME_ENTRIES if _legal(e, fmt, texels)]
+                    legal = [e for e in OLD_VOLUME_ENTRIES if _legal(e, fmt, texels)]
                     entry = legal[int(rng.integers(len(legal)))]
             if entry[0] == 'resample' and target is not None:
                 step, made = _draw_step(c, cur, ('resample', target))
@@ -524,6 +882,90 @@ def _build(seed):
         if c.texels[cur].ndim == 4 and c.one_channel_before(cur) is not None and rng.random() < 0.5:
             cur = c.one_channel_before(cur)
     return c.steps
+
+
+def _reads_derived(step):
+    return step['src'] > 0 or any(step['kwargs'].get(key) is not None and step['kwargs'][key][0] == 'volume' and step['kwargs'][key][1] > 0
+                                  for key in ('b', 'texels'))
+
+
+def _draw_later_chain(seed, attempt):
+    c = _Chain(seed)
+    rng = c.rng = np.random.default_rng([CONSTANT + seed, attempt])
+    n = seed - LATER_SEEDS
+    tiny = seed % 16 == 0
+    rank = n - n // 16 - 1
+    plan = LATER_PLANS[rank] if not tiny and rank < len(LATER_PLANS) else None
+    free = rank - len(LATER_PLANS)
+    c.fine = plan is not None and plan[2] == 'noise' and ('basins_measure', None) in plan[1]
+    if tiny:
+        fmt, shape, style = _UNORM[(seed // 16) % 4], (1, 1, 1), None
+    elif plan is not None:
+        fmt, shape, style = _U1[rank % 2], plan[0], plan[2]
+    else:
+        fmt = ('R8', 'RG8', 'R16', 'RG16', 'RG8', 'R16', 'RG16', 'R8')[free % 8]
+        shape = draw_shape(rng, fits=lambda s: s[0] * s[1] * s[2] <= (2 if free % 3 == 2 else 1) * SLOW_VOXELS)
+        style = ('noise', 'sphere', 'sparse', 'blobs')[int(rng.integers(4))]
+    source = draw_texels(rng, fmt, shape, style=style)
+    cur = c.add_volume(source)
+    c.steps.append({'op': 'source', 'sub': None, 'src': None, 'out': 0, 'kwargs': {'format': fmt, 'texels': source}, 'expect': c.texels[0],
+                    'shape': tuple(shape), 'format': fmt, 'b_source': None})
+    begin = list(plan[1]) if plan is not None else []
+    wishes = [LATER_ENTRIES[(3 * n + j) % len(LATER_ENTRIES)] for j in range(3)]
+    count = max(int(rng.integers(3, 7)), len(begin))
+    forced = seed % 4 == 3
+    for k in range(count):
+        if begin and not _legal(begin[0], format_of(c.texels[cur]), c.texels[cur]):
+            cur = c.one_channel_before(cur)
+        texels = c.texels[cur]
+        fmt = format_of(texels)
+        planned = begin.pop(0) if begin else None
+        for redraw in range(REDRAWS + 1):
+            if planned is not None:                              # a planned entry is drawn again as itself: its family is to see this shape
+                entry = planned
+            else:
+                roll, later = rng.random(), rng.random() < 0.75
+                pool = [('upload_block', None)] if roll < 0.2 and 0 < k < count - 1 and c.steps[-1]['op'] != 'upload_block' else \
+                    (LATER_SCALAR_ENTRIES if later else OLD_SCALAR_ENTRIES) if roll < 0.45 and k > 0 else \
+                    (LATER_VOLUME_ENTRIES if later else OLD_VOLUME_ENTRIES)
+                wished = [e for e in wishes if e not in c.used and _legal(e, fmt, texels)]
+                legal = [e for e in pool if _legal(e, fmt, texels)] or [e for e in LATER_VOLUME_ENTRIES if _legal(e, fmt, texels)]
+                fresh = [e for e in legal if e not in c.used]
+                if wished and redraw == 0 and rng.random() < 0.8:
+                    entry = wished[0]
+                else:
+                    entry = (fresh or legal)[int(rng.integers(len(fresh or legal)))]
+            step, made = (_draw_later_step if entry[0] in LATER else _draw_step)(c, cur, entry)
+            if made is None or texels.size == 1 or made.size == 1 or not _constant(made) or redraw == REDRAWS:
+                break
+        if forced and FAMILY.get(entry[0]) in FORCED and entry[0] in LATER and entry[0] not in UNHOOKED:
+            hooks = FORCED[FAMILY[entry[0]]]
+            step['forced'] = hooks[(seed // 4 + k) % len(hooks)]
+        c.used.add(entry)
+        if made is not None:
+            step['out'] = c.add_volume(made)
+            cur = step['out']
+        elif step['op'] == 'upload_block':
+            c.texels[cur] = step['expect']
+        c.steps.append(step)
+        if c.texels[cur].ndim == 4 and c.one_channel_before(cur) is not None and rng.random() < 0.5:
+            cur = c.one_channel_before(cur)
+    return c.steps
+
+
+def _build_later(seed):
+    """a chain of the later rules: at least two steps of the later units, one of which reads a volume that a derive step made; a draw
+    that misses this is drawn again from the next stream of the seed"""
+    for attempt in range(64):
+        steps = _draw_later_chain(seed, attempt)
+        later = [s for s in steps[1:] if s['op'] in LATER]
+        if len(later) >= 2 and any(_reads_derived(s) for s in later):
+            return steps
+    raise AssertionError('seed %d: no chain of the later rules' % seed)
+
+
+def _build(seed):
+    return _build_old(seed) if seed < LATER_SEEDS else _build_later(seed)
 
 
 @functools.lru_cache(maxsize=None)
@@ -550,6 +992,36 @@ def _text(value):
     return repr(value)
 
 
+def _later_text(op, kw, other, emitted):
+    """the call of a step of the later units on its source, as text"""
+    g = lambda *keys: ', '.join(_text(kw[k]) for k in keys)
+    tails = {'keep': lambda: 'keep(%s)' % g('first', 'last', 'fill'), 'label': lambda: 'label()', 'keep_set': lambda: 'keep_set(%s)' % g('ranks', 'fill'),
+             'info': lambda: 'info', 'list': lambda: 'list(%s)' % g('first', 'n'), 'ranks': lambda: 'ranks(*%r)' % (kw['box'],),
+             'measure': lambda: 'measure(%s, %s, %d)' % (g('first', 'n'), other, kw['values_channel'])}
+    if op == 'geodesic':
+        return 'geodesic(%s)' % g('op', 'h', 'connectivity', 'channel')
+    if op == 'reconstruct':
+        return 'reconstruct(%s, %s)' % (other, g('op', 'connectivity', 'channel', 'mask_channel'))
+    if op.startswith('basins_'):
+        return 'watershed(%s, texels=%s).%s' % (g('lo', 'hi', 'polarity', 'connectivity', 'min_voxels', 'channel'), emitted, tails[op[7:]]())
+    if op.startswith('split_'):
+        return 'split(%s).%s' % (g('lo', 'hi', 'h', 'steps', 'connectivity', 'min_voxels'), tails[op[6:]]())
+    if op in ('keep_set', 'measure'):
+        return 'components(%s).%s' % (g('lo', 'hi', 'connectivity', 'min_voxels'), tails[op]())
+    if op == 'thickness':
+        return 'thickness(%s)' % g('lo', 'hi', 'steps', 'seeds')
+    if op == 'open_ball':
+        return 'open_ball(%s)' % g('lo', 'hi', 'radius', 'fill')
+    if op.startswith('thickness_'):
+        tail = {'within': lambda: 'within(%s)' % g('r2_lo', 'r2_hi', 'fill'), 'channel': lambda: 'channel(%s)' % g('steps'), 'info': lambda: 'info',
+                'squared': lambda: 'squared(*%r)' % (kw['box'],)}[op[10:]]()
+        return 'distance(%s).thickness().%s' % (g('lo', 'hi', 'seeds'), tail)
+    if op == 'centreline':
+        return 'centreline(%s)' % g('lo', 'hi', 'mode')
+    tail = {'within': lambda: 'within(%s)' % g('k_lo', 'k_hi', 'fill'), 'info': lambda: 'info', 'burn': lambda: 'burn(*%r)' % (kw['box'],)}[op[9:]]()
+    return 'skeleton(%s).%s' % (g('lo', 'hi', 'mode', 'passes'), tail)
+
+
 def describe(seed):
     """the chain as lines for a Python session: ``steps = chain(seed)`` gives the arrays the lines name by step and keyword"""
     steps = chain(seed)
@@ -557,8 +1029,8 @@ def describe(seed):
     for i, s in enumerate(steps):
         kw, src = s['kwargs'], 'v%s' % s['src']
         args = ', '.join('%s=%s' % (k, _text(v)) for k, v in kw.items() if k not in ('b', 'block', 'texels', 'box'))
-        if 'b' in kw:
-            other = 'v%d' % kw['b'][1] if kw['b'][0] == 'volume' else 'upload(K(%d)["b"][1])' % i
+        other, emitted = (None if kw.get(key) is None or s['op'] == 'source' else 'v%d' % kw[key][1] if kw[key][0] == 'volume' else
+                          'upload(K(%d)["%s"][1])' % (i, key) for key in ('b', 'texels'))
         d, h, w = s['shape']
         if s['op'] == 'source':
             dtype, channels = FORMATS[kw['format']]
@@ -574,6 +1046,11 @@ def describe(seed):
             tail = {'within': 'within(%r, %r, %r)' % (kw.get('r2_lo'), kw.get('r2_hi'), kw.get('fill')), 'channel': 'channel(%r)' % kw.get('steps'),
                     'distance_info': 'info', 'distance_squared': 'squared(*%r)' % (kw.get('box'),)}[s['op']]
             call = '%s.%s' % (made, tail)
+        elif s['op'] in LATER:
+            call = '%s.%s' % (src, _later_text(s['op'], kw, other, emitted))
+            if s.get('forced') is not None:
+                call += '    # and forced: %s' % {'skeleton': '_flags=%r', 'thickness': 'thickness_timed(_flags=%r)', 'reconstruct': 'reconstruct_timed(_tile_rounds=%r)',
+                                                   'watershed': '_caps=%r'}[FAMILY[s['op']]] % (s['forced'],)
         elif s['op'] == 'combine':
             rest = ', '.join('%s=%r' % (k, v) for k, v in kw.items() if k not in ('b', 'op'))
             call = '%s.combine(%s, %r, %s)' % (src, other, kw['op'], rest)
