@@ -135,7 +135,26 @@ typedef struct vpt_uniforms {
 VPT_API int vpt_device_count(int *count);
 VPT_API int vpt_context_create(int device_ordinal, vpt_context **out);
 /* same, but work is enqueued on a caller-owned HIP stream (e.g. torch.cuda.current_stream().cuda_stream) so that
- * it orders with the caller's other work (RCCL collectives) without host synchronisation; the stream is not destroyed */
+ * it orders with the caller's other work (RCCL collectives) without host synchronisation; the stream is not destroyed.
+ *
+ * Stream order (tests/test_gpu_stream_order.py asserts both lists on a caller's stream, behind a delay kernel).  Every entry point
+ * takes effect in the order of the calls, after whatever the caller enqueued on the stream before the call and before whatever it
+ * enqueues afterwards; device memory handed out (vpt_renderer_render_buffer_device, vpt_renderer_frame_ring_device,
+ * vpt_tonemapper_output_device) or handed in (vpt_volume_upload_block_device, vpt_renderer_set_render_target, the vpt_renderer_play_into*
+ * buckets) is read and written in that order.  A renderer's own render buffer behind split passes (VPT_OPTION_SPLIT_STREAMS) is
+ * complete on the stream after vpt_renderer_join or any of the three *_device calls.
+ *   Return WITHOUT a host wait (the work is only enqueued): vpt_volume_upload_block_device; vpt_volume_finalize of a volume that is not
+ *   stored as floats; vpt_volume_set_filter; vpt_volume_reduce, vpt_volume_smooth and vpt_volume_rank with one pass, vpt_volume_combine,
+ *   vpt_volume_window, vpt_volume_derive_gradient, vpt_volume_resample in its NEAREST mode; vpt_renderer_set_volume, vpt_renderer_reset
+ *   (MCM: under the matrix of the last reset), vpt_renderer_render, vpt_renderer_play (VPT_PLAY_FUSED, VPT_PLAY_FRAMES),
+ *   vpt_renderer_play_into, vpt_renderer_play_into_display, vpt_renderer_set_render_target, vpt_renderer_join,
+ *   vpt_renderer_set_option once the side streams exist, the three *_device calls above, vpt_tonemapper_render.
+ *   WAIT for the host (the stream is drained before they return): every upload from host memory (vpt_volume_upload_block,
+ *   vpt_renderer_set_transfer_function, vpt_renderer_set_environment*, vpt_tonemapper_set_source_image), vpt_volume_finalize of a float
+ *   volume (R32F, RG32F and the packed formats decoded into them: one scan for non-finite texels), vpt_volume_smooth / _rank with two
+ *   or more passes, the filtered vpt_volume_resample, the voxel fields (vpt_volume_components, vpt_volume_distance and the volumes derived
+ *   from them), every query and read-back, vpt_renderer_create, vpt_renderer_resize, every destroy, the first use of a lazily created object (the side
+ *   streams of a renderer, a frame ring), vpt_context_synchronize. */
 VPT_API int vpt_context_create_on_stream(int device_ordinal, void *hip_stream, vpt_context **out);
 VPT_API int vpt_context_destroy(vpt_context *ctx);
 VPT_API int vpt_context_synchronize(vpt_context *ctx);
