@@ -473,6 +473,59 @@ VPT_API int vpt_skeleton_profile(vpt_skeleton *sk, double *ms, uint64_t *launche
 VPT_API int vpt_volume_skeleton_capped(vpt_volume *src, uint32_t lo, uint32_t hi, int mode, int passes, int flags, vpt_skeleton **out);
 VPT_API int vpt_skeleton_destroy(vpt_skeleton *sk);
 
+/* ---- isosurface mesh by naive surface nets, on the device (extension; DESIGN.md "Surface") */
+/* What hands a structure's surface to everything else (printing, simulation, CAD, a mesh viewer), and a surface area better than a count
+ * of voxel faces: one vertex per cell the surface crosses, one quad per grid edge it crosses.  No case table; vertices are shared and the
+ * mesh is closed by construction.  The result is a pure function of the input in integers, in a fixed order.
+ *   Input: a finalized R8, RG8, R16 or RG16 volume `src` (any other format: VPT_ERR_UNSUPPORTED, naming it); `channel` is 0, or 1 of a
+ *   two-channel volume; 1 <= level <= M, where M is 255 or 65535 (otherwise VPT_ERR_INVALID).  The surface lies at code level - 1/2, so no
+ *   grid point ever lies on it and there are no degenerate cases.
+ *   Grid: voxel (x, y, z) is the grid point at those integer coordinates.  The grid is padded by one layer on every side: grid points run
+ *   from -1 to W, H and D.  code(g) is the whole unsigned code of the channel inside the volume and 0 outside; inside(g) = code(g) >= level.
+ *   A structure that touches the border is therefore closed there: outside the volume is background, as in the sibling units.
+ *   Cells: cell c = (i, j, k), with -1 <= i <= W - 1 and likewise for j and k, has the eight corners c + o, o in {0, 1}^3, and twelve
+ *   edges.  There are (W + 1)(H + 1)(D + 1) cells.
+ *   Crossing: a grid edge (g, g + e_a) crosses when inside differs at its two ends.  Let a = code(g) and b = code(g + e_a).  Then
+ *     n = |2 level - 1 - 2 a|,  d = 2 |b - a|,  t = (n 65536 + d / 2) div d   (in integers wide enough that nothing wraps: n 65536 < 2^34)
+ *   t lies in 1 .. 65535.  The crossing point is g 65536 + t e_a, in fixed point of 1 / 65536 voxel.
+ *   Vertex: a cell is active when at least one of its twelve edges crosses.  Let m be the number of its crossing edges and, per axis, s the
+ *   sum over those edges of (crossing point - c 65536) (at most 12 * 65536).  Per axis the stored coordinate is
+ *     q = (c_axis + 1) 65536 + (2 s + m) div (2 m),
+ *   a uint32, at most (W + 1) 65536.  The position in voxel-index units is q / 65536 - 1.  Vertices are numbered in raster order of their
+ *   cells: k slowest, then j, then i.
+ *   Quads: take each crossing edge (g, a); let u = (a + 1) mod 3 and v = (a + 2) mod 3.  The quad's corners are the vertices of the cells
+ *   g - e_u - e_v, g - e_v, g, g - e_u, in that order when inside(g), otherwise in the order [0, 3, 2, 1] of that list.  All four cells
+ *   exist and are active (a crossing edge has an end inside the volume, so g's coordinates off the axis are real ones and g_a >= -1).
+ *   Quads are numbered by g in raster order, then by axis x, y, z.  The triangles are (q0, q1, q2) and (q0, q2, q3); with this winding
+ *   the right-hand normals point from the object to the background.
+ *   Worked example: a 3 x 3 x 3 R8 volume of zeros with 255 at (1, 1, 1), level 128: every crossing has n = 255, d = 510, t = 32768; 8
+ *   vertices and 6 quads; the vertex of cell (0, 0, 0) is (120149, 120149, 120149) (s = 163840, m = 3), that of cell (1, 1, 1) is
+ *   (141995, 141995, 141995).
+ *   In numpy: vpt_amd.surface.surface_texels (the authority); in plain JS: js/vpt/surface.js.
+ * Limits: 2^32 or more vertices or quads: VPT_ERR_UNSUPPORTED, naming the count.  No code at or above the level: an empty surface; no emit
+ * kernel runs and the reads of n = 0 succeed.  Two runs give identical bytes.
+ * vpt_volume_surface runs on the context's stream behind any upload into src, and it blocks: it reads the two totals back before it
+ * allocates the result, as vpt_volume_components does.  src is not changed and may be destroyed afterwards.  A null argument:
+ * VPT_ERR_INVALID.  A failed allocation: VPT_ERR_HIP, nothing is leaked. */
+typedef struct vpt_surface vpt_surface;
+/* cells: (W + 1)(H + 1)(D + 1); inside: the voxels with code >= level; crossings[a]: the crossing edges along axis a (they add up to quads) */
+struct vpt_surface_info { uint64_t vertices, quads, cells, inside; uint64_t crossings[3]; uint32_t level; int32_t width, height, depth, channel; };
+VPT_API int vpt_volume_surface(vpt_volume *src, int channel, uint32_t level, vpt_surface **out);
+/* (for tests) scan_words > 0: words per block of the prefix sums, so that a small volume crosses both levels of the scan; the result is
+ * the contract's whatever the value */
+VPT_API int vpt_volume_surface_capped(vpt_volume *src, int channel, uint32_t level, uint32_t scan_words, vpt_surface **out);
+VPT_API int vpt_surface_info(vpt_surface *s, struct vpt_surface_info *info);
+/* the vertices / quads first .. first + n - 1 as 3 n / 4 n uint32 words; a window not within the count: VPT_ERR_INVALID; n = 0 checks the
+ * arguments and writes nothing (host_dst may then be null); nbytes below the window's bytes: VPT_ERR_INVALID.  Block. */
+VPT_API int vpt_surface_vertices(vpt_surface *s, uint64_t first, uint64_t n, uint32_t *host_dst, size_t nbytes);
+VPT_API int vpt_surface_quads(vpt_surface *s, uint64_t first, uint64_t n, uint32_t *host_dst, size_t nbytes);
+/* the handle's buffers on the device (null for an empty surface), valid until destroy */
+VPT_API int vpt_surface_device(vpt_surface *s, void **vertices, void **quads);
+/* (for measurements) ms[VPT_SURFACE_PHASES]: the stream drained after each */
+#define VPT_SURFACE_PHASES 5   /* inside plane, classify, prefix sums, emit vertices, emit quads */
+VPT_API int vpt_surface_profile(vpt_surface *s, double *ms);
+VPT_API int vpt_surface_destroy(vpt_surface *s);
+
 /* ---- resampling to any grid size on the device (extension; DESIGN.md "Resampling") */
 /* The step in front of everything that counts voxels (the rank filters' 3 x 3 x 3 box, components, distances "in voxel units"): a volume of
  * anisotropic voxels is brought to an isotropic grid, one that is too large or too coarse to a chosen size.  The result is a new, finalized

@@ -611,6 +611,56 @@ static napi_value SkeletonDestroy(napi_env env, napi_callback_info info) {
     VPT_CHECK(vpt_skeleton_destroy(k));
     return undefined(env);
 }
+// ---- surface --------------------------------------------------------------------------------------------
+// volumeSurface(volume, channel, level, scanWords) -> a surface handle; scanWords < 0: vpt_volume_surface, otherwise vpt_volume_surface_capped
+static napi_value VolumeSurface(napi_env env, napi_callback_info info) {
+    napi_value a[4]; vpt_volume *v; int32_t channel, scan_words; uint32_t level;
+    if (!get_args(env, info, 4, a) || !get_handle(env, a[0], &v) || !get_i32(env, a[1], &channel) || !get_u32(env, a[2], &level) || !get_i32(env, a[3], &scan_words)) return nullptr;
+    vpt_surface *out = nullptr;
+    if (scan_words < 0) VPT_CHECK(vpt_volume_surface(v, channel, level, &out));
+    else VPT_CHECK(vpt_volume_surface_capped(v, channel, level, (uint32_t)scan_words, &out));
+    return make_external(env, out);
+}
+// surfaceInfo(surface) -> [vertices, quads, cells, inside, crossings x, y, z, level, width, height, depth, channel]
+static napi_value SurfaceInfo(napi_env env, napi_callback_info info) {
+    napi_value a[1]; vpt_surface *s;
+    if (!get_args(env, info, 1, a) || !get_handle(env, a[0], &s)) return nullptr;
+    struct vpt_surface_info i;
+    VPT_CHECK(vpt_surface_info(s, &i));
+    const double fields[12] = { (double)i.vertices, (double)i.quads, (double)i.cells, (double)i.inside, (double)i.crossings[0], (double)i.crossings[1],
+                                (double)i.crossings[2], (double)i.level, (double)i.width, (double)i.height, (double)i.depth, (double)i.channel };
+    napi_value out;
+    napi_create_array_with_length(env, 12, &out);
+    for (int f = 0; f < 12; f++) napi_set_element(env, out, f, number(env, fields[f]));
+    return out;
+}
+// surfaceVertices(surface, first, dst) / surfaceQuads(surface, first, dst): dst is a Uint32Array of 3 n / 4 n words
+static napi_value surface_page(napi_env env, napi_callback_info info, bool quads) {
+    napi_value a[3]; vpt_surface *s; uint64_t first; void *data; size_t n;
+    if (!get_args(env, info, 3, a) || !get_handle(env, a[0], &s) || !get_u64(env, a[1], &first) || !get_bytes(env, a[2], &data, &n)) return nullptr;
+    if (quads) VPT_CHECK(vpt_surface_quads(s, first, n / 16, (uint32_t *)data, n));
+    else VPT_CHECK(vpt_surface_vertices(s, first, n / 12, (uint32_t *)data, n));
+    return undefined(env);
+}
+static napi_value SurfaceVertices(napi_env env, napi_callback_info info) { return surface_page(env, info, false); }
+static napi_value SurfaceQuads(napi_env env, napi_callback_info info) { return surface_page(env, info, true); }
+// surfaceProfile(surface) -> [ms inside, classify, scan, vertices, quads]
+static napi_value SurfaceProfile(napi_env env, napi_callback_info info) {
+    napi_value a[1]; vpt_surface *s;
+    if (!get_args(env, info, 1, a) || !get_handle(env, a[0], &s)) return nullptr;
+    double ms[VPT_SURFACE_PHASES];
+    VPT_CHECK(vpt_surface_profile(s, ms));
+    napi_value out;
+    napi_create_array_with_length(env, VPT_SURFACE_PHASES, &out);
+    for (int p = 0; p < VPT_SURFACE_PHASES; p++) napi_set_element(env, out, p, number(env, ms[p]));
+    return out;
+}
+static napi_value SurfaceDestroy(napi_env env, napi_callback_info info) {
+    napi_value a[1]; vpt_surface *s;
+    if (!get_args(env, info, 1, a) || !get_handle(env, a[0], &s)) return nullptr;
+    VPT_CHECK(vpt_surface_destroy(s));
+    return undefined(env);
+}
 static napi_value DistanceDestroy(napi_env env, napi_callback_info info) {
     napi_value a[1]; vpt_distance *d;
     if (!get_args(env, info, 1, a) || !get_handle(env, a[0], &d)) return nullptr;
@@ -941,6 +991,8 @@ static napi_value Init(napi_env env, napi_value exports) {
     EXPORT("distanceDestroy", DistanceDestroy); EXPORT("distanceThickness", DistanceThickness); EXPORT("distanceThicknessTimed", DistanceThicknessTimed);
     EXPORT("volumeSkeleton", VolumeSkeleton); EXPORT("skeletonInfo", SkeletonInfo); EXPORT("skeletonBurn", SkeletonBurn); EXPORT("skeletonWithin", SkeletonWithin);
     EXPORT("skeletonProfile", SkeletonProfile); EXPORT("skeletonDestroy", SkeletonDestroy);
+    EXPORT("volumeSurface", VolumeSurface); EXPORT("surfaceInfo", SurfaceInfo); EXPORT("surfaceVertices", SurfaceVertices); EXPORT("surfaceQuads", SurfaceQuads);
+    EXPORT("surfaceProfile", SurfaceProfile); EXPORT("surfaceDestroy", SurfaceDestroy);
     EXPORT("rendererCreate", RendererCreate); EXPORT("rendererDestroy", RendererDestroy); EXPORT("rendererSetShard", RendererSetShard);
     EXPORT("rendererLocalRows", RendererLocalRows); EXPORT("rendererGlobalRow", RendererGlobalRow);
     EXPORT("rendererSetVolume", RendererSetVolume); EXPORT("rendererSetTransferFunction", RendererSetTransferFunction);

@@ -12,6 +12,7 @@ const { COMBINE_STATS, checkCombineOp, checkCombineChannel, checkCombineWeights,
 const { checkReconstructOp, checkGeodesicOp, checkGeodesicH, checkSourceChannel } = require('./reconstruct.js');
 const { checkPolarity } = require('./watershed.js');
 const { THIN_KEPT, SKELETON_INFO_FIELDS, checkThinMode, checkSkeletonRange, checkThinPasses, checkBurnWithin } = require('./skeleton.js');
+const surfaceHost = require('./surface.js');
 const { RAWReader, GL_RED, GL_RG, GL_RGB, GL_RGBA, GL_UNSIGNED_BYTE, GL_FLOAT, GL_HALF_FLOAT, GL_BYTE } = R;
 
 // [type, format, internalFormat, native format name, channels in the file, element kind] of the formats keyed on all three: SNORM bytes
@@ -647,6 +648,18 @@ centreline(lo, hi, mode) {
     try { return k.volume(); } finally { k.destroy(); }
 }
 
+// ---- extension: isosurface mesh by naive surface nets (include/vpt.h; DESIGN.md "Surface") ----
+// the surface at code level - 1/2 of channel `channel` (default 0) of this (R8, RG8, R16 or RG16) volume as a Surface object: one vertex per
+// cell the surface crosses, one quad per grid edge it crosses, extracted on the device (js/vpt/surface.js states the contract).  The
+// object owns what it holds; this volume is not changed.  scanWords (for tests): the words per block of the prefix sums
+surface(level, channel, scanWords) {
+    const N = native(), layout = texelLayout(N, this.modality);
+    const norm16 = [N.VPT_FORMAT_R16, N.VPT_FORMAT_RG16, N.VPT_FORMAT_R16_SNORM, N.VPT_FORMAT_RG16_SNORM].includes(layout.fmt);
+    channel = surfaceHost.checkSurfaceChannel(channel !== undefined ? channel : 0, layout.channels);
+    surfaceHost.checkSurfaceLevel(level, norm16 ? 65535 : 255);
+    return new Surface(N.volumeSurface(this.texture, channel, level, scanWords !== undefined && scanWords !== null ? scanWords : -1));
+}
+
 }
 
 // the ready Volume `out` around a derived native volume: `modality` with the given dimensions in one block, and a copy of `meta`
@@ -901,4 +914,59 @@ function checkRankPasses(passes) {
     if (!Number.isInteger(passes) || passes < 1 || passes > 8) { throw new Error('rank-filter passes are an integer in 1 .. 8, not ' + JSON.stringify(passes)); }
     return passes;
 }
-module.exports = { Volume, Components, Distance, Skeleton, RAWReader, filterCode, gradientArguments, windowFormatBits, percentileWindow, checkPasses, checkLevels, rankOperatorCode, checkRankPasses };
+// The surface of a volume at a level as a mesh (Volume.surface): Uint32 [V][3] vertices in fixed point of 1 / 65536 voxel and Uint32 [Q][4]
+// quads on the device, in the contract's order.  Extract once, read, measure and write several times.  Outlives the volume it was made from;
+// destroy() (or close()) frees the device memory.
+class Surface {
+
+constructor(handle) { this._h = handle; }
+
+_handle() {
+    if (!this._h) { throw new Error('the surface has been destroyed'); }
+    return this._h;
+}
+
+destroy() {
+    if (this._h) { native().surfaceDestroy(this._h); this._h = null; }
+}
+
+close() { this.destroy(); }
+
+// { vertices, quads, cells, inside, crossings: [x, y, z], level, width, height, depth, channel }
+get info() {
+    const i = native().surfaceInfo(this._handle());
+    return { vertices: i[0], quads: i[1], cells: i[2], inside: i[3], crossings: [i[4], i[5], i[6]], level: i[7], width: i[8], height: i[9], depth: i[10], channel: i[11] };
+}
+
+// Uint32Array [n][3]: the stored coordinates q (x, y, z) of the vertices first .. first + n - 1 (defaults: all)
+vertices(first, n) {
+    const w = surfaceHost.checkSurfaceWindow(first !== undefined ? first : 0, n, this.info.vertices, 'vertices'), out = new Uint32Array(3 * w[1]);
+    native().surfaceVertices(this._handle(), w[0], out);
+    return out;
+}
+
+// Uint32Array [n][4]: the vertex numbers of the quads first .. first + n - 1 (defaults: all)
+quads(first, n) {
+    const w = surfaceHost.checkSurfaceWindow(first !== undefined ? first : 0, n, this.info.quads, 'quads'), out = new Uint32Array(4 * w[1]);
+    native().surfaceQuads(this._handle(), w[0], out);
+    return out;
+}
+
+triangles() { return surfaceHost.surfaceTriangles(this.quads()); }
+positions(spacing, origin) { return surfaceHost.surfacePositions(this.vertices(), spacing, origin); }
+area(spacing) { return surfaceHost.surfaceArea(this.vertices(), this.quads(), spacing); }
+volume(spacing) { return surfaceHost.surfaceVolume(this.vertices(), this.quads(), spacing); }
+normals(spacing) { return surfaceHost.surfaceNormals(this.vertices(), this.quads(), spacing); }
+writeStl(path, spacing, origin) { surfaceHost.writeStl(path, this.vertices(), this.quads(), spacing, origin); }
+writePly(path, spacing, origin) { surfaceHost.writePly(path, this.vertices(), this.quads(), spacing, origin); }
+writeObj(path, spacing, origin) { surfaceHost.writeObj(path, this.vertices(), this.quads(), spacing, origin); }
+
+// (for measurements) { inside, classify, scan, vertices, quads } in milliseconds
+get profile() {
+    const r = native().surfaceProfile(this._handle());
+    return { inside: r[0], classify: r[1], scan: r[2], vertices: r[3], quads: r[4] };
+}
+
+}
+
+module.exports = { Volume, Components, Distance, Skeleton, Surface, RAWReader, filterCode, gradientArguments, windowFormatBits, percentileWindow, checkPasses, checkLevels, rankOperatorCode, checkRankPasses };

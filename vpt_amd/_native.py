@@ -59,6 +59,8 @@ SYMBOLS = [
     "vpt_distance_thickness", "vpt_distance_thickness_timed", "vpt_distance_thickness_capped",
     "vpt_volume_skeleton", "vpt_volume_skeleton_capped", "vpt_skeleton_info", "vpt_skeleton_burn", "vpt_skeleton_within", "vpt_skeleton_profile",
     "vpt_skeleton_destroy",
+    "vpt_volume_surface", "vpt_volume_surface_capped", "vpt_surface_info", "vpt_surface_vertices", "vpt_surface_quads", "vpt_surface_device",
+    "vpt_surface_profile", "vpt_surface_destroy",
     "vpt_volume_resample", "vpt_volume_resample_timed",
     "vpt_volume_combine", "vpt_volume_combine_timed", "vpt_volume_compare",
     "vpt_volume_reconstruct", "vpt_volume_geodesic", "vpt_volume_reconstruct_timed", "vpt_volume_geodesic_timed", "vpt_volume_reconstruct_capped",
@@ -151,6 +153,15 @@ class SkeletonInfo(C.Structure):
     _fields_ = [(name, C.c_uint64) for name in ("object_voxels", "kept_voxels", "passes", "converged", "isolated", "ends", "regular", "junctions")]
 
 
+SURFACE_PHASES = 5
+
+
+class SurfaceInfo(C.Structure):
+    """struct vpt_surface_info (include/vpt.h)"""
+    _fields_ = [("vertices", C.c_uint64), ("quads", C.c_uint64), ("cells", C.c_uint64), ("inside", C.c_uint64), ("crossings", C.c_uint64 * 3),
+                ("level", C.c_uint32), ("width", C.c_int32), ("height", C.c_int32), ("depth", C.c_int32), ("channel", C.c_int32)]
+
+
 class CombineParams(C.Structure):
     """struct vpt_combine_params (include/vpt.h)"""
     _fields_ = [("op", C.c_int), ("b_channel", C.c_int), ("lo", C.c_uint32), ("hi", C.c_uint32), ("fill", C.c_uint32),
@@ -241,6 +252,10 @@ def lib():
         "vpt_skeleton_info": [P, C.POINTER(SkeletonInfo)], "vpt_skeleton_burn": [P, I, I, I, I, I, I, P, SZ],
         "vpt_skeleton_within": [P, C.c_uint32, C.c_uint32, C.c_uint32, PP],
         "vpt_skeleton_profile": [P, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)], "vpt_skeleton_destroy": [P],
+        "vpt_volume_surface": [P, I, C.c_uint32, PP], "vpt_volume_surface_capped": [P, I, C.c_uint32, C.c_uint32, PP],
+        "vpt_surface_info": [P, C.POINTER(SurfaceInfo)], "vpt_surface_vertices": [P, C.c_uint64, C.c_uint64, P, SZ],
+        "vpt_surface_quads": [P, C.c_uint64, C.c_uint64, P, SZ], "vpt_surface_device": [P, PP, PP],
+        "vpt_surface_profile": [P, C.POINTER(C.c_double)], "vpt_surface_destroy": [P],
         "vpt_volume_resample": [P, I, I, I, I, PP], "vpt_volume_resample_timed": [P, I, I, I, I, PP, C.POINTER(C.c_double)],
         "vpt_volume_combine": [P, P, C.POINTER(CombineParams), PP], "vpt_volume_combine_timed": [P, P, C.POINTER(CombineParams), PP, C.POINTER(C.c_double)],
         "vpt_volume_compare": [P, P, I, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)],

@@ -544,6 +544,24 @@ class Volume(EventTarget):
         finally:
             k.destroy()
 
+    # ---- extension: isosurface mesh by naive surface nets (include/vpt.h; DESIGN.md "Surface") ----
+    def surface(self, level, channel=0, _scan_words=None):
+        """The surface at code ``level`` - 1/2 of channel ``channel`` of this (R8, RG8, R16 or RG16) volume as a ``Surface`` object: one
+        vertex per cell the surface crosses, one quad per grid edge it crosses, extracted on the device (vpt_amd.surface.surface_texels
+        states the contract).  The object owns what it holds: this volume is not changed and may be destroyed.  ``_scan_words`` (for
+        tests): the words per block of the prefix sums of vpt_volume_surface_capped."""
+        from .surface import check_channel, check_level
+        fmt = self.native_format()[0]
+        norm16 = fmt in (N.FORMAT_R16, N.FORMAT_RG16, N.FORMAT_R16_SNORM, N.FORMAT_RG16_SNORM)
+        channel = check_channel(channel, self._texel_layout()[0])
+        level = check_level(level, 65535 if norm16 else 255)
+        h = C.c_void_p()
+        if _scan_words is None:
+            N.check(N.lib().vpt_volume_surface(self.texture, channel, level, C.byref(h)))
+        else:
+            N.check(N.lib().vpt_volume_surface_capped(self.texture, channel, level, int(_scan_words), C.byref(h)))
+        return Surface(h)
+
     # ---- extension: resampling to any grid size (include/vpt.h; DESIGN.md "Resampling") ----
     def resample(self, width, height, depth, mode='filtered'):
         """A new, ready volume in this volume's format and with its filter on a grid of width x height x depth texels (each 1 .. 4096) that
@@ -1121,3 +1139,118 @@ class Skeleton(_VoxelField):
         return dict(zip(('seed', 'border', 'steps', 'census'), ms)), int(launches.value), int(tiles.value)
 
     close = _VoxelField.destroy
+
+
+class _DeviceArray:
+    """a buffer on the device as torch takes it (the CUDA array interface)"""
+
+    def __init__(self, pointer, shape, owner):
+        self.__cuda_array_interface__ = {'shape': shape, 'typestr': '<i4', 'data': (int(pointer), False), 'version': 2, 'strides': None}
+        self._owner = owner
+
+
+class Surface:
+    """The surface of a volume at a level as a mesh (``Volume.surface``): uint32 [V][3] vertices in fixed point of 1 / 65536 voxel and
+    uint32 [Q][4] quads on the device, in the contract's order.  Extract once, read, measure and write several times.  Outlives the volume
+    it was made from; ``destroy()`` (or ``close()``) frees the device memory."""
+
+    def __init__(self, handle):
+        self._h = handle
+
+    def _handle(self):
+        if not self._h:
+            raise RuntimeError('the surface has been destroyed')
+        return self._h
+
+    def destroy(self):
+        if self._h:
+            N.lib().vpt_surface_destroy(self._h)
+            self._h = None
+
+    close = destroy
+
+    @property
+    def info(self):
+        """{'vertices', 'quads', 'cells', 'inside', 'crossings': [x, y, z], 'level', 'width', 'height', 'depth', 'channel'}"""
+        i = N.SurfaceInfo()
+        N.check(N.lib().vpt_surface_info(self._handle(), C.byref(i)))
+        out = {name: int(getattr(i, name)) for name, _ in N.SurfaceInfo._fields_ if name != 'crossings'}
+        out['crossings'] = [int(c) for c in i.crossings]
+        return out
+
+    def _page(self, read, count, per, first, n):
+        from .surface import check_window
+        first, n = check_window(first, n, count, 'vertices' if per == 3 else 'quads')
+        out = np.empty((n, per), np.uint32)
+        N.check(read(self._handle(), first, n, out.ctypes.data_as(C.c_void_p), out.nbytes))
+        return out
+
+    def vertices(self, first=0, n=None):
+        """uint32 [n][3]: the stored coordinates q (x, y, z) of the vertices first .. first + n - 1 (n None: to the end)"""
+        return self._page(N.lib().vpt_surface_vertices, self.info['vertices'], 3, first, n)
+
+    def quads(self, first=0, n=None):
+        """uint32 [n][4]: the vertex numbers of the quads first .. first + n - 1 (n None: to the end)"""
+        return self._page(N.lib().vpt_surface_quads, self.info['quads'], 4, first, n)
+
+    def triangles(self):
+        """uint32 [2 Q][3]: (q0, q1, q2) and (q0, q2, q3) of every quad"""
+        from .surface import triangles
+        return triangles(self.quads())
+
+    def positions(self, spacing=(1, 1, 1), origin=(0, 0, 0)):
+        """float64 [V][3]: (q / 65536 - 1) * spacing + origin"""
+        from .surface import positions
+        return positions(self.vertices(), spacing, origin)
+
+    def area(self, spacing=(1, 1, 1)):
+        """float64: the area of the triangles"""
+        from .surface import area
+        return area(self.vertices(), self.quads(), spacing)
+
+    def volume(self, spacing=(1, 1, 1)):
+        """float64: the volume the triangles enclose"""
+        from .surface import volume
+        return volume(self.vertices(), self.quads(), spacing)
+
+    def normals(self, spacing=(1, 1, 1)):
+        """float64 [V][3]: area-weighted, per vertex, pointing from the object to the background"""
+        from .surface import normals
+        return normals(self.vertices(), self.quads(), spacing)
+
+    def write_stl(self, path, spacing=(1, 1, 1), origin=(0, 0, 0)):
+        from .surface import write_stl
+        write_stl(path, self.vertices(), self.quads(), spacing, origin)
+
+    def write_ply(self, path, spacing=(1, 1, 1), origin=(0, 0, 0)):
+        from .surface import write_ply
+        write_ply(path, self.vertices(), self.quads(), spacing, origin)
+
+    def write_obj(self, path, spacing=(1, 1, 1), origin=(0, 0, 0)):
+        from .surface import write_obj
+        write_obj(path, self.vertices(), self.quads(), spacing, origin)
+
+    def device(self):
+        """(vertices, quads): the addresses of the handle's buffers on the device (None for an empty surface), valid until destroy"""
+        v, q = C.c_void_p(), C.c_void_p()
+        N.check(N.lib().vpt_surface_device(self._handle(), C.byref(v), C.byref(q)))
+        return v.value, q.value
+
+    def device_tensors(self):
+        """(vertices [V][3], quads [Q][4]) as torch int32 tensors over the handle's own buffers (the uint32 words bit for bit; no
+        copy): valid until destroy, to be used on the context's stream or behind a synchronisation of it"""
+        import torch
+        i = self.info
+        v, q = self.device()
+        device = torch.device('cuda', torch.cuda.current_device())
+        if not i['vertices']:
+            return torch.empty((0, 3), dtype=torch.int32, device=device), torch.empty((0, 4), dtype=torch.int32, device=device)
+        return (torch.as_tensor(_DeviceArray(v, (i['vertices'], 3), self), device=device),
+                torch.as_tensor(_DeviceArray(q, (i['quads'], 4), self), device=device))
+
+    @property
+    def profile(self):
+        """(for measurements) {'inside', 'classify', 'scan', 'vertices', 'quads'}: milliseconds of the five phases"""
+        ms = (C.c_double * N.SURFACE_PHASES)()
+        N.check(N.lib().vpt_surface_profile(self._handle(), ms))
+        return dict(zip(('inside', 'classify', 'scan', 'vertices', 'quads'), ms))
