@@ -175,8 +175,8 @@ def test_hooks_and_sequences(gpu_ctx, oracle, geom, fast, split, form):
         r.play(9, fused=True)                                   # the passes-in-registers kernel: every tile's whole state
         r.render(); r.render()
         outs.extend(all_buffers(r))
-        if on:
-            assert r.settled_passes() >= 3
+        if on:                                                  # (host logic alone under the white environment: exact, by the stream count)
+            assert r.settled_passes() == {2: 10, 1: 5}[split]
 
     def bucket(r, sc, outs, on):
         r.set_option(N.OPTION_BUCKET_KERNEL, 1)
@@ -190,8 +190,8 @@ def test_hooks_and_sequences(gpu_ctx, oracle, geom, fast, split, form):
         r.set_render_target(0, 0)
         r.render(); r.render()
         outs.extend(all_buffers(r))
-        if on:
-            assert r.settled_passes() >= 2
+        if on:                                                  # (one stream: no bucket kernels, the frames one by one)
+            assert r.settled_passes() == {2: 3, 1: 10}[split]
 
     if form == "hooks":
         compare(hooks, gpu_ctx, oracle, geom, fast, split, fused=False)

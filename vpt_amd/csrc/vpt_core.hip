@@ -333,10 +333,8 @@ static int renderer_alloc_buffers(vpt_renderer *r) {
     r->frame_ring.reset(); r->ring_frames = 0;
     r->frame.reset(); r->acc.reset(); r->render.reset(); r->scratch.reset(); r->ndc_x.reset(); r->ndc_y.reset();
     for (int i = 0; i < 4; i++) r->st[i].reset();
-    r->cls.miss_words.reset(); r->cls.words_fresh = false;
-    r->cls.valid = false; r->cls.stale = false; r->cls.pending = 0;   // new geometry, zeroed state: classes come back with the next reset
-    r->cls.built = false;
-    r->cls.passes = 0; r->cls.fused_passes = 0; r->cls.reset_seen = false; r->cls.n_complete = 0;   // (zeroed buffers are not a reset: nothing is skipped before one)
+    r->cls.miss_words.reset(); r->cls.valid = false; r->cls.built = false;   // new geometry, zeroed state: classes come back with the next reset
+    r->cls.miss.geometry_rebuilt(); r->cls.track.geometry_rebuilt();   // (zeroed buffers are not a reset: nothing is skipped before one)
     r->dos_cur = 0; r->dos_rect_valid = false;
     int nblocks = (r->H + r->R - 1) / r->R;                 // row blocks in the image
     int mine = (nblocks - r->g + r->G - 1) / r->G;          // blocks b with b % G == g
@@ -407,7 +405,7 @@ extern "C" int vpt_renderer_set_environment(vpt_renderer *r, const uint8_t *rgba
     if (!r || !rgba) return fail(VPT_ERR_INVALID, "null argument");
     VPT_TRY(join_side(r));
     if (w < 1 || h < 1 || w > 16384 || h > 16384) return fail(VPT_ERR_INVALID, "environment size %dx%d out of range", w, h);
-    if (r->kind == VPT_RENDERER_MCM) { VPT_TRY(mcm_catch_up(r)); r->cls.env_changed = true; }   // (the MISS pixels' running mean moves again: k_mcm_miss_settled waits for a reset)
+    if (r->kind == VPT_RENDERER_MCM) VPT_TRY(mcm_environment_changed(r));
     std::vector<float4> t((size_t)w * h);
     for (size_t i = 0; i < t.size(); i++)
         t[i] = make_float4((float)rgba[4 * i] / 255.0f, (float)rgba[4 * i + 1] / 255.0f,
@@ -416,7 +414,7 @@ extern "C" int vpt_renderer_set_environment(vpt_renderer *r, const uint8_t *rgba
     r->env_w = w; r->env_h = h; r->env_const = t[0];
     r->env_opaque = true;
     for (size_t i = 0; i < t.size(); i++) if (rgba[4 * i + 3] != 255) { r->env_opaque = false; break; }
-    r->cls.poisoned = true;                                  // (MCS: the fixed points of the ray-missing pixels move with the environment)
+    r->cls.track.environment_changed();
     return VPT_OK;
 }
 // every alpha of the host texels is 1 in its format (RGBE8 has none: always opaque)
@@ -438,7 +436,7 @@ extern "C" int vpt_renderer_set_environment_texels(vpt_renderer *r, const void *
     if (format < VPT_ENV_RGBA8 || format > VPT_ENV_RGBE8) return fail(VPT_ERR_INVALID, "unknown environment format %d", format);
     if (w < 1 || h < 1 || w > 16384 || h > 16384) return fail(VPT_ERR_INVALID, "environment size %dx%d out of range", w, h);
     VPT_TRY(join_side(r));                                   // side streams may still read the old map
-    if (r->kind == VPT_RENDERER_MCM) { VPT_TRY(mcm_catch_up(r)); r->cls.env_changed = true; }   // (as vpt_renderer_set_environment)
+    if (r->kind == VPT_RENDERER_MCM) VPT_TRY(mcm_environment_changed(r));
     vpt_context *c = r->ctx;
     HIP_TRY(hipSetDevice(c->device));
     static const size_t texel_bytes[] = { 4, 8, 16, 4 };
@@ -457,7 +455,7 @@ extern "C" int vpt_renderer_set_environment_texels(vpt_renderer *r, const void *
     HIP_TRY(hipStreamSynchronize(c->stream));                // (the caller's buffer may be released on return; the staging buffer goes with this scope)
     r->env_const = first;
     r->env_opaque = env_texels_opaque(texels, n, format);
-    r->cls.poisoned = true;                                  // (as vpt_renderer_set_environment)
+    r->cls.track.environment_changed();
     return VPT_OK;
 }
 // VPT_OPTION_SPLIT_STREAMS as the library sets it itself (round 4: the measured best form is the default, not an option a caller has to know).
@@ -947,7 +945,7 @@ extern "C" int vpt_renderer_bucket_launches(vpt_renderer *r, uint64_t *launches)
 }
 extern "C" int vpt_renderer_settled_passes(vpt_renderer *r, uint64_t *passes) {
     if (!r || !passes) return fail(VPT_ERR_INVALID, "null argument");
-    *passes = r->cls.settled_passes;
+    *passes = r->cls.miss.settled_passes();
     return VPT_OK;
 }
 extern "C" int vpt_renderer_join(vpt_renderer *r) {
@@ -962,8 +960,7 @@ extern "C" int vpt_renderer_set_render_target(vpt_renderer *r, void *ptr, size_t
     if (ptr && nbytes < need) return fail(VPT_ERR_INVALID, "render target too small: %zu < %zu", nbytes, need);
     r->render_target = (uint2 *)ptr; r->target_is_callers = ptr != nullptr;
     // what the library knows about this memory's texels (marcher_track: tiles it may skip) ends here: the caller may have used it in between
-    for (int i = 0; i < r->cls.n_complete; i++)
-        if (ptr && r->cls.complete[i] == ptr) { r->cls.complete[i] = r->cls.complete[--r->cls.n_complete]; break; }
+    if (ptr) r->cls.forget_destinations(ptr);
     return VPT_OK;
 }
 extern "C" int vpt_renderer_set_lao_params(vpt_renderer *r, const struct vpt_lao_params *p) {
@@ -1007,8 +1004,8 @@ extern "C" int vpt_renderer_set_option(vpt_renderer *r, int option, int value) {
         case VPT_OPTION_SETTLED_MISS:
             if (r->kind != VPT_RENDERER_MCM) return fail(VPT_ERR_UNSUPPORTED, "VPT_OPTION_SETTLED_MISS: an MCM option");
             if (value < 0 || value > 2) return fail(VPT_ERR_INVALID, "VPT_OPTION_SETTLED_MISS: 0 (off), 1 (settled) or 2 (packed)");
-            if (!value || (value != 2 && r->cls.words_fresh)) VPT_TRY(mcm_catch_up(r));   // (1: k_mcm_miss_settled reads the direction array)
-            r->cls.settled_opt = value; return VPT_OK;
+            if (r->cls.miss.option_wants_catch_up(value)) VPT_TRY(mcm_catch_up(r));
+            r->cls.miss.set_option(value); return VPT_OK;
         case VPT_OPTION_VERIFY_TILE_CLASSES:
             if (r->kind != VPT_RENDERER_MCM) return fail(VPT_ERR_UNSUPPORTED, "VPT_OPTION_VERIFY_TILE_CLASSES: an MCM option");
             r->cls.verify = value != 0; return VPT_OK;

@@ -29,6 +29,7 @@
 // members and everything else in them has a default member initialiser, so `new` builds a valid object and `delete` frees all of it.
 // vpt_handles.h holds their siblings for the other two resources: Event and Stream, the owners of a HIP event and of a HIP stream, and
 // EventPairs, the pool of timing event pairs behind vpt_renderer_set_profiling.  The destroy functions leave everything idle and `delete`.
+// vpt_pass_state.h holds what a renderer's passes remember about the tile classes between two calls (Destinations, MarcherTrack, MissState).
 // Nothing device-side crosses a translation unit: a kernel is compiled by the unit that names it (the three MCM units share one header).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -49,6 +50,7 @@
 #include "vpt_kernels.h"
 #include "vpt_buffers.h"
 #include "vpt_handles.h"
+#include "vpt_pass_state.h"
 
 // ---------------------------------------------------------------------------------------------
 // errors
@@ -106,10 +108,10 @@ struct vpt_volume {
 };
 
 // Tile classes (vpt_kernels.h, "Tile classes"): per reset the host sorts the 16x16 tiles into those none of whose camera rays
-// can meet the cube (MISS) and the rest (HIT).  While every pass uses the reset's matrix (and blur == 0) a MISS tile's photons
-// never enter the cube, so its passes run k_mcm_miss on 32 B of state; `stale` says that the position / transmittance arrays
-// of the MISS tiles are behind and k_mcm_materialize must run before anything but k_mcm_miss looks at them.
-#define VPT_COMPLETE_DESTS 40
+// can meet the cube (MISS) and the rest (HIT).  Three parts: the lists themselves with their options (here: device memory and HIP
+// handles), and what the passes over them remember between two calls (vpt_pass_state.h, plain host C++ with private fields) — `track`
+// for the accumulating ray marchers (marcher_track), `miss` for MCM's MISS tiles (vpt_mcm.hip).  A renderer is either MCM or a marcher:
+// one of the two is always idle.
 struct TileClasses {
     bool enabled = true, verify = false;   // VPT_OPTION_TILE_CLASSES (default on), VPT_OPTION_VERIFY_TILE_CLASSES
     bool one_stream = false;       // VPT_OPTION_TILE_CLASSES = 2: the MCM class kernels also where they must follow each other on one stream (each alone on the chip: measurements)
@@ -122,31 +124,13 @@ struct TileClasses {
     bool built = false; float built_mvp[16] = {}; int built_geom[6] = {};
     // uploads go through two pinned staging buffers in turn, no host wait: staged[i] = the copy out of staging[i] has been enqueued and completes
     PinnedBuf<uint32_t> staging[2]; Event staged[2]; int stage_next = 0;
-    bool stale = false, stale_fast = false;   // MISS tiles' position / transmittance arrays are behind; the pass that left them ran the fast variant
     DevBuf<unsigned long long> violations;
-    // the accumulating ray marchers (MIP, EAM, ISO, MCS, Depth): see marcher_track
-    uint64_t passes = 0, fused_passes = 0;   // generate / fused passes since the reset
-    bool poisoned = false;         // a pass since the reset used another matrix than the first: nothing can be skipped until the next reset
-    bool first_mix_one = false;    // the first pass since the reset was a fused pass with mix == 1 (MCS, Depth: accumulator = frame exactly)
-    bool list_now = false;         // the launch being enqueued covers the HIT tiles only
-    bool reset_seen = false;       // vpt_renderer_reset has run on the present buffers (zero-filled buffers are not a reset)
-    // render destinations (the renderer's own buffer, a caller's target, the slots of a bucket or of the gather ring) that a WHOLE-image fused
-    // pass has written since the reset: only there do the skipped tiles hold their final texels (marcher_track)
-    const void *complete[VPT_COMPLETE_DESTS] = {}; int n_complete = 0;
-    // MCM, the settled form of the MISS-tile pass (VPT_OPTION_SETTLED_MISS, k_mcm_miss_settled; vpt_mcm.hip "settled").  `complete` holds for
-    // MCM the destinations whose MISS texels all show the settled radiance.
-    int settled_opt = 2;           // VPT_OPTION_SETTLED_MISS: 0 off, 1 k_mcm_miss_settled, 2 k_mcm_miss_packed
-    // the packed form's records: the two jitter words of every MISS pixel's last reset, npix_padded of them in the state arrays' tile order
-    // (allocated with the first packed pass).  words_fresh: the last pass of the MISS tiles was a packed one — the records are newer than
-    // the direction array (then `stale` holds too), and k_mcm_materialize rebuilds it from them
+    // the packed form's records (k_mcm_miss_packed): the two jitter words of every MISS pixel's last reset, npix_padded of them in the state
+    // arrays' tile order (allocated with the first packed pass); while miss.words_fresh() k_mcm_materialize rebuilds the direction array from them
     DevBuf<uint2> miss_words;
-    bool words_fresh = false;
-    uint64_t events = 0;          // events of every pixel since the reset (= `samples` of a MISS pixel, `pending` included)
-    uint32_t pending = 0;          // events k_mcm_miss_settled has run that the samples array does not show yet (k_mcm_materialize adds them)
-    bool env_changed = false;      // the environment was set since the reset: the MISS pixels' mean is on the move again until the next one
-    int settle = 0, probes = 0;    // 0: not known whether the MISS pixels' radiance is final, 1: proven, 2: given up until the next reset; read-backs spent on it
-    uint64_t complete_events = 0;  // `events` behind the pass that last rebuilt `complete` while settle == 0
-    uint64_t settled_passes = 0;   // passes whose MISS tiles ran the settled kernel (vpt_renderer_settled_passes)
+    MarcherTrack track; MissState miss;
+    // what the library knows about the texels of this memory ends here: the caller may have used it in between
+    void forget_destinations(const void *lo, size_t bytes = 1) { track.forget_destinations(lo, bytes); miss.forget_destinations(lo, bytes); }
 };
 // Split passes (VPT_OPTION_SPLIT_STREAMS = K): a sampling pass is dealt to up to K streams as tile-row ranges or parts of a tile list;
 // range i runs on range_stream(r, i), the context's stream for i = 0 and a private side stream otherwise.  A pixel's pass depends on
@@ -293,6 +277,8 @@ int mcm_multi(vpt_renderer *r, const PassArgs &a, uint32_t npasses, uint2 *ring)
 int mcm_before_pass(vpt_renderer *r, const PassArgs &a, bool *same_matrix);
 int mcm_materialize(vpt_renderer *r);
 int mcm_catch_up(vpt_renderer *r);                                            // mcm_materialize if the settled forms left samples pending or the direction array behind
+int mcm_environment_changed(vpt_renderer *r);                                 // the environment is about to be replaced
+void mcm_events_run(vpt_renderer *r, uint64_t events);                        // every form of MCM pass counts its events here
 int mcm_bucket_ready(vpt_renderer *r, const PassArgs &a, bool *ready);
 int mcm_bucket(vpt_renderer *r, const PassArgs &a, const FrameVar *v, int count, void *ring, uint32_t slot_pixels, bool last_to_render_buffer,
                const uint8_t *display_table);
@@ -408,7 +394,7 @@ static int launch_sampling(K kernel, vpt_renderer *r, const PassArgs &a) {
     const dim3 block(wave ? 64u : (unsigned)VPT_BLOCK);
     const bool split = split_allowed(r);
     if (split) VPT_TRY(ensure_split_streams(r));
-    if (r->cls.list_now) {
+    if (r->cls.track.list_now()) {
         // the HIT tiles only (marcher_track): K equal parts of the list on the K streams
         const int k = split ? std::min(split_for(r, r->cls.n_hit), r->cls.n_hit) : 1;
         VPT_TRY(streams_deal(r, Deal{ DEAL_LISTS, k }));

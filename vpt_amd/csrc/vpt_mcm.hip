@@ -41,9 +41,21 @@ template <bool FUSE> static PassKernel format_miss_kernel(int v, bool fast) {
     return dispatch_variant<VPT_V_NEAREST | VPT_V_RG | VPT_V_F32>(
         v, [&](auto F) { return fast ? (PassKernel)k_mcm_miss<FUSE, F() | VPT_V_FAST, false, true> : (PassKernel)k_mcm_miss<FUSE, F(), false, true>; }, no_pass_kernel);
 }
+// LINEAR one-channel byte volumes: the MISS-tile kernel of a form — the one list of what is instantiated.  Bit-exact arithmetic exists
+// with LATE = true only (launch_mcm_classes: `late`); the settled forms have no FUSE parameter
+template <bool FUSE> static PassKernel miss_kernel(int vf, MissForm form, bool fast, bool late, bool check) {
+    if (vf) return format_miss_kernel<FUSE>(vf, fast);
+    constexpr int Q = VPT_V_FAST; static_assert(MISS_PLAIN == 0 && MISS_PACKED == 1 && MISS_SETTLED == 2, "the rows' order");
+    static const PassKernel kernels[3][6] = {                  // <arithmetic, CHECK, LATE>
+        { k_mcm_miss<FUSE, Q, true, true>, k_mcm_miss<FUSE, Q, true, false>, k_mcm_miss<FUSE, 0, true, true>, k_mcm_miss<FUSE, Q, false, true>, k_mcm_miss<FUSE, Q, false, false>, k_mcm_miss<FUSE, 0, false, true> },
+        { k_mcm_miss_packed<Q, true, true>, k_mcm_miss_packed<Q, true, false>, k_mcm_miss_packed<0, true, true>, k_mcm_miss_packed<Q, false, true>, k_mcm_miss_packed<Q, false, false>, k_mcm_miss_packed<0, false, true> },
+        { k_mcm_miss_settled<Q, true, true>, k_mcm_miss_settled<Q, true, false>, k_mcm_miss_settled<0, true, true>, k_mcm_miss_settled<Q, false, true>, k_mcm_miss_settled<Q, false, false>, k_mcm_miss_settled<0, false, true> } };
+    return kernels[form][(check ? 0 : 3) + (fast ? (late ? 0 : 1) : 2)];
+}
 // position / transmittance of the MISS tiles, as the last pass's arithmetic would have stored them
 int mcm_materialize(vpt_renderer *r) {
-    if (!r->cls.stale) return VPT_OK;
+    MissState &m = r->cls.miss;
+    if (!m.stale()) return VPT_OK;
     VPT_TRY(join_side(r));
     HIP_TRY(hipSetDevice(r->ctx->device));
     PassArgs a;
@@ -52,15 +64,20 @@ int mcm_materialize(vpt_renderer *r) {
     mat4_sums(&a);
     a.pm.tile_list = r->cls.list + r->cls.n_hit; a.pm.list_n = r->cls.n_miss;
     if (r->cls.n_miss > 0) {
-        const uint32_t words = r->cls.words_fresh ? 1u : 0u;   // the direction array first, from k_mcm_miss_packed's records
-        if (r->cls.stale_fast) hipLaunchKernelGGL(k_mcm_materialize<true>, dim3((unsigned)r->cls.n_miss), dim3(VPT_BLOCK), 0, r->ctx->stream, a, r->cls.pending, words);
-        else hipLaunchKernelGGL(k_mcm_materialize<false>, dim3((unsigned)r->cls.n_miss), dim3(VPT_BLOCK), 0, r->ctx->stream, a, r->cls.pending, words);
+        const uint32_t words = m.words_fresh() ? 1u : 0u;      // the direction array first, from k_mcm_miss_packed's records
+        if (m.stale_fast()) hipLaunchKernelGGL(k_mcm_materialize<true>, dim3((unsigned)r->cls.n_miss), dim3(VPT_BLOCK), 0, r->ctx->stream, a, m.pending(), words);
+        else hipLaunchKernelGGL(k_mcm_materialize<false>, dim3((unsigned)r->cls.n_miss), dim3(VPT_BLOCK), 0, r->ctx->stream, a, m.pending(), words);
         HIP_TRY(hipGetLastError());
     }
-    r->cls.stale = false; r->cls.pending = 0; r->cls.words_fresh = false;
+    m.materialized();
     return VPT_OK;
 }
-int mcm_catch_up(vpt_renderer *r) { return (r->cls.pending || r->cls.words_fresh) ? mcm_materialize(r) : VPT_OK; }
+int mcm_catch_up(vpt_renderer *r) { return r->cls.miss.owes() ? mcm_materialize(r) : VPT_OK; }
+// (the MISS pixels' running mean moves again: the settled forms wait for a reset)
+int mcm_environment_changed(vpt_renderer *r) { VPT_TRY(mcm_catch_up(r)); r->cls.miss.environment_changed(); return VPT_OK; }
+// every form of pass runs its events of every pixel and says so here: the general, class and persistent passes (launch_mcm_pass), a
+// bucket, a sequence in one launch (mcm_multi) and the replay of a cached graph (vpt_render.hip)
+void mcm_events_run(vpt_renderer *r, uint64_t events) { r->cls.miss.events_run(events); }
 
 // ---- the settled form of the MISS-tile pass (k_mcm_miss_settled) ---------------------------------------------------------------------
 // Every event of a MISS pixel deposits the constant e of a 1x1 environment into the running mean r <- r + (e - r) / n, from r = 1 at the
@@ -92,7 +109,6 @@ static bool settle_channel_final(float e, float rad, uint64_t n) {
 // settle_from_reset cannot decide)
 static int settle_probe(vpt_renderer *r) {
     TileClasses &c = r->cls;
-    c.probes++;
     const uint32_t *list = c.staging[c.stage_next ^ 1];          // the host copy of the lists on the device (classes_build)
     long long k = -1;
     for (int i = 0; list && i < c.n_miss && k < 0; i++) {
@@ -105,26 +121,15 @@ static int settle_probe(vpt_renderer *r) {
         float4 v;
         HIP_TRY(hipMemcpyAsync(&v, r->st[3].get() + k, sizeof(v), hipMemcpyDeviceToHost, r->ctx->stream));
         HIP_TRY(hipStreamSynchronize(r->ctx->stream));
-        const bool counted = v.w >= 0.0f && (uint64_t)(v.w + 0.5f) == c.events;
-        if (counted && settle_channel_final(r->env_const.x, v.x, c.events) && settle_channel_final(r->env_const.y, v.y, c.events) &&
-            settle_channel_final(r->env_const.z, v.z, c.events)) {
-            c.settle = 1;
-            if (c.complete_events != c.events) c.n_complete = 0;   // destinations written before the last pass show an earlier mean
-            return VPT_OK;
-        }
-    }
-    if (k < 0 || c.probes >= 4) c.settle = 2;
+        const uint64_t n = c.miss.events();
+        c.miss.probed(true, v.w >= 0.0f && (uint64_t)(v.w + 0.5f) == n,
+                      settle_channel_final(r->env_const.x, v.x, n) && settle_channel_final(r->env_const.y, v.y, n) && settle_channel_final(r->env_const.z, v.z, n));
+    } else c.miss.probed(false, false, false);
     return VPT_OK;
-}
-static bool settled_destination(const vpt_renderer *r, const void *dest) {
-    for (int i = 0; i < r->cls.n_complete; i++) if (r->cls.complete[i] == dest) return true;
-    return false;
 }
 // an MCM reset with matrix u->mvp_inverse has just been enqueued
 static int mcm_classify(vpt_renderer *r, const vpt_uniforms *u) {
-    r->cls.valid = false; r->cls.stale = false; r->cls.words_fresh = false;   // the reset rewrote every array
-    r->cls.events = 0; r->cls.pending = 0; r->cls.env_changed = false; r->cls.n_complete = 0; r->cls.complete_events = 0;
-    r->cls.probes = 0; r->cls.settle = settle_from_reset(r) ? 1 : 0;
+    r->cls.valid = false; r->cls.miss.reset(settle_from_reset(r));   // the reset rewrote every array
     if (!r->cls.enabled || u->blur != 0.0f) return VPT_OK;
     return classes_build(r, u->mvp_inverse);
 }
@@ -163,40 +168,18 @@ static int launch_mcm_classes(vpt_renderer *r, const PassArgs &a) {
     // every gather stays inside that allocation and reads what the R32F twin's would (tests/test_gpu_norm16.py: 1080p classes, atlas on / off).
     int vm = variant_of(r) & ~VPT_V_QCUBIC;
     if (vm & VPT_V_NORM16) vm = (vm & ~(VPT_V_NORM16 | VPT_V_SNORM)) | VPT_V_F32;
-    if (vm & ~VPT_V_WIDE) km = format_miss_kernel<FUSE>(vm & ~VPT_V_WIDE, fast);
-    else if (check) km = fast ? (late ? (PassKernel)k_mcm_miss<FUSE, VPT_V_FAST, true, true> : (PassKernel)k_mcm_miss<FUSE, VPT_V_FAST, true, false>)
-                         : (PassKernel)k_mcm_miss<FUSE, 0, true, true>;
-    else km = fast ? (late ? (PassKernel)k_mcm_miss<FUSE, VPT_V_FAST, false, true> : (PassKernel)k_mcm_miss<FUSE, VPT_V_FAST, false, false>)
-                   : (PassKernel)k_mcm_miss<FUSE, 0, false, true>;
-    if (!kh || !km) return fail(VPT_ERR_INVALID, "no MCM tile-class kernels for variant %d", variant_of(r));
-    // the settled form of the MISS part: the radiance of the MISS pixels is proven final, their samples stay countable in a float, and (a
-    // fused pass) the destination already shows every MISS texel and no display table rides on the store
+    const int vf = vm & ~VPT_V_WIDE;                           // a format with a MISS-tile kernel of its own: no settled forms
+    if (!kh) return fail(VPT_ERR_INVALID, "no MCM tile-class kernels for variant %d", variant_of(r));
+    // the form of the MISS part (MissState::plan) and what has to run in front of it
     TileClasses &c = r->cls;
-    const bool wanted = c.settled_opt && !(vm & ~VPT_V_WIDE) && c.n_miss > 0 && !c.env_changed && !r->no_split && settle_env_usable(r) &&
-                        a.steps >= 1u && c.events >= 1 && c.events + a.steps < (1ull << 24);
-    if (wanted && c.settle == 0 && c.pending == 0) VPT_TRY(settle_probe(r));
-    const bool settled = wanted && c.settle == 1 && (!FUSE || (a.tm_table == nullptr && settled_destination(r, a.render)));
-    // ... in its packed form (VPT_OPTION_SETTLED_MISS = 2): 8-byte records of jitter words in place of the direction texels
-    const bool packed = settled && c.settled_opt == 2;
-    if (packed) {
-        if (!c.miss_words) HIP_TRY(c.miss_words.alloc(r->npix_padded));   // (every record is written by a pass before one reads it: miss_load_dir)
-        if (check) km = fast ? (late ? (PassKernel)k_mcm_miss_packed<VPT_V_FAST, true, true> : (PassKernel)k_mcm_miss_packed<VPT_V_FAST, true, false>)
-                             : (PassKernel)k_mcm_miss_packed<0, true, true>;
-        else km = fast ? (late ? (PassKernel)k_mcm_miss_packed<VPT_V_FAST, false, true> : (PassKernel)k_mcm_miss_packed<VPT_V_FAST, false, false>)
-                       : (PassKernel)k_mcm_miss_packed<0, false, true>;
-    } else if (settled) {
-        if (c.words_fresh) VPT_TRY(mcm_materialize(r));        // (k_mcm_miss_settled reads the direction array)
-        if (check) km = fast ? (late ? (PassKernel)k_mcm_miss_settled<VPT_V_FAST, true, true> : (PassKernel)k_mcm_miss_settled<VPT_V_FAST, true, false>)
-                             : (PassKernel)k_mcm_miss_settled<0, true, true>;
-        else km = fast ? (late ? (PassKernel)k_mcm_miss_settled<VPT_V_FAST, false, true> : (PassKernel)k_mcm_miss_settled<VPT_V_FAST, false, false>)
-                       : (PassKernel)k_mcm_miss_settled<0, false, true>;
-    } else {
-        VPT_TRY(mcm_catch_up(r));
-        if (FUSE && c.n_miss > 0 && a.steps >= 1u && c.settle != 2) {     // this pass leaves every MISS texel of its destination behind
-            if (c.settle == 0) { c.n_complete = 0; c.complete_events = c.events + a.steps; }   // (a later proof covers the last pass's texels only)
-            if (!settled_destination(r, a.render) && c.n_complete < VPT_COMPLETE_DESTS) c.complete[c.n_complete++] = (const void *)a.render;
-        }
-    }
+    const MissPass pass = { FUSE, a.steps, !vf, c.n_miss, r->no_split, settle_env_usable(r), a.tm_table != nullptr, (const void *)a.render };
+    MissPlan plan = c.miss.plan(pass);
+    if (plan.probe_first) { VPT_TRY(settle_probe(r)); plan = c.miss.plan(pass, true); }
+    if (plan.materialize_first || plan.catch_up_first) VPT_TRY(mcm_materialize(r));
+    // (the packed form's records: every one is written by a pass before one reads it, miss_load_dir)
+    if (plan.form == MISS_PACKED && !c.miss_words) HIP_TRY(c.miss_words.alloc(r->npix_padded));
+    km = miss_kernel<FUSE>(vf, plan.form, fast, late, check);
+    if (!km) return fail(VPT_ERR_INVALID, "no MCM tile-class kernels for variant %d", variant_of(r));   // (no vf is without one: never)
     const size_t lds_hit = lds_bytes(r), lds_miss = (size_t)r->tf_w * 2 * sizeof(float4);
     VPT_TRY(lds_prepare((const void *)kh, lds_hit));
     const int k = split_allowed(r) ? r->split : 1;
@@ -222,9 +205,9 @@ static int launch_mcm_classes(vpt_renderer *r, const PassArgs &a) {
     VPT_TRY(streams_deal(r, Deal{ DEAL_LISTS, k == 1 ? 1 : std::max(np, 1) }));
     auto part_args = [&](int i) {
         PassArgs part = a;
-        part.pm.tile_list = parts[i].list; part.pm.list_n = parts[i].n; part.miss_load_pos = r->cls.stale ? 0u : 1u; part.violations = r->cls.violations;
+        part.pm.tile_list = parts[i].list; part.pm.list_n = parts[i].n; part.miss_load_pos = c.miss.stale() ? 0u : 1u; part.violations = r->cls.violations;
         part.miss_verify = check ? 1u : 0u;
-        part.miss_words = c.miss_words; part.miss_load_dir = c.words_fresh ? 0u : 1u;
+        part.miss_words = c.miss_words; part.miss_load_dir = c.miss.words_fresh() ? 0u : 1u;
         VPT_TIMING_ARG(part, i < hit_parts);
         return part;
     };
@@ -249,9 +232,7 @@ static int launch_mcm_classes(vpt_renderer *r, const PassArgs &a) {
             if (e1) hipEventRecord(e1, range_stream(r, 1));
         }
     }
-    r->cls.stale = r->cls.n_miss > 0; r->cls.stale_fast = fast;
-    if (settled) { c.pending += a.steps; c.settled_passes++; }
-    c.words_fresh = packed;
+    c.miss.class_pass_done(plan.form, a.steps, fast, c.n_miss);
     return VPT_OK;
 }
 
@@ -298,7 +279,7 @@ int mcm_bucket(vpt_renderer *r, const PassArgs &a, const FrameVar *v, int count,
     FrameSeeds fs;
     for (int f = 0; f < VPT_BUCKET_FRAMES; f++) fs.seed[f] = f < count ? v[f].seed : 0.0f;
     PassArgs part = a;
-    part.miss_load_pos = r->cls.stale ? 0u : 1u; part.violations = r->cls.violations; part.tm_table = display_table;
+    part.miss_load_pos = r->cls.miss.stale() ? 0u : 1u; part.violations = r->cls.violations; part.tm_table = display_table;
     if (!last_to_render_buffer) part.render = nullptr;
     if (r->cls.n_hit > 0) {
         part.pm.tile_list = r->cls.list; part.pm.list_n = r->cls.n_hit;
@@ -308,10 +289,10 @@ int mcm_bucket(vpt_renderer *r, const PassArgs &a, const FrameVar *v, int count,
         part.pm.tile_list = r->cls.list + r->cls.n_hit; part.pm.list_n = r->cls.n_miss;
         hipLaunchKernelGGL(km, dim3((unsigned)r->cls.n_miss), dim3(VPT_BLOCK), lds_miss, range_stream(r, 1), part, fs, (uint32_t)count, ring, slot_pixels);
     }
-    r->cls.stale = r->cls.n_miss > 0; r->cls.stale_fast = fast;
+    r->cls.miss.bucket_done(fast, r->cls.n_miss);
     r->tm_valid = false;
     r->bucket_launches++;
-    r->cls.events += (uint64_t)a.steps * (uint64_t)count;
+    mcm_events_run(r, (uint64_t)a.steps * (uint64_t)count);
     return VPT_OK;
 }
 
@@ -365,7 +346,7 @@ static int launch_mcm_pass(vpt_renderer *r, const PassArgs &a) {
         if (r->mcm_persistent && persistent_volume(r->vol)) { LAUNCH_MCM_PERSIST(FUSE, r, a); rc = VPT_OK; }
         else rc = mcm_general_pass(r, a, FUSE);
     }
-    if (rc == VPT_OK) r->cls.events += a.steps;              // every form runs `steps` events of every pixel (launch_mcm_classes looks at the count before its pass)
+    if (rc == VPT_OK) mcm_events_run(r, a.steps);             // every form runs `steps` events of every pixel (launch_mcm_classes looks at the count before its pass)
     return rc;
 }
 

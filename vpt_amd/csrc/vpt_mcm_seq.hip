@@ -24,7 +24,7 @@ int mcm_multi(vpt_renderer *r, const PassArgs &a, uint32_t npasses, uint2 *ring)
     VPT_TRY(streams_deal(r, Deal{ DEAL_ROWS, 1 }));   // one stream: the side streams are joined first
     auto launch = [&](auto V) { return ring ? launch_frames(k_mcm_frames<V()>, r, a, npasses, ring) : launch_multi(k_mcm_multi<V()>, r, a, npasses); };
     auto none = [&] { return fail(VPT_ERR_INVALID, "no frame-sequence kernel for variant %d", variant_of(r)); };
-    r->cls.events += (uint64_t)a.steps * npasses;
+    mcm_events_run(r, (uint64_t)a.steps * npasses);
     if (a.vol.records) return dispatch_variant<VPT_V_CLASS_BITS>(class_variant(r, a), launch, none);   // column records: LINEAR one-channel byte volumes
     if (r->fast_math) return dispatch_sampler_variant(variant_of(r), [&](auto V) { return launch(std::integral_constant<int, V() | VPT_V_FAST>{}); }, none);
     return dispatch_sampler_variant(variant_of(r), launch, none);

@@ -216,11 +216,7 @@ extern "C" int vpt_renderer_play_into_display(vpt_renderer *r, vpt_tonemapper *t
     if (stride_bytes < need || stride_bytes % 4) return fail(VPT_ERR_INVALID, "target stride %zu: at least %zu bytes, a multiple of 4", stride_bytes, need);
     HIP_TRY(hipSetDevice(r->ctx->device));
     // the displayed frames replace whatever RGBA16F frames this memory held: none of it is a destination whose skipped tiles are in place any more
-    for (int i = 0; i < r->cls.n_complete;) {
-        const char *d = (const char *)r->cls.complete[i], *lo = (const char *)first_target;
-        if (d >= lo && d < lo + (size_t)count * stride_bytes) r->cls.complete[i] = r->cls.complete[--r->cls.n_complete];
-        else i++;
-    }
+    r->cls.forget_destinations(first_target, (size_t)count * stride_bytes);
     PassArgs a;
     VPT_TRY(play_args(r, base, count, &a));
     const FrameVar *v = (const FrameVar *)frame_vars;

@@ -12,43 +12,14 @@
 // acc = -1, then -(m + fl(1 - m)) = -1 for every m in [0, 1]).  So once one whole fused pass has run since the reset, and as long as
 // every pass since the reset used ONE matrix, the tiles none of whose rays meet the cube (classify_tiles — the same conservative
 // MISS class as MCM's) hold final values in accumulator and render buffer, and a fused pass needs to launch the HIT tiles only.
-// Called for every generate / fused pass; sets r->cls.list_now for the launch that follows.
+// ... and only into a destination whose skipped tiles already hold those values: one that a whole-image fused pass has written since the
+// reset (a caller's render target, the slots of a bucket, the gather's ring: each takes one whole pass first).  MarcherTrack
+// (vpt_pass_state.h) keeps all of that.  Called for every generate / fused pass; sets the track's list_now for the launch that follows.
 static int marcher_track(vpt_renderer *r, const PassArgs &a, bool fused, float first_mix) {
-    // (MCS: the alpha channel's first step is fl(fl(e - 1) + 1) from the reset's 1, which is e itself only for e = 1: opaque environments)
     TileClasses &c = r->cls;
-    c.list_now = false;
-    const int k = r->kind;
-    if (k != VPT_RENDERER_MIP && k != VPT_RENDERER_EAM && k != VPT_RENDERER_ISO && k != VPT_RENDERER_MCS && k != VPT_RENDERER_DEPTH) return VPT_OK;
-    if (c.passes == 0) {
-        c.n_complete = 0;
-        memcpy(c.mvp, a.mvp_inv.m, sizeof(c.mvp));
-        c.valid = false; c.poisoned = false;
-        c.first_mix_one = fused && first_mix == 1.0f;
-    } else if (memcmp(c.mvp, a.mvp_inv.m, sizeof(c.mvp)) != 0) {
-        c.poisoned = true;
-    }
-    c.passes++;
-    if (fused && c.enabled && !c.poisoned && !r->no_split /* not while a graph is being captured: its grid would be frozen */) {
-        const bool fixed_point = k == VPT_RENDERER_DEPTH ? c.first_mix_one : (k == VPT_RENDERER_MCS ? (c.first_mix_one && r->env_opaque) : true);
-        if (c.fused_passes >= 1 && fixed_point && c.reset_seen) {
-            // ... and only into a destination whose skipped tiles already hold those values: one that a whole-image fused pass has written
-            // since the reset (a caller's render target, the slots of a bucket, the gather's ring: each takes one whole pass first)
-            bool complete = false;
-            for (int i = 0; i < c.n_complete && !complete; i++) complete = c.complete[i] == (const void *)a.render;
-            if (complete) {
-                if (!c.valid) VPT_TRY(classes_build(r, c.mvp));
-                c.list_now = c.valid && c.n_hit > 0 && c.n_miss > 0;
-            }
-        }
-    }
-    if (fused) {
-        c.fused_passes++;
-        if (!c.list_now && !c.poisoned) {                         // a whole-image pass under the reset's matrix: its destination is complete now
-            bool known = false;
-            for (int i = 0; i < c.n_complete && !known; i++) known = c.complete[i] == (const void *)a.render;
-            if (!known && c.n_complete < VPT_COMPLETE_DESTS) c.complete[c.n_complete++] = (const void *)a.render;
-        }
-    }
+    if (!c.track.pass(r->kind, a.mvp_inv.m, fused, first_mix, c.enabled, r->no_split, r->env_opaque, (const void *)a.render)) return VPT_OK;
+    if (!c.valid) VPT_TRY(classes_build(r, a.mvp_inv.m));
+    c.track.use_lists(c.valid && c.n_hit > 0 && c.n_miss > 0);
     return VPT_OK;
 }
 
@@ -73,7 +44,7 @@ extern "C" int vpt_renderer_reset(vpt_renderer *r, const vpt_uniforms *u) {
     HIP_TRY(hipSetDevice(r->ctx->device));
     PassArgs a;
     VPT_TRY(make_args(r, u, false, &a));
-    r->cls.passes = 0; r->cls.fused_passes = 0; r->cls.poisoned = false; r->cls.list_now = false; r->cls.reset_seen = true;
+    r->cls.track.reset();
     if (r->kind != VPT_RENDERER_MCM) r->cls.valid = false;
     if (r->kind == VPT_RENDERER_MCM) VPT_TRY(mcm_reset(r, a, u));
     else if (is_march_kind(r->kind)) VPT_TRY(march_reset(r, a));
@@ -139,7 +110,7 @@ int launch_fused(vpt_renderer *r, const PassArgs &a) {
     // render target, the gather ring, a multi-pass or captured sequence — leaves that output behind the render buffer)
     r->tm_valid = r->tm_valid && a.tm_table != nullptr && a.multi_passes <= 1 && !r->no_split;
     VPT_TRY(marcher_track(r, a, true, a.mix));
-    struct ListOff { vpt_renderer *r; ~ListOff() { r->cls.list_now = false; } } list_off{ r };
+    struct ListOff { vpt_renderer *r; ~ListOff() { r->cls.track.use_lists(false); } } list_off{ r };
     if (r->kind == VPT_RENDERER_MCM) return mcm_pass(r, a, true);
     if (is_march_kind(r->kind)) return march_fused(r, a);
     return extra_fused(r, a);
@@ -287,10 +258,9 @@ static int play_graph(vpt_renderer *r, PassArgs &a, const float *frame_vars, int
         VPT_TRY(rc);
         r->play_graph = fresh.release();
     } else {
-        // a cached graph is replayed without passing through launch_fused: the marchers' pass tracking is told by hand
-        for (int i = 0; i < count; i++) VPT_TRY(marcher_track(r, a, true, v[i].mix));
-        r->cls.list_now = false;
-        if (r->kind == VPT_RENDERER_MCM) r->cls.events += (uint64_t)a.steps * (uint64_t)count;   // (as mcm_pass counts them)
+        // a cached graph is replayed without passing through launch_fused: the pass tracking is told (play_form: no tile classes here)
+        for (int i = 0; i < count; i++) r->cls.track.replayed(r->kind, a.mvp_inv.m, v[i].mix, (const void *)a.render);
+        if (r->kind == VPT_RENDERER_MCM) mcm_events_run(r, (uint64_t)a.steps * (uint64_t)count);   // (as mcm_pass counts them)
     }
     {
         Timed t(r, true, (uint32_t)count);       // a replay is timed as a whole: events inside a graph cannot be read back
