@@ -12,6 +12,9 @@ The twin is the slabs stacked along z with `gap` background planes between them.
 within `halo` planes of a slab, the same texels in the twin as in the large volume as long as gap >= 2 * halo, so the numpy statement on
 the twin is the expected result there (tests/test_large_volumes_host.py shows that on small shapes for every operation the GPU tests use).
 
+Where the statement is too slow for planes of noise (reconstruction, watershed, thickness, skeleton), a slab holds a few small solids
+instead and the expected texels come from the statement on a crop round each (`solids` and what follows it).
+
 `sparse_volume` builds the vpt_amd.Volume the way Volume._from_raw_array does, without a host array of the whole volume:
 vpt_volume_create zero-fills on the device, one vpt_volume_upload_block per slab, vpt_volume_finalize."""
 import ctypes as C
@@ -35,7 +38,7 @@ class Layout:
 
     def __init__(self, shape, thick, gap, marks=(1 << 31,), even=False):
         nx, ny, nz = shape
-        self.shape, self.thick, self.gap = (nx, ny, nz), thick, gap
+        self.shape, self.thick, self.gap, self.marks = (nx, ny, nz), thick, gap, tuple(marks)
         plane = nx * ny
         starts = [0]
         for mark in marks:
@@ -146,6 +149,216 @@ def counts(blocks, nbins, shift, n):
         want += np.bincount((b.reshape(-1) >> shift).astype(np.int64), minlength=nbins)
     want[0] += n - sum(b.size for b in blocks)
     return want
+
+
+# ---- a few small solids a slab, and the statements on crops round them --------------------------------------------------------------
+# Statements that iterate to a fixed point (reconstruction, the watershed's plateaus), recurse over level sets (thickness) or visit voxels
+# one by one (thinning) cost minutes on planes of 10^6 noise voxels.  `solids` fills a slab with background but for a few small solids with
+# seeded noise inside; the expected texels come from the statement on a crop round each solid: the solid's box widened by MARGIN background
+# voxels in x and y (cut at the volume's faces, the origin lowered to an even voxel), the whole slab along z with MARGIN background planes
+# beyond it where the volume has background there and none at the volume's own first and last plane.  A crop's face is therefore a face of
+# the volume or background, its origin is even on every axis when the slab's first plane is (Layout(..., even=True)), and two crops of a
+# slab are disjoint, so two solids lie at least 2 MARGIN voxels apart.  tests/test_large_volumes_host.py shows per operation that this is
+# the statement on the whole volume.
+MARGIN = 2
+
+
+def _ball(r):
+    z, y, x = np.indices((2 * r + 1,) * 3) - r
+    return x * x + y * y + z * z <= r * r + 1
+
+
+def _shell():
+    """a cube of 7 voxels with walls of 2 round an enclosed cavity of 3: the thinning keeps a closed surface, fill_holes fills the cavity,
+    the surface closes twice"""
+    s = np.ones((7, 7, 7), bool)
+    s[2:5, 2:5, 2:5] = False
+    return s
+
+
+def _box(d, h, w):
+    return np.ones((d, h, w), bool)
+
+
+def _balls():
+    """eight balls x^2 + y^2 + z^2 <= c in a row along x, a voxel apart: the largest D, and so T2, of each is another number (2, 3, 4, 5,
+    6, 8, 9, 10)"""
+    z, y, x = np.indices((7, 7, 7)) - 3
+    return np.concatenate([np.pad(x * x + y * y + z * z <= c, ((0, 0), (0, 0), (0, 1))) for c in (1, 2, 3, 4, 5, 6, 8, 9)], axis=2)[:, :, :-1]
+
+
+def solids(lay, dtype, seed, channels=1):
+    """(blocks, crops): one block [thick][ny][nx] (two channels: [...][2]) per slab, 0 but for a few solids whose voxels hold seeded noise
+    over the upper three quarters of the codes (seeds seed, seed + 1, ... per slab), and the crops [(slab, y0, y1, x0, x1)].
+      first slab:  a box in the corner x = 0, y = 0, z = 0; a shell across the word edge x = 32 and the tile edges y = 8, z = 4; a bar along
+                   x across the word edge x = 64
+      a mark's slab:  a bar along x that holds the mark's voxel; a ball, bars along y and z, a plate
+      last slab:   a box that holds the volume's last voxel; a ball.  In a volume of more than 2^32 voxels all of it lies beyond voxel 2^32
+      every slab:  a row of eight balls of growing radius (one crop), so the thickness takes many values"""
+    nx, ny, nz = lay.shape
+    T, M = lay.thick, int(np.iinfo(dtype).max)
+    assert T >= 8 and T % 2 == 0 and lay.gap >= MARGIN and nx >= 72 and ny >= 60
+    blocks, crops = [], []
+    for i, z0 in enumerate(lay.starts):
+        rng = np.random.default_rng(seed + i)
+        marks = [m for m in lay.marks if z0 <= m // (nx * ny) < z0 + T]
+        if i == 0:
+            placed = [(_box(5, 4, 6), 0, 0, 0), (_shell(), 1, 5, 28), (_box(3, 3, 13), 2, 14, 58), (_balls(), 1, 22, 4)]
+        elif i == len(lay.starts) - 1:
+            placed = [(_box(4, 5, 6), T - 4, ny - 5, nx - 6), (_ball(3), 0, 3, 5), (_balls(), 0, 14, 4)]
+        else:
+            (m,) = marks
+            zm, ym, xm = m // (nx * ny) - z0, m // nx % ny, m % nx
+            at = (min(max(zm - 1, 0), T - 3), min(max(ym - 1, 0), ny - 3), min(max(xm - 6, 0), nx - 13))
+            yb = 2 if ym >= ny // 2 else ny - 29                   # the other solids keep to the half of the plane without the mark
+            placed = [(_box(3, 3, 13),) + at, (_ball(3), 0, yb, 10), (_box(3, 13, 3), 4, yb, 24), (_box(T, 3, 3), 0, yb + 2, 36), (_box(2, 9, 11), 3, yb + 1, 44),
+                      (_balls(), 1, yb + 18, 4)]
+            assert placed[0][0][zm - at[0], ym - at[1], xm - at[2]]
+        block = np.zeros((T, ny, nx) + ((2,) if channels == 2 else ()), dtype)
+        mine = []
+        for solid, z, y, x in placed:
+            d, h, w = solid.shape
+            assert 0 <= z and z + d <= T and 0 <= y and y + h <= ny and 0 <= x and x + w <= nx
+            block[z:z + d, y:y + h, x:x + w][solid] = rng.integers(M // 4 + 1, M + 1, size=(int(solid.sum()),) + block.shape[3:])
+            y0, x0 = max(y - MARGIN, 0), max(x - MARGIN, 0)
+            mine.append((i, y0 - y0 % 2, min(y + h + MARGIN, ny), x0 - x0 % 2, min(x + w + MARGIN, nx)))
+        for _, y0, y1, x0, x1 in mine:                              # a crop's face inside the volume is background
+            rim = [block[:, y, x0:x1] for y, inner in ((y0, y0 > 0), (y1 - 1, y1 < ny)) if inner] + [block[:, y0:y1, x] for x, inner in ((x0, x0 > 0), (x1 - 1, x1 < nx)) if inner]
+            assert not any(r.any() for r in rim)
+        for a in range(len(mine)):
+            for b in range(a):
+                (_, ay0, ay1, ax0, ax1), (_, by0, by1, bx0, bx1) = mine[a], mine[b]
+                assert ay1 <= by0 or by1 <= ay0 or ax1 <= bx0 or bx1 <= ax0, "two crops of slab %d overlap" % i
+        blocks.append(block)
+        crops += mine
+    return blocks, crops
+
+
+def crop_array(lay, blocks, crop):
+    """(the crop as an array, its origin (z, y, x) in the volume, the background planes in front of the slab's)"""
+    i, y0, y1, x0, x1 = crop
+    z0, T = lay.starts[i], lay.thick
+    lo, hi = (MARGIN if z0 > 0 else 0), (MARGIN if z0 + T < lay.shape[2] else 0)
+    inner = blocks[i][:, y0:y1, x0:x1]
+    a = np.zeros((lo + T + hi,) + inner.shape[1:], inner.dtype)
+    a[lo:lo + T] = inner
+    return a, (z0 - lo, y0, x0), lo
+
+
+def on_crops(lay, blocks, crops, statement):
+    """per slab an array [thick][ny][nx](...) of what `statement` makes of every crop, 0 elsewhere; the statement's result on a crop's
+    background planes beyond the slab must be 0 too"""
+    out = None
+    for crop in crops:
+        i, y0, y1, x0, x1 = crop
+        a, _, lo = crop_array(lay, blocks, crop)
+        r = statement(a)
+        if out is None:
+            out = [np.zeros(b.shape[:3] + r.shape[3:], r.dtype) for b in blocks]
+        assert not r[:lo].any() and not r[lo + lay.thick:].any()
+        out[i][:, y0:y1, x0:x1] = r[lo:lo + lay.thick]
+    return out
+
+
+def watershed_on_crops(lay, blocks, crops, lo, hi, polarity, connectivity, channel=0):
+    """(rank blocks, the basins as (x, y, z, voxels) of the volume) of vpt_amd.watershed_texels with lo >= 1: no basin leaves its solid, so
+    the volume's basins are the crops' together, ranked by voxel count descending, then by the root's linear index in the volume"""
+    import vpt_amd
+    assert lo >= 1
+    nx, ny, _ = lay.shape
+    found, per = [], []
+    for c, crop in enumerate(crops):
+        a, (oz, oy, ox), _ = crop_array(lay, blocks, crop)
+        ranks, basins = vpt_amd.watershed_texels(a, lo, hi, polarity, connectivity, 1, channel)
+        per.append((ranks, np.zeros(len(basins) + 1, np.uint32)))
+        found += [(-v, ((z + oz) * ny + y + oy) * nx + x + ox, c, k + 1) for k, (x, y, z, v) in enumerate(basins)]
+    found.sort()
+    for rank, (_, _, c, k) in enumerate(found):
+        per[c][1][k] = rank + 1
+    it = iter(per)
+
+    def ranked(_):                                                # (on_crops takes the crops in their order)
+        ranks, table = next(it)
+        return table[ranks]
+    return on_crops(lay, blocks, crops, ranked), [(root % nx, root // nx % ny, root // (nx * ny), -v) for v, root, _, _ in found]
+
+
+def skeleton_on_crops(lay, blocks, crops, lo, hi, mode, passes=0):
+    """(burn blocks, info) of vpt_amd.skeleton_burn_texels: a voxel's fate depends on its 26 neighbours and on the parities of its
+    coordinates only, so the crops thin independently; the counts add up and the volume needs as many passes as the slowest crop"""
+    import vpt_amd
+    infos = []
+
+    def statement(a):
+        burn, info = vpt_amd.skeleton_burn_texels(a, lo, hi, mode, passes)
+        infos.append(info)
+        return burn
+    for crop in crops:
+        assert all(o % 2 == 0 for o in crop_array(lay, blocks, crop)[1]), "the parities of a crop are not the volume's"
+    out = on_crops(lay, blocks, crops, statement)
+    info = {name: sum(i[name] for i in infos) for name in infos[0]}
+    info['passes'], info['converged'] = max(i['passes'] for i in infos), min(i['converged'] for i in infos)
+    return out, info
+
+
+def surface_on_crops(lay, blocks, crops, level, channel=0):
+    """(vertices, quads, info) of vpt_amd.surface.surface_texels: a crop's mesh is the part of the volume's in its cells (the statement
+    reads 0 outside a crop as outside the volume, and a crop keeps background round its solid).  Its vertices move by the crop's origin;
+    the volume numbers vertices by their cells in raster order and quads by the grid point g of their edge in raster order, then by the
+    axis.  The cell of a vertex is its stored coordinate div 65536 (the fraction is below 1: a cell's crossings are never all on its upper
+    face); the third vertex of a quad is the one of cell g, and the first differs from it along the two axes that are not the edge's."""
+    from vpt_amd.surface import ONE, surface_texels
+    nx, ny, nz = lay.shape
+    V, Q, base = [], [], 0
+    info = {'vertices': 0, 'quads': 0, 'inside': 0, 'crossings': [0, 0, 0]}
+    for crop in crops:
+        a, (oz, oy, ox), _ = crop_array(lay, blocks, crop)
+        mine = {}
+        v, q = surface_texels(a, level, channel, info=mine)
+        V.append(v.astype(np.int64) + np.array([ox, oy, oz], np.int64) * ONE)
+        Q.append(q.astype(np.int64) + base)
+        base += len(v)
+        for name in ('vertices', 'quads', 'inside'):
+            info[name] += mine[name]
+        info['crossings'] = [s + t for s, t in zip(info['crossings'], mine['crossings'])]
+    v, q = np.concatenate(V), np.concatenate(Q)
+    cell = v // ONE
+    key = (cell[:, 2] * (ny + 2) + cell[:, 1]) * (nx + 2) + cell[:, 0]
+    order = np.argsort(key, kind='stable')
+    assert len(np.unique(key)) == len(key)
+    number = np.empty(len(v), np.int64)
+    number[order] = np.arange(len(v))
+    axis = np.argmin(cell[q[:, 2]] - cell[q[:, 0]], axis=1)
+    assert ((cell[q[:, 2]] - cell[q[:, 0]]).sum(axis=1) == 2).all()
+    quads = number[q][np.argsort(key[q[:, 2]] * 3 + axis, kind='stable')]
+    info.update(cells=(nx + 1) * (ny + 1) * (nz + 1), level=level, width=nx, height=ny, depth=nz, channel=channel)
+    return v[order].astype(np.uint32), quads.astype(np.uint32), info
+
+
+def shift_twin_vertices(lay, vertices):
+    """the vertices of a surface of the twin as the volume has them: 65536 (z_volume - z_twin) added to the z word of each slab's (the
+    cells of a slab are its planes and the one in front: gap >= 2 keeps the slabs' cells apart); their order and the quads stay"""
+    from vpt_amd.surface import ONE
+    assert lay.gap >= 2
+    out = vertices.astype(np.int64)
+    k = out[:, 2] // ONE                                          # the cell's z + 1
+    seen = np.zeros(len(out), bool)
+    for z0, t0 in zip(lay.starts, lay.twin_starts):
+        mine = (k >= t0) & (k <= t0 + lay.thick)
+        assert not (seen & mine).any()
+        out[mine, 2] += ONE * (z0 - t0)
+        seen |= mine
+    assert seen.all()
+    return out.astype(np.uint32)
+
+
+def thickness_tiles(lay, d2_blocks):
+    """the 8 x 8 x 4 tiles of the volume that hold a voxel with D > 0"""
+    total = 0
+    for z0, d2 in zip(lay.starts, d2_blocks):
+        z, y, x = np.nonzero(d2)
+        total += len(np.unique((((z + z0) // 4) * 4096 + y // 8) * 4096 + x // 8))
+    return total
 
 
 # ---- device memory ---------------------------------------------------------------------------------------------------------------

@@ -6,7 +6,8 @@ Vertices, quads and every info field are held, byte for byte, to vpt_amd.surface
 A word of the inside plane holds 32 grid points along x of a row padded to W + 2, a word of cells 32 of a row of W + 1; a workgroup of the
 vertex kernel owns 256 words, of the quad kernel 128, a block of the prefix sums 2048 (or what _scan_words says).  The shapes are the
 smallest at which that can go wrong: widths round the word edges with voxels in the first and the last column, structures on all six
-faces, every cell active over 650 words with 2 and 3 words a scan block, the widest volume the library takes."""
+faces, every cell active over 650 words with 2 and 3 words a scan block, the widest volume the library takes, and the three shapes at which
+the grid-stride loops of k_sf_inside, of the scan kernels and of k_sf_classify make a second trip."""
 import ctypes as C
 import os
 import subprocess
@@ -126,6 +127,69 @@ def test_checkerboard_crosses_both_scan_levels(gpu_ctx, scan_words):
     voxels of a checkerboard are 0 (15 925 - 4 = 15 921 vertices by the statement)"""
     v, _ = check(gpu_ctx, checkerboard(), 1, scan_words=scan_words)
     assert len(v) == 49 * 25 * 13 - 4 == 15921
+
+
+def sprinkled(shape, seed, also):
+    """uint8 noise below 128 with a seeded 1.5 % of the voxels, the eight corners and the voxels `also` raised to a seeded code of 128 and
+    above: a surface at level 128 of many specks"""
+    rng = np.random.default_rng(seed)
+    a = rng.integers(0, 128, shape, dtype=np.uint8)
+    chosen = rng.random(shape) < 0.015
+    for z in (0, shape[0] - 1):
+        for y in (0, shape[1] - 1):
+            for x in (0, shape[2] - 1):
+                chosen[z, y, x] = True
+    for at in also:
+        chosen[at] = True
+    a[chosen] = rng.integers(128, 256, int(chosen.sum()), dtype=np.uint8)
+    return a
+
+
+def cell_words(vertices, H, cwpr=1):
+    """the word of the cell masks that holds each vertex's cell: ((k + 1) (H + 1) + j + 1) cwpr + (i + 1) div 32"""
+    cell = vertices.astype(np.int64) >> 16
+    return (cell[:, 2] * (H + 1) + cell[:, 1]) * cwpr + (cell[:, 0] >> 5)
+
+
+def test_second_trip_of_the_inside_kernels_loop(gpu_ctx):
+    """k_sf_inside: stream_grid(items, 4) launches at most 8 192 workgroups of 4 waves, and a wave takes the items wave, wave + 32 768, ...
+    An item is 64 grid points of a padded row: W = 1 gives one word and one item a row, H = D = 180 gives (H + 2) (D + 2) = 182^2 = 33 124
+    items, so the waves 0 .. 355 make a second trip.  It begins at item 32 768 = row 180 x 182 + 8: z = 179, y = 7; voxels are set there and
+    in the row before it (y = 6), the last of the first trip."""
+    H = D = 180
+    assert (H + 2) * (D + 2) == 33124 > 8192 * 4 and divmod(8192 * 4, H + 2) == (D, 8)
+    a = sprinkled((D, H, 1), 31, [(179, 6, 0), (179, 7, 0)])
+    v, _ = check(gpu_ctx, a, 128)
+    assert len(v) > 1000 and int(v[:, 2].max()) >> 16 == D and int(v[:, 2].min()) >> 16 == 0
+
+
+def test_second_trip_of_the_scan_kernels_loops(gpu_ctx):
+    """k_sf_block_sums, k_sf_scan_add: stream_grid(blocks, 1, 65 535) launches at most 65 535 workgroups, and one takes the blocks b,
+    b + 65 535, ...  With _scan_words = 1 a block is a word; W = 1 gives one word a cell row, H = D = 256 gives (H + 1) (D + 1) = 257^2 =
+    66 049 blocks, so the workgroups 0 .. 513 make a second trip, and a thread of k_sf_scan_blocks owns a run of per = ceil(66 049 / 256) =
+    259 sums (never more than 2 before).  The second trip begins at word 65 535 = cell row 255 x 257 + 0: cells j = -1, k = 254, which the
+    voxel y = 0, z = 254 makes active; word 65 534 is the cells j = 255, k = 253, of the voxel y = 255, z = 253."""
+    H = D = 256
+    words = (H + 1) * (D + 1)
+    assert words == 66049 > 65535 and (words + 255) // 256 == 259 and divmod(65535, H + 1) == (255, 0)
+    a = sprinkled((D, H, 1), 32, [(254, 0, 0), (253, 255, 0)])
+    v, _ = check(gpu_ctx, a, 128, scan_words=1)
+    w = cell_words(v, H)
+    assert 65534 in w and 65535 in w and (w < 65534).any() and (w > 65535).any()
+
+
+def test_second_trip_of_the_classify_kernels_loop(gpu_ctx):
+    """k_sf_classify: stream_grid(words) launches at most 8 192 workgroups of 256 threads, and a thread takes the words w, w + 2 097 152,
+    ...  W = 2 gives one word a cell row (W + 1 <= 32), H = D = 1448 gives (H + 1) (D + 1) = 1449^2 = 2 099 601 words, so the threads
+    0 .. 2 448 make a second trip.  It begins at word 2 097 152 = cell row 1447 x 1449 + 449: cells j = 448, k = 1446, which the voxel
+    y = 449, z = 1446 makes active; word 2 097 151 is the cells j = 447, of the voxel y = 447."""
+    H = D = 1448
+    words = (H + 1) * (D + 1)
+    assert words == 2099601 > 8192 * 256 and divmod(8192 * 256, H + 1) == (1447, 449)
+    a = sprinkled((D, H, 2), 33, [(1446, 449, 0), (1446, 447, 1)])
+    v, _ = check(gpu_ctx, a, 128)
+    w = cell_words(v, H)
+    assert 2097151 in w and 2097152 in w and (w < 2097151).any() and (w > 2097152).any()
 
 
 def test_widest_volume(gpu_ctx):

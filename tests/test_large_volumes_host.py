@@ -3,14 +3,17 @@
 The GPU tests never see a large volume's expected texels as a whole: they take them from the numpy statement applied to the twin, the
 slabs stacked with background planes between them (tests/large_volumes.py).  That rests on one equivalence, shown here for every operation
 those tests use, with the same slab layout on 11 x 9 x 40 voxels: the statement on the whole sparse volume, restricted to the planes the
-GPU tests compare, equals the statement on the twin there; and the background planes they read are what they expect."""
+GPU tests compare, equals the statement on the twin there; and the background planes they read are what they expect.  For the operations of
+tests/test_gpu_derive_large.py, whose slabs hold a few small solids, the same on 75 x 61 x 44 voxels: the statement on a crop round each
+solid, put together, equals the statement on the whole volume everywhere."""
 import numpy as np
 import pytest
 
 import vpt_amd
 from vpt_amd.resample import nearest_index
 
-from large_volumes import (TIER_A, TIER_B, REACH, Layout, voxels, volume_bytes, distance_squared_within, slab_distances, counts)
+from large_volumes import (TIER_A, TIER_B, REACH, MARGIN, Layout, voxels, volume_bytes, distance_squared_within, slab_distances, counts, solids, crop_array,
+                           on_crops, watershed_on_crops, skeleton_on_crops, surface_on_crops, shift_twin_vertices, thickness_tiles)
 
 SHAPE = (11, 9, 40)                                               # nx, ny, nz
 MARK = 11 * 9 * 21 + 5                                            # the linear voxel index the middle slab straddles
@@ -199,3 +202,146 @@ def test_the_windowed_distances_are_the_statement_where_they_are_small():
             small = got <= reach * reach + 2 * reach
             assert np.array_equal(got[small], exact[small]) and small.any()
             assert np.array_equal(got[exact <= reach * reach], exact[exact <= reach * reach])
+
+
+# ---- solids: reconstruction, watershed, thickness, skeleton, surface ----------------------------------------------------------------
+# The solids need 72 voxels along x (a bar across the word edge x = 64) and room for a mark's bar beside the other solids of its slab, so
+# these run on 75 x 61 x 44 voxels; the mark is a voxel of plane 20, row 55.
+SOLID_SHAPE = (75, 61, 44)
+SOLID_MARK = (20 * 61 + 55) * 75 + 40
+
+
+def solid_layout(gap=2):
+    return Layout(SOLID_SHAPE, 8, gap, marks=(SOLID_MARK,), even=True)
+
+
+def test_the_solids_lie_where_the_large_tests_need_them():
+    for shape, marks in [(SOLID_SHAPE, (SOLID_MARK,))] + [(s, (1 << 31,)) for s in list(TIER_A.values()) + list(TIER_B.values())]:
+        nx, ny, nz = shape
+        lay = Layout(shape, 8, 2, marks=marks, even=True)
+        blocks, crops = solids(lay, np.uint8, 1)
+        assert blocks[0][0, 0, 0] and blocks[-1][-1, -1, -1]                                 # the corner x = y = z = 0 and the volume's last voxel
+        m = marks[0]
+        z = m // (nx * ny)
+        (slab,) = [i for i, z0 in enumerate(lay.starts) if z0 <= z < z0 + 8]
+        assert blocks[slab][z - lay.starts[slab], m // nx % ny, m % nx]                     # the mark's voxel
+        first = blocks[0] > 0
+        assert first[:, :, 31].any() and first[:, :, 32].any() and first[:, :, 63].any() and first[:, :, 64].any()      # word edges along x
+        assert first[:, 7, 28:35].any() and first[:, 8, 28:35].any() and first[3, :, 28:35].any() and first[4, :, 28:35].any()      # tile edges y = 8, z = 4
+        if voxels(shape) > 1 << 32:
+            assert lay.starts[-1] * nx * ny > 1 << 32                                        # all of the last slab lies beyond voxel 2^32
+        assert len({i for i, *_ in crops}) == 3 and all(o % 2 == 0 for c in crops for o in crop_array(lay, blocks, c)[1])
+        inside = [np.zeros(b.shape, bool) for b in blocks]
+        for i, y0, y1, x0, x1 in crops:
+            inside[i][:, y0:y1, x0:x1] = True
+        assert not any(b[~w].any() for b, w in zip(blocks, inside))                          # nothing lies outside the crops
+        assert all(len(np.unique(b)) >= 8 for b in blocks)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_reconstruction_on_crops(dtype):
+    """By dilation (and the operations built on it: hmax, dome): a voxel rises only along paths inside the mask, and background (0) parts
+    the solids and the slabs, so one background plane between two slabs is enough.  The erosion side (fill_holes): the background falls from
+    the marker on the volume's faces; a crop's faces are faces of the volume or background that is connected to one, in the volume as in the
+    crop (the first and the last slab touch the z faces in both, the others keep MARGIN background planes)."""
+    M = int(np.iinfo(dtype).max)
+    lay = solid_layout()
+    mask, crops = solids(lay, dtype, 3)
+    other, _ = solids(lay, dtype, 13)
+    marker = [np.where(np.random.default_rng(23 + i).random(b.shape) < 0.1, b, 0).astype(dtype) for i, b in enumerate(other)]
+    pair = [np.ascontiguousarray(np.stack([a, b], axis=-1)) for a, b in zip(marker, mask)]
+    for connectivity in (6, 26):
+        whole = vpt_amd.reconstruct_texels(lay.whole(marker), lay.whole(mask), 'dilation', connectivity)
+        got = on_crops(lay, pair, crops, lambda a: vpt_amd.reconstruct_texels(a, a, 'dilation', connectivity, 0, 1))
+        assert np.array_equal(whole, lay.whole(got)) and len(np.unique(whole)) >= 8
+        assert (whole != np.minimum(lay.whole(marker), lay.whole(mask))).any()               # something rose
+    for op, h, connectivity in (('fill_holes', 0, 6), ('fill_holes', 0, 26), ('dome', M // 8, 6), ('hmax', M // 8, 26), ('minima', 0, 6)):
+        whole = vpt_amd.geodesic_texels(lay.whole(mask), op, h, connectivity)
+        floor = M if op == 'minima' else 0                                                   # the background is one minimum: M everywhere on it
+        got = on_crops(lay, mask, crops, lambda a: floor ^ vpt_amd.geodesic_texels(a, op, h, connectivity))
+        assert np.array_equal(whole, floor ^ lay.whole(got)), op
+        assert (whole[lay.between()] == floor).all()
+        assert len(np.unique(whole)) >= (2 if op == 'minima' else 8)
+        if op == 'fill_holes':
+            assert (whole > lay.whole(mask)).sum() >= 27                                     # the shell's cavity
+    # the second channel of a two-channel source
+    both, crops2 = solids(lay, dtype, 5, channels=2)
+    assert crops2 == crops
+    whole = vpt_amd.geodesic_texels(lay.whole(both), 'hmax', M // 8, 6, 1)
+    assert np.array_equal(whole, lay.whole(on_crops(lay, both, crops, lambda a: vpt_amd.geodesic_texels(a, 'hmax', M // 8, 6, 1))))
+    assert not np.array_equal(whole, vpt_amd.geodesic_texels(lay.whole(both), 'hmax', M // 8, 6, 0))
+
+
+@pytest.mark.parametrize("polarity,connectivity", [('minima', 6), ('maxima', 26)])
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_watershed_on_crops(dtype, polarity, connectivity):
+    """lo >= 1: the background is outside the domain, no basin leaves its solid; one background plane parts the slabs."""
+    M = int(np.iinfo(dtype).max)
+    lay = solid_layout()
+    blocks, crops = solids(lay, dtype, 7)
+    ranks, listed = vpt_amd.watershed_texels(lay.whole(blocks), 1, M, polarity, connectivity)
+    got, got_listed = watershed_on_crops(lay, blocks, crops, 1, M, polarity, connectivity)
+    assert listed == got_listed and len(listed) >= 16 and len({c[3] for c in listed}) >= 3
+    assert np.array_equal(ranks, lay.whole(got))
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_thickness_on_crops(dtype):
+    """seeds 'rest': D inside a solid is the distance to the nearest background voxel, which lies in the solid's box widened by one voxel,
+    and the balls stay inside their solid.  (gap + 1)^2 exceeds the largest D."""
+    M = int(np.iinfo(dtype).max)
+    lay = solid_layout(4)
+    blocks, crops = solids(lay, dtype, 9)
+    d2 = vpt_amd.distance_squared_texels(lay.whole(blocks), 1, M, 'rest')
+    got_d2 = on_crops(lay, blocks, crops, lambda a: vpt_amd.distance_squared_texels(a, 1, M, 'rest'))
+    assert np.array_equal(d2, lay.whole(got_d2))
+    assert int(d2.max()) < (lay.gap + 1) ** 2 and int(d2.max()) < (MARGIN + 1) ** 2 + 8
+    t2 = vpt_amd.thickness_squared_texels(d2)
+    got = on_crops(lay, blocks, crops, lambda a: vpt_amd.thickness_squared_texels(vpt_amd.distance_squared_texels(a, 1, M, 'rest')))
+    assert np.array_equal(t2, lay.whole(got)) and len(np.unique(t2)) >= 8
+    z, y, x = np.nonzero(d2)
+    assert thickness_tiles(lay, got_d2) == len(set(zip(z // 4, y // 8, x // 8)))
+    pair = on_crops(lay, blocks, crops, lambda a: vpt_amd.thickness_texels(a, 1, M, 3))
+    assert np.array_equal(vpt_amd.thickness_texels(lay.whole(blocks), 1, M, 3), lay.whole(pair))
+
+
+@pytest.mark.parametrize("mode", ['ends', 'kernel', 'isthmus'])
+def test_skeleton_on_crops(mode):
+    """gap >= 2 and even, and every crop's origin is even: the eight subfields of a pass are the parities of (x, y, z)."""
+    lay = solid_layout()
+    assert lay.gap >= 2 and lay.gap % 2 == 0 and all(z % 2 == 0 for z in lay.starts)
+    blocks, crops = solids(lay, np.uint8, 11)
+    burn, info = vpt_amd.skeleton_burn_texels(lay.whole(blocks), 1, 255, mode)
+    got, got_info = skeleton_on_crops(lay, blocks, crops, 1, 255, mode)
+    assert info == got_info and info['kept_voxels'] > 0 and info['passes'] >= 3
+    assert np.array_equal(burn, lay.whole(got))
+    # a crop moved by one voxel thins otherwise: the parities matter
+    moved = np.zeros((8, 12, 14), np.uint8)
+    moved[1:7, 3:9, 3:12] = 200
+    moved[2:4, 2:5, 2:4] = 200
+    assert not np.array_equal(vpt_amd.skeleton_burn_texels(moved, 1, 255, mode)[0][:, :, 1:],
+                              vpt_amd.skeleton_burn_texels(np.roll(moved, -1, axis=2), 1, 255, mode)[0][:, :, :-1])
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_surface_on_crops_and_on_the_twin(dtype):
+    from vpt_amd.surface import surface_texels
+    M = int(np.iinfo(dtype).max)
+    lay = solid_layout()
+    for channels, channel in ((1, 0), (2, 1)):
+        blocks, crops = solids(lay, dtype, 15, channels)
+        info = {}
+        v, q = surface_texels(lay.whole(blocks), M // 2, channel, info=info)
+        gv, gq, got_info = surface_on_crops(lay, blocks, crops, M // 2, channel)
+        assert info == got_info and len(v) >= 1000
+        assert np.array_equal(v, gv) and np.array_equal(q, gq)
+    # noise slabs: the twin's vertices moved along z, the quads as they are (gap >= 2)
+    for thick in (1, 2):
+        lay = Layout(SOLID_SHAPE, thick, 2, marks=(SOLID_MARK,))
+        blocks = lay.noise(dtype, 17)
+        level = M - (M + 1) // 16 + 1
+        info, twin_info = {}, {}
+        v, q = surface_texels(lay.whole(blocks), level, info=info)
+        tv, tq = surface_texels(lay.twin(blocks), level, info=twin_info)
+        assert np.array_equal(v, shift_twin_vertices(lay, tv)) and np.array_equal(q, tq) and len(v) >= 1000
+        assert {k: info[k] for k in ('vertices', 'quads', 'inside', 'crossings')} == {k: twin_info[k] for k in ('vertices', 'quads', 'inside', 'crossings')}
