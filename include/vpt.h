@@ -473,6 +473,85 @@ VPT_API int vpt_skeleton_profile(vpt_skeleton *sk, double *ms, uint64_t *launche
 VPT_API int vpt_volume_skeleton_capped(vpt_volume *src, uint32_t lo, uint32_t hi, int mode, int passes, int flags, vpt_skeleton **out);
 VPT_API int vpt_skeleton_destroy(vpt_skeleton *sk);
 
+/* ---- skeleton graph: branches, nodes, step counts and spur pruning, on the device (extension; DESIGN.md "Skeleton graph") */
+/* What a centreline is for: how many branches there are, how long each is, where they meet and which are only spurs.  Every field is an
+ * integer and the result is a pure function of the input, whatever the order of work.
+ *   Input: a set K of voxels: the voxels of an R8 / R16 volume whose code lies in lo .. hi, compared as whole unsigned codes
+ *   (vpt_volume_graph), or the kept voxels (burn == VPT_THIN_KEPT) of a skeleton (vpt_skeleton_graph).  Everything outside K, and everything
+ *   outside the volume, is absent.  The contract holds for any set, thin or not.
+ *   Classes: deg(p) = |N26(p) & K|; class(p) = 0 for p outside K, otherwise 1 + min(deg(p), 3): 1 isolated, 2 end, 3 regular, 4 junction.
+ *   Branches: the 26-connected components of the voxels of class 1 .. 3.  Nodes: the 26-connected components of the voxels of class 4.
+ *   Both are labelled in the components' canonical order (voxels descending, then root index ascending; ranks from 1).  A branch voxel has
+ *   at most two neighbours in K, so a branch is one voxel, a simple path or a simple cycle.
+ *   Branch record (struct vpt_graph_branch, 64 bytes, no padding), with linear index = (z height + y) width + x:
+ *     voxels        the branch's voxels
+ *     free_ends     its voxels of class 2
+ *     attachments   the pairs (branch voxel, 26-adjacent node voxel)
+ *     node_lo, _hi  the smallest and largest node rank over those pairs, 0 / 0 when there are none
+ *     steps_face, steps_edge, steps_corner
+ *                   the unordered 26-adjacent pairs inside the branch, plus the attachment pairs, by how many coordinates differ (1, 2, 3)
+ *     tip_lo, _hi   the smallest and largest linear index among the branch's voxels with fewer than two neighbours in their own branch;
+ *                   for a cycle both are its root (its smallest linear index)
+ *     kind          from the other fields, the first line that applies:
+ *                     VPT_GRAPH_SEGMENT   free_ends == 2
+ *                     VPT_GRAPH_SPUR      free_ends == 1 && attachments == 1
+ *                     VPT_GRAPH_LINK      attachments == 2 && node_lo != node_hi
+ *                     VPT_GRAPH_LOOP      attachments == 2 && node_lo == node_hi
+ *                     VPT_GRAPH_ISOLATED  voxels == 1            (free_ends == 0 && attachments == 0)
+ *                     VPT_GRAPH_CYCLE     otherwise              (free_ends == 0 && attachments == 0 && voxels >= 3)
+ *   It follows that free_ends + attachments is 0 or 2; that the steps add up to voxels - 1 + attachments for a path, to voxels for a cycle and
+ *   to 0 for an isolated voxel; and that the nodes' degrees add up to the branches' attachments.
+ *   Node record (struct vpt_graph_node): voxels; degree, the attachment pairs that name the node.
+ *   In numpy: vpt_amd.graph.graph_texels (the authority); in plain JS: js/vpt/graph.js.
+ * Length is derived on the host only: (steps_face + sqrt 2 steps_edge + sqrt 3 steps_corner) times a spacing.  It assumes cubic voxels
+ * (vpt_volume_resample makes them).
+ * vpt_volume_graph and vpt_skeleton_graph run on the context's stream behind any upload into src and they block, like
+ * vpt_volume_components: the labelling reads counts back.  The source and the skeleton are not changed and may be destroyed afterwards.  Two
+ * runs give identical bytes.  An empty K gives a graph of zero branches and nodes.  Formats other than R8 / R16: VPT_ERR_UNSUPPORTED, naming
+ * the format.  More than 2^32 - 2 voxels, or more than 4096 along an axis: VPT_ERR_UNSUPPORTED.  A null argument, lo > hi, hi beyond the
+ * format's largest code: VPT_ERR_INVALID.  A failed allocation: VPT_ERR_HIP, nothing is leaked. */
+#define VPT_GRAPH_ISOLATED 0
+#define VPT_GRAPH_SEGMENT  1
+#define VPT_GRAPH_SPUR     2
+#define VPT_GRAPH_LINK     3
+#define VPT_GRAPH_LOOP     4
+#define VPT_GRAPH_CYCLE    5
+#define VPT_GRAPH_PRUNE_DEBRIS 1u
+typedef struct vpt_graph vpt_graph;
+struct vpt_graph_branch { uint32_t voxels, free_ends, attachments, kind, node_lo, node_hi; uint64_t steps_face, steps_edge, steps_corner, tip_lo, tip_hi; };
+struct vpt_graph_node { uint64_t voxels, degree; };
+/* kept_voxels = |K|; node_voxels: those of class 4; the six counts of kinds add up to branches; the step and attachment totals are over all
+ * branches */
+struct vpt_graph_info { uint64_t kept_voxels, node_voxels, branches, nodes, isolated, segments, spurs, links, loops, cycles,
+                        steps_face, steps_edge, steps_corner, attachments; };
+VPT_API int vpt_volume_graph(vpt_volume *src, uint32_t lo, uint32_t hi, vpt_graph **out);
+VPT_API int vpt_skeleton_graph(vpt_skeleton *sk, vpt_graph **out);
+VPT_API int vpt_graph_info(vpt_graph *g, struct vpt_graph_info *info);
+/* the records of the branches / nodes of rank first + 1 .. first + n; a window not within the count: VPT_ERR_INVALID; n = 0 checks the
+ * arguments and writes nothing (dst may then be null) */
+VPT_API int vpt_graph_branches(vpt_graph *g, uint64_t first, uint64_t n, struct vpt_graph_branch *dst);
+VPT_API int vpt_graph_nodes(vpt_graph *g, uint64_t first, uint64_t n, struct vpt_graph_node *dst);
+/* the branches / the nodes as a new vpt_components handle that the caller owns (vpt_components_destroy) and that outlives the graph: ranks
+ * are branch / node ranks, the texel snapshot is the source's codes (for vpt_skeleton_graph: the skeleton's own snapshot), so
+ * vpt_components_keep, _keep_set, _label, _ranks, _list and _measure work on branches and nodes unchanged and speak in source codes:
+ * measure(values = a thickness pair, channel 1) gives the mean and the largest radius per branch. */
+VPT_API int vpt_graph_branch_components(vpt_graph *g, vpt_components **out);
+VPT_API int vpt_graph_node_components(vpt_graph *g, vpt_components **out);
+/* a new, finalized RG8 / RG16 volume with the source's filter: (code, class): a row of a 2-D transfer function colours ends and junctions */
+VPT_API int vpt_graph_classes(vpt_graph *g, vpt_volume **out);
+/* a new, finalized volume of the source's size, format and filter: the source code where the voxel is in K and its branch is not dropped,
+ * `fill` elsewhere.  A branch is dropped when wf steps_face + we steps_edge + wc steps_corner <= length (64-bit arithmetic) and it is a SPUR,
+ * or flag bit 0 (VPT_GRAPH_PRUNE_DEBRIS) is set and it is a SEGMENT or ISOLATED.  Node voxels always stay, so with flags = 0 the result has
+ * as many 26-components as K.  One round: all spurs of a node go together (a Y whose three arms are all within `length` is reduced to its
+ * node), and the result is not thinned again.  A weight above 65535, fill above the format's largest code, unknown flag bits, a null
+ * argument: VPT_ERR_INVALID. */
+VPT_API int vpt_graph_prune(vpt_graph *g, uint64_t length, uint32_t wf, uint32_t we, uint32_t wc, uint32_t flags, uint32_t fill, vpt_volume **out);
+/* (for measurements) ms[VPT_GRAPH_PHASES]: seed, classify (counts, prefix sums, classes and the kept-voxel list), branch labelling, node
+ * labelling, links, host ordering; the stream drained after each; launches: kernels of this unit launched (the labellings' are theirs) */
+#define VPT_GRAPH_PHASES 6
+VPT_API int vpt_graph_profile(vpt_graph *g, double *ms, uint64_t *launches);
+VPT_API int vpt_graph_destroy(vpt_graph *g);
+
 /* ---- isosurface mesh by naive surface nets, on the device (extension; DESIGN.md "Surface") */
 /* What hands a structure's surface to everything else (printing, simulation, CAD, a mesh viewer), and a surface area better than a count
  * of voxel faces: one vertex per cell the surface crosses, one quad per grid edge it crosses.  No case table; vertices are shared and the

@@ -611,6 +611,95 @@ static napi_value SkeletonDestroy(napi_env env, napi_callback_info info) {
     VPT_CHECK(vpt_skeleton_destroy(k));
     return undefined(env);
 }
+// ---- graph ----------------------------------------------------------------------------------------------
+// volumeGraph(volume, lo, hi) -> a graph handle
+static napi_value VolumeGraph(napi_env env, napi_callback_info info) {
+    napi_value a[3]; vpt_volume *v; uint32_t lo, hi;
+    if (!get_args(env, info, 3, a) || !get_handle(env, a[0], &v) || !get_u32(env, a[1], &lo) || !get_u32(env, a[2], &hi)) return nullptr;
+    vpt_graph *out = nullptr;
+    VPT_CHECK(vpt_volume_graph(v, lo, hi, &out));
+    return make_external(env, out);
+}
+// skeletonGraph(skeleton) -> a graph handle
+static napi_value SkeletonGraph(napi_env env, napi_callback_info info) {
+    napi_value a[1]; vpt_skeleton *k;
+    if (!get_args(env, info, 1, a) || !get_handle(env, a[0], &k)) return nullptr;
+    vpt_graph *out = nullptr;
+    VPT_CHECK(vpt_skeleton_graph(k, &out));
+    return make_external(env, out);
+}
+// graphInfo(graph) -> the fourteen fields of struct vpt_graph_info, in its order
+static napi_value GraphInfo(napi_env env, napi_callback_info info) {
+    napi_value a[1]; vpt_graph *g;
+    if (!get_args(env, info, 1, a) || !get_handle(env, a[0], &g)) return nullptr;
+    struct vpt_graph_info i;
+    VPT_CHECK(vpt_graph_info(g, &i));
+    const uint64_t fields[14] = { i.kept_voxels, i.node_voxels, i.branches, i.nodes, i.isolated, i.segments, i.spurs, i.links, i.loops, i.cycles,
+                                  i.steps_face, i.steps_edge, i.steps_corner, i.attachments };
+    napi_value out;
+    napi_create_array_with_length(env, 14, &out);
+    for (int f = 0; f < 14; f++) napi_set_element(env, out, f, number(env, (double)fields[f]));
+    return out;
+}
+// graphBranches(graph, first, dst): dst holds 64 n bytes, the records (struct vpt_graph_branch) of branches first .. first + n - 1;
+// graphNodes(graph, first, dst): 16 n bytes (struct vpt_graph_node); js/vpt/Volume.js reads the fields out
+static napi_value GraphBranches(napi_env env, napi_callback_info info) {
+    napi_value a[3]; vpt_graph *g; uint64_t first; void *data; size_t n;
+    if (!get_args(env, info, 3, a) || !get_handle(env, a[0], &g) || !get_u64(env, a[1], &first) || !get_bytes(env, a[2], &data, &n)) return nullptr;
+    VPT_CHECK(vpt_graph_branches(g, first, n / sizeof(struct vpt_graph_branch), (struct vpt_graph_branch *)data));
+    return undefined(env);
+}
+static napi_value GraphNodes(napi_env env, napi_callback_info info) {
+    napi_value a[3]; vpt_graph *g; uint64_t first; void *data; size_t n;
+    if (!get_args(env, info, 3, a) || !get_handle(env, a[0], &g) || !get_u64(env, a[1], &first) || !get_bytes(env, a[2], &data, &n)) return nullptr;
+    VPT_CHECK(vpt_graph_nodes(g, first, n / sizeof(struct vpt_graph_node), (struct vpt_graph_node *)data));
+    return undefined(env);
+}
+// graphComponents(graph, which) -> a components handle the caller owns; which 0: the branches, 1: the nodes
+static napi_value GraphComponents(napi_env env, napi_callback_info info) {
+    napi_value a[2]; vpt_graph *g; int32_t which;
+    if (!get_args(env, info, 2, a) || !get_handle(env, a[0], &g) || !get_i32(env, a[1], &which)) return nullptr;
+    vpt_components *out = nullptr;
+    if (which == 0) VPT_CHECK(vpt_graph_branch_components(g, &out));
+    else VPT_CHECK(vpt_graph_node_components(g, &out));
+    return make_external(env, out);
+}
+// graphClasses(graph) -> a new volume handle
+static napi_value GraphClasses(napi_env env, napi_callback_info info) {
+    napi_value a[1]; vpt_graph *g;
+    if (!get_args(env, info, 1, a) || !get_handle(env, a[0], &g)) return nullptr;
+    vpt_volume *out = nullptr;
+    VPT_CHECK(vpt_graph_classes(g, &out));
+    return make_external(env, out);
+}
+// graphPrune(graph, length, wf, we, wc, flags, fill) -> a new volume handle; length: a BigUint64Array of one element (every 64-bit length)
+static napi_value GraphPrune(napi_env env, napi_callback_info info) {
+    napi_value a[7]; vpt_graph *g; void *data; size_t n; uint32_t wf, we, wc, flags, fill;
+    if (!get_args(env, info, 7, a) || !get_handle(env, a[0], &g) || !get_bytes(env, a[1], &data, &n)) return nullptr;
+    if (n != sizeof(uint64_t)) { napi_throw_type_error(env, nullptr, "expected a BigUint64Array of one element"); return nullptr; }
+    if (!get_u32(env, a[2], &wf) || !get_u32(env, a[3], &we) || !get_u32(env, a[4], &wc) || !get_u32(env, a[5], &flags) || !get_u32(env, a[6], &fill)) return nullptr;
+    vpt_volume *out = nullptr;
+    VPT_CHECK(vpt_graph_prune(g, *(const uint64_t *)data, wf, we, wc, flags, fill, &out));
+    return make_external(env, out);
+}
+// graphProfile(graph) -> [ms seed, ms classify, ms branches, ms nodes, ms links, ms host, launches]
+static napi_value GraphProfile(napi_env env, napi_callback_info info) {
+    napi_value a[1]; vpt_graph *g;
+    if (!get_args(env, info, 1, a) || !get_handle(env, a[0], &g)) return nullptr;
+    double ms[VPT_GRAPH_PHASES]; uint64_t launches = 0;
+    VPT_CHECK(vpt_graph_profile(g, ms, &launches));
+    napi_value out;
+    napi_create_array_with_length(env, VPT_GRAPH_PHASES + 1, &out);
+    for (int p = 0; p < VPT_GRAPH_PHASES; p++) napi_set_element(env, out, p, number(env, ms[p]));
+    napi_set_element(env, out, VPT_GRAPH_PHASES, number(env, (double)launches));
+    return out;
+}
+static napi_value GraphDestroy(napi_env env, napi_callback_info info) {
+    napi_value a[1]; vpt_graph *g;
+    if (!get_args(env, info, 1, a) || !get_handle(env, a[0], &g)) return nullptr;
+    VPT_CHECK(vpt_graph_destroy(g));
+    return undefined(env);
+}
 // ---- surface --------------------------------------------------------------------------------------------
 // volumeSurface(volume, channel, level, scanWords) -> a surface handle; scanWords < 0: vpt_volume_surface, otherwise vpt_volume_surface_capped
 static napi_value VolumeSurface(napi_env env, napi_callback_info info) {
@@ -991,6 +1080,9 @@ static napi_value Init(napi_env env, napi_value exports) {
     EXPORT("distanceDestroy", DistanceDestroy); EXPORT("distanceThickness", DistanceThickness); EXPORT("distanceThicknessTimed", DistanceThicknessTimed);
     EXPORT("volumeSkeleton", VolumeSkeleton); EXPORT("skeletonInfo", SkeletonInfo); EXPORT("skeletonBurn", SkeletonBurn); EXPORT("skeletonWithin", SkeletonWithin);
     EXPORT("skeletonProfile", SkeletonProfile); EXPORT("skeletonDestroy", SkeletonDestroy);
+    EXPORT("volumeGraph", VolumeGraph); EXPORT("skeletonGraph", SkeletonGraph); EXPORT("graphInfo", GraphInfo); EXPORT("graphBranches", GraphBranches);
+    EXPORT("graphNodes", GraphNodes); EXPORT("graphComponents", GraphComponents); EXPORT("graphClasses", GraphClasses); EXPORT("graphPrune", GraphPrune);
+    EXPORT("graphProfile", GraphProfile); EXPORT("graphDestroy", GraphDestroy);
     EXPORT("volumeSurface", VolumeSurface); EXPORT("surfaceInfo", SurfaceInfo); EXPORT("surfaceVertices", SurfaceVertices); EXPORT("surfaceQuads", SurfaceQuads);
     EXPORT("surfaceProfile", SurfaceProfile); EXPORT("surfaceDestroy", SurfaceDestroy);
     EXPORT("rendererCreate", RendererCreate); EXPORT("rendererDestroy", RendererDestroy); EXPORT("rendererSetShard", RendererSetShard);

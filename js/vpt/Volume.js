@@ -12,6 +12,7 @@ const { COMBINE_STATS, checkCombineOp, checkCombineChannel, checkCombineWeights,
 const { checkReconstructOp, checkGeodesicOp, checkGeodesicH, checkSourceChannel } = require('./reconstruct.js');
 const { checkPolarity } = require('./watershed.js');
 const { THIN_KEPT, SKELETON_INFO_FIELDS, checkThinMode, checkSkeletonRange, checkThinPasses, checkBurnWithin } = require('./skeleton.js');
+const graphHost = require('./graph.js');
 const surfaceHost = require('./surface.js');
 const { RAWReader, GL_RED, GL_RG, GL_RGB, GL_RGBA, GL_UNSIGNED_BYTE, GL_FLOAT, GL_HALF_FLOAT, GL_BYTE } = R;
 
@@ -643,9 +644,46 @@ skeleton(lo, hi, mode, passes, flags) {
     return new Skeleton(this, N.volumeSkeleton(this.texture, lo, hi, code, passes, flags !== undefined && flags !== null ? flags : -1));
 }
 // the voxels of the codes lo .. hi that survive the thinning (mode default 'ends') keep their codes; 0 elsewhere
-centreline(lo, hi, mode) {
-    const k = this.skeleton(lo, hi, mode);
-    try { return k.volume(); } finally { k.destroy(); }
+// with prune (a length in the default step weights 10 / 14 / 17), up to pruneRounds (default 1) times: the skeleton's graph, its spurs within
+// prune dropped (Graph.prune), the rest thinned again; a round that drops nothing ends it.  The pruned volume is filled with a code outside
+// lo .. hi (0 when lo > 0, otherwise hi + 1), so a range that covers every code is refused with prune set
+centreline(lo, hi, mode, prune, pruneRounds) {
+    if (prune === undefined || prune === null) {
+        const k = this.skeleton(lo, hi, mode);
+        try { return k.volume(); } finally { k.destroy(); }
+    }
+    const norm16 = this.nativeFormat() === native().VPT_FORMAT_R16;
+    checkSkeletonRange(lo, hi, norm16 ? 65535 : 255);
+    pruneRounds = pruneRounds !== undefined && pruneRounds !== null ? pruneRounds : 1;
+    if (!Number.isInteger(prune) || prune < 0) { throw new Error('prune is a non-negative integer, not ' + JSON.stringify(prune)); }
+    if (!Number.isInteger(pruneRounds) || pruneRounds < 1 || pruneRounds > 65535) { throw new Error('pruneRounds is an integer in 1 .. 65535, not ' + JSON.stringify(pruneRounds)); }
+    if (lo === 0 && hi >= (norm16 ? 65535 : 255)) { throw new Error(`centreline with prune: the range [${lo}, ${hi}] covers every code, none is left to fill with`); }
+    const fill = lo > 0 ? 0 : hi + 1;
+    let k = this.skeleton(lo, hi, mode);
+    try {
+        for (let round = 0; round < pruneRounds; round++) {
+            const g = k.graph();
+            let pruned;
+            try {
+                if (!graphHost.graphDropped(g.branchRecords(), prune).some(Boolean)) { break; }
+                pruned = g.prune(prune, undefined, false, fill);
+            } finally { g.destroy(); }
+            let again;
+            try { again = pruned.skeleton(lo, hi, mode); } finally { pruned.destroy(); }
+            k.destroy();
+            k = again;
+        }
+        return k.volume();
+    } finally { k.destroy(); }
+}
+
+// ---- extension: the graph of a voxel set: branches, nodes, step counts, spur pruning (include/vpt.h; DESIGN.md "Skeleton graph") ----
+// the graph of the voxels of the codes lo .. hi of this (R8 / R16) volume as a Graph object, built on the device (js/vpt/graph.js states the
+// contract): meant for a thinned set (centreline), defined for any.  The object owns what it needs; this volume is not changed
+graph(lo, hi) {
+    const N = native(), norm16 = this.nativeFormat() === N.VPT_FORMAT_R16;
+    graphHost.checkGraphRange(lo, hi, norm16 ? 65535 : 255);
+    return new Graph(this, N.volumeGraph(this.texture, lo, hi));
 }
 
 // ---- extension: isosurface mesh by naive surface nets (include/vpt.h; DESIGN.md "Surface") ----
@@ -751,6 +789,98 @@ volume() { return this.within(THIN_KEPT, THIN_KEPT, 0); }
 profile() {
     const r = native().skeletonProfile(this._handle());
     return { ms: { seed: r[0], border: r[1], steps: r[2], census: r[3] }, launches: r[4], tiles: r[5] };
+}
+
+// the graph of the kept voxels as a Graph object, built on the device; its emitters and its branches / nodes speak in the codes of this
+// skeleton's source.  This object is not changed
+graph() { return new Graph(fieldSource(this), native().skeletonGraph(this._handle())); }
+
+close() { this.destroy(); }
+
+}
+
+// what VoxelField reads of its source, for a field made of another field: the description of that field's source
+function fieldSource(field) {
+    const N = native();
+    return { _gl: field._gl, nativeFormat: () => (field._norm16 ? N.VPT_FORMAT_R16 : N.VPT_FORMAT_R8), modality: Object.assign({}, field._modality),
+        metadata: { meta: Object.assign({}, field._meta) } };
+}
+
+// The graph of a set of voxels (Volume.graph, Skeleton.graph): the class of every voxel, the branches and the nodes as two labellings and one
+// record per branch and node, on the device.  Build once; list, measure, prune and colour several times.  Outlives what it was made from;
+// destroy() (or close()) frees the device memory (branches and nodes once taken are the caller's).
+class Graph extends VoxelField {
+
+constructor(source, handle) {
+    super(source, handle, 'graph', 'graphDestroy', null);
+    this._branches = null; this._nodes = null;
+}
+
+// { kept_voxels, node_voxels, branches, nodes, isolated, segments, spurs, links, loops, cycles, steps_face, steps_edge, steps_corner, attachments }
+get info() {
+    const i = native().graphInfo(this._handle()), out = {};
+    graphHost.GRAPH_INFO_FIELDS.forEach((f, k) => { out[f] = i[k]; });
+    return out;
+}
+
+// the branches / the nodes as a Components object (made at the first use; the caller destroys it): ranks are branch / node ranks, texels the
+// source's codes, so measure, keepSet, keep and label work on them unchanged
+get branches() {
+    if (!this._branches) { this._branches = new Components(fieldSource(this), native().graphComponents(this._handle(), 0)); }
+    return this._branches;
+}
+get nodes() {
+    if (!this._nodes) { this._nodes = new Components(fieldSource(this), native().graphComponents(this._handle(), 1)); }
+    return this._nodes;
+}
+
+_window(first, n, count, what) {
+    first = first !== undefined && first !== null ? first : 0;
+    n = n !== undefined && n !== null ? n : count - first;
+    if (!Number.isInteger(first) || !Number.isInteger(n) || first < 0 || first > count || n < 0 || n > count - first) {
+        throw new Error(`${what} ${JSON.stringify(first)} .. +${JSON.stringify(n)} are not within the ${count} of the graph`);
+    }
+    return [first, n];
+}
+
+// one record per branch of rank first + 1 .. first + n (default: all): { voxels, free_ends, attachments, kind, node_lo, node_hi, steps_face,
+// steps_edge, steps_corner, tip_lo, tip_hi } as numbers (js/vpt/graph.js GRAPH_BRANCH_FIELDS; the 64-bit fields are exact below 2^53)
+branchRecords(first, n) {
+    const w = this._window(first, n, this.info.branches, 'branches'), bytes = new ArrayBuffer(64 * w[1]), view = new DataView(bytes), out = [];
+    native().graphBranches(this._handle(), w[0], new Uint8Array(bytes));
+    for (let k = 0; k < w[1]; k++) {
+        const r = {};
+        graphHost.GRAPH_BRANCH_FIELDS.forEach((f, j) => { r[f] = j < 6 ? view.getUint32(64 * k + 4 * j, true) : Number(view.getBigUint64(64 * k + 24 + 8 * (j - 6), true)); });
+        out.push(r);
+    }
+    return out;
+}
+// one record per node: { voxels, degree }
+nodeRecords(first, n) {
+    const w = this._window(first, n, this.info.nodes, 'nodes'), bytes = new ArrayBuffer(16 * w[1]), view = new DataView(bytes), out = [];
+    native().graphNodes(this._handle(), w[0], new Uint8Array(bytes));
+    for (let k = 0; k < w[1]; k++) { out.push({ voxels: Number(view.getBigUint64(16 * k, true)), degree: Number(view.getBigUint64(16 * k + 8, true)) }); }
+    return out;
+}
+
+// per branch: (steps_face + sqrt 2 steps_edge + sqrt 3 steps_corner) * spacing (default 1); assumes cubic voxels
+lengths(spacing) { return graphHost.graphLengths(this.branchRecords(), spacing); }
+
+// a new, ready RG8 / RG16 volume with the source's filter: (code, class): a row of a 2-D transfer function colours ends (2) and junctions (4)
+classes() { return this._derived(native().graphClasses(this._handle()), true); }
+
+// a new, ready volume of the source's size, format and filter: the source's code where the voxel is in the set and its branch is not
+// dropped, fill (default 0) elsewhere.  A branch is dropped when weights (default [10, 14, 17]) . (steps_face, steps_edge, steps_corner) <=
+// length (a number or a BigInt) and it is a spur, or (debris) a segment or an isolated voxel.  One round, not thinned again
+prune(length, weights, debris, fill) {
+    const p = graphHost.checkPrune(length, weights, debris ? graphHost.GRAPH_PRUNE_DEBRIS : 0, fill, this._norm16 ? 65535 : 255);
+    return this._derived(native().graphPrune(this._handle(), BigUint64Array.of(p[0]), p[1][0], p[1][1], p[1][2], p[2], p[3]));
+}
+
+// (for measurements) { ms: { seed, classify, branches, nodes, links, host }, launches }
+profile() {
+    const r = native().graphProfile(this._handle());
+    return { ms: { seed: r[0], classify: r[1], branches: r[2], nodes: r[3], links: r[4], host: r[5] }, launches: r[6] };
 }
 
 close() { this.destroy(); }
@@ -969,4 +1099,4 @@ get profile() {
 
 }
 
-module.exports = { Volume, Components, Distance, Skeleton, Surface, RAWReader, filterCode, gradientArguments, windowFormatBits, percentileWindow, checkPasses, checkLevels, rankOperatorCode, checkRankPasses };
+module.exports = { Volume, Components, Distance, Skeleton, Graph, Surface, RAWReader, filterCode, gradientArguments, windowFormatBits, percentileWindow, checkPasses, checkLevels, rankOperatorCode, checkRankPasses };

@@ -6,7 +6,7 @@ constructing a Context does, and raises if it is missing (no CPU fallback)."""
 from .property_bag import PropertyBag, EventTarget, Event, CustomEvent
 from .scene import Node, Transform, PerspectiveCamera, mat4, quat, vec3, default_camera, mvp_inverse_matrix
 from .context import Context
-from .volume import Volume, Components, Distance, Skeleton, Surface
+from .volume import Volume, Components, Distance, Skeleton, Surface, Graph
 from .loaders import AbstractLoader, BlobLoader, FileLoader, LoaderFactory
 from .readers import AbstractReader, RAWReader, ZIPReader, BVPReader, ReaderFactory
 from .renderers import (AbstractRenderer, MIPRenderer, EAMRenderer, MCSRenderer, MCMRenderer, ISORenderer, DepthRenderer, LAORenderer, DOSRenderer,
@@ -27,6 +27,7 @@ from .measure import measure_texels, keep_set_texels, derive, MEASURE_DTYPE
 from .distance import distance_squared_texels, within_texels, channel_texels, check_seeds, check_steps, check_radius
 from .distance import thickness_squared_texels, thickness_texels, open_ball_texels
 from .skeleton import skeleton_burn_texels, skeleton_texels, burn_within_texels, check_skeleton
+from .graph import graph_texels, skeleton_graph_texels, prune_texels, classes_texels, centreline_texels, BRANCH_DTYPE, NODE_DTYPE
 from .surface import surface_texels, write_stl, write_ply, write_obj
 from .resample import resample_texels, isotropic_shape, axis_taps, nearest_index, count_ties, check_mode, check_size, check_spacing
 from .combine import combine_texels, compare_stats, OPS, check_op, check_weights, check_channel
@@ -48,6 +49,7 @@ __all__ = [
     'distance_squared_texels', 'within_texels', 'channel_texels', 'check_seeds', 'check_steps', 'check_radius', 'Distance',
     'thickness_squared_texels', 'thickness_texels', 'open_ball_texels',
     'skeleton_burn_texels', 'skeleton_texels', 'burn_within_texels', 'check_skeleton', 'Skeleton',
+    'graph_texels', 'skeleton_graph_texels', 'prune_texels', 'classes_texels', 'centreline_texels', 'BRANCH_DTYPE', 'NODE_DTYPE', 'Graph',
     'surface_texels', 'write_stl', 'write_ply', 'write_obj', 'Surface',
     'resample_texels', 'isotropic_shape', 'axis_taps', 'nearest_index', 'count_ties', 'check_mode', 'check_size', 'check_spacing',
     'combine_texels', 'compare_stats', 'OPS', 'check_op', 'check_weights', 'check_channel',

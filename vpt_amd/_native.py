@@ -59,6 +59,8 @@ SYMBOLS = [
     "vpt_distance_thickness", "vpt_distance_thickness_timed", "vpt_distance_thickness_capped",
     "vpt_volume_skeleton", "vpt_volume_skeleton_capped", "vpt_skeleton_info", "vpt_skeleton_burn", "vpt_skeleton_within", "vpt_skeleton_profile",
     "vpt_skeleton_destroy",
+    "vpt_volume_graph", "vpt_skeleton_graph", "vpt_graph_info", "vpt_graph_branches", "vpt_graph_nodes", "vpt_graph_branch_components",
+    "vpt_graph_node_components", "vpt_graph_classes", "vpt_graph_prune", "vpt_graph_profile", "vpt_graph_destroy",
     "vpt_volume_surface", "vpt_volume_surface_capped", "vpt_surface_info", "vpt_surface_vertices", "vpt_surface_quads", "vpt_surface_device",
     "vpt_surface_profile", "vpt_surface_destroy",
     "vpt_volume_resample", "vpt_volume_resample_timed",
@@ -151,6 +153,27 @@ SKELETON_PHASES = 4
 class SkeletonInfo(C.Structure):
     """struct vpt_skeleton_info (include/vpt.h)"""
     _fields_ = [(name, C.c_uint64) for name in ("object_voxels", "kept_voxels", "passes", "converged", "isolated", "ends", "regular", "junctions")]
+
+
+GRAPH_PHASES = 6
+GRAPH_PRUNE_DEBRIS = 1
+
+
+class GraphBranch(C.Structure):
+    """struct vpt_graph_branch (include/vpt.h): 64 bytes, no padding (vpt_amd.graph.BRANCH_DTYPE is its numpy form)"""
+    _fields_ = [(name, C.c_uint32) for name in ("voxels", "free_ends", "attachments", "kind", "node_lo", "node_hi")] + \
+               [(name, C.c_uint64) for name in ("steps_face", "steps_edge", "steps_corner", "tip_lo", "tip_hi")]
+
+
+class GraphNode(C.Structure):
+    """struct vpt_graph_node (include/vpt.h)"""
+    _fields_ = [("voxels", C.c_uint64), ("degree", C.c_uint64)]
+
+
+class GraphInfo(C.Structure):
+    """struct vpt_graph_info (include/vpt.h)"""
+    _fields_ = [(name, C.c_uint64) for name in ("kept_voxels", "node_voxels", "branches", "nodes", "isolated", "segments", "spurs", "links", "loops", "cycles",
+                                                "steps_face", "steps_edge", "steps_corner", "attachments")]
 
 
 SURFACE_PHASES = 5
@@ -252,6 +275,11 @@ def lib():
         "vpt_skeleton_info": [P, C.POINTER(SkeletonInfo)], "vpt_skeleton_burn": [P, I, I, I, I, I, I, P, SZ],
         "vpt_skeleton_within": [P, C.c_uint32, C.c_uint32, C.c_uint32, PP],
         "vpt_skeleton_profile": [P, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)], "vpt_skeleton_destroy": [P],
+        "vpt_volume_graph": [P, C.c_uint32, C.c_uint32, PP], "vpt_skeleton_graph": [P, PP], "vpt_graph_info": [P, C.POINTER(GraphInfo)],
+        "vpt_graph_branches": [P, C.c_uint64, C.c_uint64, C.POINTER(GraphBranch)], "vpt_graph_nodes": [P, C.c_uint64, C.c_uint64, C.POINTER(GraphNode)],
+        "vpt_graph_branch_components": [P, PP], "vpt_graph_node_components": [P, PP], "vpt_graph_classes": [P, PP],
+        "vpt_graph_prune": [P, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, PP],
+        "vpt_graph_profile": [P, C.POINTER(C.c_double), C.POINTER(C.c_uint64)], "vpt_graph_destroy": [P],
         "vpt_volume_surface": [P, I, C.c_uint32, PP], "vpt_volume_surface_capped": [P, I, C.c_uint32, C.c_uint32, PP],
         "vpt_surface_info": [P, C.POINTER(SurfaceInfo)], "vpt_surface_vertices": [P, C.c_uint64, C.c_uint64, P, SZ],
         "vpt_surface_quads": [P, C.c_uint64, C.c_uint64, P, SZ], "vpt_surface_device": [P, PP, PP],

@@ -23,6 +23,7 @@
 //   vpt_volume_thickness.hip    local thickness, the largest inscribed ball: a vpt_distance handle (vpt_volume_distance.h) made of another one (tile maxima, the cover walk)
 //   vpt_volume_skeleton.hip     curve skeleton and topological kernel by subfield thinning: burn passes as a voxel field (vpt_volume_skeleton.h; bit planes, border marking, eight sub-steps a pass under an exact tile cull, the census)
 //   vpt_volume_surface.hip      the isosurface as a mesh by naive surface nets: a vpt_surface handle (inside plane, classify, prefix sums without a wait between workgroups, vertices and quads placed by offset + popcount)
+//   vpt_volume_graph.hip        the graph of a voxel set (a skeleton): classes, branches and nodes as two labellings (vpt_volume_graph.h; bit plane, prefix-sum placed voxel list, links, prune and class emitters)
 // vpt_variants.h (through vpt_device.h) holds the variant bits of the sampling kernels and the switch from a run-time variant to a template
 // argument; launch_variant below is its use for a renderer's sampling pass.
 // vpt_buffers.h holds DevBuf<T> / PinnedBuf<T>, the owners of device and pinned host memory: the objects below own their memory through such

@@ -80,6 +80,10 @@ struct ComponentsPasses {
 };
 // tile pass, merge and flatten until nothing gives up, sizes, census, list, ranks: fills c->values, c->list, c->info, c->ms, c->launches
 int components_build(vpt_components *c, uint32_t min_voxels, int merge_steps, int flatten_steps, const ComponentsPasses &passes);
+// the passes of a value range, for a builder whose foreground is a range lo .. hi of a one-byte field of its own rather than of the
+// handle's texels (vpt_volume_graph.hip: the class field): the tile pass over `field`, and the merge across tiles (it reads L alone)
+void components_launch_field_tiles(const vpt_components *c, const uint8_t *field, int conn, uint32_t lo, uint32_t hi, uint32_t *words);
+void components_launch_merge(const vpt_components *c, int conn, int cap, uint32_t *words);
 // the caps of a _capped entry point against the smallest for which the bounds of components_build's loops hold
 int components_check_caps(int merge_steps, int flatten_steps);
 // the chase steps the entry points without caps pass

@@ -251,21 +251,24 @@ static int flatten_launches(int cap) {
 }
 
 template <typename T>
-static void launch_label_tiles(const vpt_components *c, int conn, uint32_t lo, uint32_t hi, uint32_t *words) {
+static void launch_label_tiles(const vpt_components *c, const T *s, int conn, uint32_t lo, uint32_t hi, uint32_t *words) {
     const dim3 grid((unsigned)((c->nx + CC_TX - 1) / CC_TX), (unsigned)((c->ny + CC_TY - 1) / CC_TY), (unsigned)((c->nz + CC_TZ - 1) / CC_TZ));
-    const T *s = (const T *)c->texels.get();
     hipStream_t st = c->ctx->stream;
     if (conn == 6) hipLaunchKernelGGL((k_label_tiles<T, 6>), grid, dim3(256), 0, st, s, c->values.get(), c->nx, c->ny, c->nz, lo, hi, words);
     else if (conn == 18) hipLaunchKernelGGL((k_label_tiles<T, 18>), grid, dim3(256), 0, st, s, c->values.get(), c->nx, c->ny, c->nz, lo, hi, words);
     else hipLaunchKernelGGL((k_label_tiles<T, 26>), grid, dim3(256), 0, st, s, c->values.get(), c->nx, c->ny, c->nz, lo, hi, words);
 }
-static void launch_merge(const vpt_components *c, int conn, int cap, uint32_t *words) {
+void components_launch_merge(const vpt_components *c, int conn, int cap, uint32_t *words) {
     const size_t n = c->voxels();
     const dim3 grid(stream_grid(n));
     hipStream_t st = c->ctx->stream;
     if (conn == 6) hipLaunchKernelGGL(k_merge<6>, grid, dim3(256), 0, st, c->values.get(), c->nx, c->ny, c->nz, n, cap, words);
     else if (conn == 18) hipLaunchKernelGGL(k_merge<18>, grid, dim3(256), 0, st, c->values.get(), c->nx, c->ny, c->nz, n, cap, words);
     else hipLaunchKernelGGL(k_merge<26>, grid, dim3(256), 0, st, c->values.get(), c->nx, c->ny, c->nz, n, cap, words);
+}
+
+void components_launch_field_tiles(const vpt_components *c, const uint8_t *field, int conn, uint32_t lo, uint32_t hi, uint32_t *words) {
+    launch_label_tiles<uint8_t>(c, field, conn, lo, hi, words);
 }
 
 // the body of vpt_volume_components and vpt_volume_watershed behind the argument checks (ComponentsPasses: vpt_volume_components.h); `c` is
@@ -385,11 +388,11 @@ static int components_create(vpt_volume *src, uint32_t lo, uint32_t hi, int conn
     const ComponentsPasses passes = {
         "connected components",
         [=](uint32_t *words) {
-            if (h->norm16) launch_label_tiles<uint16_t>(h, connectivity, lo, hi, words);
-            else launch_label_tiles<uint8_t>(h, connectivity, lo, hi, words);
+            if (h->norm16) launch_label_tiles<uint16_t>(h, (const uint16_t *)h->texels.get(), connectivity, lo, hi, words);
+            else launch_label_tiles<uint8_t>(h, (const uint8_t *)h->texels.get(), connectivity, lo, hi, words);
             return (int)VPT_OK;
         },
-        [=](int cap, uint32_t *words) { launch_merge(h, connectivity, cap, words); } };
+        [=](int cap, uint32_t *words) { components_launch_merge(h, connectivity, cap, words); } };
     const int rc = components_build(h, min_voxels, merge_steps, flatten_steps, passes);
     if (rc != VPT_OK) { (void)hipStreamSynchronize(ctx->stream); return rc; }      // the buffers are freed on return: nothing may still use them
     *out = c.release();

@@ -535,14 +535,54 @@ class Volume(EventTarget):
             N.check(N.lib().vpt_volume_skeleton_capped(self.texture, lo, hi, code, passes, int(_flags), C.byref(h)))
         return Skeleton(self, h)
 
-    def centreline(self, lo, hi, mode='ends'):
+    def centreline(self, lo, hi, mode='ends', prune=None, prune_rounds=1):
         """A new, ready volume like this one in which the voxels of the codes lo .. hi that survive the thinning keep their codes; 0
-        elsewhere (vpt_amd.skeleton_texels states it)"""
+        elsewhere (vpt_amd.skeleton_texels states it).  With ``prune`` (a length in the default step weights 10 / 14 / 17: ten a voxel),
+        up to ``prune_rounds`` times: the skeleton's graph, its spurs within ``prune`` dropped (``Graph.prune``), the rest thinned again;
+        a round that drops nothing ends it (vpt_amd.graph.centreline_texels states it).  The pruned volume is filled with a code outside
+        lo .. hi (0 when lo > 0, otherwise hi + 1), so a range that covers every code is refused with ``prune`` set."""
+        if prune is None:
+            k = self.skeleton(lo, hi, mode)
+            try:
+                return k.volume()
+            finally:
+                k.destroy()
+        from .graph import check_centreline_prune, dropped
+        from .skeleton import check_range
+        norm16 = self.native_format()[0] in (N.FORMAT_R16, N.FORMAT_RG16, N.FORMAT_R16_SNORM, N.FORMAT_RG16_SNORM)
+        lo, hi = check_range(lo, hi, 65535 if norm16 else 255)
+        prune, prune_rounds, fill = check_centreline_prune(lo, hi, prune, prune_rounds, 65535 if norm16 else 255)
         k = self.skeleton(lo, hi, mode)
         try:
+            for _ in range(prune_rounds):
+                g = k.graph()
+                try:
+                    if not dropped(g.branch_records(), prune).any():
+                        break
+                    pruned = g.prune(prune, fill=fill)
+                finally:
+                    g.destroy()
+                try:
+                    again = pruned.skeleton(lo, hi, mode)
+                finally:
+                    pruned.destroy()
+                k.destroy()
+                k = again
             return k.volume()
         finally:
             k.destroy()
+
+    # ---- extension: the graph of a voxel set: branches, nodes, step counts, spur pruning (include/vpt.h; DESIGN.md "Skeleton graph") ----
+    def graph(self, lo, hi):
+        """The graph of the voxels of the codes lo .. hi of this (R8 / R16) volume as a ``Graph`` object, built on the device
+        (vpt_amd.graph.graph_texels states the contract): meant for a thinned set (``centreline``), defined for any.  The object owns what
+        it needs: this volume is not changed and may be destroyed."""
+        from .graph import check_range
+        norm16 = self.native_format()[0] in (N.FORMAT_R16, N.FORMAT_RG16, N.FORMAT_R16_SNORM, N.FORMAT_RG16_SNORM)
+        lo, hi = check_range(lo, hi, 65535 if norm16 else 255)
+        h = C.c_void_p()
+        N.check(N.lib().vpt_volume_graph(self.texture, lo, hi, C.byref(h)))
+        return Graph(self, h)
 
     # ---- extension: isosurface mesh by naive surface nets (include/vpt.h; DESIGN.md "Surface") ----
     def surface(self, level, channel=0, _scan_words=None):
@@ -1137,6 +1177,112 @@ class Skeleton(_VoxelField):
         launches, tiles = C.c_uint64(0), C.c_uint64(0)
         N.check(N.lib().vpt_skeleton_profile(self._handle(), ms, C.byref(launches), C.byref(tiles)))
         return dict(zip(('seed', 'border', 'steps', 'census'), ms)), int(launches.value), int(tiles.value)
+
+    def graph(self):
+        """The graph of the kept voxels as a ``Graph`` object, built on the device (vpt_amd.graph.skeleton_graph_texels states it); its
+        emitters and its ``branches`` / ``nodes`` speak in the codes of this skeleton's source.  This object is not changed and may be
+        destroyed."""
+        h = C.c_void_p()
+        N.check(N.lib().vpt_skeleton_graph(self._handle(), C.byref(h)))
+        return Graph(_FieldSource(self), h)
+
+    close = _VoxelField.destroy
+
+
+class _FieldSource:
+    """what ``_VoxelField`` reads of its source, for a field made of another field: the description of that field's source"""
+
+    def __init__(self, field):
+        self._gl = field._gl
+        self.modality = dict(field._modality)
+        self.metadata = {'meta': dict(field._meta)}
+
+
+class Graph(_VoxelField):
+    """The graph of a set of voxels (``Volume.graph``, ``Skeleton.graph``): the class of every voxel, the branches and the nodes as two
+    labellings and one record per branch and node, on the device.  Build once; list, measure, prune and colour several times.  Outlives
+    what it was made from; ``destroy()`` (or ``close()``) frees the device memory (``branches`` and ``nodes`` once taken are the caller's)."""
+    _noun, _destroy = 'graph', 'vpt_graph_destroy'
+
+    def __init__(self, source, handle):
+        super().__init__(source, handle)
+        self._source = _FieldSource(self)
+        self._branches = self._nodes = None
+
+    @property
+    def info(self):
+        """{'kept_voxels', 'node_voxels', 'branches', 'nodes', 'isolated', 'segments', 'spurs', 'links', 'loops', 'cycles', 'steps_face',
+        'steps_edge', 'steps_corner', 'attachments'}"""
+        i = N.GraphInfo()
+        N.check(N.lib().vpt_graph_info(self._handle(), C.byref(i)))
+        return {name: int(getattr(i, name)) for name, _ in N.GraphInfo._fields_}
+
+    def _components(self, call):
+        h = C.c_void_p()
+        N.check(getattr(N.lib(), call)(self._handle(), C.byref(h)))
+        return Components(self._source, h)
+
+    @property
+    def branches(self):
+        """the branches as a ``Components`` object (made at the first use; the caller destroys it): ranks are branch ranks, texels the
+        source's codes, so ``measure``, ``keep_set``, ``keep`` and ``label`` work on branches unchanged"""
+        if self._branches is None:
+            self._branches = self._components('vpt_graph_branch_components')
+        return self._branches
+
+    @property
+    def nodes(self):
+        """the nodes as a ``Components`` object (made at the first use; the caller destroys it)"""
+        if self._nodes is None:
+            self._nodes = self._components('vpt_graph_node_components')
+        return self._nodes
+
+    def _records(self, call, count, dtype, ctype, first, n):
+        from .measure import check_window
+        first, n = check_window(first, n, count)
+        out = np.zeros(n, dtype)
+        N.check(getattr(N.lib(), call)(self._handle(), first, n, out.ctypes.data_as(C.POINTER(ctype))))
+        return out
+
+    def branch_records(self, first=0, n=None):
+        """A structured array (vpt_amd.graph.BRANCH_DTYPE), one record per branch of rank first + 1 .. first + n (n None: to the end)"""
+        from .graph import BRANCH_DTYPE
+        return self._records('vpt_graph_branches', self.info['branches'], BRANCH_DTYPE, N.GraphBranch, first, n)
+
+    def node_records(self, first=0, n=None):
+        """A structured array (vpt_amd.graph.NODE_DTYPE), one record per node of rank first + 1 .. first + n (n None: to the end)"""
+        from .graph import NODE_DTYPE
+        return self._records('vpt_graph_nodes', self.info['nodes'], NODE_DTYPE, N.GraphNode, first, n)
+
+    def lengths(self, spacing=1.0):
+        """float64 per branch: (steps_face + sqrt 2 steps_edge + sqrt 3 steps_corner) * spacing; assumes cubic voxels (``Volume.isotropic``)"""
+        from .graph import lengths
+        return lengths(self.branch_records(), spacing)
+
+    def classes(self):
+        """A new, ready RG8 / RG16 volume with the source's filter: (code, class) (vpt_amd.graph.classes_texels states it): a row of a 2-D
+        transfer function colours ends (2) and junctions (4)"""
+        h = C.c_void_p()
+        N.check(N.lib().vpt_graph_classes(self._handle(), C.byref(h)))
+        return self._derived(h, pair=True)
+
+    def prune(self, length, weights=(10, 14, 17), debris=False, fill=0):
+        """A new, ready volume of the source's size, format and filter: the source's code where the voxel is in the set and its branch is
+        not dropped, ``fill`` elsewhere (vpt_amd.graph.prune_texels states it).  A branch is dropped when weights . (steps_face, steps_edge,
+        steps_corner) <= length and it is a spur, or (``debris``) a segment or an isolated voxel.  One round, not thinned again; all spurs
+        of a node go together."""
+        from .graph import check_prune, PRUNE_DEBRIS
+        length, (wf, we, wc), flags, fill = check_prune(length, weights, PRUNE_DEBRIS if debris else 0, fill, 65535 if self._norm16 else 255)
+        h = C.c_void_p()
+        N.check(N.lib().vpt_graph_prune(self._handle(), length, wf, we, wc, flags, fill, C.byref(h)))
+        return self._derived(h)
+
+    def profile(self):
+        """(for measurements) ({'seed', 'classify', 'branches', 'nodes', 'links', 'host'} in milliseconds, kernel launches of the unit)"""
+        ms = (C.c_double * N.GRAPH_PHASES)()
+        launches = C.c_uint64(0)
+        N.check(N.lib().vpt_graph_profile(self._handle(), ms, C.byref(launches)))
+        return dict(zip(('seed', 'classify', 'branches', 'nodes', 'links', 'host'), ms)), int(launches.value)
 
     close = _VoxelField.destroy
 
