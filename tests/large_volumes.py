@@ -301,6 +301,29 @@ def skeleton_on_crops(lay, blocks, crops, lo, hi, mode, passes=0):
     return out, info
 
 
+def graph_on_crops(lay, kept, crops):
+    """(the graph_cases.Assembled graph of the volume, {'classes', 'branch_ranks', 'node_ranks': blocks per slab}) of the bool blocks
+    `kept`: a voxel's class and a branch's record depend on 26-neighbours only, a crop keeps background on every face inside the volume, so
+    the crops' graphs side by side are the volume's; ranks, node ranks and tips are translated to the volume (graph_cases.graph_on_pieces)"""
+    from graph_cases import graph_on_pieces
+    nx, ny, nz = lay.shape
+    pieces = []
+    for crop in crops:
+        a, origin, _ = crop_array(lay, kept, crop)
+        pieces.append((origin, a))
+    graph = graph_on_pieces((nz, ny, nx), pieces)
+    fields = {}
+    for name in ('classes', 'branch_ranks', 'node_ranks'):
+        fields[name] = [np.zeros(b.shape[:3], np.uint8 if name == 'classes' else np.uint32) for b in kept]
+        for k, crop in enumerate(crops):                          # piece k is crop k
+            i, y0, y1, x0, x1 = crop
+            lo = crop_array(lay, kept, crop)[2]
+            r = getattr(graph, name)(k)
+            assert not r[:lo].any() and not r[lo + lay.thick:].any()
+            fields[name][i][:, y0:y1, x0:x1] = r[lo:lo + lay.thick]
+    return graph, fields
+
+
 def surface_on_crops(lay, blocks, crops, level, channel=0):
     """(vertices, quads, info) of vpt_amd.surface.surface_texels: a crop's mesh is the part of the volume's in its cells (the statement
     reads 0 outside a crop as outside the volume, and a crop keeps background round its solid).  Its vertices move by the crop's origin;

@@ -47,10 +47,11 @@ ASYNC_ENTRIES = (
     'upload_block_device', 'finalize', 'reduce', 'smooth(1)', 'rank(1)', 'combine', 'window', 'derive_gradient', 'resample(nearest)',
     'reset', 'render', 'play(fused)', 'play(frames)', 'play_into', 'play_into_display', 'set_render_target', 'join', 'setVolume',
     'setFilter', 'set_option', 'render_buffer_device', 'frame_ring_device', 'tonemapper.render', 'tonemapper.output_device',
+    'graph.classes', 'graph.branch_components', 'label',
 )
 BLOCKING_ENTRIES = (
     'upload_block', 'setTransferFunction', 'set_environment', 'set_environment_texels', 'finalize(float)', 'smooth(n)', 'rank(n)',
-    'resample(filtered)', 'components', 'keep', 'distance', 'channel', 'read', 'resize', 'destroy', 'context.destroy',
+    'resample(filtered)', 'components', 'keep', 'distance', 'channel', 'graph', 'graph.prune', 'read', 'resize', 'destroy', 'context.destroy',
 )
 FAMILIES = {
     'A': 'producer -> upload_block_device -> passes -> consumer',
@@ -422,6 +423,9 @@ def derive(h, op, v, earlier, second):
     if op == 'distance_channel':
         f = h.own(h.do('distance', v.distance, 128, 255))
         return [h.do('channel', f.channel, 1)]
+    if op == 'graph_prune':                   # the labellings read counts back; the pruning drains the stream before it frees its bitmap
+        g = h.own(h.do('graph', v.graph, 224, 255))
+        return [h.do('graph.prune', g.prune, 20, (10, 14, 17), True, 3)]
     raise ValueError(op)
 
 
@@ -449,6 +453,44 @@ def sc_derive(h, op):
     passes(h, r, 2)
     h.closed()
     h.take(tgt)
+
+
+def sc_graph_emitters(h):
+    """A graph built before the gate (vpt_volume_graph blocks).  Behind the gate its class pair volume, a copy of its branch labelling and
+    that copy's label volume are only enqueued: vpt_graph_classes and the hand-out launch a kernel or a copy and return, and
+    vpt_components_label of the copy does the same.  The first copy the consumer takes is the pair volume under passes, the second the
+    label volume and then the volume the producer filled, accumulated (MIP keeps the maximum).  Only that last volume depends on the
+    producer: it alone tells stale inputs from fresh ones.  The pair and the label volume come from texels uploaded before the gate, so
+    the scenario shows that the three entries do not wait for the host and that their bytes are the twin's beside split passes and a
+    producer's upload, not that they order behind producer work."""
+    w, hh, d = DIMS['r8']
+    kept = h.volume('r8', h.noise('r8', 34))
+    g = h.own(kept.graph(224, 255))
+    v = h.volume('r8')
+    r = h.renderer('mip', kept)
+    h.warm(r)
+    blocks = sources(h, h.noise('r8', 35), boxes('slab', w, hh, d))
+    tgt = h.target(r)
+    h.gate()
+    passes(h, r, 1)
+    h.lag()
+    produce_and_upload(h, v, blocks)
+    pair = h.own(h.do('graph.classes', g.classes))
+    branches = h.own(h.do('graph.branch_components', getattr, g, 'branches'))
+    label = h.own(h.do('label', branches.label))
+    h.do('set_render_target', r.set_render_target, tgt.data_ptr(), bytes_of(h, tgt))
+    h.do('setVolume', r.setVolume, pair)
+    h.do('reset', r.reset)
+    passes(h, r, 2)
+    h.take(tgt)
+    h.do('setVolume', r.setVolume, label)
+    h.do('reset', r.reset)
+    passes(h, r, 1)
+    h.do('setVolume', r.setVolume, v)
+    passes(h, r, 2)
+    h.closed()
+    h.take(tgt)
+    h.check('the class pair and the label volume show in the frames', lambda outs: outs[0].any() and outs[1].any() and not (outs[0] == outs[1]).all())
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -723,8 +765,11 @@ def _table():
                         ('resample_nearest', ['resample(nearest)']), ('chain', ['smooth(1)', 'window', 'reduce'])):
         t.append(scenario('C_%s' % op, 'C', 'asynchronous', sc_derive, derived + entries, op=op))
     for op, entries in (('smooth3', ['smooth(n)']), ('rank2', ['rank(n)']), ('resample_filtered', ['resample(filtered)']),
-                        ('components_keep', ['components', 'keep']), ('distance_channel', ['distance', 'channel'])):
+                        ('components_keep', ['components', 'keep']), ('distance_channel', ['distance', 'channel']),
+                        ('graph_prune', ['graph', 'graph.prune'])):
         t.append(scenario('C_%s' % op, 'C', 'blocking', sc_derive, derived + entries, op=op))
+    t.append(scenario('C_graph_emitters', 'C', 'asynchronous', sc_graph_emitters,
+                      derived + ['reset', 'graph.classes', 'graph.branch_components', 'label']))
     # D
     tables = up + ['reset', 'render'] + own
     for kind, change, waits, entries in (('mip', 'tf', 'blocking', ['setTransferFunction']), ('mcm', 'tf', 'blocking', ['setTransferFunction']),

@@ -1,4 +1,4 @@
-"""GPU: reconstruction and the geodesic operations, the watershed, local thickness, the skeleton and the surface on volumes of more than
+"""GPU: reconstruction and the geodesic operations, the watershed, local thickness, the skeleton, its graph and the surface on volumes of more than
 2^31 (tier A) and more than 2^32 (tier B) voxels, where a linear index, a byte offset, a tile number or a counter kept in 32 bits goes wrong.
 
 The method is that of tests/test_gpu_large_volumes.py: slabs of whole planes at z = 0, round the plane of linear voxel 2^31 (and 2^30 where
@@ -18,7 +18,8 @@ import vpt_amd
 from vpt_amd.surface import surface_texels
 
 from large_volumes import (TIER_A, TIER_B, Layout, voxels, volume_bytes, field_bytes, sparse_volume, planes, differences, solids, on_crops,
-                           watershed_on_crops, skeleton_on_crops, surface_on_crops, shift_twin_vertices, thickness_tiles)
+                           watershed_on_crops, skeleton_on_crops, graph_on_crops, surface_on_crops, shift_twin_vertices, thickness_tiles)
+from graph_cases import dropped, prune_texels
 from test_gpu_large_volumes import DTYPE, require, tier, hold, background, refused
 
 pytestmark = pytest.mark.gpu
@@ -189,8 +190,8 @@ def test_watershed_of_more_than_2_31_voxels(gpu_ctx, kind, bits, channels, polar
 # ---- what 32-bit labels refuse ---------------------------------------------------------------------------------------------------
 @pytest.mark.timeout(120)
 def test_reconstruct_and_watershed_refuse_more_than_2_32_voxels(gpu_ctx):
-    """Tier B: reconstruction keeps tile-local 32-bit voxel numbers and the watershed 32-bit labels; both say so.  Peak: one zero-filled R8
-    volume, 19.9 GiB."""
+    """Tier B: reconstruction keeps tile-local 32-bit voxel numbers, the watershed 32-bit labels and the graph 32-bit labels, list entries and
+    counts; all say so.  Peak: one zero-filled R8 volume, 19.9 GiB."""
     shape = TIER_B['odd']
     n = tier(shape, 1 << 32)
     nx, ny, _ = shape
@@ -204,6 +205,9 @@ def test_reconstruct_and_watershed_refuse_more_than_2_32_voxels(gpu_ctx):
             refused(lambda: src.geodesic(op, 1 if op == 'hmax' else 0), "geodesic", str(n), "2^32 - 2")
         refused(lambda: src.watershed(1, 255), "watershed", str(n), "2^32 - 2")
         refused(lambda: src.watershed(1, 255, 'maxima', 26), "watershed", "2^32 - 2")
+        # the graph's labels, list entries and counts are 32-bit too (Skeleton.graph: test_skeleton_in_large_volumes, which has a skeleton)
+        refused(lambda: src.graph(1, 255), "graph", str(n), "2^32 - 2")
+        refused(lambda: src.graph(0, 0), "graph", "2^32 - 2")
     finally:
         src.destroy()
 
@@ -278,6 +282,8 @@ def test_skeleton_in_large_volumes(gpu_ctx, tier_name, kind, bits, mode):
         src.destroy()
     try:
         assert found.info == info
+        if tier_name == 'B':                                      # more than 2^32 - 2 voxels: the graph of this skeleton is refused
+            refused(found.graph, "graph", str(voxels(shape)), "2^32 - 2")
         hold_field(found.burn, burn, lay, "burn passes", distinct=4)
         peeled = found.within(2, None)
         try:
@@ -296,6 +302,101 @@ def test_skeleton_in_large_volumes(gpu_ctx, tier_name, kind, bits, mode):
             kept.destroy()
     finally:
         found.destroy()
+
+
+# ---- the graph -------------------------------------------------------------------------------------------------------------------
+def hold_graph(g, want, fields, blocks, lay, prune, what):
+    """a graph on the device against the crops' graphs put together: info and every record; the ranks as voxel fields; the class pair and
+    one pruning in the slabs' planes; background between the slabs"""
+    twin_codes = lay.twin(blocks)
+    assert g.info == want.info, "%s: %r, expected %r" % (what, g.info, want.info)
+    assert g.branch_records().tobytes() == want.branches.tobytes(), what + ": branch records"
+    assert g.node_records().tobytes() == want.nodes.tobytes(), what + ": node records"
+    for take, name in ((lambda: g.branches, 'branch_ranks'), (lambda: g.nodes, 'node_ranks')):
+        handed = take()
+        try:
+            assert handed.info['listed'] == len(want.branches if name == 'branch_ranks' else want.nodes)
+            hold_field(handed.ranks, fields[name], lay, "%s: %s" % (what, name), distinct=2)
+        finally:
+            handed.destroy()
+    pair = g.classes()
+    try:
+        classes = lay.twin(fields['classes'])
+        hold(pair, np.ascontiguousarray(np.stack([twin_codes, classes.astype(twin_codes.dtype)], axis=-1)), lay.windows(), what + ": classes")
+        background(pair, lay.between(), 0, what + ": classes")
+    finally:
+        pair.destroy()
+    length, debris, fill = prune
+    gone = dropped(want.branches, length, flags=1 if debris else 0)
+    assert 0 < int(gone.sum()) < len(gone), "%s: prune(%d) drops %d of %d branches" % (what, length, int(gone.sum()), len(gone))
+    pruned = g.prune(length, debris=debris, fill=fill)
+    try:
+        expected = [prune_texels(b, c, r, want.branches, length, flags=1 if debris else 0, fill=fill) for b, c, r in zip(blocks, fields['classes'], fields['branch_ranks'])]
+        assert any((e != np.where(c != 0, b, fill)).any() for e, b, c in zip(expected, blocks, fields['classes']))      # a dropped voxel in a slab
+        twin = np.full(twin_codes.shape, fill, twin_codes.dtype)
+        for t0, e in zip(lay.twin_starts, expected):
+            twin[t0:t0 + lay.thick] = e
+        hold(pruned, twin, lay.windows(), what + ": prune")
+        background(pruned, lay.between(), fill, what + ": prune")
+    finally:
+        pruned.destroy()
+
+
+@pytest.mark.timeout(300)
+@pytest.mark.parametrize("kind,bits", [('odd', 16), ('aligned', 8)])
+def test_graph_of_more_than_2_31_voxels(gpu_ctx, kind, bits):
+    """Tier A, the solids, two graphs: of the 'ends' skeleton (Skeleton.graph: the thinned bars, boxes and balls, one bar through voxel
+    2^31) and of the upper eighth of the codes of the solids themselves (Volume.graph: specks and short chains of the noise, with nodes where
+    they clump).  The list of kept voxels holds 32-bit linear indices, the tips travel through the wave's shuffles as 32-bit values, and the
+    class field is labelled by the components' tile pass at 26-connectivity over more than 2^31 voxels.  Expected: the statement on the
+    crops, put together (large_volumes.graph_on_crops; tests/test_large_volumes_host.py holds that to the statement on a whole volume).
+    Peak, n voxels, V the source, F a voxel field: while the skeleton's graph is built V + F (the skeleton) + 2 F (the branches' and the
+    nodes' labellings) + n (the class field) + the bit plane + 4 n (the components' count array, components_build) = 21.4 + 45.1 + 12.7 =
+    79.2 GiB (R16), 10.6 + 37.5 + 12.7 = 60.8 GiB (R8); while it is read V + 2 F + n + a handed-out copy F or the class pair volume (the
+    larger: RG) = 21.4 + 30.0 + 2.5 + 42.7 = 96.6 GiB (R16), 10.6 + 25.0 + 2.5 + 21.2 = 59.3 GiB (R8); the list is kilobytes.  The
+    thinning that runs first, with V resident, stays below both (test_skeleton_in_large_volumes: V + F + three bit planes + the tile flags =
+    37.4 GiB R16, 24.0 GiB R8); it is in the maximum all the same."""
+    shape = TIER_A[kind]
+    n = tier(shape, 1 << 31, 0xFFFFFFFE)
+    nx, ny, nz = shape
+    item = bits // 8
+    V, F, plane = volume_bytes(shape, item), field_bytes(shape, item), 4 * 2 * ((nx + 63) // 64) * ny * nz
+    require(max(V + F + 3 * plane + 16 * tiles_of(shape, 64, 8, 4), V + 3 * F + 5 * n + plane, V + 2 * F + n + max(F, volume_bytes(shape, item, 2))))
+    dtype, M = DTYPE[bits], (1 << bits) - 1
+    lay = solid_layout(shape, four_bytes=True)
+    blocks, crops = solids(lay, dtype, 301)
+    lo = M - M // 8
+    burn, _ = skeleton_on_crops(lay, blocks, crops, 1, M, 'ends')
+    cases = {'skeleton': [b == 0xFFFFFFFF for b in burn], 'range': [b >= lo for b in blocks]}
+    stated = {}
+    for what, kept in cases.items():
+        want, fields = graph_on_crops(lay, kept, crops)
+        # what makes the case say something, from the statement alone
+        assert want.info['branches'] >= 8 and int(want.branches['tip_hi'].max()) >= 1 << 31, what
+        last = fields['branch_ranks'][-1]
+        assert last.any() and (fields['branch_ranks'][-2] != 0).any(), what                 # a branch in the last slab, and in the slab of voxel 2^31
+        z, y, x = np.nonzero(last)
+        assert int(((z + lay.starts[-1]) * ny + y).max()) * nx >= 1 << 31, what              # a listed branch voxel whose index needs 32 bits
+        stated[what] = (want, fields)
+    assert stated['range'][0].info['nodes'] >= 4 and stated['range'][0].info['links'] >= 1 and stated['range'][0].info['spurs'] >= 4
+    src = sparse_volume(gpu_ctx, lay, blocks)
+    try:
+        found = src.skeleton(1, M, 'ends')
+        try:
+            g = found.graph()
+        finally:
+            found.destroy()
+        try:
+            hold_graph(g, *stated['skeleton'], blocks, lay, (40, True, 5), "the skeleton's graph R%d %s" % (bits, kind))
+        finally:
+            g.destroy()
+        g = src.graph(lo, M)
+    finally:
+        src.destroy()
+    try:
+        hold_graph(g, *stated['range'], blocks, lay, (20, False, 0), "the graph of %d .. %d R%d %s" % (lo, M, bits, kind))
+    finally:
+        g.destroy()
 
 
 # ---- the surface -----------------------------------------------------------------------------------------------------------------

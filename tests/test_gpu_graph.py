@@ -19,6 +19,7 @@ from vpt_amd import graph as G
 from vpt_amd.measure import keep_set_texels, measure_texels
 from vpt_amd.skeleton import KEPT, skeleton_burn_texels, skeleton_texels
 
+import graph_cases as GC
 from test_gpu_pyramid import upload, whole
 from test_graph_host import RANDOM
 from test_skeleton_host import HI, LO, SHAPES
@@ -331,3 +332,278 @@ def test_the_error_returns_name_what_was_wrong(gpu_ctx):
             pair.graph(1, 2)
     finally:
         g.destroy(); pair.destroy(); v.destroy()
+
+
+# ---- at scale: every width, the axis limit, runs in a wave, many blocks, second trips -----------------------------------------------
+# Each test asserts on the CPU, from the statement alone, the condition that makes it say something, then holds the device to the
+# statement as above.  The device's layout, restated: a word of the bit plane holds 32 voxels along x, a row has wpr = 2 ceil(nx / 64)
+# words, a scan block 256 words, a launch at most 8192 workgroups of 256 threads.
+WIDTHS = (1, 2, 31, 32, 33, 63, 64, 65, 95, 96, 97, 127, 128, 129)
+GRID_CAP = 8192
+
+
+def frozen(g):
+    for key in ('classes', 'branch_ranks', 'node_ranks', 'branches', 'nodes'):
+        g[key].setflags(write=False)
+    return g
+
+
+def graph_of_range(gpu_ctx, a):
+    """Volume.graph over the window of `a`'s dtype; the source is destroyed at once: the graph owns what it needs"""
+    lo, hi = window(a.dtype.type)
+    v = upload(gpu_ctx, a)
+    try:
+        return v.graph(lo, hi)
+    finally:
+        v.destroy()
+
+
+def release(g):
+    for c in (g._branches, g._nodes):
+        if c is not None:
+            c.destroy()
+    g.destroy()
+
+
+@functools.lru_cache(maxsize=None)
+def width_case(nx):
+    """[3][5][nx] at density 0.15 and, at every x that is a multiple of 32 inside the volume, a kept pair across it along a row and one
+    across it on a space diagonal: (the set, its statement)"""
+    mask = np.random.default_rng(1000 + nx).random((3, 5, nx)) < 0.15
+    for x in range(32, nx, 32):
+        mask[0, 0, x - 1:x + 1] = True
+        mask[1, 3, x - 1] = mask[2, 4, x] = True
+    mask.setflags(write=False)
+    return mask, frozen(G.graph_of(mask))
+
+
+@pytest.mark.timeout(120)
+@pytest.mark.parametrize("dtype", DTYPES, ids=lambda d: np.dtype(d).name)
+@pytest.mark.parametrize("nx", WIDTHS)
+def test_every_width_round_a_word_and_a_segment(gpu_ctx, nx, dtype):
+    """nx decides the segments a row (tnx), the words a row with their padding, whether gr_word(wx +- 1) leaves the row and whether the
+    emitters have a tail (n % 4)."""
+    mask, want = width_case(nx)
+    kept = want['classes'] != 0
+    assert {(3 * 5 * w) % 4 == 0 for w in WIDTHS} == {True, False} and kept.any()
+    for x in range(32, nx, 32):                                   # both sides of every word edge, along a row and along a diagonal
+        assert (kept[:, :, x - 1] & kept[:, :, x]).any(), x
+        assert (kept[:-1, :-1, x - 1] & kept[1:, 1:, x]).any(), x
+    g = graph_of_range(gpu_ctx, host_texels(mask, dtype))
+    try:
+        check_graph(g, host_texels(mask, dtype), want, "width %d %s" % (nx, np.dtype(dtype).name))
+    finally:
+        release(g)
+
+
+LINES = {'x': ((2, 2, 4096), [(0, 0, slice(None))]), 'y': ((2, 4096, 2), [(0, slice(None), 0)]), 'z': ((4096, 2, 2), [(slice(None), 0, 0)]),
+         'x twice': ((2, 3, 4096), [(0, 0, slice(None)), (0, 2, slice(None))]), 'y twice': ((2, 4096, 3), [(0, slice(None), 0), (0, slice(None), 2)]),
+         'z twice': ((4096, 3, 2), [(slice(None), 0, 0), (slice(None), 2, 0)])}
+
+
+@functools.lru_cache(maxsize=None)
+def line_case(name):
+    shape, lines = LINES[name]
+    mask = np.zeros(shape, bool)
+    for line in lines:
+        mask[line] = True
+    mask.setflags(write=False)
+    return mask, frozen(G.graph_of(mask))
+
+
+@pytest.mark.timeout(120)
+@pytest.mark.parametrize("dtype", DTYPES, ids=lambda d: np.dtype(d).name)
+@pytest.mark.parametrize("name", list(LINES))
+def test_a_line_as_long_as_an_axis_may_be(gpu_ctx, name, dtype):
+    """4096 voxels along one axis, 2 along the others: one segment of 4095 face steps from the first voxel of the axis to the last.  A
+    second line two voxels away needs three voxels across, so it has a case of its own: along y and z the list then alternates between the
+    two branches voxel by voxel (runs of one lane), along x each line is 64 whole waves."""
+    mask, want = line_case(name)
+    lines = len(LINES[name][1])
+    axis = 'zyx'.index(name[0])
+    assert mask.shape[axis] == 4096 and want['info']['segments'] == want['info']['branches'] == lines and want['info']['nodes'] == 0
+    flat = np.flatnonzero(mask.reshape(-1))
+    for k, b in enumerate(want['branches']):
+        assert (int(b['voxels']), int(b['steps_face']), int(b['steps_edge']), int(b['steps_corner']), int(b['free_ends'])) == (4096, 4095, 0, 0, 2)
+        mine = np.flatnonzero((want['branch_ranks'] == k + 1).reshape(-1))
+        assert (int(b['tip_lo']), int(b['tip_hi'])) == (int(mine[0]), int(mine[-1]))
+    if lines == 2 and axis != 2:
+        runs = [run for wave in GC.wave_runs(want) for run in wave]
+        assert all(lanes == 1 for _, _, lanes in runs) and len(runs) == len(flat) == 8192
+    g = graph_of_range(gpu_ctx, host_texels(mask, dtype))
+    try:
+        check_graph(g, host_texels(mask, dtype), want, "line %s %s" % (name, np.dtype(dtype).name))
+    finally:
+        release(g)
+
+
+def test_no_volume_has_an_axis_of_4097_voxels(gpu_ctx):
+    """vpt_volume_graph refuses more than 4096 voxels an axis (UNSUPPORTED, "at most 4096"), and so does the statement; a caller cannot get
+    there: vpt_volume_create refuses such a volume first, and a skeleton is made of a volume."""
+    with pytest.raises(ValueError, match='at most 4096'):
+        G.graph_texels(np.zeros((1, 1, 4097), np.uint8), 1, 2)
+    for shape in ((1, 1, 4097), (1, 4097, 1), (4097, 1, 1)):
+        with pytest.raises(vpt_amd.VptError, match='out of range') as e:
+            upload(gpu_ctx, np.zeros(shape, np.uint8))
+        assert e.value.code == N.ERR_INVALID
+
+
+@pytest.mark.timeout(120)
+@pytest.mark.parametrize("dtype", DTYPES, ids=lambda d: np.dtype(d).name)
+def test_runs_of_one_branch_along_a_wave(gpu_ctx, dtype):
+    """k_gr_links sums a run of one key towards its first lane before it touches the record: graph_cases.wave_case holds a run over a whole
+    wave, one that begins mid-wave and carries on through the next two, two runs of one branch parted by another branch and by node
+    voxels, and a last run that is lane 63 alone."""
+    mask = GC.wave_case()
+    want = wave_statement()
+    met = GC.wave_conditions(GC.wave_runs(want))
+    assert all(met[k] for k in ('full', 'carried', 'apart', 'over nodes', 'last lane')), met
+    assert want['info']['kept_voxels'] > 6 * 64 and want['info']['loops'] == 1 and want['info']['nodes'] > 0
+    g = graph_of_range(gpu_ctx, host_texels(mask, dtype))
+    try:
+        check_graph(g, host_texels(mask, dtype), want, "runs in a wave %s" % np.dtype(dtype).name)
+    finally:
+        release(g)
+
+
+@functools.lru_cache(maxsize=None)
+def wave_statement():
+    return frozen(G.graph_of(GC.wave_case()))
+
+
+MANY = (127, 251, 65)                                             # [depth][height][width]
+
+
+@functools.lru_cache(maxsize=None)
+def many_blocks_case():
+    """sparse noise and sixty small clumps in [127][251][65], three planes in the middle left empty: (the set, its statement)"""
+    rng = np.random.default_rng(77)
+    mask = rng.random(MANY) < 0.0016
+    for _ in range(60):
+        z, y, x = (int(rng.integers(0, n - 6)) for n in MANY)
+        mask[z:z + 3, y:y + 4, x:x + 6] |= rng.random((3, 4, 6)) < 0.25
+    mask[60:63] = False
+    mask[-1, -1, -2:] = True                                      # the last block, which the run of one holds, is not empty
+    mask.setflags(write=False)
+    return mask, frozen(G.graph_of(mask))
+
+
+@pytest.mark.timeout(120)
+@pytest.mark.parametrize("dtype", DTYPES, ids=lambda d: np.dtype(d).name)
+def test_the_scan_of_many_blocks_places_the_list(gpu_ctx, dtype):
+    """499 scan blocks: a thread of k_gr_scan_blocks owns a run of two, thread 249 a run of one, threads 250 .. 255 none; a voxel's place
+    in the list, and so whether k_gr_links ever sees it, rests on the offset of its block."""
+    mask, want = many_blocks_case()
+    nz, ny, nx = MANY
+    wpr = 2 * ((nx + 63) // 64)
+    plane_words = nz * ny * wpr
+    blocks = (plane_words + 255) // 256
+    run = (blocks + 255) // 256
+    assert plane_words > 65536 and blocks % 256 != 0 and run >= 2 and blocks % run != 0 and (blocks + run - 1) // run < 256
+    z, y, x = np.nonzero(want['classes'])
+    block = np.unique(((z * ny + y) * wpr + x // 32) // 256)
+    assert len(np.unique(block // run)) >= 200 and int(block.max()) == blocks - 1
+    empty = np.setdiff1d(np.arange(int(block.min()), int(block.max())), block)
+    assert len(empty) >= 1                                        # an all-empty block between two that are not
+    assert 3500 <= want['info']['kept_voxels'] <= 6000 and want['info']['nodes'] > 0 and want['info']['links'] > 0 and (nz * ny * nx) % 4 != 0
+    g = graph_of_range(gpu_ctx, host_texels(mask, dtype))
+    try:
+        check_graph(g, host_texels(mask, dtype), want, "many blocks %s" % np.dtype(dtype).name)
+    finally:
+        release(g)
+
+
+def texels_of_pieces(shape, pieces, dtype):
+    """the pieces' sets in codes of the range, everything else below it; a motif's texels are made once"""
+    made = {}
+    a = np.zeros(shape, dtype)
+    for (oz, oy, ox), kept in pieces:
+        if id(kept) not in made:
+            made[id(kept)] = host_texels(kept, dtype, seed=5 + len(made))
+        d, h, w = kept.shape
+        a[oz:oz + d, oy:oy + h, ox:ox + w] = made[id(kept)]
+    return a
+
+
+def pruned_shares(want, prunings):
+    """per pruning whether the statement drops 'none', 'some' or 'all' of the branches"""
+    gone = [int(GC.dropped(want['branches'], length, weights, G.PRUNE_DEBRIS if debris else 0).sum()) for length, weights, debris, _ in prunings]
+    return ['none' if n == 0 else 'all' if n == len(want['branches']) else 'some' for n in gone]
+
+
+def check_assembled(g, a, want, prunings, what):
+    """`check_graph` against a statement put together from pieces (graph_cases.Assembled.statement), with the pruning stated without a
+    Python loop over the records"""
+    assert g.info == want['info'], what
+    assert g.branch_records().tobytes() == want['branches'].tobytes(), what + ": branch records"
+    assert g.node_records().tobytes() == want['nodes'].tobytes(), what + ": node records"
+    for handed, name in ((g.branches, 'branch_ranks'), (g.nodes, 'node_ranks')):      # a copy of 4 bytes a voxel each: freed before the next
+        try:
+            same(handed.ranks(), want[name], "%s: %s" % (what, name))
+        finally:
+            handed.destroy()
+    pair = g.classes()
+    try:
+        got = whole(pair)
+    finally:
+        pair.destroy()
+    same(got[..., 0], a, what + ": classes, the codes")
+    same(got[..., 1], want['classes'].astype(a.dtype), what + ": classes")
+    del got
+    for length, weights, debris, fill in prunings:
+        flags = G.PRUNE_DEBRIS if debris else 0
+        out = g.prune(length, weights, debris, fill)
+        try:
+            same(whole(out), GC.prune_texels(a, want['classes'], want['branch_ranks'], want['branches'], length, weights, flags, fill), what + ": prune %r" % ((length, weights, debris, fill),))
+        finally:
+            out.destroy()
+
+
+@pytest.mark.timeout(300)
+def test_the_second_trip_of_every_loop_over_voxels(gpu_ctx):
+    """R16.  5400 copies of a padded random set that holds all six kinds, the last one another set: more than 2^21 kept voxels, so
+    k_gr_links makes a second trip; k_gr_seed has more than 32 768 waves' worth of segments, the emitters more than 2^21 quads and the scan
+    thousands of blocks.  The statement is put together from the two motifs (graph_cases.graph_on_pieces)."""
+    first, last = GC.padded(RANDOM['random 6x10x70 0.10 1']()), GC.padded(RANDOM['random 6x10x70 0.10 2']())
+    for seed in (1, 2):
+        info = statement('random 6x10x70 0.10 %d' % seed)['info']
+        assert all(info[k] > 0 for k in ('isolated', 'segments', 'spurs', 'links', 'loops', 'cycles'))
+    shape = (8 * 54, 12 * 25, 72 * 4)
+    nz, ny, nx = shape
+    pieces = GC.tiling(shape, first, last)
+    assert pieces[-1][1] is last and tuple(o + s for o, s in zip(pieces[-1][0], last.shape)) == shape and not np.array_equal(first, last)
+    want = GC.graph_on_pieces(shape, pieces).statement()
+    per_launch = GRID_CAP * 256
+    assert want['info']['kept_voxels'] > per_launch                                          # k_gr_links
+    assert ny * nz * ((nx + 63) // 64) > GRID_CAP * 4                                        # k_gr_seed: a wave an item
+    assert nx * ny * nz // 4 > per_launch                                                    # k_gr_prune, k_gr_classes
+    assert (ny * nz * 2 * ((nx + 63) // 64) + 255) // 256 > 16 * 256                         # k_gr_scan_blocks: runs of 17 and more
+    assert want['info']['nodes'] > 0 and int(want['branches']['tip_hi'].max()) > nx * ny * (nz - 8)
+    prunings = ((20, (10, 14, 17), False, 3), (30, (10, 14, 17), True, 65535))
+    assert pruned_shares(want, prunings) == ['some', 'some']
+    a = texels_of_pieces(shape, pieces, np.uint16)
+    g = graph_of_range(gpu_ctx, a)
+    try:
+        check_assembled(g, a, want, prunings, "rich tiling")
+    finally:
+        release(g)
+
+
+@pytest.mark.timeout(300)
+def test_the_second_trip_of_the_loop_over_branches(gpu_ctx):
+    """R8.  Isolated voxels on even coordinates and a few two-voxel segments, 2160 copies of [8][16][64]: more than 2^21 branches in 17.7 M
+    voxels, so k_gr_init makes a second trip, every rank above 181 440 ties in voxel count and is ordered by its root, and the drop bitmap
+    of a pruning has more than 65 536 words."""
+    shape = (8 * 27, 16 * 20, 64 * 4)
+    pieces = GC.tiling(shape, GC.dust_motif())
+    want = GC.graph_on_pieces(shape, pieces, low_faces=False).statement()
+    assert want['info']['branches'] > GRID_CAP * 256 and want['info']['branches'] // 32 + 1 > 65536
+    assert want['info']['segments'] > 0 and want['info']['isolated'] > GRID_CAP * 256 - want['info']['segments']
+    prunings = ((5, (10, 14, 17), True, 0), (9, (0, 14, 17), False, 9), (10, (10, 14, 17), True, 200))
+    assert pruned_shares(want, prunings) == ['some', 'none', 'all']      # the isolated voxels; no spur to drop; the segments too
+    a = texels_of_pieces(shape, pieces, np.uint8)
+    g = graph_of_range(gpu_ctx, a)
+    try:
+        check_assembled(g, a, want, prunings, "dust tiling")
+    finally:
+        release(g)

@@ -15,6 +15,10 @@ A step that carries 'forced' runs twice, plainly and through the unit's test hoo
 reconstruct_timed _tile_rounds, watershed _caps): the forced result must be the statement's and, byte for byte, the plain call's.
 The slowest of the new seeds measured on an MI355X is seed 148 at 0.65 s (the 96 together: 6 s), most of it the statements on the CPU.
 
+Seeds 224 .. 255 are drawn by the graph rules: centrelines with pruning rounds, the graph of a range or of a skeleton behind other steps,
+its pruning, its class pair (which later two-channel steps and the 2-D transfer function take), its records, and its branches and nodes as
+Components used after the graph has been destroyed.
+
 VPT_VOLFUZZ_SEEDS=a:b widens the sweep."""
 import os
 
@@ -209,6 +213,40 @@ class Replay:
         finally:
             k.destroy()
 
+    def graph_step(self, s):
+        """a step of the graph rules: the graph of a value range or of a skeleton (which is destroyed before the graph is used), used once
+        and destroyed; the handed-out components are used after the graph is gone"""
+        op, kw, src = s['op'], s['kwargs'], self.vols[s['src']]
+        if op == 'centreline_prune':
+            return src.centreline(kw['lo'], kw['hi'], kw['mode'], prune=kw['prune'], prune_rounds=kw['prune_rounds']), None
+        if kw['via'] == 'skeleton':
+            k = src.skeleton(kw['lo'], kw['hi'], kw['mode'])
+            try:
+                g = k.graph()
+            finally:
+                k.destroy()
+        else:
+            g = src.graph(kw['lo'], kw['hi'])
+        handed = None
+        try:
+            if op == 'graph_prune':
+                return g.prune(kw['length'], kw['weights'], kw['debris'], kw['fill']), None
+            if op == 'graph_classes':
+                return g.classes(), None
+            if op == 'graph_info':
+                return None, g.info
+            if op == 'graph_branches':
+                return None, g.branch_records(kw['first'], kw['n'])
+            if op == 'graph_nodes':
+                return None, g.node_records()
+            handed = g.branches if op == 'branches_keep_set' else g.nodes
+            g.destroy()
+            return (handed.keep_set(kw['ranks'], kw['fill']) if op == 'branches_keep_set' else handed.label()), None
+        finally:
+            if handed is not None:
+                handed.destroy()
+            g.destroy()
+
     def later(self, i):
         """step i of the later units; where the case forces the slow path, again through the hook: the same bytes, the same scalar"""
         s = self.steps[i]
@@ -258,6 +296,8 @@ class Replay:
             return src.rank(kw['op'], kw['passes']), None
         if op == 'resample':
             return src.resample(kw['width'], kw['height'], kw['depth'], kw['mode']), None
+        if op in V.GRAPH:
+            return self.graph_step(s)
         if op in V.LATER:
             return self.later(i)
         if op in V.FAMILY and op != 'resample':                   # components and distances: made, used once, destroyed

@@ -18,6 +18,7 @@ from vpt_amd import graph as G
 from vpt_amd.components import components_texels, neighbour_offsets
 from vpt_amd.skeleton import KEPT, skeleton_burn_texels
 
+import graph_cases as GC
 from test_skeleton_host import HI, LO, SHAPES, texels
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -256,6 +257,78 @@ def test_the_empty_set_and_a_single_voxel():
     assert np.array_equal(G.prune_texels(a, g, 5, fill=9), np.full(a.shape, 9, np.uint8))
     g = G.graph_texels(np.full((1, 1, 1), 7, np.uint8), 7, 7)
     assert rows(g['branches'], 'voxels', 'kind', 'tip_lo', 'tip_hi') == [(1, G.ISOLATED, 0, 0)] and g['info']['isolated'] == 1
+
+
+# ---- content made of pieces (tests/graph_cases.py) ---------------------------------------------------------------------------------
+def equals_whole(assembled, kept):
+    """the assembled statement is graph_of of the whole set: info, every record, every rank, byte for byte"""
+    want, got = G.graph_of(kept), assembled.statement()
+    assert got['info'] == want['info']
+    for key in ('classes', 'branch_ranks', 'node_ranks', 'branches', 'nodes'):
+        assert got[key].dtype == want[key].dtype and got[key].shape == want[key].shape and got[key].tobytes() == want[key].tobytes(), key
+    return want
+
+
+def motif(seed):
+    return GC.padded(random_set((6, 10, 70), 0.10, seed))
+
+
+def test_a_tiling_of_one_motif_assembles_to_the_statement_on_the_whole():
+    shape = (16, 24, 144)                                         # 2 x 2 x 2 periods of [8][12][72]
+    pieces = GC.tiling(shape, motif(1))
+    assert len(pieces) == 8 and len({id(m) for _, m in pieces}) == 1
+    want = equals_whole(GC.graph_on_pieces(shape, pieces), GC.set_of(shape, pieces))
+    one = statement('random 6x10x70 0.10 1')['info']
+    assert want['info'] == {k: 8 * v for k, v in one.items()} and one['nodes'] > 0 and one['cycles'] > 0
+    # equal voxel counts in different pieces: ranked by the root's index in the volume, which no piece's own order knows
+    assert len(set(want['branches']['voxels'].tolist())) < len(want['branches']) // 8
+
+
+def test_a_tiling_of_two_motifs_and_an_odd_volume_assemble_to_the_statement_on_the_whole():
+    shape = (17, 27, 149)                                         # the periods do not fill it
+    a, b = motif(2), motif(3)
+    pieces = [(o, b if i in (1, 2, 4, 7) else a) for i, (o, _) in enumerate(GC.tiling(shape, a))]
+    assert len(pieces) == 8
+    want = equals_whole(GC.graph_on_pieces(shape, pieces), GC.set_of(shape, pieces))
+    # pieces of different content tie in voxel count, and a node of one piece and a node of another trade places in the order
+    ranks = [GC.graph_on_pieces(shape, pieces).node_table[k][1:] for k in range(8)]
+    assert all(len(r) > 0 for r in ranks) and any(int(ranks[k].min()) < int(ranks[0].max()) for k in range(1, 8))
+    assert int(want['branches']['tip_hi'].max()) > 8 * 12 * 72 and int(want['branches']['node_hi'].max()) == want['info']['nodes']
+
+
+def test_the_dust_tiling_needs_only_the_upper_faces():
+    shape = (16, 32, 128)
+    pieces = GC.tiling(shape, GC.dust_motif())
+    want = equals_whole(GC.graph_on_pieces(shape, pieces, low_faces=False), GC.set_of(shape, pieces))
+    assert want['info']['branches'] == 8 * 980 and want['info']['isolated'] == 8 * 896 and want['info']['segments'] == 8 * 84 and want['info']['nodes'] == 0
+    with pytest.raises(AssertionError, match='first plane'):
+        GC.graph_on_pieces(shape, pieces)
+    with pytest.raises(AssertionError, match='overlap'):
+        GC.graph_on_pieces(shape, pieces + [((4, 8, 32), pieces[0][1])], low_faces=False)
+    with pytest.raises(AssertionError, match='last plane'):
+        GC.graph_on_pieces(shape, [((0, 0, 0), np.ones((2, 2, 2), bool))])
+
+
+@pytest.mark.parametrize("name", ['torus', 'random 6x10x70 0.10 1', 'random 9x11x12 0.14 2'])
+def test_the_vectorised_pruning_is_the_statements(name):
+    kept, g = kept_set(name), statement(name)
+    a = texels(kept)
+    for length, weights, flags in ((0, (10, 14, 17), 0), (20, (10, 14, 17), 0), (45, (10, 14, 17), 1), (2, (1, 0, 65535), 0), ((1 << 64) - 1, (65535,) * 3, 1)):
+        assert np.array_equal(GC.dropped(g['branches'], length, weights, flags), G.dropped(g['branches'], length, weights, flags))
+        assert np.array_equal(GC.prune_texels(a, g['classes'], g['branch_ranks'], g['branches'], length, weights, flags, 3), G.prune_texels(a, g, length, weights, flags, 3))
+    big = np.zeros(2, G.BRANCH_DTYPE)                             # a cost that wraps modulo 2^64, as the device's does
+    big['kind'], big['steps_face'] = G.SPUR, (1 << 63, 5)
+    assert GC.dropped(big, 9, (2, 0, 0)).tolist() == G.dropped(big, 9, (2, 0, 0)).tolist() == [True, False]
+
+
+def test_the_wave_case_holds_the_runs_it_is_for():
+    g = G.graph_of(GC.wave_case())
+    waves = GC.wave_runs(g)
+    assert sum(lanes for runs in waves for _, _, lanes in runs) == g['info']['kept_voxels'] == 416
+    met = GC.wave_conditions(waves)
+    assert met['full'] == [1, 2] and met['carried'] == [0] and waves[0][-1] == (1, 37, 27) and met['last lane'] == [3]
+    assert 4 in met['over nodes'] and 6 in met['apart']
+    assert int(g['branches'][0]['voxels']) == 200 and int(g['branches'][1]['kind']) == G.LOOP and g['info']['isolated'] == 63
 
 
 # ---- the JS statement -------------------------------------------------------------------------------------------------------------

@@ -13,7 +13,7 @@ import vpt_amd
 from vpt_amd.resample import nearest_index
 
 from large_volumes import (TIER_A, TIER_B, REACH, MARGIN, Layout, voxels, volume_bytes, distance_squared_within, slab_distances, counts, solids, crop_array,
-                           on_crops, watershed_on_crops, skeleton_on_crops, surface_on_crops, shift_twin_vertices, thickness_tiles)
+                           on_crops, watershed_on_crops, skeleton_on_crops, graph_on_crops, surface_on_crops, shift_twin_vertices, thickness_tiles)
 
 SHAPE = (11, 9, 40)                                               # nx, ny, nz
 MARK = 11 * 9 * 21 + 5                                            # the linear voxel index the middle slab straddles
@@ -321,6 +321,28 @@ def test_skeleton_on_crops(mode):
     moved[2:4, 2:5, 2:4] = 200
     assert not np.array_equal(vpt_amd.skeleton_burn_texels(moved, 1, 255, mode)[0][:, :, 1:],
                               vpt_amd.skeleton_burn_texels(np.roll(moved, -1, axis=2), 1, 255, mode)[0][:, :, :-1])
+
+
+def test_graph_on_crops():
+    """The graph of the 'ends' skeleton's kept set and of value ranges of the solids themselves: info, every record and every rank of the
+    crops' graphs put together (graph_on_crops) are graph_of of the whole volume.  The range 1 .. M keeps every solid whole (nodes); a range
+    of the upper codes leaves specks and short chains of the noise inside them (branches)."""
+    from vpt_amd import graph as G
+    lay = solid_layout()
+    blocks, crops = solids(lay, np.uint8, 11)
+    burn, _ = skeleton_on_crops(lay, blocks, crops, 1, 255, 'ends')
+    sets = {'skeleton': [b == 0xFFFFFFFF for b in burn], '1 .. M': [b >= 1 for b in blocks], '224 .. M': [b >= 224 for b in blocks]}
+    seen = {}
+    for what, kept in sets.items():
+        want = G.graph_of(lay.whole(kept))
+        graph, fields = graph_on_crops(lay, kept, crops)
+        assert graph.info == want['info'], what
+        assert graph.branches.tobytes() == want['branches'].tobytes() and graph.nodes.tobytes() == want['nodes'].tobytes(), what
+        for name, blocks_of in fields.items():
+            assert np.array_equal(lay.whole(blocks_of), want[name]) and lay.whole(blocks_of).dtype == want[name].dtype, (what, name)
+        seen[what] = want['info']
+    assert seen['skeleton']['branches'] >= len(crops) // 2 and seen['skeleton']['kept_voxels'] > 0
+    assert seen['1 .. M']['nodes'] >= len(crops) and seen['224 .. M']['branches'] >= 64 and seen['224 .. M']['links'] > 0 and seen['224 .. M']['spurs'] > 0
 
 
 @pytest.mark.parametrize("dtype", DTYPES)

@@ -3,9 +3,9 @@ scenarios do.  Reads the table only: no GPU, no torch."""
 import stream_order_worker as S
 
 # the entries that wait for the host by design: host uploads, the tables, a float volume's finalize, multi-pass rank and smooth, the
-# filtered resample, every query and read-back (the voxel fields' labelling and transform read counts back)
+# filtered resample, every query and read-back (the voxel fields' labelling and transform read counts back, the graph's two labellings too)
 MUST_BLOCK = {'upload_block', 'setTransferFunction', 'set_environment', 'set_environment_texels', 'finalize(float)', 'smooth(n)', 'rank(n)',
-              'resample(filtered)', 'read', 'components', 'distance'}
+              'resample(filtered)', 'read', 'components', 'distance', 'graph'}
 # the entries include/vpt.h lists as returning without a host wait: each needs a scenario that finds the gate closed behind it
 MUST_NOT_BLOCK = {'upload_block_device', 'finalize', 'reduce', 'smooth(1)', 'rank(1)', 'combine', 'window', 'derive_gradient', 'resample(nearest)',
                   'render', 'play_into', 'play_into_display', 'set_render_target', 'join'}
@@ -52,6 +52,16 @@ def test_every_asynchronous_entry_has_a_scenario_that_looks_at_the_gate():
 def test_every_family_is_present():
     assert {s['family'] for s in S.SCENARIOS} == set('ABCDEFG') == set(S.FAMILIES)
     assert all(s['name'].startswith(s['family'] + '_') for s in S.SCENARIOS)
+
+
+def test_the_graph_is_reached_on_a_callers_stream():
+    (s,) = [s for s in S.SCENARIOS if 'graph' in s['entries']]
+    assert s['family'] == 'C' and s['waits'] == 'blocking' and {'graph', 'graph.prune', 'upload_block_device', 'render'} <= set(s['entries'])
+    # the emitters of a graph built before the gate are looked at behind it; include/vpt.h does not list them among the entries that
+    # return without a host wait, so MUST_NOT_BLOCK does not name them
+    (s,) = [s for s in S.SCENARIOS if 'graph.classes' in s['entries']]
+    assert s['family'] == 'C' and s['waits'] == 'asynchronous' and {'graph.branch_components', 'label', 'upload_block_device'} <= set(s['entries'])
+    assert not {'graph.classes', 'graph.branch_components', 'label'} & MUST_NOT_BLOCK
 
 
 def test_the_gate_is_ten_enqueue_times_and_under_half_a_second():

@@ -6,6 +6,7 @@ later rules (128 ..): that the thinning steps make several passes and cross a wo
 centre tiles than one step of the walk takes and hold a ball that reaches past the neighbouring tile, that reconstructions propagate and
 clamp, that watersheds split and a basin crosses tiles, that a block of the measuring kernel holds more ranks than its table has slots, and
 that every forced slow path occurs.  The counts come from each step's 'facts', taken from the statements when the step was drawn."""
+import hashlib
 import time
 
 import numpy as np
@@ -22,7 +23,7 @@ PRODUCING = [(seed, i, s) for seed, i, s in STEPS if s['out'] is not None]
 
 def test_generation_is_quick_and_repeats_itself():
     assert GENERATION_SECONDS < 30.0, "%.1f s for %d chains" % (GENERATION_SECONDS, len(SEEDS))
-    for seed in SEEDS[:6] + SEEDS[V.LATER_SEEDS:V.LATER_SEEDS + 6]:
+    for seed in SEEDS[:6] + SEEDS[V.LATER_SEEDS:V.LATER_SEEDS + 6] + SEEDS[V.GRAPH_SEEDS:V.GRAPH_SEEDS + 6]:
         again = V._build(seed)
         assert len(again) == len(CHAINS[seed])
         for a, b in zip(again, CHAINS[seed]):
@@ -60,7 +61,7 @@ def test_few_results_are_constant():
 
 
 def test_every_operation_occurs_three_times():
-    count = {entry: 0 for entry in V.ENTRIES}
+    count = {entry: 0 for entry in V.ENTRIES + V.GRAPH_ENTRIES}
     for _, _, s in STEPS:
         count[(s['op'], s['sub'])] += 1
     rare = {entry: n for entry, n in count.items() if n < 3}
@@ -152,10 +153,29 @@ def test_the_first_seeds_are_drawn_by_the_first_rules():
     for seed in SEEDS[:V.LATER_SEEDS]:
         assert all(s['op'] in V.OLD_OPS + ('source',) for s in CHAINS[seed]), seed
     assert len(SEEDS) % 16 == 0 and SEEDS[0] == 0 and len(SEEDS) > V.LATER_SEEDS
+    for seed in SEEDS[V.LATER_SEEDS:V.GRAPH_SEEDS]:
+        assert not any(s['op'] in V.GRAPH for s in CHAINS[seed]), seed
+
+
+def chains_digest(seeds):
+    h = hashlib.sha256()
+    for seed in seeds:
+        for s in CHAINS[seed]:
+            h.update(repr((s['op'], s['sub'], s['src'], s['out'], s['shape'], s['format'])).encode())
+            e = s['expect']
+            h.update(np.ascontiguousarray(e).tobytes() if isinstance(e, np.ndarray) else repr(e).encode())
+    return h.hexdigest()
+
+
+def test_the_chains_before_the_graph_rules_are_what_they_were():
+    """every step's operation, volumes, shape, format and expected bytes of seeds 0 .. 127 and 128 .. 223, as they were drawn before the
+    graph rules joined (the digests were taken from the file as it was then)"""
+    assert chains_digest(SEEDS[:V.LATER_SEEDS]) == '028619680012038586cbcde812576811ed7d9fe13303d3a6e646c6a254f84727'
+    assert chains_digest(SEEDS[V.LATER_SEEDS:V.GRAPH_SEEDS]) == '729049973b01db6e17a77b1a8cf9dea0013a862ca36d4b2e6eb3e954a37c8dc8'
 
 
 def test_a_later_chain_has_two_later_steps_and_one_reads_a_derived_volume():
-    for seed in SEEDS[V.LATER_SEEDS:]:
+    for seed in SEEDS[V.LATER_SEEDS:V.GRAPH_SEEDS]:
         later = [s for s in CHAINS[seed][1:] if s['op'] in V.LATER]
         assert len(later) >= 2 and any(V._reads_derived(s) for s in later), seed
         for s in later:
@@ -230,3 +250,43 @@ def test_every_forced_slow_path_occurs_three_times():
         if s['forced'] is not None:
             count[(V.FAMILY[s['op']], s['forced'])] += 1
     assert all(n >= 3 for n in count.values()), count
+
+
+# ---- the graph rules (seeds 224 ..) ------------------------------------------------------------------------------------------------
+GRAPH_STEPS = [(seed, i, s) for seed, i, s in STEPS if s['op'] in V.GRAPH]
+
+
+def test_the_graph_seeds_reach_the_graph_behind_other_steps():
+    assert len(SEEDS) == V.GRAPH_SEEDS + 32 and all(seed >= V.GRAPH_SEEDS for seed, _, _ in GRAPH_STEPS)
+    for seed in SEEDS[V.GRAPH_SEEDS:]:
+        mine = [s for s in CHAINS[seed][1:] if s['op'] in V.GRAPH]
+        assert len(mine) >= 2 and any(V._reads_derived(s) for s in mine), seed
+        assert all(int(np.prod(s['shape'])) <= V.SLOW_VOXELS for s in mine), seed
+    count = {op: 0 for op in V.GRAPH}
+    for _, _, s in GRAPH_STEPS:
+        count[s['op']] += 1
+    assert all(n >= 2 for n in count.values()), count
+    # a class pair stands in front of another step (two-channel steps and the 2-D transfer function follow it), and is a chain's last volume
+    read = last = 0
+    for seed in SEEDS[V.GRAPH_SEEDS:]:
+        steps = CHAINS[seed]
+        made = {s['out'] for s in steps[1:] if s['op'] == 'graph_classes'}
+        read += sum(1 for s in steps[1:] if s['src'] in made)
+        last += max(s['out'] for s in steps if s['out'] is not None) in made
+    assert read >= 2 and last >= 1, (read, last)
+    assert {s['kwargs']['via'] for _, _, s in GRAPH_STEPS if s['op'] != 'centreline_prune'} == {'skeleton', 'range'}
+    assert {s['kwargs']['prune_rounds'] for _, _, s in GRAPH_STEPS if s['op'] == 'centreline_prune'} == {1, 3}
+
+
+def test_the_drawn_prunings_drop_a_spur_and_keep_one():
+    prunes = [s for _, _, s in GRAPH_STEPS if s['op'] == 'graph_prune']
+    assert len(prunes) >= 8
+    assert 2 * sum(s['facts']['spur_dropped'] and s['facts']['spur_kept'] for s in prunes) >= len(prunes)
+    assert any(s['kwargs']['debris'] for s in prunes) and any(not s['kwargs']['debris'] for s in prunes)
+    assert any(s['kwargs']['weights'] != (10, 14, 17) for s in prunes) and any(s['kwargs']['fill'] for s in prunes)
+    lines = [s for _, _, s in GRAPH_STEPS if s['op'] == 'centreline_prune']
+    assert 2 * sum(s['facts']['differs_from_unpruned'] for s in lines) >= len(lines), [s['facts'] for s in lines]
+    graphs = [s['facts'] for _, _, s in GRAPH_STEPS if s['op'] != 'centreline_prune']
+    assert 2 * sum(f['branches'] >= 3 and f['nodes'] >= 1 for f in graphs) >= len(graphs)
+    windows = [s['kwargs'] for _, _, s in GRAPH_STEPS if s['op'] == 'graph_branches']
+    assert any(k['first'] > 0 for k in windows) and any(k['n'] is not None for k in windows)

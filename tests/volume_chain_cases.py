@@ -39,7 +39,15 @@ units, one of which reads a volume a derive step made, else it is drawn again fr
 == 3) forces the slow paths: its steps of the families of FORCED carry 'forced', the hook's value, and run plainly and through the hook.
 A later step carries 'facts': what the statements said of it when it was drawn (passes, basins, centre tiles ...), for the conditions.
 
-DEFAULT_SEEDS ends at 224: the smallest multiple of 16 at which every condition of tests/test_volume_chain_cases.py holds.  The last to
+Seeds from GRAPH_SEEDS = 224 on are drawn by the graph rules (``_draw_later_chain(graph=True)``, ``_draw_graph_step``): the later rules
+with an R8 or R16 source of 200 .. GRAPH_VOXELS voxels (blobs, a sphere or sparse noise), GRAPH_PLANS for the first ten, wishes over
+GRAPH_ENTRIES, and a step that is, three times in five, an entry of GRAPH: a centreline with pruning rounds, the pruning, the class pair
+and the records of the graph of a value range or of a skeleton, and its branches and nodes as Components once the graph is gone.  A chain
+must hold two such steps, one of which reads a derived volume.  The entries of GRAPH are in none of the lists above and every draw the
+rules add stands behind ``if graph``: the chains of seeds 0 .. 223 are, byte for byte, what they were (pinned by digest in
+tests/test_volume_chain_cases.py).
+
+The later rules alone end at 224: the smallest multiple of 16 at which every condition of tests/test_volume_chain_cases.py held.  The last to
 come are every (format, entry) pair (RG8 basins_label first occurs in 208 .. 223), a labelling with more than 512 ranks in one block
 of the measuring kernel together with values from a derived pair's second channel (192 .. 207), and three steps of every forced hook
 (reconstruct's: 192 .. 207)."""
@@ -63,8 +71,10 @@ from vpt_amd.watershed import watershed_texels, split_texels
 from vpt_amd.window import window_texels, percentile_window
 
 CONSTANT = 20261019
-DEFAULT_SEEDS = (0, 224)
+DEFAULT_SEEDS = (0, 256)
 LATER_SEEDS = 128                                      # the first seed drawn by the later rules (module docstring)
+GRAPH_SEEDS = 224                                      # the first seed drawn by the graph rules (module docstring)
+GRAPH_VOXELS = 6000                                    # the sources of those seeds: the graph statement visits kept voxels one by one
 MAX_VOXELS = 100000
 SLOW_VOXELS = 20000                                    # the thinning and thickness statements: seconds beyond (tests/test_gpu_thickness_fuzz.py's cap)
 MAX_ROW_PASS = 400000                                  # resample: target width x source height x source depth (the row pass's workspace)
@@ -102,6 +112,15 @@ LATER = {
     'thickness_squared': _U1, 'thickness_info': _U1, 'skeleton_burn': _U1, 'skeleton_info': _U1,
 }
 LEGAL.update(LATER)
+# the skeleton graph: the set is a value range of the volume (Volume.graph) or the kept voxels of its skeleton (Skeleton.graph)
+GRAPH = {
+    'centreline_prune': _U1,                           # Volume.centreline(lo, hi, mode, prune, prune_rounds)
+    'graph_prune': _U1, 'graph_classes': _U1,          # Graph.prune(length, weights, debris, fill); Graph.classes(): the (code, class) pair
+    'branches_keep_set': _U1, 'nodes_label': _U1,      # Graph.branches / .nodes, used after the graph has been destroyed
+    'graph_info': _U1, 'graph_branches': _U1, 'graph_nodes': _U1,
+}
+LEGAL.update(GRAPH)
+GRAPH_SCALAR_OPS = ('graph_info', 'graph_branches', 'graph_nodes')
 RESAMPLE_FILTERED = _UNORM
 COMBINE_OPS = ('mask', 'min', 'max', 'absdiff', 'blend', 'pair')
 SCALAR_OPS = ('range', 'histogram', 'code_histogram', 'percentile_window', 'compare', 'components_info', 'components_list',
@@ -133,6 +152,10 @@ LATER_ENTRIES = LATER_VOLUME_ENTRIES + LATER_SCALAR_ENTRIES
 VOLUME_ENTRIES = OLD_VOLUME_ENTRIES + LATER_VOLUME_ENTRIES
 SCALAR_ENTRIES = OLD_SCALAR_ENTRIES + LATER_SCALAR_ENTRIES
 ENTRIES = OLD_ENTRIES + LATER_ENTRIES
+# the entries of the graph rules: kept apart, so that the chains of seeds 0 .. 223 stay what they were (ENTRIES is what they are drawn from)
+GRAPH_VOLUME_ENTRIES = [(op, None) for op in GRAPH if op not in GRAPH_SCALAR_OPS]
+GRAPH_SCALAR_ENTRIES = [(op, None) for op in GRAPH_SCALAR_OPS]
+GRAPH_ENTRIES = GRAPH_VOLUME_ENTRIES + GRAPH_SCALAR_ENTRIES
 
 # kernel family -> the extents (x, y, z) of its tile; None: the kernel has no tile along that axis
 TILES = {
@@ -157,6 +180,7 @@ FAMILY = {'derive_gradient': 'gradient', 'smooth': 'smooth', 'rank': 'rank', 'ke
           'thickness': 'thickness', 'open_ball': 'thickness', 'thickness_within': 'thickness', 'thickness_channel': 'thickness',
           'thickness_squared': 'thickness', 'thickness_info': 'thickness', 'centreline': 'skeleton', 'skeleton_within': 'skeleton',
           'skeleton_burn': 'skeleton', 'skeleton_info': 'skeleton'}
+FAMILY.update({op: 'graph' for op in GRAPH})
 SLOW_FAMILIES = ('thickness', 'skeleton')              # at most SLOW_VOXELS voxels a step
 # the kernels with a vector form and a texel-by-texel form, chosen by the row length: nx % 4 (gradient, smooth, rank: ALIGNED), the row's
 # bytes % 32 (k_reduce); window and combine go by 16-byte groups of the whole volume
@@ -238,6 +262,20 @@ def _later_plans():
 
 
 LATER_PLANS = _later_plans()
+# the seeds of the graph rules that are planned: every graph entry begins a chain on both widths, on shapes that cross a word of the
+# bit plane (32), a 64-voxel segment and a labelling tile (64 x 8 x 4)
+GRAPH_PLANS = [
+    ((5, 9, 65), [('centreline_prune', None), ('graph_info', None), ('graph_prune', None)], 'blobs'),
+    ((9, 17, 33), [('graph_prune', None), ('graph_classes', None), ('graph_branches', None)], 'sphere'),
+    ((6, 10, 70), [('graph_classes', None), ('branches_keep_set', None), ('graph_nodes', None)], 'blobs'),
+    ((9, 8, 66), [('branches_keep_set', None), ('nodes_label', None), ('graph_info', None)], 'blobs'),
+    ((12, 14, 31), [('nodes_label', None), ('centreline_prune', None), ('graph_branches', None)], 'sphere'),
+    ((5, 16, 64), [('graph_nodes', None), ('graph_prune', None), ('centreline_prune', None)], 'blobs'),
+    ((7, 9, 96), [('graph_info', None), ('graph_classes', None), ('nodes_label', None)], 'blobs'),
+    ((13, 13, 32), [('graph_branches', None), ('branches_keep_set', None), ('graph_prune', None)], 'sphere'),
+    ((4, 11, 129), [('centreline_prune', None), ('graph_nodes', None), ('graph_classes', None)], 'blobs'),
+    ((10, 12, 40), [('graph_prune', None), ('nodes_label', None), ('graph_info', None)], 'sphere'),
+]
 
 
 # ---- texels --------------------------------------------------------------------------------------------------------------------
@@ -750,6 +788,67 @@ def _draw_later_step(c, cur, entry):
     return step, made
 
 
+def _draw_graph_step(c, cur, entry):
+    """``_draw_step`` for the entries of the graph rules.  The set is the kept voxels of a skeleton of volume ``cur`` ('via': 'skeleton',
+    three times in four) or a value range of it ('range'; a range from a quantile up of what a centreline step made is a thin set too).  A
+    prune length is, four times in five, the median cost of the graph's spurs, so that it drops one and keeps one where their costs differ."""
+    from vpt_amd import graph as G
+    rng, (op, _) = c.rng, entry
+    a = c.texels[cur]
+    fmt = format_of(a)
+    M = int(np.iinfo(a.dtype).max)
+    grid = a.shape[:3]
+    made, expect, facts = None, None, {}
+    lo, hi = _object_range(rng, a)
+    mode = tuple(SKELETON_MODES)[int(rng.integers(3))]
+    if op == 'centreline_prune':
+        if lo == 0 and hi >= M:
+            hi = M - 1
+        burn, _ = skeleton_burn_texels(a, lo, hi, mode)
+        spurs = G.skeleton_graph_texels(burn)['branches']
+        spurs = spurs[spurs['kind'] == G.SPUR]
+        costs = np.sort(10 * spurs['steps_face'].astype(np.int64) + 14 * spurs['steps_edge'].astype(np.int64) + 17 * spurs['steps_corner'].astype(np.int64))
+        prune = int(costs[len(costs) // 2]) if len(costs) and rng.random() < 0.8 else int(rng.integers(0, 60))
+        kw = {'lo': lo, 'hi': hi, 'mode': mode, 'prune': prune, 'prune_rounds': (1, 3)[int(rng.integers(2))]}
+        made = G.centreline_texels(a, lo, hi, mode, prune, kw['prune_rounds'])
+        facts = {'spurs': int(len(costs)), 'differs_from_unpruned': bool((made != burn_within_texels(a, burn, KEPT, KEPT, 0)).any())}
+    else:
+        via = 'skeleton' if rng.random() < 0.75 else 'range'
+        kw = {'via': via, 'lo': lo, 'hi': hi, 'mode': mode}
+        g = G.skeleton_graph_texels(skeleton_burn_texels(a, lo, hi, mode)[0]) if via == 'skeleton' else G.graph_texels(a, lo, hi)
+        facts = dict(g['info'], via=via)
+        fill = int(rng.integers(0, M + 1)) if rng.random() < 0.5 else 0
+        if op == 'graph_prune':
+            b = g['branches']
+            weights = G.DEFAULT_WEIGHTS if rng.random() < 0.6 else tuple(int(w) for w in rng.integers(0, 30, size=3))
+            cost = weights[0] * b['steps_face'].astype(np.int64) + weights[1] * b['steps_edge'].astype(np.int64) + weights[2] * b['steps_corner'].astype(np.int64)
+            spurs = np.sort(cost[b['kind'] == G.SPUR])
+            length = int(spurs[(len(spurs) - 1) // 2]) if len(spurs) and rng.random() < 0.8 else int(rng.integers(0, 80))
+            kw.update({'length': length, 'weights': weights, 'debris': bool(rng.random() < 0.4), 'fill': fill})
+            made = G.prune_texels(a, g, length, weights, G.PRUNE_DEBRIS if kw['debris'] else 0, fill)
+            facts.update(spur_dropped=bool(len(spurs) and spurs[0] <= length), spur_kept=bool(len(spurs) and spurs[-1] > length))
+        elif op == 'graph_classes':
+            made = G.classes_texels(a, g)
+        elif op == 'branches_keep_set':
+            kw.update({'ranks': _draw_selection(rng, len(g['branches'])), 'fill': fill})
+            made = keep_set_texels(a, g['branch_ranks'], kw['ranks'], fill)
+        elif op == 'nodes_label':
+            made = label_texels(a, g['node_ranks'])
+        elif op == 'graph_info':
+            expect = g['info']
+        elif op == 'graph_branches':
+            n = len(g['branches'])
+            first = int(rng.integers(0, n + 1))
+            kw.update({'first': first, 'n': None if rng.random() < 0.5 else int(rng.integers(0, n - first + 1))})
+            expect = g['branches'][first:] if kw['n'] is None else g['branches'][first:first + kw['n']]
+        else:
+            assert op == 'graph_nodes', op
+            expect = g['nodes']
+    step = {'op': op, 'sub': None, 'src': cur, 'out': None, 'kwargs': kw, 'expect': made if made is not None else expect, 'shape': tuple(grid),
+            'format': fmt, 'b_source': None, 'facts': facts, 'forced': None}
+    return step, made
+
+
 def _draw_selected(c, cur, tail, kw, emitted, ranks, listed, facts, every, foreground):
     """(the texels made, the scalar expected) of ``tail`` (keep, label, keep_set, info, list, ranks, measure) of a labelling of volume
     ``cur`` whose emitters speak of ``emitted``; fills ``kw`` in"""
@@ -806,6 +905,8 @@ def _legal(entry, fmt, texels):
     if op == 'range' and fmt == 'R32F' and np.isnan(texels).all():
         return False
     if FAMILY.get(op) in SLOW_FAMILIES and op in LATER and int(np.prod(texels.shape[:3])) > SLOW_VOXELS:
+        return False
+    if op in GRAPH and int(np.prod(texels.shape[:3])) > SLOW_VOXELS:
         return False
     return True
 
@@ -889,19 +990,26 @@ def _reads_derived(step):
                                   for key in ('b', 'texels'))
 
 
-def _draw_later_chain(seed, attempt):
+def _draw_later_chain(seed, attempt, graph=False):
+    """a chain of the later rules; ``graph``: of the graph rules (module docstring).  Every draw the graph rules add stands behind
+    ``if graph``, so the streams of seeds 128 .. 223 are what they were"""
     c = _Chain(seed)
     rng = c.rng = np.random.default_rng([CONSTANT + seed, attempt])
-    n = seed - LATER_SEEDS
+    n = seed - (GRAPH_SEEDS if graph else LATER_SEEDS)
     tiny = seed % 16 == 0
     rank = n - n // 16 - 1
-    plan = LATER_PLANS[rank] if not tiny and rank < len(LATER_PLANS) else None
-    free = rank - len(LATER_PLANS)
+    plans = GRAPH_PLANS if graph else LATER_PLANS
+    plan = plans[rank] if not tiny and rank < len(plans) else None
+    free = rank - len(plans)
     c.fine = plan is not None and plan[2] == 'noise' and ('basins_measure', None) in plan[1]
     if tiny:
         fmt, shape, style = _UNORM[(seed // 16) % 4], (1, 1, 1), None
     elif plan is not None:
         fmt, shape, style = _U1[rank % 2], plan[0], plan[2]
+    elif graph:
+        fmt = _U1[free % 2]
+        shape = draw_shape(rng, fits=lambda s: 200 <= s[0] * s[1] * s[2] <= GRAPH_VOXELS)
+        style = ('blobs', 'sphere', 'blobs', 'sparse')[int(rng.integers(4))]
     else:
         fmt = ('R8', 'RG8', 'R16', 'RG16', 'RG8', 'R16', 'RG16', 'R8')[free % 8]
         shape = draw_shape(rng, fits=lambda s: s[0] * s[1] * s[2] <= (2 if free % 3 == 2 else 1) * SLOW_VOXELS)
@@ -911,7 +1019,8 @@ def _draw_later_chain(seed, attempt):
     c.steps.append({'op': 'source', 'sub': None, 'src': None, 'out': 0, 'kwargs': {'format': fmt, 'texels': source}, 'expect': c.texels[0],
                     'shape': tuple(shape), 'format': fmt, 'b_source': None})
     begin = list(plan[1]) if plan is not None else []
-    wishes = [LATER_ENTRIES[(3 * n + j) % len(LATER_ENTRIES)] for j in range(3)]
+    wished_of = GRAPH_ENTRIES if graph else LATER_ENTRIES
+    wishes = [wished_of[(3 * n + j) % len(wished_of)] for j in range(3)]
     count = max(int(rng.integers(3, 7)), len(begin))
     forced = seed % 4 == 3
     for k in range(count):
@@ -928,6 +1037,8 @@ def _draw_later_chain(seed, attempt):
                 pool = [('upload_block', None)] if roll < 0.2 and 0 < k < count - 1 and c.steps[-1]['op'] != 'upload_block' else \
                     (LATER_SCALAR_ENTRIES if later else OLD_SCALAR_ENTRIES) if roll < 0.45 and k > 0 else \
                     (LATER_VOLUME_ENTRIES if later else OLD_VOLUME_ENTRIES)
+                if graph and pool[0][0] != 'upload_block' and rng.random() < 0.6:
+                    pool = GRAPH_SCALAR_ENTRIES if roll < 0.45 and k > 0 else GRAPH_VOLUME_ENTRIES
                 wished = [e for e in wishes if e not in c.used and _legal(e, fmt, texels)]
                 legal = [e for e in pool if _legal(e, fmt, texels)] or [e for e in LATER_VOLUME_ENTRIES if _legal(e, fmt, texels)]
                 fresh = [e for e in legal if e not in c.used]
@@ -935,7 +1046,7 @@ def _draw_later_chain(seed, attempt):
                     entry = wished[0]
                 else:
                     entry = (fresh or legal)[int(rng.integers(len(fresh or legal)))]
-            step, made = (_draw_later_step if entry[0] in LATER else _draw_step)(c, cur, entry)
+            step, made = (_draw_graph_step if entry[0] in GRAPH else _draw_later_step if entry[0] in LATER else _draw_step)(c, cur, entry)
             if made is None or texels.size == 1 or made.size == 1 or not _constant(made) or redraw == REDRAWS:
                 break
         if forced and FAMILY.get(entry[0]) in FORCED and entry[0] in LATER and entry[0] not in UNHOOKED:
@@ -964,8 +1075,18 @@ def _build_later(seed):
     raise AssertionError('seed %d: no chain of the later rules' % seed)
 
 
+def _build_graph(seed):
+    """a chain of the graph rules: at least two steps of the graph family, one of which reads a volume that a derive step made"""
+    for attempt in range(64):
+        steps = _draw_later_chain(seed, attempt, graph=True)
+        mine = [s for s in steps[1:] if s['op'] in GRAPH]
+        if len(mine) >= 2 and any(_reads_derived(s) for s in mine):
+            return steps
+    raise AssertionError('seed %d: no chain of the graph rules' % seed)
+
+
 def _build(seed):
-    return _build_old(seed) if seed < LATER_SEEDS else _build_later(seed)
+    return _build_old(seed) if seed < LATER_SEEDS else _build_later(seed) if seed < GRAPH_SEEDS else _build_graph(seed)
 
 
 @functools.lru_cache(maxsize=None)
@@ -1022,6 +1143,18 @@ def _later_text(op, kw, other, emitted):
     return 'skeleton(%s).%s' % (g('lo', 'hi', 'mode', 'passes'), tail)
 
 
+def _graph_text(op, kw):
+    """the call of a step of the graph rules on its source, as text"""
+    if op == 'centreline_prune':
+        return 'centreline(%d, %d, %r, prune=%d, prune_rounds=%d)' % (kw['lo'], kw['hi'], kw['mode'], kw['prune'], kw['prune_rounds'])
+    made = 'skeleton(%d, %d, %r).graph()' % (kw['lo'], kw['hi'], kw['mode']) if kw['via'] == 'skeleton' else 'graph(%d, %d)' % (kw['lo'], kw['hi'])
+    tail = {'graph_prune': lambda: 'prune(%r, %r, %r, %r)' % (kw['length'], kw['weights'], kw['debris'], kw['fill']), 'graph_classes': lambda: 'classes()',
+            'branches_keep_set': lambda: 'branches.keep_set(%s, %r)    # the graph destroyed first' % (_text(kw['ranks']), kw['fill']),
+            'nodes_label': lambda: 'nodes.label()    # the graph destroyed first', 'graph_info': lambda: 'info',
+            'graph_branches': lambda: 'branch_records(%r, %r)' % (kw['first'], kw['n']), 'graph_nodes': lambda: 'node_records()'}[op]()
+    return '%s.%s' % (made, tail)
+
+
 def describe(seed):
     """the chain as lines for a Python session: ``steps = chain(seed)`` gives the arrays the lines name by step and keyword"""
     steps = chain(seed)
@@ -1046,6 +1179,8 @@ def describe(seed):
             tail = {'within': 'within(%r, %r, %r)' % (kw.get('r2_lo'), kw.get('r2_hi'), kw.get('fill')), 'channel': 'channel(%r)' % kw.get('steps'),
                     'distance_info': 'info', 'distance_squared': 'squared(*%r)' % (kw.get('box'),)}[s['op']]
             call = '%s.%s' % (made, tail)
+        elif s['op'] in GRAPH:
+            call = '%s.%s' % (src, _graph_text(s['op'], kw))
         elif s['op'] in LATER:
             call = '%s.%s' % (src, _later_text(s['op'], kw, other, emitted))
             if s.get('forced') is not None:
